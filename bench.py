@@ -12,15 +12,17 @@ A STEP = one pass of the hot path over one batch: every rank encodes its F resid
 8 GPUs; 34 GB of pixels, about 190 GB with streams, output and workspaces).  Frames are synthetic
 (`photo` class of qoi_amd/synth.py), generated on the device, distinct per frame and rank, and
 already resident in HBM when the timed region starts.  value = pixels round-tripped per
-second over all ranks.  After the timed region the round trip is verified bit-exact on the whole
+second over all ranks.  A plain run sets up, warms up, times the steps and prints the line;
+--dump-outputs DIR also writes a fixed sample of what the last step returned (dump_outputs).
+With --full, after the timed region the round trip is verified bit-exact on the whole
 batch and four of its streams are checked against the REFERENCE codec (byte-identical to its
-encoder's, decoded by its decoder to the source pixels).
+encoder's, decoded by its decoder to the source pixels), and the extra objects below are measured.
 
 --scaling weak (default): F frames per GPU whatever N is.  --scaling strong: the 8192 frames of
 configs[4] in total, 8192/N per GPU, processed as passes over at most F resident frames.
 `--gpus N` without a torch.distributed.run environment starts the N ranks itself.
 
-Extra objects on the JSON line (rank 0, N = 1 unless noted):
+Extra objects on the JSON line with --full (rank 0, N = 1 unless noted; roofline* come from the timed steps and are in every line):
   roofline             enc_sets, the kernel the north star's 50 % target is stated on: algorithmic bytes
                        (4 B read per pixel) / its mean launch duration measured with HIP
                        events on the launch stream during the timed steps, against the 8 TB/s HBM peak
@@ -234,6 +236,41 @@ def hash_check_against_reference(torch, ctx, pixels, pstride, streams, sstride, 
     bad = [f for f, hw in zip(frames, want) if int(mine[f]) != hw]
     return {"checker": kind, "frames_hashed_on_device": F, "frames_checked_against_reference": len(frames), "mismatches": bad[:8],
             "all_equal": not bad, "device_hashes": mine}
+
+
+DUMP_SEED = 20261016          # fixes which frames and which bytes --dump-outputs samples
+
+
+def dump_sample(n, lengths, npx, n_frames=8, n_stream_bytes=1 << 18, n_pixel_bytes=1 << 19):
+    """The sample --dump-outputs takes of a batch of n images whose streams are `lengths` bytes long: the images (S of them), per image
+    K positions in its stream (fixed fractions of its length; the first and the last byte included), and P byte offsets into the
+    decoded pixels (the same for every image).  Fixed by DUMP_SEED."""
+    rng = np.random.default_rng(DUMP_SEED)
+    frames = np.sort(rng.choice(n, size=min(n_frames, n), replace=False))
+    lengths = np.asarray(lengths, dtype=np.int64)
+    frac = np.concatenate([[0.0], np.sort(rng.random(n_stream_bytes - 2)), [1.0]])
+    pos = np.minimum((frac[None, :] * lengths[frames, None]).astype(np.int64), np.maximum(lengths[frames, None] - 1, 0))
+    offs = np.sort(rng.integers(0, npx * 4, size=n_pixel_bytes))
+    return frames, pos, offs
+
+
+def dump_outputs(torch, out_dir, streams, sstride, lens, decoded, pstride, n, npx, with_decode) -> None:
+    """What the step that ran last handed its caller, as .npy files under out_dir (about 24 MB in all; the sample: dump_sample):
+    stream_lengths  float64[n]      the byte count qoimi_encode_batch wrote for every image of the batch
+    sample_frames   float64[S]      the images sampled
+    streams_sample  float32[S, K]   bytes of their streams at K positions
+    decoded_sample  float32[S, P]   bytes of their decoded pixels at P offsets (absent with --encode-only)"""
+    os.makedirs(out_dir, exist_ok=True)
+    lengths = lens[:n].cpu().numpy().astype(np.int64)
+    frames, pos, offs = dump_sample(n, lengths, npx)
+    idx = torch.from_numpy(frames[:, None] * sstride + pos).to(streams.device)
+    files = {"stream_lengths": lengths.astype(np.float64), "sample_frames": frames.astype(np.float64),
+             "streams_sample": streams[idx].cpu().numpy().astype(np.float32)}
+    if with_decode:
+        idx = torch.from_numpy(frames[:, None] * pstride + offs[None, :]).to(decoded.device)
+        files["decoded_sample"] = decoded[idx].cpu().numpy().astype(np.float32)
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def equal_batches(torch, a, b, F, stride, nbytes) -> bool:
@@ -469,8 +506,13 @@ def main() -> None:
         return
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: bit-exact and reference checks of the batch, the side legs (single frame, drop-in, other content, "
+                         "3 channels, configs[2] / [3], mixed directory, alternating classes) and the CPU baselines; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of what the last step returned (stream lengths, stream and decoded bytes) as DIR/<name>.npy")
     ap.add_argument("--frames", type=int, default=1024, help="4K frames resident per GPU (= per step when scaling is weak); 1024 = one GPU's shard of BASELINE configs[4]")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="strong: 8192 frames in total (configs[4]), 8192/N per GPU in passes over <= --frames resident frames")
     ap.add_argument("--total-frames", type=int, default=8192, help="frames of the whole job under --scaling strong")
@@ -488,6 +530,8 @@ def main() -> None:
                          "gloo: counters as CPU tensors, ranks may share a GPU (rank r uses device r mod device count) - how the "
                          "multi-rank path is exercised on a one-GPU box (tests/test_bench_ranks.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -538,8 +582,9 @@ def main() -> None:
     ctx.encode_status(stream)
     sizes = [int(x) for x in lens[:F].cpu().numpy()]
     descs = [desc] * F
-    hash_first = torch.zeros(F, dtype=torch.int64, device=dev)        # every stream of the first encode, hashed on the device
-    ctx.hash_streams(streams.data_ptr(), sstride, lens.data_ptr(), F, hash_first.data_ptr(), stream)
+    if args.full:
+        hash_first = torch.zeros(F, dtype=torch.int64, device=dev)    # every stream of the first encode, hashed on the device
+        ctx.hash_streams(streams.data_ptr(), sstride, lens.data_ptr(), F, hash_first.data_ptr(), stream)
 
     # Strong scaling with more frames per rank than fit at once: every pass codes DIFFERENT frames - the resident buffer is refilled
     # with the pass's frame ids (synthetic frames are made on the device) and the stream lengths are read back after the encode,
@@ -575,6 +620,7 @@ def main() -> None:
 
     for _ in range(args.warmup):
         step()
+    # per-kernel HIP events in every run, plain or --full: kernel_ms_per_step and roofline* come from these steps
     ctx.set_profiling(True)
     synth_events.clear(); bytes_coded[0] = 0.0
     barrier()
@@ -590,12 +636,19 @@ def main() -> None:
     ctx.encode_status(stream)
     ws_main = ctx.workspace_bytes()                 # what the headline batch needed (the side legs below may grow the arenas further)
     launches = args.steps * passes
-
-    # bit-exact round trip (qoibench.c:408-417) on the whole batch, and four of its streams against the reference codec
-    ok = args.encode_only or equal_batches(torch, decoded[:n_last * pstride], pixels[:n_last * pstride], n_last, pstride, npx * 4)
     dstats = ctx.decode_stats()
+
+    # what the last step handed its caller, before anything below reuses the buffers (rank 0's frames)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, streams, sstride, lens, decoded, pstride, n_last, npx, not args.encode_only)
+
+    # Everything from here to the counters is --full only: a plain run reports the timed steps and nothing else.
+    # bit-exact round trip (qoibench.c:408-417) on the whole batch, and four of its streams against the reference codec
+    ok = True
+    if args.full:
+        ok = args.encode_only or equal_batches(torch, decoded[:n_last * pstride], pixels[:n_last * pstride], n_last, pstride, npx * 4)
     refcheck = None
-    if rank == 0 and not args.encode_only:
+    if args.full and rank == 0 and not args.encode_only:
         refcheck = check_against_reference(torch, pixels, pstride, streams, sstride, sizes, w, h, sorted({0, min(1, n_last - 1), n_last // 2, n_last - 1}))
         ok = ok and refcheck["streams_byte_identical"] and refcheck["reference_decoder_round_trips"]
         # ... and byte identity as a property of the whole batch: every stream the LAST timed step wrote is hashed on the device; 64
@@ -619,7 +672,7 @@ def main() -> None:
     # The same decode through a record arena of 24 GiB (qoimi_set_decode_record_cap: sub-batches of whole images): what the context then
     # holds and what that costs - a report beside the headline, on its buffers, before the side legs overwrite them.
     capped = None
-    if not args.encode_only and world == 1 and rank == 0 and not args.no_others and not regen and F >= 64:
+    if args.full and not args.encode_only and world == 1 and rank == 0 and not args.no_others and not regen and F >= 64:
         try:
             _, total_b0 = torch.cuda.mem_get_info(dev)
             ctx.set_decode_record_cap(24 << 30, True)
@@ -639,7 +692,7 @@ def main() -> None:
     # BASELINE configs[1]: ONE 4K frame, encode + decode, device-resident (33 MB: served by the 256 MiB Infinity
     # Cache on repeat runs and bound by launch latency, not by HBM - reported next to the batch figure, never as it)
     single = None
-    if not args.encode_only and not args.no_single and rank == 0:
+    if args.full and not args.encode_only and not args.no_single and rank == 0:
         one = (ctypes.c_int * 1)(sizes[0])                 # the C caller's arguments as C arrays (int sizes[1], qoi_desc descs[1]): no per-call list conversion in the binding
         one_desc = (api.QoiDesc * 1)(desc)
         enc1 = lambda: ctx.encode_batch(pixels.data_ptr(), pstride, desc, 1, streams.data_ptr(), sstride, lens.data_ptr(), stream)
@@ -676,13 +729,13 @@ def main() -> None:
     # The reference's own entry points (qoi.h:278/289) on HOST pointers: pixels and stream cross PCIe in both directions inside the
     # call.  Reported beside the copies alone (the same bytes, the same pageable buffers, torch copy_), never as `value`.
     dropin = None
-    if not args.encode_only and not args.no_single and rank == 0 and world == 1:
+    if args.full and not args.encode_only and not args.no_single and rank == 0 and world == 1:
         dropin = dropin_path(torch, api, ctx, pixels, w, h, dev)
 
     # next to the headline content always report `noise` (5 B/px written: most stream traffic) and
     # `constant` (longest runs) - same batch, 3 timed steps each, rank 0 of a single-GPU run only
     other = None
-    if world == 1 and not args.encode_only and not args.no_others:
+    if args.full and world == 1 and not args.encode_only and not args.no_others:
         other = {}
         for kind in ("noise", "constant", "uiflat", "photo_hard", "sprite_alpha", "photo"):
             if kind == args.kind:
@@ -724,7 +777,7 @@ def main() -> None:
 
     # the same photographs as 3-channel input and output (qoi.h:406-413, 580-586: channels = 3), a quarter of the batch
     rgb = None
-    if world == 1 and rank == 0 and not args.encode_only and not args.no_others:
+    if args.full and world == 1 and rank == 0 and not args.encode_only and not args.no_others:
         F3 = max(1, min(F, 256))
         ps3 = (npx * 3 + 255) // 256 * 256
         d3 = api.QoiDesc(w, h, 3, api.QOI_SRGB)
@@ -757,7 +810,7 @@ def main() -> None:
     # BASELINE configs[2]: 1024 x 1920x1080 RGBA, encode only (the HBM-bound roofline run) and configs[3]: one 16384 x 16384
     # image, encode + decode - in the buffers of the main batch where they fit
     cfg2 = cfg3 = None
-    if world == 1 and rank == 0 and not args.no_configs and not args.encode_only:
+    if args.full and world == 1 and rank == 0 and not args.no_configs and not args.encode_only:
         w2, h2, F2 = 1920, 1080, 1024
         n2 = w2 * h2
         ps2, ss2 = (n2 * 4 + 255) // 256 * 256, (api.encode_bound(w2, h2, 4) + 255) // 256 * 256
@@ -815,7 +868,7 @@ def main() -> None:
     # What the reference's own harness walks (qoibench.c:491-555): a DIRECTORY of images of different shapes and contents, here one
     # qoimi_encode_images + one qoimi_decode_batch over 288 images of 64 shapes, the six content classes interleaved.
     mixed = None
-    if world == 1 and rank == 0 and not args.no_others and not args.encode_only:
+    if args.full and world == 1 and rank == 0 and not args.no_others and not args.encode_only:
         try:
             mixed = mixed_directory_leg(torch, api, synth, ctx, pixels, streams, decoded, lens, stream, timed)
         except Exception as e:                                                  # a report, not a gate
@@ -823,7 +876,7 @@ def main() -> None:
     # ... and batches of different content in rotation on ONE context, nothing primed: what the call-to-call heuristics (set size by the
     # previous batch's bytes per pixel, pass selection by the previous batch's flagged images) cost a workload that alternates
     alternating = None
-    if world == 1 and rank == 0 and not args.no_others and not args.encode_only and F >= 384 and (w, h) == (3840, 2160):
+    if args.full and world == 1 and rank == 0 and not args.no_others and not args.encode_only and F >= 384 and (w, h) == (3840, 2160):
         try:
             alternating = alternating_leg(torch, api, synth, ctx, pixels, streams, decoded, lens, stream, timed, w, h, pstride, sstride, desc)
         except Exception as e:
@@ -887,10 +940,10 @@ def main() -> None:
                                     if not strong else
                                     f"BASELINE configs[4] strong scaling: {args.total_frames} x {w}x{h} RGBA frames in total, {args.total_frames // world} per GPU per step "
                                     f"in {passes} pass(es) over {F} resident frames") +
-                                   f", encode + decode, content={args.kind}, HBM-resident, bit-exact round trip verified",
+                                   f", encode + decode, content={args.kind}, HBM-resident" + (", bit-exact round trip verified" if args.full else ""),
                        "frames_per_gpu": len(my_frames), "frames_resident": F, "passes_per_step": passes, "width": w, "height": h, "content": args.kind,
                        "stream_bytes_per_px": round(total_stream_bytes / total_px, 4), "parallelism": f"frames sharded x{world}"},
-            "verified_bit_exact": n_ok == world, "reference_check": refcheck,
+            "verified_bit_exact": n_ok == world if args.full else None, "reference_check": refcheck,
             "distinct_frames_per_step": "every pass refills the resident buffer with its own frame ids (refill and stream-length read-back inside the timed region)" if regen
                                         else "the resident frames (one pass per step)",
             "counter_backend": args.counter_backend, "frames_coded_all_ranks": int(frames_coded), "frame_id_sum_all_ranks": int(frame_id_sum),
@@ -972,7 +1025,7 @@ def main() -> None:
     if rank == 0:
         # The reference CPU path beside the GPU figure, for EVERY world size: rank 0 times it after the final barrier (the other
         # ranks are through; the GPUs are idle), so the line the driver parses at N = 2, 4, 8 carries the same objects as at N = 1.
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.kind, w, h, args.cpu_seconds)
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args.kind, w, h, min(args.cpu_seconds, 6.0))
         print(json.dumps(out), flush=True)

@@ -4,6 +4,14 @@ import sys
 import numpy as np
 import pytest
 
+# torch before any test loads libqoi_mi355x*.so: the library then binds to the HIP runtime torch already loaded.  Loaded first, it
+# pulls in the system's runtime and torch its own beside it, and on a GPU box the runtime that comes second sees no device - a
+# whole-suite run (test_abi.py loads the library early) would fail every GPU test after it.
+try:
+    import torch  # noqa: F401
+except ImportError:
+    pass
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:

@@ -10,7 +10,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "2", "--warmup", "1", "--width", "1920", "--height", "1080", "--no-others", "--no-single", "--no-configs"]
+COMMON = ["--full", "--steps", "2", "--warmup", "1", "--width", "1920", "--height", "1080", "--no-others", "--no-single", "--no-configs"]
 
 
 def run_bench(extra):

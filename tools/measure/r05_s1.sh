@@ -7,7 +7,7 @@ OUT=gpurun_out/r05_s1
 mkdir -p "$OUT"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
 echo "== pytest -m gpu"; timeout 1500 python -m pytest tests -m gpu -q -x --timeout 900 > "$OUT/pytest.log" 2>&1; echo "rc=$?" >> "$OUT/pytest.log"; tail -4 "$OUT/pytest.log"
-echo "== bench"; timeout 900 python bench.py > "$OUT/bench.log" 2>&1; echo "rc=$?" >> "$OUT/bench.log"; tail -c 600 "$OUT/bench.log"
+echo "== bench"; timeout 900 python bench.py --full > "$OUT/bench.log" 2>&1; echo "rc=$?" >> "$OUT/bench.log"; tail -c 600 "$OUT/bench.log"
 echo "== set size on the new classes (128 frames)"
 for K in photo_hard sprite_alpha; do for R in 1 2 3; do
   KIND=$K QOIMI_ENC_SET_SLABS=$R timeout 200 python tools/measure/enc_time.py - 128 2>&1 | tail -1 | sed "s/^/$K R=$R /"

@@ -6,7 +6,7 @@ OUT=gpurun_out/r05_s28
 mkdir -p "$OUT"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1 HSA_ENABLE_COREDUMP=0
 ulimit -c 0
-timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu --no-single --no-configs > "$OUT/bench.log" 2>&1; echo "rc=$?" >> "$OUT/bench.log"
+timeout 900 python bench.py --full --steps 2 --warmup 1 --no-cpu --no-single --no-configs > "$OUT/bench.log" 2>&1; echo "rc=$?" >> "$OUT/bench.log"
 python - "$OUT/bench.log" <<'PY' | tee "$OUT/others.txt"
 import json, sys
 line = [l for l in open(sys.argv[1]).read().splitlines() if l.lstrip().startswith('{"metric"')][0]

@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1 HSA_ENABLE_COREDUMP=0
 ulimit -c 0
 for A in 1 0; do
-QOIMI_ENC_ALL_G2=$A timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu --no-single --no-configs > "$OUT/bench_$A.log" 2>&1; echo "rc=$?" >> "$OUT/bench_$A.log"
+QOIMI_ENC_ALL_G2=$A timeout 900 python bench.py --full --steps 2 --warmup 1 --no-cpu --no-single --no-configs > "$OUT/bench_$A.log" 2>&1; echo "rc=$?" >> "$OUT/bench_$A.log"
 python - "$OUT/bench_$A.log" $A <<'PY' | tee -a "$OUT/others.txt"
 import json, sys
 line = [l for l in open(sys.argv[1]).read().splitlines() if l.lstrip().startswith('{"metric"')][0]

@@ -19,7 +19,7 @@ timeout 300 python tools/measure/overlap_probe.py 512 2 2>&1 | tail -1 | tee "$O
 timeout 300 python tools/measure/overlap_probe.py 512 4 2>&1 | tail -1 | tee -a "$OUT/overlap.txt"
 echo "== drop-in with the reference's worst-case buffer"
 for W in 0 1; do
-  QOIMI_ENCODE_WORST_CASE_BUFFER=$W timeout 300 python bench.py --frames 8 --steps 2 --warmup 1 --no-cpu --no-others --no-configs 2>/dev/null | tail -1 | \
+  QOIMI_ENCODE_WORST_CASE_BUFFER=$W timeout 300 python bench.py --full --frames 8 --steps 2 --warmup 1 --no-cpu --no-others --no-configs 2>/dev/null | tail -1 | \
     python -c "import json,sys; d=json.loads(sys.stdin.read()); print('worst_case=$W', json.dumps(d['dropin_host_pointers']))" | tee -a "$OUT/dropin_worst_case.txt"
 done
 echo "== done"

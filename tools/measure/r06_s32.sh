@@ -12,7 +12,7 @@ done | cut -c1-1300 | tee "$OUT/mixed_by_seg.txt"
 for K in photo sprite_alpha photo_hard noise uiflat; do for F in 8 32 128 256; do
   KIND=$K timeout 200 python tools/measure/dec_time.py - $F 2>&1 | tail -1 | sed -E "s/^.*'decode_total'/total/" | sed "s/^/$K F=$F /"
 done; done | tee "$OUT/batch_auto.txt"
-timeout 900 python bench.py --no-cpu > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -c 600 "$OUT/bench.err"
+timeout 900 python bench.py --full --no-cpu > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -c 600 "$OUT/bench.err"
 python - <<'PY' | tee "$OUT/bench_brief.txt"
 import json
 d = json.loads(open("gpurun_out/r06_s32/bench.json").read().strip().splitlines()[-1])
