@@ -175,6 +175,52 @@ int qoimi_decode_batch(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
                        const int *sizes, const qoi_desc *descs, int n_images, int channels,
                        void *d_pixels, size_t pixel_stride, void *stream);
 
+/* The same for streams and images wherever the caller put them - the decoder's counterpart of qoimi_encode_images:
+ *   stream_offsets HOST size_t[n_images]: stream i is sizes[i] bytes at d_streams + stream_offsets[i]
+ *   pixel_offsets  HOST size_t[n_images]: image i is written tightly packed (w*h*out_channels bytes) at d_pixels + pixel_offsets[i]
+ *   sizes, descs, channels: as above; the images may differ in shape and share the output channel count
+ * ANY byte offsets, in any order, with gaps or none: streams back to back as qoimi_pack_streams leaves them (align 1 included), images
+ * back to back, image 5 in front of image 0.  Exactly w*h*out_channels bytes are written per image and not one byte beside them.  Input
+ * ranges may overlap or coincide (one stream decoded twice); OUTPUT ranges must not overlap: QOIMI_E_ARG.  Everything the host can see -
+ * sizes[i] < 22, a rejected descriptor, channels, mixed output channel counts, overlapping outputs - is rejected before anything is
+ * launched; the caller's buffers are then untouched.  Same rules, same leniency, same synchronous return, same bit-exactness for EVERY
+ * input stream as qoimi_decode_batch, which is a caller of the same path (offsets i*stride).
+ * Speed: the call is laid out by ascending stream offset internally, so a pack read in any order decodes like a sorted one; a call whose
+ * pixel offsets do not ascend with its stream offsets is still exact, but images that lie in front of their neighbours are written with
+ * plain stores (slower); so is a stream that ENDS behind the end of the stream that follows it (it takes the full parse, counted in
+ * qoimi_decode_stats [3]). */
+int qoimi_decode_images(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets, const int *sizes,
+                        const qoi_desc *descs, int n_images, int channels,
+                        void *d_pixels, const size_t *pixel_offsets, void *stream);
+
+/* Streams back to back, on the device: stream i (d_stream_len[i] bytes at d_streams + i*stream_stride - what qoimi_encode_batch and
+ * qoimi_hash_streams take; after qoimi_encode_images a caller that used stream_offsets[i] = i*stride can use it as well) is copied to
+ * d_packed + d_packed_off[i].
+ *   d_packed_off   DEVICE unsigned long long[n_streams + 1], written by the call: the exclusive scan of the lengths, every start rounded up
+ *                  to `align`; d_packed_off[n_streams] is the END of the last stream (not rounded) = the bytes the pack needs
+ *   align          a power of two, 1..256 (1: back to back).  Gap bytes between aligned streams are not written.
+ *   packed_capacity bytes at d_packed.  A stream that does not fit WHOLLY below it is not copied, not in part; d_packed_off is complete
+ *                  in any case, so d_packed_off[n_streams] > packed_capacity says what happened and how much to allocate.  Nothing at or
+ *                  behind d_packed + packed_capacity is ever written.  packed_capacity 0 (d_packed may then be NULL): offsets only.
+ * Asynchronous on `stream`: no host synchronisation, no read-back - lengths are read and offsets written on the device, so the call can
+ * be enqueued straight behind qoimi_encode_batch.  Source [d_streams, + n_streams*stream_stride) and destination [d_packed, +
+ * packed_capacity) must not overlap (QOIMI_E_ARG).  stream_stride may be any value (odd too), source and destination any alignment.
+ * A length outside [0, stream_stride] is the caller's error; it is clamped to that range, so nothing outside the source range is read -
+ * but for the aligned 4-byte words that hold a stream's first and last byte. */
+int qoimi_pack_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stride, const int *d_stream_len, int n_streams,
+                       unsigned align, void *d_packed, size_t packed_capacity,
+                       unsigned long long *d_packed_off /* device, n_streams + 1 */, void *stream);
+
+/* What makes a pack self-describing: the header of every stream, read on the device and parsed by the rules of qoi.h:497-521.
+ *   stream_offsets, sizes  HOST arrays as for qoimi_decode_images
+ *   descs_out      HOST qoi_desc[n_streams]: filled for every stream of 22 bytes or more, valid or not (as qoi_decode fills *desc before
+ *                  it validates; a shorter stream leaves its entry untouched, as qoi_decode returns before it touches *desc)
+ *   first_bad      HOST, may be NULL: the lowest index that fails, -1 if none
+ * QOIMI_OK if every stream passes (size >= 22, magic, non-zero width / height, channels 3 / 4, colorspace <= 1, the pixel cap), else
+ * QOIMI_E_ARG.  Synchronous.  With it (d_packed, offsets, sizes) is all a caller has to keep: read_descs -> allocate -> decode_images. */
+int qoimi_read_descs(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets, const int *sizes, int n_streams,
+                     qoi_desc *descs_out /* host */, int *first_bad /* host, may be NULL */, void *stream);
+
 /* Fill device memory with synthetic RGBA frames frame_id = first_frame .. first_frame+n-1
  * (benchmark/test utility; same function of (kind, seed, frame, pixel) as synth.py). */
 int qoimi_synth_frames(qoimi_ctx *ctx, int kind, unsigned seed, unsigned first_frame,

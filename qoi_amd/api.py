@@ -36,6 +36,7 @@ EXPORTS = (
     "qoimi_encode_batch", "qoimi_encode_status", "qoimi_decode_batch", "qoimi_synth_frames",
     "qoimi_decode_stats", "qoimi_version", "qoimi_set_profiling", "qoimi_get_profile", "qoimi_kernel_name",
     "qoimi_encode_suspect_calls", "qoimi_encode_retries", "qoimi_set_encode_small_call_order", "qoimi_workspace_bytes", "qoimi_set_decode_record_cap", "qoimi_hash_streams", "qoimi_encode_images",
+    "qoimi_decode_images", "qoimi_pack_streams", "qoimi_read_descs",
 )
 
 
@@ -113,6 +114,12 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_encode_images.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(QoiDesc), ci, vp, ctypes.POINTER(sz), vp, vp]
     lib.qoimi_hash_streams.restype = ci
     lib.qoimi_hash_streams.argtypes = [vp, vp, sz, vp, ci, vp, vp]
+    lib.qoimi_decode_images.restype = ci
+    lib.qoimi_decode_images.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ctypes.POINTER(QoiDesc), ci, ci, vp, ctypes.POINTER(sz), vp]
+    lib.qoimi_pack_streams.restype = ci
+    lib.qoimi_pack_streams.argtypes = [vp, vp, sz, vp, ci, ctypes.c_uint, vp, sz, vp, vp]
+    lib.qoimi_read_descs.restype = ci
+    lib.qoimi_read_descs.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ctypes.POINTER(QoiDesc), ctypes.POINTER(ci), vp]
     _lib = lib
     return lib
 
@@ -273,6 +280,37 @@ class Context:
             c_descs = (QoiDesc * n)(*descs)
         self._check(self._lib.qoimi_decode_batch(self._h, d_streams, stream_stride, c_sizes, c_descs, n, channels,
                                                  d_pixels, pixel_stride, stream), "qoimi_decode_batch")
+
+    def decode_images(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc],
+                      channels: int, d_pixels: int, pixel_offsets: Sequence[int], stream: int = 0) -> None:
+        """Streams and images at per-image byte offsets, any order (``qoimi_decode_images``): image i is written tightly packed."""
+        n = len(sizes)
+        if len(descs) != n or len(stream_offsets) != n or len(pixel_offsets) != n:
+            raise QoiError("decode_images: one stream offset, size, descriptor and pixel offset per image")
+        so = (ctypes.c_size_t * n)(*[int(x) for x in stream_offsets])
+        po = (ctypes.c_size_t * n)(*[int(x) for x in pixel_offsets])
+        self._check(self._lib.qoimi_decode_images(self._h, d_streams, so, (ctypes.c_int * n)(*[int(x) for x in sizes]), (QoiDesc * n)(*descs),
+                                                  n, channels, d_pixels, po, stream), "qoimi_decode_images")
+
+    def pack_streams(self, d_streams: int, stream_stride: int, d_stream_len: int, n_streams: int, align: int,
+                     d_packed: int, packed_capacity: int, d_packed_off: int, stream: int = 0) -> None:
+        """Strided streams -> back to back at d_packed; d_packed_off: device uint64[n_streams + 1] (``qoimi_pack_streams``, asynchronous)."""
+        self._check(self._lib.qoimi_pack_streams(self._h, d_streams, stream_stride, d_stream_len, n_streams, align,
+                                                 d_packed, packed_capacity, d_packed_off, stream), "qoimi_pack_streams")
+
+    def read_descs(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], stream: int = 0):
+        """The headers of the streams of a pack: (descs, first_bad) - first_bad is None when every stream passes the rules of
+        qoi.h:497-521, else the lowest failing index (``qoimi_read_descs`` then returns QOIMI_E_ARG; the descriptors are filled anyway)."""
+        n = len(sizes)
+        if len(stream_offsets) != n:
+            raise QoiError("read_descs: one stream offset per size")
+        so = (ctypes.c_size_t * n)(*[int(x) for x in stream_offsets])
+        descs = (QoiDesc * n)()
+        bad = ctypes.c_int(-1)
+        rc = self._lib.qoimi_read_descs(self._h, d_streams, so, (ctypes.c_int * n)(*[int(x) for x in sizes]), n, descs, ctypes.byref(bad), stream)
+        if rc != 0 and bad.value < 0:
+            self._check(rc, "qoimi_read_descs")
+        return list(descs), (bad.value if bad.value >= 0 else None)
 
     def synth_frames(self, kind: int, seed: int, first_frame: int, n_frames: int, width: int, height: int,
                      d_pixels: int, pixel_stride: int, stream: int = 0) -> None:

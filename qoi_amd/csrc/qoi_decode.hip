@@ -2414,7 +2414,8 @@ __global__ __launch_bounds__(64) void dec_summarize_rec(DecParams p) {
 // data-dependent loops (LaneWriter::drain) the compiler has to wait with vmcnt(0): profiles/r02 - 75 % of the wavefront
 // cycles of the first dec_segments_rec were spent there, waiting for store acknowledgements.
 // Group stores go through a descriptor based at the image of the wavefront's first segment (32-bit offsets); a lane whose
-// image lies 2 GiB or more behind that base (never with sane strides) uses plain stores on a rare path.
+// image lies 2 GiB or more behind that base (never with sane strides) or in front of it (qoimi_decode_images: the caller's pixel offsets need not
+// ascend with the stream offsets) uses plain stores on a rare path.
 template <int OCH, uint32_t RING_ = 32, uint32_t GROUP_ = 16>
 struct BurstWriter : LaneWriter<OCH, RING_, GROUP_> {
     typedef LaneWriter<OCH, RING_, GROUP_> Base;
@@ -2427,7 +2428,7 @@ struct BurstWriter : LaneWriter<OCH, RING_, GROUP_> {
         Base::init(row_addr, image, px_pos);
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)wave_base, 0, (int)kRange, 0x00020000);
         const unsigned long long d = (unsigned long long)(image - wave_base);
-        boff = d + image_bytes < (unsigned long long)kRange ? (uint32_t)d : kFar;
+        boff = (image >= wave_base && d + image_bytes < (unsigned long long)kRange) ? (uint32_t)d : kFar;      // (an image BELOW the base: the plain stores too)
     }
     __device__ __forceinline__ void drain_block() {
         // head of a segment / after a long run: up to the next group boundary pixel by pixel (LaneWriter::drain's first loop)
@@ -2582,7 +2583,7 @@ __global__ __launch_bounds__(64) void dec_segments_rec(DecParams p) {
     {   // descriptor base: the image of the wavefront's first segment (its lanes' images follow it in memory)
         const uint32_t q0 = blockIdx.x * 64u;
         const uint32_t img0 = find_image(p.images, p.n_images, q0 < p.total_segs ? q0 : 0u);
-        W.init(lds_addr_of(&s_out[lane]), p.pixels + (size_t)p.images[img0].out_index * p.pixel_stride, p.pixels + (size_t)im.out_index * p.pixel_stride,
+        W.init(lds_addr_of(&s_out[lane]), p.pixels + p.images[img0].pixel_off, p.pixels + im.pixel_off,
                im.npx * (uint32_t)OCH, px_first);
     }
     LdsTab32 tab{&s_tab[lane]};
@@ -2807,7 +2808,7 @@ __global__ __launch_bounds__(256) void dec_expand_runs(DecParams p) {
         const uint32_t n = p.run_cnt[q];
         const uint4* __restrict__ dsc = desc_base != kNoRunDesc ? p.run_desc + (size_t)(desc_base + (q - seg_base)) * p.desc_cap
                                                                  : reinterpret_cast<const uint4*>(p.summary + (size_t)q * 65u);
-        uint8_t* __restrict__ out = p.pixels + (size_t)p.images[img].out_index * p.pixel_stride;
+        uint8_t* __restrict__ out = p.pixels + p.images[img].pixel_off;
         auto get_desc = [&](uint32_t at) {                   // (two 8-byte halves: see dec_segments_rec)
             const uint2* d = reinterpret_cast<const uint2*>(dsc + at);
             const uint2 a = d[0], b = d[1];
@@ -2868,7 +2869,7 @@ __global__ __launch_bounds__(64) void dec_sequential(DecParams p) {
     uint32_t px = p.entry[q0 * 65u + 64u];
     __builtin_amdgcn_wave_barrier();
     if (lane != 0u) return;
-    uint8_t* out = p.pixels + (size_t)im.out_index * p.pixel_stride;
+    uint8_t* out = p.pixels + im.pixel_off;
     uint32_t pos = p.px_off[q0], stash = 0u;
     const uint32_t limit = im.npx;
     for (uint32_t j = im.start_seg; j < im.n_active && pos < limit; ++j) {
@@ -2954,7 +2955,7 @@ __global__ __launch_bounds__(256) void dec_fill(DecParams p) {
     if (blockIdx.x == 0u && threadIdx.x == 64u && !p.tail_fused) *p.run_queue_n = 0u;        // the round's run descriptors are written out (dec_expand_runs ran before this launch)
     if (im.total_px >= im.npx) return;
     const uint32_t px = im.n_active ? im.final_px : kInitPx;
-    uint8_t* out = p.pixels + (size_t)im.out_index * p.pixel_stride;
+    uint8_t* out = p.pixels + im.pixel_off;
     for (uint32_t i = im.total_px + slice * 256u + threadIdx.x; i < im.npx; i += kFillSlices * 256u) {
         if (OCH == 4) reinterpret_cast<uint32_t*>(out)[i] = px;
         else { uint8_t* d = out + (size_t)i * 3u; d[0] = (uint8_t)px; d[1] = (uint8_t)(px >> 8); d[2] = (uint8_t)(px >> 16); }

@@ -15,6 +15,8 @@
 
 #include <condition_variable>
 #include <mutex>
+#include <algorithm>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -27,6 +29,7 @@
 #pragma GCC visibility pop
 #include "qoi_decode_core.h"
 #include "qoi_kernels.h"
+#include "qoi_pack.hip"        // the pack kernels and their launchers: part of this translation unit (no build lists the file itself)
 
 using namespace qoimi;
 
@@ -93,6 +96,7 @@ struct Carver {   // hands out 256-byte aligned pieces of an arena
 
 struct qoimi_ctx {
     int device = 0;
+    int n_cus = 256;            // compute units of the device (the grid of the pack's copy)
     Arena enc_ws, dec_ws;       // kernel workspaces
     Arena dec_scan;             // look-back words of dec_scan_entry (calls of a few images): tagged with dec_epoch, zeroed when allocated / when the tag wraps
     uint32_t dec_epoch = 0;     // number of the last such call (16 bits are compared)
@@ -205,6 +209,7 @@ extern "C" int qoimi_ctx_create(int device, qoimi_ctx** out) {
         return fail(QOIMI_E_NO_GPU, std::string("kernels are built for gfx950 only, device is ") + prop.gcnArchName);
     qoimi_ctx* c = new qoimi_ctx();
     c->device = device;
+    if (prop.multiProcessorCount > 0) c->n_cus = prop.multiProcessorCount;
     {   // record arena of a decode call: up to a sixth of the device's memory (48 GiB on a 288 GB MI355X: the 1024-frame shard of
         // BASELINE configs[4] in one piece, 45.1 GB of workspace = 4.3 x its stream bytes at 36.4 ms), never less than 1 GiB.  A caller
         // short of device memory caps it (QOIMI_DEC_REC_CAP_MB): 24 GiB = two sub-batches, 27.4 GB = 2.6 x the stream bytes at 36.8 ms
@@ -335,7 +340,7 @@ extern "C" int qoimi_get_profile(qoimi_ctx* c, void* stream, double* ms, long lo
 extern "C" const char* qoimi_kernel_name(int i) {
     static const char* names[kT_count] = {"", "enc_slab_summary", "enc_scan_groups", "enc_scan_images", "enc_slabs", "enc_slabs_generic", "enc_offsets", "enc_compact",
         "dec_parse", "dec_chain_parse", "dec_transcode", "dec_chain_slots", "dec_summarize", "dec_chain_state",
-        "dec_segments", "dec_prepare_restart", "dec_fill", "dec_expand_runs", "encode_total", "decode_total"};
+        "dec_segments", "dec_prepare_restart", "dec_fill", "dec_expand_runs", "pack_offsets", "pack_copy", "encode_total", "decode_total"};
     return (i >= 0 && i < kT_count) ? names[i] : "";
 }
 
@@ -836,11 +841,11 @@ static uint32_t choose_seg_bytes(const qoimi_ctx* c, const int* sizes, const qoi
 }
 
 // one sub-batch: everything of qoimi_decode_batch for images whose record arena fits dec_rec_cap
-static int decode_some(qoimi_ctx* c, const void* d_streams, size_t stream_stride,
+static int decode_some(qoimi_ctx* c, const void* d_streams, const size_t* stream_offs, size_t stream_limit,
                        const int* sizes, const qoi_desc* descs, int n_images, int channels,
-                       void* d_pixels, size_t pixel_stride, void* stream, uint32_t B, bool lone_image, long long stats[4], const int* place = nullptr) {
-    // place (a call decoded class by class): image i of this sub-call is the caller's image place[i] - its stream at place[i] * stream_stride,
-    // its pixels at place[i] * pixel_stride; sizes / descs are the sub-call's own arrays
+                       void* d_pixels, const size_t* pixel_offs, size_t pixel_limit, void* stream, uint32_t B, long long stats[4]) {
+    // image i of this sub-call: its stream at d_streams + stream_offs[i], its pixels at d_pixels + pixel_offs[i]; stream_limit / pixel_limit: the
+    // strides of qoimi_decode_batch, which no stream / image may exceed (qoimi_decode_images: no limit); all arrays are the sub-call's own
     int och = 0;
     std::vector<DecImage> imgs((size_t)n_images);
     uint64_t total = 0, total_g = 0, flat_total = 0;
@@ -864,12 +869,12 @@ static int decode_some(qoimi_ctx* c, const void* d_streams, size_t stream_stride
         if (och && o != och) return fail(QOIMI_E_ARG, "all images of a batch must share the output channel count");
         och = o;
         const size_t npx = (size_t)descs[i].width * descs[i].height;
-        if (npx * (size_t)o > pixel_stride) return fail(QOIMI_E_ARG, "pixel_stride smaller than a decoded image");
-        if ((size_t)sizes[i] > stream_stride && !lone_image) return fail(QOIMI_E_ARG, "stream longer than stream_stride");
+        if (npx * (size_t)o > pixel_limit) return fail(QOIMI_E_ARG, "pixel_stride smaller than a decoded image");
+        if ((size_t)sizes[i] > stream_limit) return fail(QOIMI_E_ARG, "stream longer than stream_stride");
         DecImage& im = imgs[(size_t)i];
         memset(&im, 0, sizeof im);
-        im.stream_off = (size_t)(place ? place[i] : i) * stream_stride;
-        im.out_index = (uint32_t)(place ? place[i] : i);
+        im.stream_off = stream_offs[i];
+        im.pixel_off = pixel_offs[i];
         im.chunks_end = (uint32_t)(sizes[i] - kTrailerBytes);
         im.npx = (uint32_t)npx;
         if (fused_layout) { total = (total + kScanSegs - 1u) / kScanSegs * kScanSegs; total_g = total / 64u; }
@@ -916,7 +921,7 @@ static int decode_some(qoimi_ctx* c, const void* d_streams, size_t stream_stride
         for (int i = 0; i < n_images && !any_flat; ++i) any_flat = sizes[i] > 22 && dec_image_is_flat((uint32_t)sizes[i] - 8u, descs[i].width * descs[i].height);
         p.first_inner = any_flat ? (uint32_t)c->dec_inner1 : 0u;
     }
-    p.pixels = (uint8_t*)d_pixels; p.pixel_stride = pixel_stride;
+    p.pixels = (uint8_t*)d_pixels;
     const size_t Q = total + 1;   // +1: check of segment q reads entry[q+1]
     {   // P1/P2 on 128-byte pieces when a segment is 1, 2, 4 ... 64 of them
         const uint32_t g = B / 128u;
@@ -1100,18 +1105,15 @@ static int decode_some(qoimi_ctx* c, const void* d_streams, size_t stream_stride
     return QOIMI_OK;
 }
 
-extern "C" int qoimi_decode_batch(qoimi_ctx* c, const void* d_streams, size_t stream_stride,
-                                  const int* sizes, const qoi_desc* descs, int n_images, int channels,
-                                  void* d_pixels, size_t pixel_stride, void* stream) {
-    if (!c || !d_streams || !sizes || !descs || !d_pixels || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
-    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
-    for (int i = 1; i < n_images && channels == 0; ++i)
-        if (descs[i].channels != descs[0].channels) return fail(QOIMI_E_ARG, "all images of a batch must share the output channel count");
+// Everything of a decode call behind its argument checks: images at per-image offsets (ascending stream offsets: see qoimi_decode_images).
+static int decode_offsets(qoimi_ctx* c, const void* d_streams, const size_t* stream_offs, size_t stream_limit,
+                          const int* sizes, const qoi_desc* descs, int n_images, int channels,
+                          void* d_pixels, const size_t* pixel_offs, size_t pixel_limit, void* stream) {
     // The chunk records take four bytes per stream byte (worst case) while a call is in flight.  Calls whose streams would
     // need more than dec_rec_cap are decoded as consecutive sub-batches of whole images through the same workspace.
     const uint64_t cap_stream = (uint64_t)(c->dec_rec_cap / 4u) - (uint64_t)(c->dec_rec_cap / 4u) / 64u;
     long long acc[4] = {0, 0, 0, 0};
-    auto sub_batches = [&](const int* sz_v, const qoi_desc* ds_v, const int* place, int n_all, uint32_t B) -> int {
+    auto sub_batches = [&](const int* sz_v, const qoi_desc* ds_v, const size_t* so_v, const size_t* po_v, int n_all, uint32_t B) -> int {
         for (int first = 0; first < n_all;) {
             uint64_t bytes = 0;
             int n = 0;
@@ -1121,10 +1123,7 @@ extern "C" int qoimi_decode_batch(qoimi_ctx* c, const void* d_streams, size_t st
                 bytes += sz; ++n;
             }
             long long st3[4] = {0, 0, 0, 0};
-            int rc;
-            if (place) rc = decode_some(c, d_streams, stream_stride, sz_v + first, ds_v + first, n, channels, d_pixels, pixel_stride, stream, B, false, st3, place + first);
-            else rc = decode_some(c, (const uint8_t*)d_streams + (size_t)first * stream_stride, stream_stride, sz_v + first, ds_v + first, n, channels,
-                                  (uint8_t*)d_pixels + (size_t)first * pixel_stride, pixel_stride, stream, B, n_images == 1, st3);
+            const int rc = decode_some(c, d_streams, so_v + first, stream_limit, sz_v + first, ds_v + first, n, channels, d_pixels, po_v + first, pixel_limit, stream, B, st3);
             if (rc != QOIMI_OK) return rc;
             acc[0] = st3[0] > acc[0] ? st3[0] : acc[0]; acc[1] += st3[1]; acc[2] += st3[2]; acc[3] += st3[3];
             first += n;
@@ -1135,33 +1134,149 @@ extern "C" int qoimi_decode_batch(qoimi_ctx* c, const void* d_streams, size_t st
     // photographs - is decoded CLASS BY CLASS: the flat images' passes (a few refinement passes in front of their P4, the P4 that leaves run
     // descriptors) are as long as one lane's walk over one segment, and the segment size the other images' bytes ask for made each of them
     // ~270 us for a few hundred lanes (3 of the mixed directory's 5.4 ms, profiles/r06_s28_mixed_timeline.txt).  Each class takes the
-    // segment size of its own bytes; an image's place in the caller's buffers travels in the table (DecImage::out_index).
+    // segment size of its own bytes; an image's place in the caller's buffers travels in the table (DecImage::stream_off / pixel_off).
     int n_flat = 0;
     if (n_images > 4)
         for (int i = 0; i < n_images; ++i)
             n_flat += (sizes[i] > 22 && descs[i].width != 0 && dec_image_is_flat((uint32_t)sizes[i] - 8u, (uint32_t)((uint64_t)descs[i].width * descs[i].height))) ? 1 : 0;
     if (n_flat != 0 && n_flat != n_images && c->dec_run_desc && c->dec_class_split) {
         for (int cls = 0; cls < 2; ++cls) {
-            std::vector<int> place, sz_v; std::vector<qoi_desc> ds_v;
+            std::vector<int> sz_v; std::vector<qoi_desc> ds_v; std::vector<size_t> so_v, po_v;
             for (int i = 0; i < n_images; ++i) {
                 const bool flat = sizes[i] > 22 && descs[i].width != 0 && dec_image_is_flat((uint32_t)sizes[i] - 8u, (uint32_t)((uint64_t)descs[i].width * descs[i].height));
-                if ((flat ? 1 : 0) == cls) { place.push_back(i); sz_v.push_back(sizes[i]); ds_v.push_back(descs[i]); }
+                if ((flat ? 1 : 0) == cls) { sz_v.push_back(sizes[i]); ds_v.push_back(descs[i]); so_v.push_back(stream_offs[i]); po_v.push_back(pixel_offs[i]); }
             }
-            const uint32_t B = choose_seg_bytes(c, sz_v.data(), ds_v.data(), (int)place.size(), cls == 0);      // (QOIMI_SEG_BYTES: the other images' size; the flat class keeps its rule)
+            const uint32_t B = choose_seg_bytes(c, sz_v.data(), ds_v.data(), (int)sz_v.size(), cls == 0);      // (QOIMI_SEG_BYTES: the other images' size; the flat class keeps its rule)
             const long long before = acc[0];
             acc[0] = 0;
-            const int rc = sub_batches(sz_v.data(), ds_v.data(), place.data(), (int)place.size(), B);
+            const int rc = sub_batches(sz_v.data(), ds_v.data(), so_v.data(), po_v.data(), (int)sz_v.size(), B);
             if (rc != QOIMI_OK) return rc;
-            if (cls == 0 && place.size() > 4u) c->dec_nonflat_repair = acc[0] > 1;
+            if (cls == 0 && sz_v.size() > 4u) c->dec_nonflat_repair = acc[0] > 1;
             acc[0] = acc[0] > before ? acc[0] : before;
         }
     } else {
         const uint32_t B = choose_seg_bytes(c, sizes, descs, n_images);
-        const int rc = sub_batches(sizes, descs, nullptr, n_images, B);
+        const int rc = sub_batches(sizes, descs, stream_offs, pixel_offs, n_images, B);
         if (rc != QOIMI_OK) return rc;
         if (n_images > 4 && n_flat == 0) c->dec_nonflat_repair = acc[0] > 1;
     }
     c->dec_stats[0] = acc[0]; c->dec_stats[1] = acc[1]; c->dec_stats[2] = acc[2]; c->dec_stats[3] = acc[3];
+    return QOIMI_OK;
+}
+
+// The strided form: image i at i * stride - a caller of the path above.
+extern "C" int qoimi_decode_batch(qoimi_ctx* c, const void* d_streams, size_t stream_stride,
+                                  const int* sizes, const qoi_desc* descs, int n_images, int channels,
+                                  void* d_pixels, size_t pixel_stride, void* stream) {
+    if (!c || !d_streams || !sizes || !descs || !d_pixels || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    for (int i = 1; i < n_images && channels == 0; ++i)
+        if (descs[i].channels != descs[0].channels) return fail(QOIMI_E_ARG, "all images of a batch must share the output channel count");
+    size_t few[8];                                            // (a call of a few images allocates nothing for its offsets)
+    std::vector<size_t> many;
+    size_t* so = few; size_t* po = few + 4;
+    if (n_images > 4) { many.resize(2u * (size_t)n_images); so = many.data(); po = so + n_images; }
+    for (int i = 0; i < n_images; ++i) { so[i] = (size_t)i * stream_stride; po[i] = (size_t)i * pixel_stride; }
+    // (a lone stream may be longer than its stride: there is nothing behind it)
+    return decode_offsets(c, d_streams, so, n_images == 1 ? ~(size_t)0 : stream_stride, sizes, descs, n_images, channels, d_pixels, po, pixel_stride, stream);
+}
+
+// Streams and images wherever the caller's offsets put them.  Two things in the kernels are written for ascending addresses: the
+// transcoder's stream descriptor (one per wavefront, from its first lane's stream to its last lane's end) and the pixel writer's (based at
+// the image of the wavefront's first segment).  The image table is therefore laid out by ascending STREAM offset here - a sorted pack runs
+// as qoimi_decode_batch does; a stream that ends behind its successor's end (overlapping input ranges) is out of its wavefront's reach and
+// takes the plain-pointer parse (counted in qoimi_decode_stats [3]); an image that lies in front of its wavefront's base is written with
+// plain stores (correct, slower).
+extern "C" int qoimi_decode_images(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes,
+                                   const qoi_desc* descs, int n_images, int channels,
+                                   void* d_pixels, const size_t* pixel_offsets, void* stream) {
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !d_pixels || !pixel_offsets || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    // everything the host can see is looked at before anything is launched: a rejected call leaves the caller's buffers as they were
+    std::vector<size_t> out_bytes((size_t)n_images);
+    for (int i = 0; i < n_images; ++i) {
+        if (sizes[i] < kHeaderBytes + kTrailerBytes) return fail(QOIMI_E_ARG, "stream shorter than 22 bytes (qoi.h:500)");
+        if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor rejected (qoi.h:513-521 rules)");
+        if (channels == 0 && descs[i].channels != descs[0].channels) return fail(QOIMI_E_ARG, "all images of a batch must share the output channel count");
+        out_bytes[(size_t)i] = (size_t)descs[i].width * descs[i].height * (size_t)(channels ? channels : descs[i].channels);
+    }
+    std::vector<int> order((size_t)n_images);
+    std::iota(order.begin(), order.end(), 0);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return pixel_offsets[a] < pixel_offsets[b]; });
+    for (int k = 1; k < n_images; ++k) {
+        const int a = order[(size_t)k - 1], b = order[(size_t)k];
+        if (pixel_offsets[a] + out_bytes[(size_t)a] > pixel_offsets[b]) return fail(QOIMI_E_ARG, "the output ranges of two images overlap");
+    }
+    const bool ascending = std::is_sorted(stream_offsets, stream_offsets + n_images);
+    if (ascending) return decode_offsets(c, d_streams, stream_offsets, ~(size_t)0, sizes, descs, n_images, channels, d_pixels, pixel_offsets, ~(size_t)0, stream);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return stream_offsets[a] < stream_offsets[b]; });
+    std::vector<size_t> so((size_t)n_images), po((size_t)n_images); std::vector<int> sz((size_t)n_images); std::vector<qoi_desc> ds((size_t)n_images);
+    for (int k = 0; k < n_images; ++k) { const int i = order[(size_t)k]; so[(size_t)k] = stream_offsets[i]; po[(size_t)k] = pixel_offsets[i]; sz[(size_t)k] = sizes[i]; ds[(size_t)k] = descs[i]; }
+    return decode_offsets(c, d_streams, so.data(), ~(size_t)0, sz.data(), ds.data(), n_images, channels, d_pixels, po.data(), ~(size_t)0, stream);
+}
+
+// ------------------------------------------------------------------------------------
+// packed streams
+// ------------------------------------------------------------------------------------
+extern "C" int qoimi_pack_streams(qoimi_ctx* c, const void* d_streams, size_t stream_stride, const int* d_stream_len, int n_streams,
+                                  unsigned align, void* d_packed, size_t packed_capacity, unsigned long long* d_packed_off, void* stream) {
+    if (!c || !d_streams || !d_stream_len || !d_packed_off || n_streams <= 0 || (!d_packed && packed_capacity != 0)) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (align == 0 || align > 256u || (align & (align - 1u)) != 0) return fail(QOIMI_E_ARG, "align must be a power of two, 1..256");
+    if (stream_stride == 0 || stream_stride > (size_t)0x7FFFFFFF + 256u) return fail(QOIMI_E_ARG, "stream_stride out of range");
+    {
+        const uintptr_t s0 = (uintptr_t)d_streams, s1 = s0 + (size_t)n_streams * stream_stride, p0 = (uintptr_t)d_packed, p1 = p0 + packed_capacity;
+        if (packed_capacity != 0 && s0 < p1 && p0 < s1) return fail(QOIMI_E_ARG, "source and destination overlap");
+    }
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (c->timer.n > KernelTimer::kMax - 32) { HIP_TRY(hipStreamSynchronize(st)); timer_collect(c); }
+    launch_pack_streams((const uint8_t*)d_streams, stream_stride, d_stream_len, (uint32_t)n_streams, align, (uint8_t*)d_packed, packed_capacity,
+                        (u64*)d_packed_off, (uint32_t)c->n_cus * 8u, st, &c->timer);
+    HIP_TRY(hipGetLastError());
+    return QOIMI_OK;
+}
+
+static uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
+// The 14 header bytes of a stream by the rules of qoi.h:505-521: *desc is filled whatever they hold; true if a decoder accepts them.
+static bool parse_header(const uint8_t* bytes, qoi_desc* desc) {
+    const bool magic_ok = memcmp(bytes, "qoif", 4) == 0;
+    desc->width = be32(bytes + 4);                                        // filled before validation, qoi.h:507-511
+    desc->height = be32(bytes + 8);
+    desc->channels = bytes[12];
+    desc->colorspace = bytes[13];
+    return desc_ok(desc) && magic_ok;                                     // qoi.h:513-521
+}
+
+extern "C" int qoimi_read_descs(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, int n_streams,
+                                qoi_desc* descs_out, int* first_bad, void* stream) {
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs_out || n_streams <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
+    // offsets in, header bytes out: both through the context's pinned staging, which the kernel reads and writes in place
+    const size_t n = (size_t)n_streams, bytes = n * (sizeof(u64) + 16u) + 256u;
+    if (bytes > c->pin_cap) {
+        if (c->pin_buf) (void)hipHostFree(c->pin_buf);
+        c->pin_buf = nullptr; c->pin_cap = 0;
+        HIP_TRY(hipHostMalloc(&c->pin_buf, bytes + 4096));
+        c->pin_cap = bytes + 4096;
+    }
+    u64* offs = (u64*)c->pin_buf;
+    uint8_t* hdr = (uint8_t*)c->pin_buf + ((n * sizeof(u64) + 255u) & ~(size_t)255u);
+    for (size_t i = 0; i < n; ++i) offs[i] = sizes[i] >= kHeaderBytes + kTrailerBytes ? (u64)stream_offsets[i] : ~0ull;
+    launch_gather_headers((const uint8_t*)d_streams, offs, (uint32_t)n_streams, (uint32_t*)hdr, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    int bad = -1;
+    for (size_t i = 0; i < n; ++i) {
+        bool ok = false;
+        if (sizes[i] >= kHeaderBytes + kTrailerBytes) ok = parse_header(hdr + 16u * i, &descs_out[i]);    // (a shorter stream: qoi_decode returns before it touches *desc, qoi.h:497-503)
+        if (!ok && bad < 0) bad = (int)i;
+    }
+    if (first_bad) *first_bad = bad;
+    if (bad >= 0) return fail(QOIMI_E_ARG, "stream " + std::to_string(bad) + ": shorter than 22 bytes or header rejected (qoi.h:497-521 rules)");
     return QOIMI_OK;
 }
 
@@ -1377,18 +1492,11 @@ extern "C" void* qoi_encode(const void* data, const qoi_desc* desc, int* out_len
     return result;
 }
 
-static uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-
 extern "C" void* qoi_decode(const void* data, int size, qoi_desc* desc, int channels) {
     if (!data || !desc || (channels != 0 && channels != 3 && channels != 4) ||
         size < kHeaderBytes + kTrailerBytes) return NULL;                 // qoi.h:497-503
     const uint8_t* bytes = (const uint8_t*)data;
-    const bool magic_ok = memcmp(bytes, "qoif", 4) == 0;
-    desc->width = be32(bytes + 4);                                        // filled before validation, qoi.h:507-511
-    desc->height = be32(bytes + 8);
-    desc->channels = bytes[12];
-    desc->colorspace = bytes[13];
-    if (!desc_ok(desc) || !magic_ok) return NULL;                         // qoi.h:513-521
+    if (!parse_header(bytes, desc)) return NULL;                          // desc filled before validation, qoi.h:507-521
     const int och = channels ? channels : desc->channels;                 // qoi.h:523-525
     const size_t out_bytes = (size_t)desc->width * desc->height * (size_t)och;
 

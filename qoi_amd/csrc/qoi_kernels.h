@@ -16,6 +16,7 @@ enum KernelTag { kT_begin = 0,
                  kT_enc_summary, kT_enc_scan_groups, kT_enc_scan_images, kT_enc_slabs, kT_enc_slabs_generic, kT_enc_offsets, kT_enc_compact,
                  kT_dec_parse, kT_dec_chain_parse, kT_dec_slot_walk, kT_dec_chain_slots, kT_dec_summarize,
                  kT_dec_chain_state, kT_dec_segments, kT_dec_restart, kT_dec_fill, kT_dec_expand,
+                 kT_pack_offsets, kT_pack_copy,
                  kT_enc_total, kT_dec_total,    // a whole qoimi_encode_batch / qoimi_decode_batch on the caller's stream (kernels of a call may overlap)
                  kT_count };
 struct KernelTimer {
@@ -139,7 +140,7 @@ struct DecImage {
     uint32_t start_seg;    // first segment still to be (re)decoded; n_active: done
     uint32_t final_px;     // exit pixel of the last active segment                 (P4)
     uint32_t desc_base;    // flat images (run descriptors): index of the image's first segment among the flat images' segments; kNoRunDesc: none
-    uint32_t out_index;    // the image's place in the caller's pixel buffer: pixels + out_index * pixel_stride (a call decoded class by class: not the table index)
+    size_t   pixel_off;    // the image's place in the caller's pixel buffer: pixels + pixel_off (any byte offset, in any order)
 };
 constexpr uint32_t kNoRunDesc = 0xFFFFFFFFu;
 
@@ -156,7 +157,7 @@ struct DecParams {
     uint32_t* recs;                      // chunk records (qoi_decode_core.h), [block of 64 segments][granule row][lane = segment & 63] x 16 bytes:
                                          // a wavefront's granule row is one contiguous KiB - every record load / store is fully coalesced
     uint32_t* rec_gran;                  // [total_segs + 1] granules (4 records) written per segment
-    uint8_t* pixels; size_t pixel_stride;
+    uint8_t* pixels;                     // image i at pixels + images[i].pixel_off
     // workspace, per global segment q
     ParseRec* parse;           // P1
     uint8_t*  entry_phase;     // S1
@@ -257,5 +258,11 @@ struct SynthParams {
 };
 void launch_synth(const SynthParams& p, hipStream_t st);
 void launch_hash_streams(const uint8_t* streams, size_t stride, const int* lens, uint32_t n, u64* out, hipStream_t st);
+
+// ---- packed streams ----------------------------------------------------------------
+// off[n + 1]: exclusive scan of the lengths, starts rounded up to align; then the copy (grid: workgroups, sized to the device)
+void launch_pack_streams(const uint8_t* streams, size_t stride, const int* lens, uint32_t n, unsigned align, uint8_t* packed, size_t cap, u64* off,
+                         uint32_t grid, hipStream_t st, KernelTimer* tm);
+void launch_gather_headers(const uint8_t* streams, const u64* offs, uint32_t n, uint32_t* out, hipStream_t st);
 
 }  // namespace qoimi
