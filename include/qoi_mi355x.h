@@ -221,6 +221,48 @@ int qoimi_pack_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
 int qoimi_read_descs(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets, const int *sizes, int n_streams,
                      qoi_desc *descs_out /* host */, int *first_bad /* host, may be NULL */, void *stream);
 
+/* What is in the streams of a pack, and whether they are intact: the chunk walk of every stream WITHOUT decoding it - no pixel state, no
+ * colour table, no output image; a function of the stream bytes alone.  qoi_decode and the decode calls above keep the reference's
+ * leniency (a cut stream decodes into repeated pixels, a chunk may reach into the trailer, surplus chunks and a wrong end marker are
+ * ignored, all with QOIMI_OK); this call is the strict counterpart.
+ * The walk (normative; qoi_amd/streaminfo.py: inspect_stream states it in Python): p = 14, end = size - 8; while p < end read b = s[p]:
+ *   0xFE -> RGB, 4 bytes;  0xFF -> RGBA, 5 bytes;  b >> 6 == 0 -> INDEX, 1 byte;  == 1 -> DIFF, 1 byte;  == 2 -> LUMA, 2 bytes;
+ *   == 3 -> RUN, 1 byte, (b & 63) + 1 pixels; every other chunk is 1 pixel.  Count the chunk, add its pixels, advance p by its length.
+ * walk_end = p.  These are the tag rules of qoi.h:547-575, but the walk is bounded by the BYTES, not by width*height as the reference's
+ * loop is: only so can it tell a stream that is short of pixels from one that has too many.  A chunk that starts below size - 8 ends
+ * below size - 3, so nothing outside [offset, offset + size) is read - but for the aligned 4-byte words that hold a first or last byte. */
+enum { QOIMI_OP_INDEX = 0, QOIMI_OP_DIFF, QOIMI_OP_LUMA, QOIMI_OP_RUN, QOIMI_OP_RGB, QOIMI_OP_RGBA };
+enum {
+    QOIMI_SI_TOO_SHORT      = 1,   /* size < 22: nothing was read, every other field is 0 */
+    QOIMI_SI_HEADER_BAD     = 2,   /* fails the rules qoimi_read_descs applies (qoi.h:497-521) */
+    QOIMI_SI_PIXELS_SHORT   = 4,   /* pixels < width*height: the decoder repeats the last pixel (qoi.h:544) */
+    QOIMI_SI_PIXELS_OVER    = 8,   /* pixels > width*height: the decoder clips a run / ignores chunks */
+    QOIMI_SI_LAST_CHUNK_CUT = 16,  /* walk_end > size - 8: the last chunk reaches into the final 8 bytes */
+    QOIMI_SI_NO_END_MARKER  = 32,  /* the final 8 bytes are not 0,0,0,0,0,0,0,1 (qoi.h:103,339) */
+    QOIMI_SI_REPEATED_INDEX = 64   /* repeat_index != 0 (qoi.h:118-119) */
+};
+typedef struct {                    /* 64 bytes, offsets 0/8/16/40/44/48/52 */
+    unsigned long long pixels;      /* pixels the chunks produce, runs counted in full, NOT clipped to width*height */
+    unsigned long long run_pixels;  /* of those, produced by QOI_OP_RUN chunks */
+    unsigned int ops[6];            /* chunks by kind, indexed by QOIMI_OP_* */
+    unsigned int repeat_index;      /* INDEX chunks that directly follow an INDEX chunk with the same byte */
+    unsigned int walk_end;          /* byte offset in the stream where the walk ends (size-8 ... size-4) */
+    unsigned int flags;             /* QOIMI_SI_* */
+    unsigned int reserved[3];       /* 0 */
+} qoimi_stream_info;
+
+/*   stream_offsets, sizes  HOST arrays as for qoimi_decode_images: any byte offsets, any order; ranges may overlap or coincide
+ *   infos_out      HOST qoimi_stream_info[n_streams]
+ *   first_flagged  HOST, may be NULL: the lowest index with flags != 0, -1 if none
+ * PIXELS_SHORT / PIXELS_OVER are evaluated only when the header passes (against the 64-bit product width*height); a stream of 22 bytes or
+ * more with a bad header is walked all the same.  A stream is conforming when flags == 0.
+ * Synchronous.  QOIMI_OK when the inspection ran, whatever it found (n_streams == 0 included); QOIMI_E_ARG for a NULL ctx, stream_offsets,
+ * sizes or infos_out, d_streams == NULL with n_streams > 0, n_streams < 0 or a negative size: nothing is launched, infos_out is untouched.
+ * Cost: the stream bytes are read twice by kernels that do nothing else; workspace (counted in qoimi_workspace_bytes [1]) is 1/32 of the
+ * stream bytes plus 69 bytes per 16 KiB block of a stream and 16 per stream.  One call at a time per context, as everywhere. */
+int qoimi_inspect_streams(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets, const int *sizes, int n_streams,
+                          qoimi_stream_info *infos_out /* host */, int *first_flagged /* host, may be NULL */, void *stream);
+
 /* Fill device memory with synthetic RGBA frames frame_id = first_frame .. first_frame+n-1
  * (benchmark/test utility; same function of (kind, seed, frame, pixel) as synth.py). */
 int qoimi_synth_frames(qoimi_ctx *ctx, int kind, unsigned seed, unsigned first_frame,
@@ -234,7 +276,8 @@ int qoimi_synth_frames(qoimi_ctx *ctx, int kind, unsigned seed, unsigned first_f
 int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stride, const int *d_stream_len, int n_streams,
                        unsigned long long *d_hash, void *stream);
 
-/* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace, [1] decode workspace,
+/* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace, [1] decode workspace
+ * (and the tables of qoimi_inspect_streams),
  * [2] staging buffers of the host-pointer entry points (qoi_encode / qoi_decode of the calling thread's context). */
 void qoimi_workspace_bytes(qoimi_ctx *ctx, size_t out[3]);
 

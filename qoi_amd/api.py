@@ -36,7 +36,7 @@ EXPORTS = (
     "qoimi_encode_batch", "qoimi_encode_status", "qoimi_decode_batch", "qoimi_synth_frames",
     "qoimi_decode_stats", "qoimi_version", "qoimi_set_profiling", "qoimi_get_profile", "qoimi_kernel_name",
     "qoimi_encode_suspect_calls", "qoimi_encode_retries", "qoimi_set_encode_small_call_order", "qoimi_workspace_bytes", "qoimi_set_decode_record_cap", "qoimi_hash_streams", "qoimi_encode_images",
-    "qoimi_decode_images", "qoimi_pack_streams", "qoimi_read_descs",
+    "qoimi_decode_images", "qoimi_pack_streams", "qoimi_read_descs", "qoimi_inspect_streams",
 )
 
 
@@ -47,6 +47,12 @@ class QoiDesc(ctypes.Structure):
 
     def __repr__(self):
         return f"QoiDesc({self.width}x{self.height}, channels={self.channels}, colorspace={self.colorspace})"
+
+
+class StreamInfo(ctypes.Structure):
+    """``qoimi_stream_info``: 64 bytes, the layout of ``streaminfo.INFO_DTYPE``."""
+    _fields_ = [("pixels", ctypes.c_ulonglong), ("run_pixels", ctypes.c_ulonglong), ("ops", ctypes.c_uint * 6),
+                ("repeat_index", ctypes.c_uint), ("walk_end", ctypes.c_uint), ("flags", ctypes.c_uint), ("reserved", ctypes.c_uint * 3)]
 
 
 class QoiError(RuntimeError):
@@ -120,6 +126,8 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_pack_streams.argtypes = [vp, vp, sz, vp, ci, ctypes.c_uint, vp, sz, vp, vp]
     lib.qoimi_read_descs.restype = ci
     lib.qoimi_read_descs.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ctypes.POINTER(QoiDesc), ctypes.POINTER(ci), vp]
+    lib.qoimi_inspect_streams.restype = ci
+    lib.qoimi_inspect_streams.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ctypes.POINTER(StreamInfo), ctypes.POINTER(ci), vp]
     _lib = lib
     return lib
 
@@ -311,6 +319,22 @@ class Context:
         if rc != 0 and bad.value < 0:
             self._check(rc, "qoimi_read_descs")
         return list(descs), (bad.value if bad.value >= 0 else None)
+
+    def inspect_streams(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], stream: int = 0):
+        """Chunk statistics and strict checks of the streams of a pack (``qoimi_inspect_streams``): (infos, first_flagged) - infos is a
+        numpy array of ``streaminfo.INFO_DTYPE``, first_flagged the lowest index with flags != 0 or None."""
+        from .streaminfo import INFO_DTYPE
+        n = len(sizes)
+        if len(stream_offsets) != n:
+            raise QoiError("inspect_streams: one stream offset per size")
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        infos = np.zeros(n, dtype=INFO_DTYPE)
+        first = ctypes.c_int(-1)
+        self._check(self._lib.qoimi_inspect_streams(self._h, d_streams, so.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
+                                                    sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n,
+                                                    infos.ctypes.data_as(ctypes.POINTER(StreamInfo)), ctypes.byref(first), stream), "qoimi_inspect_streams")
+        return infos, (first.value if first.value >= 0 else None)
 
     def synth_frames(self, kind: int, seed: int, first_frame: int, n_frames: int, width: int, height: int,
                      d_pixels: int, pixel_stride: int, stream: int = 0) -> None:

@@ -30,6 +30,7 @@
 #include "qoi_decode_core.h"
 #include "qoi_kernels.h"
 #include "qoi_pack.hip"        // the pack kernels and their launchers: part of this translation unit (no build lists the file itself)
+#include "qoi_inspect.hip"     // ... and the kernels of qoimi_inspect_streams, the same way
 
 using namespace qoimi;
 
@@ -98,6 +99,7 @@ struct qoimi_ctx {
     int device = 0;
     int n_cus = 256;            // compute units of the device (the grid of the pack's copy)
     Arena enc_ws, dec_ws;       // kernel workspaces
+    Arena insp_ws;              // tables, maps and partial counts of qoimi_inspect_streams (its own: a decode call finds dec_ws as it left it)
     Arena dec_scan;             // look-back words of dec_scan_entry (calls of a few images): tagged with dec_epoch, zeroed when allocated / when the tag wraps
     uint32_t dec_epoch = 0;     // number of the last such call (16 bits are compared)
     struct { void* at = nullptr; unsigned gen = 0; bool valid = false; } dec_hdr_zero;
@@ -274,7 +276,7 @@ extern "C" void qoimi_ctx_destroy(qoimi_ctx* c) {
     DeviceGuard guard(c->device);
     (void)hipDeviceSynchronize();       // calls still in flight write to the arenas and to the pinned words freed below
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    c->enc_ws.release(); c->dec_ws.release(); c->dec_scan.release(); c->io_a.release(); c->io_b.release(); c->io_c.release();
+    c->enc_ws.release(); c->dec_ws.release(); c->insp_ws.release(); c->dec_scan.release(); c->io_a.release(); c->io_b.release(); c->io_c.release();
     if (c->host_word) (void)hipHostFree(c->host_word);
     if (c->pin_buf) (void)hipHostFree(c->pin_buf);
     if (c->enc_pin_buf) (void)hipHostFree(c->enc_pin_buf);
@@ -340,7 +342,8 @@ extern "C" int qoimi_get_profile(qoimi_ctx* c, void* stream, double* ms, long lo
 extern "C" const char* qoimi_kernel_name(int i) {
     static const char* names[kT_count] = {"", "enc_slab_summary", "enc_scan_groups", "enc_scan_images", "enc_slabs", "enc_slabs_generic", "enc_offsets", "enc_compact",
         "dec_parse", "dec_chain_parse", "dec_transcode", "dec_chain_slots", "dec_summarize", "dec_chain_state",
-        "dec_segments", "dec_prepare_restart", "dec_fill", "dec_expand_runs", "pack_offsets", "pack_copy", "encode_total", "decode_total"};
+        "dec_segments", "dec_prepare_restart", "dec_fill", "dec_expand_runs", "pack_offsets", "pack_copy",
+        "inspect_maps", "inspect_scan", "inspect_count", "inspect_reduce", "encode_total", "decode_total"};
     return (i >= 0 && i < kT_count) ? names[i] : "";
 }
 
@@ -354,7 +357,7 @@ extern "C" int qoimi_set_encode_small_call_order(qoimi_ctx* c, int by_workgroup_
 
 // device memory the context holds: [0] encode workspace, [1] decode workspace, [2] staging of the host-pointer entry points
 extern "C" void qoimi_workspace_bytes(qoimi_ctx* c, size_t out[3]) {
-    out[0] = c ? c->enc_ws.cap : 0; out[1] = c ? c->dec_ws.cap : 0;
+    out[0] = c ? c->enc_ws.cap : 0; out[1] = c ? c->dec_ws.cap + c->insp_ws.cap : 0;
     out[2] = c ? c->io_a.cap + c->io_b.cap + c->io_c.cap : 0;
 }
 
@@ -1277,6 +1280,109 @@ extern "C" int qoimi_read_descs(qoimi_ctx* c, const void* d_streams, const size_
     }
     if (first_bad) *first_bad = bad;
     if (bad >= 0) return fail(QOIMI_E_ARG, "stream " + std::to_string(bad) + ": shorter than 22 bytes or header rejected (qoi.h:497-521 rules)");
+    return QOIMI_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// chunk statistics and strict checks (qoi_inspect.hip)
+// ------------------------------------------------------------------------------------
+static_assert(sizeof(qoimi_stream_info) == sizeof(InsResult) && offsetof(qoimi_stream_info, ops) == 16 && offsetof(qoimi_stream_info, repeat_index) == 40 &&
+              offsetof(qoimi_stream_info, walk_end) == 44 && offsetof(qoimi_stream_info, flags) == 48 && offsetof(qoimi_stream_info, reserved) == 52,
+              "qoimi_stream_info is what inspect_reduce writes");
+
+extern "C" int qoimi_inspect_streams(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, int n_streams,
+                                     qoimi_stream_info* infos_out, int* first_flagged, void* stream) {
+    if (!c || !stream_offsets || !sizes || !infos_out || n_streams < 0 || (!d_streams && n_streams > 0)) return fail(QOIMI_E_ARG, "NULL/negative argument");
+    const size_t n = (size_t)n_streams;
+    const int kMin = kHeaderBytes + kTrailerBytes;
+    // the block table's size: a block is up to kInsBlock bytes of ONE stream's body
+    size_t nb = 0, npieces = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (sizes[i] < 0) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + ": negative size");
+        if (sizes[i] <= kMin) continue;
+        const size_t body = (size_t)(sizes[i] - kMin);
+        nb += (body + kInsBlock - 1u) / kInsBlock;
+        npieces += (body + kInsPiece - 1u) / kInsPiece;
+    }
+    if (nb >= 0x7FFFFFFFu || npieces >= 0xFFFFFFFFu) return fail(QOIMI_E_ARG, "more than 2^31 blocks of stream bytes in one call");
+    if (first_flagged) *first_flagged = -1;
+    if (n == 0) return QOIMI_OK;
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
+    if (c->timer.n > KernelTimer::kMax - 32) { HIP_TRY(hipStreamSynchronize(st)); timer_collect(c); }
+    // pinned staging: [stream table][block table] go to the device, [results][header + trailer bytes] are written by inspect_reduce in place
+    auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
+    const size_t tab_bytes = up(n * sizeof(InsStream)) + up(nb * sizeof(InsBlock));
+    const size_t bytes = tab_bytes + up(n * sizeof(InsResult)) + up(n * 32u);
+    if (bytes > c->pin_cap) {
+        if (c->pin_buf) (void)hipHostFree(c->pin_buf);
+        c->pin_buf = nullptr; c->pin_cap = 0;
+        HIP_TRY(hipHostMalloc(&c->pin_buf, bytes + 4096));
+        c->pin_cap = bytes + 4096;
+    }
+    uint8_t* pin = (uint8_t*)c->pin_buf;
+    InsStream* h_tab = (InsStream*)pin;
+    InsBlock* h_blk = (InsBlock*)(pin + up(n * sizeof(InsStream)));
+    InsResult* h_res = (InsResult*)(pin + tab_bytes);
+    const uint8_t* h_raw = pin + tab_bytes + up(n * sizeof(InsResult));
+    {
+        uint32_t b = 0, pc = 0;
+        for (size_t i = 0; i < n; ++i) {
+            h_tab[i].off = sizes[i] >= kMin ? (u64)stream_offsets[i] : ~0ull;
+            h_tab[i].size = (uint32_t)sizes[i]; h_tab[i].first_blk = b;
+            if (sizes[i] <= kMin) continue;
+            const uint32_t body = (uint32_t)(sizes[i] - kMin);
+            for (uint32_t at = 0; at < body; at += kInsBlock) {
+                const uint32_t len = body - at < kInsBlock ? body - at : kInsBlock;
+                h_blk[b].off = (u64)stream_offsets[i] + (u64)kHeaderBytes + at;
+                h_blk[b].len = len | (at == 0 ? kInsFirst : 0u);
+                h_blk[b].piece_base = pc;
+                ++b; pc += (len + kInsPiece - 1u) / kInsPiece;
+            }
+        }
+    }
+    // device workspace: the tables, a map and an entry phase per block, a map per piece (2 bytes per 64 stream bytes), a partial per block
+    Carver sizer(nullptr);
+    sizer.take<uint8_t>(tab_bytes); sizer.take<uint32_t>(nb); sizer.take<uint8_t>(nb); sizer.take<uint16_t>(npieces); sizer.take<InsPartial>(nb);
+    { const int rc = c->insp_ws.reserve(sizer.off + 256u); if (rc != QOIMI_OK) return rc; }
+    Carver cv(c->insp_ws.base);
+    uint8_t* d_tab = cv.take<uint8_t>(tab_bytes);
+    uint32_t* d_map = cv.take<uint32_t>(nb);
+    uint8_t* d_entry = cv.take<uint8_t>(nb);
+    uint16_t* d_piece = cv.take<uint16_t>(npieces);
+    InsPartial* d_part = cv.take<InsPartial>(nb);
+    HIP_TRY(hipMemcpyAsync(d_tab, pin, tab_bytes, hipMemcpyHostToDevice, st));
+    launch_inspect((const uint8_t*)d_streams, (const InsStream*)d_tab, (uint32_t)n, (const InsBlock*)(d_tab + up(n * sizeof(InsStream))), (uint32_t)nb,
+                   d_map, d_entry, d_piece, d_part, h_res, (uint32_t*)(pin + tab_bytes + up(n * sizeof(InsResult))), st, &c->timer);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    static const uint8_t kEnd[8] = {0, 0, 0, 0, 0, 0, 0, 1};                // qoi.h:339
+    int flagged = -1;
+    for (size_t i = 0; i < n; ++i) {
+        qoimi_stream_info info;
+        memset(&info, 0, sizeof(info));
+        if (sizes[i] < kMin) info.flags = QOIMI_SI_TOO_SHORT;
+        else {
+            memcpy(&info, &h_res[i], sizeof(info));
+            const uint8_t* raw = h_raw + 32u * i;
+            qoi_desc d;
+            unsigned f = 0;
+            if (!parse_header(raw, &d)) f |= QOIMI_SI_HEADER_BAD;
+            else {
+                const unsigned long long want = (unsigned long long)d.width * d.height;
+                if (info.pixels < want) f |= QOIMI_SI_PIXELS_SHORT;
+                if (info.pixels > want) f |= QOIMI_SI_PIXELS_OVER;
+            }
+            if (info.walk_end > (unsigned)(sizes[i] - kTrailerBytes)) f |= QOIMI_SI_LAST_CHUNK_CUT;
+            if (memcmp(raw + kHeaderBytes, kEnd, 8) != 0) f |= QOIMI_SI_NO_END_MARKER;
+            if (info.repeat_index != 0) f |= QOIMI_SI_REPEATED_INDEX;
+            info.flags = f;
+        }
+        infos_out[i] = info;
+        if (info.flags != 0 && flagged < 0) flagged = (int)i;
+    }
+    if (first_flagged) *first_flagged = flagged;
     return QOIMI_OK;
 }
 

@@ -17,6 +17,7 @@ enum KernelTag { kT_begin = 0,
                  kT_dec_parse, kT_dec_chain_parse, kT_dec_slot_walk, kT_dec_chain_slots, kT_dec_summarize,
                  kT_dec_chain_state, kT_dec_segments, kT_dec_restart, kT_dec_fill, kT_dec_expand,
                  kT_pack_offsets, kT_pack_copy,
+                 kT_inspect_maps, kT_inspect_scan, kT_inspect_count, kT_inspect_reduce,
                  kT_enc_total, kT_dec_total,    // a whole qoimi_encode_batch / qoimi_decode_batch on the caller's stream (kernels of a call may overlap)
                  kT_count };
 struct KernelTimer {
