@@ -211,6 +211,47 @@ int qoimi_pack_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
                        unsigned align, void *d_packed, size_t packed_capacity,
                        unsigned long long *d_packed_off /* device, n_streams + 1 */, void *stream);
 
+/* Pixels in, pack out, in one call: the result is DEFINED as that of qoimi_encode_batch into a buffer of stride S, qoimi_encode_status, then
+ * qoimi_pack_streams(..., align, d_packed, packed_capacity, d_packed_off, ...) over all n_images streams - the same pack bytes, the same
+ * d_packed_off[0 .. n_images] (starts rounded up to `align`, [n_images] the unrounded end = the bytes the pack needs), the same d_stream_len -
+ * but the caller never owns n_images * S bytes of strided streams: the context encodes consecutive sub-batches of whole images into a staging
+ * arena of its own and appends each to the pack on the device (the running end of the pack never travels through the host).
+ *   d_packed_off   DEVICE unsigned long long[n_images + 1], d_stream_len DEVICE int[n_images]: written by the call
+ *   packed_off_out HOST unsigned long long[n_images + 1], stream_len_out HOST int[n_images], each may be NULL: copies of the two device
+ *                  tables, as qoimi_decode_images, qoimi_read_descs and qoimi_inspect_streams take them
+ *   align, packed_capacity: as qoimi_pack_streams - a stream that does not fit WHOLLY below packed_capacity is not copied, not in part, gap
+ *                  bytes are not written, nothing at or behind d_packed + packed_capacity is written, both tables are complete in any case;
+ *                  packed_capacity 0 (d_packed may then be NULL): lengths and offsets only.  An overflow is NOT an error: the call returns
+ *                  QOIMI_OK and packed_off_out[n_images] > packed_capacity says what happened and how much to allocate.
+ *   staging_bytes  device memory the call may hold for strided streams (an arena of the context, counted in qoimi_workspace_bytes [0], grown
+ *                  like the other arenas; a mixed-shape call adds 8 bytes per image for a table).  0: 1 GiB.  The sub-batch plan (normative;
+ *                  qoi_amd/packplan.py: plan states it in Python): a slot is qoimi_encode_bound(desc_i) rounded up to 256 bytes, images are
+ *                  taken in order, a sub-batch closes when the next slot would not fit in staging_bytes; a request smaller than one slot is
+ *                  raised to that slot, so every sub-batch holds at least one image.  Equal shapes: max(1, staging_bytes / slot) images each.
+ * Descriptors and pixel_stride are checked by the rules of qoimi_encode_batch; NULL ctx / d_pixels / desc / d_packed_off / d_stream_len,
+ * n_images <= 0, align not a power of two in 1..256 and d_packed == NULL with packed_capacity != 0 are rejected as well.  Every rejection
+ * (QOIMI_E_ARG) happens before anything is launched: the caller's buffers are untouched.
+ * SYNCHRONOUS: returns when the pack, both device tables and the non-NULL host tables are complete.  Every sub-batch is encoded, then its
+ * status is looked at exactly as qoimi_encode_status does (a placement wait that gave up is repaired before the sub-batch is copied: the pack
+ * never takes bytes from a sub-batch whose status has not been looked at), then it is appended.  A failure of that status (QOIMI_E_INTERNAL,
+ * the once-only report of a failed LDS-order repeat included) ends the call with that code; the pack is then incomplete.  Afterwards
+ * qoimi_encode_status returns QOIMI_OK and never encodes "the last call" again - it went into staging.
+ * Each sub-batch counts as ONE encode call for the counters of the LDS-order self-test (qoimi_encode_suspect_calls, the repeat every 256
+ * calls).  d_pixels and [d_packed, + packed_capacity) must not overlap. */
+int qoimi_encode_packed(qoimi_ctx *ctx, const void *d_pixels, size_t pixel_stride, const qoi_desc *desc, int n_images,
+                        unsigned align, void *d_packed, size_t packed_capacity,
+                        unsigned long long *d_packed_off /* device, n_images + 1 */, int *d_stream_len /* device, n_images */,
+                        size_t staging_bytes,
+                        unsigned long long *packed_off_out /* host, n_images + 1, may be NULL */,
+                        int *stream_len_out /* host, n_images, may be NULL */, void *stream);
+
+/* The same for images of different shapes and channel counts, defined the same way with qoimi_encode_images (pixel_offsets, descs: HOST
+ * arrays as there; every descriptor is checked before anything is launched). */
+int qoimi_encode_images_packed(qoimi_ctx *ctx, const void *d_pixels, const size_t *pixel_offsets, const qoi_desc *descs, int n_images,
+                               unsigned align, void *d_packed, size_t packed_capacity,
+                               unsigned long long *d_packed_off, int *d_stream_len, size_t staging_bytes,
+                               unsigned long long *packed_off_out, int *stream_len_out, void *stream);
+
 /* What makes a pack self-describing: the header of every stream, read on the device and parsed by the rules of qoi.h:497-521.
  *   stream_offsets, sizes  HOST arrays as for qoimi_decode_images
  *   descs_out      HOST qoi_desc[n_streams]: filled for every stream of 22 bytes or more, valid or not (as qoi_decode fills *desc before
@@ -276,7 +317,8 @@ int qoimi_synth_frames(qoimi_ctx *ctx, int kind, unsigned seed, unsigned first_f
 int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stride, const int *d_stream_len, int n_streams,
                        unsigned long long *d_hash, void *stream);
 
-/* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace, [1] decode workspace
+/* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace (and the staging arena of
+ * qoimi_encode_packed), [1] decode workspace
  * (and the tables of qoimi_inspect_streams),
  * [2] staging buffers of the host-pointer entry points (qoi_encode / qoi_decode of the calling thread's context). */
 void qoimi_workspace_bytes(qoimi_ctx *ctx, size_t out[3]);

@@ -37,6 +37,7 @@ EXPORTS = (
     "qoimi_decode_stats", "qoimi_version", "qoimi_set_profiling", "qoimi_get_profile", "qoimi_kernel_name",
     "qoimi_encode_suspect_calls", "qoimi_encode_retries", "qoimi_set_encode_small_call_order", "qoimi_workspace_bytes", "qoimi_set_decode_record_cap", "qoimi_hash_streams", "qoimi_encode_images",
     "qoimi_decode_images", "qoimi_pack_streams", "qoimi_read_descs", "qoimi_inspect_streams",
+    "qoimi_encode_packed", "qoimi_encode_images_packed",
 )
 
 
@@ -128,6 +129,11 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_read_descs.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ctypes.POINTER(QoiDesc), ctypes.POINTER(ci), vp]
     lib.qoimi_inspect_streams.restype = ci
     lib.qoimi_inspect_streams.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(ci), ci, ctypes.POINTER(StreamInfo), ctypes.POINTER(ci), vp]
+    ullp = ctypes.POINTER(ctypes.c_ulonglong)
+    lib.qoimi_encode_packed.restype = ci
+    lib.qoimi_encode_packed.argtypes = [vp, vp, sz, ctypes.POINTER(QoiDesc), ci, ctypes.c_uint, vp, sz, vp, vp, sz, ullp, ctypes.POINTER(ci), vp]
+    lib.qoimi_encode_images_packed.restype = ci
+    lib.qoimi_encode_images_packed.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(QoiDesc), ci, ctypes.c_uint, vp, sz, vp, vp, sz, ullp, ctypes.POINTER(ci), vp]
     _lib = lib
     return lib
 
@@ -306,6 +312,30 @@ class Context:
         self._check(self._lib.qoimi_pack_streams(self._h, d_streams, stream_stride, d_stream_len, n_streams, align,
                                                  d_packed, packed_capacity, d_packed_off, stream), "qoimi_pack_streams")
 
+    def encode_packed(self, d_pixels: int, pixel_stride: int, desc: QoiDesc, n_images: int, align: int, d_packed: int, packed_capacity: int,
+                      d_packed_off: int, d_stream_len: int, staging_bytes: int = 0, stream: int = 0):
+        """Pixels -> pack in one call through bounded staging (``qoimi_encode_packed``, synchronous): (offsets uint64[n + 1], sizes
+        int32[n]) as numpy arrays - offsets[:n] and sizes are what ``read_descs`` / ``decode_images`` / ``inspect_streams`` take,
+        offsets[n] the bytes the pack needs (larger than packed_capacity: the streams that did not fit wholly are absent)."""
+        off, sizes = np.zeros(n_images + 1, dtype=np.uint64), np.zeros(n_images, dtype=np.intc)
+        self._check(self._lib.qoimi_encode_packed(self._h, d_pixels, pixel_stride, ctypes.byref(desc), n_images, align, d_packed, packed_capacity,
+                                                  d_packed_off, d_stream_len, staging_bytes, off.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
+                                                  sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), stream), "qoimi_encode_packed")
+        return off, sizes
+
+    def encode_images_packed(self, d_pixels: int, pixel_offsets: Sequence[int], descs: Sequence[QoiDesc], align: int, d_packed: int,
+                             packed_capacity: int, d_packed_off: int, d_stream_len: int, staging_bytes: int = 0, stream: int = 0):
+        """The same for images of different shapes / channel counts (``qoimi_encode_images_packed``)."""
+        n = len(descs)
+        if len(pixel_offsets) != n:
+            raise QoiError("encode_images_packed: one pixel offset per descriptor")
+        po = (ctypes.c_size_t * n)(*[int(x) for x in pixel_offsets])
+        off, sizes = np.zeros(n + 1, dtype=np.uint64), np.zeros(n, dtype=np.intc)
+        self._check(self._lib.qoimi_encode_images_packed(self._h, d_pixels, po, (QoiDesc * n)(*descs), n, align, d_packed, packed_capacity,
+                                                         d_packed_off, d_stream_len, staging_bytes, off.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
+                                                         sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), stream), "qoimi_encode_images_packed")
+        return off, sizes
+
     def read_descs(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], stream: int = 0):
         """The headers of the streams of a pack: (descs, first_bad) - first_bad is None when every stream passes the rules of
         qoi.h:497-521, else the lowest failing index (``qoimi_read_descs`` then returns QOIMI_E_ARG; the descriptors are filled anyway)."""
@@ -356,7 +386,7 @@ class Context:
         return {self._lib.qoimi_kernel_name(i).decode(): (ms[i], calls[i]) for i in range(1, n)}
 
     def workspace_bytes(self) -> dict:
-        """Device bytes the context's arenas hold: encode workspace, decode workspace, staging of the host-pointer entry points."""
+        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace, staging of the host-pointer entry points."""
         out = (ctypes.c_size_t * 3)()
         self._lib.qoimi_workspace_bytes(self._h, out)
         return {"encode": int(out[0]), "decode": int(out[1]), "staging": int(out[2])}

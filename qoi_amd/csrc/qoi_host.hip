@@ -99,6 +99,7 @@ struct qoimi_ctx {
     int device = 0;
     int n_cus = 256;            // compute units of the device (the grid of the pack's copy)
     Arena enc_ws, dec_ws;       // kernel workspaces
+    Arena enc_stage;            // qoimi_encode_packed: the strided streams of one sub-batch (and the source offsets of a mixed-shape call) on their way into the pack
     Arena insp_ws;              // tables, maps and partial counts of qoimi_inspect_streams (its own: a decode call finds dec_ws as it left it)
     Arena dec_scan;             // look-back words of dec_scan_entry (calls of a few images): tagged with dec_epoch, zeroed when allocated / when the tag wraps
     uint32_t dec_epoch = 0;     // number of the last such call (16 bits are compared)
@@ -276,7 +277,7 @@ extern "C" void qoimi_ctx_destroy(qoimi_ctx* c) {
     DeviceGuard guard(c->device);
     (void)hipDeviceSynchronize();       // calls still in flight write to the arenas and to the pinned words freed below
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    c->enc_ws.release(); c->dec_ws.release(); c->insp_ws.release(); c->dec_scan.release(); c->io_a.release(); c->io_b.release(); c->io_c.release();
+    c->enc_ws.release(); c->enc_stage.release(); c->dec_ws.release(); c->insp_ws.release(); c->dec_scan.release(); c->io_a.release(); c->io_b.release(); c->io_c.release();
     if (c->host_word) (void)hipHostFree(c->host_word);
     if (c->pin_buf) (void)hipHostFree(c->pin_buf);
     if (c->enc_pin_buf) (void)hipHostFree(c->enc_pin_buf);
@@ -343,7 +344,7 @@ extern "C" const char* qoimi_kernel_name(int i) {
     static const char* names[kT_count] = {"", "enc_slab_summary", "enc_scan_groups", "enc_scan_images", "enc_slabs", "enc_slabs_generic", "enc_offsets", "enc_compact",
         "dec_parse", "dec_chain_parse", "dec_transcode", "dec_chain_slots", "dec_summarize", "dec_chain_state",
         "dec_segments", "dec_prepare_restart", "dec_fill", "dec_expand_runs", "pack_offsets", "pack_copy",
-        "inspect_maps", "inspect_scan", "inspect_count", "inspect_reduce", "encode_total", "decode_total"};
+        "inspect_maps", "inspect_scan", "inspect_count", "inspect_reduce", "pack_offsets_append", "pack_copy_append", "encode_total", "decode_total"};
     return (i >= 0 && i < kT_count) ? names[i] : "";
 }
 
@@ -355,9 +356,9 @@ extern "C" int qoimi_set_encode_small_call_order(qoimi_ctx* c, int by_workgroup_
     return QOIMI_OK;
 }
 
-// device memory the context holds: [0] encode workspace, [1] decode workspace, [2] staging of the host-pointer entry points
+// device memory the context holds: [0] encode workspace (and the staging of qoimi_encode_packed), [1] decode workspace, [2] staging of the host-pointer entry points
 extern "C" void qoimi_workspace_bytes(qoimi_ctx* c, size_t out[3]) {
-    out[0] = c ? c->enc_ws.cap : 0; out[1] = c ? c->dec_ws.cap + c->insp_ws.cap : 0;
+    out[0] = c ? c->enc_ws.cap + c->enc_stage.cap : 0; out[1] = c ? c->dec_ws.cap + c->insp_ws.cap : 0;
     out[2] = c ? c->io_a.cap + c->io_b.cap + c->io_c.cap : 0;
 }
 
@@ -1238,6 +1239,125 @@ extern "C" int qoimi_pack_streams(qoimi_ctx* c, const void* d_streams, size_t st
                         (u64*)d_packed_off, (uint32_t)c->n_cus * 8u, st, &c->timer);
     HIP_TRY(hipGetLastError());
     return QOIMI_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// encode into a pack through bounded staging
+// ------------------------------------------------------------------------------------
+// The staging qoimi_encode_packed takes when the caller passes 0.
+static const size_t kPackStagingDefault = (size_t)1 << 30;
+
+// The sub-batch plan (normative; qoi_amd/packplan.py: plan states it in Python): a slot is an image's encode bound rounded up to 256 bytes,
+// images are taken in order, a sub-batch closes when the next slot would not fit in staging_bytes - but never empty: a slot larger than the
+// request is a sub-batch of its own.  Returns the first image of every sub-batch and, behind the last one, n.
+static std::vector<int> pack_plan(const std::vector<size_t>& slots, size_t staging_bytes) {
+    std::vector<int> firsts(1, 0);
+    size_t used = 0;
+    for (size_t i = 0; i < slots.size(); ++i) {
+        if ((int)i > firsts.back() && (slots[i] > staging_bytes || used > staging_bytes - slots[i])) { firsts.push_back((int)i); used = 0; }
+        used += slots[i];
+    }
+    firsts.push_back((int)slots.size());
+    return firsts;
+}
+
+static int pin_reserve(qoimi_ctx* c, size_t bytes) {
+    if (bytes <= c->pin_cap) return QOIMI_OK;
+    if (c->pin_buf) (void)hipHostFree(c->pin_buf);
+    c->pin_buf = nullptr; c->pin_cap = 0;
+    HIP_TRY(hipHostMalloc(&c->pin_buf, bytes + 4096));
+    c->pin_cap = bytes + 4096;
+    return QOIMI_OK;
+}
+
+// Both entry points: descs holds one descriptor (pixel_offsets == nullptr: image i at i * pixel_stride) or n_images of them.  Every sub-batch
+// is one call of the encoder as it is into the staging arena, qoimi_encode_status (which waits for it and encodes it again order-free if a
+// placement wait gave up: the pack never takes bytes of a sub-batch whose status has not been looked at), then the append scan and copy on the
+// caller's stream; the next sub-batch's encoder is ordered behind that copy by the stream.
+static int encode_packed(qoimi_ctx* c, const void* d_pixels, size_t pixel_stride, const size_t* pixel_offsets, const qoi_desc* descs, int n_images,
+                         unsigned align, void* d_packed, size_t packed_capacity, unsigned long long* d_packed_off, int* d_stream_len,
+                         size_t staging_bytes, unsigned long long* packed_off_out, int* stream_len_out, void* stream) {
+    const bool mixed = pixel_offsets != nullptr;
+    const size_t n = (size_t)n_images;
+    std::vector<size_t> slots(n), src(n);
+    size_t largest = 0;
+    for (size_t i = 0; i < n; ++i) {
+        slots[i] = (qoimi_encode_bound(&descs[mixed ? i : 0]) + 255u) & ~(size_t)255u;
+        if (slots[i] > largest) largest = slots[i];
+    }
+    const std::vector<int> firsts = pack_plan(slots, staging_bytes ? staging_bytes : kPackStagingDefault);
+    size_t need = 0;                                         // the largest sub-batch
+    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
+        size_t at = 0;
+        for (int i = firsts[k]; i < firsts[k + 1]; ++i) { src[(size_t)i] = at; at += slots[(size_t)i]; }
+        if (at > need) need = at;
+    }
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
+    const size_t table_bytes = mixed ? (n * sizeof(u64) + 255u) & ~(size_t)255u : 0;
+    { int rc = c->enc_stage.reserve(table_bytes + need); if (rc) return rc; }
+    { int rc = pin_reserve(c, (n + 1u) * sizeof(u64) + n * sizeof(int) + 256u); if (rc) return rc; }
+    u64* const d_src = mixed ? (u64*)c->enc_stage.base : nullptr;
+    uint8_t* const staging = (uint8_t*)c->enc_stage.base + table_bytes;
+    if (mixed) {                                             // where stream j lies in the staging of its sub-batch: one table for the whole call
+        for (size_t i = 0; i < n; ++i) ((u64*)c->pin_buf)[i] = (u64)src[i];
+        HIP_TRY(hipMemcpyAsync(d_src, c->pin_buf, n * sizeof(u64), hipMemcpyHostToDevice, st));
+    }
+    int rc = QOIMI_OK;
+    for (size_t k = 0; k + 1 < firsts.size() && rc == QOIMI_OK; ++k) {
+        const int first = firsts[k], m = firsts[k + 1] - first;
+        size_t span = 0;
+        for (int i = first; i < first + m; ++i) span += slots[(size_t)i];
+        rc = mixed ? qoimi_encode_images(c, d_pixels, pixel_offsets + first, descs + first, m, staging, src.data() + first, d_stream_len + first, stream)
+                   : qoimi_encode_batch(c, (const uint8_t*)d_pixels + (size_t)first * pixel_stride, pixel_stride, descs, m, staging, largest, d_stream_len + first, stream);
+        if (rc == QOIMI_OK) rc = qoimi_encode_status(c, stream);
+        if (rc != QOIMI_OK) break;
+        if (c->timer.n > KernelTimer::kMax - 32) { HIP_TRY(hipStreamSynchronize(st)); timer_collect(c); }
+        // (a stream is no longer than its slot and align is at most 256, so the sub-batch takes no more of the pack than `span` bytes:
+        // that many tiles, one more for where the range begins in its first tile and one for the destination's own alignment)
+        const size_t tiles = span / kPackTile + 3u, most = (size_t)c->n_cus * 8u;
+        launch_pack_append(staging, largest, d_src, d_stream_len, (uint32_t)first, (uint32_t)m, align, (uint8_t*)d_packed, packed_capacity,
+                           (u64*)d_packed_off, (uint32_t)(tiles < most ? tiles : most), st, &c->timer);
+        if (hipGetLastError() != hipSuccess) rc = fail(QOIMI_E_INTERNAL, "launch of the pack's append kernels failed");
+    }
+    // whatever happened, qoimi_encode_status must not encode "the last call" again: it went into staging
+    c->last_enc.valid = false; c->last_enc_err = nullptr; c->last_enc_err2 = nullptr;
+    if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
+    u64* const h_off = (u64*)c->pin_buf; int* const h_len = (int*)(h_off + n + 1u);
+    HIP_TRY(hipMemcpyAsync(h_off, d_packed_off, (n + 1u) * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_len, d_stream_len, n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (packed_off_out) memcpy(packed_off_out, h_off, (n + 1u) * sizeof(u64));
+    if (stream_len_out) memcpy(stream_len_out, h_len, n * sizeof(int));
+    return QOIMI_OK;
+}
+
+static int encode_packed_args(qoimi_ctx* c, const void* d_pixels, int n_images, unsigned align, void* d_packed, size_t packed_capacity,
+                              const void* d_packed_off, const void* d_stream_len) {
+    if (!c || !d_pixels || !d_packed_off || !d_stream_len || n_images <= 0 || (!d_packed && packed_capacity != 0)) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (align == 0 || align > 256u || (align & (align - 1u)) != 0) return fail(QOIMI_E_ARG, "align must be a power of two, 1..256");
+    return QOIMI_OK;
+}
+
+extern "C" int qoimi_encode_packed(qoimi_ctx* c, const void* d_pixels, size_t pixel_stride, const qoi_desc* desc, int n_images,
+                                   unsigned align, void* d_packed, size_t packed_capacity, unsigned long long* d_packed_off, int* d_stream_len,
+                                   size_t staging_bytes, unsigned long long* packed_off_out, int* stream_len_out, void* stream) {
+    if (int rc = encode_packed_args(c, d_pixels, n_images, align, d_packed, packed_capacity, d_packed_off, d_stream_len)) return rc;
+    if (!desc_ok(desc)) return fail(QOIMI_E_ARG, "descriptor rejected (qoi.h:364-372 rules)");
+    if (pixel_stride < (size_t)desc->width * desc->height * desc->channels) return fail(QOIMI_E_ARG, "pixel_stride smaller than one image");
+    return encode_packed(c, d_pixels, pixel_stride, nullptr, desc, n_images, align, d_packed, packed_capacity, d_packed_off, d_stream_len,
+                         staging_bytes, packed_off_out, stream_len_out, stream);
+}
+
+extern "C" int qoimi_encode_images_packed(qoimi_ctx* c, const void* d_pixels, const size_t* pixel_offsets, const qoi_desc* descs, int n_images,
+                                          unsigned align, void* d_packed, size_t packed_capacity, unsigned long long* d_packed_off, int* d_stream_len,
+                                          size_t staging_bytes, unsigned long long* packed_off_out, int* stream_len_out, void* stream) {
+    if (int rc = encode_packed_args(c, d_pixels, n_images, align, d_packed, packed_capacity, d_packed_off, d_stream_len)) return rc;
+    if (!pixel_offsets || !descs) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    for (int i = 0; i < n_images; ++i) if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor rejected (qoi.h:364-372 rules)");
+    return encode_packed(c, d_pixels, 0, pixel_offsets, descs, n_images, align, d_packed, packed_capacity, d_packed_off, d_stream_len,
+                         staging_bytes, packed_off_out, stream_len_out, stream);
 }
 
 static uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }

@@ -18,6 +18,7 @@ enum KernelTag { kT_begin = 0,
                  kT_dec_chain_state, kT_dec_segments, kT_dec_restart, kT_dec_fill, kT_dec_expand,
                  kT_pack_offsets, kT_pack_copy,
                  kT_inspect_maps, kT_inspect_scan, kT_inspect_count, kT_inspect_reduce,
+                 kT_pack_offsets_append, kT_pack_copy_append,
                  kT_enc_total, kT_dec_total,    // a whole qoimi_encode_batch / qoimi_decode_batch on the caller's stream (kernels of a call may overlap)
                  kT_count };
 struct KernelTimer {
@@ -264,6 +265,8 @@ void launch_hash_streams(const uint8_t* streams, size_t stride, const int* lens,
 // off[n + 1]: exclusive scan of the lengths, starts rounded up to align; then the copy (grid: workgroups, sized to the device)
 void launch_pack_streams(const uint8_t* streams, size_t stride, const int* lens, uint32_t n, unsigned align, uint8_t* packed, size_t cap, u64* off,
                          uint32_t grid, hipStream_t st, KernelTimer* tm);
+void launch_pack_append(const uint8_t* staging, size_t stride, const u64* src_off, const int* lens, uint32_t first, uint32_t m, unsigned align,
+                        uint8_t* packed, size_t cap, u64* off, uint32_t grid, hipStream_t st, KernelTimer* tm);
 void launch_gather_headers(const uint8_t* streams, const u64* offs, uint32_t n, uint32_t* out, hipStream_t st);
 
 }  // namespace qoimi
