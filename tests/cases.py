@@ -112,6 +112,46 @@ def encode_cases() -> List[Dict]:
     return cases
 
 
+def _redraw_repeats(px: np.ndarray, rng: np.random.Generator, cols) -> None:
+    """Redraws columns `cols` of every pixel that repeats an earlier one (or is all zero) until every pixel of the image is a value
+    of its own: a pixel the colour table cannot hold (qoi.h:430-436 - it holds earlier pixels and zeroes) is never a QOI_OP_INDEX.
+    Random colours alone do repeat: the table offers 64 values to each of w*h pixels, 162 000 x 64 / 2^24 = 0.6 hits in a
+    517 x 313 RGB image."""
+    while True:
+        key = px.astype(np.uint32) @ (np.uint32(1) << (8 * np.arange(px.shape[1], dtype=np.uint32)))
+        again = np.ones(len(px), dtype=bool)
+        again[np.unique(key, return_index=True)[1]] = False
+        again |= key == 0
+        if not again.any():
+            return
+        px[np.ix_(again, cols)] = rng.integers(0, 256, size=(int(again.sum()), len(cols)), dtype=np.uint8)
+
+
+def full_slot_rgba(w: int, h: int, seed: int) -> np.ndarray:
+    """h x w x 4 pixels whose stream is exactly w*h*5 + 22 bytes, the encoder's bound (qoi.h:374-376): random colours, no pixel
+    twice, and an alpha that differs from the previous pixel's everywhere (steps of 1..255, the first one from the start value's
+    255), so every pixel is a QOI_OP_RGBA (qoi.h:461-474)."""
+    rng = np.random.default_rng([seed, w, h, 4])
+    px = rng.integers(0, 256, size=(w * h, 4), dtype=np.uint8)
+    px[:, 3] = (255 + np.cumsum(rng.integers(1, 256, size=w * h))) & 255
+    _redraw_repeats(px, rng, [0, 1, 2])
+    return px.reshape(h, w, 4)
+
+
+def full_slot_rgb(w: int, h: int, seed: int) -> np.ndarray:
+    """h x w x 3 pixels whose stream is exactly w*h*4 + 22 bytes: random red and blue, no pixel twice, green steps of 96..160 -
+    outside the windows of QOI_OP_DIFF (-2..1) and QOI_OP_LUMA (-32..31), qoi.h:443-459 - so every pixel is a QOI_OP_RGB."""
+    rng = np.random.default_rng([seed, w, h, 3])
+    px = rng.integers(0, 256, size=(w * h, 3), dtype=np.uint8)
+    px[:, 1] = np.cumsum(rng.integers(96, 161, size=w * h)) & 255
+    _redraw_repeats(px, rng, [0, 2])
+    return px.reshape(h, w, 3)
+
+
+def full_slot_image(w: int, h: int, ch: int, seed: int) -> np.ndarray:
+    return full_slot_rgba(w, h, seed) if ch == 4 else full_slot_rgb(w, h, seed)
+
+
 def encode_arg_cases() -> List[Dict]:
     """Argument validation of qoi.h:364-372; pixels are never read, expected result NULL."""
     return [

@@ -27,9 +27,15 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def random_image(rng: np.random.Generator, w: int, h: int) -> np.ndarray:
-    """h x w x 4 uint8: a patchwork of stretches (along the scan order, as the encoder sees the pixels)."""
+def random_image(rng: np.random.Generator, w: int, h: int, full_slot: float = 0.0, ch: int = 4) -> np.ndarray:
+    """h x w x 4 uint8: a patchwork of stretches (along the scan order, as the encoder sees the pixels).  full_slot > 0 (--odd-strides;
+    0 draws nothing, so the other modes' sequences stay what their seeds always gave): with that probability an image whose
+    `ch`-channel stream fills its slot to the last byte of qoimi_encode_bound instead (tests/cases.py: full_slot_image)."""
     n = w * h
+    if full_slot > 0.0 and rng.random() < full_slot:
+        import cases
+        f = cases.full_slot_image(w, h, ch, int(rng.integers(0, 1 << 31)))
+        return f if ch == 4 else np.concatenate([f, np.full((h, w, 1), 255, dtype=np.uint8)], axis=2)
     a = np.empty((n, 4), dtype=np.uint8)
     palette = rng.integers(0, 256, size=(int(rng.integers(2, 40)), 4), dtype=np.uint8)
     if rng.random() < 0.5:
@@ -183,7 +189,7 @@ def main() -> int:
                 os.environ[k] = v
             else:
                 os.environ.pop(k, None)
-        frames = [np.ascontiguousarray(random_image(rng, w, h)[:, :, :ch]) for _ in range(n)]
+        frames = [np.ascontiguousarray(random_image(rng, w, h, 0.15 if args.odd_strides else 0.0, ch)[:, :, :ch]) for _ in range(n)]
         if args.only >= 0 and it != args.only:
             continue
         if args.form is not None:
@@ -202,7 +208,9 @@ def main() -> int:
             npx = w * h
             desc = api.QoiDesc(w, h, ch, 0)
             po, so, oo = (int(x) for x in rng.integers(0, 16, size=3))
-            ps = npx * ch + int(rng.integers(0, 19)); ss = api.encode_bound(w, h, ch) + int(rng.integers(0, 35)); ost = npx * ch + int(rng.integers(0, 19))
+            # (no slack at all in a third of the calls each: the stride is the image / the bound, a stream may end on its slot's last byte)
+            dp, ds = (0 if rng.random() < 0.33 else int(rng.integers(0, 19))), (0 if rng.random() < 0.33 else int(rng.integers(0, 35)))
+            ps = npx * ch + dp; ss = api.encode_bound(w, h, ch) + ds; ost = npx * ch + int(rng.integers(0, 19))
             d_pix = torch.zeros(po + n * ps + 64, dtype=torch.uint8, device="cuda")
             d_str = torch.full((so + n * ss + 64,), 0xEE, dtype=torch.uint8, device="cuda")
             d_out = torch.full((oo + n * ost + 64,), 0xCD, dtype=torch.uint8, device="cuda")

@@ -14,7 +14,8 @@ import libsel  # noqa: E402
 libsel.use_test_library()
 
 import torch  # noqa: E402,F401  (first: the library binds to the HIP runtime torch loaded)
-from gpu_util import DeviceBatch  # noqa: E402
+import cases  # noqa: E402
+from gpu_util import DeviceBatch, EdgeBatch  # noqa: E402
 from oracle import oracle_py  # noqa: E402
 from qoi_amd import api, synth  # noqa: E402
 
@@ -34,6 +35,30 @@ def spin_bound(n, w, h):
     lens = b.encode()                 # encode_batch + encode_status (raises on an error status)
     for i in range(n):
         assert b.stream_bytes(i, lens[i]) == oracle.encode(synth.frame_rgba("photo", w, h, 300 + i), w, h, 4), i
+    r = c.encode_retries()
+    assert r >= 1, "the bounded wait never gave up: the hook did not act"
+    print(f"retries {r}")
+    c.close()
+
+
+def spin_bound_tight(n, w, h):
+    """spin_bound where the retry has no room for error: qoimi_encode_status encodes the call again "from the caller's buffers" with
+    the bases and strides it remembered - here odd bases, pixel_stride = npx*4 and stream_stride = qoimi_encode_bound exactly
+    (gpu_util.EdgeBatch), one image of the call filling its slot to the last byte (cases.full_slot_image) with the next stream's
+    header right behind it.  The reference's bytes, nothing written outside a stream, and the retry did happen."""
+    os.environ["QOIMI_TEST_SPIN_BOUND"] = "1"
+    os.environ["QOIMI_ENC_TREE_TICKET"] = "0"
+    c = api.Context(0)
+    del os.environ["QOIMI_TEST_SPIN_BOUND"], os.environ["QOIMI_ENC_TREE_TICKET"]
+    b = EdgeBatch(c, w, h, 4, n, po=3, so=9, oo=5, dp=0, ds=0)
+    frames = [synth.frame_rgba("photo", w, h, 300 + i) for i in range(n)]
+    frames[n // 2] = cases.full_slot_image(w, h, 4, 1)
+    want = [oracle.encode(f, w, h, 4) for f in frames]
+    assert len(want[n // 2]) == b.bound, "the image does not fill its slot: the scenario does not test"
+    for i, f in enumerate(frames):
+        b.upload(i, f)
+    lens, host = b.encode()           # encode_batch + encode_status (raises on an error status)
+    b.check_streams(host, lens, want, f"spin_bound_tight {n} x {w}x{h}")
     r = c.encode_retries()
     assert r >= 1, "the bounded wait never gave up: the hook did not act"
     print(f"retries {r}")
@@ -73,4 +98,4 @@ def recheck_fail():
 
 if __name__ == "__main__":
     name, args = sys.argv[1], [int(a) for a in sys.argv[2:]]
-    {"spin_bound": spin_bound, "recheck_fail": recheck_fail}[name](*args)
+    {"spin_bound": spin_bound, "spin_bound_tight": spin_bound_tight, "recheck_fail": recheck_fail}[name](*args)
