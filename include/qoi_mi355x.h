@@ -132,7 +132,7 @@ int qoimi_encode_images(qoimi_ctx *ctx, const void *d_pixels, const size_t *pixe
  * probe for good; the call that notices is encoded with it and returns QOIMI_OK (its own stream is sound), qoimi_last_error()
  * says what happened, the next qoimi_encode_status() returns QOIMI_E_INTERNAL ONCE, and this counter returns how many calls were
  * made since the launch of the last check that passed (the calls before the failed repeat was launched and the ones made while
- * it ran) - re-verify or re-encode those.  0 = never.
+ * it ran) - re-verify (qoimi_verify_images checks streams against the pixels they were made from, on the device) or re-encode those.  0 = never.
  * QOIMI_ENC_PROBE=0 in the environment selects the order-independent probe from the start (about 1.5 x the encode time). */
 long long qoimi_encode_suspect_calls(qoimi_ctx *ctx);
 
@@ -304,6 +304,65 @@ typedef struct {                    /* 64 bytes, offsets 0/8/16/40/44/48/52 */
 int qoimi_inspect_streams(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets, const int *sizes, int n_streams,
                           qoimi_stream_info *infos_out /* host */, int *first_flagged /* host, may be NULL */, void *stream);
 
+/* Are two sets of device images equal, pixel by pixel?  (The comparison is stated in Python by qoi_amd/imagediff.py: diff.)
+ *   a_offsets, b_offsets  HOST size_t[n_images]: image i of side A lies tightly packed at d_a + a_offsets[i] - descs[i].width * height pixels
+ *                  of ca bytes, ca = a_channels, or descs[i].channels when a_channels is 0 (the convention of qoimi_decode_images' `channels`);
+ *                  side B the same with b_channels.  ANY byte offsets, in any order; A and B may be the same buffer and ranges may overlap
+ *                  (nothing is written).  Not one byte outside an image's range influences the result; reads may touch the aligned 4-byte
+ *                  words that hold a first or last byte.
+ *   descs          HOST qoi_desc[n_images]: every one must pass the rules of qoi.h:364-372 (colorspace takes no part in the comparison)
+ *   diffs_out      HOST qoimi_image_diff[n_images]
+ *   first_diff     HOST, may be NULL: the lowest index with flags != 0, -1 if none
+ * Two pixels are equal when their first min(ca, cb) bytes are: an RGB buffer against an RGBA buffer compares r, g, b.
+ * Synchronous.  QOIMI_OK whenever the comparison ran, whatever it found; QOIMI_E_ARG for a NULL ctx, d_a, d_b, a_offsets, b_offsets, descs or
+ * diffs_out, n_images <= 0, a_channels or b_channels not 0, 3 or 4, a rejected descriptor: nothing is launched, diffs_out is untouched.
+ * Cost: every byte of both sides is read once by one launch for all images (cmp_pixels), a second launch of a thread per image reads the
+ * pixels at the first differences (cmp_first); 64 bytes of workspace per image (counted in qoimi_workspace_bytes [1]). */
+enum { QOIMI_DIFF_PIXELS = 1,          /* mismatched != 0 */
+       QOIMI_DIFF_HEADER = 2 };        /* qoimi_verify_images only: see there; the image was not decoded, every other field is 0 / ~0 */
+typedef struct {                        /* 32 bytes, offsets 0/8/16/20/24/28 */
+    unsigned long long mismatched;      /* pixels that differ */
+    unsigned long long first;           /* row-major index of the first differing pixel, ~0ull if none */
+    unsigned int want;                  /* pixel `first` of side A, bytes r,g,b,a little-endian; a channel the buffer does not hold reads 0xFF; 0 if none */
+    unsigned int got;                   /* the same of side B */
+    unsigned int flags;                 /* QOIMI_DIFF_* */
+    unsigned int reserved;              /* 0 */
+} qoimi_image_diff;
+int qoimi_compare_images(qoimi_ctx *ctx,
+                         const void *d_a, const size_t *a_offsets /* host */, int a_channels,
+                         const void *d_b, const size_t *b_offsets /* host */, int b_channels,
+                         const qoi_desc *descs /* host */, int n_images,
+                         qoimi_image_diff *diffs_out /* host */, int *first_diff /* host, may be NULL */, void *stream);
+
+/* Do these streams decode back to exactly these pixels?  diffs_out[i] is DEFINED as: decode stream i (sizes[i] bytes at d_streams +
+ * stream_offsets[i]) as qoi_decode does, with its leniency (qoi.h:488-590), to descs[i].channels output channels; take that decode as side B
+ * and the caller's image i (tightly packed at d_pixels + pixel_offsets[i], descs[i].channels bytes per pixel) as side A of
+ * qoimi_compare_images with ca = cb = descs[i].channels.  The caller never owns the decode: the context decodes consecutive sub-batches of
+ * whole images into a staging arena of its own and compares each in place; one table of results travels to the host at the end.
+ *   QOIMI_DIFF_HEADER  a stream shorter than 22 bytes, one whose header fails the rules of qoimi_read_descs, or whose header differs from
+ *                  descs[i] in width, height, channels or colorspace is not decoded: this flag alone, first = ~0, every other field 0.  Its
+ *                  neighbours are unaffected.
+ *   staging_bytes  device memory the call may hold for decoded pixels (an arena of the context, counted in qoimi_workspace_bytes [1]; it grows
+ *                  when a call needs more and is allocated as the largest sub-batch of the call's plan plus a page, no slack).  0: 1 GiB.
+ *                  The staging is decoded at ONE channel count per call, och = 3 if every descs[i].channels is 3, else 4 (alpha is compared
+ *                  exactly where the source image has it, and got reports a 3-channel image's alpha as 0xFF).  The sub-batch plan
+ *                  (normative; qoi_amd/packplan.py: plan over width * height * och): a slot is width * height * och rounded up to 256
+ *                  bytes, images are taken in order, a sub-batch closes when the next slot would not fit in staging_bytes; a request
+ *                  smaller than one slot is raised to that slot.  An image flagged QOIMI_DIFF_HEADER keeps its place and its slot in the
+ *                  plan - the plan is a function of descs and staging_bytes alone - and is left out of its sub-batch's decode and compare.
+ * Every sub-batch is one qoimi_decode_images call as it is (same bit-exactness for EVERY input stream), then the compare kernels on `stream`.
+ * Synchronous.  QOIMI_OK when the verification ran, whatever it found; the code of a decode sub-call that failed ends the call.  QOIMI_E_ARG
+ * for a NULL ctx, d_pixels, pixel_offsets, descs, d_streams, stream_offsets, sizes or diffs_out, n_images <= 0, a negative size, a rejected
+ * descs[i]: reported before anything is launched, diffs_out is untouched.  d_pixels and d_streams are only read.
+ * The sub-batches count as decode calls for everything a context's decode calls choose by what came before (the single-pass path of calls of
+ * a few images, segment sizes, qoimi_decode_stats - which holds the last sub-batch's), as the sub-batches of qoimi_encode_packed count as
+ * encode calls.  One call at a time per context, as everywhere. */
+int qoimi_verify_images(qoimi_ctx *ctx,
+                        const void *d_pixels, const size_t *pixel_offsets /* host */, const qoi_desc *descs /* host */, int n_images,
+                        const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                        size_t staging_bytes,
+                        qoimi_image_diff *diffs_out /* host */, int *first_diff /* host, may be NULL */, void *stream);
+
 /* Fill device memory with synthetic RGBA frames frame_id = first_frame .. first_frame+n-1
  * (benchmark/test utility; same function of (kind, seed, frame, pixel) as synth.py). */
 int qoimi_synth_frames(qoimi_ctx *ctx, int kind, unsigned seed, unsigned first_frame,
@@ -319,7 +378,7 @@ int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
 
 /* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace (and the staging arena of
  * qoimi_encode_packed), [1] decode workspace
- * (and the tables of qoimi_inspect_streams),
+ * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images),
  * [2] staging buffers of the host-pointer entry points (qoi_encode / qoi_decode of the calling thread's context). */
 void qoimi_workspace_bytes(qoimi_ctx *ctx, size_t out[3]);
 

@@ -38,6 +38,7 @@ EXPORTS = (
     "qoimi_encode_suspect_calls", "qoimi_encode_retries", "qoimi_set_encode_small_call_order", "qoimi_workspace_bytes", "qoimi_set_decode_record_cap", "qoimi_hash_streams", "qoimi_encode_images",
     "qoimi_decode_images", "qoimi_pack_streams", "qoimi_read_descs", "qoimi_inspect_streams",
     "qoimi_encode_packed", "qoimi_encode_images_packed",
+    "qoimi_compare_images", "qoimi_verify_images",
 )
 
 
@@ -54,6 +55,12 @@ class StreamInfo(ctypes.Structure):
     """``qoimi_stream_info``: 64 bytes, the layout of ``streaminfo.INFO_DTYPE``."""
     _fields_ = [("pixels", ctypes.c_ulonglong), ("run_pixels", ctypes.c_ulonglong), ("ops", ctypes.c_uint * 6),
                 ("repeat_index", ctypes.c_uint), ("walk_end", ctypes.c_uint), ("flags", ctypes.c_uint), ("reserved", ctypes.c_uint * 3)]
+
+
+class ImageDiff(ctypes.Structure):
+    """``qoimi_image_diff``: 32 bytes, the layout of ``imagediff.DIFF_DTYPE``."""
+    _fields_ = [("mismatched", ctypes.c_ulonglong), ("first", ctypes.c_ulonglong), ("want", ctypes.c_uint), ("got", ctypes.c_uint),
+                ("flags", ctypes.c_uint), ("reserved", ctypes.c_uint)]
 
 
 class QoiError(RuntimeError):
@@ -134,6 +141,11 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_encode_packed.argtypes = [vp, vp, sz, ctypes.POINTER(QoiDesc), ci, ctypes.c_uint, vp, sz, vp, vp, sz, ullp, ctypes.POINTER(ci), vp]
     lib.qoimi_encode_images_packed.restype = ci
     lib.qoimi_encode_images_packed.argtypes = [vp, vp, ctypes.POINTER(sz), ctypes.POINTER(QoiDesc), ci, ctypes.c_uint, vp, sz, vp, vp, sz, ullp, ctypes.POINTER(ci), vp]
+    szp, dp = ctypes.POINTER(sz), ctypes.POINTER(QoiDesc)
+    lib.qoimi_compare_images.restype = ci
+    lib.qoimi_compare_images.argtypes = [vp, vp, szp, ci, vp, szp, ci, dp, ci, ctypes.POINTER(ImageDiff), ctypes.POINTER(ci), vp]
+    lib.qoimi_verify_images.restype = ci
+    lib.qoimi_verify_images.argtypes = [vp, vp, szp, dp, ci, vp, szp, ctypes.POINTER(ci), sz, ctypes.POINTER(ImageDiff), ctypes.POINTER(ci), vp]
     _lib = lib
     return lib
 
@@ -366,6 +378,46 @@ class Context:
                                                     infos.ctypes.data_as(ctypes.POINTER(StreamInfo)), ctypes.byref(first), stream), "qoimi_inspect_streams")
         return infos, (first.value if first.value >= 0 else None)
 
+    def compare_images(self, d_a: int, a_offsets: Sequence[int], a_channels: int, d_b: int, b_offsets: Sequence[int], b_channels: int,
+                       descs: Sequence[QoiDesc], stream: int = 0):
+        """Two sets of device images, pixel by pixel (``qoimi_compare_images``): (diffs, first_diff) - diffs is a numpy array of
+        ``imagediff.DIFF_DTYPE``, first_diff the lowest index with flags != 0 or -1, as the C call gives it.  a_channels / b_channels: bytes per pixel of a side,
+        0 for each image's ``descs[i].channels``."""
+        from .imagediff import DIFF_DTYPE
+        n = len(descs)
+        if len(a_offsets) != n or len(b_offsets) != n:
+            raise QoiError("compare_images: one offset per side and descriptor")
+        ao = np.ascontiguousarray(a_offsets, dtype=np.uintp)
+        bo = np.ascontiguousarray(b_offsets, dtype=np.uintp)
+        diffs = np.zeros(n, dtype=DIFF_DTYPE)
+        first = ctypes.c_int(-1)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        self._check(self._lib.qoimi_compare_images(self._h, d_a, ao.ctypes.data_as(szp), a_channels, d_b, bo.ctypes.data_as(szp), b_channels,
+                                                   (QoiDesc * n)(*descs), n, diffs.ctypes.data_as(ctypes.POINTER(ImageDiff)),
+                                                   ctypes.byref(first), stream), "qoimi_compare_images")
+        return diffs, first.value
+
+    def verify_images(self, d_pixels: int, pixel_offsets: Sequence[int], descs: Sequence[QoiDesc], d_streams: int,
+                      stream_offsets: Sequence[int], sizes: Sequence[int], staging_bytes: int = 0, stream: int = 0):
+        """Do the streams decode back to exactly these pixels (``qoimi_verify_images``, synchronous, through bounded staging)?
+        (diffs, first_diff) as ``compare_images`` gives them; a stream whose header does not match its descriptor is flagged
+        ``imagediff.DIFF_HEADER`` and not decoded."""
+        from .imagediff import DIFF_DTYPE
+        n = len(descs)
+        if len(pixel_offsets) != n or len(stream_offsets) != n or len(sizes) != n:
+            raise QoiError("verify_images: one pixel offset, stream offset and size per descriptor")
+        po = np.ascontiguousarray(pixel_offsets, dtype=np.uintp)
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        diffs = np.zeros(n, dtype=DIFF_DTYPE)
+        first = ctypes.c_int(-1)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        self._check(self._lib.qoimi_verify_images(self._h, d_pixels, po.ctypes.data_as(szp), (QoiDesc * n)(*descs), n, d_streams,
+                                                  so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), staging_bytes,
+                                                  diffs.ctypes.data_as(ctypes.POINTER(ImageDiff)), ctypes.byref(first), stream),
+                    "qoimi_verify_images")
+        return diffs, first.value
+
     def synth_frames(self, kind: int, seed: int, first_frame: int, n_frames: int, width: int, height: int,
                      d_pixels: int, pixel_stride: int, stream: int = 0) -> None:
         self._check(self._lib.qoimi_synth_frames(self._h, kind, seed, first_frame, n_frames, width, height,
@@ -386,7 +438,7 @@ class Context:
         return {self._lib.qoimi_kernel_name(i).decode(): (ms[i], calls[i]) for i in range(1, n)}
 
     def workspace_bytes(self) -> dict:
-        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace, staging of the host-pointer entry points."""
+        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images``), staging of the host-pointer entry points."""
         out = (ctypes.c_size_t * 3)()
         self._lib.qoimi_workspace_bytes(self._h, out)
         return {"encode": int(out[0]), "decode": int(out[1]), "staging": int(out[2])}

@@ -31,6 +31,7 @@
 #include "qoi_kernels.h"
 #include "qoi_pack.hip"        // the pack kernels and their launchers: part of this translation unit (no build lists the file itself)
 #include "qoi_inspect.hip"     // ... and the kernels of qoimi_inspect_streams, the same way
+#include "qoi_compare.hip"     // ... and those of qoimi_compare_images / qoimi_verify_images
 
 using namespace qoimi;
 
@@ -101,6 +102,10 @@ struct qoimi_ctx {
     Arena enc_ws, dec_ws;       // kernel workspaces
     Arena enc_stage;            // qoimi_encode_packed: the strided streams of one sub-batch (and the source offsets of a mixed-shape call) on their way into the pack
     Arena insp_ws;              // tables, maps and partial counts of qoimi_inspect_streams (its own: a decode call finds dec_ws as it left it)
+    Arena cmp_ws;               // image table and result table of qoimi_compare_images / qoimi_verify_images
+    Arena ver_stage;            // qoimi_verify_images: the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
+    void* cmp_pin_buf = nullptr; size_t cmp_pin_cap = 0;   // pinned staging of those two calls' tables and results (their own: the decode calls inside
+                                // qoimi_verify_images reuse pin_buf at once)
     Arena dec_scan;             // look-back words of dec_scan_entry (calls of a few images): tagged with dec_epoch, zeroed when allocated / when the tag wraps
     uint32_t dec_epoch = 0;     // number of the last such call (16 bits are compared)
     struct { void* at = nullptr; unsigned gen = 0; bool valid = false; } dec_hdr_zero;
@@ -277,10 +282,11 @@ extern "C" void qoimi_ctx_destroy(qoimi_ctx* c) {
     DeviceGuard guard(c->device);
     (void)hipDeviceSynchronize();       // calls still in flight write to the arenas and to the pinned words freed below
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    c->enc_ws.release(); c->enc_stage.release(); c->dec_ws.release(); c->insp_ws.release(); c->dec_scan.release(); c->io_a.release(); c->io_b.release(); c->io_c.release();
+    c->enc_ws.release(); c->enc_stage.release(); c->dec_ws.release(); c->insp_ws.release(); c->cmp_ws.release(); c->ver_stage.release(); c->dec_scan.release(); c->io_a.release(); c->io_b.release(); c->io_c.release();
     if (c->host_word) (void)hipHostFree(c->host_word);
     if (c->pin_buf) (void)hipHostFree(c->pin_buf);
     if (c->enc_pin_buf) (void)hipHostFree(c->enc_pin_buf);
+    if (c->cmp_pin_buf) (void)hipHostFree(c->cmp_pin_buf);
     if (c->enc_pin_ev) (void)hipEventDestroy(c->enc_pin_ev);
     delete c;
 }
@@ -344,7 +350,7 @@ extern "C" const char* qoimi_kernel_name(int i) {
     static const char* names[kT_count] = {"", "enc_slab_summary", "enc_scan_groups", "enc_scan_images", "enc_slabs", "enc_slabs_generic", "enc_offsets", "enc_compact",
         "dec_parse", "dec_chain_parse", "dec_transcode", "dec_chain_slots", "dec_summarize", "dec_chain_state",
         "dec_segments", "dec_prepare_restart", "dec_fill", "dec_expand_runs", "pack_offsets", "pack_copy",
-        "inspect_maps", "inspect_scan", "inspect_count", "inspect_reduce", "pack_offsets_append", "pack_copy_append", "encode_total", "decode_total"};
+        "inspect_maps", "inspect_scan", "inspect_count", "inspect_reduce", "pack_offsets_append", "pack_copy_append", "encode_total", "decode_total", "cmp_pixels", "cmp_first"};
     return (i >= 0 && i < kT_count) ? names[i] : "";
 }
 
@@ -356,9 +362,10 @@ extern "C" int qoimi_set_encode_small_call_order(qoimi_ctx* c, int by_workgroup_
     return QOIMI_OK;
 }
 
-// device memory the context holds: [0] encode workspace (and the staging of qoimi_encode_packed), [1] decode workspace, [2] staging of the host-pointer entry points
+// device memory the context holds: [0] encode workspace (and the staging of qoimi_encode_packed), [1] decode workspace (and the tables of
+// qoimi_inspect_streams, the tables and the staging of qoimi_compare_images / qoimi_verify_images), [2] staging of the host-pointer entry points
 extern "C" void qoimi_workspace_bytes(qoimi_ctx* c, size_t out[3]) {
-    out[0] = c ? c->enc_ws.cap + c->enc_stage.cap : 0; out[1] = c ? c->dec_ws.cap + c->insp_ws.cap : 0;
+    out[0] = c ? c->enc_ws.cap + c->enc_stage.cap : 0; out[1] = c ? c->dec_ws.cap + c->insp_ws.cap + c->cmp_ws.cap + c->ver_stage.cap : 0;
     out[2] = c ? c->io_a.cap + c->io_b.cap + c->io_c.cap : 0;
 }
 
@@ -1503,6 +1510,199 @@ extern "C" int qoimi_inspect_streams(qoimi_ctx* c, const void* d_streams, const 
         if (info.flags != 0 && flagged < 0) flagged = (int)i;
     }
     if (first_flagged) *first_flagged = flagged;
+    return QOIMI_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// images against images, streams against their pixels (qoi_compare.hip)
+// ------------------------------------------------------------------------------------
+static_assert(sizeof(qoimi_image_diff) == sizeof(CmpDiff) && offsetof(qoimi_image_diff, first) == 8 && offsetof(qoimi_image_diff, want) == 16 &&
+              offsetof(qoimi_image_diff, got) == 20 && offsetof(qoimi_image_diff, flags) == 24 && offsetof(qoimi_image_diff, reserved) == 28,
+              "qoimi_image_diff is what cmp_pixels and cmp_first write");
+static_assert(QOIMI_DIFF_PIXELS == 1, "cmp_first writes the flag as a number");
+
+static int cmp_pin_reserve(qoimi_ctx* c, size_t bytes) {
+    if (bytes <= c->cmp_pin_cap) return QOIMI_OK;
+    if (c->cmp_pin_buf) (void)hipHostFree(c->cmp_pin_buf);
+    c->cmp_pin_buf = nullptr; c->cmp_pin_cap = 0;
+    HIP_TRY(hipHostMalloc(&c->cmp_pin_buf, bytes + 4096));
+    c->cmp_pin_cap = bytes + 4096;
+    return QOIMI_OK;
+}
+
+static inline size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
+
+// Fills entry `e` for an image of npx pixels and returns the tiles it takes.
+static uint32_t cmp_entry(CmpImage* e, size_t a_off, size_t b_off, size_t npx, uint32_t first_tile, unsigned ca, unsigned cb, unsigned ra, unsigned rb, uint32_t index) {
+    e->a_off = (u64)a_off; e->b_off = (u64)b_off; e->npx = (uint32_t)npx; e->first_tile = first_tile;
+    e->chan = ca | (cb << 8) | (ra << 16) | (rb << 24); e->index = index;
+    return (uint32_t)((npx + kCmpTilePx - 1u) / kCmpTilePx);
+}
+
+// The two kernels over table entries [from, from + m) of the device table (their tiles begin at 0).  With per-kernel timing on, the stream is
+// waited for and the events are folded at once: the interval of a launch that follows must not begin at this one's first event.
+static int compare_launch(qoimi_ctx* c, const void* d_a, const void* d_b, const CmpImage* d_tab, uint32_t m, uint32_t tiles, CmpDiff* d_diffs, hipStream_t st) {
+    if (c->timer.n > KernelTimer::kMax - 32) { HIP_TRY(hipStreamSynchronize(st)); timer_collect(c); }
+    const uint32_t most = (uint32_t)c->n_cus * 8u;
+    launch_compare((const uint8_t*)d_a, (const uint8_t*)d_b, d_tab, m, tiles, d_diffs, tiles < most ? tiles : most, st, &c->timer);
+    HIP_TRY(hipGetLastError());
+    if (c->timer.on) { HIP_TRY(hipStreamSynchronize(st)); timer_collect(c); }
+    return QOIMI_OK;
+}
+
+extern "C" int qoimi_compare_images(qoimi_ctx* c, const void* d_a, const size_t* a_offsets, int a_channels,
+                                    const void* d_b, const size_t* b_offsets, int b_channels,
+                                    const qoi_desc* descs, int n_images, qoimi_image_diff* diffs_out, int* first_diff, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves diffs_out as it was)
+    if (!c || !d_a || !d_b || !a_offsets || !b_offsets || !descs || !diffs_out || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if ((a_channels != 0 && a_channels != 3 && a_channels != 4) || (b_channels != 0 && b_channels != 3 && b_channels != 4))
+        return fail(QOIMI_E_ARG, "a_channels / b_channels must be 0, 3 or 4");
+    const size_t n = (size_t)n_images;
+    uint64_t tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:364-372 rules)");
+        tiles += ((uint64_t)descs[i].width * descs[i].height + kCmpTilePx - 1u) / kCmpTilePx;
+    }
+    if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of pixels in one call");
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
+    // pinned staging: [image table][results as they start] go to the device in one copy, [results] come back
+    const size_t tab_bytes = up256(n * sizeof(CmpImage)), res_bytes = up256(n * sizeof(CmpDiff));
+    { const int rc = cmp_pin_reserve(c, tab_bytes + 2u * res_bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = c->cmp_ws.reserve(tab_bytes + res_bytes); if (rc != QOIMI_OK) return rc; }
+    uint8_t* pin = (uint8_t*)c->cmp_pin_buf;
+    CmpImage* h_tab = (CmpImage*)pin;
+    CmpDiff* h_init = (CmpDiff*)(pin + tab_bytes);
+    CmpDiff* h_res = (CmpDiff*)(pin + tab_bytes + res_bytes);
+    uint32_t t = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const unsigned ca = a_channels ? (unsigned)a_channels : descs[i].channels, cb = b_channels ? (unsigned)b_channels : descs[i].channels;
+        t += cmp_entry(&h_tab[i], a_offsets[i], b_offsets[i], (size_t)descs[i].width * descs[i].height, t, ca, cb, ca, cb, (uint32_t)i);
+        memset(&h_init[i], 0, sizeof(CmpDiff));
+        h_init[i].first = ~0ull;
+    }
+    uint8_t* dev = (uint8_t*)c->cmp_ws.base;
+    HIP_TRY(hipMemcpyAsync(dev, pin, tab_bytes + n * sizeof(CmpDiff), hipMemcpyHostToDevice, st));
+    { const int rc = compare_launch(c, d_a, d_b, (const CmpImage*)dev, (uint32_t)n, t, (CmpDiff*)(dev + tab_bytes), st); if (rc != QOIMI_OK) return rc; }
+    HIP_TRY(hipMemcpyAsync(h_res, dev + tab_bytes, n * sizeof(CmpDiff), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int lowest = -1;
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(&diffs_out[i], &h_res[i], sizeof(qoimi_image_diff));
+        if (h_res[i].flags != 0u && lowest < 0) lowest = (int)i;
+    }
+    if (first_diff) *first_diff = lowest;
+    return QOIMI_OK;
+}
+
+// An arena of exactly what is asked for plus a page (the staging of qoimi_verify_images: the caller states its size).
+static int reserve_exact(Arena& a, size_t bytes) {
+    if (bytes <= a.cap) return QOIMI_OK;
+    a.release();
+    HIP_TRY(hipMalloc(&a.base, bytes + 4096u));
+    a.cap = bytes + 4096u; ++a.gen;
+    return QOIMI_OK;
+}
+
+// Streams against their pixels: every sub-batch of the plan is one call of the decoder as it is into the staging arena (the images whose
+// header does not match their descriptor left out), then the compare kernels on the caller's stream - the caller's pixels side A, the staging
+// side B; the next sub-batch's decoder is ordered behind them by the stream.  The results stay on the device until the last one is done.
+extern "C" int qoimi_verify_images(qoimi_ctx* c, const void* d_pixels, const size_t* pixel_offsets, const qoi_desc* descs, int n_images,
+                                   const void* d_streams, const size_t* stream_offsets, const int* sizes, size_t staging_bytes,
+                                   qoimi_image_diff* diffs_out, int* first_diff, void* stream) {
+    if (!c || !d_pixels || !pixel_offsets || !descs || !d_streams || !stream_offsets || !sizes || !diffs_out || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    const size_t n = (size_t)n_images;
+    unsigned och = 3;                                          // ONE output channel count for the staging of the whole call
+    uint64_t all_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (sizes[i] < 0) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + ": negative size");
+        if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:364-372 rules)");
+        if (descs[i].channels == 4) och = 4;
+        all_tiles += ((uint64_t)descs[i].width * descs[i].height + kCmpTilePx - 1u) / kCmpTilePx;
+    }
+    if (all_tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of pixels in one call");
+    // the plan: a function of descs and staging_bytes alone (qoi_amd/packplan.py: plan over width * height * och)
+    std::vector<size_t> slots(n), at(n);
+    for (size_t i = 0; i < n; ++i) slots[i] = up256((size_t)descs[i].width * descs[i].height * och);
+    const std::vector<int> firsts = pack_plan(slots, staging_bytes ? staging_bytes : kPackStagingDefault);
+    size_t need = 0;                                           // the largest sub-batch
+    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
+        size_t used = 0;
+        for (int i = firsts[k]; i < firsts[k + 1]; ++i) { at[(size_t)i] = used; used += slots[(size_t)i]; }
+        if (used > need) need = used;
+    }
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
+    // pinned staging: [image table][results as they start] go to the device in one copy, [results] come back; [offsets][header bytes] are
+    // read and written in place by gather_headers
+    const size_t tab_bytes = up256(n * sizeof(CmpImage)), res_bytes = up256(n * sizeof(CmpDiff)), off_bytes = up256(n * sizeof(u64));
+    { const int rc = cmp_pin_reserve(c, tab_bytes + 2u * res_bytes + off_bytes + n * 16u); if (rc != QOIMI_OK) return rc; }
+    { const int rc = c->cmp_ws.reserve(tab_bytes + res_bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = reserve_exact(c->ver_stage, need); if (rc != QOIMI_OK) return rc; }
+    uint8_t* pin = (uint8_t*)c->cmp_pin_buf;
+    CmpImage* h_tab = (CmpImage*)pin;
+    CmpDiff* h_init = (CmpDiff*)(pin + tab_bytes);
+    CmpDiff* h_res = (CmpDiff*)(pin + tab_bytes + res_bytes);
+    u64* h_off = (u64*)(pin + tab_bytes + 2u * res_bytes);
+    const uint8_t* h_hdr = pin + tab_bytes + 2u * res_bytes + off_bytes;
+    // 1. the headers: a stream that is too short, fails the rules of qoimi_read_descs or says something else than descs[i] is not decoded
+    const int kMin = kHeaderBytes + kTrailerBytes;
+    for (size_t i = 0; i < n; ++i) h_off[i] = sizes[i] >= kMin ? (u64)stream_offsets[i] : ~0ull;
+    launch_gather_headers((const uint8_t*)d_streams, h_off, (uint32_t)n, (uint32_t*)h_hdr, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<uint8_t> header_bad(n);
+    for (size_t i = 0; i < n; ++i) {
+        qoi_desc d;
+        header_bad[i] = !(sizes[i] >= kMin && parse_header(h_hdr + 16u * i, &d) && d.width == descs[i].width && d.height == descs[i].height &&
+                          d.channels == descs[i].channels && d.colorspace == descs[i].colorspace);
+    }
+    // 2. one table for the whole call: the entries of a sub-batch's decoded images stand together, their tiles begin at 0
+    struct Sub { uint32_t entry, m, tiles; };
+    std::vector<Sub> subs(firsts.size() - 1u);
+    uint32_t entries = 0;
+    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
+        Sub& s = subs[k];
+        s.entry = entries; s.tiles = 0;
+        for (int i = firsts[k]; i < firsts[k + 1]; ++i) {
+            if (header_bad[(size_t)i]) continue;
+            const unsigned ch = descs[i].channels;             // a_channels = 0; side B holds och bytes per pixel and stands for a decode at ch
+            s.tiles += cmp_entry(&h_tab[entries++], pixel_offsets[i], at[(size_t)i], (size_t)descs[i].width * descs[i].height, s.tiles, ch, och, ch, ch, (uint32_t)i);
+        }
+        s.m = entries - s.entry;
+    }
+    for (size_t i = 0; i < n; ++i) { memset(&h_init[i], 0, sizeof(CmpDiff)); h_init[i].first = ~0ull; }
+    uint8_t* dev = (uint8_t*)c->cmp_ws.base;
+    CmpDiff* d_diffs = (CmpDiff*)(dev + tab_bytes);
+    HIP_TRY(hipMemcpyAsync(dev, pin, tab_bytes + n * sizeof(CmpDiff), hipMemcpyHostToDevice, st));
+    // 3. sub-batch by sub-batch
+    std::vector<size_t> so, po; std::vector<int> sz; std::vector<qoi_desc> ds;
+    for (size_t k = 0; k < subs.size(); ++k) {
+        if (subs[k].m == 0u) continue;
+        so.clear(); po.clear(); sz.clear(); ds.clear();
+        for (int i = firsts[k]; i < firsts[k + 1]; ++i) {
+            if (header_bad[(size_t)i]) continue;
+            so.push_back(stream_offsets[i]); po.push_back(at[(size_t)i]); sz.push_back(sizes[i]); ds.push_back(descs[i]);
+        }
+        const int rc = qoimi_decode_images(c, d_streams, so.data(), sz.data(), ds.data(), (int)subs[k].m, (int)och, c->ver_stage.base, po.data(), stream);
+        if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
+        const int rc2 = compare_launch(c, d_pixels, c->ver_stage.base, (const CmpImage*)dev + subs[k].entry, subs[k].m, subs[k].tiles, d_diffs, st);
+        if (rc2 != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc2; }
+    }
+    // 4. one read-back
+    HIP_TRY(hipMemcpyAsync(h_res, d_diffs, n * sizeof(CmpDiff), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int lowest = -1;
+    for (size_t i = 0; i < n; ++i) {
+        if (header_bad[i]) {
+            memset(&diffs_out[i], 0, sizeof(qoimi_image_diff));
+            diffs_out[i].first = ~0ull; diffs_out[i].flags = QOIMI_DIFF_HEADER;
+        } else memcpy(&diffs_out[i], &h_res[i], sizeof(qoimi_image_diff));
+        if (diffs_out[i].flags != 0u && lowest < 0) lowest = (int)i;
+    }
+    if (first_diff) *first_diff = lowest;
     return QOIMI_OK;
 }
 

@@ -20,6 +20,7 @@ enum KernelTag { kT_begin = 0,
                  kT_inspect_maps, kT_inspect_scan, kT_inspect_count, kT_inspect_reduce,
                  kT_pack_offsets_append, kT_pack_copy_append,
                  kT_enc_total, kT_dec_total,    // a whole qoimi_encode_batch / qoimi_decode_batch on the caller's stream (kernels of a call may overlap)
+                 kT_cmp_pixels, kT_cmp_first,   // (behind the totals: the indices in front of them are what callers of qoimi_kernel_name know)
                  kT_count };
 struct KernelTimer {
     static constexpr int kMax = 512;

@@ -1,0 +1,349 @@
+"""qoimi_verify_images on the GPU (-m gpu): do the streams of a pack decode back to exactly the pixels they were made from?  The expectation
+is the definition: the oracle decodes the stream as it is given (damaged, cut, with a foreign chunk) to the image's channel count, and
+qoi_amd/imagediff.py: diff compares that with the source pixels.  Sub-batch boundaries are forced through staging_bytes by the plan of
+qoi_amd/packplan.py (the launch count of cmp_pixels says that the call really ran that many sub-batches)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from qoi_amd.imagediff import DIFF_DTYPE, DIFF_HEADER, DIFF_PIXELS, NONE, diff
+from test_gpu_encode_packed import KINDS, Batch, dev, filled
+
+pytestmark = pytest.mark.gpu
+E_ARG = -1
+MIXED_SHAPES = [(1, 1, 4), (1, 97, 4), (131, 1, 3), (37, 23, 3), (257, 9, 4), (64, 48, 3), (333, 7, 4), (130, 70, 4), (130, 70, 3)]
+
+
+@pytest.fixture(scope="module")
+def api():
+    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
+    from qoi_amd import api as _api
+    assert torch.cuda.is_available()
+    return _api
+
+
+@pytest.fixture(scope="module")
+def ctx(api):
+    c = api.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def oracle(ref, port):
+    return ref or port
+
+
+@pytest.fixture(scope="module")
+def mixed(api, oracle):
+    """the mixed batch of tests/test_gpu_encode_packed.py: 3 and 4 channels, all content classes"""
+    return Batch(api, oracle, MIXED_SHAPES, [KINDS[(i + 2) % 5] for i in range(len(MIXED_SHAPES))])
+
+
+@pytest.fixture(scope="module")
+def all_rgb(api, oracle):
+    shapes = [(w, h, 3) for (w, h, _) in MIXED_SHAPES[:7]]
+    return Batch(api, oracle, shapes, [KINDS[i % 5] for i in range(len(shapes))])
+
+
+@pytest.fixture(scope="module")
+def equal(api, oracle):
+    return Batch(api, oracle, [(64, 48, 4)] * 13, [KINDS[i % 5] for i in range(13)])
+
+
+def make_pack(ctx, b, align):
+    """encode_images_packed -> (pack tensor, stream offsets, sizes); the streams are the oracle's (tests/test_gpu_encode_packed.py)"""
+    import torch
+    cap = sum(b.bounds) + 256 * b.n
+    packed = filled(cap, 0)
+    off = torch.zeros(b.n + 1, dtype=torch.int64, device="cuda")
+    lens = torch.zeros(b.n, dtype=torch.int32, device="cuda")
+    so, sizes = ctx.encode_images_packed(b.d_px.data_ptr(), b.pix_off, b.descs, align, packed.data_ptr(), cap, off.data_ptr(), lens.data_ptr())
+    assert sizes.tolist() == b.lens
+    return packed, [int(x) for x in so[:b.n]], [int(x) for x in sizes]
+
+
+def staged_bounds(b):
+    och = 4 if any(ch == 4 for (_, _, ch) in b.shapes) else 3
+    return [w * h * och for (w, h, _) in b.shapes]
+
+
+def expected(oracle, b, streams, sizes, header_bad=()):
+    """The definition, image by image: streams[i][:sizes[i]] through the oracle at the image's channel count, then diff against the source."""
+    out = np.zeros(b.n, dtype=DIFF_DTYPE)
+    first = -1
+    for i, (w, h, ch) in enumerate(b.shapes):
+        if i in header_bad:
+            out[i] = (0, NONE, 0, 0, DIFF_HEADER, 0)
+        else:
+            got, _ = oracle.decode(bytes(streams[i][:sizes[i]]), ch)
+            assert got is not None, i
+            m, f, want, have = diff(b.px[i], got, w * h, ch, ch)
+            out[i] = (m, f, want, have, DIFF_PIXELS if m else 0, 0)
+        if out[i]["flags"] and first < 0:
+            first = i
+    return out, first
+
+
+def verify(ctx, b, packed, so, sizes, staging, count_subs=True):
+    from qoi_amd.packplan import plan
+    ctx.set_profiling(True)
+    got, first = ctx.verify_images(b.d_px.data_ptr(), b.pix_off, b.descs, packed.data_ptr(), so, sizes, staging)
+    prof = ctx.get_profile(0)
+    ctx.set_profiling(False)
+    if count_subs:
+        subs = plan(staged_bounds(b), staging if staging else 1 << 30)
+        assert prof["cmp_pixels"][1] == prof["cmp_first"][1] == len(subs), (staging, prof["cmp_pixels"], subs)
+    return got, first
+
+
+def assert_same(got, first, want, want_first, what):
+    for i in range(len(want)):
+        assert got[i] == want[i], (what, i, got[i], want[i])
+    assert first == want_first, (what, first, want_first)
+
+
+def assert_clean(got, first, what):
+    assert first == -1, what
+    assert not got["flags"].any() and not got["mismatched"].any() and (got["first"] == NONE).all(), what
+    assert not got["want"].any() and not got["got"].any() and not got["reserved"].any(), what
+
+
+# ------------------------------------------------------------------ 1: clean round trips
+@pytest.mark.parametrize("align", [1, 64])
+def test_clean_mixed(ctx, mixed, align):
+    packed, so, sizes = make_pack(ctx, mixed, align)
+    px_before, pack_before = mixed.d_px.cpu().numpy(), packed.cpu().numpy()
+    for staging in (0, 20000):
+        got, first = verify(ctx, mixed, packed, so, sizes, staging)
+        assert_clean(got, first, (align, staging))
+    assert np.array_equal(mixed.d_px.cpu().numpy(), px_before) and np.array_equal(packed.cpu().numpy(), pack_before)
+
+
+def test_clean_all_rgb(ctx, all_rgb):
+    packed, so, sizes = make_pack(ctx, all_rgb, 1)
+    assert staged_bounds(all_rgb)[3] == 37 * 23 * 3                   # the staging of an all-RGB call holds 3 bytes per pixel
+    for staging in (0, 1, 9000):
+        got, first = verify(ctx, all_rgb, packed, so, sizes, staging)
+        assert_clean(got, first, staging)
+
+
+def test_clean_strided_streams(ctx, equal):
+    """thirteen equal RGBA frames through encode_batch: the streams lie strided, not packed"""
+    import torch
+    b = equal
+    stride = b.bounds[0] + 3
+    streams = filled(b.n * stride, 0x3C)
+    lens = torch.zeros(b.n, dtype=torch.int32, device="cuda")
+    ctx.encode_batch(b.d_px.data_ptr(), b.px[0].size, b.descs[0], b.n, streams.data_ptr(), stride, lens.data_ptr(), 0)
+    ctx.encode_status(0)
+    sizes = lens.cpu().numpy().tolist()
+    assert sizes == b.lens
+    got, first = verify(ctx, b, streams, [i * stride for i in range(b.n)], sizes, 0)
+    assert_clean(got, first, "strided")
+
+
+# ------------------------------------------------------------------ 2: sub-batching
+def test_sub_batching(ctx, oracle, equal, mixed):
+    from qoi_amd.packplan import plan, slot
+    results = []
+    packed, so, sizes = make_pack(ctx, equal, 4)
+    host = packed.cpu().numpy().copy()
+    k = so[5] + 14 + 40                                                # stream 5 is noise: a byte inside its chunks
+    host[k] ^= 0x10
+    host[so[9] + 20] ^= 0xFF
+    damaged = dev(host)
+    streams = [host[o:o + n] for o, n in zip(so, sizes)]
+    want, want_first = expected(oracle, equal, streams, sizes)
+    assert want["mismatched"][5] > 0 and want_first == 5
+    one = slot(64 * 48 * 4)
+    for staging, subs in ((1, 13), (2 * one, 7), (13 * one, 1), (0, 1)):
+        assert len(plan(staged_bounds(equal), staging if staging else 1 << 30)) == subs
+        got, first = verify(ctx, equal, damaged, so, sizes, staging)
+        assert_same(got, first, want, want_first, staging)
+        results.append(got)
+    assert all(np.array_equal(r, results[0]) for r in results)
+    # mixed shapes: sub-batches of different counts, one image's slot above the request, the images in another order than the pack's
+    packed, so, sizes = make_pack(ctx, mixed, 1)
+    streams = [packed.cpu().numpy()[o:o + n] for o, n in zip(so, sizes)]
+    perm = [4, 8, 0, 7, 2, 6, 1, 5, 3]
+    p = Batch.__new__(Batch)
+    p.n, p.shapes, p.d_px = mixed.n, [mixed.shapes[i] for i in perm], mixed.d_px
+    p.px, p.descs, p.pix_off = [mixed.px[i] for i in perm], [mixed.descs[i] for i in perm], [mixed.pix_off[i] for i in perm]
+    whole = sum(slot(x) for x in staged_bounds(p))
+    for staging in (1, 20000, whole, whole - 1, 0):
+        got, first = verify(ctx, p, packed, [so[i] for i in perm], [sizes[i] for i in perm], staging)
+        assert_clean(got, first, ("permuted", staging))
+    assert len(plan(staged_bounds(p), whole)) == 1 and len(plan(staged_bounds(p), whole - 1)) == 2
+
+
+# ------------------------------------------------------------------ 3: damage
+def rgb_chunk_near(stream, start):
+    """offset of the red byte of the first QOI_OP_RGB chunk at or behind byte `start` of the chunk walk (qoi.h:547-575 tag rules)"""
+    p = 14
+    while p < len(stream) - 8:
+        b = int(stream[p])
+        if b == 0xFE and p >= start:
+            return p + 1
+        p += 4 if b == 0xFE else 5 if b == 0xFF else 2 if b >> 6 == 2 else 1
+    raise AssertionError("no QOI_OP_RGB chunk")
+
+
+def test_damaged_streams(ctx, oracle, mixed):
+    packed, so, sizes = make_pack(ctx, mixed, 1)
+    clean = packed.cpu().numpy()
+    noise, photo, small_noise = 8, 5, 3
+    cases = {}
+    # a flipped byte inside a literal chunk of a noise image
+    host = clean.copy()
+    host[so[noise] + rgb_chunk_near(clean[so[noise]:so[noise] + sizes[noise]], sizes[noise] // 2)] ^= 0x40
+    cases["literal chunk"] = (host, list(sizes), noise)
+    # a flipped byte early in a photo image: what follows is decoded against another pixel
+    host = clean.copy()
+    host[so[photo] + 14 + 6] ^= 0x1F
+    cases["early byte"] = (host, list(sizes), photo)
+    # a size cut by 9, and down to 22 bytes: the decoder repeats the last pixel
+    cut9 = list(sizes)
+    cut9[noise] -= 9
+    cases["cut by 9"] = (clean, cut9, noise)
+    cut_all = list(sizes)
+    cut_all[small_noise] = 22
+    cases["cut to 22"] = (clean, cut_all, small_noise)
+    for name, (host, sz, victim) in cases.items():
+        streams = [host[o:o + n] for o, n in zip(so, sizes)]
+        want, want_first = expected(oracle, mixed, streams, sz)
+        assert want["mismatched"][victim] > 0, name
+        assert want_first == victim and int(want["flags"].astype(bool).sum()) == 1, name          # undamaged neighbours report 0
+        d = dev(host)
+        for staging in (0, 20000):
+            got, first = verify(ctx, mixed, d, so, sz, staging)
+            assert_same(got, first, want, want_first, (name, staging))
+        assert np.array_equal(d.cpu().numpy(), host), name
+    assert expected(oracle, mixed, [clean[o:o + n] for o, n in zip(so, sizes)], cases["early byte"][1])[0]["mismatched"].sum() == 0
+
+
+# ------------------------------------------------------------------ 4: headers
+def test_headers(ctx, oracle, mixed):
+    packed, so, sizes = make_pack(ctx, mixed, 1)
+    host = packed.cpu().numpy().copy()
+    sz = list(sizes)
+    sz[1] = 21                                                         # shorter than 22 bytes
+    host[so[2]] = ord("Q")                                             # bad magic
+    host[so[4] + 7] ^= 1                                               # width changed in the stream
+    host[so[5] + 12] = 4                                               # channels 3 -> 4
+    host[so[6] + 12] = 3                                               # channels 4 -> 3
+    host[so[7] + 13] = 1                                               # colorspace differs from descs[i]
+    host[so[8] + rgb_chunk_near(host[so[8]:so[8] + sizes[8]], 200)] ^= 0x08      # ... and a neighbour with damaged chunks
+    bad = {1, 2, 4, 5, 6, 7}
+    streams = [host[o:o + n] for o, n in zip(so, sizes)]
+    want, want_first = expected(oracle, mixed, streams, sz, header_bad=bad)
+    assert want_first == 1 and want["flags"].tolist() == [0, 2, 2, 0, 2, 2, 2, 2, 1] and want["mismatched"][8] > 0
+    d = dev(host)
+    for staging in (0, 1, 20000):
+        got, first = verify(ctx, mixed, d, so, sz, staging, count_subs=False)
+        assert_same(got, first, want, want_first, staging)
+    for i in bad:
+        assert (got[i]["mismatched"], got[i]["first"], got[i]["want"], got[i]["got"], got[i]["reserved"]) == (0, NONE, 0, 0, 0)
+    # a header that passes no rule at all (width 0), alone in its call: nothing is decoded, nothing is compared
+    host2 = packed.cpu().numpy().copy()
+    host2[so[3] + 4:so[3] + 8] = 0
+    ctx.set_profiling(True)
+    d2 = dev(host2)
+    got, first = ctx.verify_images(mixed.d_px.data_ptr(), [mixed.pix_off[3]], [mixed.descs[3]], d2.data_ptr(), [so[3]], [sizes[3]])
+    prof = ctx.get_profile(0)
+    ctx.set_profiling(False)
+    assert first == 0 and got["flags"].tolist() == [DIFF_HEADER] and prof["cmp_pixels"][1] == 0
+
+
+# ------------------------------------------------------------------ 5: an RGBA chunk in the stream of a 3-channel image
+def test_rgba_chunk_in_rgb_stream(api, ctx, oracle, equal):
+    """4 x 2, 3 channels; the stream sets an alpha of 77 that a decode to 3 channels never shows - alone (the staging holds 3 bytes per
+    pixel) and beside a 4-channel image (the staging holds 4: got still reports the 3-channel decode, alpha 0xFF)"""
+    header = b"qoif" + (4).to_bytes(4, "big") + (2).to_bytes(4, "big") + bytes([3, 0])
+    stream = header + bytes([0xFF, 10, 20, 30, 77, 0xC0 | 2, 0xFE, 1, 2, 3, 0xC0 | 2]) + bytes([0, 0, 0, 0, 0, 0, 0, 1])
+    px = np.array([[10, 20, 30]] * 4 + [[1, 2, 3]] * 4, dtype=np.uint8)
+    ref_px, _ = oracle.decode(stream, 3)
+    assert np.array_equal(ref_px.reshape(-1, 3), px)
+    off = px.copy()
+    off[5, 1] = 99
+    other = equal.px[3]                                                # a 64 x 48 RGBA frame and its stream
+    for source, clean in ((px, True), (off, False)):
+        m, f, want, have = diff(source, ref_px, 8, 3, 3)
+        assert (m == 0) == clean and (clean or (f, want >> 24, have >> 24) == (5, 0xFF, 0xFF))
+        d_px = dev(np.concatenate([np.zeros(5, np.uint8), source.reshape(-1), other]))
+        d_st = dev(np.concatenate([np.zeros(3, np.uint8), np.frombuffer(stream, np.uint8), np.frombuffer(equal.want[3], np.uint8)]))
+        d3, d4 = api.QoiDesc(4, 2, 3, 0), equal.descs[3]
+        got, first = ctx.verify_images(d_px.data_ptr(), [5], [d3], d_st.data_ptr(), [3], [len(stream)])
+        assert got[0] == np.array((m, f, want, have, DIFF_PIXELS if m else 0, 0), dtype=DIFF_DTYPE) and first == (-1 if clean else 0)
+        got, first = ctx.verify_images(d_px.data_ptr(), [5 + 24, 5], [d4, d3], d_st.data_ptr(), [3 + len(stream), 3], [len(equal.want[3]), len(stream)])
+        assert got[1] == np.array((m, f, want, have, DIFF_PIXELS if m else 0, 0), dtype=DIFF_DTYPE) and first == (-1 if clean else 1)
+        assert got[0]["flags"] == 0
+
+
+# ------------------------------------------------------------------ 6: the context afterwards, rejections
+def test_context_afterwards_and_rejections(api, ctx, mixed):
+    import torch
+    b = mixed
+    packed, so, sizes = make_pack(ctx, b, 1)
+    want_pack = packed.cpu().numpy()
+    got, first = verify(ctx, b, packed, so, sizes, 20000)
+    assert_clean(got, first, "before")
+    # a plain encode_images and a plain decode_images of the batch on the same context: byte- and bit-exact
+    stream_off = [int(x) for x in np.cumsum([0] + [x + 5 for x in b.bounds[:-1]])]
+    streams = filled(stream_off[-1] + b.bounds[-1] + 64, 0)
+    lens = torch.zeros(b.n, dtype=torch.int32, device="cuda")
+    ctx.encode_images(b.d_px.data_ptr(), b.pix_off, b.descs, streams.data_ptr(), stream_off, lens.data_ptr(), 0)
+    ctx.encode_status(0)
+    assert lens.cpu().numpy().tolist() == b.lens
+    host = streams.cpu().numpy()
+    for i, s in enumerate(b.want):
+        assert host[stream_off[i]:stream_off[i] + len(s)].tobytes() == s, i
+    for ch in (3, 4):
+        idx = [i for i, (_, _, c) in enumerate(b.shapes) if c == ch]
+        out = filled(sum(b.px[i].size for i in idx) + 64, 0xCD)
+        po = [int(x) for x in np.cumsum([0] + [b.px[i].size for i in idx[:-1]])]
+        ctx.decode_images(packed.data_ptr(), [so[i] for i in idx], [sizes[i] for i in idx], [b.descs[i] for i in idx], 0, out.data_ptr(), po)
+        res = out.cpu().numpy()
+        for k, i in enumerate(idx):
+            assert np.array_equal(res[po[k]:po[k] + b.px[i].size], b.px[i]), i
+    assert np.array_equal(packed.cpu().numpy(), want_pack)
+    # rejections with a live context: nothing is launched, the output keeps its bytes
+    lib = api.load_library()
+    n = b.n
+    po_c, so_c = (ctypes.c_size_t * n)(*b.pix_off), (ctypes.c_size_t * n)(*so)
+    ds, sz = (api.QoiDesc * n)(*b.descs), (ctypes.c_int * n)(*sizes)
+    neg = (ctypes.c_int * n)(*(sizes[:4] + [-1] + sizes[5:]))
+    bad_ds = (api.QoiDesc * n)(*(b.descs[:6] + [api.QoiDesc(333, 7, 2, 0)] + b.descs[7:]))
+    out = (api.ImageDiff * n)()
+    ctypes.memset(out, 0x5A, ctypes.sizeof(out))
+    fd = ctypes.c_int(7)
+    X, P = b.d_px.data_ptr(), packed.data_ptr()
+    assert lib.qoimi_verify_images(ctx._h, X, po_c, ds, n, P, so_c, neg, 0, out, ctypes.byref(fd), None) == E_ARG
+    assert lib.qoimi_verify_images(ctx._h, X, po_c, bad_ds, n, P, so_c, sz, 0, out, ctypes.byref(fd), None) == E_ARG
+    assert bytes(out) == b"\x5A" * ctypes.sizeof(out) and fd.value == 7
+    assert lib.qoimi_verify_images(ctx._h, X, po_c, ds, n, P, so_c, sz, 0, out, None, None) == 0            # first_diff may be NULL
+    assert [d.flags for d in out] == [0] * n
+
+
+def test_staging_bounds_the_memory(api, oracle):
+    """16 RGBA images of 256 x 256: through 2 slots the context holds 14 slots less than through one sub-batch of all 16 (the decoder's
+    own workspace is smaller too), and the staging arena is counted in the decode workspace"""
+    from qoi_amd.packplan import slot
+    n, w, h = 16, 256, 256
+    b = Batch(api, oracle, [(w, h, 4)] * n, ["photo"] * n)
+    S = slot(w * h * 4)
+    small, big = api.Context(0), api.Context(0)
+    try:
+        packed, so, sizes = make_pack(small, b, 1)
+        before = small.workspace_bytes()["decode"]
+        got, first = verify(small, b, packed, so, sizes, 2 * S)
+        assert_clean(got, first, "2 slots")
+        held_small = small.workspace_bytes()["decode"] - before
+        got, first = verify(big, b, packed, so, sizes, 0)
+        assert_clean(got, first, "one sub-batch")
+        held_big = big.workspace_bytes()["decode"]
+        assert held_small >= 2 * S, (held_small, S)
+        assert held_big >= held_small + 14 * S, (held_big, held_small, S)
+    finally:
+        small.close(); big.close()
