@@ -363,6 +363,48 @@ int qoimi_verify_images(qoimi_ctx *ctx,
                         size_t staging_bytes,
                         qoimi_image_diff *diffs_out /* host */, int *first_diff /* host, may be NULL */, void *stream);
 
+/* Every image of a pack at 1/f of its size, without the caller ever owning the full-size images.  QOI cannot be decoded at reduced size (every
+ * pixel depends on the one before), so the streams are decoded in full - into a staging arena of the context, sub-batch by sub-batch - and each
+ * sub-batch is reduced on the device by an exact integer box filter.
+ * The result (normative; qoi_amd/thumbs.py: thumbnail states it in Python): decode stream i exactly as qoimi_decode_images does (same leniency,
+ * bit-exact for EVERY input stream) to och = channels, or descs[i].channels when channels is 0 (the same for all images of the call), which gives
+ * D of w x h pixels.  With f = factors[i], tw = ceil(w / f), th = ceil(h / f), output pixel (X, Y) covers the source block x in [X*f, min(w,
+ * X*f+f)), y in [Y*f, min(h, Y*f+f)) of cnt pixels; S_c is the sum of channel c over the block.  Divisions are integer divisions (floor).
+ *   QOIMI_THUMB_PLAIN           every output channel is (S_c + cnt/2) / cnt - a half rounds up
+ *   QOIMI_THUMB_ALPHA_WEIGHTED  where och == 4: A = S_a, output alpha is (A + cnt/2) / cnt; if A > 0, r, g and b are (sum(c_k * a_k) + A/2) / A
+ *                               over the block's pixels k, if A == 0 they are the PLAIN value.  With och == 3 this mode is PLAIN.
+ * f == 1 reproduces the decode byte for byte in both modes.  Every sum fits in 32 bits (64 * 64 * 255 * 255 < 2^32).
+ *   stream_offsets, sizes, descs, channels  HOST arrays / value as for qoimi_decode_images
+ *   factors        HOST unsigned[n_images], each 1..64
+ *   thumb_offsets  HOST size_t[n_images]: thumbnail i is written tightly packed, tw * th * och bytes (qoimi_thumbnail_size), at d_thumbs +
+ *                  thumb_offsets[i].  ANY byte offsets in any order; not one byte beside a thumbnail is written; ranges must not overlap
+ *   staging_bytes  device memory the call may hold for decoded pixels (the arena qoimi_verify_images uses, counted in qoimi_workspace_bytes [1],
+ *                  allocated as the largest sub-batch of the call's plan plus a page, no slack).  0: 1 GiB.  The staging always holds 4 bytes per
+ *                  pixel (a 3-channel stream decodes with alpha 255, which a 3-channel thumbnail does not store).  The sub-batch plan
+ *                  (normative; qoi_amd/packplan.py: plan over width * height * 4): a slot is width * height * 4 rounded up to 256 bytes, images
+ *                  are taken in order, a sub-batch closes when the next slot would not fit in staging_bytes; a request smaller than one slot is
+ *                  raised to that slot, so every sub-batch holds at least one image.
+ * Every sub-batch is one qoimi_decode_images call as it is, at 4 output channels, then one launch of the reduction kernel on `stream`.
+ * SYNCHRONOUS: returns when every thumbnail is written.  The code of a decode sub-call that failed ends the call.  QOIMI_E_ARG for a NULL ctx,
+ * d_streams, stream_offsets, sizes, descs, factors, d_thumbs or thumb_offsets, n_images <= 0, sizes[i] < 22, a rejected descriptor, channels not
+ * 0 / 3 / 4, mixed output channel counts, a factor outside 1..64, a mode that is neither of the two, overlapping output ranges, a sub-batch
+ * of the plan with 2^31 - 1 or more tiles of 256 work items of the reduction kernel (an output pixel is 1 to 16 items; no staging a device can hold
+ * comes near it): reported before anything is launched, the caller's buffers are untouched.  The sub-batches count as decode calls of the context, as those of
+ * qoimi_verify_images do.  One call at a time per context, as everywhere. */
+enum { QOIMI_THUMB_PLAIN = 0, QOIMI_THUMB_ALPHA_WEIGHTED = 1 };
+int qoimi_decode_thumbnails(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                            const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                            const unsigned *factors /* host, n_images, each 1..64 */, int mode,
+                            void *d_thumbs, const size_t *thumb_offsets /* host */, size_t staging_bytes, void *stream);
+
+/* tw = ceil(width / factor), th = ceil(height / factor); returns tw * th * channels - the bytes of the thumbnail - or 0 if desc is rejected,
+ * factor is not in 1..64 or channels is not 3 / 4 (tw / th are then left alone).  Pure host arithmetic: no context, no GPU.  tw / th may be NULL. */
+size_t qoimi_thumbnail_size(const qoi_desc *desc, unsigned factor, int channels, unsigned *tw, unsigned *th);
+
+/* Of the context's last qoimi_decode_thumbnails call: [0] sub-batches decoded, [1] launches of the reduction kernel (it has no entry in
+ * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] 0. */
+void qoimi_thumbnail_stats(qoimi_ctx *ctx, long long out[4]);
+
 /* Fill device memory with synthetic RGBA frames frame_id = first_frame .. first_frame+n-1
  * (benchmark/test utility; same function of (kind, seed, frame, pixel) as synth.py). */
 int qoimi_synth_frames(qoimi_ctx *ctx, int kind, unsigned seed, unsigned first_frame,
@@ -378,7 +420,8 @@ int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
 
 /* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace (and the staging arena of
  * qoimi_encode_packed), [1] decode workspace
- * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images),
+ * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images
+ * and qoimi_decode_thumbnails, which share them),
  * [2] staging buffers of the host-pointer entry points (qoi_encode / qoi_decode of the calling thread's context). */
 void qoimi_workspace_bytes(qoimi_ctx *ctx, size_t out[3]);
 

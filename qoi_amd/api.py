@@ -39,6 +39,7 @@ EXPORTS = (
     "qoimi_decode_images", "qoimi_pack_streams", "qoimi_read_descs", "qoimi_inspect_streams",
     "qoimi_encode_packed", "qoimi_encode_images_packed",
     "qoimi_compare_images", "qoimi_verify_images",
+    "qoimi_decode_thumbnails", "qoimi_thumbnail_size", "qoimi_thumbnail_stats",
 )
 
 
@@ -146,6 +147,13 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_compare_images.argtypes = [vp, vp, szp, ci, vp, szp, ci, dp, ci, ctypes.POINTER(ImageDiff), ctypes.POINTER(ci), vp]
     lib.qoimi_verify_images.restype = ci
     lib.qoimi_verify_images.argtypes = [vp, vp, szp, dp, ci, vp, szp, ctypes.POINTER(ci), sz, ctypes.POINTER(ImageDiff), ctypes.POINTER(ci), vp]
+    up = ctypes.POINTER(ctypes.c_uint)
+    lib.qoimi_decode_thumbnails.restype = ci
+    lib.qoimi_decode_thumbnails.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, ci, up, ci, vp, szp, sz, vp]
+    lib.qoimi_thumbnail_size.restype = sz
+    lib.qoimi_thumbnail_size.argtypes = [dp, ctypes.c_uint, ci, up, up]
+    lib.qoimi_thumbnail_stats.restype = None
+    lib.qoimi_thumbnail_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     _lib = lib
     return lib
 
@@ -163,6 +171,16 @@ def last_error() -> str:
 
 def encode_bound(width: int, height: int, channels: int) -> int:
     return int(load_library().qoimi_encode_bound(ctypes.byref(QoiDesc(width, height, channels, 0))))
+
+
+def thumbnail_size(width: int, height: int, channels_in: int, factor: int, channels: int) -> Tuple[int, int, int]:
+    """``qoimi_thumbnail_size`` for an image of width x height x channels_in: (bytes, tw, th) of its thumbnail at `factor` with `channels`
+    (3 or 4) bytes per pixel; (0, 0, 0) where the C function returns 0."""
+    if not (0 <= factor < 2 ** 32 and 0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
+        return 0, 0, 0
+    tw, th = ctypes.c_uint(0), ctypes.c_uint(0)
+    n = int(load_library().qoimi_thumbnail_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), factor, channels, ctypes.byref(tw), ctypes.byref(th)))
+    return n, tw.value, th.value
 
 
 # ----------------------------------------------------------------------------------
@@ -418,6 +436,33 @@ class Context:
                     "qoimi_verify_images")
         return diffs, first.value
 
+    def decode_thumbnails(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                          factors, mode: int, d_thumbs: int, thumb_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
+        """Every image of a pack at 1/f of its size (``qoimi_decode_thumbnails``, synchronous, through bounded staging): thumbnail i is
+        written tightly packed at d_thumbs + thumb_offsets[i].  factors: one int for all images or one per image, each 1..64;
+        mode: ``thumbs.PLAIN`` or ``thumbs.ALPHA_WEIGHTED``; ``qoi_amd/thumbs.py: thumbnail`` states the result."""
+        n = len(sizes)
+        if isinstance(factors, (int, np.integer)):
+            factors = [int(factors)] * n
+        if len(descs) != n or len(stream_offsets) != n or len(thumb_offsets) != n or len(factors) != n:
+            raise QoiError("decode_thumbnails: one stream offset, size, descriptor, factor and thumbnail offset per image")
+        if any(not 0 <= int(f) < 2 ** 32 for f in factors):
+            raise QoiError("decode_thumbnails: a factor outside 1..64")
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        to = np.ascontiguousarray(thumb_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        fs = np.ascontiguousarray(factors, dtype=np.uintc)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        self._check(self._lib.qoimi_decode_thumbnails(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                      (QoiDesc * n)(*descs), n, channels, fs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), mode,
+                                                      d_thumbs, to.ctypes.data_as(szp), staging_bytes, stream), "qoimi_decode_thumbnails")
+
+    def thumbnail_stats(self) -> Tuple[int, int, int, int]:
+        """Of the last ``decode_thumbnails`` call: (sub-batches decoded, launches of the reduction kernel, bytes of staging planned, 0)."""
+        out = (ctypes.c_longlong * 4)()
+        self._lib.qoimi_thumbnail_stats(self._h, out)
+        return tuple(int(x) for x in out)
+
     def synth_frames(self, kind: int, seed: int, first_frame: int, n_frames: int, width: int, height: int,
                      d_pixels: int, pixel_stride: int, stream: int = 0) -> None:
         self._check(self._lib.qoimi_synth_frames(self._h, kind, seed, first_frame, n_frames, width, height,
@@ -438,7 +483,7 @@ class Context:
         return {self._lib.qoimi_kernel_name(i).decode(): (ms[i], calls[i]) for i in range(1, n)}
 
     def workspace_bytes(self) -> dict:
-        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images``), staging of the host-pointer entry points."""
+        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails``), staging of the host-pointer entry points."""
         out = (ctypes.c_size_t * 3)()
         self._lib.qoimi_workspace_bytes(self._h, out)
         return {"encode": int(out[0]), "decode": int(out[1]), "staging": int(out[2])}

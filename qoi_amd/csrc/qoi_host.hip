@@ -32,6 +32,7 @@
 #include "qoi_pack.hip"        // the pack kernels and their launchers: part of this translation unit (no build lists the file itself)
 #include "qoi_inspect.hip"     // ... and the kernels of qoimi_inspect_streams, the same way
 #include "qoi_compare.hip"     // ... and those of qoimi_compare_images / qoimi_verify_images
+#include "qoi_thumb.hip"       // ... and the box reduction of qoimi_decode_thumbnails
 
 using namespace qoimi;
 
@@ -103,7 +104,8 @@ struct qoimi_ctx {
     Arena enc_stage;            // qoimi_encode_packed: the strided streams of one sub-batch (and the source offsets of a mixed-shape call) on their way into the pack
     Arena insp_ws;              // tables, maps and partial counts of qoimi_inspect_streams (its own: a decode call finds dec_ws as it left it)
     Arena cmp_ws;               // image table and result table of qoimi_compare_images / qoimi_verify_images
-    Arena ver_stage;            // qoimi_verify_images: the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
+    Arena ver_stage;            // qoimi_verify_images / qoimi_decode_thumbnails: the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
+    long long thumb_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_thumbnails call: sub-batches decoded, launches of thumb_reduce, bytes of staging planned, 0
     void* cmp_pin_buf = nullptr; size_t cmp_pin_cap = 0;   // pinned staging of those two calls' tables and results (their own: the decode calls inside
                                 // qoimi_verify_images reuse pin_buf at once)
     Arena dec_scan;             // look-back words of dec_scan_entry (calls of a few images): tagged with dec_epoch, zeroed when allocated / when the tag wraps
@@ -363,7 +365,8 @@ extern "C" int qoimi_set_encode_small_call_order(qoimi_ctx* c, int by_workgroup_
 }
 
 // device memory the context holds: [0] encode workspace (and the staging of qoimi_encode_packed), [1] decode workspace (and the tables of
-// qoimi_inspect_streams, the tables and the staging of qoimi_compare_images / qoimi_verify_images), [2] staging of the host-pointer entry points
+// qoimi_inspect_streams, the tables and the staging of qoimi_compare_images / qoimi_verify_images / qoimi_decode_thumbnails), [2] staging of the
+// host-pointer entry points
 extern "C" void qoimi_workspace_bytes(qoimi_ctx* c, size_t out[3]) {
     out[0] = c ? c->enc_ws.cap + c->enc_stage.cap : 0; out[1] = c ? c->dec_ws.cap + c->insp_ws.cap + c->cmp_ws.cap + c->ver_stage.cap : 0;
     out[2] = c ? c->io_a.cap + c->io_b.cap + c->io_c.cap : 0;
@@ -1703,6 +1706,109 @@ extern "C" int qoimi_verify_images(qoimi_ctx* c, const void* d_pixels, const siz
         if (diffs_out[i].flags != 0u && lowest < 0) lowest = (int)i;
     }
     if (first_diff) *first_diff = lowest;
+    return QOIMI_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// thumbnails of a pack (qoi_thumb.hip)
+// ------------------------------------------------------------------------------------
+static_assert(QOIMI_THUMB_PLAIN == 0 && QOIMI_THUMB_ALPHA_WEIGHTED == 1, "the table's mode bit");
+
+extern "C" size_t qoimi_thumbnail_size(const qoi_desc* desc, unsigned factor, int channels, unsigned* tw, unsigned* th) {
+    if (!desc_ok(desc) || factor < 1u || factor > kThumbMaxFactor || (channels != 3 && channels != 4)) return 0;
+    const uint32_t x = thumb_extent(desc->width, factor), y = thumb_extent(desc->height, factor);
+    if (tw) *tw = x;
+    if (th) *th = y;
+    return (size_t)x * y * (size_t)channels;
+}
+
+extern "C" void qoimi_thumbnail_stats(qoimi_ctx* c, long long out[4]) {
+    for (int i = 0; i < 4; ++i) out[i] = c ? c->thumb_stats[i] : 0;
+}
+
+// Every sub-batch of the plan is one call of the decoder as it is into the staging arena, at 4 output channels (every staged pixel an aligned
+// dword), then one launch of thumb_reduce on the caller's stream; the next sub-batch's decoder is ordered behind it by the stream.
+extern "C" int qoimi_decode_thumbnails(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                       int n_images, int channels, const unsigned* factors, int mode, void* d_thumbs, const size_t* thumb_offsets,
+                                       size_t staging_bytes, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !factors || !d_thumbs || !thumb_offsets || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    if (mode != QOIMI_THUMB_PLAIN && mode != QOIMI_THUMB_ALPHA_WEIGHTED) return fail(QOIMI_E_ARG, "mode must be QOIMI_THUMB_PLAIN or QOIMI_THUMB_ALPHA_WEIGHTED");
+    const size_t n = (size_t)n_images;
+    std::vector<size_t> out_bytes(n), slots(n), at(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (sizes[i] < kHeaderBytes + kTrailerBytes) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + " shorter than 22 bytes (qoi.h:500)");
+        if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:513-521 rules)");
+        if (channels == 0 && descs[i].channels != descs[0].channels) return fail(QOIMI_E_ARG, "all images of a call must share the output channel count");
+        if (factors[i] < 1u || factors[i] > kThumbMaxFactor) return fail(QOIMI_E_ARG, "factor " + std::to_string(i) + " outside 1..64");
+        out_bytes[i] = (size_t)thumb_extent(descs[i].width, factors[i]) * thumb_extent(descs[i].height, factors[i]) * (size_t)(channels ? channels : descs[i].channels);
+        slots[i] = up256((size_t)descs[i].width * descs[i].height * 4u);
+    }
+    const unsigned och = channels ? (unsigned)channels : descs[0].channels;
+    {
+        std::vector<int> order(n);
+        std::iota(order.begin(), order.end(), 0);
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return thumb_offsets[a] < thumb_offsets[b]; });
+        for (size_t k = 1; k < n; ++k) {
+            const size_t a = (size_t)order[k - 1], b = (size_t)order[k];
+            if (thumb_offsets[b] - thumb_offsets[a] < out_bytes[a]) return fail   // (sorted: the difference cannot wrap)
+               (QOIMI_E_ARG, "the output ranges of two thumbnails overlap");
+        }
+    }
+    // the plan: a function of descs and staging_bytes alone (qoi_amd/packplan.py: plan over width * height * 4)
+    const std::vector<int> firsts = pack_plan(slots, staging_bytes ? staging_bytes : kPackStagingDefault);
+    struct Sub { uint32_t tiles; };
+    std::vector<Sub> subs(firsts.size() - 1u);
+    size_t need = 0;                                           // the largest sub-batch
+    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
+        size_t used = 0;
+        uint64_t tiles = 0;
+        for (int i = firsts[k]; i < firsts[k + 1]; ++i) {
+            at[(size_t)i] = used; used += slots[(size_t)i];
+            tiles += thumb_tiles(descs[i].width, descs[i].height, factors[i]);
+        }
+        if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of thumbnail pixels in one sub-batch");
+        subs[k].tiles = (uint32_t)tiles;
+        if (used > need) need = used;
+    }
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    c->thumb_stats[0] = 0; c->thumb_stats[1] = 0; c->thumb_stats[2] = (long long)need; c->thumb_stats[3] = 0;
+    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
+    // one image table for the whole call, through pinned staging; the entries of a sub-batch stand together, their tiles begin at 0
+    const size_t tab_bytes = up256(n * sizeof(ThumbImage));
+    { const int rc = cmp_pin_reserve(c, tab_bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = c->cmp_ws.reserve(tab_bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = reserve_exact(c->ver_stage, need); if (rc != QOIMI_OK) return rc; }
+    ThumbImage* h_tab = (ThumbImage*)c->cmp_pin_buf;
+    const uint32_t weighted = (mode == QOIMI_THUMB_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
+    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
+        uint32_t t = 0;
+        for (int i = firsts[k]; i < firsts[k + 1]; ++i) {
+            ThumbImage& e = h_tab[i];
+            uint32_t lg, cols;
+            thumb_split(factors[i], lg, cols);
+            e.src_off = (u64)at[(size_t)i]; e.dst_off = (u64)thumb_offsets[i];
+            e.w = descs[i].width; e.h = descs[i].height; e.f = factors[i];
+            e.tw = thumb_extent(e.w, e.f); e.th = thumb_extent(e.h, e.f);
+            e.first_tile = t; e.cfg = lg | (cols << 8) | (och << 16) | (weighted << 24); e.reserved = 0u;
+            t += (uint32_t)thumb_tiles(e.w, e.h, e.f);
+        }
+    }
+    const ThumbImage* d_tab = (const ThumbImage*)c->cmp_ws.base;
+    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, n * sizeof(ThumbImage), hipMemcpyHostToDevice, st));
+    const uint32_t most = (uint32_t)c->n_cus * 8u;
+    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
+        const int first = firsts[k], m = firsts[k + 1] - first;
+        const int rc = qoimi_decode_images(c, d_streams, stream_offsets + first, sizes + first, descs + first, m, 4, c->ver_stage.base, at.data() + first, stream);
+        if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
+        c->thumb_stats[0] += 1;
+        launch_thumb((const uint8_t*)c->ver_stage.base, d_tab + first, (uint32_t)m, subs[k].tiles, (uint8_t*)d_thumbs, subs[k].tiles < most ? subs[k].tiles : most, st);
+        { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string("thumb_reduce: ") + hipGetErrorString(e)); } }
+        c->thumb_stats[1] += 1;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
     return QOIMI_OK;
 }
 
