@@ -405,6 +405,57 @@ size_t qoimi_thumbnail_size(const qoi_desc *desc, unsigned factor, int channels,
  * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] 0. */
 void qoimi_thumbnail_stats(qoimi_ctx *ctx, long long out[4]);
 
+/* Rectangles of a pack's images, as they are, without the caller ever owning the full-size images: a tile server cuts a large scan into tiles, a
+ * training loader takes one or several crops per image, often mirrored.  QOI cannot be decoded from the middle (every pixel depends on the one
+ * before), so a referenced stream is decoded from its start - into a staging arena of the context, sub-batch by sub-batch - but only down to the
+ * last row any crop needs, and the rectangles are gathered from there on the device.
+ * The result (normative; qoi_amd/crops.py: crop states it in Python): decode stream crops[j].image exactly as qoimi_decode_images does (same
+ * leniency, bit-exact for EVERY input stream) to och = channels, or the images' own channel count when channels is 0 (then the same for all
+ * REFERENCED images), which gives D of h rows of w pixels.  Output j is D[y .. y + height) x [x .. x + width), its rows in reverse order with
+ * QOIMI_CROP_FLIP_Y and its columns with QOIMI_CROP_FLIP_X, written tightly packed row-major, width * height * och bytes (qoimi_crop_size), at
+ * d_out + out_offsets[j].
+ *   stream_offsets, sizes, descs, channels  HOST arrays / value as for qoimi_decode_images.  An image that no crop names is NOT decoded and its
+ *                  sizes[i] and descs[i] are not even checked
+ *   crops          HOST qoimi_crop[n_crops], in any order of image; several may name the same image, their rectangles may overlap or coincide
+ *   out_offsets    HOST size_t[n_crops]: ANY byte offsets in any order; not one byte beside an output is written (two outputs may share an
+ *                  aligned word: no word is ever read and written back); ranges must not overlap
+ *   staging_bytes  device memory the call may hold for decoded pixels (the arena qoimi_verify_images and qoimi_decode_thumbnails use, counted in
+ *                  qoimi_workspace_bytes [1], allocated as the largest sub-batch of the call's plan plus a page, no slack).  0: 1 GiB.  The
+ *                  staging always holds 4 bytes per pixel.  The plan (normative; qoi_amd/crops.py: plan): the referenced images are taken in
+ *                  ascending index order; rows_i is the maximum of y + height over the crops of image i; a slot is width_i * rows_i * 4
+ *                  rounded up to 256 bytes; sub-batches are cut by qoi_amd/packplan.py: plan over those slots (a request smaller than one slot
+ *                  is raised to that slot).  A 256-row band at the top of a 16384 x 16384 scan is staged in 16 MiB instead of 1 GiB.
+ * Every sub-batch is one qoimi_decode_images call as it is, at 4 output channels and with each descriptor's height replaced by rows_i (the
+ * decoder decodes to the descriptor it is given, so this is exactly the first rows_i rows of the full decode), then one launch of the gather
+ * kernel over all crops of the sub-batch's images on `stream`.
+ * SYNCHRONOUS: returns when every output is written.  The code of a decode sub-call that failed ends the call.  QOIMI_E_ARG for a NULL ctx,
+ * d_streams, stream_offsets, sizes, descs, crops, d_out or out_offsets, n_images <= 0, n_crops <= 0, channels not 0 / 3 / 4, crops[j].image >=
+ * n_images, a zero width or height, a rectangle that leaves its image, a flag bit other than the two, a referenced stream shorter than 22 bytes,
+ * a rejected referenced descriptor, mixed channel counts among the referenced images when channels is 0, overlapping output ranges, an output
+ * whose last byte's address d_out + out_offsets[j] + size - 1 does not fit in a pointer, a sub-batch
+ * of the plan with 2^31 - 1 or more tiles of 256 work items of the gather kernel (an item is one aligned 16-byte word of an output): reported
+ * before anything is launched, the caller's buffers are untouched.  The sub-batches count as decode calls of the context, as those of
+ * qoimi_verify_images do.  One call at a time per context, as everywhere. */
+enum { QOIMI_CROP_FLIP_X = 1, QOIMI_CROP_FLIP_Y = 2 };
+typedef struct {                 /* 24 bytes, offsets 0/4/8/12/16/20 */
+    unsigned int image;          /* index into the call's images */
+    unsigned int x, y;           /* top-left corner in the source image */
+    unsigned int width, height;  /* both >= 1; x + width <= image width, y + height <= image height */
+    unsigned int flags;          /* QOIMI_CROP_FLIP_* ; no other bit */
+} qoimi_crop;
+int qoimi_decode_crops(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                       const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                       const qoimi_crop *crops /* host */, int n_crops,
+                       void *d_out, const size_t *out_offsets /* host, n_crops */, size_t staging_bytes, void *stream);
+
+/* width * height * channels - the bytes of the crop's output - or 0 if desc is rejected, crop is NULL, has a zero width or height, leaves the
+ * image of desc or carries an unknown flag bit, or channels is not 3 / 4 (crop->image is not looked at).  Pure host arithmetic: no context, no GPU. */
+size_t qoimi_crop_size(const qoi_desc *desc, const qoimi_crop *crop, int channels);
+
+/* Of the context's last qoimi_decode_crops call: [0] sub-batches decoded, [1] launches of the gather kernel (it has no entry in
+ * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] images decoded (the referenced ones). */
+void qoimi_crop_stats(qoimi_ctx *ctx, long long out[4]);
+
 /* Fill device memory with synthetic RGBA frames frame_id = first_frame .. first_frame+n-1
  * (benchmark/test utility; same function of (kind, seed, frame, pixel) as synth.py). */
 int qoimi_synth_frames(qoimi_ctx *ctx, int kind, unsigned seed, unsigned first_frame,
@@ -420,8 +471,8 @@ int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
 
 /* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace (and the staging arena of
  * qoimi_encode_packed), [1] decode workspace
- * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images
- * and qoimi_decode_thumbnails, which share them),
+ * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images,
+ * qoimi_decode_thumbnails and qoimi_decode_crops, which share them),
  * [2] staging buffers of the host-pointer entry points (qoi_encode / qoi_decode of the calling thread's context). */
 void qoimi_workspace_bytes(qoimi_ctx *ctx, size_t out[3]);
 

@@ -40,6 +40,7 @@ EXPORTS = (
     "qoimi_encode_packed", "qoimi_encode_images_packed",
     "qoimi_compare_images", "qoimi_verify_images",
     "qoimi_decode_thumbnails", "qoimi_thumbnail_size", "qoimi_thumbnail_stats",
+    "qoimi_decode_crops", "qoimi_crop_size", "qoimi_crop_stats",
 )
 
 
@@ -62,6 +63,15 @@ class ImageDiff(ctypes.Structure):
     """``qoimi_image_diff``: 32 bytes, the layout of ``imagediff.DIFF_DTYPE``."""
     _fields_ = [("mismatched", ctypes.c_ulonglong), ("first", ctypes.c_ulonglong), ("want", ctypes.c_uint), ("got", ctypes.c_uint),
                 ("flags", ctypes.c_uint), ("reserved", ctypes.c_uint)]
+
+
+class QoimiCrop(ctypes.Structure):
+    """``qoimi_crop``: 24 bytes - a rectangle of image ``image`` and how it is mirrored (``crops.FLIP_X`` / ``crops.FLIP_Y``)."""
+    _fields_ = [("image", ctypes.c_uint), ("x", ctypes.c_uint), ("y", ctypes.c_uint), ("width", ctypes.c_uint), ("height", ctypes.c_uint),
+                ("flags", ctypes.c_uint)]
+
+
+assert ctypes.sizeof(QoimiCrop) == 24 and [getattr(QoimiCrop, f).offset for f, _ in QoimiCrop._fields_] == [0, 4, 8, 12, 16, 20]
 
 
 class QoiError(RuntimeError):
@@ -154,6 +164,13 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_thumbnail_size.argtypes = [dp, ctypes.c_uint, ci, up, up]
     lib.qoimi_thumbnail_stats.restype = None
     lib.qoimi_thumbnail_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+    cp = ctypes.POINTER(QoimiCrop)
+    lib.qoimi_decode_crops.restype = ci
+    lib.qoimi_decode_crops.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, ci, cp, ci, vp, szp, sz, vp]
+    lib.qoimi_crop_size.restype = sz
+    lib.qoimi_crop_size.argtypes = [dp, cp, ci]
+    lib.qoimi_crop_stats.restype = None
+    lib.qoimi_crop_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     _lib = lib
     return lib
 
@@ -181,6 +198,24 @@ def thumbnail_size(width: int, height: int, channels_in: int, factor: int, chann
     tw, th = ctypes.c_uint(0), ctypes.c_uint(0)
     n = int(load_library().qoimi_thumbnail_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), factor, channels, ctypes.byref(tw), ctypes.byref(th)))
     return n, tw.value, th.value
+
+
+def _crop_array(crops):
+    """crops as a ``QoimiCrop`` array: a sequence of such structures or of (image, x, y, width, height, flags) tuples; None if a field
+    does not fit an unsigned int."""
+    rows = [(c.image, c.x, c.y, c.width, c.height, c.flags) if isinstance(c, QoimiCrop) else tuple(int(v) for v in c) for c in crops]
+    if any(len(r) != 6 or any(not 0 <= v < 2 ** 32 for v in r) for r in rows):
+        return None
+    return (QoimiCrop * len(rows))(*[QoimiCrop(*r) for r in rows])
+
+
+def crop_size(width: int, height: int, channels_in: int, crop, channels: int) -> int:
+    """``qoimi_crop_size`` for an image of width x height x channels_in: the bytes of the output of `crop` (a ``QoimiCrop`` or an (image, x, y,
+    width, height, flags) tuple) with `channels` (3 or 4) bytes per pixel; 0 where the C function returns 0."""
+    arr = _crop_array([crop])
+    if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
+        return 0
+    return int(load_library().qoimi_crop_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels))
 
 
 # ----------------------------------------------------------------------------------
@@ -463,6 +498,33 @@ class Context:
         self._lib.qoimi_thumbnail_stats(self._h, out)
         return tuple(int(x) for x in out)
 
+    def decode_crops(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                     crops, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
+        """Rectangles of a pack's images (``qoimi_decode_crops``, synchronous, through bounded staging): output j is written tightly packed at
+        d_out + out_offsets[j].  crops: ``QoimiCrop`` structures or (image, x, y, width, height, flags) tuples, flags of ``crops.FLIP_X`` /
+        ``crops.FLIP_Y``; an image no crop names is not decoded; ``qoi_amd/crops.py: crop`` states the result."""
+        n = len(sizes)
+        if len(descs) != n or len(stream_offsets) != n:
+            raise QoiError("decode_crops: one stream offset, size and descriptor per image")
+        if len(out_offsets) != len(crops):
+            raise QoiError("decode_crops: one output offset per crop")
+        arr = _crop_array(crops)
+        if arr is None:
+            raise QoiError("decode_crops: a crop is not six unsigned 32-bit fields")
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        self._check(self._lib.qoimi_decode_crops(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                 (QoiDesc * n)(*descs), n, channels, arr, len(arr), d_out, oo.ctypes.data_as(szp), staging_bytes,
+                                                 stream), "qoimi_decode_crops")
+
+    def crop_stats(self) -> Tuple[int, int, int, int]:
+        """Of the last ``decode_crops`` call: (sub-batches decoded, launches of the gather kernel, bytes of staging planned, images decoded)."""
+        out = (ctypes.c_longlong * 4)()
+        self._lib.qoimi_crop_stats(self._h, out)
+        return tuple(int(x) for x in out)
+
     def synth_frames(self, kind: int, seed: int, first_frame: int, n_frames: int, width: int, height: int,
                      d_pixels: int, pixel_stride: int, stream: int = 0) -> None:
         self._check(self._lib.qoimi_synth_frames(self._h, kind, seed, first_frame, n_frames, width, height,
@@ -483,7 +545,7 @@ class Context:
         return {self._lib.qoimi_kernel_name(i).decode(): (ms[i], calls[i]) for i in range(1, n)}
 
     def workspace_bytes(self) -> dict:
-        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails``), staging of the host-pointer entry points."""
+        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops``), staging of the host-pointer entry points."""
         out = (ctypes.c_size_t * 3)()
         self._lib.qoimi_workspace_bytes(self._h, out)
         return {"encode": int(out[0]), "decode": int(out[1]), "staging": int(out[2])}

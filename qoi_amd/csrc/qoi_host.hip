@@ -33,6 +33,7 @@
 #include "qoi_inspect.hip"     // ... and the kernels of qoimi_inspect_streams, the same way
 #include "qoi_compare.hip"     // ... and those of qoimi_compare_images / qoimi_verify_images
 #include "qoi_thumb.hip"       // ... and the box reduction of qoimi_decode_thumbnails
+#include "qoi_crop.hip"        // ... and the gather of qoimi_decode_crops
 
 using namespace qoimi;
 
@@ -104,8 +105,9 @@ struct qoimi_ctx {
     Arena enc_stage;            // qoimi_encode_packed: the strided streams of one sub-batch (and the source offsets of a mixed-shape call) on their way into the pack
     Arena insp_ws;              // tables, maps and partial counts of qoimi_inspect_streams (its own: a decode call finds dec_ws as it left it)
     Arena cmp_ws;               // image table and result table of qoimi_compare_images / qoimi_verify_images
-    Arena ver_stage;            // qoimi_verify_images / qoimi_decode_thumbnails: the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
+    Arena ver_stage;            // qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops: the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
     long long thumb_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_thumbnails call: sub-batches decoded, launches of thumb_reduce, bytes of staging planned, 0
+    long long crop_stats[4] = {0, 0, 0, 0};    // the last qoimi_decode_crops call: sub-batches decoded, launches of crop_gather, bytes of staging planned, images decoded
     void* cmp_pin_buf = nullptr; size_t cmp_pin_cap = 0;   // pinned staging of those two calls' tables and results (their own: the decode calls inside
                                 // qoimi_verify_images reuse pin_buf at once)
     Arena dec_scan;             // look-back words of dec_scan_entry (calls of a few images): tagged with dec_epoch, zeroed when allocated / when the tag wraps
@@ -365,7 +367,7 @@ extern "C" int qoimi_set_encode_small_call_order(qoimi_ctx* c, int by_workgroup_
 }
 
 // device memory the context holds: [0] encode workspace (and the staging of qoimi_encode_packed), [1] decode workspace (and the tables of
-// qoimi_inspect_streams, the tables and the staging of qoimi_compare_images / qoimi_verify_images / qoimi_decode_thumbnails), [2] staging of the
+// qoimi_inspect_streams, the tables and the staging of qoimi_compare_images / qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops), [2] staging of the
 // host-pointer entry points
 extern "C" void qoimi_workspace_bytes(qoimi_ctx* c, size_t out[3]) {
     out[0] = c ? c->enc_ws.cap + c->enc_stage.cap : 0; out[1] = c ? c->dec_ws.cap + c->insp_ws.cap + c->cmp_ws.cap + c->ver_stage.cap : 0;
@@ -1807,6 +1809,145 @@ extern "C" int qoimi_decode_thumbnails(qoimi_ctx* c, const void* d_streams, cons
         launch_thumb((const uint8_t*)c->ver_stage.base, d_tab + first, (uint32_t)m, subs[k].tiles, (uint8_t*)d_thumbs, subs[k].tiles < most ? subs[k].tiles : most, st);
         { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string("thumb_reduce: ") + hipGetErrorString(e)); } }
         c->thumb_stats[1] += 1;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return QOIMI_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// rectangles of a pack's images (qoi_crop.hip)
+// ------------------------------------------------------------------------------------
+static_assert(sizeof(qoimi_crop) == 24 && offsetof(qoimi_crop, image) == 0 && offsetof(qoimi_crop, x) == 4 && offsetof(qoimi_crop, y) == 8 &&
+              offsetof(qoimi_crop, width) == 12 && offsetof(qoimi_crop, height) == 16 && offsetof(qoimi_crop, flags) == 20, "qoimi_crop layout");
+static_assert(QOIMI_CROP_FLIP_X == (int)kCropFlipX && QOIMI_CROP_FLIP_Y == (int)kCropFlipY, "the table's flag bits");
+
+// nullptr if the rectangle is fine for an accepted descriptor, else what is wrong with it
+static const char* crop_rect_wrong(const qoi_desc* d, const qoimi_crop* r) {
+    if (r->width == 0u || r->height == 0u) return "zero width or height";
+    if ((r->flags & ~(unsigned)(QOIMI_CROP_FLIP_X | QOIMI_CROP_FLIP_Y)) != 0u) return "unknown flag bit";
+    if ((uint64_t)r->x + r->width > d->width || (uint64_t)r->y + r->height > d->height) return "the rectangle leaves its image";
+    return nullptr;
+}
+
+extern "C" size_t qoimi_crop_size(const qoi_desc* desc, const qoimi_crop* crop, int channels) {
+    if (!desc_ok(desc) || !crop || (channels != 3 && channels != 4) || crop_rect_wrong(desc, crop)) return 0;
+    return (size_t)crop->width * crop->height * (size_t)channels;
+}
+
+extern "C" void qoimi_crop_stats(qoimi_ctx* c, long long out[4]) {
+    for (int i = 0; i < 4; ++i) out[i] = c ? c->crop_stats[i] : 0;
+}
+
+// The referenced images, in ascending order, are planned into sub-batches over slots of w * rows * 4 bytes, rows the last row any crop of
+// the image needs; every sub-batch is one call of the decoder as it is into the staging arena, at 4 output channels and with each
+// descriptor's height shortened to those rows (the decoder decodes to the descriptor it is given: the prefix of the full decode), then one
+// launch of crop_gather over the sub-batch's crops on the caller's stream; the next sub-batch's decoder is ordered behind it by the stream.
+extern "C" int qoimi_decode_crops(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                  int n_images, int channels, const qoimi_crop* crops, int n_crops, void* d_out, const size_t* out_offsets,
+                                  size_t staging_bytes, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !crops || !d_out || !out_offsets || n_images <= 0 || n_crops <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    const size_t n = (size_t)n_crops;
+    std::vector<uint32_t> rows((size_t)n_images, 0u);          // the rows of image i that are decoded; 0: no crop names it
+    std::vector<size_t> out_bytes(n);
+    unsigned och = (unsigned)channels;
+    for (size_t j = 0; j < n; ++j) {
+        const qoimi_crop& r = crops[j];
+        if (r.image >= (unsigned)n_images) return fail(QOIMI_E_ARG, "crop " + std::to_string(j) + ": no image " + std::to_string(r.image));
+        const size_t i = r.image;
+        if (rows[i] == 0u) {                                   // (an image no crop names is never looked at)
+            if (sizes[i] < kHeaderBytes + kTrailerBytes) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + " shorter than 22 bytes (qoi.h:500)");
+            if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:513-521 rules)");
+        }
+        if (channels == 0) {
+            if (och == 0u) och = descs[i].channels;
+            else if (descs[i].channels != och) return fail(QOIMI_E_ARG, "all referenced images of a call must share the output channel count");
+        }
+        if (const char* wrong = crop_rect_wrong(&descs[i], &r)) return fail(QOIMI_E_ARG, "crop " + std::to_string(j) + ": " + wrong);
+        if (r.y + r.height > rows[i]) rows[i] = r.y + r.height;
+        out_bytes[j] = (size_t)r.width * r.height * och;
+        const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_out;   // (so that no address of an output wraps, whatever the offsets)
+        if (out_offsets[j] > room || out_bytes[j] > room - out_offsets[j]) return fail(QOIMI_E_ARG, "crop " + std::to_string(j) + ": the output ends behind the address space");
+    }
+    {
+        std::vector<size_t> order(n);
+        std::iota(order.begin(), order.end(), (size_t)0);
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return out_offsets[a] < out_offsets[b]; });
+        for (size_t k = 1; k < n; ++k) {
+            const size_t a = order[k - 1], b = order[k];
+            if (out_offsets[b] - out_offsets[a] < out_bytes[a]) return fail   // (sorted: the difference cannot wrap)
+               (QOIMI_E_ARG, "the output ranges of two crops overlap");
+        }
+    }
+    // the plan: a function of descs, crops and staging_bytes alone (qoi_amd/crops.py: plan - packplan.plan over width * rows * 4 of the referenced images)
+    std::vector<int> refs;                                     // the referenced images, ascending
+    std::vector<int> ref_of((size_t)n_images, -1);
+    for (int i = 0; i < n_images; ++i) if (rows[(size_t)i] != 0u) { ref_of[(size_t)i] = (int)refs.size(); refs.push_back(i); }
+    const size_t nr = refs.size();
+    std::vector<size_t> slots(nr), at(nr);
+    for (size_t r = 0; r < nr; ++r) slots[r] = up256((size_t)descs[refs[r]].width * rows[(size_t)refs[r]] * 4u);
+    const std::vector<int> firsts = pack_plan(slots, staging_bytes ? staging_bytes : kPackStagingDefault);
+    std::vector<size_t> by_ref(n);                             // the crops in the order of their images' sub-batches
+    std::iota(by_ref.begin(), by_ref.end(), (size_t)0);
+    std::stable_sort(by_ref.begin(), by_ref.end(), [&](size_t a, size_t b) { return ref_of[crops[a].image] < ref_of[crops[b].image]; });
+    struct Sub { uint32_t entry, m, tiles; };
+    std::vector<Sub> subs(firsts.size() - 1u);
+    std::vector<uint32_t> first_tile(n);                       // of by_ref[e], within its sub-batch
+    size_t need = 0;                                           // the largest sub-batch
+    {
+        size_t e = 0;
+        for (size_t k = 0; k + 1 < firsts.size(); ++k) {
+            size_t used = 0;
+            for (int r = firsts[k]; r < firsts[k + 1]; ++r) { at[(size_t)r] = used; used += slots[(size_t)r]; }
+            if (used > need) need = used;
+            uint64_t tiles = 0;
+            subs[k].entry = (uint32_t)e;
+            for (; e < n && ref_of[crops[by_ref[e]].image] < firsts[k + 1]; ++e) {
+                if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output words in one sub-batch");
+                first_tile[e] = (uint32_t)tiles;
+                tiles += crop_tiles((uint64_t)(uintptr_t)d_out + out_offsets[by_ref[e]], out_bytes[by_ref[e]]);
+            }
+            if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output words in one sub-batch");
+            subs[k].m = (uint32_t)(e - subs[k].entry); subs[k].tiles = (uint32_t)tiles;
+        }
+    }
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    c->crop_stats[0] = 0; c->crop_stats[1] = 0; c->crop_stats[2] = (long long)need; c->crop_stats[3] = (long long)nr;
+    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
+    // one crop table for the whole call, through pinned staging; the entries of a sub-batch stand together, their tiles begin at 0
+    const size_t tab_bytes = up256(n * sizeof(CropEntry));
+    { const int rc = cmp_pin_reserve(c, tab_bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = c->cmp_ws.reserve(tab_bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = reserve_exact(c->ver_stage, need); if (rc != QOIMI_OK) return rc; }
+    CropEntry* h_tab = (CropEntry*)c->cmp_pin_buf;
+    for (size_t e = 0; e < n; ++e) {
+        const qoimi_crop& r = crops[by_ref[e]];
+        CropEntry& t = h_tab[e];
+        t.src_off = (u64)at[(size_t)ref_of[r.image]]; t.dst_off = (u64)out_offsets[by_ref[e]];
+        t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.ch = r.height;
+        t.first_tile = first_tile[e]; t.cfg = och | (r.flags << 8); t.reserved = 0u;
+    }
+    const CropEntry* d_tab = (const CropEntry*)c->cmp_ws.base;
+    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, n * sizeof(CropEntry), hipMemcpyHostToDevice, st));
+    const uint32_t most = (uint32_t)c->n_cus * 8u;
+    std::vector<size_t> so; std::vector<int> sz; std::vector<qoi_desc> ds;
+    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
+        const int first = firsts[k], m = firsts[k + 1] - first;
+        so.clear(); sz.clear(); ds.clear();
+        for (int r = first; r < first + m; ++r) {
+            const int i = refs[(size_t)r];
+            qoi_desc d = descs[i];
+            d.height = rows[(size_t)i];
+            so.push_back(stream_offsets[i]); sz.push_back(sizes[i]); ds.push_back(d);
+        }
+        const int rc = qoimi_decode_images(c, d_streams, so.data(), sz.data(), ds.data(), m, 4, c->ver_stage.base, at.data() + first, stream);
+        if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
+        c->crop_stats[0] += 1;
+        launch_crop((const uint8_t*)c->ver_stage.base, d_tab + subs[k].entry, subs[k].m, subs[k].tiles, (uint8_t*)d_out, subs[k].tiles < most ? subs[k].tiles : most, st);
+        { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string("crop_gather: ") + hipGetErrorString(e)); } }
+        c->crop_stats[1] += 1;
     }
     HIP_TRY(hipStreamSynchronize(st));
     return QOIMI_OK;
