@@ -456,6 +456,69 @@ size_t qoimi_crop_size(const qoi_desc *desc, const qoimi_crop *crop, int channel
  * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] images decoded (the referenced ones). */
 void qoimi_crop_stats(qoimi_ctx *ctx, long long out[4]);
 
+/* Rectangles of a pack's images resampled to caller-chosen sizes, without the caller ever owning the full-size images or the unscaled rectangles: a
+ * training loader wants every sample of a batch at one fixed size (random-resized-crop, often mirrored), a tile server a tile of fixed size at
+ * any zoom.  The common generalisation of qoimi_decode_thumbnails and qoimi_decode_crops: with out_width x out_height equal to width x height it is
+ * qoimi_decode_crops byte for byte, and where width and height are the same integer multiple f of out_width and out_height it is the
+ * qoimi_decode_thumbnails reduction of the rectangle at f, byte for byte in both modes.
+ * The result (normative; qoi_amd/resize.py: resize states it in Python): decode stream items[j].image exactly as qoimi_decode_images does (same
+ * leniency, bit-exact for EVERY input stream) to och = channels, or the images' own channel count when channels is 0 (then the same for all
+ * REFERENCED images), which gives D of h rows of w pixels.  R = D[y .. y + height) x [x .. x + width), cw = width, rh = height, ow = out_width,
+ * oh = out_height; all arithmetic is integer, every division floors.  Output column X weighs source column k of R with wx(X, k) = max(0,
+ * min((X+1)*cw, (k+1)*ow) - max(X*cw, k*ow)) - the overlap of [X*cw, (X+1)*cw) with [k*ow, (k+1)*ow), summing to cw over k; wy(Y, r) is the same
+ * with rh, oh and sums to rh.  T = cw * rh, N_c = sum over r, k of wy(Y, r) * wx(X, k) * R[r][k].c.
+ *   QOIMI_RESIZE_PLAIN           every channel of output pixel (X, Y) is (N_c + T/2) / T: ONE rounding, no rounded intermediate between a
+ *                                horizontal and a vertical pass
+ *   QOIMI_RESIZE_ALPHA_WEIGHTED  where och == 4: A = N_a, output alpha is (A + T/2) / T; if A > 0, r, g and b are (sum wy * wx * c * a + A/2) / A,
+ *                                if A == 0 they are the PLAIN value.  With och == 3 this mode is PLAIN.
+ * The oh x ow result has its rows in reverse order with QOIMI_RESIZE_FLIP_Y and its columns with QOIMI_RESIZE_FLIP_X (the weights are symmetric:
+ * this is the resampled mirrored rectangle) and is written tightly packed row-major, ow * oh * och bytes (qoimi_resize_size), at d_out +
+ * out_offsets[j].  T < 400 000 000, N_c <= 255 * T < 2^37, the alpha-weighted sums are below 2^45.  Upscaling is allowed in either axis; downscaling
+ * stops at 64 per axis (width <= 64 * out_width, height <= 64 * out_height - the limit of qoimi_decode_thumbnails), so an output pixel overlaps
+ * at most 65 x 65 source pixels.
+ *   stream_offsets, sizes, descs, channels  HOST arrays / value as for qoimi_decode_images.  An image that no item names is NOT decoded and its
+ *                  sizes[i] and descs[i] are not even checked
+ *   items          HOST qoimi_resize[n_items], in any order of image; several may name the same image, their rectangles may overlap or coincide
+ *   out_offsets    HOST size_t[n_items]: ANY byte offsets in any order; not one byte beside an output is written (two outputs may share an
+ *                  aligned word: no word is ever read and written back); ranges must not overlap
+ *   staging_bytes  as for qoimi_decode_crops: the arena qoimi_verify_images, qoimi_decode_thumbnails and qoimi_decode_crops use, counted in
+ *                  qoimi_workspace_bytes [1], allocated as the largest sub-batch of the call's plan plus a page; 4 bytes per pixel; 0: 1 GiB.
+ *                  The plan is that of qoimi_decode_crops over the items' rectangles (normative; qoi_amd/resize.py: plan): the referenced
+ *                  images in ascending order, rows_i the maximum of y + height over the items of image i, slots of width_i * rows_i * 4 rounded
+ *                  up to 256 bytes, sub-batches cut by qoi_amd/packplan.py: plan (a request smaller than one slot is raised to that slot).
+ * Every sub-batch is one qoimi_decode_images call as it is, at 4 output channels and with each descriptor's height replaced by rows_i, then one
+ * launch of the filter kernel over all items of the sub-batch's images on `stream`.
+ * SYNCHRONOUS: returns when every output is written.  The code of a decode sub-call that failed ends the call.  QOIMI_E_ARG for a NULL ctx,
+ * d_streams, stream_offsets, sizes, descs, items, d_out or out_offsets, n_images <= 0, n_items <= 0, channels not 0 / 3 / 4, a mode that is
+ * neither of the two, items[j].image >= n_images, a zero width, height, out_width or out_height, a rectangle that leaves its image, width > 64 *
+ * out_width or height > 64 * out_height, a flag bit other than the two, a referenced stream shorter than 22 bytes, a rejected referenced
+ * descriptor, mixed channel counts among the referenced images when channels is 0, overlapping output ranges, an output whose last byte's
+ * address does not fit in a pointer, a sub-batch of the plan with 2^31 - 1 or more tiles of 256 work items of the filter kernel (an output pixel
+ * is 1 to 16 work items): reported before anything is launched, the caller's buffers are untouched.  The sub-batches count as decode calls of the
+ * context, as those of qoimi_verify_images do.  One call at a time per context, as everywhere. */
+enum { QOIMI_RESIZE_FLIP_X = 1, QOIMI_RESIZE_FLIP_Y = 2 };
+enum { QOIMI_RESIZE_PLAIN = 0, QOIMI_RESIZE_ALPHA_WEIGHTED = 1 };
+typedef struct {                 /* 32 bytes, offsets 0/4/8/12/16/20/24/28 */
+    unsigned int image;          /* index into the call's images */
+    unsigned int x, y;           /* top-left corner of the source rectangle */
+    unsigned int width, height;  /* both >= 1; x + width <= image width, y + height <= image height */
+    unsigned int out_width, out_height;  /* both >= 1; width <= 64 * out_width, height <= 64 * out_height */
+    unsigned int flags;          /* QOIMI_RESIZE_FLIP_* ; no other bit */
+} qoimi_resize;
+int qoimi_decode_resized(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                         const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                         const qoimi_resize *items /* host */, int n_items, int mode,
+                         void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream);
+
+/* out_width * out_height * channels - the bytes of the item's output - or 0 if desc is rejected, item is NULL, has a zero width or height in or
+ * out, leaves the image of desc, reduces by more than 64 in an axis or carries an unknown flag bit, channels is not 3 / 4, or the product does
+ * not fit a size_t (item->image is not looked at).  Pure host arithmetic: no context, no GPU. */
+size_t qoimi_resize_size(const qoi_desc *desc, const qoimi_resize *item, int channels);
+
+/* Of the context's last qoimi_decode_resized call: [0] sub-batches decoded, [1] launches of the filter kernel (it has no entry in
+ * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] images decoded (the referenced ones). */
+void qoimi_resize_stats(qoimi_ctx *ctx, long long out[4]);
+
 /* Fill device memory with synthetic RGBA frames frame_id = first_frame .. first_frame+n-1
  * (benchmark/test utility; same function of (kind, seed, frame, pixel) as synth.py). */
 int qoimi_synth_frames(qoimi_ctx *ctx, int kind, unsigned seed, unsigned first_frame,
@@ -472,7 +535,7 @@ int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
 /* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace (and the staging arena of
  * qoimi_encode_packed), [1] decode workspace
  * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images,
- * qoimi_decode_thumbnails and qoimi_decode_crops, which share them),
+ * qoimi_decode_thumbnails, qoimi_decode_crops and qoimi_decode_resized, which share them),
  * [2] staging buffers of the host-pointer entry points (qoi_encode / qoi_decode of the calling thread's context). */
 void qoimi_workspace_bytes(qoimi_ctx *ctx, size_t out[3]);
 

@@ -41,6 +41,7 @@ EXPORTS = (
     "qoimi_compare_images", "qoimi_verify_images",
     "qoimi_decode_thumbnails", "qoimi_thumbnail_size", "qoimi_thumbnail_stats",
     "qoimi_decode_crops", "qoimi_crop_size", "qoimi_crop_stats",
+    "qoimi_decode_resized", "qoimi_resize_size", "qoimi_resize_stats",
 )
 
 
@@ -72,6 +73,16 @@ class QoimiCrop(ctypes.Structure):
 
 
 assert ctypes.sizeof(QoimiCrop) == 24 and [getattr(QoimiCrop, f).offset for f, _ in QoimiCrop._fields_] == [0, 4, 8, 12, 16, 20]
+
+
+class QoimiResize(ctypes.Structure):
+    """``qoimi_resize``: 32 bytes - a rectangle of image ``image``, the size it is resampled to and how the result is mirrored
+    (``resize.FLIP_X`` / ``resize.FLIP_Y``)."""
+    _fields_ = [("image", ctypes.c_uint), ("x", ctypes.c_uint), ("y", ctypes.c_uint), ("width", ctypes.c_uint), ("height", ctypes.c_uint),
+                ("out_width", ctypes.c_uint), ("out_height", ctypes.c_uint), ("flags", ctypes.c_uint)]
+
+
+assert ctypes.sizeof(QoimiResize) == 32 and [getattr(QoimiResize, f).offset for f, _ in QoimiResize._fields_] == [0, 4, 8, 12, 16, 20, 24, 28]
 
 
 class QoiError(RuntimeError):
@@ -171,6 +182,13 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_crop_size.argtypes = [dp, cp, ci]
     lib.qoimi_crop_stats.restype = None
     lib.qoimi_crop_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+    rp = ctypes.POINTER(QoimiResize)
+    lib.qoimi_decode_resized.restype = ci
+    lib.qoimi_decode_resized.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, ci, rp, ci, ci, vp, szp, sz, vp]
+    lib.qoimi_resize_size.restype = sz
+    lib.qoimi_resize_size.argtypes = [dp, rp, ci]
+    lib.qoimi_resize_stats.restype = None
+    lib.qoimi_resize_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     _lib = lib
     return lib
 
@@ -216,6 +234,25 @@ def crop_size(width: int, height: int, channels_in: int, crop, channels: int) ->
     if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
         return 0
     return int(load_library().qoimi_crop_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels))
+
+
+def _resize_array(items):
+    """items as a ``QoimiResize`` array: a sequence of such structures or of (image, x, y, width, height, out_width, out_height, flags)
+    tuples; None if a field does not fit an unsigned int."""
+    rows = [(r.image, r.x, r.y, r.width, r.height, r.out_width, r.out_height, r.flags) if isinstance(r, QoimiResize) else tuple(int(v) for v in r)
+            for r in items]
+    if any(len(r) != 8 or any(not 0 <= v < 2 ** 32 for v in r) for r in rows):
+        return None
+    return (QoimiResize * len(rows))(*[QoimiResize(*r) for r in rows])
+
+
+def resize_size(width: int, height: int, channels_in: int, item, channels: int) -> int:
+    """``qoimi_resize_size`` for an image of width x height x channels_in: the bytes of the output of `item` (a ``QoimiResize`` or an (image,
+    x, y, width, height, out_width, out_height, flags) tuple) with `channels` (3 or 4) bytes per pixel; 0 where the C function returns 0."""
+    arr = _resize_array([item])
+    if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
+        return 0
+    return int(load_library().qoimi_resize_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels))
 
 
 # ----------------------------------------------------------------------------------
@@ -525,6 +562,34 @@ class Context:
         self._lib.qoimi_crop_stats(self._h, out)
         return tuple(int(x) for x in out)
 
+    def decode_resized(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                       items, mode: int, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
+        """Rectangles of a pack's images resampled to fixed sizes (``qoimi_decode_resized``, synchronous, through bounded staging): output j
+        is written tightly packed at d_out + out_offsets[j].  items: ``QoimiResize`` structures or (image, x, y, width, height, out_width,
+        out_height, flags) tuples, flags of ``resize.FLIP_X`` / ``resize.FLIP_Y``; mode: ``resize.PLAIN`` or ``resize.ALPHA_WEIGHTED``; an image
+        no item names is not decoded; ``qoi_amd/resize.py: resize`` states the result."""
+        n = len(sizes)
+        if len(descs) != n or len(stream_offsets) != n:
+            raise QoiError("decode_resized: one stream offset, size and descriptor per image")
+        if len(out_offsets) != len(items):
+            raise QoiError("decode_resized: one output offset per item")
+        arr = _resize_array(items)
+        if arr is None:
+            raise QoiError("decode_resized: an item is not eight unsigned 32-bit fields")
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        self._check(self._lib.qoimi_decode_resized(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                   (QoiDesc * n)(*descs), n, channels, arr, len(arr), mode, d_out, oo.ctypes.data_as(szp),
+                                                   staging_bytes, stream), "qoimi_decode_resized")
+
+    def resize_stats(self) -> Tuple[int, int, int, int]:
+        """Of the last ``decode_resized`` call: (sub-batches decoded, launches of the filter kernel, bytes of staging planned, images decoded)."""
+        out = (ctypes.c_longlong * 4)()
+        self._lib.qoimi_resize_stats(self._h, out)
+        return tuple(int(x) for x in out)
+
     def synth_frames(self, kind: int, seed: int, first_frame: int, n_frames: int, width: int, height: int,
                      d_pixels: int, pixel_stride: int, stream: int = 0) -> None:
         self._check(self._lib.qoimi_synth_frames(self._h, kind, seed, first_frame, n_frames, width, height,
@@ -545,7 +610,7 @@ class Context:
         return {self._lib.qoimi_kernel_name(i).decode(): (ms[i], calls[i]) for i in range(1, n)}
 
     def workspace_bytes(self) -> dict:
-        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops``), staging of the host-pointer entry points."""
+        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops`` / ``decode_resized``), staging of the host-pointer entry points."""
         out = (ctypes.c_size_t * 3)()
         self._lib.qoimi_workspace_bytes(self._h, out)
         return {"encode": int(out[0]), "decode": int(out[1]), "staging": int(out[2])}

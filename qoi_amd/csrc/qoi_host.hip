@@ -34,6 +34,7 @@
 #include "qoi_compare.hip"     // ... and those of qoimi_compare_images / qoimi_verify_images
 #include "qoi_thumb.hip"       // ... and the box reduction of qoimi_decode_thumbnails
 #include "qoi_crop.hip"        // ... and the gather of qoimi_decode_crops
+#include "qoi_resize.hip"      // ... and the area filter of qoimi_decode_resized
 
 using namespace qoimi;
 
@@ -105,9 +106,10 @@ struct qoimi_ctx {
     Arena enc_stage;            // qoimi_encode_packed: the strided streams of one sub-batch (and the source offsets of a mixed-shape call) on their way into the pack
     Arena insp_ws;              // tables, maps and partial counts of qoimi_inspect_streams (its own: a decode call finds dec_ws as it left it)
     Arena cmp_ws;               // image table and result table of qoimi_compare_images / qoimi_verify_images
-    Arena ver_stage;            // qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops: the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
+    Arena ver_stage;            // qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops / qoimi_decode_resized: the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
     long long thumb_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_thumbnails call: sub-batches decoded, launches of thumb_reduce, bytes of staging planned, 0
     long long crop_stats[4] = {0, 0, 0, 0};    // the last qoimi_decode_crops call: sub-batches decoded, launches of crop_gather, bytes of staging planned, images decoded
+    long long resize_stats[4] = {0, 0, 0, 0};  // the last qoimi_decode_resized call: sub-batches decoded, launches of resize_filter, bytes of staging planned, images decoded
     void* cmp_pin_buf = nullptr; size_t cmp_pin_cap = 0;   // pinned staging of those two calls' tables and results (their own: the decode calls inside
                                 // qoimi_verify_images reuse pin_buf at once)
     Arena dec_scan;             // look-back words of dec_scan_entry (calls of a few images): tagged with dec_epoch, zeroed when allocated / when the tag wraps
@@ -367,7 +369,7 @@ extern "C" int qoimi_set_encode_small_call_order(qoimi_ctx* c, int by_workgroup_
 }
 
 // device memory the context holds: [0] encode workspace (and the staging of qoimi_encode_packed), [1] decode workspace (and the tables of
-// qoimi_inspect_streams, the tables and the staging of qoimi_compare_images / qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops), [2] staging of the
+// qoimi_inspect_streams, the tables and the staging of qoimi_compare_images / qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops / qoimi_decode_resized), [2] staging of the
 // host-pointer entry points
 extern "C" void qoimi_workspace_bytes(qoimi_ctx* c, size_t out[3]) {
     out[0] = c ? c->enc_ws.cap + c->enc_stage.cap : 0; out[1] = c ? c->dec_ws.cap + c->insp_ws.cap + c->cmp_ws.cap + c->ver_stage.cap : 0;
@@ -1838,6 +1840,55 @@ extern "C" void qoimi_crop_stats(qoimi_ctx* c, long long out[4]) {
     for (int i = 0; i < 4; ++i) out[i] = c ? c->crop_stats[i] : 0;
 }
 
+// Shared by qoimi_decode_crops and qoimi_decode_resized: both gather from the first rows of the images their items name.
+// true if two of the output ranges [offsets[j], + bytes[j]) overlap
+static bool ranges_overlap(const size_t* offsets, const std::vector<size_t>& bytes) {
+    const size_t n = bytes.size();
+    std::vector<size_t> order(n);
+    std::iota(order.begin(), order.end(), (size_t)0);
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return offsets[a] < offsets[b]; });
+    for (size_t k = 1; k < n; ++k) {
+        const size_t a = order[k - 1], b = order[k];
+        if (offsets[b] - offsets[a] < bytes[a]) return true;   // (sorted: the difference cannot wrap)
+    }
+    return false;
+}
+
+// The plan of qoi_amd/crops.py: plan.  rows[i]: the rows of image i that are decoded, 0: no item names it.  refs: the referenced images,
+// ascending; ref_of: image -> index into refs or -1; slots: width * rows * 4 rounded up to 256; firsts: the sub-batches as indices into refs
+// (pack_plan); at: every slot's offset within its sub-batch; need: the largest sub-batch.
+struct RowsPlan { std::vector<int> refs, ref_of, firsts; std::vector<size_t> slots, at; size_t need = 0; };
+static RowsPlan plan_rows(const qoi_desc* descs, int n_images, const std::vector<uint32_t>& rows, size_t staging_bytes) {
+    RowsPlan p;
+    p.ref_of.assign((size_t)n_images, -1);
+    for (int i = 0; i < n_images; ++i) if (rows[(size_t)i] != 0u) { p.ref_of[(size_t)i] = (int)p.refs.size(); p.refs.push_back(i); }
+    const size_t nr = p.refs.size();
+    p.slots.resize(nr); p.at.resize(nr);
+    for (size_t r = 0; r < nr; ++r) p.slots[r] = up256((size_t)descs[p.refs[r]].width * rows[(size_t)p.refs[r]] * 4u);
+    p.firsts = pack_plan(p.slots, staging_bytes ? staging_bytes : kPackStagingDefault);
+    for (size_t k = 0; k + 1 < p.firsts.size(); ++k) {
+        size_t used = 0;
+        for (int r = p.firsts[k]; r < p.firsts[k + 1]; ++r) { p.at[(size_t)r] = used; used += p.slots[(size_t)r]; }
+        if (used > p.need) p.need = used;
+    }
+    return p;
+}
+
+// Sub-batch k of the plan into the staging arena: one call of the decoder as it is, at 4 output channels and with each descriptor's height
+// shortened to the image's rows.
+static int decode_rows(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs, const RowsPlan& p,
+                       const std::vector<uint32_t>& rows, size_t k, void* stream) {
+    const int first = p.firsts[k], m = p.firsts[k + 1] - first;
+    std::vector<size_t> so; std::vector<int> sz; std::vector<qoi_desc> ds;
+    for (int r = first; r < first + m; ++r) {
+        const int i = p.refs[(size_t)r];
+        qoi_desc d = descs[i];
+        d.height = rows[(size_t)i];
+        so.push_back(stream_offsets[i]); sz.push_back(sizes[i]); ds.push_back(d);
+    }
+    return qoimi_decode_images(c, d_streams, so.data(), sz.data(), ds.data(), m, 4, c->ver_stage.base, p.at.data() + first, stream);
+}
+
 // The referenced images, in ascending order, are planned into sub-batches over slots of w * rows * 4 bytes, rows the last row any crop of
 // the image needs; every sub-batch is one call of the decoder as it is into the staging arena, at 4 output channels and with each
 // descriptor's height shortened to those rows (the decoder decodes to the descriptor it is given: the prefix of the full decode), then one
@@ -1870,37 +1921,22 @@ extern "C" int qoimi_decode_crops(qoimi_ctx* c, const void* d_streams, const siz
         const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_out;   // (so that no address of an output wraps, whatever the offsets)
         if (out_offsets[j] > room || out_bytes[j] > room - out_offsets[j]) return fail(QOIMI_E_ARG, "crop " + std::to_string(j) + ": the output ends behind the address space");
     }
-    {
-        std::vector<size_t> order(n);
-        std::iota(order.begin(), order.end(), (size_t)0);
-        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return out_offsets[a] < out_offsets[b]; });
-        for (size_t k = 1; k < n; ++k) {
-            const size_t a = order[k - 1], b = order[k];
-            if (out_offsets[b] - out_offsets[a] < out_bytes[a]) return fail   // (sorted: the difference cannot wrap)
-               (QOIMI_E_ARG, "the output ranges of two crops overlap");
-        }
-    }
+    if (ranges_overlap(out_offsets, out_bytes)) return fail(QOIMI_E_ARG, "the output ranges of two crops overlap");
     // the plan: a function of descs, crops and staging_bytes alone (qoi_amd/crops.py: plan - packplan.plan over width * rows * 4 of the referenced images)
-    std::vector<int> refs;                                     // the referenced images, ascending
-    std::vector<int> ref_of((size_t)n_images, -1);
-    for (int i = 0; i < n_images; ++i) if (rows[(size_t)i] != 0u) { ref_of[(size_t)i] = (int)refs.size(); refs.push_back(i); }
-    const size_t nr = refs.size();
-    std::vector<size_t> slots(nr), at(nr);
-    for (size_t r = 0; r < nr; ++r) slots[r] = up256((size_t)descs[refs[r]].width * rows[(size_t)refs[r]] * 4u);
-    const std::vector<int> firsts = pack_plan(slots, staging_bytes ? staging_bytes : kPackStagingDefault);
+    const RowsPlan plan = plan_rows(descs, n_images, rows, staging_bytes);
+    const std::vector<int>& ref_of = plan.ref_of;
+    const std::vector<int>& firsts = plan.firsts;
+    const std::vector<size_t>& at = plan.at;
+    const size_t nr = plan.refs.size(), need = plan.need;
     std::vector<size_t> by_ref(n);                             // the crops in the order of their images' sub-batches
     std::iota(by_ref.begin(), by_ref.end(), (size_t)0);
     std::stable_sort(by_ref.begin(), by_ref.end(), [&](size_t a, size_t b) { return ref_of[crops[a].image] < ref_of[crops[b].image]; });
     struct Sub { uint32_t entry, m, tiles; };
     std::vector<Sub> subs(firsts.size() - 1u);
     std::vector<uint32_t> first_tile(n);                       // of by_ref[e], within its sub-batch
-    size_t need = 0;                                           // the largest sub-batch
     {
         size_t e = 0;
         for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-            size_t used = 0;
-            for (int r = firsts[k]; r < firsts[k + 1]; ++r) { at[(size_t)r] = used; used += slots[(size_t)r]; }
-            if (used > need) need = used;
             uint64_t tiles = 0;
             subs[k].entry = (uint32_t)e;
             for (; e < n && ref_of[crops[by_ref[e]].image] < firsts[k + 1]; ++e) {
@@ -1932,22 +1968,142 @@ extern "C" int qoimi_decode_crops(qoimi_ctx* c, const void* d_streams, const siz
     const CropEntry* d_tab = (const CropEntry*)c->cmp_ws.base;
     HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, n * sizeof(CropEntry), hipMemcpyHostToDevice, st));
     const uint32_t most = (uint32_t)c->n_cus * 8u;
-    std::vector<size_t> so; std::vector<int> sz; std::vector<qoi_desc> ds;
     for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-        const int first = firsts[k], m = firsts[k + 1] - first;
-        so.clear(); sz.clear(); ds.clear();
-        for (int r = first; r < first + m; ++r) {
-            const int i = refs[(size_t)r];
-            qoi_desc d = descs[i];
-            d.height = rows[(size_t)i];
-            so.push_back(stream_offsets[i]); sz.push_back(sizes[i]); ds.push_back(d);
-        }
-        const int rc = qoimi_decode_images(c, d_streams, so.data(), sz.data(), ds.data(), m, 4, c->ver_stage.base, at.data() + first, stream);
+        const int rc = decode_rows(c, d_streams, stream_offsets, sizes, descs, plan, rows, k, stream);
         if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
         c->crop_stats[0] += 1;
         launch_crop((const uint8_t*)c->ver_stage.base, d_tab + subs[k].entry, subs[k].m, subs[k].tiles, (uint8_t*)d_out, subs[k].tiles < most ? subs[k].tiles : most, st);
         { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string("crop_gather: ") + hipGetErrorString(e)); } }
         c->crop_stats[1] += 1;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return QOIMI_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// rectangles of a pack's images resampled to fixed sizes (qoi_resize.hip)
+// ------------------------------------------------------------------------------------
+static_assert(sizeof(qoimi_resize) == 32 && offsetof(qoimi_resize, image) == 0 && offsetof(qoimi_resize, x) == 4 && offsetof(qoimi_resize, y) == 8 &&
+              offsetof(qoimi_resize, width) == 12 && offsetof(qoimi_resize, height) == 16 && offsetof(qoimi_resize, out_width) == 20 &&
+              offsetof(qoimi_resize, out_height) == 24 && offsetof(qoimi_resize, flags) == 28, "qoimi_resize layout");
+static_assert(QOIMI_RESIZE_FLIP_X == (int)kResizeFlipX && QOIMI_RESIZE_FLIP_Y == (int)kResizeFlipY, "the table's flag bits");
+static_assert(QOIMI_RESIZE_PLAIN == 0 && QOIMI_RESIZE_ALPHA_WEIGHTED == 1, "the table's mode bit");
+
+// nullptr if the item is fine for an accepted descriptor, else what is wrong with it
+static const char* resize_item_wrong(const qoi_desc* d, const qoimi_resize* r) {
+    if (r->width == 0u || r->height == 0u || r->out_width == 0u || r->out_height == 0u) return "zero width or height";
+    if ((r->flags & ~(unsigned)(QOIMI_RESIZE_FLIP_X | QOIMI_RESIZE_FLIP_Y)) != 0u) return "unknown flag bit";
+    if ((uint64_t)r->x + r->width > d->width || (uint64_t)r->y + r->height > d->height) return "the rectangle leaves its image";
+    if (r->width > (uint64_t)kResizeMaxRatio * r->out_width || r->height > (uint64_t)kResizeMaxRatio * r->out_height) return "reduced by more than 64 in an axis";
+    return nullptr;
+}
+
+// out_width * out_height * och, false if that does not fit a size_t
+static bool resize_bytes(const qoimi_resize* r, unsigned och, size_t* bytes) {
+    const uint64_t px = (uint64_t)r->out_width * r->out_height;
+    if (px > ~(size_t)0 / och) return false;
+    *bytes = (size_t)px * och;
+    return true;
+}
+
+extern "C" size_t qoimi_resize_size(const qoi_desc* desc, const qoimi_resize* item, int channels) {
+    size_t bytes = 0;
+    if (!desc_ok(desc) || !item || (channels != 3 && channels != 4) || resize_item_wrong(desc, item) || !resize_bytes(item, (unsigned)channels, &bytes)) return 0;
+    return bytes;
+}
+
+extern "C" void qoimi_resize_stats(qoimi_ctx* c, long long out[4]) {
+    for (int i = 0; i < 4; ++i) out[i] = c ? c->resize_stats[i] : 0;
+}
+
+// The plan and the sub-batch loop of qoimi_decode_crops (plan_rows, decode_rows) over the items' rectangles; every sub-batch is one call of the
+// decoder as it is into the staging arena, then one launch of resize_filter over the sub-batch's items on the caller's stream; the next
+// sub-batch's decoder is ordered behind it by the stream.
+extern "C" int qoimi_decode_resized(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                    int n_images, int channels, const qoimi_resize* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
+                                    size_t staging_bytes, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    if (mode != QOIMI_RESIZE_PLAIN && mode != QOIMI_RESIZE_ALPHA_WEIGHTED) return fail(QOIMI_E_ARG, "mode must be QOIMI_RESIZE_PLAIN or QOIMI_RESIZE_ALPHA_WEIGHTED");
+    const size_t n = (size_t)n_items;
+    std::vector<uint32_t> rows((size_t)n_images, 0u);          // the rows of image i that are decoded; 0: no item names it
+    std::vector<size_t> out_bytes(n);
+    unsigned och = (unsigned)channels;
+    for (size_t j = 0; j < n; ++j) {
+        const qoimi_resize& r = items[j];
+        if (r.image >= (unsigned)n_images) return fail(QOIMI_E_ARG, "item " + std::to_string(j) + ": no image " + std::to_string(r.image));
+        const size_t i = r.image;
+        if (rows[i] == 0u) {                                   // (an image no item names is never looked at)
+            if (sizes[i] < kHeaderBytes + kTrailerBytes) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + " shorter than 22 bytes (qoi.h:500)");
+            if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:513-521 rules)");
+        }
+        if (channels == 0) {
+            if (och == 0u) och = descs[i].channels;
+            else if (descs[i].channels != och) return fail(QOIMI_E_ARG, "all referenced images of a call must share the output channel count");
+        }
+        if (const char* wrong = resize_item_wrong(&descs[i], &r)) return fail(QOIMI_E_ARG, "item " + std::to_string(j) + ": " + wrong);
+        if (r.y + r.height > rows[i]) rows[i] = r.y + r.height;
+        const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_out;   // (so that no address of an output wraps, whatever the offsets)
+        if (!resize_bytes(&r, och, &out_bytes[j]) || out_offsets[j] > room || out_bytes[j] > room - out_offsets[j]) return fail
+           (QOIMI_E_ARG, "item " + std::to_string(j) + ": the output ends behind the address space");
+    }
+    if (ranges_overlap(out_offsets, out_bytes)) return fail(QOIMI_E_ARG, "the output ranges of two items overlap");
+    // the plan: a function of descs, the items' rectangles and staging_bytes alone (qoi_amd/resize.py: plan - that of qoimi_decode_crops)
+    const RowsPlan plan = plan_rows(descs, n_images, rows, staging_bytes);
+    const std::vector<int>& ref_of = plan.ref_of;
+    const std::vector<int>& firsts = plan.firsts;
+    std::vector<size_t> by_ref(n);                             // the items in the order of their images' sub-batches
+    std::iota(by_ref.begin(), by_ref.end(), (size_t)0);
+    std::stable_sort(by_ref.begin(), by_ref.end(), [&](size_t a, size_t b) { return ref_of[items[a].image] < ref_of[items[b].image]; });
+    struct Sub { uint32_t entry, m, tiles; };
+    std::vector<Sub> subs(firsts.size() - 1u);
+    std::vector<uint32_t> first_tile(n);                       // of by_ref[e], within its sub-batch
+    {
+        size_t e = 0;
+        for (size_t k = 0; k + 1 < firsts.size(); ++k) {
+            uint64_t tiles = 0;
+            subs[k].entry = (uint32_t)e;
+            for (; e < n && ref_of[items[by_ref[e]].image] < firsts[k + 1]; ++e) {
+                if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output pixels in one sub-batch");
+                first_tile[e] = (uint32_t)tiles;
+                const qoimi_resize& r = items[by_ref[e]];
+                tiles += resize_tiles(r.width, r.out_width, r.out_height);
+            }
+            if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output pixels in one sub-batch");
+            subs[k].m = (uint32_t)(e - subs[k].entry); subs[k].tiles = (uint32_t)tiles;
+        }
+    }
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    c->resize_stats[0] = 0; c->resize_stats[1] = 0; c->resize_stats[2] = (long long)plan.need; c->resize_stats[3] = (long long)plan.refs.size();
+    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
+    // one item table for the whole call, through pinned staging; the entries of a sub-batch stand together, their tiles begin at 0
+    const size_t tab_bytes = up256(n * sizeof(ResizeEntry));
+    { const int rc = cmp_pin_reserve(c, tab_bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = c->cmp_ws.reserve(tab_bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = reserve_exact(c->ver_stage, plan.need); if (rc != QOIMI_OK) return rc; }
+    ResizeEntry* h_tab = (ResizeEntry*)c->cmp_pin_buf;
+    const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
+    for (size_t e = 0; e < n; ++e) {
+        const qoimi_resize& r = items[by_ref[e]];
+        ResizeEntry& t = h_tab[e];
+        uint32_t lg, cols;
+        resize_split(r.width, r.out_width, lg, cols);
+        t.src_off = (u64)plan.at[(size_t)ref_of[r.image]]; t.dst_off = (u64)out_offsets[by_ref[e]];
+        t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
+        t.first_tile = first_tile[e]; t.cfg = lg | (cols << 8) | (och << 16) | (weighted << 24) | (r.flags << 28); t.reserved = 0u;
+    }
+    const ResizeEntry* d_tab = (const ResizeEntry*)c->cmp_ws.base;
+    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, n * sizeof(ResizeEntry), hipMemcpyHostToDevice, st));
+    const uint32_t most = (uint32_t)c->n_cus * 8u;
+    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
+        const int rc = decode_rows(c, d_streams, stream_offsets, sizes, descs, plan, rows, k, stream);
+        if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
+        c->resize_stats[0] += 1;
+        launch_resize((const uint8_t*)c->ver_stage.base, d_tab + subs[k].entry, subs[k].m, subs[k].tiles, (uint8_t*)d_out, subs[k].tiles < most ? subs[k].tiles : most, st);
+        { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string("resize_filter: ") + hipGetErrorString(e)); } }
+        c->resize_stats[1] += 1;
     }
     HIP_TRY(hipStreamSynchronize(st));
     return QOIMI_OK;

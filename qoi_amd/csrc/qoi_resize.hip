@@ -1,0 +1,103 @@
+// qoi_resize.hip — qoimi_decode_resized: rectangles of a sub-batch of decoded images resampled to caller-chosen sizes by an exact integer area
+// filter (resize_filter).  gfx950, wave64.  Included by qoi_host.hip and compiled with it (not a translation unit of its own).
+//
+// The result (normative; qoi_amd/resize.py: resize states it in Python, qoi_resize_core.h holds the arithmetic): image i stands in the staging
+// arena as w x rows pixels of 4 bytes (the decoder's output at 4 channels down to the last row an item needs: a 256-aligned slot, every pixel an
+// aligned dword); an item is a rectangle cw x rh of it, resampled to ow x oh pixels with the weights wy * wx of the overlaps, rounded once,
+// plain or with the colours weighted by alpha, rows and / or columns reversed, written tightly packed with och = 3 or 4 bytes per pixel at any
+// byte address.
+//
+//   resize_filter Work is cut over the OUTPUT.  An output pixel overlaps up to 65 x 65 staged pixels (cw <= 64 * ow, rh <= 64 * oh).  Its columns
+//                 belong to L = 1, 2, 4, 8 or 16 neighbouring lanes, chosen from the item's bound of columns per output column (resize_taps)
+//                 so that a lane holds at most four of them (five for 65); lane l takes the columns [k0 + l*c, + c) in every row with a
+//                 weight.  A WORK ITEM is one lane's share; work item = (output pixel of the unflipped result, row-major) * L + l, so consecutive
+//                 lanes read consecutive addresses of a staged row.  TILES of kResizeThreads work items of ONE item are laid over the table
+//                 the host builds (an entry holds its item's first tile); a workgroup takes a contiguous range of tiles - one binary
+//                 search, then it steps on from item to item - so one launch serves every item of a sub-batch.
+//                 A lane computes its column weights once and a row weight per row from the closed form (no table in memory), loads its
+//                 pixels as aligned dwords - plain loads: items may share source pixels - and adds weight * channel into 64-bit sums (four,
+//                 seven with alpha weighting), one 32 x 32 -> 64 multiply-add each.  The L lanes of a pixel add their sums with log2(L)
+//                 butterfly steps over both halves of each sum (L divides 64 and work items are numbered so that a pixel's lanes are
+//                 neighbours in one wavefront); the first of them divides (qoi_resize_core.h) and stores the pixel at its place, mirrored
+//                 or not: one dword where the output holds 4 bytes per pixel and the address is aligned, else 3 or 4 bytes - never a word it
+//                 would have to read first, two outputs may share one.  No LDS, no barrier, no atomics; not one byte outside an item's
+//                 output is written.
+#pragma once
+#include "qoi_dev.h"
+#include "qoi_resize_core.h"
+
+namespace qoimi {
+
+// cfg: log2(L) | c << 8 | och << 16 | (alpha weighted ? 1 : 0) << 24 | flags << 28
+struct ResizeEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, rh, ow, oh, first_tile, cfg, reserved; };
+static_assert(sizeof(ResizeEntry) == 56, "table layout");
+
+struct ResizeMem {
+    const uint32_t* src;
+    __device__ __forceinline__ uint32_t load(u64 i) const { return src[i]; }
+    __device__ __forceinline__ void store1(u64 a, uint32_t v) const { *reinterpret_cast<uint8_t*>(a) = (uint8_t)v; }
+    __device__ __forceinline__ void store4(u64 a, uint32_t v) const { *reinterpret_cast<uint32_t*>(a) = v; }
+};
+
+__device__ __forceinline__ u64 resize_xor_add(u64 v, uint32_t step) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, (int)step), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), (int)step);
+    return v + (((u64)hi << 32) | lo);
+}
+
+// One tile of an item: work items [base, base + kResizeThreads) as far as the item has them.
+template <bool WEIGHTED>
+__device__ __forceinline__ void resize_tile(const ResizeMem& mem, u64 q, const ResizeEntry& e, u64 base) {
+    const uint32_t lg = e.cfg & 255u, c = (e.cfg >> 8) & 255u, och = (e.cfg >> 16) & 255u;
+    const ResizeGeom g = {e.w, e.x, e.y, e.cw, e.rh, e.ow, e.oh, e.cfg >> 28};
+    const u64 item = base + threadIdx.x, o = item >> lg;
+    const uint32_t l = (uint32_t)item & ((1u << lg) - 1u);
+    const bool valid = o < (u64)e.ow * e.oh;                      // (a pixel's lanes are valid or not together)
+    const uint32_t Y = valid ? (uint32_t)resize_div(o, e.ow) : 0u, X = valid ? (uint32_t)(o - (u64)Y * e.ow) : 0u;
+    ResizeSums s;
+    if (valid) resize_lane<WEIGHTED>(mem, g, X, Y, l, c, s);
+    else {
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) s.S[k] = 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < 3u; ++k) s.W[k] = 0u;
+    }
+    for (uint32_t step = 1u; step < (1u << lg); step <<= 1) {    // (lg is the item's: the whole workgroup takes the same steps)
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) s.S[k] = resize_xor_add(s.S[k], step);
+        if (WEIGHTED) {
+#pragma unroll
+            for (uint32_t k = 0; k < 3u; ++k) s.W[k] = resize_xor_add(s.W[k], step);
+        }
+    }
+    if (valid && l == 0u) resize_finish(mem, g, q, och, WEIGHTED, X, Y, s);
+}
+
+__global__ __launch_bounds__(kResizeThreads) void resize_filter(const uint8_t* __restrict__ stage, const ResizeEntry* __restrict__ tab, uint32_t m, uint32_t tiles,
+                                                                 uint8_t* out) {
+    const u64 per_wg = ((u64)tiles + gridDim.x - 1u) / gridDim.x;
+    const u64 lo64 = (u64)blockIdx.x * per_wg, hi64 = lo64 + per_wg < (u64)tiles ? lo64 + per_wg : (u64)tiles;
+    if (lo64 >= hi64) return;
+    const uint32_t t_lo = (uint32_t)lo64, t_hi = (uint32_t)hi64;
+    uint32_t i = 0;                                               // the item of tile t_lo: the last one whose first tile is not behind it
+    for (uint32_t hi = m - 1u; i < hi;) {
+        const uint32_t mid = i + (hi - i + 1u) / 2u;
+        if (tab[mid].first_tile <= t_lo) i = mid; else hi = mid - 1u;
+    }
+    for (uint32_t t = t_lo; t < t_hi; ++t) {
+        if (i + 1u < m && tab[i + 1u].first_tile <= t) ++i;       // (every item has a tile: one step at most)
+        const ResizeEntry e = tab[i];
+        const ResizeMem mem = {reinterpret_cast<const uint32_t*>(stage + e.src_off)};
+        const u64 q = (u64)reinterpret_cast<uintptr_t>(out) + e.dst_off;
+        const u64 base = (u64)(t - e.first_tile) * kResizeThreads;
+        if ((e.cfg >> 24) & 1u) resize_tile<true>(mem, q, e, base);
+        else resize_tile<false>(mem, q, e, base);
+    }
+}
+
+// The kernel over the m table entries at tab (their tiles: [0, tiles)); grid: workgroups, at most `tiles`.  No timer marks: the kernel has no
+// entry in the name table (qoimi_resize_stats counts its launches).
+void launch_resize(const uint8_t* stage, const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, uint32_t grid, hipStream_t st) {
+    hipLaunchKernelGGL(resize_filter, dim3(grid), dim3(kResizeThreads), 0, st, stage, tab, m, tiles, out);
+}
+
+}  // namespace qoimi
