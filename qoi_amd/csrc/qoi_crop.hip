@@ -14,8 +14,8 @@
 //                 last word of a crop may be partial (both in one for a crop shorter than a word): such a lane writes the crop's own bytes
 //                 with byte, halfword and dword stores, never a word it would have to read first - two crops may share an aligned word and
 //                 are served by different lanes.  TILES of kCropThreads items of ONE crop are laid over the crop table the host builds (an
-//                 entry holds its crop's first tile); a workgroup takes a contiguous range of tiles - one binary search, then it steps on
-//                 from crop to crop - so one launch serves every crop of a sub-batch.  No LDS, no barrier, no atomics; not one byte
+//                 entry holds its crop's first tile); a workgroup takes a contiguous range of tiles (qoi_dev.h: walk_tiles), so one launch
+//                 serves every crop of a sub-batch.  No LDS, no barrier, no atomics; not one byte
 //                 outside a crop's output is written.
 #pragma once
 #include "qoi_dev.h"
@@ -43,29 +43,18 @@ struct CropMem {
 
 __global__ __launch_bounds__(kCropThreads) void crop_gather(const uint8_t* __restrict__ stage, const CropEntry* __restrict__ tab, uint32_t m, uint32_t tiles,
                                                              uint8_t* out) {
-    const u64 per_wg = ((u64)tiles + gridDim.x - 1u) / gridDim.x;
-    const u64 lo64 = (u64)blockIdx.x * per_wg, hi64 = lo64 + per_wg < (u64)tiles ? lo64 + per_wg : (u64)tiles;
-    if (lo64 >= hi64) return;
-    const uint32_t t_lo = (uint32_t)lo64, t_hi = (uint32_t)hi64;
-    uint32_t i = 0;                                               // the crop of tile t_lo: the last one whose first tile is not behind it
-    for (uint32_t hi = m - 1u; i < hi;) {
-        const uint32_t mid = i + (hi - i + 1u) / 2u;
-        if (tab[mid].first_tile <= t_lo) i = mid; else hi = mid - 1u;
-    }
-    for (uint32_t t = t_lo; t < t_hi; ++t) {
-        if (i + 1u < m && tab[i + 1u].first_tile <= t) ++i;       // (every crop has a tile: one step at most)
-        const CropEntry e = tab[i];
+    walk_tiles(tab, m, tiles, [&](const CropEntry& e, uint32_t tile) {
         const uint32_t och = e.cfg & 255u;
         const CropRect g = {e.w, e.x, e.y, e.cw, e.ch, e.cfg >> 8};
         const CropMem mem = {reinterpret_cast<const uint32_t*>(stage + e.src_off)};
         const u64 q = (u64)reinterpret_cast<uintptr_t>(out) + e.dst_off;
         const uint32_t B = e.cw * e.ch * och;                     // (an image holds fewer than 400 000 000 pixels)
-        const u64 k = (u64)(t - e.first_tile) * kCropThreads + threadIdx.x;
+        const u64 k = (u64)tile * kCropThreads + threadIdx.x;
         if (k < crop_items(q, B)) {
             if (och == 3u) crop_item<3u>(mem, g, q, B, (uint32_t)k);
             else crop_item<4u>(mem, g, q, B, (uint32_t)k);
         }
-    }
+    });
 }
 
 // The kernel over the m table entries at tab (their tiles: [0, tiles)); grid: workgroups, at most `tiles`.  No timer marks: the kernel has no

@@ -64,6 +64,30 @@ __device__ __forceinline__ int wave_max(int v) {
     return v;
 }
 
+// The tile walk of the table-driven kernels over staged pixels (thumb_reduce, crop_gather, resize_filter).  The host lays `tiles` tiles over
+// a table of m entries - any struct with a first_tile; every entry has a tile, the first_tile ascend from 0 - and launches at most `tiles`
+// workgroups.  A workgroup takes a contiguous range of tiles: one binary search for the entry of its first tile (the last one whose first
+// tile is not behind it), then it steps on from entry to entry, one step at most per tile.  body(entry, tile within the entry) runs once per
+// tile and is reached by every thread of the workgroup together (nothing here depends on the lane), so it may hold cross-lane operations.
+// (cmp_pixels walks its table the same way but has work to do at every step to the next entry; it keeps its own loop.)
+template <class Entry, class Body>
+__device__ __forceinline__ void walk_tiles(const Entry* __restrict__ tab, uint32_t m, uint32_t tiles, Body body) {
+    const u64 per_wg = ((u64)tiles + gridDim.x - 1u) / gridDim.x;
+    const u64 lo64 = (u64)blockIdx.x * per_wg, hi64 = lo64 + per_wg < (u64)tiles ? lo64 + per_wg : (u64)tiles;
+    if (lo64 >= hi64) return;
+    const uint32_t t_lo = (uint32_t)lo64, t_hi = (uint32_t)hi64;
+    uint32_t i = 0;
+    for (uint32_t hi = m - 1u; i < hi;) {
+        const uint32_t mid = i + (hi - i + 1u) / 2u;
+        if (tab[mid].first_tile <= t_lo) i = mid; else hi = mid - 1u;
+    }
+    for (uint32_t t = t_lo; t < t_hi; ++t) {
+        if (i + 1u < m && tab[i + 1u].first_tile <= t) ++i;
+        const Entry e = tab[i];
+        body(e, t - e.first_tile);
+    }
+}
+
 // Relaxed agent-scope 8-byte granules ("the data is the flag", guide G16 R2).
 __device__ __forceinline__ void granule_store(u64* p, u64 v) {
     __hip_atomic_store((gu64*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

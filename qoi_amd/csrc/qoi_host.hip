@@ -29,6 +29,7 @@
 #pragma GCC visibility pop
 #include "qoi_decode_core.h"
 #include "qoi_kernels.h"
+#include "qoi_stage_plan.h"   // the plans of the calls that work through bounded staging: host arithmetic alone, tested without a GPU
 #include "qoi_pack.hip"        // the pack kernels and their launchers: part of this translation unit (no build lists the file itself)
 #include "qoi_inspect.hip"     // ... and the kernels of qoimi_inspect_streams, the same way
 #include "qoi_compare.hip"     // ... and those of qoimi_compare_images / qoimi_verify_images
@@ -1258,23 +1259,7 @@ extern "C" int qoimi_pack_streams(qoimi_ctx* c, const void* d_streams, size_t st
 // ------------------------------------------------------------------------------------
 // encode into a pack through bounded staging
 // ------------------------------------------------------------------------------------
-// The staging qoimi_encode_packed takes when the caller passes 0.
-static const size_t kPackStagingDefault = (size_t)1 << 30;
-
-// The sub-batch plan (normative; qoi_amd/packplan.py: plan states it in Python): a slot is an image's encode bound rounded up to 256 bytes,
-// images are taken in order, a sub-batch closes when the next slot would not fit in staging_bytes - but never empty: a slot larger than the
-// request is a sub-batch of its own.  Returns the first image of every sub-batch and, behind the last one, n.
-static std::vector<int> pack_plan(const std::vector<size_t>& slots, size_t staging_bytes) {
-    std::vector<int> firsts(1, 0);
-    size_t used = 0;
-    for (size_t i = 0; i < slots.size(); ++i) {
-        if ((int)i > firsts.back() && (slots[i] > staging_bytes || used > staging_bytes - slots[i])) { firsts.push_back((int)i); used = 0; }
-        used += slots[i];
-    }
-    firsts.push_back((int)slots.size());
-    return firsts;
-}
-
+// (the sub-batch plan: qoi_stage_plan.h: stage_plan)
 static int pin_reserve(qoimi_ctx* c, size_t bytes) {
     if (bytes <= c->pin_cap) return QOIMI_OK;
     if (c->pin_buf) (void)hipHostFree(c->pin_buf);
@@ -1293,19 +1278,16 @@ static int encode_packed(qoimi_ctx* c, const void* d_pixels, size_t pixel_stride
                          size_t staging_bytes, unsigned long long* packed_off_out, int* stream_len_out, void* stream) {
     const bool mixed = pixel_offsets != nullptr;
     const size_t n = (size_t)n_images;
-    std::vector<size_t> slots(n), src(n);
+    std::vector<size_t> slots(n);
     size_t largest = 0;
     for (size_t i = 0; i < n; ++i) {
-        slots[i] = (qoimi_encode_bound(&descs[mixed ? i : 0]) + 255u) & ~(size_t)255u;
+        slots[i] = up256(qoimi_encode_bound(&descs[mixed ? i : 0]));
         if (slots[i] > largest) largest = slots[i];
     }
-    const std::vector<int> firsts = pack_plan(slots, staging_bytes ? staging_bytes : kPackStagingDefault);
-    size_t need = 0;                                         // the largest sub-batch
-    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-        size_t at = 0;
-        for (int i = firsts[k]; i < firsts[k + 1]; ++i) { src[(size_t)i] = at; at += slots[(size_t)i]; }
-        if (at > need) need = at;
-    }
+    const StagePlan plan = stage_plan(slots, staging_bytes);
+    const std::vector<int>& firsts = plan.firsts;
+    const std::vector<size_t>& src = plan.at;                // where stream i lies in the staging of its sub-batch
+    const size_t need = plan.need;
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)stream;
     if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
@@ -1537,8 +1519,6 @@ static int cmp_pin_reserve(qoimi_ctx* c, size_t bytes) {
     return QOIMI_OK;
 }
 
-static inline size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
 // Fills entry `e` for an image of npx pixels and returns the tiles it takes.
 static uint32_t cmp_entry(CmpImage* e, size_t a_off, size_t b_off, size_t npx, uint32_t first_tile, unsigned ca, unsigned cb, unsigned ra, unsigned rb, uint32_t index) {
     e->a_off = (u64)a_off; e->b_off = (u64)b_off; e->npx = (uint32_t)npx; e->first_tile = first_tile;
@@ -1630,15 +1610,12 @@ extern "C" int qoimi_verify_images(qoimi_ctx* c, const void* d_pixels, const siz
     }
     if (all_tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of pixels in one call");
     // the plan: a function of descs and staging_bytes alone (qoi_amd/packplan.py: plan over width * height * och)
-    std::vector<size_t> slots(n), at(n);
+    std::vector<size_t> slots(n);
     for (size_t i = 0; i < n; ++i) slots[i] = up256((size_t)descs[i].width * descs[i].height * och);
-    const std::vector<int> firsts = pack_plan(slots, staging_bytes ? staging_bytes : kPackStagingDefault);
-    size_t need = 0;                                           // the largest sub-batch
-    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-        size_t used = 0;
-        for (int i = firsts[k]; i < firsts[k + 1]; ++i) { at[(size_t)i] = used; used += slots[(size_t)i]; }
-        if (used > need) need = used;
-    }
+    const StagePlan plan = stage_plan(slots, staging_bytes);
+    const std::vector<int>& firsts = plan.firsts;
+    const std::vector<size_t>& at = plan.at;
+    const size_t need = plan.need;
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)stream;
     if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
@@ -1714,6 +1691,99 @@ extern "C" int qoimi_verify_images(qoimi_ctx* c, const void* d_pixels, const siz
 }
 
 // ------------------------------------------------------------------------------------
+// decode through staging, then one table-driven kernel per sub-batch: what qoimi_decode_thumbnails, qoimi_decode_crops and
+// qoimi_decode_resized share (their plans: qoi_stage_plan.h)
+// ------------------------------------------------------------------------------------
+// Sub-batch k of the plan into the staging arena: one call of the decoder as it is, at 4 output channels (every staged pixel an aligned
+// dword) and with each descriptor's height shortened to the image's rows (the decoder decodes to the descriptor it is given: the prefix of
+// the full decode).
+static int decode_rows(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs, const RowsPlan& p,
+                       const std::vector<uint32_t>& rows, size_t k, void* stream) {
+    const int first = p.firsts[k], m = p.firsts[k + 1] - first;
+    std::vector<size_t> so; std::vector<int> sz; std::vector<qoi_desc> ds;
+    for (int r = first; r < first + m; ++r) {
+        const int i = p.refs[(size_t)r];
+        qoi_desc d = descs[i];
+        d.height = rows[(size_t)i];
+        so.push_back(stream_offsets[i]); sz.push_back(sizes[i]); ds.push_back(d);
+    }
+    return qoimi_decode_images(c, d_streams, so.data(), sz.data(), ds.data(), m, 4, c->ver_stage.base, p.at.data() + first, stream);
+}
+
+// What check_items makes of a call's items.  rows[i]: the rows of image i that are decoded, 0: no item names it; out_bytes[j]: the bytes of
+// output j; och: the output channel count of the call.
+struct CheckedItems { std::vector<uint32_t> rows; std::vector<size_t> out_bytes; unsigned och = 0; };
+
+// The items of qoimi_decode_crops (`noun` "crop") and of qoimi_decode_resized ("item"), looked at in the order that decides which message a
+// call with several faults gets.  wrong(desc, item): nullptr if the item is fine for an accepted descriptor, else what is wrong with it;
+// bytes_of(item, och, &bytes): false if the output's size does not fit a size_t.
+template <class Item, class Wrong, class Bytes>
+static int check_items(const std::string& noun, const int* sizes, const qoi_desc* descs, int n_images, int channels, const Item* items, size_t n,
+                       const void* d_out, const size_t* out_offsets, Wrong wrong, Bytes bytes_of, CheckedItems& out) {
+    std::vector<uint32_t>& rows = out.rows;
+    rows.assign((size_t)n_images, 0u);
+    out.out_bytes.resize(n);
+    unsigned och = (unsigned)channels;
+    for (size_t j = 0; j < n; ++j) {
+        const Item& r = items[j];
+        if (r.image >= (unsigned)n_images) return fail(QOIMI_E_ARG, noun + " " + std::to_string(j) + ": no image " + std::to_string(r.image));
+        const size_t i = r.image;
+        if (rows[i] == 0u) {                                   // (an image no item names is never looked at)
+            if (sizes[i] < kHeaderBytes + kTrailerBytes) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + " shorter than 22 bytes (qoi.h:500)");
+            if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:513-521 rules)");
+        }
+        if (channels == 0) {
+            if (och == 0u) och = descs[i].channels;
+            else if (descs[i].channels != och) return fail(QOIMI_E_ARG, "all referenced images of a call must share the output channel count");
+        }
+        if (const char* what = wrong(&descs[i], &r)) return fail(QOIMI_E_ARG, noun + " " + std::to_string(j) + ": " + what);
+        if (r.y + r.height > rows[i]) rows[i] = r.y + r.height;
+        const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_out;   // (so that no address of an output wraps, whatever the offsets)
+        if (!bytes_of(&r, och, &out.out_bytes[j]) || out_offsets[j] > room || out.out_bytes[j] > room - out_offsets[j]) return fail
+           (QOIMI_E_ARG, noun + " " + std::to_string(j) + ": the output ends behind the address space");
+    }
+    if (ranges_overlap(out_offsets, out.out_bytes)) return fail(QOIMI_E_ARG, "the output ranges of two " + noun + "s overlap");
+    out.och = och;
+    return QOIMI_OK;
+}
+
+// Everything behind "the plan is made and the call is accepted".  One table for the whole call, through pinned staging: fill(entry, e) writes
+// entry e (of item items.by_ref[e]; the entries of a sub-batch stand together, their tiles begin at 0).  Then, sub-batch by sub-batch, one call
+// of the decoder as it is into the staging arena and one launch over the sub-batch's entries on the caller's stream -
+// launch(its entries on the device, m, tiles, workgroups, stream), `kernel` in the message if it fails; the next sub-batch's decoder is ordered
+// behind it by the stream.  stats: sub-batches decoded, launches, bytes of staging planned, `decoded`.
+template <class Entry, class Fill, class Launch>
+static int run_staged(qoimi_ctx* c, long long (&stats)[4], long long decoded, const char* kernel, const void* d_streams, const size_t* stream_offsets,
+                      const int* sizes, const qoi_desc* descs, const RowsPlan& plan, const std::vector<uint32_t>& rows, const ItemPlan& items,
+                      Fill fill, Launch launch, void* stream) {
+    const size_t n = items.by_ref.size();
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    stats[0] = 0; stats[1] = 0; stats[2] = (long long)plan.need; stats[3] = decoded;
+    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
+    const size_t tab_bytes = up256(n * sizeof(Entry));
+    { const int rc = cmp_pin_reserve(c, tab_bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = c->cmp_ws.reserve(tab_bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = reserve_exact(c->ver_stage, plan.need); if (rc != QOIMI_OK) return rc; }
+    Entry* h_tab = (Entry*)c->cmp_pin_buf;
+    for (size_t e = 0; e < n; ++e) fill(h_tab[e], e);
+    const Entry* d_tab = (const Entry*)c->cmp_ws.base;
+    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, n * sizeof(Entry), hipMemcpyHostToDevice, st));
+    const uint32_t most = (uint32_t)c->n_cus * 8u;
+    for (size_t k = 0; k < items.subs.size(); ++k) {
+        const ItemSub& s = items.subs[k];
+        const int rc = decode_rows(c, d_streams, stream_offsets, sizes, descs, plan, rows, k, stream);
+        if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
+        stats[0] += 1;
+        launch(d_tab + s.entry, s.m, s.tiles, s.tiles < most ? s.tiles : most, st);
+        { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string(kernel) + ": " + hipGetErrorString(e)); } }
+        stats[1] += 1;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return QOIMI_OK;
+}
+
+// ------------------------------------------------------------------------------------
 // thumbnails of a pack (qoi_thumb.hip)
 // ------------------------------------------------------------------------------------
 static_assert(QOIMI_THUMB_PLAIN == 0 && QOIMI_THUMB_ALPHA_WEIGHTED == 1, "the table's mode bit");
@@ -1730,8 +1800,8 @@ extern "C" void qoimi_thumbnail_stats(qoimi_ctx* c, long long out[4]) {
     for (int i = 0; i < 4; ++i) out[i] = c ? c->thumb_stats[i] : 0;
 }
 
-// Every sub-batch of the plan is one call of the decoder as it is into the staging arena, at 4 output channels (every staged pixel an aligned
-// dword), then one launch of thumb_reduce on the caller's stream; the next sub-batch's decoder is ordered behind it by the stream.
+// The plan of the gather calls with every image referenced at its full height and item j naming image j (qoi_amd/packplan.py: plan over
+// width * height * 4); run_staged with one launch of thumb_reduce per sub-batch.
 extern "C" int qoimi_decode_thumbnails(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                        int n_images, int channels, const unsigned* factors, int mode, void* d_thumbs, const size_t* thumb_offsets,
                                        size_t staging_bytes, void* stream) {
@@ -1740,80 +1810,37 @@ extern "C" int qoimi_decode_thumbnails(qoimi_ctx* c, const void* d_streams, cons
     if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
     if (mode != QOIMI_THUMB_PLAIN && mode != QOIMI_THUMB_ALPHA_WEIGHTED) return fail(QOIMI_E_ARG, "mode must be QOIMI_THUMB_PLAIN or QOIMI_THUMB_ALPHA_WEIGHTED");
     const size_t n = (size_t)n_images;
-    std::vector<size_t> out_bytes(n), slots(n), at(n);
+    std::vector<size_t> out_bytes(n);
+    std::vector<uint32_t> rows(n), image_of(n);
+    std::vector<uint64_t> tiles_of(n);
     for (size_t i = 0; i < n; ++i) {
         if (sizes[i] < kHeaderBytes + kTrailerBytes) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + " shorter than 22 bytes (qoi.h:500)");
         if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:513-521 rules)");
         if (channels == 0 && descs[i].channels != descs[0].channels) return fail(QOIMI_E_ARG, "all images of a call must share the output channel count");
         if (factors[i] < 1u || factors[i] > kThumbMaxFactor) return fail(QOIMI_E_ARG, "factor " + std::to_string(i) + " outside 1..64");
         out_bytes[i] = (size_t)thumb_extent(descs[i].width, factors[i]) * thumb_extent(descs[i].height, factors[i]) * (size_t)(channels ? channels : descs[i].channels);
-        slots[i] = up256((size_t)descs[i].width * descs[i].height * 4u);
+        rows[i] = descs[i].height; image_of[i] = (uint32_t)i;
+        tiles_of[i] = thumb_tiles(descs[i].width, descs[i].height, factors[i]);
     }
     const unsigned och = channels ? (unsigned)channels : descs[0].channels;
-    {
-        std::vector<int> order(n);
-        std::iota(order.begin(), order.end(), 0);
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return thumb_offsets[a] < thumb_offsets[b]; });
-        for (size_t k = 1; k < n; ++k) {
-            const size_t a = (size_t)order[k - 1], b = (size_t)order[k];
-            if (thumb_offsets[b] - thumb_offsets[a] < out_bytes[a]) return fail   // (sorted: the difference cannot wrap)
-               (QOIMI_E_ARG, "the output ranges of two thumbnails overlap");
-        }
-    }
-    // the plan: a function of descs and staging_bytes alone (qoi_amd/packplan.py: plan over width * height * 4)
-    const std::vector<int> firsts = pack_plan(slots, staging_bytes ? staging_bytes : kPackStagingDefault);
-    struct Sub { uint32_t tiles; };
-    std::vector<Sub> subs(firsts.size() - 1u);
-    size_t need = 0;                                           // the largest sub-batch
-    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-        size_t used = 0;
-        uint64_t tiles = 0;
-        for (int i = firsts[k]; i < firsts[k + 1]; ++i) {
-            at[(size_t)i] = used; used += slots[(size_t)i];
-            tiles += thumb_tiles(descs[i].width, descs[i].height, factors[i]);
-        }
-        if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of thumbnail pixels in one sub-batch");
-        subs[k].tiles = (uint32_t)tiles;
-        if (used > need) need = used;
-    }
-    DeviceGuard guard(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    c->thumb_stats[0] = 0; c->thumb_stats[1] = 0; c->thumb_stats[2] = (long long)need; c->thumb_stats[3] = 0;
-    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
-    // one image table for the whole call, through pinned staging; the entries of a sub-batch stand together, their tiles begin at 0
-    const size_t tab_bytes = up256(n * sizeof(ThumbImage));
-    { const int rc = cmp_pin_reserve(c, tab_bytes); if (rc != QOIMI_OK) return rc; }
-    { const int rc = c->cmp_ws.reserve(tab_bytes); if (rc != QOIMI_OK) return rc; }
-    { const int rc = reserve_exact(c->ver_stage, need); if (rc != QOIMI_OK) return rc; }
-    ThumbImage* h_tab = (ThumbImage*)c->cmp_pin_buf;
+    // (unlike check_items, this call has never looked whether an output ends inside the address space)
+    if (ranges_overlap(thumb_offsets, out_bytes)) return fail(QOIMI_E_ARG, "the output ranges of two thumbnails overlap");
+    const RowsPlan plan = plan_rows(descs, n_images, rows, staging_bytes);
+    const ItemPlan items = plan_items(image_of, plan.ref_of, plan.firsts, tiles_of);   // (entry i is image i)
+    if (items.overflow) return fail(QOIMI_E_ARG, "more than 2^31 tiles of thumbnail pixels in one sub-batch");
     const uint32_t weighted = (mode == QOIMI_THUMB_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
-    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-        uint32_t t = 0;
-        for (int i = firsts[k]; i < firsts[k + 1]; ++i) {
-            ThumbImage& e = h_tab[i];
+    return run_staged<ThumbImage>(c, c->thumb_stats, 0, "thumb_reduce", d_streams, stream_offsets, sizes, descs, plan, rows, items,
+        [&](ThumbImage& e, size_t i) {
             uint32_t lg, cols;
             thumb_split(factors[i], lg, cols);
-            e.src_off = (u64)at[(size_t)i]; e.dst_off = (u64)thumb_offsets[i];
+            e.src_off = (u64)plan.at[i]; e.dst_off = (u64)thumb_offsets[i];
             e.w = descs[i].width; e.h = descs[i].height; e.f = factors[i];
             e.tw = thumb_extent(e.w, e.f); e.th = thumb_extent(e.h, e.f);
-            e.first_tile = t; e.cfg = lg | (cols << 8) | (och << 16) | (weighted << 24); e.reserved = 0u;
-            t += (uint32_t)thumb_tiles(e.w, e.h, e.f);
-        }
-    }
-    const ThumbImage* d_tab = (const ThumbImage*)c->cmp_ws.base;
-    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, n * sizeof(ThumbImage), hipMemcpyHostToDevice, st));
-    const uint32_t most = (uint32_t)c->n_cus * 8u;
-    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-        const int first = firsts[k], m = firsts[k + 1] - first;
-        const int rc = qoimi_decode_images(c, d_streams, stream_offsets + first, sizes + first, descs + first, m, 4, c->ver_stage.base, at.data() + first, stream);
-        if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
-        c->thumb_stats[0] += 1;
-        launch_thumb((const uint8_t*)c->ver_stage.base, d_tab + first, (uint32_t)m, subs[k].tiles, (uint8_t*)d_thumbs, subs[k].tiles < most ? subs[k].tiles : most, st);
-        { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string("thumb_reduce: ") + hipGetErrorString(e)); } }
-        c->thumb_stats[1] += 1;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return QOIMI_OK;
+            e.first_tile = items.first_tile[i]; e.cfg = lg | (cols << 8) | (och << 16) | (weighted << 24); e.reserved = 0u;
+        },
+        [&](const ThumbImage* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            launch_thumb((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_thumbs, grid, st);
+        }, stream);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1831,6 +1858,12 @@ static const char* crop_rect_wrong(const qoi_desc* d, const qoimi_crop* r) {
     return nullptr;
 }
 
+// width * height * och (a rectangle inside an image: it always fits)
+static bool crop_bytes(const qoimi_crop* r, unsigned och, size_t* bytes) {
+    *bytes = (size_t)r->width * r->height * och;
+    return true;
+}
+
 extern "C" size_t qoimi_crop_size(const qoi_desc* desc, const qoimi_crop* crop, int channels) {
     if (!desc_ok(desc) || !crop || (channels != 3 && channels != 4) || crop_rect_wrong(desc, crop)) return 0;
     return (size_t)crop->width * crop->height * (size_t)channels;
@@ -1840,59 +1873,9 @@ extern "C" void qoimi_crop_stats(qoimi_ctx* c, long long out[4]) {
     for (int i = 0; i < 4; ++i) out[i] = c ? c->crop_stats[i] : 0;
 }
 
-// Shared by qoimi_decode_crops and qoimi_decode_resized: both gather from the first rows of the images their items name.
-// true if two of the output ranges [offsets[j], + bytes[j]) overlap
-static bool ranges_overlap(const size_t* offsets, const std::vector<size_t>& bytes) {
-    const size_t n = bytes.size();
-    std::vector<size_t> order(n);
-    std::iota(order.begin(), order.end(), (size_t)0);
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return offsets[a] < offsets[b]; });
-    for (size_t k = 1; k < n; ++k) {
-        const size_t a = order[k - 1], b = order[k];
-        if (offsets[b] - offsets[a] < bytes[a]) return true;   // (sorted: the difference cannot wrap)
-    }
-    return false;
-}
-
-// The plan of qoi_amd/crops.py: plan.  rows[i]: the rows of image i that are decoded, 0: no item names it.  refs: the referenced images,
-// ascending; ref_of: image -> index into refs or -1; slots: width * rows * 4 rounded up to 256; firsts: the sub-batches as indices into refs
-// (pack_plan); at: every slot's offset within its sub-batch; need: the largest sub-batch.
-struct RowsPlan { std::vector<int> refs, ref_of, firsts; std::vector<size_t> slots, at; size_t need = 0; };
-static RowsPlan plan_rows(const qoi_desc* descs, int n_images, const std::vector<uint32_t>& rows, size_t staging_bytes) {
-    RowsPlan p;
-    p.ref_of.assign((size_t)n_images, -1);
-    for (int i = 0; i < n_images; ++i) if (rows[(size_t)i] != 0u) { p.ref_of[(size_t)i] = (int)p.refs.size(); p.refs.push_back(i); }
-    const size_t nr = p.refs.size();
-    p.slots.resize(nr); p.at.resize(nr);
-    for (size_t r = 0; r < nr; ++r) p.slots[r] = up256((size_t)descs[p.refs[r]].width * rows[(size_t)p.refs[r]] * 4u);
-    p.firsts = pack_plan(p.slots, staging_bytes ? staging_bytes : kPackStagingDefault);
-    for (size_t k = 0; k + 1 < p.firsts.size(); ++k) {
-        size_t used = 0;
-        for (int r = p.firsts[k]; r < p.firsts[k + 1]; ++r) { p.at[(size_t)r] = used; used += p.slots[(size_t)r]; }
-        if (used > p.need) p.need = used;
-    }
-    return p;
-}
-
-// Sub-batch k of the plan into the staging arena: one call of the decoder as it is, at 4 output channels and with each descriptor's height
-// shortened to the image's rows.
-static int decode_rows(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs, const RowsPlan& p,
-                       const std::vector<uint32_t>& rows, size_t k, void* stream) {
-    const int first = p.firsts[k], m = p.firsts[k + 1] - first;
-    std::vector<size_t> so; std::vector<int> sz; std::vector<qoi_desc> ds;
-    for (int r = first; r < first + m; ++r) {
-        const int i = p.refs[(size_t)r];
-        qoi_desc d = descs[i];
-        d.height = rows[(size_t)i];
-        so.push_back(stream_offsets[i]); sz.push_back(sizes[i]); ds.push_back(d);
-    }
-    return qoimi_decode_images(c, d_streams, so.data(), sz.data(), ds.data(), m, 4, c->ver_stage.base, p.at.data() + first, stream);
-}
-
 // The referenced images, in ascending order, are planned into sub-batches over slots of w * rows * 4 bytes, rows the last row any crop of
-// the image needs; every sub-batch is one call of the decoder as it is into the staging arena, at 4 output channels and with each
-// descriptor's height shortened to those rows (the decoder decodes to the descriptor it is given: the prefix of the full decode), then one
-// launch of crop_gather over the sub-batch's crops on the caller's stream; the next sub-batch's decoder is ordered behind it by the stream.
+// the image needs (qoi_amd/crops.py: plan - a function of descs, crops and staging_bytes alone); run_staged with one launch of crop_gather
+// over the sub-batch's crops.
 extern "C" int qoimi_decode_crops(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                   int n_images, int channels, const qoimi_crop* crops, int n_crops, void* d_out, const size_t* out_offsets,
                                   size_t staging_bytes, void* stream) {
@@ -1900,84 +1883,26 @@ extern "C" int qoimi_decode_crops(qoimi_ctx* c, const void* d_streams, const siz
     if (!c || !d_streams || !stream_offsets || !sizes || !descs || !crops || !d_out || !out_offsets || n_images <= 0 || n_crops <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
     if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
     const size_t n = (size_t)n_crops;
-    std::vector<uint32_t> rows((size_t)n_images, 0u);          // the rows of image i that are decoded; 0: no crop names it
-    std::vector<size_t> out_bytes(n);
-    unsigned och = (unsigned)channels;
-    for (size_t j = 0; j < n; ++j) {
-        const qoimi_crop& r = crops[j];
-        if (r.image >= (unsigned)n_images) return fail(QOIMI_E_ARG, "crop " + std::to_string(j) + ": no image " + std::to_string(r.image));
-        const size_t i = r.image;
-        if (rows[i] == 0u) {                                   // (an image no crop names is never looked at)
-            if (sizes[i] < kHeaderBytes + kTrailerBytes) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + " shorter than 22 bytes (qoi.h:500)");
-            if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:513-521 rules)");
-        }
-        if (channels == 0) {
-            if (och == 0u) och = descs[i].channels;
-            else if (descs[i].channels != och) return fail(QOIMI_E_ARG, "all referenced images of a call must share the output channel count");
-        }
-        if (const char* wrong = crop_rect_wrong(&descs[i], &r)) return fail(QOIMI_E_ARG, "crop " + std::to_string(j) + ": " + wrong);
-        if (r.y + r.height > rows[i]) rows[i] = r.y + r.height;
-        out_bytes[j] = (size_t)r.width * r.height * och;
-        const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_out;   // (so that no address of an output wraps, whatever the offsets)
-        if (out_offsets[j] > room || out_bytes[j] > room - out_offsets[j]) return fail(QOIMI_E_ARG, "crop " + std::to_string(j) + ": the output ends behind the address space");
-    }
-    if (ranges_overlap(out_offsets, out_bytes)) return fail(QOIMI_E_ARG, "the output ranges of two crops overlap");
-    // the plan: a function of descs, crops and staging_bytes alone (qoi_amd/crops.py: plan - packplan.plan over width * rows * 4 of the referenced images)
-    const RowsPlan plan = plan_rows(descs, n_images, rows, staging_bytes);
-    const std::vector<int>& ref_of = plan.ref_of;
-    const std::vector<int>& firsts = plan.firsts;
-    const std::vector<size_t>& at = plan.at;
-    const size_t nr = plan.refs.size(), need = plan.need;
-    std::vector<size_t> by_ref(n);                             // the crops in the order of their images' sub-batches
-    std::iota(by_ref.begin(), by_ref.end(), (size_t)0);
-    std::stable_sort(by_ref.begin(), by_ref.end(), [&](size_t a, size_t b) { return ref_of[crops[a].image] < ref_of[crops[b].image]; });
-    struct Sub { uint32_t entry, m, tiles; };
-    std::vector<Sub> subs(firsts.size() - 1u);
-    std::vector<uint32_t> first_tile(n);                       // of by_ref[e], within its sub-batch
-    {
-        size_t e = 0;
-        for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-            uint64_t tiles = 0;
-            subs[k].entry = (uint32_t)e;
-            for (; e < n && ref_of[crops[by_ref[e]].image] < firsts[k + 1]; ++e) {
-                if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output words in one sub-batch");
-                first_tile[e] = (uint32_t)tiles;
-                tiles += crop_tiles((uint64_t)(uintptr_t)d_out + out_offsets[by_ref[e]], out_bytes[by_ref[e]]);
-            }
-            if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output words in one sub-batch");
-            subs[k].m = (uint32_t)(e - subs[k].entry); subs[k].tiles = (uint32_t)tiles;
-        }
-    }
-    DeviceGuard guard(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    c->crop_stats[0] = 0; c->crop_stats[1] = 0; c->crop_stats[2] = (long long)need; c->crop_stats[3] = (long long)nr;
-    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
-    // one crop table for the whole call, through pinned staging; the entries of a sub-batch stand together, their tiles begin at 0
-    const size_t tab_bytes = up256(n * sizeof(CropEntry));
-    { const int rc = cmp_pin_reserve(c, tab_bytes); if (rc != QOIMI_OK) return rc; }
-    { const int rc = c->cmp_ws.reserve(tab_bytes); if (rc != QOIMI_OK) return rc; }
-    { const int rc = reserve_exact(c->ver_stage, need); if (rc != QOIMI_OK) return rc; }
-    CropEntry* h_tab = (CropEntry*)c->cmp_pin_buf;
-    for (size_t e = 0; e < n; ++e) {
-        const qoimi_crop& r = crops[by_ref[e]];
-        CropEntry& t = h_tab[e];
-        t.src_off = (u64)at[(size_t)ref_of[r.image]]; t.dst_off = (u64)out_offsets[by_ref[e]];
-        t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.ch = r.height;
-        t.first_tile = first_tile[e]; t.cfg = och | (r.flags << 8); t.reserved = 0u;
-    }
-    const CropEntry* d_tab = (const CropEntry*)c->cmp_ws.base;
-    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, n * sizeof(CropEntry), hipMemcpyHostToDevice, st));
-    const uint32_t most = (uint32_t)c->n_cus * 8u;
-    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-        const int rc = decode_rows(c, d_streams, stream_offsets, sizes, descs, plan, rows, k, stream);
-        if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
-        c->crop_stats[0] += 1;
-        launch_crop((const uint8_t*)c->ver_stage.base, d_tab + subs[k].entry, subs[k].m, subs[k].tiles, (uint8_t*)d_out, subs[k].tiles < most ? subs[k].tiles : most, st);
-        { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string("crop_gather: ") + hipGetErrorString(e)); } }
-        c->crop_stats[1] += 1;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return QOIMI_OK;
+    CheckedItems ok;
+    if (const int rc = check_items("crop", sizes, descs, n_images, channels, crops, n, d_out, out_offsets, crop_rect_wrong, crop_bytes, ok)) return rc;
+    const unsigned och = ok.och;
+    const RowsPlan plan = plan_rows(descs, n_images, ok.rows, staging_bytes);
+    std::vector<uint32_t> image_of(n);
+    std::vector<uint64_t> tiles_of(n);
+    for (size_t j = 0; j < n; ++j) { image_of[j] = crops[j].image; tiles_of[j] = crop_tiles((uint64_t)(uintptr_t)d_out + out_offsets[j], ok.out_bytes[j]); }
+    const ItemPlan items = plan_items(image_of, plan.ref_of, plan.firsts, tiles_of);
+    if (items.overflow) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output words in one sub-batch");
+    return run_staged<CropEntry>(c, c->crop_stats, (long long)plan.refs.size(), "crop_gather", d_streams, stream_offsets, sizes, descs, plan, ok.rows, items,
+        [&](CropEntry& t, size_t e) {
+            const size_t j = items.by_ref[e];
+            const qoimi_crop& r = crops[j];
+            t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]]; t.dst_off = (u64)out_offsets[j];
+            t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.ch = r.height;
+            t.first_tile = items.first_tile[e]; t.cfg = och | (r.flags << 8); t.reserved = 0u;
+        },
+        [&](const CropEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            launch_crop((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
+        }, stream);
 }
 
 // ------------------------------------------------------------------------------------
@@ -2016,9 +1941,8 @@ extern "C" void qoimi_resize_stats(qoimi_ctx* c, long long out[4]) {
     for (int i = 0; i < 4; ++i) out[i] = c ? c->resize_stats[i] : 0;
 }
 
-// The plan and the sub-batch loop of qoimi_decode_crops (plan_rows, decode_rows) over the items' rectangles; every sub-batch is one call of the
-// decoder as it is into the staging arena, then one launch of resize_filter over the sub-batch's items on the caller's stream; the next
-// sub-batch's decoder is ordered behind it by the stream.
+// The plan of qoimi_decode_crops over the items' rectangles (qoi_amd/resize.py: plan); run_staged with one launch of resize_filter over the
+// sub-batch's items.
 extern "C" int qoimi_decode_resized(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                     int n_images, int channels, const qoimi_resize* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
                                     size_t staging_bytes, void* stream) {
@@ -2027,86 +1951,29 @@ extern "C" int qoimi_decode_resized(qoimi_ctx* c, const void* d_streams, const s
     if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
     if (mode != QOIMI_RESIZE_PLAIN && mode != QOIMI_RESIZE_ALPHA_WEIGHTED) return fail(QOIMI_E_ARG, "mode must be QOIMI_RESIZE_PLAIN or QOIMI_RESIZE_ALPHA_WEIGHTED");
     const size_t n = (size_t)n_items;
-    std::vector<uint32_t> rows((size_t)n_images, 0u);          // the rows of image i that are decoded; 0: no item names it
-    std::vector<size_t> out_bytes(n);
-    unsigned och = (unsigned)channels;
-    for (size_t j = 0; j < n; ++j) {
-        const qoimi_resize& r = items[j];
-        if (r.image >= (unsigned)n_images) return fail(QOIMI_E_ARG, "item " + std::to_string(j) + ": no image " + std::to_string(r.image));
-        const size_t i = r.image;
-        if (rows[i] == 0u) {                                   // (an image no item names is never looked at)
-            if (sizes[i] < kHeaderBytes + kTrailerBytes) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + " shorter than 22 bytes (qoi.h:500)");
-            if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:513-521 rules)");
-        }
-        if (channels == 0) {
-            if (och == 0u) och = descs[i].channels;
-            else if (descs[i].channels != och) return fail(QOIMI_E_ARG, "all referenced images of a call must share the output channel count");
-        }
-        if (const char* wrong = resize_item_wrong(&descs[i], &r)) return fail(QOIMI_E_ARG, "item " + std::to_string(j) + ": " + wrong);
-        if (r.y + r.height > rows[i]) rows[i] = r.y + r.height;
-        const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_out;   // (so that no address of an output wraps, whatever the offsets)
-        if (!resize_bytes(&r, och, &out_bytes[j]) || out_offsets[j] > room || out_bytes[j] > room - out_offsets[j]) return fail
-           (QOIMI_E_ARG, "item " + std::to_string(j) + ": the output ends behind the address space");
-    }
-    if (ranges_overlap(out_offsets, out_bytes)) return fail(QOIMI_E_ARG, "the output ranges of two items overlap");
-    // the plan: a function of descs, the items' rectangles and staging_bytes alone (qoi_amd/resize.py: plan - that of qoimi_decode_crops)
-    const RowsPlan plan = plan_rows(descs, n_images, rows, staging_bytes);
-    const std::vector<int>& ref_of = plan.ref_of;
-    const std::vector<int>& firsts = plan.firsts;
-    std::vector<size_t> by_ref(n);                             // the items in the order of their images' sub-batches
-    std::iota(by_ref.begin(), by_ref.end(), (size_t)0);
-    std::stable_sort(by_ref.begin(), by_ref.end(), [&](size_t a, size_t b) { return ref_of[items[a].image] < ref_of[items[b].image]; });
-    struct Sub { uint32_t entry, m, tiles; };
-    std::vector<Sub> subs(firsts.size() - 1u);
-    std::vector<uint32_t> first_tile(n);                       // of by_ref[e], within its sub-batch
-    {
-        size_t e = 0;
-        for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-            uint64_t tiles = 0;
-            subs[k].entry = (uint32_t)e;
-            for (; e < n && ref_of[items[by_ref[e]].image] < firsts[k + 1]; ++e) {
-                if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output pixels in one sub-batch");
-                first_tile[e] = (uint32_t)tiles;
-                const qoimi_resize& r = items[by_ref[e]];
-                tiles += resize_tiles(r.width, r.out_width, r.out_height);
-            }
-            if (tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output pixels in one sub-batch");
-            subs[k].m = (uint32_t)(e - subs[k].entry); subs[k].tiles = (uint32_t)tiles;
-        }
-    }
-    DeviceGuard guard(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    c->resize_stats[0] = 0; c->resize_stats[1] = 0; c->resize_stats[2] = (long long)plan.need; c->resize_stats[3] = (long long)plan.refs.size();
-    if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
-    // one item table for the whole call, through pinned staging; the entries of a sub-batch stand together, their tiles begin at 0
-    const size_t tab_bytes = up256(n * sizeof(ResizeEntry));
-    { const int rc = cmp_pin_reserve(c, tab_bytes); if (rc != QOIMI_OK) return rc; }
-    { const int rc = c->cmp_ws.reserve(tab_bytes); if (rc != QOIMI_OK) return rc; }
-    { const int rc = reserve_exact(c->ver_stage, plan.need); if (rc != QOIMI_OK) return rc; }
-    ResizeEntry* h_tab = (ResizeEntry*)c->cmp_pin_buf;
+    CheckedItems ok;
+    if (const int rc = check_items("item", sizes, descs, n_images, channels, items, n, d_out, out_offsets, resize_item_wrong, resize_bytes, ok)) return rc;
+    const unsigned och = ok.och;
+    const RowsPlan plan = plan_rows(descs, n_images, ok.rows, staging_bytes);
+    std::vector<uint32_t> image_of(n);
+    std::vector<uint64_t> tiles_of(n);
+    for (size_t j = 0; j < n; ++j) { image_of[j] = items[j].image; tiles_of[j] = resize_tiles(items[j].width, items[j].out_width, items[j].out_height); }
+    const ItemPlan order = plan_items(image_of, plan.ref_of, plan.firsts, tiles_of);
+    if (order.overflow) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output pixels in one sub-batch");
     const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
-    for (size_t e = 0; e < n; ++e) {
-        const qoimi_resize& r = items[by_ref[e]];
-        ResizeEntry& t = h_tab[e];
-        uint32_t lg, cols;
-        resize_split(r.width, r.out_width, lg, cols);
-        t.src_off = (u64)plan.at[(size_t)ref_of[r.image]]; t.dst_off = (u64)out_offsets[by_ref[e]];
-        t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
-        t.first_tile = first_tile[e]; t.cfg = lg | (cols << 8) | (och << 16) | (weighted << 24) | (r.flags << 28); t.reserved = 0u;
-    }
-    const ResizeEntry* d_tab = (const ResizeEntry*)c->cmp_ws.base;
-    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, n * sizeof(ResizeEntry), hipMemcpyHostToDevice, st));
-    const uint32_t most = (uint32_t)c->n_cus * 8u;
-    for (size_t k = 0; k + 1 < firsts.size(); ++k) {
-        const int rc = decode_rows(c, d_streams, stream_offsets, sizes, descs, plan, rows, k, stream);
-        if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
-        c->resize_stats[0] += 1;
-        launch_resize((const uint8_t*)c->ver_stage.base, d_tab + subs[k].entry, subs[k].m, subs[k].tiles, (uint8_t*)d_out, subs[k].tiles < most ? subs[k].tiles : most, st);
-        { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string("resize_filter: ") + hipGetErrorString(e)); } }
-        c->resize_stats[1] += 1;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return QOIMI_OK;
+    return run_staged<ResizeEntry>(c, c->resize_stats, (long long)plan.refs.size(), "resize_filter", d_streams, stream_offsets, sizes, descs, plan, ok.rows, order,
+        [&](ResizeEntry& t, size_t e) {
+            const size_t j = order.by_ref[e];
+            const qoimi_resize& r = items[j];
+            uint32_t lg, cols;
+            resize_split(r.width, r.out_width, lg, cols);
+            t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]]; t.dst_off = (u64)out_offsets[j];
+            t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
+            t.first_tile = order.first_tile[e]; t.cfg = lg | (cols << 8) | (och << 16) | (weighted << 24) | (r.flags << 28); t.reserved = 0u;
+        },
+        [&](const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            launch_resize((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
+        }, stream);
 }
 
 // ------------------------------------------------------------------------------------

@@ -12,8 +12,8 @@
 //                 so that a lane holds at most four of them (five for 65); lane l takes the columns [k0 + l*c, + c) in every row with a
 //                 weight.  A WORK ITEM is one lane's share; work item = (output pixel of the unflipped result, row-major) * L + l, so consecutive
 //                 lanes read consecutive addresses of a staged row.  TILES of kResizeThreads work items of ONE item are laid over the table
-//                 the host builds (an entry holds its item's first tile); a workgroup takes a contiguous range of tiles - one binary
-//                 search, then it steps on from item to item - so one launch serves every item of a sub-batch.
+//                 the host builds (an entry holds its item's first tile); a workgroup takes a contiguous range of tiles (qoi_dev.h:
+//                 walk_tiles), so one launch serves every item of a sub-batch.
 //                 A lane computes its column weights once and a row weight per row from the closed form (no table in memory), loads its
 //                 pixels as aligned dwords - plain loads: items may share source pixels - and adds weight * channel into 64-bit sums (four,
 //                 seven with alpha weighting), one 32 x 32 -> 64 multiply-add each.  The L lanes of a pixel add their sums with log2(L)
@@ -74,24 +74,13 @@ __device__ __forceinline__ void resize_tile(const ResizeMem& mem, u64 q, const R
 
 __global__ __launch_bounds__(kResizeThreads) void resize_filter(const uint8_t* __restrict__ stage, const ResizeEntry* __restrict__ tab, uint32_t m, uint32_t tiles,
                                                                  uint8_t* out) {
-    const u64 per_wg = ((u64)tiles + gridDim.x - 1u) / gridDim.x;
-    const u64 lo64 = (u64)blockIdx.x * per_wg, hi64 = lo64 + per_wg < (u64)tiles ? lo64 + per_wg : (u64)tiles;
-    if (lo64 >= hi64) return;
-    const uint32_t t_lo = (uint32_t)lo64, t_hi = (uint32_t)hi64;
-    uint32_t i = 0;                                               // the item of tile t_lo: the last one whose first tile is not behind it
-    for (uint32_t hi = m - 1u; i < hi;) {
-        const uint32_t mid = i + (hi - i + 1u) / 2u;
-        if (tab[mid].first_tile <= t_lo) i = mid; else hi = mid - 1u;
-    }
-    for (uint32_t t = t_lo; t < t_hi; ++t) {
-        if (i + 1u < m && tab[i + 1u].first_tile <= t) ++i;       // (every item has a tile: one step at most)
-        const ResizeEntry e = tab[i];
+    walk_tiles(tab, m, tiles, [&](const ResizeEntry& e, uint32_t tile) {
         const ResizeMem mem = {reinterpret_cast<const uint32_t*>(stage + e.src_off)};
         const u64 q = (u64)reinterpret_cast<uintptr_t>(out) + e.dst_off;
-        const u64 base = (u64)(t - e.first_tile) * kResizeThreads;
+        const u64 base = (u64)tile * kResizeThreads;
         if ((e.cfg >> 24) & 1u) resize_tile<true>(mem, q, e, base);
         else resize_tile<false>(mem, q, e, base);
-    }
+    });
 }
 
 // The kernel over the m table entries at tab (their tiles: [0, tiles)); grid: workgroups, at most `tiles`.  No timer marks: the kernel has no

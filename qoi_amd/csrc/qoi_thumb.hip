@@ -12,8 +12,8 @@
 //                 ITEM is one lane's share; item = (output pixel, row-major) * L + l, so consecutive lanes read consecutive addresses of a
 //                 source row: 16 bytes each for f = 4, 8, 16, 32, 64 (one wavefront: one contiguous KiB per row), 8 for f = 2, c dwords for
 //                 the others.  TILES of kThumbThreads items of ONE image are laid over the image table the host builds (an entry holds its
-//                 image's first tile); a workgroup takes a contiguous range of tiles - one binary search, then it steps on from image to
-//                 image - so one launch serves every image of a sub-batch, a 4K frame and a 1 x 1 image alike.
+//                 image's first tile); a workgroup takes a contiguous range of tiles (qoi_dev.h: walk_tiles), so one launch serves every
+//                 image of a sub-batch, a 4K frame and a 1 x 1 image alike.
 //                 A lane walks down its columns row by row: one 16-byte load per row where the row pitch and the column are multiples of
 //                 four pixels (then every row of the 256-aligned slot is 16-byte aligned there), 8-byte loads where both are even, dwords
 //                 otherwise.  Loads are non-temporal: every staged byte is read once, by exactly one lane.  A lane sees at most 4 x 64 =
@@ -104,23 +104,12 @@ __device__ __forceinline__ void thumb_tile(const uint32_t* __restrict__ src, uin
 
 __global__ __launch_bounds__(kThumbThreads) void thumb_reduce(const uint8_t* __restrict__ stage, const ThumbImage* __restrict__ tab, uint32_t m, uint32_t tiles,
                                                                uint8_t* __restrict__ out) {
-    const u64 per_wg = ((u64)tiles + gridDim.x - 1u) / gridDim.x;
-    const u64 lo64 = (u64)blockIdx.x * per_wg, hi64 = lo64 + per_wg < (u64)tiles ? lo64 + per_wg : (u64)tiles;
-    if (lo64 >= hi64) return;
-    const uint32_t t_lo = (uint32_t)lo64, t_hi = (uint32_t)hi64;
-    uint32_t i = 0;                                               // the image of tile t_lo: the last one whose first tile is not behind it
-    for (uint32_t hi = m - 1u; i < hi;) {
-        const uint32_t mid = i + (hi - i + 1u) / 2u;
-        if (tab[mid].first_tile <= t_lo) i = mid; else hi = mid - 1u;
-    }
-    for (uint32_t t = t_lo; t < t_hi; ++t) {
-        if (i + 1u < m && tab[i + 1u].first_tile <= t) ++i;       // (every image has a tile: one step at most)
-        const ThumbImage im = tab[i];
+    walk_tiles(tab, m, tiles, [&](const ThumbImage& im, uint32_t tile) {
         const uint32_t* src = reinterpret_cast<const uint32_t*>(stage + im.src_off);
-        const uint32_t item_base = (t - im.first_tile) * kThumbThreads;
+        const uint32_t item_base = tile * kThumbThreads;
         if (im.cfg >> 24) thumb_tile<true>(src, out + im.dst_off, im, item_base);
         else thumb_tile<false>(src, out + im.dst_off, im, item_base);
-    }
+    });
 }
 
 // The kernel over the m table entries at tab (their tiles: [0, tiles)); grid: workgroups, at most `tiles`.  No timer marks: the kernel has no

@@ -1,5 +1,5 @@
 """The sub-batch plan of ``qoimi_encode_packed`` / ``qoimi_encode_images_packed`` as a pure function - the normative statement of what
-qoi_host.hip: pack_plan computes, so a caller (and the tests) can tell where the sub-batch boundaries of a call fall."""
+qoi_stage_plan.h: pack_plan computes, so a caller (and the tests) can tell where the sub-batch boundaries of a call fall."""
 from typing import List, Sequence, Tuple
 
 SLOT_ALIGN = 256

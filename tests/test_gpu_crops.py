@@ -175,6 +175,22 @@ def test_large_crops_between_small_ones(ctx, mixed):
             assert_crops(p, got, cs, channels, ("large", channels, shift))
 
 
+def test_tile_walk_regimes(api, ctx, oracle, mixed):
+    """(qoi_dev.h: walk_tiles) a launch with ONE table entry, its 9 tiles spread over as many workgroups; and more tiles than the grid's clamp
+    of 8 workgroups per compute unit - 37 more crops of one tile each - so that a workgroup takes two tiles and steps from crop to crop.
+    The 3-byte outputs stand back to back: neighbours share aligned words."""
+    import torch
+    one = (BIG, 0, 0, 130, 70, 3)
+    assert -(-len(crops.items(64, 130 * 70 * 4)) // 256) == 9                        # (run: 64 bytes behind an aligned buffer)
+    assert_crops(mixed, run(ctx, mixed, 4, [one]), [one], 4, "one entry")
+    n = 8 * torch.cuda.get_device_properties(0).multi_processor_count + 37
+    p = Pack(ctx, oracle, Batch(api, oracle, [(8, 8, 4)], ["noise"]))
+    cs = [(0, j % 8, (j // 8) % 8, 1, 1, j & 3) for j in range(n)]
+    for channels in (3, 4):
+        assert_crops(p, run(ctx, p, channels, cs, front=64 + 5), cs, channels, ("many", channels))
+        assert ctx.crop_stats()[:2] == (1, 1)
+
+
 # ------------------------------------------------------------------ 6: sub-batches
 def test_sub_batches(api, mixed, equal):
     c = api.Context(0)

@@ -215,6 +215,22 @@ def test_large_items_between_small_ones(ctx, mixed):
         assert_items(p, got, items, channels, ALPHA_WEIGHTED, ("large", channels, shift))
 
 
+def test_tile_walk_regimes(api, ctx, oracle, mixed):
+    """(qoi_dev.h: walk_tiles) a launch with ONE table entry, its 12 tiles spread over as many workgroups; and more tiles than the grid's
+    clamp of 8 workgroups per compute unit - 37 more items of one tile each - so that a workgroup takes two tiles and steps from item to item.
+    The 3-byte outputs stand back to back: neighbours share aligned words."""
+    import torch
+    one = (BIG, 0, 0, 130, 70, 61, 47, 3)
+    assert resize.tiles(130, 61, 47) == 12 and resize.tiles(1, 1, 1) == 1
+    assert_items(mixed, run(ctx, mixed, 4, [one], ALPHA_WEIGHTED), [one], 4, ALPHA_WEIGHTED, "one entry")
+    n = 8 * torch.cuda.get_device_properties(0).multi_processor_count + 37
+    p = Pack(ctx, oracle, Batch(api, oracle, [(8, 8, 4)], ["noise"]))
+    items = [(0, j % 8, (j // 8) % 8, 1, 1, 1, 1, j & 3) for j in range(n)]
+    for channels, mode in ((3, PLAIN), (4, ALPHA_WEIGHTED)):
+        assert_items(p, run(ctx, p, channels, items, mode, front=64 + 5), items, channels, mode, ("many", channels))
+        assert ctx.resize_stats()[:2] == (1, 1)
+
+
 # ------------------------------------------------------------------ 5: sub-batches
 def test_sub_batches(api, mixed, equal):
     c = api.Context(0)

@@ -205,6 +205,21 @@ def test_extremes(api, ctx, oracle):
     assert left[3] == 0 and np.array_equal(left, thumbs.thumbnail(half[:, :64], 64, PLAIN).reshape(-1))      # all transparent: the plain value
 
 
+def test_more_tiles_than_the_grid(api, ctx, oracle):
+    """(qoi_dev.h: walk_tiles) more tiles than the grid's clamp of 8 workgroups per compute unit - 37 more images of 1 x 1, one tile each - so
+    that a workgroup takes two tiles and steps from image to image.  (One entry in a launch: test_sub_batches; an image of 36 tiles over as
+    many workgroups: test_identity.)"""
+    import torch
+    n = 8 * torch.cuda.get_device_properties(0).multi_processor_count + 37
+    px = np.random.default_rng(11).integers(0, 256, size=(n, 4), dtype=np.uint8)
+    p = Pack(ctx, oracle, batch_of(api, oracle, [(1, 1, 4)] * n, list(px)))
+    for channels, mode in ((3, PLAIN), (4, ALPHA_WEIGHTED)):
+        got, _, _ = run(ctx, p, channels, 1, mode)
+        assert np.array_equal(np.concatenate(got), px[:, :channels].reshape(-1)), (channels, mode)
+        assert_thumbs(p, got, channels, [1] * n, mode, ("many", channels))
+        assert ctx.thumbnail_stats()[:2] == (1, 1)
+
+
 # ------------------------------------------------------------------ 4: sub-batches
 def test_sub_batches(api, ctx, equal):
     from qoi_amd.packplan import plan, slot
