@@ -519,6 +519,63 @@ size_t qoimi_resize_size(const qoi_desc *desc, const qoimi_resize *item, int cha
  * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] images decoded (the referenced ones). */
 void qoimi_resize_stats(qoimi_ctx *ctx, long long out[4]);
 
+/* What is in the pixels of rectangles of a pack's images, without the caller ever owning the decoded images: a tile server learns which tiles
+ * of a scan are blank (a constant tile need not be stored) and which are fully opaque (they can be re-encoded with 3 channels), a training
+ * loader gets the per-channel sums its normalisation needs and can drop empty or single-colour samples.  The referenced streams are decoded as
+ * for qoimi_decode_crops - into the staging arena, sub-batch by sub-batch, down to the last row any region needs - and reduced there.
+ * The result (normative; qoi_amd/pixelstats.py: stats states it in Python): decode stream regions[j].image exactly as qoimi_decode_images does
+ * (same leniency, bit-exact for EVERY input stream) to 4 channels, which gives D of h rows of w pixels; the call has no channels argument, images
+ * of both channel counts mix freely, and a 3-channel stream has alpha 255 everywhere (its regions are OPAQUE, sum[3] = 255 * pixels).  Region j is
+ * D[y .. y + height) x [x .. x + width); stats_out[j] holds, over its pixels: their number, per channel r, g, b, a the sum, the sum of squares,
+ * the minimum and the maximum, the numbers of pixels with a == 255, with a == 0 and with r == g == b, `first`, and the flags, which are a
+ * function of the other fields.  The two FLIP bits of qoimi_crop are accepted and change nothing but `first`: it is pixel (0, 0) of the
+ * FLIPPED rectangle, the first pixel qoimi_decode_crops would write.  All arithmetic is integer: the result is a function of the inputs alone.
+ *   stream_offsets, sizes, descs  HOST arrays as for qoimi_decode_images.  An image that no region names is NOT decoded and its sizes[i] and
+ *                  descs[i] are not even checked
+ *   regions        HOST qoimi_crop[n_regions], in any order of image; several may name the same image, overlap or coincide: each has its own
+ *                  result
+ *   stats_out      HOST qoimi_pixel_stat[n_regions]
+ *   d_hist         NULL, or DEVICE unsigned[n_regions][4][256]: d_hist[j][c][v] is the number of pixels of region j whose channel c is v (below
+ *                  400 000 000).  Zeroed by the call; it stays on the device - 4 KiB per region are the caller's to copy or not.  With NULL
+ *                  nothing of it is computed
+ *   staging_bytes  as for qoimi_decode_crops: the arena qoimi_verify_images and the gather calls use, counted in qoimi_workspace_bytes [1],
+ *                  allocated as the largest sub-batch of the call's plan plus a page; 4 bytes per pixel; 0: 1 GiB.  The plan is that of
+ *                  qoimi_decode_crops over the regions (normative; qoi_amd/pixelstats.py: plan, which is qoi_amd/crops.py: plan)
+ * Every sub-batch is one qoimi_decode_images call as it is, at 4 output channels and with each descriptor's height replaced by rows_i, then one
+ * launch of the reduction kernel over all regions of the sub-batch's images on `stream`.
+ * SYNCHRONOUS: returns when stats_out is filled and d_hist written.  The code of a decode sub-call that failed ends the call.  QOIMI_E_ARG for a
+ * NULL ctx, d_streams, stream_offsets, sizes, descs, regions or stats_out, n_images <= 0, n_regions <= 0, regions[j].image >= n_images, a zero
+ * width or height, a rectangle that leaves its image, a flag bit other than the two, a referenced stream shorter than 22 bytes, a rejected
+ * referenced descriptor, a sub-batch of the plan with 2^31 - 1 or more tiles of 1024 pixels of a region: reported before anything is launched,
+ * stats_out is untouched.  The sub-batches count as decode calls of the context, as those of qoimi_verify_images do.  One call at a time per
+ * context, as everywhere. */
+enum { QOIMI_PS_CONSTANT = 1,      /* every pixel of the rectangle equals `first` (all four bytes): min[c] == max[c] for c = 0..3 */
+       QOIMI_PS_OPAQUE = 2,        /* opaque_pixels == pixels */
+       QOIMI_PS_TRANSPARENT = 4,   /* transparent_pixels == pixels */
+       QOIMI_PS_GREY = 8 };        /* grey_pixels == pixels (r == g == b everywhere) */
+typedef struct {                          /* 128 bytes, offsets 0/8/40/72/76/80/84/88/96/104 */
+    unsigned long long pixels;            /* width * height of the rectangle */
+    unsigned long long sum[4];            /* per channel r, g, b, a */
+    unsigned long long sum_sq[4];         /* per channel, sum of squares (<= 255^2 * 4e8 < 2^45) */
+    unsigned char min[4], max[4];
+    unsigned int first;                   /* pixel (0, 0) of the rectangle, r | g<<8 | b<<16 | a<<24 */
+    unsigned int flags;                   /* QOIMI_PS_*: a function of the other fields, as stated above */
+    unsigned long long opaque_pixels;     /* a == 255 */
+    unsigned long long transparent_pixels;/* a == 0 */
+    unsigned long long grey_pixels;       /* r == g && g == b */
+    unsigned int reserved[4];             /* 0 */
+} qoimi_pixel_stat;
+int qoimi_pixel_stats(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                      const qoi_desc *descs /* host */, int n_images,
+                      const qoimi_crop *regions /* host */, int n_regions,
+                      qoimi_pixel_stat *stats_out /* host, n_regions */,
+                      unsigned *d_hist /* DEVICE unsigned[n_regions][4][256], may be NULL */,
+                      size_t staging_bytes, void *stream);
+
+/* Of the context's last qoimi_pixel_stats call: [0] sub-batches decoded, [1] launches of the reduction kernel (it has no entry in
+ * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] images decoded (the referenced ones). */
+void qoimi_pixel_stats_counters(qoimi_ctx *ctx, long long out[4]);
+
 /* Fill device memory with synthetic RGBA frames frame_id = first_frame .. first_frame+n-1
  * (benchmark/test utility; same function of (kind, seed, frame, pixel) as synth.py). */
 int qoimi_synth_frames(qoimi_ctx *ctx, int kind, unsigned seed, unsigned first_frame,
@@ -535,7 +592,7 @@ int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
 /* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace (and the staging arena of
  * qoimi_encode_packed), [1] decode workspace
  * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images,
- * qoimi_decode_thumbnails, qoimi_decode_crops and qoimi_decode_resized, which share them),
+ * qoimi_decode_thumbnails, qoimi_decode_crops, qoimi_decode_resized and qoimi_pixel_stats, which share them),
  * [2] staging buffers of the host-pointer entry points (qoi_encode / qoi_decode of the calling thread's context). */
 void qoimi_workspace_bytes(qoimi_ctx *ctx, size_t out[3]);
 

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -42,6 +42,7 @@ EXPORTS = (
     "qoimi_decode_thumbnails", "qoimi_thumbnail_size", "qoimi_thumbnail_stats",
     "qoimi_decode_crops", "qoimi_crop_size", "qoimi_crop_stats",
     "qoimi_decode_resized", "qoimi_resize_size", "qoimi_resize_stats",
+    "qoimi_pixel_stats", "qoimi_pixel_stats_counters",
 )
 
 
@@ -83,6 +84,16 @@ class QoimiResize(ctypes.Structure):
 
 
 assert ctypes.sizeof(QoimiResize) == 32 and [getattr(QoimiResize, f).offset for f, _ in QoimiResize._fields_] == [0, 4, 8, 12, 16, 20, 24, 28]
+
+
+class QoimiPixelStat(ctypes.Structure):
+    """``qoimi_pixel_stat``: 128 bytes - what ``qoimi_pixel_stats`` says of one region (``pixelstats.stats`` states the fields)."""
+    _fields_ = [("pixels", ctypes.c_ulonglong), ("sum", ctypes.c_ulonglong * 4), ("sum_sq", ctypes.c_ulonglong * 4), ("min", ctypes.c_ubyte * 4),
+                ("max", ctypes.c_ubyte * 4), ("first", ctypes.c_uint), ("flags", ctypes.c_uint), ("opaque_pixels", ctypes.c_ulonglong),
+                ("transparent_pixels", ctypes.c_ulonglong), ("grey_pixels", ctypes.c_ulonglong), ("reserved", ctypes.c_uint * 4)]
+
+
+assert ctypes.sizeof(QoimiPixelStat) == 128 and [getattr(QoimiPixelStat, f).offset for f, _ in QoimiPixelStat._fields_] == [0, 8, 40, 72, 76, 80, 84, 88, 96, 104, 112]
 
 
 class QoiError(RuntimeError):
@@ -189,6 +200,10 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_resize_size.argtypes = [dp, rp, ci]
     lib.qoimi_resize_stats.restype = None
     lib.qoimi_resize_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+    lib.qoimi_pixel_stats.restype = ci
+    lib.qoimi_pixel_stats.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, cp, ci, ctypes.POINTER(QoimiPixelStat), vp, sz, vp]
+    lib.qoimi_pixel_stats_counters.restype = None
+    lib.qoimi_pixel_stats_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     _lib = lib
     return lib
 
@@ -590,6 +605,31 @@ class Context:
         self._lib.qoimi_resize_stats(self._h, out)
         return tuple(int(x) for x in out)
 
+    def pixel_stats(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], regions,
+                    d_hist: int = 0, staging_bytes: int = 0, stream: int = 0) -> List[QoimiPixelStat]:
+        """Pixel statistics of rectangles of a pack's images (``qoimi_pixel_stats``, synchronous, through bounded staging): one
+        ``QoimiPixelStat`` per region.  regions: ``QoimiCrop`` structures or (image, x, y, width, height, flags) tuples; d_hist: 0, or device
+        memory of 4096 bytes per region that receives uint32[n_regions][4][256]; an image no region names is not decoded;
+        ``qoi_amd/pixelstats.py: stats`` states the result."""
+        n = len(sizes)
+        if len(descs) != n or len(stream_offsets) != n:
+            raise QoiError("pixel_stats: one stream offset, size and descriptor per image")
+        arr = _crop_array(regions)
+        if arr is None:
+            raise QoiError("pixel_stats: a region is not six unsigned 32-bit fields")
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        out = (QoimiPixelStat * max(len(arr), 1))()
+        self._check(self._lib.qoimi_pixel_stats(self._h, d_streams, so.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                (QoiDesc * n)(*descs), n, arr, len(arr), out, d_hist or None, staging_bytes, stream), "qoimi_pixel_stats")
+        return list(out)[:len(arr)]
+
+    def pixel_stats_counters(self) -> Tuple[int, int, int, int]:
+        """Of the last ``pixel_stats`` call: (sub-batches decoded, launches of the reduction kernel, bytes of staging planned, images decoded)."""
+        out = (ctypes.c_longlong * 4)()
+        self._lib.qoimi_pixel_stats_counters(self._h, out)
+        return tuple(int(x) for x in out)
+
     def synth_frames(self, kind: int, seed: int, first_frame: int, n_frames: int, width: int, height: int,
                      d_pixels: int, pixel_stride: int, stream: int = 0) -> None:
         self._check(self._lib.qoimi_synth_frames(self._h, kind, seed, first_frame, n_frames, width, height,
@@ -610,7 +650,7 @@ class Context:
         return {self._lib.qoimi_kernel_name(i).decode(): (ms[i], calls[i]) for i in range(1, n)}
 
     def workspace_bytes(self) -> dict:
-        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops`` / ``decode_resized``), staging of the host-pointer entry points."""
+        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops`` / ``decode_resized`` / ``pixel_stats``), staging of the host-pointer entry points."""
         out = (ctypes.c_size_t * 3)()
         self._lib.qoimi_workspace_bytes(self._h, out)
         return {"encode": int(out[0]), "decode": int(out[1]), "staging": int(out[2])}

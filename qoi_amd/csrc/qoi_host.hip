@@ -36,6 +36,7 @@
 #include "qoi_thumb.hip"       // ... and the box reduction of qoimi_decode_thumbnails
 #include "qoi_crop.hip"        // ... and the gather of qoimi_decode_crops
 #include "qoi_resize.hip"      // ... and the area filter of qoimi_decode_resized
+#include "qoi_stats.hip"       // ... and the reduction of qoimi_pixel_stats
 
 using namespace qoimi;
 
@@ -107,10 +108,11 @@ struct qoimi_ctx {
     Arena enc_stage;            // qoimi_encode_packed: the strided streams of one sub-batch (and the source offsets of a mixed-shape call) on their way into the pack
     Arena insp_ws;              // tables, maps and partial counts of qoimi_inspect_streams (its own: a decode call finds dec_ws as it left it)
     Arena cmp_ws;               // image table and result table of qoimi_compare_images / qoimi_verify_images
-    Arena ver_stage;            // qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops / qoimi_decode_resized: the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
+    Arena ver_stage;            // qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops / qoimi_decode_resized / qoimi_pixel_stats: the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
     long long thumb_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_thumbnails call: sub-batches decoded, launches of thumb_reduce, bytes of staging planned, 0
     long long crop_stats[4] = {0, 0, 0, 0};    // the last qoimi_decode_crops call: sub-batches decoded, launches of crop_gather, bytes of staging planned, images decoded
     long long resize_stats[4] = {0, 0, 0, 0};  // the last qoimi_decode_resized call: sub-batches decoded, launches of resize_filter, bytes of staging planned, images decoded
+    long long pixel_stats[4] = {0, 0, 0, 0};   // the last qoimi_pixel_stats call: sub-batches decoded, launches of stats_reduce, bytes of staging planned, images decoded
     void* cmp_pin_buf = nullptr; size_t cmp_pin_cap = 0;   // pinned staging of those two calls' tables and results (their own: the decode calls inside
                                 // qoimi_verify_images reuse pin_buf at once)
     Arena dec_scan;             // look-back words of dec_scan_entry (calls of a few images): tagged with dec_epoch, zeroed when allocated / when the tag wraps
@@ -1714,15 +1716,14 @@ static int decode_rows(qoimi_ctx* c, const void* d_streams, const size_t* stream
 // output j; och: the output channel count of the call.
 struct CheckedItems { std::vector<uint32_t> rows; std::vector<size_t> out_bytes; unsigned och = 0; };
 
-// The items of qoimi_decode_crops (`noun` "crop") and of qoimi_decode_resized ("item"), looked at in the order that decides which message a
-// call with several faults gets.  wrong(desc, item): nullptr if the item is fine for an accepted descriptor, else what is wrong with it;
-// bytes_of(item, och, &bytes): false if the output's size does not fit a size_t.
-template <class Item, class Wrong, class Bytes>
-static int check_items(const std::string& noun, const int* sizes, const qoi_desc* descs, int n_images, int channels, const Item* items, size_t n,
-                       const void* d_out, const size_t* out_offsets, Wrong wrong, Bytes bytes_of, CheckedItems& out) {
+// The items of qoimi_decode_crops (`noun` "crop"), of qoimi_decode_resized ("item") and of qoimi_pixel_stats ("region"), looked at in the order
+// that decides which message a call with several faults gets.  wrong(desc, item): nullptr if the item is fine for an accepted descriptor, else
+// what is wrong with it; output(j, item, och): QOIMI_OK, or the failure of item j's output (a call without outputs: always QOIMI_OK).
+template <class Item, class Wrong, class Output>
+static int check_refs(const std::string& noun, const int* sizes, const qoi_desc* descs, int n_images, int channels, const Item* items, size_t n,
+                      Wrong wrong, Output output, CheckedItems& out) {
     std::vector<uint32_t>& rows = out.rows;
     rows.assign((size_t)n_images, 0u);
-    out.out_bytes.resize(n);
     unsigned och = (unsigned)channels;
     for (size_t j = 0; j < n; ++j) {
         const Item& r = items[j];
@@ -1738,12 +1739,25 @@ static int check_items(const std::string& noun, const int* sizes, const qoi_desc
         }
         if (const char* what = wrong(&descs[i], &r)) return fail(QOIMI_E_ARG, noun + " " + std::to_string(j) + ": " + what);
         if (r.y + r.height > rows[i]) rows[i] = r.y + r.height;
-        const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_out;   // (so that no address of an output wraps, whatever the offsets)
-        if (!bytes_of(&r, och, &out.out_bytes[j]) || out_offsets[j] > room || out.out_bytes[j] > room - out_offsets[j]) return fail
-           (QOIMI_E_ARG, noun + " " + std::to_string(j) + ": the output ends behind the address space");
+        if (const int rc = output(j, &r, och)) return rc;
     }
-    if (ranges_overlap(out_offsets, out.out_bytes)) return fail(QOIMI_E_ARG, "the output ranges of two " + noun + "s overlap");
     out.och = och;
+    return QOIMI_OK;
+}
+
+// check_refs for the calls that write an output per item at d_out + out_offsets[j]: bytes_of(item, och, &bytes): false if the output's size
+// does not fit a size_t; no output may end behind the address space, no two may overlap.
+template <class Item, class Wrong, class Bytes>
+static int check_items(const std::string& noun, const int* sizes, const qoi_desc* descs, int n_images, int channels, const Item* items, size_t n,
+                       const void* d_out, const size_t* out_offsets, Wrong wrong, Bytes bytes_of, CheckedItems& out) {
+    out.out_bytes.resize(n);
+    const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_out;       // (so that no address of an output wraps, whatever the offsets)
+    if (const int rc = check_refs(noun, sizes, descs, n_images, channels, items, n, wrong, [&](size_t j, const Item* r, unsigned och) {
+            if (!bytes_of(r, och, &out.out_bytes[j]) || out_offsets[j] > room || out.out_bytes[j] > room - out_offsets[j]) return fail
+               (QOIMI_E_ARG, noun + " " + std::to_string(j) + ": the output ends behind the address space");
+            return (int)QOIMI_OK;
+        }, out)) return rc;
+    if (ranges_overlap(out_offsets, out.out_bytes)) return fail(QOIMI_E_ARG, "the output ranges of two " + noun + "s overlap");
     return QOIMI_OK;
 }
 
@@ -1752,23 +1766,29 @@ static int check_items(const std::string& noun, const int* sizes, const qoi_desc
 // of the decoder as it is into the staging arena and one launch over the sub-batch's entries on the caller's stream -
 // launch(its entries on the device, m, tiles, workgroups, stream), `kernel` in the message if it fails; the next sub-batch's decoder is ordered
 // behind it by the stream.  stats: sub-batches decoded, launches, bytes of staging planned, `decoded`.
-template <class Entry, class Fill, class Launch>
+// extra != 0: that many bytes of results stand behind the table (256-aligned: staged_extra_at) on the device and in the pinned staging;
+// begin(pinned bytes, stream) sets them as they start - they go to the device with the table - and may enqueue more; they are copied back
+// behind the last launch and are the call's when QOIMI_OK is returned.
+static size_t staged_extra_at(size_t n, size_t entry_bytes) { return up256(n * entry_bytes); }
+
+template <class Entry, class Fill, class Launch, class Begin>
 static int run_staged(qoimi_ctx* c, long long (&stats)[4], long long decoded, const char* kernel, const void* d_streams, const size_t* stream_offsets,
                       const int* sizes, const qoi_desc* descs, const RowsPlan& plan, const std::vector<uint32_t>& rows, const ItemPlan& items,
-                      Fill fill, Launch launch, void* stream) {
+                      Fill fill, Launch launch, void* stream, size_t extra, Begin begin) {
     const size_t n = items.by_ref.size();
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)stream;
     stats[0] = 0; stats[1] = 0; stats[2] = (long long)plan.need; stats[3] = decoded;
     if (c->dec_tail_open && c->dec_tail_stream != stream) HIP_TRY(hipStreamSynchronize((hipStream_t)c->dec_tail_stream));
-    const size_t tab_bytes = up256(n * sizeof(Entry));
-    { const int rc = cmp_pin_reserve(c, tab_bytes); if (rc != QOIMI_OK) return rc; }
-    { const int rc = c->cmp_ws.reserve(tab_bytes); if (rc != QOIMI_OK) return rc; }
+    const size_t tab_bytes = staged_extra_at(n, sizeof(Entry));
+    { const int rc = cmp_pin_reserve(c, tab_bytes + extra); if (rc != QOIMI_OK) return rc; }
+    { const int rc = c->cmp_ws.reserve(tab_bytes + extra); if (rc != QOIMI_OK) return rc; }
     { const int rc = reserve_exact(c->ver_stage, plan.need); if (rc != QOIMI_OK) return rc; }
     Entry* h_tab = (Entry*)c->cmp_pin_buf;
     for (size_t e = 0; e < n; ++e) fill(h_tab[e], e);
     const Entry* d_tab = (const Entry*)c->cmp_ws.base;
-    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, n * sizeof(Entry), hipMemcpyHostToDevice, st));
+    if (extra != 0u) { const int rc = begin((uint8_t*)c->cmp_pin_buf + tab_bytes, st); if (rc != QOIMI_OK) return rc; }
+    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, extra != 0u ? tab_bytes + extra : n * sizeof(Entry), hipMemcpyHostToDevice, st));
     const uint32_t most = (uint32_t)c->n_cus * 8u;
     for (size_t k = 0; k < items.subs.size(); ++k) {
         const ItemSub& s = items.subs[k];
@@ -1779,8 +1799,18 @@ static int run_staged(qoimi_ctx* c, long long (&stats)[4], long long decoded, co
         { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string(kernel) + ": " + hipGetErrorString(e)); } }
         stats[1] += 1;
     }
+    if (extra != 0u) HIP_TRY(hipMemcpyAsync((uint8_t*)c->cmp_pin_buf + tab_bytes, (const uint8_t*)c->cmp_ws.base + tab_bytes, extra, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return QOIMI_OK;
+}
+
+// ... for the calls whose kernels write the caller's device memory and nothing else
+template <class Entry, class Fill, class Launch>
+static int run_staged(qoimi_ctx* c, long long (&stats)[4], long long decoded, const char* kernel, const void* d_streams, const size_t* stream_offsets,
+                      const int* sizes, const qoi_desc* descs, const RowsPlan& plan, const std::vector<uint32_t>& rows, const ItemPlan& items,
+                      Fill fill, Launch launch, void* stream) {
+    return run_staged<Entry>(c, stats, decoded, kernel, d_streams, stream_offsets, sizes, descs, plan, rows, items, fill, launch, stream, (size_t)0,
+                             [](uint8_t*, hipStream_t) { return (int)QOIMI_OK; });
 }
 
 // ------------------------------------------------------------------------------------
@@ -1974,6 +2004,70 @@ extern "C" int qoimi_decode_resized(qoimi_ctx* c, const void* d_streams, const s
         [&](const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
             launch_resize((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
         }, stream);
+}
+
+// ------------------------------------------------------------------------------------
+// pixel statistics of rectangles of a pack's images (qoi_stats.hip)
+// ------------------------------------------------------------------------------------
+static_assert(sizeof(qoimi_pixel_stat) == 128 && offsetof(qoimi_pixel_stat, sum) == 8 && offsetof(qoimi_pixel_stat, sum_sq) == 40 &&
+              offsetof(qoimi_pixel_stat, min) == 72 && offsetof(qoimi_pixel_stat, max) == 76 && offsetof(qoimi_pixel_stat, first) == 80 &&
+              offsetof(qoimi_pixel_stat, flags) == 84 && offsetof(qoimi_pixel_stat, opaque_pixels) == 88 && offsetof(qoimi_pixel_stat, transparent_pixels) == 96 &&
+              offsetof(qoimi_pixel_stat, grey_pixels) == 104 && offsetof(qoimi_pixel_stat, reserved) == 112, "qoimi_pixel_stat layout");
+static_assert(QOIMI_PS_CONSTANT == (int)kStatsConstant && QOIMI_PS_OPAQUE == (int)kStatsOpaque && QOIMI_PS_TRANSPARENT == (int)kStatsTransparent &&
+              QOIMI_PS_GREY == (int)kStatsGrey, "stats_flags gives the flags as numbers");
+static_assert(QOIMI_CROP_FLIP_X == (int)kStatsFlipX && QOIMI_CROP_FLIP_Y == (int)kStatsFlipY, "the table's flag bits");
+
+extern "C" void qoimi_pixel_stats_counters(qoimi_ctx* c, long long out[4]) {
+    for (int i = 0; i < 4; ++i) out[i] = c ? c->pixel_stats[i] : 0;
+}
+
+// The plan of qoimi_decode_crops over the regions (qoi_amd/pixelstats.py: plan); run_staged with one launch of stats_reduce over the
+// sub-batch's regions.  The result table stands behind the region table; `first`, the sums and the extremes come back from the device,
+// `pixels` and `flags` are made of them here.
+extern "C" int qoimi_pixel_stats(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                 int n_images, const qoimi_crop* regions, int n_regions, qoimi_pixel_stat* stats_out, unsigned* d_hist,
+                                 size_t staging_bytes, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves stats_out as it was)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !regions || !stats_out || n_images <= 0 || n_regions <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    const size_t n = (size_t)n_regions;
+    CheckedItems ok;
+    if (const int rc = check_refs("region", sizes, descs, n_images, 4, regions, n, crop_rect_wrong,
+                                  [](size_t, const qoimi_crop*, unsigned) { return (int)QOIMI_OK; }, ok)) return rc;
+    const RowsPlan plan = plan_rows(descs, n_images, ok.rows, staging_bytes);
+    std::vector<uint32_t> image_of(n);
+    std::vector<uint64_t> tiles_of(n);
+    for (size_t j = 0; j < n; ++j) { image_of[j] = regions[j].image; tiles_of[j] = stats_tiles(regions[j].width, regions[j].height); }
+    const ItemPlan items = plan_items(image_of, plan.ref_of, plan.firsts, tiles_of);
+    if (items.overflow) return fail(QOIMI_E_ARG, "more than 2^31 tiles of region pixels in one sub-batch");
+    const size_t res_at = staged_extra_at(n, sizeof(StatsEntry));
+    const int rc = run_staged<StatsEntry>(c, c->pixel_stats, (long long)plan.refs.size(), "stats_reduce", d_streams, stream_offsets, sizes, descs, plan, ok.rows, items,
+        [&](StatsEntry& t, size_t e) {
+            const size_t j = items.by_ref[e];
+            const qoimi_crop& r = regions[j];
+            t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]];
+            t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.ch = r.height;
+            t.first_tile = items.first_tile[e]; t.index = (uint32_t)j; t.cfg = r.flags; t.reserved[0] = 0u; t.reserved[1] = 0u;
+        },
+        [&](const StatsEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            launch_stats((const uint8_t*)c->ver_stage.base, tab, m, tiles, (StatsAcc*)((uint8_t*)c->cmp_ws.base + res_at), d_hist, grid, st);
+        }, stream, n * sizeof(StatsAcc),
+        [&](uint8_t* h_res, hipStream_t st) {
+            for (size_t j = 0; j < n; ++j) stats_init(((StatsAcc*)h_res)[j]);
+            if (d_hist) HIP_TRY(hipMemsetAsync(d_hist, 0, n * kStatsBins * sizeof(unsigned), st));
+            return (int)QOIMI_OK;
+        });
+    if (rc != QOIMI_OK) return rc;
+    const StatsAcc* h_res = (const StatsAcc*)((const uint8_t*)c->cmp_pin_buf + res_at);
+    for (size_t j = 0; j < n; ++j) {
+        const StatsAcc& a = h_res[j];
+        qoimi_pixel_stat& o = stats_out[j];
+        memset(&o, 0, sizeof(o));
+        o.pixels = (unsigned long long)regions[j].width * regions[j].height;
+        for (int k = 0; k < 4; ++k) { o.sum[k] = a.sum[k]; o.sum_sq[k] = a.sum_sq[k]; o.min[k] = (unsigned char)a.mn[k]; o.max[k] = (unsigned char)a.mx[k]; }
+        o.first = a.first; o.flags = stats_flags(a, o.pixels);
+        o.opaque_pixels = a.opaque; o.transparent_pixels = a.transparent; o.grey_pixels = a.grey;
+    }
+    return QOIMI_OK;
 }
 
 // ------------------------------------------------------------------------------------
