@@ -1,5 +1,5 @@
 // qoi_compare.hip — qoimi_compare_images / qoimi_verify_images: are two sets of device images equal, pixel by pixel (cmp_pixels), and what
-// stands at the first difference (cmp_first).  gfx950, wave64.  Included by qoi_host.hip and compiled with it (not a translation unit of its own).
+// stands at the first difference (cmp_first).  gfx950, wave64.  The host side: qoi_host_staged.hip (qoi_kernels.h holds the tables and declares the launcher).
 //
 // The comparison (normative; qoi_amd/imagediff.py: diff states it in Python): image i has npx pixels of ca bytes at a + a_off and of cb bytes at
 // b + b_off, both tightly packed at any byte offset; two pixels are equal when their first min(ca, cb) bytes are.  Per image: how many pixels
@@ -19,19 +19,12 @@
 //                differed - one 64-bit add and one 64-bit min go to the image's result.  Loads are non-temporal: every byte is read once.
 //   cmp_first    a thread per image, behind cmp_pixels: reads pixel `first` of both sides and fills want / got / flags, which makes the
 //                result a function of the inputs alone, whatever order the workgroups finished in.
-#pragma once
 #include "qoi_dev.h"
 
 namespace qoimi {
 
-constexpr uint32_t kCmpThreads = 256, kCmpSteps = 4, kCmpGroupPx = 4, kCmpTilePx = kCmpThreads * kCmpSteps * kCmpGroupPx;
+// (kCmpThreads, kCmpSteps, kCmpGroupPx, kCmpTilePx and the table structs CmpImage / CmpDiff: qoi_kernels.h)
 constexpr uint32_t kCmpNone = 0xFFFFFFFFu;
-
-// chan: bytes per pixel of side A | of side B << 8 | channels want reports << 16 | channels got reports << 24 (a channel that is not
-// reported reads 0xFF: qoimi_verify_images decodes 3-channel images into 4-byte pixels and reports them as the 3-channel decode they stand for)
-struct CmpImage { u64 a_off, b_off; uint32_t npx, first_tile, chan, index; };      // index: the image's entry in the result table
-struct CmpDiff  { u64 mismatched, first; uint32_t want, got, flags, reserved; };    // = qoimi_image_diff; the host sets {0, ~0, ...} before the launch
-static_assert(sizeof(CmpImage) == 32 && sizeof(CmpDiff) == 32, "table layouts");
 
 // A group of four CH-byte pixels at p (sh = address & 3) as CH dwords: the aligned dwords that hold its bytes and no other.
 template <uint32_t CH>
@@ -89,12 +82,6 @@ __device__ __forceinline__ void cmp_tile(const uint8_t* __restrict__ pa, const u
             }
         }
     }
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)v, o); v = t < v ? t : v; }
-    return v;
 }
 
 // The workgroup leaves an image (every thread calls): what its lanes found goes to the image's result - nothing, if nothing differed.
@@ -168,7 +155,6 @@ __global__ __launch_bounds__(256) void cmp_first(const uint8_t* __restrict__ a, 
     d->want = want; d->got = got; d->flags = flags; d->reserved = 0u;
 }
 
-// Both kernels over the m table entries at tab (their tiles: [0, tiles)); grid: workgroups of cmp_pixels, at most `tiles`.
 void launch_compare(const uint8_t* a, const uint8_t* b, const CmpImage* tab, uint32_t m, uint32_t tiles, CmpDiff* diffs, uint32_t grid,
                     hipStream_t st, KernelTimer* tm) {
     tm->mark(kT_begin, st);

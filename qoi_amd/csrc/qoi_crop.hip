@@ -1,5 +1,5 @@
 // qoi_crop.hip — qoimi_decode_crops: rectangles of a sub-batch of decoded images, gathered into the caller's outputs (crop_gather).  gfx950, wave64.
-// Included by qoi_host.hip and compiled with it (not a translation unit of its own).
+// The host side: qoi_host_staged.hip (qoi_kernels.h holds the table and declares the launcher).
 //
 // The result (normative; qoi_amd/crops.py: crop states it in Python, qoi_crop_core.h holds the arithmetic): image i stands in the staging
 // arena as w x rows pixels of 4 bytes (the decoder's output at 4 channels down to the last row a crop needs: a 256-aligned slot, every pixel an
@@ -17,15 +17,10 @@
 //                 entry holds its crop's first tile); a workgroup takes a contiguous range of tiles (qoi_dev.h: walk_tiles), so one launch
 //                 serves every crop of a sub-batch.  No LDS, no barrier, no atomics; not one byte
 //                 outside a crop's output is written.
-#pragma once
 #include "qoi_dev.h"
 #include "qoi_crop_core.h"
 
 namespace qoimi {
-
-// cfg: och | flags << 8
-struct CropEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, ch, first_tile, cfg, reserved; };
-static_assert(sizeof(CropEntry) == 48, "table layout");
 
 typedef uint32_t crop_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -57,8 +52,6 @@ __global__ __launch_bounds__(kCropThreads) void crop_gather(const uint8_t* __res
     });
 }
 
-// The kernel over the m table entries at tab (their tiles: [0, tiles)); grid: workgroups, at most `tiles`.  No timer marks: the kernel has no
-// entry in the name table (qoimi_crop_stats counts its launches).
 void launch_crop(const uint8_t* stage, const CropEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, uint32_t grid, hipStream_t st) {
     hipLaunchKernelGGL(crop_gather, dim3(grid), dim3(kCropThreads), 0, st, stage, tab, m, tiles, out);
 }

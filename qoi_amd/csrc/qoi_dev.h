@@ -63,8 +63,13 @@ __device__ __forceinline__ int wave_max(int v) {
     for (int o = 32; o > 0; o >>= 1) { int t = __shfl_xor(v, o); v = t > v ? t : v; }
     return v;
 }
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)v, o); v = t < v ? t : v; }
+    return v;
+}
 
-// The tile walk of the table-driven kernels over staged pixels (thumb_reduce, crop_gather, resize_filter).  The host lays `tiles` tiles over
+// The tile walk of the table-driven kernels over staged pixels (thumb_reduce, crop_gather, resize_filter, stats_reduce).  The host lays `tiles` tiles over
 // a table of m entries - any struct with a first_tile; every entry has a tile, the first_tile ascend from 0 - and launches at most `tiles`
 // workgroups.  A workgroup takes a contiguous range of tiles: one binary search for the entry of its first tile (the last one whose first
 // tile is not behind it), then it steps on from entry to entry, one step at most per tile.  body(entry, tile within the entry) runs once per

@@ -1,5 +1,5 @@
 // qoi_inspect.hip — qoimi_inspect_streams: the chunk walk of a stream without pixel state (chunk counts, pixels, run pixels, repeated
-// QOI_OP_INDEX, where the walk ends).  gfx950, wave64.  Included by qoi_host.hip and compiled with it (not a translation unit of its own).
+// QOI_OP_INDEX, where the walk ends).  gfx950, wave64.  The host side: qoi_host_pack.hip (qoi_kernels.h holds the tables and declares the launcher).
 //
 // The walk is serial only in its PHASE: a piece of a stream that is entered e = 0..4 bytes behind its first byte (the chunk in front of
 // it reaches e bytes in) leaves x = 0..4 bytes over into the next piece.  A piece is therefore a map {0..4} -> {0..4}: five 3-bit
@@ -21,21 +21,13 @@
 //
 // The stream bytes are read twice (inspect_maps, inspect_count), always as the aligned dwords that hold bytes of the body [14, size - 8):
 // a chunk that starts below size - 8 is counted by its tag byte alone, so nothing behind the body is needed for the walk.
-#pragma once
 #include "qoi_dev.h"
 
 namespace qoimi {
 
-constexpr uint32_t kInsPiece = 64u, kInsTile = 64u * kInsPiece, kInsTiles = 4u, kInsBlock = kInsTile * kInsTiles;
+// (kInsPiece, kInsTile, kInsTiles, kInsBlock, kInsFirst and the table structs: qoi_kernels.h)
 constexpr uint32_t kInsIdentity = 0u | (1u << 3) | (2u << 6) | (3u << 9) | (4u << 12);
 constexpr uint32_t kInsNoTag = 0x100u;          // "no chunk starts here" where a tag byte is expected
-constexpr uint32_t kInsFirst = 0x80000000u;     // InsBlock::len: the block is the first of its stream
-
-struct InsBlock   { u64 off; uint32_t len; uint32_t piece_base; };     // body bytes [off, off + (len & ~kInsFirst)) of the caller's buffer; index of its first piece map
-struct InsStream  { u64 off; uint32_t size; uint32_t first_blk; };     // off == ~0: shorter than 22 bytes, nothing is read
-struct InsPartial { uint32_t ops[6], run_px, repeat, first, last, exit, pad; };   // first / last: tag byte of the block's first / last chunk (kInsNoTag: none)
-struct InsResult  { u64 pixels, run_pixels; uint32_t ops[6], repeat_index, walk_end, flags, reserved[3]; };   // = qoimi_stream_info
-static_assert(sizeof(InsBlock) == 16 && sizeof(InsStream) == 16 && sizeof(InsPartial) == 48 && sizeof(InsResult) == 64, "table layouts");
 
 // bytes of the chunk whose tag byte is b (qoi.h:547-575)
 __device__ __forceinline__ uint32_t ins_len(uint32_t b) { return b >= kTagRgb ? b - 0xFAu : ((b >> 6) == 2u ? 2u : 1u); }

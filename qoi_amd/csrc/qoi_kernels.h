@@ -269,5 +269,55 @@ void launch_pack_streams(const uint8_t* streams, size_t stride, const int* lens,
 void launch_pack_append(const uint8_t* staging, size_t stride, const u64* src_off, const int* lens, uint32_t first, uint32_t m, unsigned align,
                         uint8_t* packed, size_t cap, u64* off, uint32_t grid, hipStream_t st, KernelTimer* tm);
 void launch_gather_headers(const uint8_t* streams, const u64* offs, uint32_t n, uint32_t* out, hipStream_t st);
+constexpr uint32_t kPackTile = 16384;    // bytes of the pack per tile of pack_copy
+
+// ---- chunk statistics (qoi_inspect.hip) --------------------------------------------
+constexpr uint32_t kInsPiece = 64u, kInsTile = 64u * kInsPiece, kInsTiles = 4u, kInsBlock = kInsTile * kInsTiles;
+constexpr uint32_t kInsFirst = 0x80000000u;     // InsBlock::len: the block is the first of its stream
+
+struct InsBlock   { u64 off; uint32_t len; uint32_t piece_base; };     // body bytes [off, off + (len & ~kInsFirst)) of the caller's buffer; index of its first piece map
+struct InsStream  { u64 off; uint32_t size; uint32_t first_blk; };     // off == ~0: shorter than 22 bytes, nothing is read
+struct InsPartial { uint32_t ops[6], run_px, repeat, first, last, exit, pad; };   // first / last: tag byte of the block's first / last chunk (kInsNoTag: none)
+struct InsResult  { u64 pixels, run_pixels; uint32_t ops[6], repeat_index, walk_end, flags, reserved[3]; };   // = qoimi_stream_info
+static_assert(sizeof(InsBlock) == 16 && sizeof(InsStream) == 16 && sizeof(InsPartial) == 48 && sizeof(InsResult) == 64, "table layouts");
+
+void launch_inspect(const uint8_t* streams, const InsStream* tab, uint32_t n_streams, const InsBlock* blocks, uint32_t n_blocks,
+                    uint32_t* block_map, uint8_t* entry, uint16_t* piece_map, InsPartial* partial, InsResult* result, uint32_t* raw,
+                    hipStream_t st, KernelTimer* tm);
+
+// ---- images against images (qoi_compare.hip) ---------------------------------------
+constexpr uint32_t kCmpThreads = 256, kCmpSteps = 4, kCmpGroupPx = 4, kCmpTilePx = kCmpThreads * kCmpSteps * kCmpGroupPx;
+
+// chan: bytes per pixel of side A | of side B << 8 | channels want reports << 16 | channels got reports << 24 (a channel that is not
+// reported reads 0xFF: qoimi_verify_images decodes 3-channel images into 4-byte pixels and reports them as the 3-channel decode they stand for)
+struct CmpImage { u64 a_off, b_off; uint32_t npx, first_tile, chan, index; };      // index: the image's entry in the result table
+struct CmpDiff  { u64 mismatched, first; uint32_t want, got, flags, reserved; };    // = qoimi_image_diff; the host sets {0, ~0, ...} before the launch
+static_assert(sizeof(CmpImage) == 32 && sizeof(CmpDiff) == 32, "table layouts");
+
+// Both kernels over the m table entries at tab (their tiles: [0, tiles)); grid: workgroups of cmp_pixels, at most `tiles`.
+void launch_compare(const uint8_t* a, const uint8_t* b, const CmpImage* tab, uint32_t m, uint32_t tiles, CmpDiff* diffs, uint32_t grid,
+                    hipStream_t st, KernelTimer* tm);
+
+// ---- table-driven kernels over staged pixels (qoi_thumb.hip, qoi_crop.hip, qoi_resize.hip, qoi_stats.hip) ------------------------
+// One entry per output (thumbnail, crop, resized item, region); the tile sizes, the largest factors and the arithmetic stand in
+// qoi_*_core.h, which the host tests compile without HIP.  launch_*: the kernel over the m table entries at tab (their tiles: [0, tiles));
+// grid: workgroups, at most `tiles`.  No timer marks: these kernels have no entry in the name table (the calls count their launches).
+// ThumbImage::cfg: log2(L) | c << 8 | och << 16 | (alpha weighted ? 1 : 0) << 24
+struct ThumbImage { u64 src_off, dst_off; uint32_t w, h, tw, th, f, first_tile, cfg, reserved; };
+// CropEntry::cfg: och | flags << 8
+struct CropEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, ch, first_tile, cfg, reserved; };
+// ResizeEntry::cfg: log2(L) | c << 8 | och << 16 | (alpha weighted ? 1 : 0) << 24 | flags << 28
+struct ResizeEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, rh, ow, oh, first_tile, cfg, reserved; };
+// StatsEntry::index: the region's entry in the result table (and its histogram); cfg: the region's flags
+struct StatsEntry { u64 src_off; uint32_t w, x, y, cw, ch, first_tile, index, cfg, reserved[2]; };
+static_assert(sizeof(ThumbImage) == 48 && sizeof(CropEntry) == 48 && sizeof(ResizeEntry) == 56 && sizeof(StatsEntry) == 48, "table layouts");
+struct StatsAcc;                                       // a region's result (qoi_stats_core.h)
+constexpr uint32_t kStatsBins = 4u * 256u;             // counters of a region's histogram
+
+void launch_thumb(const uint8_t* stage, const ThumbImage* tab, uint32_t m, uint32_t tiles, uint8_t* out, uint32_t grid, hipStream_t st);
+void launch_crop(const uint8_t* stage, const CropEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, uint32_t grid, hipStream_t st);
+void launch_resize(const uint8_t* stage, const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, uint32_t grid, hipStream_t st);
+// hist: NULL or the call's histograms
+void launch_stats(const uint8_t* stage, const StatsEntry* tab, uint32_t m, uint32_t tiles, StatsAcc* res, unsigned* hist, uint32_t grid, hipStream_t st);
 
 }  // namespace qoimi

@@ -1,7 +1,6 @@
 // qoi_pack.hip — streams back to back: the offsets of a pack (pack_offsets), the copy into it (pack_copy), their append forms
 // (pack_offsets_append, pack_copy_append: qoimi_encode_packed adds a sub-batch of streams to a pack that earlier launches began) and
-// the header gather of qoimi_read_descs (gather_headers).  gfx950, wave64.  Included by qoi_host.hip and compiled with it (not a translation unit of its own).
-#pragma once
+// the header gather of qoimi_read_descs (gather_headers).  gfx950, wave64.  The host side: qoi_host_pack.hip (qoi_kernels.h declares the launchers).
 #include "qoi_dev.h"
 
 namespace qoimi {
@@ -74,7 +73,7 @@ __global__ __launch_bounds__(1024) void pack_offsets_append(const int* __restric
 // a stream that does not end at or below `cap` is not written at all.
 // Loads are non-temporal (a stream is read once), stores plain (what comes next reads the pack).
 // ---------------------------------------------------------------------------------
-constexpr uint32_t kPackTile = 16384, kPackThreads = 256, kPackPer = kPackTile / 16u / kPackThreads;
+constexpr uint32_t kPackThreads = 256, kPackPer = kPackTile / 16u / kPackThreads;       // (kPackTile: qoi_kernels.h)
 // The append form (qoimi_encode_packed) copies the streams [first, e) of a sub-batch behind what earlier launches put into the pack: its range
 // of the destination is [off[first], min(off[e], cap)), searches stay inside [first, e], stream j is read at streams + (j - first) * stride
 // or, for a call of mixed shapes, at streams + src_off[j].  The granule that holds off[first] may hold the tail of the previous sub-batch's

@@ -1,5 +1,5 @@
 // qoi_resize.hip — qoimi_decode_resized: rectangles of a sub-batch of decoded images resampled to caller-chosen sizes by an exact integer area
-// filter (resize_filter).  gfx950, wave64.  Included by qoi_host.hip and compiled with it (not a translation unit of its own).
+// filter (resize_filter).  gfx950, wave64.  The host side: qoi_host_staged.hip (qoi_kernels.h holds the table and declares the launcher).
 //
 // The result (normative; qoi_amd/resize.py: resize states it in Python, qoi_resize_core.h holds the arithmetic): image i stands in the staging
 // arena as w x rows pixels of 4 bytes (the decoder's output at 4 channels down to the last row an item needs: a 256-aligned slot, every pixel an
@@ -22,15 +22,10 @@
 //                 or not: one dword where the output holds 4 bytes per pixel and the address is aligned, else 3 or 4 bytes - never a word it
 //                 would have to read first, two outputs may share one.  No LDS, no barrier, no atomics; not one byte outside an item's
 //                 output is written.
-#pragma once
 #include "qoi_dev.h"
 #include "qoi_resize_core.h"
 
 namespace qoimi {
-
-// cfg: log2(L) | c << 8 | och << 16 | (alpha weighted ? 1 : 0) << 24 | flags << 28
-struct ResizeEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, rh, ow, oh, first_tile, cfg, reserved; };
-static_assert(sizeof(ResizeEntry) == 56, "table layout");
 
 struct ResizeMem {
     const uint32_t* src;
@@ -83,8 +78,6 @@ __global__ __launch_bounds__(kResizeThreads) void resize_filter(const uint8_t* _
     });
 }
 
-// The kernel over the m table entries at tab (their tiles: [0, tiles)); grid: workgroups, at most `tiles`.  No timer marks: the kernel has no
-// entry in the name table (qoimi_resize_stats counts its launches).
 void launch_resize(const uint8_t* stage, const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, uint32_t grid, hipStream_t st) {
     hipLaunchKernelGGL(resize_filter, dim3(grid), dim3(kResizeThreads), 0, st, stage, tab, m, tiles, out);
 }

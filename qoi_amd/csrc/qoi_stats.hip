@@ -1,5 +1,5 @@
 // qoi_stats.hip — qoimi_pixel_stats: per-region pixel statistics of a sub-batch of decoded images (stats_reduce).  gfx950, wave64.
-// Included by qoi_host.hip and compiled with it (not a translation unit of its own).
+// The host side: qoi_host_staged.hip (qoi_kernels.h holds the table and declares the launcher).
 //
 // The result (normative; qoi_amd/pixelstats.py: stats states it in Python, qoi_stats_core.h holds the arithmetic and the bounds): image i stands
 // in the staging arena as w x rows pixels of 4 bytes; a region is a rectangle of it; per region: the sum and the sum of squares of every
@@ -11,8 +11,8 @@
 //                 (qoi_dev.h: walk_tiles), so one launch serves every region of a sub-batch.  A lane takes four consecutive pixels: one
 //                 division by the region's width, then it steps on; it reads them as aligned dwords - plain loads: regions may share pixels -
 //                 and nothing outside the region.  A lane keeps four sums, four 64-bit sums of squares, minimum and maximum per channel and
-//                 three counters (qoi_stats_core.h says why 32 bits hold the sums).  When the workgroup leaves a region (cmp_flush of
-//                 qoi_compare.hip) the sums are added across the wavefront in 64 bits and the minima / maxima minimised / maximised with
+//                 three counters (qoi_stats_core.h says why 32 bits hold the sums).  When the workgroup leaves a region (as cmp_flush
+//                 of qoi_compare.hip does) the sums are added across the wavefront in 64 bits and the minima / maxima minimised / maximised with
 //                 cross-lane operations, the four wavefronts meet in 19 x 4 words of LDS, and 19 lanes send one atomic each to the region's
 //                 result: 64-bit adds (none for a zero), 32-bit minima and maxima.  All integer: the result is the same whatever order the
 //                 workgroups finish in.  The lane that holds pixel 0 of tile 0 also stores `first`, the pixel the flipped region begins with.
@@ -20,19 +20,12 @@
 //                 all pixels of a wavefront are equal (flat content: 64 lanes on one counter) sends one add of the lane count per channel
 //                 instead; on leaving a region the non-zero counters go to the region's device histogram with atomic adds and the LDS copy is
 //                 cleared.  <false> holds the reduction words and no other LDS.
-#pragma once
 #include "qoi_dev.h"
-#include "qoi_compare.hip"      // wave_min_u32
 #include "qoi_stats_core.h"
 
 namespace qoimi {
 
-// index: the region's entry in the result table (and its histogram); cfg: the region's flags
-struct StatsEntry { u64 src_off; uint32_t w, x, y, cw, ch, first_tile, index, cfg, reserved[2]; };
-static_assert(sizeof(StatsEntry) == 48, "table layout");
-
 constexpr uint32_t kStatsWords = kStatsSums + 8u;      // per wavefront: 11 sums, 4 minima, 4 maxima
-constexpr uint32_t kStatsBins = 4u * 256u;
 constexpr uint32_t kStatsNone = 0xFFFFFFFFu;
 
 template <bool HIST>
@@ -140,8 +133,6 @@ __global__ __launch_bounds__(kStatsThreads) void stats_reduce(const uint8_t* __r
     if (cur != kStatsNone) stats_flush<HIST>(a, &res[cur], HIST ? hist + (u64)cur * kStatsBins : nullptr, s_part, s_bins);
 }
 
-// The kernel over the m table entries at tab (their tiles: [0, tiles)); grid: workgroups, at most `tiles`; hist: NULL or the call's
-// histograms.  No timer marks: the kernel has no entry in the name table (qoimi_pixel_stats_counters counts its launches).
 void launch_stats(const uint8_t* stage, const StatsEntry* tab, uint32_t m, uint32_t tiles, StatsAcc* res, unsigned* hist, uint32_t grid, hipStream_t st) {
     if (hist) hipLaunchKernelGGL(stats_reduce<true>, dim3(grid), dim3(kStatsThreads), 0, st, stage, tab, m, tiles, res, hist);
     else hipLaunchKernelGGL(stats_reduce<false>, dim3(grid), dim3(kStatsThreads), 0, st, stage, tab, m, tiles, res, hist);

@@ -1,5 +1,5 @@
 // qoi_thumb.hip — qoimi_decode_thumbnails: the exact integer box reduction of a sub-batch of decoded images (thumb_reduce).  gfx950, wave64.
-// Included by qoi_host.hip and compiled with it (not a translation unit of its own).
+// The host side: qoi_host_staged.hip (qoi_kernels.h holds the table and declares the launcher).
 //
 // The reduction (normative; qoi_amd/thumbs.py: thumbnail states it in Python, qoi_thumb_core.h holds the arithmetic): image i stands in the
 // staging arena as w x h pixels of 4 bytes (the decoder's output at 4 channels: a 256-aligned slot, every pixel an aligned dword); output
@@ -22,15 +22,10 @@
 //                 numbered so that a block's lanes are neighbours in one wavefront), the first of them divides (qoi_thumb_core.h) and
 //                 stores the pixel: one dword where the thumbnail holds 4 bytes per pixel and the address is aligned, else 3 or 4 bytes.
 //                 No LDS, no barrier, no atomics; not one byte outside a thumbnail is written.
-#pragma once
 #include "qoi_dev.h"
 #include "qoi_thumb_core.h"
 
 namespace qoimi {
-
-// cfg: log2(L) | c << 8 | och << 16 | (alpha weighted ? 1 : 0) << 24
-struct ThumbImage { u64 src_off, dst_off; uint32_t w, h, tw, th, f, first_tile, cfg, reserved; };
-static_assert(sizeof(ThumbImage) == 48, "table layout");
 
 typedef uint32_t thumb_u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t thumb_u32x4 __attribute__((ext_vector_type(4)));
@@ -112,8 +107,6 @@ __global__ __launch_bounds__(kThumbThreads) void thumb_reduce(const uint8_t* __r
     });
 }
 
-// The kernel over the m table entries at tab (their tiles: [0, tiles)); grid: workgroups, at most `tiles`.  No timer marks: the kernel has no
-// entry in the name table (qoimi_thumbnail_stats counts its launches).
 void launch_thumb(const uint8_t* stage, const ThumbImage* tab, uint32_t m, uint32_t tiles, uint8_t* out, uint32_t grid, hipStream_t st) {
     hipLaunchKernelGGL(thumb_reduce, dim3(grid), dim3(kThumbThreads), 0, st, stage, tab, m, tiles, out);
 }

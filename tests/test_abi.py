@@ -54,15 +54,32 @@ def test_environment_knobs_are_gated(lib):
     if os.path.exists(test):
         assert b"QOIMI_TEST_SPIN_BOUND" in open(test, "rb").read()
     assert "QOIMI_LIB" not in open(os.path.join(ROOT, "qoi_amd", "api.py")).read()
-    # ... and no kernel file asks the environment anything; the host shim asks for three documented settings, QOIMI_TUNING, and - inside
-    # the gate or the test-hook block - the knobs
-    for f in ("qoi_encode.hip", "qoi_decode.hip", "qoi_synth.hip"):
-        assert "getenv" not in open(os.path.join(ROOT, "qoi_amd", "csrc", f)).read(), f
-    host = open(os.path.join(ROOT, "qoi_amd", "csrc", "qoi_host.hip")).read()
+    # ... and no other file of the library asks the environment anything; the host shim asks for three documented settings, QOIMI_TUNING, and
+    # - inside the gate or the test-hook block - the knobs
+    csrc = os.path.join(ROOT, "qoi_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")) and f != "qoi_host.hip":
+            assert "getenv" not in open(os.path.join(csrc, f)).read(), f
+    host = open(os.path.join(csrc, "qoi_host.hip")).read()
     gate = host.index('getenv("QOIMI_TUNING")')
     outside = [m for m in re.findall(r'getenv\("(QOIMI_[A-Z0-9_]+)"\)', host[:gate])]
     assert sorted(outside) == ["QOIMI_ENCODE_TIGHT_BUFFER", "QOIMI_ENC_PROBE"], outside
     assert re.findall(r'getenv\("(QOIMI_[A-Z0-9_]+)"\)', host[host.index("static qoimi_ctx* thread_ctx()"):]) == ["QOIMI_DEVICE"]
+
+
+def test_every_hip_file_is_a_listed_translation_unit():
+    """sources.mk - the one source list of the library's Makefile and of the fuzz build - names every *.hip of qoi_amd/csrc and nothing
+    else, and no file there pulls a .hip in with #include: a kernel file cannot be compiled twice or left out of a flavour."""
+    csrc = os.path.join(ROOT, "qoi_amd", "csrc")
+    mk = open(os.path.join(csrc, "sources.mk")).read()
+    listed = re.search(r"^SRCS\s*:?=((?:.*\\\n)*.*)$", mk, re.M).group(1).replace("\\\n", " ").split()
+    assert sorted(listed) == sorted(f for f in os.listdir(csrc) if f.endswith(".hip")) and len(set(listed)) == len(listed)
+    for mf in (os.path.join(csrc, "Makefile"), os.path.join(ROOT, "tests", "fuzz", "Makefile")):
+        text = open(mf).read()
+        assert re.search(r"^include .*sources\.mk$", text, re.M) and not re.search(r"^SRCS\s*:?=", text, re.M), mf
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")):
+            assert not re.search(r'^\s*#\s*include\s*["<][^">]*\.hip[">]', open(os.path.join(csrc, f)).read(), re.M), f
 
 
 def test_desc_layout():

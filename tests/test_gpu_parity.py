@@ -1282,7 +1282,7 @@ def test_encode_batch_many_small_images(api, ctx, oracle, shape):
 
 
 def test_failed_lds_order_recheck_is_counted_and_reported_once(api):
-    """The repeat of the LDS exchange-order self-test (qoi_host.hip, include/qoi_mi355x.h): forced to fail by the test hook with a
+    """The repeat of the LDS exchange-order self-test (qoi_host_encode.hip, qoi_ctx.h: enc_poll_recheck; include/qoi_mi355x.h): forced to fail by the test hook with a
     repeat after every call.  The call that notices is encoded with the order-independent probe and succeeds, the calls made with
     the suspect probe since the last passed check are counted (all of them - the one made before the repeat was launched too),
     and the next qoimi_encode_status reports the event exactly once (tests/hook_scenarios.py: recheck_fail, on the test flavour)."""
