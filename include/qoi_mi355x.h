@@ -576,6 +576,113 @@ int qoimi_pixel_stats(qoimi_ctx *ctx, const void *d_streams, const size_t *strea
  * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] images decoded (the referenced ones). */
 void qoimi_pixel_stats_counters(qoimi_ctx *ctx, long long out[4]);
 
+/* A row seek index: a band of an image without the rows above it.  The gather calls above stop at the last row a rectangle needs but start
+ * at row 0 (every pixel depends on the one before): a 256-row band at the top of a 16384 x 16384 scan stages 16 MiB, the same band at the bottom
+ * the whole image.  The decoder's state at a row boundary is small - the previous pixel, the 64-entry colour table, a byte position, what is left
+ * of a run - so it can be kept (a SEEK POINT, 272 bytes) and written down as QOI chunks: a BAND STREAM is a header, at most 64 QOI_OP_RGBA chunks
+ * that load the table and the previous pixel, QOI_OP_RUN chunks that pad to whole rows, and the original stream's bytes from the point on.  It is
+ * an ordinary QOI stream; decoded by any decode call as it is, its rows from pad_rows on are the band's rows of the full decode, bit-exact for
+ * EVERY input stream (cut streams, wrong end markers, hostile bodies: the leniency of qoi_decode carries over).
+ * All of it (normative; qoi_amd/seekindex.py states it in Python).  For an image of w x h, a stream of `size` bytes, D its decode at 4 channels as
+ * qoimi_decode_images gives it and an interval of K rows, K * w >= 128, the seek points are at the rows K, 2K, ... < h: ceil(h / K) - 1 of them,
+ * possibly none.  Point k (from 0) sits at pixel P = (k + 1) * K * w and holds
+ *   byte_off, skip  the walk of qoimi_inspect_streams: p = 14, end = size - 8, px = 0; while p < end: n = pixels of the chunk at p; px + n > P:
+ *                   stop; else px += n, p += the chunk's length.  Stopped inside the body: byte_off = p, skip = P - px (0..61, non-zero only inside
+ *                   a QOI_OP_RUN).  The walk ran out: byte_off = size - 8, skip = 0
+ *   prev            pixel P - 1 of D as r | g << 8 | b << 16 | a << 24
+ *   table[s]        the last pixel of D in front of P whose hash (3r + 5g + 7b + 11a) % 64 is s, else 0
+ * The band stream of the band (first_row, rows) - first_row 0 or a seek row, first_row + rows <= h; e the point at first_row, e2 the first point
+ * at a row >= first_row + rows, if there is one - is, concatenated: the header qoif, w, pad_rows + rows, the original channels and colorspace; for s
+ * ascending every table[s] that is neither 0 nor prev as FF r g b a, then prev the same way (n <= 64 chunks); with pad_rows = max(1, ceil((n + skip)
+ * / w)) and R = pad_rows * w - skip - n: R / 62 bytes 0xFD and, if R % 62 != 0, one byte 0xC0 | (R % 62 - 1); the original bytes [byte_off,
+ * min(byte_off(e2) + 13, size)), up to size without e2.  first_row == 0: no loads, pad_rows = 0, the original bytes from 14 on.  pad_rows <= K always.
+ * Costs, stated plainly: building an index is one qoimi_inspect_streams plus one full decode of every image that has a point; an indexed call
+ * copies each band's stream bytes once.  Build it once per pack and keep 272 bytes per point beside the pack's offsets. */
+typedef struct { unsigned byte_off, skip, prev, reserved; unsigned table[64]; } qoimi_seek_point;   /* 272 bytes; reserved: 0 */
+typedef struct { unsigned image, first_row, rows, reserved; } qoimi_band;                            /* 16 bytes; reserved is not looked at */
+typedef struct { unsigned long long size; qoi_desc desc; unsigned pad_rows; } qoimi_band_info;       /* 24 bytes, offsets 0/8/20 */
+
+/* ceil(height / interval_rows) - 1, the seek points of an image, or -1 if desc is rejected, interval_rows == 0 or interval_rows * width < 128.
+ * Pure host arithmetic: no context, no GPU. */
+int qoimi_seek_points(const qoi_desc *desc, unsigned interval_rows);
+
+/* The seek points of every image of a pack.
+ *   stream_offsets, sizes, descs  HOST arrays as for qoimi_decode_images
+ *   interval_rows  HOST unsigned[n_images]: image i's K
+ *   points_out     HOST qoimi_seek_point[sum of qoimi_seek_points(&descs[i], interval_rows[i])], the images' points back to back in image order
+ *   staging_bytes  as for qoimi_decode_thumbnails: the arena of the gather calls, 4 bytes per pixel, slots of width * height * 4 rounded up to 256
+ *                  bytes over the images that HAVE a point, in order, sub-batches cut by qoi_amd/packplan.py: plan; 0: 1 GiB
+ * byte_off and skip come from the passes of qoimi_inspect_streams as they are, a scan of the pixels of their 16 KiB blocks and one wavefront per
+ * point that walks one block (no stream is walked serially); prev and table from one qoimi_decode_images call per sub-batch as it is, at 4 output
+ * channels, and two small kernels over the staged pixels.  Workspace beside the staging (counted in qoimi_workspace_bytes [1]): that of
+ * qoimi_inspect_streams plus 8 bytes per 16 KiB block and 552 per point.  One wavefront per image walks that image's points in order (the
+ * table is carried from point to point): the time of that step grows with the points of the image that has most, a few thousand are nothing, an
+ * interval of one row on an image of millions of rows is millions of dependent steps - choose intervals of tens to hundreds of rows.
+ * SYNCHRONOUS.  QOIMI_E_ARG for a NULL ctx, d_streams, stream_offsets, sizes, descs, interval_rows or points_out, n_images <= 0, sizes[i] < 22, a
+ * rejected descriptor, interval_rows[i] * width < 128, 2^25 seek points or more, more than 2^31 blocks of stream bytes, 2^31 - 1 or more tiles of
+ * 1024 pixels in a sub-batch:
+ * reported before anything is launched, points_out is untouched.  The sub-batches count as decode calls of the context, as those of
+ * qoimi_verify_images do.  One call at a time per context, as everywhere. */
+int qoimi_build_seek_index(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                           const qoi_desc *descs /* host */, int n_images, const unsigned *interval_rows /* host, n_images */,
+                           qoimi_seek_point *points_out /* host */, size_t staging_bytes, void *stream);
+
+/* What the band stream of `band` will be: its size, its descriptor (width, pad_rows + rows, the image's channels and colorspace) and pad_rows -
+ * from the points alone, without the stream's bytes.  points: this image's (may be NULL where the band uses none: an image without points);
+ * band->image is not looked at.  0 on success; QOIMI_E_ARG for a NULL desc, band or out, a rejected descriptor, size < 22, interval_rows * width <
+ * 128, a first_row that is neither 0 nor a seek row, rows == 0, first_row + rows > height, a band stream of 2^31 - 1 bytes or more, and a point
+ * the band uses that cannot be one.  An index is the caller's data; of the points a band uses (e, e2; the others are not read) exactly this is
+ * CHECKED, and it is what keeps every read inside the stream and every write inside the band stream: byte_off inside [14, size - 8], skip <= 61,
+ * byte_off(e2) + 13 >= byte_off(e), and n <= 64 loads for e (a point of a stream holds prev in prev's own slot; 64 table words that are all
+ * non-zero and differ from prev would be 65 loads).  Everything else is TRUSTED and, where wrong, gives wrong pixels and nothing worse: that
+ * byte_off is a chunk's first byte of THIS stream, that skip, prev and the table words are the decoder's state there, that reserved is 0.
+ * Pure host arithmetic: no context, no GPU. */
+int qoimi_band_plan(const qoi_desc *desc, int size, unsigned interval_rows, const qoimi_seek_point *points /* this image's */,
+                    const qoimi_band *band, qoimi_band_info *out);
+
+/* Band streams, written on the device: band stream j - infos_out[j].size bytes, what qoimi_band_plan says - at d_out + out_offsets[j].
+ *   stream_offsets, sizes, descs, interval_rows  HOST arrays over the n_images images, as for qoimi_build_seek_index; an image that no band names
+ *                  is not checked and its points are not read
+ *   points         HOST, the index; point_firsts HOST size_t[n_images]: image i's points begin at points[point_firsts[i]]
+ *   bands          HOST qoimi_band[n_bands], in any order; several may name the same image
+ *   out_offsets    HOST size_t[n_bands]: ANY byte offsets in any order; not one byte beside a band stream is written (two may share an aligned
+ *                  word: no word is ever read and written back); the ranges must not overlap each other or a stream a band names
+ *   infos_out      HOST qoimi_band_info[n_bands], may be NULL
+ * The caller's index is input and is checked as qoimi_band_plan checks it (byte_off, skip, the order of a band's two points, the number of
+ * loads - see there for what is checked and what is trusted): whatever it holds, nothing outside [stream_offsets[i], + sizes[i]) is read - but
+ * for the aligned 4-byte words that hold a first or last byte - and nothing beside the band streams is written.  A band stream made from another stream's index is still a stream
+ * every decode call accepts; its pixels are then not the band's.
+ * SYNCHRONOUS.  QOIMI_E_ARG for a NULL ctx, d_streams, stream_offsets, sizes, descs, interval_rows, points, point_firsts, bands, d_out or
+ * out_offsets, n_images <= 0, n_bands <= 0, more than 12 782 640 bands, bands[j].image >= n_images, whatever qoimi_band_plan rejects, overlapping ranges, 2^31 - 1 or more
+ * tiles of 256 aligned 16-byte words of output: reported before anything is launched, the caller's buffers are untouched. */
+int qoimi_make_band_streams(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                            const qoi_desc *descs /* host */, int n_images, const unsigned *interval_rows /* host */,
+                            const qoimi_seek_point *points /* host */, const size_t *point_firsts /* host, n_images */,
+                            const qoimi_band *bands /* host */, int n_bands, void *d_out, const size_t *out_offsets /* host, n_bands */,
+                            qoimi_band_info *infos_out /* host, may be NULL */, void *stream);
+
+/* qoimi_decode_crops, byte for byte, decoding each referenced image only from the last seek row at or above its topmost crop.
+ * (normative; qoi_amd/seekindex.py: bands_for_crops): per referenced image i, K = interval_rows[i], first_row = (the smallest y of its crops) / K
+ * * K, rows = (the largest y + height) - first_row.  The band streams of these bands are assembled into an arena of the context (counted in
+ * qoimi_workspace_bytes [1]; planned as the sum of the band streams' sizes, each rounded up to 16 - qoimi_seek_stats [2] - and allocated as
+ * that plus a page, no slack), then qoimi_decode_crops runs as it is over
+ * them: the band streams are the streams, their descriptors the descriptors, the referenced images numbered in ascending order, every crop's y
+ * replaced by y - first_row + pad_rows.  The sub-batch plan and the counters of qoimi_crop_stats are those of that inner call: [2] shows the
+ * saving.  Arguments and rejections of qoimi_decode_crops, and for the referenced images those of qoimi_make_band_streams (an image that no crop
+ * names is not checked and its points are not read); QOIMI_E_ARG also for a NULL interval_rows, points or point_firsts and for more than
+ * 12 782 640 referenced images.  SYNCHRONOUS. */
+int qoimi_decode_crops_indexed(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                               const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                               const qoimi_crop *crops /* host */, int n_crops,
+                               void *d_out, const size_t *out_offsets /* host, n_crops */, size_t staging_bytes, void *stream,
+                               const unsigned *interval_rows /* host, n_images */, const qoimi_seek_point *points /* host */,
+                               const size_t *point_firsts /* host, n_images */);
+
+/* [0] sub-batches decoded by the context's last qoimi_build_seek_index, [1] band streams assembled by its last qoimi_make_band_streams or
+ * qoimi_decode_crops_indexed, [2] bytes of the band arena that call planned for (qoimi_make_band_streams: 0), [3] stream bytes it copied (the
+ * tails).  The kernels have no entry in qoimi_kernel_name. */
+void qoimi_seek_stats(qoimi_ctx *ctx, long long out[4]);
+
 /* Fill device memory with synthetic RGBA frames frame_id = first_frame .. first_frame+n-1
  * (benchmark/test utility; same function of (kind, seed, frame, pixel) as synth.py). */
 int qoimi_synth_frames(qoimi_ctx *ctx, int kind, unsigned seed, unsigned first_frame,
@@ -592,7 +699,8 @@ int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
 /* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace (and the staging arena of
  * qoimi_encode_packed), [1] decode workspace
  * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images,
- * qoimi_decode_thumbnails, qoimi_decode_crops, qoimi_decode_resized and qoimi_pixel_stats, which share them),
+ * qoimi_decode_thumbnails, qoimi_decode_crops, qoimi_decode_resized, qoimi_pixel_stats and qoimi_build_seek_index, which share them, the tables of
+ * qoimi_build_seek_index and the band arena of qoimi_decode_crops_indexed),
  * [2] staging buffers of the host-pointer entry points (qoi_encode / qoi_decode of the calling thread's context). */
 void qoimi_workspace_bytes(qoimi_ctx *ctx, size_t out[3]);
 

@@ -43,6 +43,7 @@ EXPORTS = (
     "qoimi_decode_crops", "qoimi_crop_size", "qoimi_crop_stats",
     "qoimi_decode_resized", "qoimi_resize_size", "qoimi_resize_stats",
     "qoimi_pixel_stats", "qoimi_pixel_stats_counters",
+    "qoimi_seek_points", "qoimi_build_seek_index", "qoimi_band_plan", "qoimi_make_band_streams", "qoimi_decode_crops_indexed", "qoimi_seek_stats",
 )
 
 
@@ -94,6 +95,25 @@ class QoimiPixelStat(ctypes.Structure):
 
 
 assert ctypes.sizeof(QoimiPixelStat) == 128 and [getattr(QoimiPixelStat, f).offset for f, _ in QoimiPixelStat._fields_] == [0, 8, 40, 72, 76, 80, 84, 88, 96, 104, 112]
+
+
+class QoimiSeekPoint(ctypes.Structure):
+    """``qoimi_seek_point``: 272 bytes, the layout of ``seekindex.POINT_DTYPE`` - the decoder's state at a row boundary."""
+    _fields_ = [("byte_off", ctypes.c_uint), ("skip", ctypes.c_uint), ("prev", ctypes.c_uint), ("reserved", ctypes.c_uint), ("table", ctypes.c_uint * 64)]
+
+
+class QoimiBand(ctypes.Structure):
+    """``qoimi_band``: 16 bytes - rows [first_row, first_row + rows) of image ``image``; first_row is 0 or a seek row."""
+    _fields_ = [("image", ctypes.c_uint), ("first_row", ctypes.c_uint), ("rows", ctypes.c_uint), ("reserved", ctypes.c_uint)]
+
+
+class QoimiBandInfo(ctypes.Structure):
+    """``qoimi_band_info``: 24 bytes - what a band stream will be: its size, its descriptor and the rows in front of the band's own."""
+    _fields_ = [("size", ctypes.c_ulonglong), ("desc", QoiDesc), ("pad_rows", ctypes.c_uint)]
+
+
+assert ctypes.sizeof(QoimiSeekPoint) == 272 and [getattr(QoimiSeekPoint, f).offset for f, _ in QoimiSeekPoint._fields_] == [0, 4, 8, 12, 16]
+assert ctypes.sizeof(QoimiBand) == 16 and ctypes.sizeof(QoimiBandInfo) == 24 and (QoimiBandInfo.desc.offset, QoimiBandInfo.pad_rows.offset) == (8, 20)
 
 
 class QoiError(RuntimeError):
@@ -204,6 +224,19 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_pixel_stats.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, cp, ci, ctypes.POINTER(QoimiPixelStat), vp, sz, vp]
     lib.qoimi_pixel_stats_counters.restype = None
     lib.qoimi_pixel_stats_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+    pp, bp, ip = ctypes.POINTER(QoimiSeekPoint), ctypes.POINTER(QoimiBand), ctypes.POINTER(QoimiBandInfo)
+    lib.qoimi_seek_points.restype = ci
+    lib.qoimi_seek_points.argtypes = [dp, ctypes.c_uint]
+    lib.qoimi_build_seek_index.restype = ci
+    lib.qoimi_build_seek_index.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, up, pp, sz, vp]
+    lib.qoimi_band_plan.restype = ci
+    lib.qoimi_band_plan.argtypes = [dp, ci, ctypes.c_uint, pp, bp, ip]
+    lib.qoimi_make_band_streams.restype = ci
+    lib.qoimi_make_band_streams.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, up, pp, szp, bp, ci, vp, szp, ip, vp]
+    lib.qoimi_decode_crops_indexed.restype = ci
+    lib.qoimi_decode_crops_indexed.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, ci, cp, ci, vp, szp, sz, vp, up, pp, szp]
+    lib.qoimi_seek_stats.restype = None
+    lib.qoimi_seek_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     _lib = lib
     return lib
 
@@ -268,6 +301,36 @@ def resize_size(width: int, height: int, channels_in: int, item, channels: int) 
     if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
         return 0
     return int(load_library().qoimi_resize_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels))
+
+
+def seek_points(width: int, height: int, channels_in: int, interval_rows: int) -> int:
+    """``qoimi_seek_points`` for an image of width x height x channels_in: ceil(height / interval_rows) - 1, or -1 where the C function
+    returns -1 (a rejected descriptor, interval_rows == 0, interval_rows * width < 128)."""
+    if not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256 and 0 <= interval_rows < 2 ** 32):
+        return -1
+    return int(load_library().qoimi_seek_points(ctypes.byref(QoiDesc(width, height, channels_in, 0)), interval_rows))
+
+
+def _point_array(points):
+    """An index as a ``QoimiSeekPoint`` array and its length: such an array, or a numpy array of ``seekindex.POINT_DTYPE`` (copied)."""
+    if isinstance(points, ctypes.Array):
+        return points, len(points)
+    from .seekindex import POINT_DTYPE
+    a = np.ascontiguousarray(points, dtype=POINT_DTYPE).reshape(-1)
+    arr = (QoimiSeekPoint * max(a.size, 1))()
+    ctypes.memmove(arr, a.ctypes.data, a.nbytes)
+    return arr, a.size
+
+
+def band_plan(desc: QoiDesc, size: int, interval_rows: int, points, first_row: int, rows: int) -> Optional[QoimiBandInfo]:
+    """``qoimi_band_plan``: what the band stream of rows [first_row, first_row + rows) of an image will be, from the image's points (a
+    ``QoimiSeekPoint`` array or a numpy array of ``seekindex.POINT_DTYPE``) alone; None where the C function returns QOIMI_E_ARG."""
+    if not all(0 <= int(v) < 2 ** 32 for v in (interval_rows, first_row, rows)) or not -2 ** 31 <= int(size) < 2 ** 31:
+        return None
+    arr, _ = _point_array(points)
+    out = QoimiBandInfo()
+    rc = load_library().qoimi_band_plan(ctypes.byref(desc), int(size), int(interval_rows), arr, ctypes.byref(QoimiBand(0, int(first_row), int(rows), 0)), ctypes.byref(out))
+    return out if rc == 0 else None
 
 
 # ----------------------------------------------------------------------------------
@@ -628,6 +691,96 @@ class Context:
         """Of the last ``pixel_stats`` call: (sub-batches decoded, launches of the reduction kernel, bytes of staging planned, images decoded)."""
         out = (ctypes.c_longlong * 4)()
         self._lib.qoimi_pixel_stats_counters(self._h, out)
+        return tuple(int(x) for x in out)
+
+    def build_seek_index(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc],
+                         interval_rows, staging_bytes: int = 0, stream: int = 0):
+        """The seek points of every image of a pack (``qoimi_build_seek_index``, synchronous: one inspect plus one full decode): (points,
+        point_firsts) - points a numpy array of ``seekindex.POINT_DTYPE``, the images' points back to back, image i's from point_firsts[i]
+        on.  interval_rows: one int for all images or one per image, each with interval_rows * width >= 128; ``qoi_amd/seekindex.py:
+        points`` states the result."""
+        from .seekindex import POINT_DTYPE
+        n = len(sizes)
+        if isinstance(interval_rows, (int, np.integer)):
+            interval_rows = [int(interval_rows)] * n
+        if len(descs) != n or len(stream_offsets) != n or len(interval_rows) != n:
+            raise QoiError("build_seek_index: one stream offset, size, descriptor and interval per image")
+        counts = [seek_points(d.width, d.height, d.channels, int(k)) for d, k in zip(descs, interval_rows)]
+        if any(k < 0 for k in counts):
+            raise QoiError("build_seek_index: a rejected descriptor or interval_rows * width < 128")
+        firsts = [int(x) for x in np.cumsum([0] + counts[:-1])]
+        points = np.zeros(sum(counts), dtype=POINT_DTYPE)
+        room = points if points.size else np.zeros(1, dtype=POINT_DTYPE)
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        ks = np.ascontiguousarray(interval_rows, dtype=np.uintc)
+        self._check(self._lib.qoimi_build_seek_index(self._h, d_streams, so.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                     (QoiDesc * n)(*descs), n, ks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)),
+                                                     room.ctypes.data_as(ctypes.POINTER(QoimiSeekPoint)), staging_bytes, stream), "qoimi_build_seek_index")
+        return points, firsts
+
+    def make_band_streams(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], interval_rows,
+                          points, point_firsts: Sequence[int], bands, d_out: int, out_offsets: Sequence[int], stream: int = 0) -> List[QoimiBandInfo]:
+        """Band streams written on the device (``qoimi_make_band_streams``, synchronous): band stream j at d_out + out_offsets[j]; returns
+        one ``QoimiBandInfo`` per band.  bands: ``QoimiBand`` structures or (image, first_row, rows) tuples; points, point_firsts: as
+        ``build_seek_index`` returns them; ``qoi_amd/seekindex.py: band_stream`` states the result."""
+        n = len(sizes)
+        if isinstance(interval_rows, (int, np.integer)):
+            interval_rows = [int(interval_rows)] * n
+        if len(descs) != n or len(stream_offsets) != n or len(interval_rows) != n or len(point_firsts) != n:
+            raise QoiError("make_band_streams: one stream offset, size, descriptor, interval and first point per image")
+        if len(out_offsets) != len(bands):
+            raise QoiError("make_band_streams: one output offset per band")
+        rows = [(b.image, b.first_row, b.rows) if isinstance(b, QoimiBand) else tuple(int(v) for v in b) for b in bands]
+        if any(len(r) != 3 or any(not 0 <= v < 2 ** 32 for v in r) for r in rows):
+            raise QoiError("make_band_streams: a band is not three unsigned 32-bit fields")
+        arr = (QoimiBand * max(len(rows), 1))(*[QoimiBand(r[0], r[1], r[2], 0) for r in rows])
+        pts, _ = _point_array(points)
+        infos = (QoimiBandInfo * max(len(rows), 1))()
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
+        pf = np.ascontiguousarray(point_firsts, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        ks = np.ascontiguousarray(interval_rows, dtype=np.uintc)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        self._check(self._lib.qoimi_make_band_streams(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), (QoiDesc * n)(*descs), n,
+                                                      ks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), pts, pf.ctypes.data_as(szp), arr, len(rows), d_out,
+                                                      oo.ctypes.data_as(szp), infos, stream), "qoimi_make_band_streams")
+        return list(infos)[:len(rows)]
+
+    def decode_crops_indexed(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                             crops, d_out: int, out_offsets: Sequence[int], interval_rows, points, point_firsts: Sequence[int],
+                             staging_bytes: int = 0, stream: int = 0) -> None:
+        """``decode_crops`` byte for byte, decoding every referenced image only from the last seek row at or above its topmost crop
+        (``qoimi_decode_crops_indexed``).  interval_rows, points, point_firsts: as ``build_seek_index`` took and returned them;
+        ``crop_stats`` then holds the counters of the inner call over the band streams."""
+        n = len(sizes)
+        if isinstance(interval_rows, (int, np.integer)):
+            interval_rows = [int(interval_rows)] * n
+        if len(descs) != n or len(stream_offsets) != n or len(interval_rows) != n or len(point_firsts) != n:
+            raise QoiError("decode_crops_indexed: one stream offset, size, descriptor, interval and first point per image")
+        if len(out_offsets) != len(crops):
+            raise QoiError("decode_crops_indexed: one output offset per crop")
+        arr = _crop_array(crops)
+        if arr is None:
+            raise QoiError("decode_crops_indexed: a crop is not six unsigned 32-bit fields")
+        pts, _ = _point_array(points)
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
+        pf = np.ascontiguousarray(point_firsts, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        ks = np.ascontiguousarray(interval_rows, dtype=np.uintc)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        self._check(self._lib.qoimi_decode_crops_indexed(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                         (QoiDesc * n)(*descs), n, channels, arr, len(arr), d_out, oo.ctypes.data_as(szp), staging_bytes,
+                                                         stream, ks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), pts, pf.ctypes.data_as(szp)),
+                    "qoimi_decode_crops_indexed")
+
+    def seek_stats(self) -> Tuple[int, int, int, int]:
+        """(sub-batches decoded by the last ``build_seek_index``; of the last ``make_band_streams`` / ``decode_crops_indexed``: band streams
+        assembled, bytes of the band arena planned, stream bytes copied)."""
+        out = (ctypes.c_longlong * 4)()
+        self._lib.qoimi_seek_stats(self._h, out)
         return tuple(int(x) for x in out)
 
     def synth_frames(self, kind: int, seed: int, first_frame: int, n_frames: int, width: int, height: int,

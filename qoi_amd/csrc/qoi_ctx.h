@@ -111,6 +111,8 @@ struct qoimi_ctx {
     long long thumb_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_thumbnails call: sub-batches decoded, launches of thumb_reduce, bytes of staging planned, 0
     long long crop_stats[4] = {0, 0, 0, 0};    // the last qoimi_decode_crops call: sub-batches decoded, launches of crop_gather, bytes of staging planned, images decoded
     long long resize_stats[4] = {0, 0, 0, 0};  // the last qoimi_decode_resized call: sub-batches decoded, launches of resize_filter, bytes of staging planned, images decoded
+    Arena band_arena;           // qoimi_decode_crops_indexed: the band streams of one call (the sum of their sizes, each rounded up to 16, plus a page)
+    long long seek_stats[4] = {0, 0, 0, 0};    // sub-batches decoded by the last qoimi_build_seek_index; of the last qoimi_make_band_streams / qoimi_decode_crops_indexed: band streams assembled, bytes of the band arena planned, stream bytes copied
     long long pixel_stats[4] = {0, 0, 0, 0};   // the last qoimi_pixel_stats call: sub-batches decoded, launches of stats_reduce, bytes of staging planned, images decoded
     PinBuf cmp_pin;             // pinned staging of those two calls' tables and results (their own: the decode calls inside
                                 // qoimi_verify_images reuse pin at once)
@@ -268,6 +270,26 @@ static __forceinline__ void enc_poll_recheck(qoimi_ctx* c, bool report) {
         c->recheck_failed_unreported = true;
         if (report) (void)fail(QOIMI_E_INTERNAL, "the LDS exchange-order self-test failed on repetition: streams encoded since the last passed check are suspect (qoimi_encode_suspect_calls); this context now uses the order-free probe");
     } else c->enc_calls_last_passed = c->enc_calls_at_check;
+}
+
+// The tables of the inspect passes (qoi_inspect.hip) for n streams: a stream shorter than 22 bytes is not read, a block is up to kInsBlock
+// bytes of ONE stream's body, its pieces are numbered through the call.
+static inline void ins_fill_tables(const size_t* stream_offsets, const int* sizes, size_t n, InsStream* h_tab, InsBlock* h_blk) {
+    const int kMin = kHeaderBytes + kTrailerBytes;
+    uint32_t b = 0, pc = 0;
+    for (size_t i = 0; i < n; ++i) {
+        h_tab[i].off = sizes[i] >= kMin ? (u64)stream_offsets[i] : ~0ull;
+        h_tab[i].size = (uint32_t)sizes[i]; h_tab[i].first_blk = b;
+        if (sizes[i] <= kMin) continue;
+        const uint32_t body = (uint32_t)(sizes[i] - kMin);
+        for (uint32_t at = 0; at < body; at += kInsBlock) {
+            const uint32_t len = body - at < kInsBlock ? body - at : kInsBlock;
+            h_blk[b].off = (u64)stream_offsets[i] + (u64)kHeaderBytes + at;
+            h_blk[b].len = len | (at == 0 ? kInsFirst : 0u);
+            h_blk[b].piece_base = pc;
+            ++b; pc += (len + kInsPiece - 1u) / kInsPiece;
+        }
+    }
 }
 
 // a call's four counters (a NULL context: zeros)

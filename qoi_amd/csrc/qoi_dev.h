@@ -93,6 +93,19 @@ __device__ __forceinline__ void walk_tiles(const Entry* __restrict__ tab, uint32
     }
 }
 
+// A lane's piece of a stream - plen <= 64 bytes at src, any alignment - as 16 dwords; only the aligned dwords that hold one of the plen bytes are
+// read (inspect_maps, inspect_count, seek_locate).
+__device__ __forceinline__ void ins_load_piece(const uint8_t* src, uint32_t plen, uint32_t (&d)[16]) {
+    const uint32_t m = (uint32_t)reinterpret_cast<uintptr_t>(src) & 3u;
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(src - m);
+    const uint32_t span = plen ? plen + m : 0u;          // bytes from a[0] to the piece's last byte
+    uint32_t w[17];
+#pragma unroll
+    for (uint32_t k = 0; k < 17u; ++k) w[k] = 4u * k < span ? a[k] : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; ++k) d[k] = __builtin_amdgcn_alignbyte(w[k + 1u], w[k], m);
+}
+
 // Relaxed agent-scope 8-byte granules ("the data is the flag", guide G16 R2).
 __device__ __forceinline__ void granule_store(u64* p, u64 v) {
     __hip_atomic_store((gu64*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -110,7 +110,7 @@ extern "C" void qoimi_ctx_destroy(qoimi_ctx* c) {
     DeviceGuard guard(c->device);
     (void)hipDeviceSynchronize();       // calls still in flight write to the arenas and to the pinned words freed below
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    c->enc_ws.release(); c->enc_stage.release(); c->dec_ws.release(); c->insp_ws.release(); c->cmp_ws.release(); c->ver_stage.release(); c->dec_scan.release(); c->io_a.release(); c->io_b.release(); c->io_c.release();
+    c->enc_ws.release(); c->enc_stage.release(); c->dec_ws.release(); c->insp_ws.release(); c->cmp_ws.release(); c->ver_stage.release(); c->band_arena.release(); c->dec_scan.release(); c->io_a.release(); c->io_b.release(); c->io_c.release();
     if (c->host_word) (void)hipHostFree(c->host_word);
     c->pin.release(); c->enc_pin.release(); c->cmp_pin.release();
     if (c->enc_pin_ev) (void)hipEventDestroy(c->enc_pin_ev);
@@ -170,10 +170,10 @@ extern "C" int qoimi_set_encode_small_call_order(qoimi_ctx* c, int by_workgroup_
 }
 
 // device memory the context holds: [0] encode workspace (and the staging of qoimi_encode_packed), [1] decode workspace (and the tables of
-// qoimi_inspect_streams, the tables and the staging of qoimi_compare_images / qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops / qoimi_decode_resized), [2] staging of the
+// qoimi_inspect_streams, the tables and the staging of qoimi_compare_images / qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops / qoimi_decode_resized, the band arena of qoimi_decode_crops_indexed), [2] staging of the
 // host-pointer entry points
 extern "C" void qoimi_workspace_bytes(qoimi_ctx* c, size_t out[3]) {
-    out[0] = c ? c->enc_ws.cap + c->enc_stage.cap : 0; out[1] = c ? c->dec_ws.cap + c->insp_ws.cap + c->cmp_ws.cap + c->ver_stage.cap : 0;
+    out[0] = c ? c->enc_ws.cap + c->enc_stage.cap : 0; out[1] = c ? c->dec_ws.cap + c->insp_ws.cap + c->cmp_ws.cap + c->ver_stage.cap + c->band_arena.cap : 0;
     out[2] = c ? c->io_a.cap + c->io_b.cap + c->io_c.cap : 0;
 }
 
@@ -182,6 +182,7 @@ extern "C" void qoimi_thumbnail_stats(qoimi_ctx* c, long long out[4]) { copy_sta
 extern "C" void qoimi_crop_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->crop_stats : nullptr, out); }
 extern "C" void qoimi_resize_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->resize_stats : nullptr, out); }
 extern "C" void qoimi_pixel_stats_counters(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->pixel_stats : nullptr, out); }
+extern "C" void qoimi_seek_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->seek_stats : nullptr, out); }
 
 // ------------------------------------------------------------------------------------
 // synthetic frames

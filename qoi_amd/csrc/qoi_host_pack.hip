@@ -177,22 +177,7 @@ extern "C" int qoimi_inspect_streams(qoimi_ctx* c, const void* d_streams, const 
     InsBlock* h_blk = (InsBlock*)(pin + up256(n * sizeof(InsStream)));
     InsResult* h_res = (InsResult*)(pin + tab_bytes);
     const uint8_t* h_raw = pin + tab_bytes + up256(n * sizeof(InsResult));
-    {
-        uint32_t b = 0, pc = 0;
-        for (size_t i = 0; i < n; ++i) {
-            h_tab[i].off = sizes[i] >= kMin ? (u64)stream_offsets[i] : ~0ull;
-            h_tab[i].size = (uint32_t)sizes[i]; h_tab[i].first_blk = b;
-            if (sizes[i] <= kMin) continue;
-            const uint32_t body = (uint32_t)(sizes[i] - kMin);
-            for (uint32_t at = 0; at < body; at += kInsBlock) {
-                const uint32_t len = body - at < kInsBlock ? body - at : kInsBlock;
-                h_blk[b].off = (u64)stream_offsets[i] + (u64)kHeaderBytes + at;
-                h_blk[b].len = len | (at == 0 ? kInsFirst : 0u);
-                h_blk[b].piece_base = pc;
-                ++b; pc += (len + kInsPiece - 1u) / kInsPiece;
-            }
-        }
-    }
+    ins_fill_tables(stream_offsets, sizes, n, h_tab, h_blk);
     // device workspace: the tables, a map and an entry phase per block, a map per piece (2 bytes per 64 stream bytes), a partial per block
     Carver sizer(nullptr);
     sizer.take<uint8_t>(tab_bytes); sizer.take<uint32_t>(nb); sizer.take<uint8_t>(nb); sizer.take<uint16_t>(npieces); sizer.take<InsPartial>(nb);

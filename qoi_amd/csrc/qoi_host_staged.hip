@@ -1,11 +1,12 @@
 // qoi_host_staged.hip — the calls of the C-ABI shim that decode a pack's images into bounded staging and run one table-driven kernel over
 // each sub-batch: qoimi_verify_images (and qoimi_compare_images, whose kernels it runs), qoimi_decode_thumbnails, qoimi_decode_crops,
-// qoimi_decode_resized, qoimi_pixel_stats.
+// qoimi_decode_resized, qoimi_pixel_stats, and the row seek index (qoimi_build_seek_index, qoimi_make_band_streams, qoimi_decode_crops_indexed).
 #include "qoi_ctx.h"
 #include "qoi_thumb_core.h"
 #include "qoi_crop_core.h"
 #include "qoi_resize_core.h"
 #include "qoi_stats_core.h"
+#include "qoi_seek_core.h"
 
 #include <stddef.h>
 
@@ -539,4 +540,303 @@ extern "C" int qoimi_pixel_stats(qoimi_ctx* c, const void* d_streams, const size
         o.opaque_pixels = a.opaque; o.transparent_pixels = a.transparent; o.grey_pixels = a.grey;
     }
     return QOIMI_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// the row seek index (qoi_seek.hip; qoi_amd/seekindex.py states all of it)
+// ------------------------------------------------------------------------------------
+static_assert(sizeof(qoimi_seek_point) == sizeof(SeekPoint) && offsetof(qoimi_seek_point, skip) == 4 && offsetof(qoimi_seek_point, prev) == 8 &&
+              offsetof(qoimi_seek_point, table) == 16, "qoimi_seek_point is what seek_carry writes");
+static_assert(sizeof(qoimi_band) == 16 && sizeof(qoimi_band_info) == 24 && offsetof(qoimi_band_info, desc) == 8 && offsetof(qoimi_band_info, pad_rows) == 20,
+              "qoimi_band / qoimi_band_info layout");
+
+extern "C" int qoimi_seek_points(const qoi_desc* desc, unsigned interval_rows) {
+    if (!desc_ok(desc)) return -1;
+    return (int)seek_point_count(desc->width, desc->height, interval_rows);
+}
+
+// One qoimi_inspect_streams over the images that have a point, the block scan and a wavefront per point on top of its tables (byte_off,
+// skip); then run_staged over those images at their full height with seek_last + seek_carry per sub-batch (prev, table), which write the
+// points behind the image table; one copy back.
+extern "C" int qoimi_build_seek_index(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                      int n_images, const unsigned* interval_rows, qoimi_seek_point* points_out, size_t staging_bytes, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves points_out as it was)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !interval_rows || !points_out || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    const size_t n = (size_t)n_images;
+    const int kMin = kHeaderBytes + kTrailerBytes;
+    std::vector<uint32_t> rows(n), np(n), point_base(n);
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (sizes[i] < kMin) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + " shorter than 22 bytes (qoi.h:500)");
+        if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:513-521 rules)");
+        const int64_t cnt = seek_point_count(descs[i].width, descs[i].height, interval_rows[i]);
+        if (cnt < 0) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": interval_rows * width below 128");
+        np[i] = (uint32_t)cnt; point_base[i] = (uint32_t)total; rows[i] = cnt != 0 ? descs[i].height : 0u;
+        total += (uint64_t)cnt;
+    }
+    if (total >= 0x7FFFFFFFull / 64u) return fail(QOIMI_E_ARG, "more than 2^25 seek points in one call");
+    const RowsPlan plan = plan_rows(descs, n_images, rows, staging_bytes);
+    const size_t R = plan.refs.size();
+    std::vector<uint32_t> image_of(R);
+    std::vector<uint64_t> tiles_of(R);
+    size_t nb = 0, npieces = 0;
+    for (size_t r = 0; r < R; ++r) {
+        const size_t i = (size_t)plan.refs[r];
+        image_of[r] = (uint32_t)i;
+        const uint64_t ipx = (uint64_t)interval_rows[i] * descs[i].width;
+        tiles_of[r] = (uint64_t)np[i] * ((ipx + kSeekTilePx - 1u) / kSeekTilePx);
+        const size_t body = (size_t)(sizes[i] - kMin);
+        nb += (body + kInsBlock - 1u) / kInsBlock;
+        npieces += (body + kInsPiece - 1u) / kInsPiece;
+    }
+    if (nb >= 0x7FFFFFFFu || npieces >= 0xFFFFFFFFu) return fail(QOIMI_E_ARG, "more than 2^31 blocks of stream bytes in one call");
+    const ItemPlan items = plan_items(image_of, plan.ref_of, plan.firsts, tiles_of);   // (entry r is the r-th image that has a point)
+    if (items.overflow) return fail(QOIMI_E_ARG, "more than 2^31 tiles of pixels in one sub-batch");
+    c->seek_stats[0] = 0;
+    if (total == 0u) return QOIMI_OK;
+    SeekLoc* d_loc = nullptr; uint32_t* d_last = nullptr;
+    {
+        DeviceGuard guard(c->device);
+        hipStream_t st = (hipStream_t)stream;
+        if (const int rc = wait_decode_tail(c, stream)) return rc;
+        if (const int rc = timer_room(c, st)) return rc;
+        // pinned staging: [stream table][block table][jobs] go to the device, [results][header + trailer bytes] are written by inspect_reduce in place
+        const size_t tab_bytes = up256(R * sizeof(InsStream)) + up256(nb * sizeof(InsBlock)), job_bytes = up256((size_t)total * sizeof(SeekJob));
+        if (const int rc = c->pin.reserve(tab_bytes + job_bytes + up256(R * sizeof(InsResult)) + up256(R * 32u))) return rc;
+        uint8_t* pin = (uint8_t*)c->pin.buf;
+        InsStream* h_tab = (InsStream*)pin;
+        InsBlock* h_blk = (InsBlock*)(pin + up256(R * sizeof(InsStream)));
+        SeekJob* h_job = (SeekJob*)(pin + tab_bytes);
+        InsResult* h_res = (InsResult*)(pin + tab_bytes + job_bytes);
+        std::vector<size_t> so(R); std::vector<int> sz(R);
+        for (size_t r = 0; r < R; ++r) { so[r] = stream_offsets[plan.refs[r]]; sz[r] = sizes[plan.refs[r]]; }
+        ins_fill_tables(so.data(), sz.data(), R, h_tab, h_blk);
+        for (size_t r = 0; r < R; ++r) {
+            const size_t i = (size_t)plan.refs[r];
+            const uint32_t ipx = interval_rows[i] * descs[i].width;      // (below 400 000 000: a point lies inside the image)
+            for (uint32_t k = 0; k < np[i]; ++k) { SeekJob& j = h_job[point_base[i] + k]; j.stream = (uint32_t)r; j.point = point_base[i] + k; j.P = (k + 1u) * ipx; j.reserved = 0u; }
+        }
+        Carver sizer(nullptr);
+        sizer.take<uint8_t>(tab_bytes + job_bytes); sizer.take<uint32_t>(nb); sizer.take<uint8_t>(nb); sizer.take<uint16_t>(npieces); sizer.take<InsPartial>(nb);
+        sizer.take<u64>(nb); sizer.take<SeekLoc>((size_t)total); sizer.take<uint32_t>((size_t)total * 64u);
+        { const int rc = c->insp_ws.reserve(sizer.off + 256u); if (rc != QOIMI_OK) return rc; }
+        Carver cv(c->insp_ws.base);
+        uint8_t* d_tab = cv.take<uint8_t>(tab_bytes + job_bytes);
+        uint32_t* d_map = cv.take<uint32_t>(nb);
+        uint8_t* d_entry = cv.take<uint8_t>(nb);
+        uint16_t* d_piece = cv.take<uint16_t>(npieces);
+        InsPartial* d_part = cv.take<InsPartial>(nb);
+        u64* d_blk_px = cv.take<u64>(nb);
+        d_loc = cv.take<SeekLoc>((size_t)total);
+        d_last = cv.take<uint32_t>((size_t)total * 64u);
+        const InsBlock* d_blk = (const InsBlock*)(d_tab + up256(R * sizeof(InsStream)));
+        HIP_TRY(hipMemcpyAsync(d_tab, pin, tab_bytes + job_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_last, 0, (size_t)total * 64u * sizeof(uint32_t), st));
+        launch_inspect((const uint8_t*)d_streams, (const InsStream*)d_tab, (uint32_t)R, d_blk, (uint32_t)nb, d_map, d_entry, d_piece, d_part, h_res,
+                       (uint32_t*)(pin + tab_bytes + job_bytes + up256(R * sizeof(InsResult))), st, &c->timer);
+        launch_seek_locate((const uint8_t*)d_streams, (const InsStream*)d_tab, (uint32_t)R, d_blk, d_part, d_entry, d_piece, d_blk_px,
+                           (const SeekJob*)(d_tab + tab_bytes), (uint32_t)total, d_loc, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));                               // (the decode calls below reuse the pinned staging at once)
+        if (c->timer.on) timer_collect(c);
+    }
+    const size_t res_at = staged_extra_at(R, sizeof(SeekImage));
+    long long stats[4];
+    const int rc = run_staged<SeekImage>(c, stats, (long long)R, "seek_last", d_streams, stream_offsets, sizes, descs, plan, rows, items,
+        [&](SeekImage& t, size_t e) {
+            const size_t r = items.by_ref[e], i = (size_t)plan.refs[r];
+            t.src_off = (u64)plan.at[r]; t.w = descs[i].width; t.ipx = interval_rows[i] * descs[i].width; t.np = np[i];
+            t.tpi = (t.ipx + kSeekTilePx - 1u) / kSeekTilePx; t.first_tile = items.first_tile[e]; t.point_base = point_base[i];
+            t.reserved[0] = 0u; t.reserved[1] = 0u;
+        },
+        [&](const SeekImage* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            launch_seek_tables((const uint8_t*)c->ver_stage.base, tab, m, tiles, d_last, d_loc, (SeekPoint*)((uint8_t*)c->cmp_ws.base + res_at), grid, st);
+        }, stream, (size_t)total * sizeof(SeekPoint),
+        [&](uint8_t* h_points, hipStream_t) { memset(h_points, 0, (size_t)total * sizeof(SeekPoint)); return (int)QOIMI_OK; });
+    c->seek_stats[0] = stats[0];
+    if (rc != QOIMI_OK) return rc;
+    memcpy(points_out, (const uint8_t*)c->cmp_pin.buf + res_at, (size_t)total * sizeof(SeekPoint));
+    return QOIMI_OK;
+}
+
+// A band as qoimi_band_plan sees it: what it will be, what stands in front of its tail, the point it starts at (nullptr: row 0) and its
+// tail, the bytes [tail_lo, tail_lo + tail_len) of the stream.
+struct BandPlan { qoimi_band_info info; SeekPrefix f; const qoimi_seek_point* e; uint32_t tail_lo, tail_len; };
+
+// nullptr if the band is fine, else what is wrong with it
+static const char* band_wrong(const qoi_desc* d, int size, unsigned K, const qoimi_seek_point* pts, const qoimi_band* b, BandPlan& out) {
+    if (!desc_ok(d)) return "descriptor rejected (qoi.h:513-521 rules)";
+    if (size < kHeaderBytes + kTrailerBytes) return "stream shorter than 22 bytes (qoi.h:500)";
+    const int64_t np = seek_point_count(d->width, d->height, K);
+    if (np < 0) return "interval_rows * width below 128";
+    if (b->rows == 0u) return "an empty band";
+    if ((uint64_t)b->first_row + b->rows > d->height) return "the band leaves its image";
+    if (b->first_row % K != 0u) return "first_row is neither 0 nor a seek row";
+    const uint64_t k2 = ((uint64_t)b->first_row + b->rows + K - 1u) / K - 1u;
+    if ((b->first_row != 0u || k2 < (uint64_t)np) && !pts) return "no points";
+    const qoimi_seek_point* e = b->first_row != 0u ? pts + (b->first_row / K - 1u) : nullptr;
+    const qoimi_seek_point* e2 = k2 < (uint64_t)np ? pts + k2 : nullptr;
+    for (const qoimi_seek_point* p : {e, e2})
+        if (p && (p->byte_off < (unsigned)kHeaderBytes || p->byte_off > (unsigned)(size - kTrailerBytes) || p->skip > kSeekMaxSkip))
+            return "a seek point with byte_off outside [14, size - 8] or skip above 61";
+    const uint32_t lo = e ? e->byte_off : (uint32_t)kHeaderBytes;
+    const uint32_t hi = e2 && e2->byte_off + 13u < (uint32_t)size ? e2->byte_off + 13u : (uint32_t)size;
+    if (hi < lo) return "the seek points do not ascend";
+    out.f = seek_prefix_plan((const SeekPoint*)e, d->width);
+    // (a point of a stream holds prev in prev's own slot, so it has at most 64 loads; 64 table words that all differ from prev are no point)
+    if (out.f.n > kSeekMaxLoads) return "a seek point with more than 64 loads (its table does not hold prev)";
+    const uint64_t bytes = (uint64_t)seek_prefix_len(out.f) + (hi - lo);
+    if (bytes >= 0x7FFFFFFFull) return "a band stream of 2^31 - 1 bytes or more";
+    out.e = e; out.tail_lo = lo; out.tail_len = hi - lo;
+    out.info.size = bytes; out.info.desc = *d; out.info.desc.height = out.f.pad_rows + b->rows; out.info.pad_rows = out.f.pad_rows;
+    return nullptr;
+}
+
+extern "C" int qoimi_band_plan(const qoi_desc* desc, int size, unsigned interval_rows, const qoimi_seek_point* points, const qoimi_band* band,
+                               qoimi_band_info* out) {
+    if (!desc || !band || !out) return fail(QOIMI_E_ARG, "NULL argument");
+    BandPlan p;
+    if (const char* what = band_wrong(desc, size, interval_rows, points, band, p)) return fail(QOIMI_E_ARG, std::string("band: ") + what);
+    *out = p.info;
+    return QOIMI_OK;
+}
+
+// Band stream j of image image_of[j] at d_out + out_offsets[j]: the heads (header and loads) are written here and travel with the table, one
+// launch of band_assemble writes everything; the stream is waited for (the pinned staging belongs to the next call at once).  The ranges have
+// been checked.  Leaves the counters of qoimi_seek_stats [1] and [3].
+static int assemble_bands(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const std::vector<BandPlan>& plans,
+                          const std::vector<uint32_t>& image_of, void* d_out, const size_t* out_offsets, const std::vector<uint32_t>& first_tile,
+                          uint32_t tiles, void* stream) {
+    const size_t n = plans.size();
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (const int rc = wait_decode_tail(c, stream)) return rc;
+    const size_t tab_bytes = up256(n * sizeof(BandEntry)), bytes = tab_bytes + n * kSeekHeadSlot;
+    { const int rc = c->cmp_pin.reserve(bytes); if (rc != QOIMI_OK) return rc; }
+    { const int rc = c->cmp_ws.reserve(bytes); if (rc != QOIMI_OK) return rc; }
+    BandEntry* h_tab = (BandEntry*)c->cmp_pin.buf;
+    uint8_t* h_heads = (uint8_t*)c->cmp_pin.buf + tab_bytes;
+    long long copied = 0;
+    for (size_t j = 0; j < n; ++j) {
+        const BandPlan& p = plans[j];
+        BandEntry& t = h_tab[j];
+        t.src_off = (u64)stream_offsets[image_of[j]] + p.tail_lo; t.dst_off = (u64)out_offsets[j];
+        t.B = (uint32_t)p.info.size; t.head_len = p.f.head_len; t.run_full = p.f.run_full; t.run_last = p.f.run_last;
+        t.first_tile = first_tile[j]; t.head_at = (uint32_t)(j * kSeekHeadSlot); t.reserved[0] = 0u; t.reserved[1] = 0u;
+        memset(h_heads + j * kSeekHeadSlot, 0, kSeekHeadSlot);
+        seek_write_head((const SeekPoint*)p.e, p.info.desc.width, p.info.desc.height, p.info.desc.channels, p.info.desc.colorspace, h_heads + j * kSeekHeadSlot);
+        copied += (long long)p.tail_len;
+    }
+    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, bytes, hipMemcpyHostToDevice, st));
+    const uint32_t most = (uint32_t)c->n_cus * 8u;
+    launch_band_assemble((const uint8_t*)d_streams, (const BandEntry*)c->cmp_ws.base, (uint32_t)n, tiles, (const uint8_t*)c->cmp_ws.base + tab_bytes,
+                         (uint8_t*)d_out, tiles < most ? tiles : most, st);
+    { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string("band_assemble: ") + hipGetErrorString(e)); } }
+    HIP_TRY(hipStreamSynchronize(st));
+    c->seek_stats[1] = (long long)n; c->seek_stats[3] = copied;
+    return QOIMI_OK;
+}
+
+// The tiles of band streams of plans[j].info.size bytes at base + offsets[j]; false: 2^31 - 1 of them or more
+static bool band_tiles(const std::vector<BandPlan>& plans, uintptr_t base, const size_t* offsets, std::vector<uint32_t>& first_tile, uint32_t& tiles) {
+    uint64_t t = 0;
+    first_tile.resize(plans.size());
+    for (size_t j = 0; j < plans.size(); ++j) {
+        if (t >= 0x7FFFFFFFull) return false;
+        first_tile[j] = (uint32_t)t;
+        t += crop_tiles((uint64_t)base + offsets[j], plans[j].info.size);
+    }
+    tiles = (uint32_t)t;
+    return t < 0x7FFFFFFFull;
+}
+
+extern "C" int qoimi_make_band_streams(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                       int n_images, const unsigned* interval_rows, const qoimi_seek_point* points, const size_t* point_firsts,
+                                       const qoimi_band* bands, int n_bands, void* d_out, const size_t* out_offsets, qoimi_band_info* infos_out, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !interval_rows || !points || !point_firsts || !bands || !d_out || !out_offsets ||
+        n_images <= 0 || n_bands <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    const size_t n = (size_t)n_bands;
+    if (n > 0xFFFFFFFFu / kSeekHeadSlot) return fail(QOIMI_E_ARG, "more than 12 782 640 bands in one call");     // (a head's place in the table is 32 bits)
+    std::vector<BandPlan> plans(n);
+    std::vector<uint32_t> image_of(n);
+    std::vector<size_t> out_bytes(n);
+    const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_out;
+    // [start, end) of every output (kind 1) and of every stream a band names (kind 0), as addresses: no output may meet anything
+    struct Range { uintptr_t lo, hi; int out; };
+    std::vector<Range> ranges;
+    for (size_t j = 0; j < n; ++j) {
+        const qoimi_band& b = bands[j];
+        if (b.image >= (unsigned)n_images) return fail(QOIMI_E_ARG, "band " + std::to_string(j) + ": no image " + std::to_string(b.image));
+        const size_t i = b.image;
+        if (const char* what = band_wrong(&descs[i], sizes[i], interval_rows[i], points + point_firsts[i], &b, plans[j]))
+            return fail(QOIMI_E_ARG, "band " + std::to_string(j) + ": " + what);
+        image_of[j] = b.image; out_bytes[j] = (size_t)plans[j].info.size;
+        if (out_offsets[j] > room || out_bytes[j] > room - out_offsets[j]) return fail(QOIMI_E_ARG, "band " + std::to_string(j) + ": the output ends behind the address space");
+        ranges.push_back({(uintptr_t)d_out + out_offsets[j], (uintptr_t)d_out + out_offsets[j] + out_bytes[j], 1});
+        ranges.push_back({(uintptr_t)d_streams + stream_offsets[i], (uintptr_t)d_streams + stream_offsets[i] + (size_t)sizes[i], 0});
+    }
+    std::sort(ranges.begin(), ranges.end(), [](const Range& a, const Range& b) { return a.lo < b.lo; });
+    uintptr_t end_any = 0, end_out = 0;                        // the furthest end so far of any range, of an output
+    for (const Range& r : ranges) {
+        if (r.out ? r.lo < end_any : r.lo < end_out) return fail(QOIMI_E_ARG, "an output range overlaps another or a stream of the call");
+        if (r.hi > end_any) end_any = r.hi;
+        if (r.out && r.hi > end_out) end_out = r.hi;
+    }
+    std::vector<uint32_t> first_tile; uint32_t tiles = 0;
+    if (!band_tiles(plans, (uintptr_t)d_out, out_offsets, first_tile, tiles)) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output words in one call");
+    if (const int rc = assemble_bands(c, d_streams, stream_offsets, plans, image_of, d_out, out_offsets, first_tile, tiles, stream)) return rc;
+    c->seek_stats[2] = 0;
+    if (infos_out) for (size_t j = 0; j < n; ++j) infos_out[j] = plans[j].info;
+    return QOIMI_OK;
+}
+
+// The bands of qoi_amd/seekindex.py: bands_for_crops into the context's band arena, then qoimi_decode_crops as it is over them.
+extern "C" int qoimi_decode_crops_indexed(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                          int n_images, int channels, const qoimi_crop* crops, int n_crops, void* d_out, const size_t* out_offsets,
+                                          size_t staging_bytes, void* stream, const unsigned* interval_rows, const qoimi_seek_point* points,
+                                          const size_t* point_firsts) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !crops || !d_out || !out_offsets || !interval_rows || !points || !point_firsts ||
+        n_images <= 0 || n_crops <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    const size_t n = (size_t)n_crops;
+    CheckedItems ok;
+    if (const int rc = check_items("crop", sizes, descs, n_images, channels, crops, n, d_out, out_offsets, crop_rect_wrong, crop_bytes, ok)) return rc;
+    std::vector<uint32_t> top((size_t)n_images, ~0u);
+    for (size_t j = 0; j < n; ++j) if (crops[j].y < top[crops[j].image]) top[crops[j].image] = crops[j].y;
+    std::vector<BandPlan> plans;
+    std::vector<uint32_t> image_of, first_row;
+    std::vector<int> number((size_t)n_images, -1);
+    std::vector<size_t> at;                                    // where band stream r lies in the arena
+    size_t arena = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (ok.rows[(size_t)i] == 0u) continue;                // (an image no crop names is never looked at)
+        const unsigned K = interval_rows[i];
+        if (seek_point_count(descs[i].width, descs[i].height, K) < 0) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": interval_rows * width below 128");
+        qoimi_band b;
+        b.image = (unsigned)i; b.first_row = top[(size_t)i] / K * K; b.rows = ok.rows[(size_t)i] - b.first_row; b.reserved = 0u;
+        BandPlan p;
+        if (const char* what = band_wrong(&descs[i], sizes[i], K, points + point_firsts[i], &b, p)) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": " + what);
+        number[(size_t)i] = (int)plans.size();
+        plans.push_back(p); image_of.push_back((uint32_t)i); first_row.push_back(b.first_row); at.push_back(arena);
+        arena += ((size_t)p.info.size + 15u) & ~(size_t)15u;
+    }
+    std::vector<uint32_t> first_tile; uint32_t tiles = 0;
+    if (plans.size() > 0xFFFFFFFFu / kSeekHeadSlot) return fail(QOIMI_E_ARG, "more than 12 782 640 referenced images in one call");
+    if (!band_tiles(plans, (uintptr_t)0, at.data(), first_tile, tiles)) return fail(QOIMI_E_ARG, "more than 2^31 tiles of band stream words in one call");
+    {
+        DeviceGuard guard(c->device);
+        if (const int rc = reserve_exact(c->band_arena, arena)) return rc;
+    }
+    if (const int rc = assemble_bands(c, d_streams, stream_offsets, plans, image_of, c->band_arena.base, at.data(), first_tile, tiles, stream)) return rc;
+    c->seek_stats[2] = (long long)arena;
+    const size_t R = plans.size();
+    std::vector<int> sz(R); std::vector<qoi_desc> ds(R); std::vector<qoimi_crop> cs(crops, crops + n);
+    for (size_t r = 0; r < R; ++r) { sz[r] = (int)plans[r].info.size; ds[r] = plans[r].info.desc; }
+    for (size_t j = 0; j < n; ++j) {
+        const size_t r = (size_t)number[crops[j].image];
+        cs[j].image = (unsigned)r; cs[j].y = crops[j].y - first_row[r] + plans[r].info.pad_rows;
+    }
+    return qoimi_decode_crops(c, c->band_arena.base, at.data(), sz.data(), ds.data(), (int)R, channels, cs.data(), n_crops, d_out, out_offsets, staging_bytes, stream);
 }

@@ -40,17 +40,7 @@ __device__ __forceinline__ uint32_t ins_compose(uint32_t first, uint32_t then) {
     return r;
 }
 
-// A lane's piece - plen <= 64 bytes at src, any alignment - as 16 dwords; only the aligned dwords that hold one of the plen bytes are read.
-__device__ __forceinline__ void ins_load_piece(const uint8_t* src, uint32_t plen, uint32_t (&d)[16]) {
-    const uint32_t m = (uint32_t)reinterpret_cast<uintptr_t>(src) & 3u;
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(src - m);
-    const uint32_t span = plen ? plen + m : 0u;          // bytes from a[0] to the piece's last byte
-    uint32_t w[17];
-#pragma unroll
-    for (uint32_t k = 0; k < 17u; ++k) w[k] = 4u * k < span ? a[k] : 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < 16u; ++k) d[k] = __builtin_amdgcn_alignbyte(w[k + 1u], w[k], m);
-}
+// (ins_load_piece - a lane's piece as 16 dwords: qoi_dev.h)
 __device__ __forceinline__ uint32_t ins_byte(const uint32_t (&d)[16], uint32_t pos) { return (d[pos >> 2] >> (8u * (pos & 3u))) & 0xFFu; }
 
 // The map of a piece of plen bytes.  exit(pos), the bytes left over by the walk that has a chunk start at pos, is pos - plen at and behind

@@ -1,0 +1,139 @@
+"""qoimi_make_band_streams on the GPU (-m gpu): every band stream equals qoi_amd/seekindex.py: band_stream byte for byte, at odd offsets
+between guard bytes that survive - bands from row 0, bands that end in the last partial interval, a band whose tail is only the stream's last
+8 bytes - and, fed to qoimi_decode_images as it is at 3 and at 4 channels, decodes from row pad_rows on to the rows of the full decode."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from seek_cases import DevicePack, cases
+from test_gpu_encode_packed import filled
+
+pytestmark = pytest.mark.gpu
+E_ARG = -1
+GUARD = 0xA5
+
+
+@pytest.fixture(scope="module")
+def api():
+    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
+    from qoi_amd import api as _api
+    assert torch.cuda.is_available()
+    return _api
+
+
+@pytest.fixture(scope="module")
+def ctx(api):
+    c = api.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def pack(api, ref, port):
+    keep = ("noise96", "skip1", "skip61", "all_ff", "cut", "old_colour", "w1", "w63", "w65", "no_point")
+    return DevicePack(api, [c for c in cases(ref or port) if c.name in keep])
+
+
+def bands_of(pack):
+    """(image, first_row, rows): from row 0, from every kind of point, to the next seek row, into the last partial interval, one row"""
+    out = []
+    for i, c in enumerate(pack.cases):
+        n = len(c.points)
+        out.append((i, 0, c.h))
+        out.append((i, 0, min(c.K, c.h)))
+        for k in sorted({0, n // 2, n - 1} & set(range(n))):
+            first = (k + 1) * c.K
+            out += [(i, first, c.h - first), (i, first, min(c.K, c.h - first)), (i, first, 1)]
+    return out
+
+
+def make(ctx, pack, bands, shift):
+    want = [pack.cases[i].band(first, rows) for i, first, rows in bands]
+    offsets, pos = [], 64 + shift
+    for j, (s, _) in enumerate(want):
+        offsets.append(pos)
+        pos += len(s) + (0, 1, 5, 16)[j % 4]                       # back to back, a byte apart, ...: neighbours share aligned words
+    buf = filled(pos + 64, GUARD)
+    infos = ctx.make_band_streams(pack.dev.data_ptr(), pack.offsets, pack.sizes, pack.descs, pack.intervals, pack.points, pack.point_firsts, bands,
+                                  buf.data_ptr(), offsets)
+    got = buf.cpu().numpy()
+    mask = np.ones(got.size, dtype=bool)
+    for j, ((s, pad), o, info, (i, first, rows)) in enumerate(zip(want, offsets, infos, bands)):
+        c = pack.cases[i]
+        assert (info.size, info.pad_rows, info.desc.width, info.desc.height, info.desc.channels, info.desc.colorspace) == (len(s), pad, c.w, pad + rows, c.ch, 0)
+        assert got[o:o + len(s)].tobytes() == s, (c.name, first, rows, shift, int(np.argmax(got[o:o + len(s)] != np.frombuffer(s, dtype=np.uint8))))
+        mask[o:o + len(s)] = False
+    assert np.all(got[mask] == GUARD), ("a byte outside the band streams was written", int(np.argmax(mask & (got != GUARD))))
+    assert ctx.seek_stats()[1] == len(bands) and ctx.seek_stats()[2] == 0
+    return buf, offsets, infos, want
+
+
+@pytest.mark.parametrize("shift", [0, 1, 7, 15])
+def test_band_streams_equal_the_model(ctx, pack, shift):
+    bands = bands_of(pack)
+    cut = [c.name for c in pack.cases].index("cut")
+    c = pack.cases[cut]
+    last = len(c.points) * c.K
+    assert (cut, last, c.h - last) in bands and int(c.points[-1]["byte_off"]) == len(c.stream) - 8       # a tail of the last 8 bytes alone
+    assert c.band(last, c.h - last)[0].endswith(c.stream[-8:]) and (0, 0, pack.cases[0].h) in bands
+    make(ctx, pack, bands, shift)
+    assert np.array_equal(pack.dev.cpu().numpy(), pack.host)
+
+
+@pytest.mark.parametrize("och", [3, 4])
+def test_band_streams_decode_to_the_bands_rows(ctx, pack, och):
+    bands = bands_of(pack)
+    buf, offsets, infos, want = make(ctx, pack, bands, 3)
+    descs = [info.desc for info in infos]
+    nbytes = [d.width * d.height * och for d in descs]
+    pix_off = [64 + int(x) for x in np.cumsum([0] + nbytes[:-1])]
+    out = filled(pix_off[-1] + nbytes[-1] + 64, GUARD)
+    ctx.decode_images(buf.data_ptr(), offsets, [info.size for info in infos], descs, och, out.data_ptr(), pix_off)
+    got = out.cpu().numpy()
+    for (i, first, rows), info, o, nb in zip(bands, infos, pix_off, nbytes):
+        c = pack.cases[i]
+        px = got[o:o + nb].reshape(info.desc.height, c.w, och)[info.pad_rows:]
+        assert np.array_equal(px, c.full[och][first:first + rows]), (c.name, first, rows, och)
+
+
+def test_rejections_on_a_live_context(api, ctx, pack):
+    lib = api.load_library()
+    n = len(pack.cases)
+    buf = filled(1 << 17, GUARD)
+    pts, _ = api._point_array(pack.points)
+    noise = [c.name for c in pack.cases].index("noise96")
+    K = pack.cases[noise].K
+
+    def call(bands, offsets, points=pts, dest=None, sizes=pack.sizes):
+        arr = (api.QoimiBand * len(bands))(*[api.QoimiBand(i, f, r, 0) for i, f, r in bands])
+        return lib.qoimi_make_band_streams(ctx._h, pack.dev.data_ptr(), (ctypes.c_size_t * n)(*pack.offsets), (ctypes.c_int * n)(*sizes), (api.QoiDesc * n)(*pack.descs), n,
+                                           (ctypes.c_uint * n)(*pack.intervals), points, (ctypes.c_size_t * n)(*pack.point_firsts), arr, len(bands),
+                                           buf.data_ptr() if dest is None else dest, (ctypes.c_size_t * len(bands))(*offsets), None, None)
+
+    one = len(pack.cases[noise].band(K, K)[0])
+    assert call([(noise, K, K)], [64]) == 0
+    assert call([(noise, K + 1, K)], [64]) == E_ARG and "seek row" in api.last_error()
+    assert call([(noise, K, 0)], [64]) == E_ARG and call([(noise, 94, 3)], [64]) == E_ARG and call([(n, 0, 1)], [64]) == E_ARG
+    assert call([(noise, K, K), (noise, K, K)], [64, 64 + one - 1]) == E_ARG and "overlap" in api.last_error()
+    assert call([(noise, K, K), (noise, K, K)], [64, 64 + one]) == 0
+    assert call([(noise, K, K)], [pack.offsets[noise] + 100], dest=pack.dev.data_ptr()) == E_ARG and "overlap" in api.last_error()
+    bad = pack.points.copy()
+    bad[pack.point_firsts[noise]]["byte_off"] = pack.sizes[noise] - 7
+    assert call([(noise, K, K)], [64], points=api._point_array(bad)[0]) == E_ARG and "byte_off" in api.last_error()
+    bad = pack.points.copy()
+    bad[pack.point_firsts[noise]]["skip"] = 62
+    assert call([(noise, K, K)], [64], points=api._point_array(bad)[0]) == E_ARG
+    bad = pack.points.copy()
+    bad[pack.point_firsts[noise] + 1]["byte_off"] = 14                       # e2 in front of e
+    assert call([(noise, K, K)], [64], points=api._point_array(bad)[0]) == E_ARG
+    bad = pack.points.copy()                                                 # 64 non-zero table words that all differ from prev: 65 loads
+    bad[pack.point_firsts[noise]]["table"] = np.arange(64, dtype=np.uint32) + 0x01000000
+    bad[pack.point_firsts[noise]]["prev"] = 0x7F7F7F7F
+    assert call([(noise, K, K)], [64], points=api._point_array(bad)[0]) == E_ARG and "64 loads" in api.last_error()
+    bad[pack.point_firsts[noise]]["table"][5] = 0x7F7F7F7F                    # 64 loads: accepted, a stream every decoder takes (wrong pixels)
+    assert call([(noise, K, K), (noise, 0, K)], [64, 8192], points=api._point_array(bad)[0]) == 0
+    before = buf.cpu().numpy().copy()
+    assert before[64 + 14:64 + 14 + 5 * 64:5].tolist() == [0xFF] * 64 and np.all(before[8192 + 4096 + 8192:] == GUARD)
+    assert call([(noise, K, K)], [64], sizes=[21 if i == noise else s for i, s in enumerate(pack.sizes)]) == E_ARG
+    assert np.array_equal(buf.cpu().numpy(), before) and np.array_equal(pack.dev.cpu().numpy(), pack.host)

@@ -1,0 +1,145 @@
+"""qoimi_decode_crops_indexed on the GPU (-m gpu): byte for byte qoimi_decode_crops for the same crops - flips, several crops per image,
+unreferenced images with garbage descriptors, channels 0, 3 and 4 - with an index built by qoimi_build_seek_index; the staging the inner call
+plans is that of the band, not of the rows above it; an index built for another stream is rejected or decodes without touching memory outside
+the arguments."""
+import numpy as np
+import pytest
+
+from qoi_amd import crops
+from qoi_amd import seekindex as si
+from test_gpu_encode_packed import Batch, filled
+from test_gpu_thumbnails import Pack
+
+pytestmark = pytest.mark.gpu
+GUARD = 0xA5
+SHAPES = [(130, 70, 4), (64, 48, 3), (37, 23, 3), (257, 40, 4), (96, 96, 4), (1, 300, 4)]
+KINDS = ["sprite_alpha", "photo", "noise", "uiflat", "noise", "noise"]
+INTERVALS = [8, 2, 4, 16, 2, 128]
+
+
+@pytest.fixture(scope="module")
+def api():
+    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
+    from qoi_amd import api as _api
+    assert torch.cuda.is_available()
+    return _api
+
+
+@pytest.fixture(scope="module")
+def ctx(api):
+    c = api.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def oracle(ref, port):
+    return ref or port
+
+
+@pytest.fixture(scope="module")
+def pack(api, ctx, oracle):
+    p = Pack(ctx, oracle, Batch(api, oracle, SHAPES, KINDS))
+    p.index = ctx.build_seek_index(p.packed.data_ptr(), p.so, p.sizes, p.descs, INTERVALS)
+    for i, (w, h, ch) in enumerate(SHAPES):                                  # the index is the model's
+        first, n = p.index[1][i], si.n_points(w, h, INTERVALS[i])
+        full4, _ = oracle.decode(p.host[p.so[i]:p.so[i] + p.sizes[i]].tobytes(), 4)
+        assert np.array_equal(p.index[0][first:first + n], si.points(p.host[p.so[i]:p.so[i] + p.sizes[i]].tobytes(), w, h, INTERVALS[i], full4)), i
+    return p
+
+
+def both(ctx, p, channels, cs, staging=0, descs=None, sizes=None, intervals=INTERVALS, index=None, shift=0):
+    och = channels or p.shapes[cs[0][0]][2]
+    nbytes = [c[3] * c[4] * och for c in cs]
+    offsets = [64 + shift + int(x) + 3 * j for j, x in enumerate(np.cumsum([0] + nbytes[:-1]))]
+    total = offsets[-1] + nbytes[-1] + 64
+    points, firsts = index or p.index
+    plain, indexed = filled(total, GUARD), filled(total, GUARD)
+    ctx.decode_crops(p.packed.data_ptr(), p.so, p.sizes, p.descs, channels, cs, plain.data_ptr(), offsets, staging)
+    plain_stats = ctx.crop_stats()
+    ctx.decode_crops_indexed(p.packed.data_ptr(), p.so, sizes or p.sizes, descs or p.descs, channels, cs, indexed.data_ptr(), offsets, intervals, points, firsts,
+                             staging_bytes=staging)
+    return plain.cpu().numpy(), indexed.cpu().numpy(), plain_stats, ctx.crop_stats(), offsets, nbytes
+
+
+def some_crops(p, images):
+    out = []
+    for i in images:
+        w, h, _ = p.shapes[i]
+        K = INTERVALS[i]
+        out += [(i, 0, h - 1, w, 1, 1), (i, w // 2, h // 2, w - w // 2, h - h // 2, 2), (i, 0, min(h - 1, K + 1), 1, 1, 3), (i, w - 1, h - 2, 1, 2, 0)]
+    return out
+
+
+@pytest.mark.parametrize("channels", [4, 3])
+def test_identical_to_decode_crops(ctx, pack, channels):
+    cs = some_crops(pack, range(len(SHAPES)))
+    for shift in (0, 5):
+        plain, indexed, _, _, offsets, nbytes = both(ctx, pack, channels, cs, shift=shift)
+        assert np.array_equal(plain, indexed), int(np.argmax(plain != indexed))
+        for c, o, nb in zip(cs, offsets, nbytes):
+            assert np.array_equal(plain[o:o + nb], crops.crop(pack.decoded(c[0], channels), c[1:5], c[5]).reshape(-1))
+    assert ctx.seek_stats()[1] == len(SHAPES)
+
+
+@pytest.mark.parametrize("och", [4, 3])
+def test_the_images_own_channels_and_unreferenced_garbage(api, ctx, pack, och):
+    images = [i for i, s in enumerate(SHAPES) if s[2] == och]
+    cs = some_crops(pack, images) + [(images[0], 0, 0, 1, 1, 0)]             # ... and a crop in the first interval: that band starts at row 0
+    descs = [d if i in images else api.QoiDesc(0, 7, 9, 3) for i, d in enumerate(pack.descs)]
+    sizes = [s if i in images else 0 for i, s in enumerate(pack.sizes)]
+    intervals = [k if i in images else 0 for i, k in enumerate(INTERVALS)]
+    plain, indexed, _, stats, _, _ = both(ctx, pack, 0, cs, descs=descs, sizes=sizes, intervals=intervals)
+    assert np.array_equal(plain, indexed) and stats[3] == len(images) == ctx.seek_stats()[1]
+
+
+def test_sub_batches_of_the_inner_call(ctx, pack):
+    cs = some_crops(pack, range(len(SHAPES)))
+    plain, indexed, plain_stats, stats, _, _ = both(ctx, pack, 4, cs, staging=1)
+    assert np.array_equal(plain, indexed) and stats[0] == stats[1] == len(SHAPES) == plain_stats[0] and stats[2] < plain_stats[2]
+
+
+def test_a_band_at_the_bottom_stages_the_band(api, ctx, oracle):
+    """256 x 2048, K = 128, one crop in the rows 1920 to 2047: the inner call stages pad_rows + 128 rows, not 2048"""
+    w, h, K = 256, 2048, 128
+    p = Pack(ctx, oracle, Batch(api, oracle, [(w, h, 4)], ["photo"]))
+    points, firsts = ctx.build_seek_index(p.packed.data_ptr(), p.so, p.sizes, p.descs, [K])
+    assert len(points) == 15
+    cs = [(0, 3, 1920, 250, 128, 1)]
+    bands, rebased = si.bands_for_crops(p.descs, cs, [K], [points])
+    assert bands == [(0, 1920, 128)]
+    pad = si.pad_rows_of(points[14], w)
+    band_descs = [(w, pad + 128)]
+    want_staging = crops.plan(band_descs, rebased, 0)[3]
+    assert want_staging == (pad + 128) * w * 4 and 1 <= pad <= K
+    out = filled(64 + 250 * 128 * 4 + 64, GUARD)
+    ctx.decode_crops_indexed(p.packed.data_ptr(), p.so, p.sizes, p.descs, 4, cs, out.data_ptr(), [64], [K], points, firsts)
+    assert ctx.crop_stats() == (1, 1, want_staging, 1)
+    assert ctx.seek_stats()[1:3] == (1, -(-si.band_info(p.sizes[0], w, h, 4, 0, K, points, 1920, 128)["size"] // 16) * 16)
+    got = out.cpu().numpy()
+    assert np.array_equal(got[64:-64], crops.crop(p.decoded(0, 4), (3, 1920, 250, 128), 1).reshape(-1)) and np.all(got[:64] == GUARD) and np.all(got[-64:] == GUARD)
+    ctx.decode_crops(p.packed.data_ptr(), p.so, p.sizes, p.descs, 4, cs, out.data_ptr(), [64])
+    assert ctx.crop_stats()[2] == h * w * 4
+
+
+def test_an_index_of_another_stream(api, ctx, pack):
+    """the points of image 4 (96 x 96 noise) handed in for image 0 and the other way round: rejected, or decoded to some pixels - the streams
+    stay as they are, nothing beside the outputs is written, and the context goes on working"""
+    points, firsts = pack.index
+    swapped = list(firsts)
+    swapped[0], swapped[4] = firsts[4], firsts[0]
+    cs = [(0, 0, 60, 130, 10, 0), (4, 0, 90, 96, 6, 0)]
+    nbytes = [c[3] * c[4] * 4 for c in cs]
+    offsets = [64, 64 + nbytes[0] + 1]
+    out = filled(offsets[1] + nbytes[1] + 64, GUARD)
+    try:
+        ctx.decode_crops_indexed(pack.packed.data_ptr(), pack.so, pack.sizes, pack.descs, 4, cs, out.data_ptr(), offsets, INTERVALS, points, swapped)
+    except api.QoiError:
+        assert bool((out == GUARD).all())
+    got = out.cpu().numpy()
+    mask = np.ones(got.size, dtype=bool)
+    for o, nb in zip(offsets, nbytes):
+        mask[o:o + nb] = False
+    assert np.all(got[mask] == GUARD) and np.array_equal(pack.packed.cpu().numpy(), pack.host)
+    plain, indexed, _, _, _, _ = both(ctx, pack, 4, cs)
+    assert np.array_equal(plain, indexed)
