@@ -596,8 +596,10 @@ void qoimi_pixel_stats_counters(qoimi_ctx *ctx, long long out[4]);
  * ascending every table[s] that is neither 0 nor prev as FF r g b a, then prev the same way (n <= 64 chunks); with pad_rows = max(1, ceil((n + skip)
  * / w)) and R = pad_rows * w - skip - n: R / 62 bytes 0xFD and, if R % 62 != 0, one byte 0xC0 | (R % 62 - 1); the original bytes [byte_off,
  * min(byte_off(e2) + 13, size)), up to size without e2.  first_row == 0: no loads, pad_rows = 0, the original bytes from 14 on.  pad_rows <= K always.
- * Costs, stated plainly: building an index is one qoimi_inspect_streams plus one full decode of every image that has a point; an indexed call
- * copies each band's stream bytes once.  Build it once per pack and keep 272 bytes per point beside the pack's offsets. */
+ * Costs, stated plainly: building an index from the streams alone (qoimi_build_seek_index) is one qoimi_inspect_streams plus one full decode of
+ * every image that has a point; whoever still holds the pixels the pack was encoded from builds it without a decode
+ * (qoimi_seek_index_from_pixels); an indexed call copies each band's stream bytes once.  Build it once per pack and keep 272 bytes per point
+ * beside the pack's offsets. */
 typedef struct { unsigned byte_off, skip, prev, reserved; unsigned table[64]; } qoimi_seek_point;   /* 272 bytes; reserved: 0 */
 typedef struct { unsigned image, first_row, rows, reserved; } qoimi_band;                            /* 16 bytes; reserved is not looked at */
 typedef struct { unsigned long long size; qoi_desc desc; unsigned pad_rows; } qoimi_band_info;       /* 24 bytes, offsets 0/8/20 */
@@ -626,6 +628,33 @@ int qoimi_seek_points(const qoi_desc *desc, unsigned interval_rows);
 int qoimi_build_seek_index(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
                            const qoi_desc *descs /* host */, int n_images, const unsigned *interval_rows /* host, n_images */,
                            qoimi_seek_point *points_out /* host */, size_t staging_bytes, void *stream);
+
+/* The seek points of every image of a pack whose PIXELS the caller holds on the device - it has just encoded the pack from them
+ * (qoimi_encode_images_packed: packed_off_out / stream_len_out are this call's stream_offsets / sizes) - without decoding anything.
+ *   d_pixels, pixel_offsets  as for qoimi_encode_images: image i is width * height * descs[i].channels bytes, tightly packed, at d_pixels +
+ *                  pixel_offsets[i] - ANY byte offset; 3- and 4-channel images mix in one call.  Read only
+ *   stream_offsets, sizes, descs, interval_rows, points_out  as for qoimi_build_seek_index
+ * The result (normative; qoi_amd/seekindex.py: points_from_pixels): the points qoi_amd/seekindex.py: points gives with D the caller's pixels at 4
+ * channels, alpha 255 where descs[i].channels == 3.  byte_off and skip are the walk of the STREAM, exactly as for qoimi_build_seek_index; prev
+ * and table are taken from the PIXELS.  Whenever stream i decodes to those pixels - every stream this library or the reference encoder wrote
+ * from them - the result is that of qoimi_build_seek_index, byte for byte.
+ * An image's pixels are the caller's data.  CHECKED is what keeps every access inside the arguments: byte_off and skip always come from the
+ * stream itself, so byte_off lies inside [14, size - 8] and skip is at most 61 whatever the pixels hold, and of the pixels nothing is read but
+ * the aligned 4-byte words that hold a byte of an image.  TRUSTED and, where wrong, giving an index whose bands decode to wrong pixels and
+ * nothing worse: that stream i decodes to the pixels at pixel_offsets[i] (qoimi_verify_images checks exactly that).
+ * No qoimi_decode_images sub-call is made and the staging arena is not used: byte_off and skip from the passes of qoimi_inspect_streams and one
+ * wavefront per point, as for qoimi_build_seek_index; prev and table from two kernels over the caller's pixels, ONE launch each for all images of
+ * the call (there are no sub-batches; qoimi_seek_stats [0] is set to 0).  Workspace (counted in qoimi_workspace_bytes [1]): that of
+ * qoimi_inspect_streams plus 8 bytes per 16 KiB block, 552 per point and 32 per image that has a point.  The remark on intervals of one row
+ * there holds here too.
+ * SYNCHRONOUS: one wait, at the end.  QOIMI_E_ARG for a NULL ctx, d_pixels, pixel_offsets, d_streams, stream_offsets, sizes, descs, interval_rows
+ * or points_out, n_images <= 0, sizes[i] < 22, a rejected descriptor, interval_rows[i] * width < 128, an image whose last byte's address does not
+ * fit in a pointer, 2^25 seek points or more, more than 2^31 blocks of stream bytes, 2^31 - 1 or more tiles of 1024 pixels in the call:
+ * reported before anything is launched, points_out is untouched.  One call at a time per context, as everywhere. */
+int qoimi_seek_index_from_pixels(qoimi_ctx *ctx, const void *d_pixels, const size_t *pixel_offsets /* host */,
+                                 const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                                 const qoi_desc *descs /* host */, int n_images, const unsigned *interval_rows /* host, n_images */,
+                                 qoimi_seek_point *points_out /* host */, void *stream);
 
 /* What the band stream of `band` will be: its size, its descriptor (width, pad_rows + rows, the image's channels and colorspace) and pad_rows -
  * from the points alone, without the stream's bytes.  points: this image's (may be NULL where the band uses none: an image without points);
@@ -678,8 +707,32 @@ int qoimi_decode_crops_indexed(qoimi_ctx *ctx, const void *d_streams, const size
                                const unsigned *interval_rows /* host, n_images */, const qoimi_seek_point *points /* host */,
                                const size_t *point_firsts /* host, n_images */);
 
-/* [0] sub-batches decoded by the context's last qoimi_build_seek_index, [1] band streams assembled by its last qoimi_make_band_streams or
- * qoimi_decode_crops_indexed, [2] bytes of the band arena that call planned for (qoimi_make_band_streams: 0), [3] stream bytes it copied (the
+/* qoimi_decode_resized and qoimi_pixel_stats, byte for byte - `first` and the flags of the statistics included - decoding each referenced image
+ * only from the last seek row at or above its topmost item: a tile of fixed size at any zoom, or "which tiles of a scan are blank", without the
+ * rows above the tiles.  Exactly as qoimi_decode_crops_indexed (normative; qoi_amd/seekindex.py: bands_for_crops over the items' SOURCE
+ * rectangles x, y, width, height): the bands are assembled into the context's band arena, then the plain call runs as it is over them, `image`
+ * renumbered and every y replaced by y - first_row + pad_rows.  The sub-batch plan and the counters of qoimi_resize_stats /
+ * qoimi_pixel_stats_counters are those of that inner call; qoimi_seek_stats [1..3] are set as qoimi_decode_crops_indexed sets them.  Arguments
+ * and rejections of the plain call, and for the referenced images those of qoimi_make_band_streams (an image that no item names is not checked
+ * and its points are not read; what of an index is checked and what is trusted: qoimi_band_plan); QOIMI_E_ARG also for a NULL interval_rows,
+ * points or point_firsts and for more than 12 782 640 referenced images.  SYNCHRONOUS. */
+int qoimi_decode_resized_indexed(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                                 const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                                 const qoimi_resize *items /* host */, int n_items, int mode,
+                                 void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream,
+                                 const unsigned *interval_rows /* host, n_images */, const qoimi_seek_point *points /* host */,
+                                 const size_t *point_firsts /* host, n_images */);
+int qoimi_pixel_stats_indexed(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                              const qoi_desc *descs /* host */, int n_images,
+                              const qoimi_crop *regions /* host */, int n_regions,
+                              qoimi_pixel_stat *stats_out /* host, n_regions */,
+                              unsigned *d_hist /* DEVICE unsigned[n_regions][4][256], may be NULL */,
+                              size_t staging_bytes, void *stream,
+                              const unsigned *interval_rows /* host, n_images */, const qoimi_seek_point *points /* host */,
+                              const size_t *point_firsts /* host, n_images */);
+
+/* [0] sub-batches decoded by the context's last qoimi_build_seek_index (qoimi_seek_index_from_pixels: 0), [1] band streams assembled by its
+ * last qoimi_make_band_streams or indexed call (qoimi_decode_crops_indexed, qoimi_decode_resized_indexed, qoimi_pixel_stats_indexed), [2] bytes of the band arena that call planned for (qoimi_make_band_streams: 0), [3] stream bytes it copied (the
  * tails).  The kernels have no entry in qoimi_kernel_name. */
 void qoimi_seek_stats(qoimi_ctx *ctx, long long out[4]);
 
@@ -700,7 +753,7 @@ int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
  * qoimi_encode_packed), [1] decode workspace
  * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images,
  * qoimi_decode_thumbnails, qoimi_decode_crops, qoimi_decode_resized, qoimi_pixel_stats and qoimi_build_seek_index, which share them, the tables of
- * qoimi_build_seek_index and the band arena of qoimi_decode_crops_indexed),
+ * qoimi_build_seek_index and qoimi_seek_index_from_pixels and the band arena of the indexed calls),
  * [2] staging buffers of the host-pointer entry points (qoi_encode / qoi_decode of the calling thread's context). */
 void qoimi_workspace_bytes(qoimi_ctx *ctx, size_t out[3]);
 

@@ -44,6 +44,7 @@ EXPORTS = (
     "qoimi_decode_resized", "qoimi_resize_size", "qoimi_resize_stats",
     "qoimi_pixel_stats", "qoimi_pixel_stats_counters",
     "qoimi_seek_points", "qoimi_build_seek_index", "qoimi_band_plan", "qoimi_make_band_streams", "qoimi_decode_crops_indexed", "qoimi_seek_stats",
+    "qoimi_seek_index_from_pixels", "qoimi_decode_resized_indexed", "qoimi_pixel_stats_indexed",
 )
 
 
@@ -237,6 +238,12 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_decode_crops_indexed.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, ci, cp, ci, vp, szp, sz, vp, up, pp, szp]
     lib.qoimi_seek_stats.restype = None
     lib.qoimi_seek_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+    lib.qoimi_seek_index_from_pixels.restype = ci
+    lib.qoimi_seek_index_from_pixels.argtypes = [vp, vp, szp, vp, szp, ctypes.POINTER(ci), dp, ci, up, pp, vp]
+    lib.qoimi_decode_resized_indexed.restype = ci
+    lib.qoimi_decode_resized_indexed.argtypes = lib.qoimi_decode_resized.argtypes + [up, pp, szp]
+    lib.qoimi_pixel_stats_indexed.restype = ci
+    lib.qoimi_pixel_stats_indexed.argtypes = lib.qoimi_pixel_stats.argtypes + [up, pp, szp]
     _lib = lib
     return lib
 
@@ -776,8 +783,94 @@ class Context:
                                                          stream, ks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), pts, pf.ctypes.data_as(szp)),
                     "qoimi_decode_crops_indexed")
 
+    def seek_index_from_pixels(self, d_pixels: int, pixel_offsets: Sequence[int], d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int],
+                               descs: Sequence[QoiDesc], interval_rows, stream: int = 0):
+        """``build_seek_index`` for whoever holds the pixels the pack was encoded from (``qoimi_seek_index_from_pixels``, synchronous: one
+        inspect and two kernels over the pixels, no decode, no staging): image i is width * height * channels bytes at d_pixels +
+        pixel_offsets[i], any byte offset.  Returns (points, point_firsts) as ``build_seek_index`` does; that stream i decodes to those
+        pixels is not checked (``verify_images`` does that); ``qoi_amd/seekindex.py: points_from_pixels`` states the result."""
+        from .seekindex import POINT_DTYPE
+        n = len(sizes)
+        if isinstance(interval_rows, (int, np.integer)):
+            interval_rows = [int(interval_rows)] * n
+        if len(descs) != n or len(stream_offsets) != n or len(interval_rows) != n or len(pixel_offsets) != n:
+            raise QoiError("seek_index_from_pixels: one pixel offset, stream offset, size, descriptor and interval per image")
+        counts = [seek_points(d.width, d.height, d.channels, int(k)) for d, k in zip(descs, interval_rows)]
+        if any(k < 0 for k in counts):
+            raise QoiError("seek_index_from_pixels: a rejected descriptor or interval_rows * width < 128")
+        firsts = [int(x) for x in np.cumsum([0] + counts[:-1])]
+        points = np.zeros(sum(counts), dtype=POINT_DTYPE)
+        room = points if points.size else np.zeros(1, dtype=POINT_DTYPE)
+        po = np.ascontiguousarray(pixel_offsets, dtype=np.uintp)
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        ks = np.ascontiguousarray(interval_rows, dtype=np.uintc)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        self._check(self._lib.qoimi_seek_index_from_pixels(self._h, d_pixels, po.ctypes.data_as(szp), d_streams, so.ctypes.data_as(szp),
+                                                           sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), (QoiDesc * n)(*descs), n,
+                                                           ks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), room.ctypes.data_as(ctypes.POINTER(QoimiSeekPoint)),
+                                                           stream), "qoimi_seek_index_from_pixels")
+        return points, firsts
+
+    def _index_args(self, what: str, n: int, interval_rows, points, point_firsts):
+        """(interval_rows, points, point_firsts) as the three trailing arguments of an indexed call; the arrays are kept alive by the tuple."""
+        if isinstance(interval_rows, (int, np.integer)):
+            interval_rows = [int(interval_rows)] * n
+        if len(interval_rows) != n or len(point_firsts) != n:
+            raise QoiError(what + ": one interval and first point per image")
+        pts, _ = _point_array(points)
+        pf = np.ascontiguousarray(point_firsts, dtype=np.uintp)
+        ks = np.ascontiguousarray(interval_rows, dtype=np.uintc)
+        return (ks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), pts, pf.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t))), (ks, pts, pf)
+
+    def decode_resized_indexed(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                               items, mode: int, d_out: int, out_offsets: Sequence[int], interval_rows, points, point_firsts: Sequence[int],
+                               staging_bytes: int = 0, stream: int = 0) -> None:
+        """``decode_resized`` byte for byte, decoding every referenced image only from the last seek row at or above its topmost source
+        rectangle (``qoimi_decode_resized_indexed``).  interval_rows, points, point_firsts: as ``build_seek_index`` took and returned them;
+        ``resize_stats`` then holds the counters of the inner call over the band streams."""
+        n = len(sizes)
+        if len(descs) != n or len(stream_offsets) != n:
+            raise QoiError("decode_resized_indexed: one stream offset, size and descriptor per image")
+        if len(out_offsets) != len(items):
+            raise QoiError("decode_resized_indexed: one output offset per item")
+        arr = _resize_array(items)
+        if arr is None:
+            raise QoiError("decode_resized_indexed: an item is not eight unsigned 32-bit fields")
+        index, keep = self._index_args("decode_resized_indexed", n, interval_rows, points, point_firsts)
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        self._check(self._lib.qoimi_decode_resized_indexed(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                           (QoiDesc * n)(*descs), n, channels, arr, len(arr), mode, d_out, oo.ctypes.data_as(szp),
+                                                           staging_bytes, stream, *index), "qoimi_decode_resized_indexed")
+        del keep
+
+    def pixel_stats_indexed(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], regions,
+                            interval_rows, points, point_firsts: Sequence[int], d_hist: int = 0, staging_bytes: int = 0,
+                            stream: int = 0) -> List[QoimiPixelStat]:
+        """``pixel_stats`` field for field, decoding every referenced image only from the last seek row at or above its topmost region
+        (``qoimi_pixel_stats_indexed``).  interval_rows, points, point_firsts: as ``build_seek_index`` took and returned them;
+        ``pixel_stats_counters`` then holds the counters of the inner call over the band streams."""
+        n = len(sizes)
+        if len(descs) != n or len(stream_offsets) != n:
+            raise QoiError("pixel_stats_indexed: one stream offset, size and descriptor per image")
+        arr = _crop_array(regions)
+        if arr is None:
+            raise QoiError("pixel_stats_indexed: a region is not six unsigned 32-bit fields")
+        index, keep = self._index_args("pixel_stats_indexed", n, interval_rows, points, point_firsts)
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        out = (QoimiPixelStat * max(len(arr), 1))()
+        self._check(self._lib.qoimi_pixel_stats_indexed(self._h, d_streams, so.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
+                                                        sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), (QoiDesc * n)(*descs), n, arr, len(arr), out,
+                                                        d_hist or None, staging_bytes, stream, *index), "qoimi_pixel_stats_indexed")
+        del keep
+        return list(out)[:len(arr)]
+
     def seek_stats(self) -> Tuple[int, int, int, int]:
-        """(sub-batches decoded by the last ``build_seek_index``; of the last ``make_band_streams`` / ``decode_crops_indexed``: band streams
+        """(sub-batches decoded by the last ``build_seek_index``; of the last ``make_band_streams`` / indexed call: band streams
         assembled, bytes of the band arena planned, stream bytes copied)."""
         out = (ctypes.c_longlong * 4)()
         self._lib.qoimi_seek_stats(self._h, out)
@@ -803,7 +896,7 @@ class Context:
         return {self._lib.qoimi_kernel_name(i).decode(): (ms[i], calls[i]) for i in range(1, n)}
 
     def workspace_bytes(self) -> dict:
-        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops`` / ``decode_resized`` / ``pixel_stats``), staging of the host-pointer entry points."""
+        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops`` / ``decode_resized`` / ``pixel_stats``, the tables of ``build_seek_index`` / ``seek_index_from_pixels`` and the band arena of the indexed calls), staging of the host-pointer entry points."""
         out = (ctypes.c_size_t * 3)()
         self._lib.qoimi_workspace_bytes(self._h, out)
         return {"encode": int(out[0]), "decode": int(out[1]), "staging": int(out[2])}

@@ -1,6 +1,7 @@
 // qoi_host_staged.hip — the calls of the C-ABI shim that decode a pack's images into bounded staging and run one table-driven kernel over
 // each sub-batch: qoimi_verify_images (and qoimi_compare_images, whose kernels it runs), qoimi_decode_thumbnails, qoimi_decode_crops,
-// qoimi_decode_resized, qoimi_pixel_stats, and the row seek index (qoimi_build_seek_index, qoimi_make_band_streams, qoimi_decode_crops_indexed).
+// qoimi_decode_resized, qoimi_pixel_stats, and the row seek index (qoimi_build_seek_index, qoimi_seek_index_from_pixels - which stages nothing -,
+// qoimi_make_band_streams, qoimi_decode_crops_indexed, qoimi_decode_resized_indexed, qoimi_pixel_stats_indexed).
 #include "qoi_ctx.h"
 #include "qoi_thumb_core.h"
 #include "qoi_crop_core.h"
@@ -555,91 +556,131 @@ extern "C" int qoimi_seek_points(const qoi_desc* desc, unsigned interval_rows) {
     return (int)seek_point_count(desc->width, desc->height, interval_rows);
 }
 
-// One qoimi_inspect_streams over the images that have a point, the block scan and a wavefront per point on top of its tables (byte_off,
-// skip); then run_staged over those images at their full height with seek_last + seek_carry per sub-batch (prev, table), which write the
-// points behind the image table; one copy back.
-extern "C" int qoimi_build_seek_index(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
-                                      int n_images, const unsigned* interval_rows, qoimi_seek_point* points_out, size_t staging_bytes, void* stream) {
-    // (everything is looked at before the context is: a rejected call launches nothing and leaves points_out as it was)
-    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !interval_rows || !points_out || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
-    const size_t n = (size_t)n_images;
+// What the two builds of an index share.  SeekCount: what seek_count makes of a call's images - np[i] points of image i from point_base[i]
+// on, refs: the images that have a point, ascending; total points; tiles of kSeekTilePx pixels, blocks and pieces of the inspect passes over refs.
+struct SeekCount { std::vector<uint32_t> np, point_base; std::vector<size_t> refs; uint64_t total = 0, tiles = 0; size_t nb = 0, npieces = 0; };
+
+// The checks both builds make per image, in the order that decides which message a call with several faults gets; more(i): nullptr, or what
+// else is wrong with image i.
+template <class More>
+static int seek_count(const int* sizes, const qoi_desc* descs, size_t n, const unsigned* interval_rows, More more, SeekCount& k) {
     const int kMin = kHeaderBytes + kTrailerBytes;
-    std::vector<uint32_t> rows(n), np(n), point_base(n);
-    uint64_t total = 0;
+    k.np.resize(n); k.point_base.resize(n);
     for (size_t i = 0; i < n; ++i) {
         if (sizes[i] < kMin) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + " shorter than 22 bytes (qoi.h:500)");
         if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:513-521 rules)");
         const int64_t cnt = seek_point_count(descs[i].width, descs[i].height, interval_rows[i]);
         if (cnt < 0) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": interval_rows * width below 128");
-        np[i] = (uint32_t)cnt; point_base[i] = (uint32_t)total; rows[i] = cnt != 0 ? descs[i].height : 0u;
-        total += (uint64_t)cnt;
+        if (const char* what = more(i)) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": " + what);
+        k.np[i] = (uint32_t)cnt; k.point_base[i] = (uint32_t)k.total;
+        k.total += (uint64_t)cnt;
+        if (cnt == 0) continue;
+        k.refs.push_back(i);
+        const uint64_t ipx = (uint64_t)interval_rows[i] * descs[i].width;
+        k.tiles += (uint64_t)cnt * ((ipx + kSeekTilePx - 1u) / kSeekTilePx);
+        const size_t body = (size_t)(sizes[i] - kMin);
+        k.nb += (body + kInsBlock - 1u) / kInsBlock;
+        k.npieces += (body + kInsPiece - 1u) / kInsPiece;
     }
-    if (total >= 0x7FFFFFFFull / 64u) return fail(QOIMI_E_ARG, "more than 2^25 seek points in one call");
-    const RowsPlan plan = plan_rows(descs, n_images, rows, staging_bytes);
+    if (k.total >= 0x7FFFFFFFull / 64u) return fail(QOIMI_E_ARG, "more than 2^25 seek points in one call");
+    if (k.nb >= 0x7FFFFFFFu || k.npieces >= 0xFFFFFFFFu) return fail(QOIMI_E_ARG, "more than 2^31 blocks of stream bytes in one call");
+    return QOIMI_OK;
+}
+
+// byte_off and skip of every point (k.total >= 1): one qoimi_inspect_streams over the images that have a point, the block scan and a
+// wavefront per point on top of its tables, enqueued on st and NOT waited for.  Pinned staging (c->pin): [stream table][block table][jobs]
+// [extra_bytes of the caller's: fill(those bytes) writes them] go to the device in one copy, [results][header + trailer bytes] are written by
+// inspect_reduce in place (and not looked at), [room for the points, if with_points].  The workspace is carved the same way: d_extra is the
+// caller's table on the device, d_loc what seek_locate finds, d_last a zeroed uint32[64] per point, d_points (with_points) room for the points.
+struct SeekLocated { const uint8_t* d_extra; SeekLoc* d_loc; uint32_t* d_last; SeekPoint* d_points; uint8_t* h_points; };
+
+template <class Fill>
+static int locate_points(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                         const unsigned* interval_rows, const SeekCount& k, size_t extra_bytes, Fill fill, bool with_points, void* stream, SeekLocated& out) {
+    hipStream_t st = (hipStream_t)stream;
+    if (const int rc = wait_decode_tail(c, stream)) return rc;
+    if (const int rc = timer_room(c, st)) return rc;
+    const size_t R = k.refs.size(), nb = k.nb, npieces = k.npieces, total = (size_t)k.total;
+    const size_t tab_bytes = up256(R * sizeof(InsStream)) + up256(nb * sizeof(InsBlock)), job_bytes = up256(total * sizeof(SeekJob));
+    const size_t in_bytes = tab_bytes + job_bytes + up256(extra_bytes);
+    const size_t res_at = in_bytes, raw_at = res_at + up256(R * sizeof(InsResult)), pts_at = raw_at + up256(R * 32u);
+    if (const int rc = c->pin.reserve(pts_at + (with_points ? total * sizeof(SeekPoint) : 0u))) return rc;
+    uint8_t* pin = (uint8_t*)c->pin.buf;
+    InsStream* h_tab = (InsStream*)pin;
+    InsBlock* h_blk = (InsBlock*)(pin + up256(R * sizeof(InsStream)));
+    SeekJob* h_job = (SeekJob*)(pin + tab_bytes);
+    std::vector<size_t> so(R); std::vector<int> sz(R);
+    for (size_t r = 0; r < R; ++r) { so[r] = stream_offsets[k.refs[r]]; sz[r] = sizes[k.refs[r]]; }
+    ins_fill_tables(so.data(), sz.data(), R, h_tab, h_blk);
+    for (size_t r = 0; r < R; ++r) {
+        const size_t i = k.refs[r];
+        const uint32_t ipx = interval_rows[i] * descs[i].width;          // (below 400 000 000: a point lies inside the image)
+        for (uint32_t p = 0; p < k.np[i]; ++p) { SeekJob& j = h_job[k.point_base[i] + p]; j.stream = (uint32_t)r; j.point = k.point_base[i] + p; j.P = (p + 1u) * ipx; j.reserved = 0u; }
+    }
+    fill(pin + tab_bytes + job_bytes);
+    Carver sizer(nullptr);
+    sizer.take<uint8_t>(in_bytes); sizer.take<uint32_t>(nb); sizer.take<uint8_t>(nb); sizer.take<uint16_t>(npieces); sizer.take<InsPartial>(nb);
+    sizer.take<u64>(nb); sizer.take<SeekLoc>(total); sizer.take<uint32_t>(total * 64u);
+    if (with_points) sizer.take<SeekPoint>(total);
+    { const int rc = c->insp_ws.reserve(sizer.off + 256u); if (rc != QOIMI_OK) return rc; }
+    Carver cv(c->insp_ws.base);
+    uint8_t* d_tab = cv.take<uint8_t>(in_bytes);
+    uint32_t* d_map = cv.take<uint32_t>(nb);
+    uint8_t* d_entry = cv.take<uint8_t>(nb);
+    uint16_t* d_piece = cv.take<uint16_t>(npieces);
+    InsPartial* d_part = cv.take<InsPartial>(nb);
+    u64* d_blk_px = cv.take<u64>(nb);
+    out.d_loc = cv.take<SeekLoc>(total);
+    out.d_last = cv.take<uint32_t>(total * 64u);
+    out.d_points = with_points ? cv.take<SeekPoint>(total) : nullptr;
+    out.d_extra = d_tab + tab_bytes + job_bytes;
+    out.h_points = with_points ? pin + pts_at : nullptr;
+    const InsBlock* d_blk = (const InsBlock*)(d_tab + up256(R * sizeof(InsStream)));
+    HIP_TRY(hipMemcpyAsync(d_tab, pin, in_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(out.d_last, 0, total * 64u * sizeof(uint32_t), st));
+    launch_inspect((const uint8_t*)d_streams, (const InsStream*)d_tab, (uint32_t)R, d_blk, (uint32_t)nb, d_map, d_entry, d_piece, d_part, (InsResult*)(pin + res_at),
+                   (uint32_t*)(pin + raw_at), st, &c->timer);
+    launch_seek_locate((const uint8_t*)d_streams, (const InsStream*)d_tab, (uint32_t)R, d_blk, d_part, d_entry, d_piece, d_blk_px,
+                       (const SeekJob*)(d_tab + tab_bytes), (uint32_t)total, out.d_loc, st);
+    HIP_TRY(hipGetLastError());
+    return QOIMI_OK;
+}
+
+// locate_points (byte_off, skip); then run_staged over the images that have a point at their full height with seek_last + seek_carry per
+// sub-batch (prev, table), which write the points behind the image table; one copy back.
+extern "C" int qoimi_build_seek_index(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                      int n_images, const unsigned* interval_rows, qoimi_seek_point* points_out, size_t staging_bytes, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves points_out as it was)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !interval_rows || !points_out || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    const size_t n = (size_t)n_images;
+    SeekCount k;
+    if (const int rc = seek_count(sizes, descs, n, interval_rows, [](size_t) { return (const char*)nullptr; }, k)) return rc;
+    const std::vector<uint32_t>& np = k.np; const std::vector<uint32_t>& point_base = k.point_base;
+    const uint64_t total = k.total;
+    std::vector<uint32_t> rows(n);
+    for (size_t i = 0; i < n; ++i) rows[i] = np[i] != 0u ? descs[i].height : 0u;
+    const RowsPlan plan = plan_rows(descs, n_images, rows, staging_bytes);   // (plan.refs is k.refs: the images that have a point)
     const size_t R = plan.refs.size();
     std::vector<uint32_t> image_of(R);
     std::vector<uint64_t> tiles_of(R);
-    size_t nb = 0, npieces = 0;
     for (size_t r = 0; r < R; ++r) {
         const size_t i = (size_t)plan.refs[r];
         image_of[r] = (uint32_t)i;
         const uint64_t ipx = (uint64_t)interval_rows[i] * descs[i].width;
         tiles_of[r] = (uint64_t)np[i] * ((ipx + kSeekTilePx - 1u) / kSeekTilePx);
-        const size_t body = (size_t)(sizes[i] - kMin);
-        nb += (body + kInsBlock - 1u) / kInsBlock;
-        npieces += (body + kInsPiece - 1u) / kInsPiece;
     }
-    if (nb >= 0x7FFFFFFFu || npieces >= 0xFFFFFFFFu) return fail(QOIMI_E_ARG, "more than 2^31 blocks of stream bytes in one call");
     const ItemPlan items = plan_items(image_of, plan.ref_of, plan.firsts, tiles_of);   // (entry r is the r-th image that has a point)
     if (items.overflow) return fail(QOIMI_E_ARG, "more than 2^31 tiles of pixels in one sub-batch");
     c->seek_stats[0] = 0;
     if (total == 0u) return QOIMI_OK;
-    SeekLoc* d_loc = nullptr; uint32_t* d_last = nullptr;
+    SeekLocated at;
     {
         DeviceGuard guard(c->device);
-        hipStream_t st = (hipStream_t)stream;
-        if (const int rc = wait_decode_tail(c, stream)) return rc;
-        if (const int rc = timer_room(c, st)) return rc;
-        // pinned staging: [stream table][block table][jobs] go to the device, [results][header + trailer bytes] are written by inspect_reduce in place
-        const size_t tab_bytes = up256(R * sizeof(InsStream)) + up256(nb * sizeof(InsBlock)), job_bytes = up256((size_t)total * sizeof(SeekJob));
-        if (const int rc = c->pin.reserve(tab_bytes + job_bytes + up256(R * sizeof(InsResult)) + up256(R * 32u))) return rc;
-        uint8_t* pin = (uint8_t*)c->pin.buf;
-        InsStream* h_tab = (InsStream*)pin;
-        InsBlock* h_blk = (InsBlock*)(pin + up256(R * sizeof(InsStream)));
-        SeekJob* h_job = (SeekJob*)(pin + tab_bytes);
-        InsResult* h_res = (InsResult*)(pin + tab_bytes + job_bytes);
-        std::vector<size_t> so(R); std::vector<int> sz(R);
-        for (size_t r = 0; r < R; ++r) { so[r] = stream_offsets[plan.refs[r]]; sz[r] = sizes[plan.refs[r]]; }
-        ins_fill_tables(so.data(), sz.data(), R, h_tab, h_blk);
-        for (size_t r = 0; r < R; ++r) {
-            const size_t i = (size_t)plan.refs[r];
-            const uint32_t ipx = interval_rows[i] * descs[i].width;      // (below 400 000 000: a point lies inside the image)
-            for (uint32_t k = 0; k < np[i]; ++k) { SeekJob& j = h_job[point_base[i] + k]; j.stream = (uint32_t)r; j.point = point_base[i] + k; j.P = (k + 1u) * ipx; j.reserved = 0u; }
-        }
-        Carver sizer(nullptr);
-        sizer.take<uint8_t>(tab_bytes + job_bytes); sizer.take<uint32_t>(nb); sizer.take<uint8_t>(nb); sizer.take<uint16_t>(npieces); sizer.take<InsPartial>(nb);
-        sizer.take<u64>(nb); sizer.take<SeekLoc>((size_t)total); sizer.take<uint32_t>((size_t)total * 64u);
-        { const int rc = c->insp_ws.reserve(sizer.off + 256u); if (rc != QOIMI_OK) return rc; }
-        Carver cv(c->insp_ws.base);
-        uint8_t* d_tab = cv.take<uint8_t>(tab_bytes + job_bytes);
-        uint32_t* d_map = cv.take<uint32_t>(nb);
-        uint8_t* d_entry = cv.take<uint8_t>(nb);
-        uint16_t* d_piece = cv.take<uint16_t>(npieces);
-        InsPartial* d_part = cv.take<InsPartial>(nb);
-        u64* d_blk_px = cv.take<u64>(nb);
-        d_loc = cv.take<SeekLoc>((size_t)total);
-        d_last = cv.take<uint32_t>((size_t)total * 64u);
-        const InsBlock* d_blk = (const InsBlock*)(d_tab + up256(R * sizeof(InsStream)));
-        HIP_TRY(hipMemcpyAsync(d_tab, pin, tab_bytes + job_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(d_last, 0, (size_t)total * 64u * sizeof(uint32_t), st));
-        launch_inspect((const uint8_t*)d_streams, (const InsStream*)d_tab, (uint32_t)R, d_blk, (uint32_t)nb, d_map, d_entry, d_piece, d_part, h_res,
-                       (uint32_t*)(pin + tab_bytes + job_bytes + up256(R * sizeof(InsResult))), st, &c->timer);
-        launch_seek_locate((const uint8_t*)d_streams, (const InsStream*)d_tab, (uint32_t)R, d_blk, d_part, d_entry, d_piece, d_blk_px,
-                           (const SeekJob*)(d_tab + tab_bytes), (uint32_t)total, d_loc, st);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));                               // (the decode calls below reuse the pinned staging at once)
+        if (const int rc = locate_points(c, d_streams, stream_offsets, sizes, descs, interval_rows, k, 0u, [](uint8_t*) {}, false, stream, at)) return rc;
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));              // (the decode calls below reuse the pinned staging at once)
         if (c->timer.on) timer_collect(c);
     }
+    SeekLoc* d_loc = at.d_loc; uint32_t* d_last = at.d_last;
     const size_t res_at = staged_extra_at(R, sizeof(SeekImage));
     long long stats[4];
     const int rc = run_staged<SeekImage>(c, stats, (long long)R, "seek_last", d_streams, stream_offsets, sizes, descs, plan, rows, items,
@@ -656,6 +697,49 @@ extern "C" int qoimi_build_seek_index(qoimi_ctx* c, const void* d_streams, const
     c->seek_stats[0] = stats[0];
     if (rc != QOIMI_OK) return rc;
     memcpy(points_out, (const uint8_t*)c->cmp_pin.buf + res_at, (size_t)total * sizeof(SeekPoint));
+    return QOIMI_OK;
+}
+
+// locate_points (byte_off, skip) and, in the same stream order, seekpx_last + seekpx_carry over the caller's pixels in ONE launch each (prev,
+// table): no decode, no staging arena.  The image table travels with the inspect tables, the points are written on the device behind them
+// and come back in one copy; one wait, at the end.
+extern "C" int qoimi_seek_index_from_pixels(qoimi_ctx* c, const void* d_pixels, const size_t* pixel_offsets, const void* d_streams, const size_t* stream_offsets,
+                                            const int* sizes, const qoi_desc* descs, int n_images, const unsigned* interval_rows, qoimi_seek_point* points_out,
+                                            void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves points_out as it was)
+    if (!c || !d_pixels || !pixel_offsets || !d_streams || !stream_offsets || !sizes || !descs || !interval_rows || !points_out || n_images <= 0)
+        return fail(QOIMI_E_ARG, "NULL/empty argument");
+    const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_pixels;          // the last byte of an image may stand at the last address there is
+    SeekCount k;
+    if (const int rc = seek_count(sizes, descs, (size_t)n_images, interval_rows, [&](size_t i) {
+            const size_t bytes = (size_t)descs[i].width * descs[i].height * descs[i].channels;
+            return pixel_offsets[i] > room || bytes - 1u > room - pixel_offsets[i] ? "the address of its last byte does not fit in a pointer" : (const char*)nullptr;
+        }, k)) return rc;
+    if (k.tiles >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of pixels in one call");
+    c->seek_stats[0] = 0;                                      // (no sub-batch is decoded)
+    if (k.total == 0u) return QOIMI_OK;
+    const size_t R = k.refs.size(), pts_bytes = (size_t)k.total * sizeof(SeekPoint);
+    uint32_t t = 0;
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    SeekLocated at;
+    if (const int rc = locate_points(c, d_streams, stream_offsets, sizes, descs, interval_rows, k, R * sizeof(SeekPxImage), [&](uint8_t* bytes) {
+            SeekPxImage* h_img = (SeekPxImage*)bytes;
+            for (size_t r = 0; r < R; ++r) {
+                const size_t i = k.refs[r];
+                SeekPxImage& e = h_img[r];
+                e.src_off = (u64)pixel_offsets[i]; e.ipx = interval_rows[i] * descs[i].width; e.np = k.np[i];
+                e.tpi = (e.ipx + kSeekTilePx - 1u) / kSeekTilePx; e.first_tile = t; e.point_base = k.point_base[i]; e.ch = descs[i].channels;
+                t += e.np * e.tpi;
+            }
+        }, true, stream, at)) return rc;
+    const uint32_t most = (uint32_t)c->n_cus * 8u;
+    launch_seek_tables_px((const uint8_t*)d_pixels, (const SeekPxImage*)at.d_extra, (uint32_t)R, t, at.d_last, at.d_loc, at.d_points, t < most ? t : most, st);
+    { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(QOIMI_E_INTERNAL, std::string("seekpx_last: ") + hipGetErrorString(e)); } }
+    HIP_TRY(hipMemcpyAsync(at.h_points, at.d_points, pts_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (c->timer.on) timer_collect(c);
+    memcpy(points_out, at.h_points, pts_bytes);
     return QOIMI_OK;
 }
 
@@ -791,6 +875,64 @@ extern "C" int qoimi_make_band_streams(qoimi_ctx* c, const void* d_streams, cons
     return QOIMI_OK;
 }
 
+// What the indexed calls share (qoi_amd/seekindex.py: bands_for_crops).  rows[i] / top[i]: the largest y + height and the smallest y over the
+// items of image i (rows[i] == 0: no item names it, the image is not looked at).  Per referenced image, ascending, the band from the last seek
+// row at or above top[i] to rows[i]; the band streams are assembled into the context's band arena and described as the inner call takes them:
+// at / sz / ds are its stream_offsets / sizes / descs, number[i] is the band of image i and shift[r] what is added to the y of an item of band
+// r (pad_rows - first_row, modulo 2^32).  Everything is looked at before anything is launched.
+struct BandedCall { std::vector<size_t> at; std::vector<int> sz, number; std::vector<qoi_desc> ds; std::vector<uint32_t> shift; };
+
+static int stage_bands(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs, int n_images,
+                       const std::vector<uint32_t>& rows, const std::vector<uint32_t>& top, const unsigned* interval_rows, const qoimi_seek_point* points,
+                       const size_t* point_firsts, void* stream, BandedCall& out) {
+    std::vector<BandPlan> plans;
+    std::vector<uint32_t> image_of;
+    out.number.assign((size_t)n_images, -1);
+    size_t arena = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (rows[(size_t)i] == 0u) continue;                   // (an image no item names is never looked at)
+        const unsigned K = interval_rows[i];
+        if (seek_point_count(descs[i].width, descs[i].height, K) < 0) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": interval_rows * width below 128");
+        qoimi_band b;
+        b.image = (unsigned)i; b.first_row = top[(size_t)i] / K * K; b.rows = rows[(size_t)i] - b.first_row; b.reserved = 0u;
+        BandPlan p;
+        if (const char* what = band_wrong(&descs[i], sizes[i], K, points + point_firsts[i], &b, p)) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": " + what);
+        out.number[(size_t)i] = (int)plans.size();
+        plans.push_back(p); image_of.push_back((uint32_t)i); out.shift.push_back(p.info.pad_rows - b.first_row); out.at.push_back(arena);
+        arena += ((size_t)p.info.size + 15u) & ~(size_t)15u;
+    }
+    std::vector<uint32_t> first_tile; uint32_t tiles = 0;
+    if (plans.size() > 0xFFFFFFFFu / kSeekHeadSlot) return fail(QOIMI_E_ARG, "more than 12 782 640 referenced images in one call");
+    if (!band_tiles(plans, (uintptr_t)0, out.at.data(), first_tile, tiles)) return fail(QOIMI_E_ARG, "more than 2^31 tiles of band stream words in one call");
+    {
+        DeviceGuard guard(c->device);
+        if (const int rc = reserve_exact(c->band_arena, arena)) return rc;
+    }
+    if (const int rc = assemble_bands(c, d_streams, stream_offsets, plans, image_of, c->band_arena.base, out.at.data(), first_tile, tiles, stream)) return rc;
+    c->seek_stats[2] = (long long)arena;
+    for (const BandPlan& p : plans) { out.sz.push_back((int)p.info.size); out.ds.push_back(p.info.desc); }
+    return QOIMI_OK;
+}
+
+// The smallest y over the items of every image (~0: no item names it); the items have been checked.
+template <class Item>
+static std::vector<uint32_t> item_tops(const Item* items, size_t n, int n_images) {
+    std::vector<uint32_t> top((size_t)n_images, ~0u);
+    for (size_t j = 0; j < n; ++j) if (items[j].y < top[items[j].image]) top[items[j].image] = items[j].y;
+    return top;
+}
+
+// The items as the inner call takes them: `image` the band's number, y - first_row + pad_rows.
+template <class Item>
+static std::vector<Item> rebase_items(const Item* items, size_t n, const BandedCall& b) {
+    std::vector<Item> out(items, items + n);
+    for (size_t j = 0; j < n; ++j) {
+        const size_t r = (size_t)b.number[items[j].image];
+        out[j].image = (unsigned)r; out[j].y = items[j].y + b.shift[r];
+    }
+    return out;
+}
+
 // The bands of qoi_amd/seekindex.py: bands_for_crops into the context's band arena, then qoimi_decode_crops as it is over them.
 extern "C" int qoimi_decode_crops_indexed(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                           int n_images, int channels, const qoimi_crop* crops, int n_crops, void* d_out, const size_t* out_offsets,
@@ -803,40 +945,45 @@ extern "C" int qoimi_decode_crops_indexed(qoimi_ctx* c, const void* d_streams, c
     const size_t n = (size_t)n_crops;
     CheckedItems ok;
     if (const int rc = check_items("crop", sizes, descs, n_images, channels, crops, n, d_out, out_offsets, crop_rect_wrong, crop_bytes, ok)) return rc;
-    std::vector<uint32_t> top((size_t)n_images, ~0u);
-    for (size_t j = 0; j < n; ++j) if (crops[j].y < top[crops[j].image]) top[crops[j].image] = crops[j].y;
-    std::vector<BandPlan> plans;
-    std::vector<uint32_t> image_of, first_row;
-    std::vector<int> number((size_t)n_images, -1);
-    std::vector<size_t> at;                                    // where band stream r lies in the arena
-    size_t arena = 0;
-    for (int i = 0; i < n_images; ++i) {
-        if (ok.rows[(size_t)i] == 0u) continue;                // (an image no crop names is never looked at)
-        const unsigned K = interval_rows[i];
-        if (seek_point_count(descs[i].width, descs[i].height, K) < 0) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": interval_rows * width below 128");
-        qoimi_band b;
-        b.image = (unsigned)i; b.first_row = top[(size_t)i] / K * K; b.rows = ok.rows[(size_t)i] - b.first_row; b.reserved = 0u;
-        BandPlan p;
-        if (const char* what = band_wrong(&descs[i], sizes[i], K, points + point_firsts[i], &b, p)) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": " + what);
-        number[(size_t)i] = (int)plans.size();
-        plans.push_back(p); image_of.push_back((uint32_t)i); first_row.push_back(b.first_row); at.push_back(arena);
-        arena += ((size_t)p.info.size + 15u) & ~(size_t)15u;
-    }
-    std::vector<uint32_t> first_tile; uint32_t tiles = 0;
-    if (plans.size() > 0xFFFFFFFFu / kSeekHeadSlot) return fail(QOIMI_E_ARG, "more than 12 782 640 referenced images in one call");
-    if (!band_tiles(plans, (uintptr_t)0, at.data(), first_tile, tiles)) return fail(QOIMI_E_ARG, "more than 2^31 tiles of band stream words in one call");
-    {
-        DeviceGuard guard(c->device);
-        if (const int rc = reserve_exact(c->band_arena, arena)) return rc;
-    }
-    if (const int rc = assemble_bands(c, d_streams, stream_offsets, plans, image_of, c->band_arena.base, at.data(), first_tile, tiles, stream)) return rc;
-    c->seek_stats[2] = (long long)arena;
-    const size_t R = plans.size();
-    std::vector<int> sz(R); std::vector<qoi_desc> ds(R); std::vector<qoimi_crop> cs(crops, crops + n);
-    for (size_t r = 0; r < R; ++r) { sz[r] = (int)plans[r].info.size; ds[r] = plans[r].info.desc; }
-    for (size_t j = 0; j < n; ++j) {
-        const size_t r = (size_t)number[crops[j].image];
-        cs[j].image = (unsigned)r; cs[j].y = crops[j].y - first_row[r] + plans[r].info.pad_rows;
-    }
-    return qoimi_decode_crops(c, c->band_arena.base, at.data(), sz.data(), ds.data(), (int)R, channels, cs.data(), n_crops, d_out, out_offsets, staging_bytes, stream);
+    BandedCall b;
+    if (const int rc = stage_bands(c, d_streams, stream_offsets, sizes, descs, n_images, ok.rows, item_tops(crops, n, n_images), interval_rows, points, point_firsts, stream, b)) return rc;
+    const std::vector<qoimi_crop> cs = rebase_items(crops, n, b);
+    return qoimi_decode_crops(c, c->band_arena.base, b.at.data(), b.sz.data(), b.ds.data(), (int)b.sz.size(), channels, cs.data(), n_crops, d_out, out_offsets, staging_bytes, stream);
+}
+
+// ... then qoimi_decode_resized as it is over them: the bands are those of the items' SOURCE rectangles.
+extern "C" int qoimi_decode_resized_indexed(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                            int n_images, int channels, const qoimi_resize* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
+                                            size_t staging_bytes, void* stream, const unsigned* interval_rows, const qoimi_seek_point* points,
+                                            const size_t* point_firsts) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || !interval_rows || !points || !point_firsts ||
+        n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    if (mode != QOIMI_RESIZE_PLAIN && mode != QOIMI_RESIZE_ALPHA_WEIGHTED) return fail(QOIMI_E_ARG, "mode must be QOIMI_RESIZE_PLAIN or QOIMI_RESIZE_ALPHA_WEIGHTED");
+    const size_t n = (size_t)n_items;
+    CheckedItems ok;
+    if (const int rc = check_items("item", sizes, descs, n_images, channels, items, n, d_out, out_offsets, resize_item_wrong, resize_bytes, ok)) return rc;
+    BandedCall b;
+    if (const int rc = stage_bands(c, d_streams, stream_offsets, sizes, descs, n_images, ok.rows, item_tops(items, n, n_images), interval_rows, points, point_firsts, stream, b)) return rc;
+    const std::vector<qoimi_resize> rs = rebase_items(items, n, b);
+    return qoimi_decode_resized(c, c->band_arena.base, b.at.data(), b.sz.data(), b.ds.data(), (int)b.sz.size(), channels, rs.data(), n_items, mode, d_out, out_offsets, staging_bytes, stream);
+}
+
+// ... and qoimi_pixel_stats (`first` is a pixel's value, not its place: the result is the plain call's).
+extern "C" int qoimi_pixel_stats_indexed(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                         int n_images, const qoimi_crop* regions, int n_regions, qoimi_pixel_stat* stats_out, unsigned* d_hist,
+                                         size_t staging_bytes, void* stream, const unsigned* interval_rows, const qoimi_seek_point* points,
+                                         const size_t* point_firsts) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves stats_out as it was)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !regions || !stats_out || !interval_rows || !points || !point_firsts ||
+        n_images <= 0 || n_regions <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    const size_t n = (size_t)n_regions;
+    CheckedItems ok;
+    if (const int rc = check_refs("region", sizes, descs, n_images, 4, regions, n, crop_rect_wrong,
+                                  [](size_t, const qoimi_crop*, unsigned) { return (int)QOIMI_OK; }, ok)) return rc;
+    BandedCall b;
+    if (const int rc = stage_bands(c, d_streams, stream_offsets, sizes, descs, n_images, ok.rows, item_tops(regions, n, n_images), interval_rows, points, point_firsts, stream, b)) return rc;
+    const std::vector<qoimi_crop> rs = rebase_items(regions, n, b);
+    return qoimi_pixel_stats(c, c->band_arena.base, b.at.data(), b.sz.data(), b.ds.data(), (int)b.sz.size(), rs.data(), n_regions, stats_out, d_hist, staging_bytes, stream);
 }

@@ -18,6 +18,12 @@
 //   seek_carry       A wavefront per image, a lane per slot: walks the image's intervals and carries "the last position that wrote slot s"
 //                    forward; at every point it reads the pixels at those positions - the table - and pixel P - 1, joins what seek_locate
 //                    found and writes the point's 272 bytes.
+//   seekpx_last      seek_last over the CALLER'S pixels (qoimi_seek_index_from_pixels): 3 or 4 bytes per pixel, tightly packed at any byte
+//                    address.  The same tiles, table and maxima; a lane takes four CONSECUTIVE pixels of its tile - 12 or 16 bytes as the
+//                    three to five aligned dwords that hold them, turned with v_alignbyte (qoi_seekpx_core.h: seekpx_fetch; never a dword
+//                    that holds no byte of the lane's pixels) - hashes them with alpha 255 where the image has none and compares each with
+//                    its right neighbour: the next of its own, or the first of the lane to the right.  One launch for all images of a call.
+//   seekpx_carry     seek_carry with its reads of single pixels through the same fetch (one dword or two).
 //   band_assemble    Work is cut over the OUTPUT in aligned 16-byte words, as crop_gather cuts it: consecutive lanes take consecutive words
 //                    of one band stream, a word wholly inside the tail is its 16 source bytes - at any alignment: the aligned dwords that
 //                    hold them, turned with v_alignbyte - and one 16-byte store; the words of the head and the pad run and the words at a
@@ -25,6 +31,7 @@
 //                    stream's own bytes.  Never a word that would have to be read first; not one byte beside a band stream is written.
 #include "qoi_dev.h"
 #include "qoi_seek_core.h"
+#include "qoi_seekpx_core.h"
 
 namespace qoimi {
 
@@ -155,6 +162,52 @@ __global__ __launch_bounds__(256) void seek_carry(const uint8_t* __restrict__ st
     }
 }
 
+struct PxMem {       // an aligned dword of the caller's pixel buffer
+    __device__ __forceinline__ uint32_t load(u64 a) const { return *reinterpret_cast<const uint32_t*>(a); }
+};
+
+__global__ __launch_bounds__(kSeekPxThreads) void seekpx_last(const uint8_t* __restrict__ pixels, const SeekPxImage* __restrict__ tab, uint32_t m, uint32_t tiles,
+                                                    uint32_t* __restrict__ last) {
+    __shared__ uint32_t s_last[64];
+    const uint32_t tid = threadIdx.x;
+    const PxMem mem;
+    walk_tiles(tab, m, tiles, [&](const SeekPxImage& e, uint32_t tile) {
+        const uint32_t iv = tile / e.tpi, sub = tile - iv * e.tpi;
+        const uint32_t p0 = iv * e.ipx;                                  // (an image holds fewer than 400 000 000 pixels)
+        uint32_t i, n;
+        seekpx_lane_span(sub, tid, e.ipx, i, n);
+        if (tid < 64u) s_last[tid] = 0u;
+        __syncthreads();
+        uint32_t px[kSeekPxLane];
+        seekpx_fetch(mem, (u64)reinterpret_cast<uintptr_t>(pixels) + e.src_off + (u64)(p0 + i) * e.ch, n, e.ch, px);
+        const uint32_t next = __shfl_down(px[0], 1u);
+        seekpx_lane_marks(px, n, next, seekpx_next_ok(tid, i, e.ipx), p0 + i, [&](uint32_t slot, uint32_t pos1) { atomicMax(&s_last[slot], pos1); });
+        __syncthreads();
+        if (tid < 64u && s_last[tid] != 0u) atomicMax(&last[(size_t)(e.point_base + iv) * 64u + tid], s_last[tid]);
+        __syncthreads();                                                 // s_last is zeroed again by the next tile
+    });
+}
+
+__global__ __launch_bounds__(256) void seekpx_carry(const uint8_t* __restrict__ pixels, const SeekPxImage* __restrict__ tab, uint32_t m,
+                                                     const uint32_t* __restrict__ last, const SeekLoc* __restrict__ loc, SeekPoint* __restrict__ points) {
+    const uint32_t lane = lane_id(), i = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (i >= m) return;
+    const SeekPxImage E = tab[i];
+    const PxMem mem;
+    const u64 base = (u64)reinterpret_cast<uintptr_t>(pixels) + E.src_off;
+    uint32_t cur = 0;                                                    // position + 1 of the last pixel so far whose slot is `lane`
+    for (uint32_t j = 0; j < E.np; ++j) {
+        const uint32_t v = last[(size_t)(E.point_base + j) * 64u + lane];
+        cur = v != 0u ? v : cur;
+        SeekPoint* o = points + E.point_base + j;
+        o->table[lane] = cur != 0u ? seekpx_one(mem, base + (u64)(cur - 1u) * E.ch, E.ch) : 0u;
+        if (lane == 0u) {
+            const SeekLoc L = loc[E.point_base + j];
+            o->byte_off = L.byte_off; o->skip = L.skip; o->prev = seekpx_one(mem, base + ((u64)(j + 1u) * E.ipx - 1u) * E.ch, E.ch); o->reserved = 0u;
+        }
+    }
+}
+
 typedef uint32_t seek_u32x4 __attribute__((ext_vector_type(4)));
 
 struct BandMem {
@@ -200,6 +253,12 @@ void launch_seek_tables(const uint8_t* stage, const SeekImage* tab, uint32_t m, 
                         uint32_t grid, hipStream_t st) {
     hipLaunchKernelGGL(seek_last, dim3(grid), dim3(256), 0, st, stage, tab, m, tiles, last);
     hipLaunchKernelGGL(seek_carry, dim3((m + 3u) / 4u), dim3(256), 0, st, stage, tab, m, (const uint32_t*)last, loc, points);
+}
+
+void launch_seek_tables_px(const uint8_t* pixels, const SeekPxImage* tab, uint32_t m, uint32_t tiles, uint32_t* last, const SeekLoc* loc, SeekPoint* points,
+                           uint32_t grid, hipStream_t st) {
+    hipLaunchKernelGGL(seekpx_last, dim3(grid), dim3(kSeekPxThreads), 0, st, pixels, tab, m, tiles, last);
+    hipLaunchKernelGGL(seekpx_carry, dim3((m + 3u) / 4u), dim3(256), 0, st, pixels, tab, m, (const uint32_t*)last, loc, points);
 }
 
 void launch_band_assemble(const uint8_t* streams, const BandEntry* tab, uint32_t m, uint32_t tiles, const uint8_t* heads, uint8_t* out, uint32_t grid,

@@ -1,5 +1,6 @@
-"""The row seek index as pure functions - the normative statement of ``qoimi_build_seek_index``, ``qoimi_band_plan``,
-``qoimi_make_band_streams`` and of the bands ``qoimi_decode_crops_indexed`` decodes (plain numpy / integer arithmetic, no GPU).
+"""The row seek index as pure functions - the normative statement of ``qoimi_build_seek_index``, ``qoimi_seek_index_from_pixels``,
+``qoimi_band_plan``, ``qoimi_make_band_streams`` and of the bands ``qoimi_decode_crops_indexed``, ``qoimi_decode_resized_indexed`` and
+``qoimi_pixel_stats_indexed`` decode (plain numpy / integer arithmetic, no GPU).
 
 A QOI decoder's whole state at a row boundary is small: the previous pixel, the 64-entry colour table, a byte position and what is left of
 a run.  A SEEK POINT writes it down; a BAND STREAM spells it as QOI chunks in front of the original stream's bytes from there on, so that
@@ -116,6 +117,19 @@ def points(data: bytes, w: int, h: int, K: int, D, size: Optional[int] = None) -
         out[k]["prev"] = words[P - 1]
         out[k]["table"] = table
     return out
+
+
+def points_from_pixels(data: bytes, w: int, h: int, K: int, pixels, channels: int, size: Optional[int] = None) -> np.ndarray:
+    """The normative statement of ``qoimi_seek_index_from_pixels``: ``points(data, w, h, K, D, size)`` with D the caller's `pixels` - uint8 of
+    h * w * channels values in any shape, channels 3 or 4 - at 4 channels, alpha 255 where channels == 3.  ``byte_off`` and ``skip`` are the walk
+    of the STREAM, ``prev`` and ``table`` come from the PIXELS; that the stream decodes to them is not looked at.  Whenever it does - every
+    stream an encoder wrote from them - this is ``points`` over the stream's decode."""
+    if channels not in (3, 4):
+        raise ValueError("points_from_pixels: channels is 3 or 4")
+    px = np.asarray(pixels, dtype=np.uint8).reshape(h * w, channels)
+    D = np.full((h * w, 4), 255, dtype=np.uint8)
+    D[:, :channels] = px
+    return points(data, w, h, K, D, size)
 
 
 def _loads(point) -> List[int]:
