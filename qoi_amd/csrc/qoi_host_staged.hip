@@ -1,6 +1,7 @@
 // qoi_host_staged.hip — the calls of the C-ABI shim that decode a pack's images into bounded staging and run one table-driven kernel over
 // each sub-batch: qoimi_verify_images (and qoimi_compare_images, whose kernels it runs), qoimi_decode_thumbnails, qoimi_decode_crops,
-// qoimi_decode_resized, qoimi_pixel_stats, and the row seek index (qoimi_build_seek_index, qoimi_seek_index_from_pixels - which stages nothing -,
+// qoimi_decode_resized, qoimi_pixel_stats, and the row seek index (qoimi_build_seek_index, qoimi_seek_index_from_pixels - which stages nothing;
+// one kernel pair, seekpx_last + seekpx_carry, serves both builds: over the staging arena and over the caller's pixels -,
 // qoimi_make_band_streams, qoimi_decode_crops_indexed, qoimi_decode_resized_indexed, qoimi_pixel_stats_indexed).
 #include "qoi_ctx.h"
 #include "qoi_thumb_core.h"
@@ -547,7 +548,7 @@ extern "C" int qoimi_pixel_stats(qoimi_ctx* c, const void* d_streams, const size
 // the row seek index (qoi_seek.hip; qoi_amd/seekindex.py states all of it)
 // ------------------------------------------------------------------------------------
 static_assert(sizeof(qoimi_seek_point) == sizeof(SeekPoint) && offsetof(qoimi_seek_point, skip) == 4 && offsetof(qoimi_seek_point, prev) == 8 &&
-              offsetof(qoimi_seek_point, table) == 16, "qoimi_seek_point is what seek_carry writes");
+              offsetof(qoimi_seek_point, table) == 16, "qoimi_seek_point is what seekpx_carry writes");
 static_assert(sizeof(qoimi_band) == 16 && sizeof(qoimi_band_info) == 24 && offsetof(qoimi_band_info, desc) == 8 && offsetof(qoimi_band_info, pad_rows) == 20,
               "qoimi_band / qoimi_band_info layout");
 
@@ -557,8 +558,17 @@ extern "C" int qoimi_seek_points(const qoi_desc* desc, unsigned interval_rows) {
 }
 
 // What the two builds of an index share.  SeekCount: what seek_count makes of a call's images - np[i] points of image i from point_base[i]
-// on, refs: the images that have a point, ascending; total points; tiles of kSeekTilePx pixels, blocks and pieces of the inspect passes over refs.
-struct SeekCount { std::vector<uint32_t> np, point_base; std::vector<size_t> refs; uint64_t total = 0, tiles = 0; size_t nb = 0, npieces = 0; };
+// on, refs: the images that have a point, ascending, ref_tiles: the tiles of kSeekTilePx pixels each of them takes; total points; tiles of all
+// of refs, blocks and pieces of the inspect passes over refs.
+struct SeekCount { std::vector<uint32_t> np, point_base; std::vector<size_t> refs; std::vector<uint64_t> ref_tiles; uint64_t total = 0, tiles = 0; size_t nb = 0, npieces = 0; };
+
+// Fills the entry of an image with np >= 1 points whose pixels stand at `off` of a pixel buffer, ch bytes each, and returns the tiles it takes.
+// (interval_rows * w is below 400 000 000: a point lies inside the image.)
+static uint32_t seekpx_entry(SeekPxImage& e, size_t off, uint32_t ch, uint32_t interval_rows, uint32_t w, uint32_t np, uint32_t point_base, uint32_t first_tile) {
+    e.src_off = (u64)off; e.ipx = interval_rows * w; e.np = np; e.tpi = seek_interval_tiles(e.ipx);
+    e.first_tile = first_tile; e.point_base = point_base; e.ch = ch;
+    return np * e.tpi;
+}
 
 // The checks both builds make per image, in the order that decides which message a call with several faults gets; more(i): nullptr, or what
 // else is wrong with image i.
@@ -576,8 +586,8 @@ static int seek_count(const int* sizes, const qoi_desc* descs, size_t n, const u
         k.total += (uint64_t)cnt;
         if (cnt == 0) continue;
         k.refs.push_back(i);
-        const uint64_t ipx = (uint64_t)interval_rows[i] * descs[i].width;
-        k.tiles += (uint64_t)cnt * ((ipx + kSeekTilePx - 1u) / kSeekTilePx);
+        k.ref_tiles.push_back((uint64_t)cnt * seek_interval_tiles(interval_rows[i] * descs[i].width));   // (a point lies inside the image: 32 bits)
+        k.tiles += k.ref_tiles.back();
         const size_t body = (size_t)(sizes[i] - kMin);
         k.nb += (body + kInsBlock - 1u) / kInsBlock;
         k.npieces += (body + kInsPiece - 1u) / kInsPiece;
@@ -646,8 +656,8 @@ static int locate_points(qoimi_ctx* c, const void* d_streams, const size_t* stre
     return QOIMI_OK;
 }
 
-// locate_points (byte_off, skip); then run_staged over the images that have a point at their full height with seek_last + seek_carry per
-// sub-batch (prev, table), which write the points behind the image table; one copy back.
+// locate_points (byte_off, skip); then run_staged over the images that have a point at their full height with seekpx_last + seekpx_carry
+// over the staging arena per sub-batch (prev, table), which write the points behind the image table; one copy back.
 extern "C" int qoimi_build_seek_index(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                       int n_images, const unsigned* interval_rows, qoimi_seek_point* points_out, size_t staging_bytes, void* stream) {
     // (everything is looked at before the context is: a rejected call launches nothing and leaves points_out as it was)
@@ -661,15 +671,8 @@ extern "C" int qoimi_build_seek_index(qoimi_ctx* c, const void* d_streams, const
     for (size_t i = 0; i < n; ++i) rows[i] = np[i] != 0u ? descs[i].height : 0u;
     const RowsPlan plan = plan_rows(descs, n_images, rows, staging_bytes);   // (plan.refs is k.refs: the images that have a point)
     const size_t R = plan.refs.size();
-    std::vector<uint32_t> image_of(R);
-    std::vector<uint64_t> tiles_of(R);
-    for (size_t r = 0; r < R; ++r) {
-        const size_t i = (size_t)plan.refs[r];
-        image_of[r] = (uint32_t)i;
-        const uint64_t ipx = (uint64_t)interval_rows[i] * descs[i].width;
-        tiles_of[r] = (uint64_t)np[i] * ((ipx + kSeekTilePx - 1u) / kSeekTilePx);
-    }
-    const ItemPlan items = plan_items(image_of, plan.ref_of, plan.firsts, tiles_of);   // (entry r is the r-th image that has a point)
+    const std::vector<uint32_t> image_of(plan.refs.begin(), plan.refs.end());
+    const ItemPlan items = plan_items(image_of, plan.ref_of, plan.firsts, k.ref_tiles);   // (entry r is the r-th image that has a point)
     if (items.overflow) return fail(QOIMI_E_ARG, "more than 2^31 tiles of pixels in one sub-batch");
     c->seek_stats[0] = 0;
     if (total == 0u) return QOIMI_OK;
@@ -681,17 +684,15 @@ extern "C" int qoimi_build_seek_index(qoimi_ctx* c, const void* d_streams, const
         if (c->timer.on) timer_collect(c);
     }
     SeekLoc* d_loc = at.d_loc; uint32_t* d_last = at.d_last;
-    const size_t res_at = staged_extra_at(R, sizeof(SeekImage));
+    const size_t res_at = staged_extra_at(R, sizeof(SeekPxImage));
     long long stats[4];
-    const int rc = run_staged<SeekImage>(c, stats, (long long)R, "seek_last", d_streams, stream_offsets, sizes, descs, plan, rows, items,
-        [&](SeekImage& t, size_t e) {
+    const int rc = run_staged<SeekPxImage>(c, stats, (long long)R, "seekpx_last", d_streams, stream_offsets, sizes, descs, plan, rows, items,
+        [&](SeekPxImage& t, size_t e) {
             const size_t r = items.by_ref[e], i = (size_t)plan.refs[r];
-            t.src_off = (u64)plan.at[r]; t.w = descs[i].width; t.ipx = interval_rows[i] * descs[i].width; t.np = np[i];
-            t.tpi = (t.ipx + kSeekTilePx - 1u) / kSeekTilePx; t.first_tile = items.first_tile[e]; t.point_base = point_base[i];
-            t.reserved[0] = 0u; t.reserved[1] = 0u;
+            (void)seekpx_entry(t, plan.at[r], 4u, interval_rows[i], descs[i].width, np[i], point_base[i], items.first_tile[e]);
         },
-        [&](const SeekImage* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
-            launch_seek_tables((const uint8_t*)c->ver_stage.base, tab, m, tiles, d_last, d_loc, (SeekPoint*)((uint8_t*)c->cmp_ws.base + res_at), grid, st);
+        [&](const SeekPxImage* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            launch_seek_tables_px((const uint8_t*)c->ver_stage.base, tab, m, tiles, d_last, d_loc, (SeekPoint*)((uint8_t*)c->cmp_ws.base + res_at), grid, st);
         }, stream, (size_t)total * sizeof(SeekPoint),
         [&](uint8_t* h_points, hipStream_t) { memset(h_points, 0, (size_t)total * sizeof(SeekPoint)); return (int)QOIMI_OK; });
     c->seek_stats[0] = stats[0];
@@ -727,10 +728,7 @@ extern "C" int qoimi_seek_index_from_pixels(qoimi_ctx* c, const void* d_pixels, 
             SeekPxImage* h_img = (SeekPxImage*)bytes;
             for (size_t r = 0; r < R; ++r) {
                 const size_t i = k.refs[r];
-                SeekPxImage& e = h_img[r];
-                e.src_off = (u64)pixel_offsets[i]; e.ipx = interval_rows[i] * descs[i].width; e.np = k.np[i];
-                e.tpi = (e.ipx + kSeekTilePx - 1u) / kSeekTilePx; e.first_tile = t; e.point_base = k.point_base[i]; e.ch = descs[i].channels;
-                t += e.np * e.tpi;
+                t += seekpx_entry(h_img[r], pixel_offsets[i], descs[i].channels, interval_rows[i], descs[i].width, k.np[i], k.point_base[i], t);
             }
         }, true, stream, at)) return rc;
     const uint32_t most = (uint32_t)c->n_cus * 8u;

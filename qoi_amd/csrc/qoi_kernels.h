@@ -324,23 +324,19 @@ void launch_stats(const uint8_t* stage, const StatsEntry* tab, uint32_t m, uint3
 struct SeekPoint;                                       // = qoimi_seek_point (qoi_seek_core.h)
 struct SeekJob { uint32_t stream, point, P, reserved; };   // seek point `point` of the call: pixel P of stream `stream` of the inspect tables
 struct SeekLoc { uint32_t byte_off, skip; };            // what seek_locate finds for a job
-// an image with np >= 1 seek points, staged at src_off as rows of w pixels of 4 bytes: ipx = interval_rows * w pixels per interval, tpi tiles
-// of kSeekTilePx pixels per interval, np * tpi tiles; point_base: its first point among the call's
-struct SeekImage { u64 src_off; uint32_t w, ipx, np, tpi, first_tile, point_base, reserved[2]; };
 // a band stream of B bytes at dst_off: head_len bytes at heads + head_at, run_full bytes 0xFD, the byte run_last (0: none), the tail from streams + src_off
 struct BandEntry { u64 src_off, dst_off; uint32_t B, head_len, run_full, run_last, first_tile, head_at, reserved[2]; };
-// an image with np >= 1 seek points in the CALLER'S pixel buffer: ch = 3 or 4 bytes per pixel, tightly packed at pixels + src_off (any byte
-// offset); the other fields as in SeekImage (qoimi_seek_index_from_pixels; the fetch: qoi_seekpx_core.h)
+// an image with np >= 1 seek points in a pixel buffer: the caller's, or the staging arena at 4 bytes per pixel.  ch = 3 or 4 bytes per pixel,
+// tightly packed at pixels + src_off (any byte offset); ipx = interval_rows * width pixels per interval, tpi tiles of kSeekTilePx pixels per
+// interval, np * tpi tiles; point_base: its first point among the call's (both builds of an index; the fetch: qoi_seekpx_core.h)
 struct SeekPxImage { u64 src_off; uint32_t ipx, np, tpi, first_tile, point_base, ch; };
-static_assert(sizeof(SeekJob) == 16 && sizeof(SeekLoc) == 8 && sizeof(SeekImage) == 40 && sizeof(BandEntry) == 48 && sizeof(SeekPxImage) == 32, "table layouts");
+static_assert(sizeof(SeekJob) == 16 && sizeof(SeekLoc) == 8 && sizeof(BandEntry) == 48 && sizeof(SeekPxImage) == 32, "table layouts");
 
 // Behind launch_inspect over the same tables: blk_px[n_blocks] receives the exclusive scan of the blocks' pixels per stream, loc[job.point] every job's place.
 void launch_seek_locate(const uint8_t* streams, const InsStream* tab, uint32_t n_streams, const InsBlock* blocks, const InsPartial* partial,
                         const uint8_t* entry, const uint16_t* piece_map, u64* blk_px, const SeekJob* jobs, uint32_t n_jobs, SeekLoc* loc, hipStream_t st);
-// last: a zeroed uint32[64] per point of the call; points: the call's points on the device.  grid: workgroups of seek_last, at most `tiles`.
-void launch_seek_tables(const uint8_t* stage, const SeekImage* tab, uint32_t m, uint32_t tiles, uint32_t* last, const SeekLoc* loc, SeekPoint* points,
-                        uint32_t grid, hipStream_t st);
-// ... over the m images of a call at once, whose pixels the caller holds: seekpx_last + seekpx_carry
+// seekpx_last + seekpx_carry over the m images of a table in a pixel buffer: the caller's, or the staging arena at 4 bytes per pixel.
+// last: a zeroed uint32[64] per point of the call; points: the call's points on the device.  grid: workgroups of seekpx_last, at most `tiles`.
 void launch_seek_tables_px(const uint8_t* pixels, const SeekPxImage* tab, uint32_t m, uint32_t tiles, uint32_t* last, const SeekLoc* loc, SeekPoint* points,
                            uint32_t grid, hipStream_t st);
 void launch_band_assemble(const uint8_t* streams, const BandEntry* tab, uint32_t m, uint32_t tiles, const uint8_t* heads, uint8_t* out, uint32_t grid,

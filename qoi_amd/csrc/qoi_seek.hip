@@ -1,5 +1,5 @@
 // qoi_seek.hip — the row seek index: where the chunk walk of a stream stands at a pixel (seek_block_scan, seek_locate), the colour table and
-// the previous pixel there (seek_last, seek_carry), and band streams written from an index (band_assemble).  gfx950, wave64.  The host side:
+// the previous pixel there (seekpx_last, seekpx_carry), and band streams written from an index (band_assemble).  gfx950, wave64.  The host side:
 // qoi_host_staged.hip (qoi_kernels.h holds the tables and declares the launchers; qoi_seek_core.h the arithmetic; qoi_amd/seekindex.py the
 // normative statement).
 //
@@ -11,19 +11,18 @@
 //                    pixels of its chunks (a chunk belongs to the piece its tag byte is in), the counts are scanned over the wavefront and
 //                    carried from tile to tile, and the one lane whose piece holds P walks its piece again, up to the chunk.  No lane
 //                    holds P: the walk ran out in front of P (the block is the stream's last), byte_off = size - 8, skip = 0.
-//   seek_last        Over the staged 4-byte pixels of a sub-batch's images: tiles of kSeekTilePx pixels of ONE interval (qoi_dev.h:
-//                    walk_tiles); every lane hashes its pixels and leaves position + 1 with an LDS atomic maximum in the slot's word - a pixel
-//                    that equals its right neighbour is left out, the neighbour's position is larger - then 64 lanes fold the tile's words
-//                    into the interval's 64 words in global memory, atomic maxima as well.  Positions are below 400 000 000: 32 bits.
-//   seek_carry       A wavefront per image, a lane per slot: walks the image's intervals and carries "the last position that wrote slot s"
-//                    forward; at every point it reads the pixels at those positions - the table - and pixel P - 1, joins what seek_locate
-//                    found and writes the point's 272 bytes.
-//   seekpx_last      seek_last over the CALLER'S pixels (qoimi_seek_index_from_pixels): 3 or 4 bytes per pixel, tightly packed at any byte
-//                    address.  The same tiles, table and maxima; a lane takes four CONSECUTIVE pixels of its tile - 12 or 16 bytes as the
-//                    three to five aligned dwords that hold them, turned with v_alignbyte (qoi_seekpx_core.h: seekpx_fetch; never a dword
-//                    that holds no byte of the lane's pixels) - hashes them with alpha 255 where the image has none and compares each with
-//                    its right neighbour: the next of its own, or the first of the lane to the right.  One launch for all images of a call.
-//   seekpx_carry     seek_carry with its reads of single pixels through the same fetch (one dword or two).
+//   seekpx_last      Over a pixel buffer - the caller's (qoimi_seek_index_from_pixels: 3 or 4 bytes per pixel, tightly packed at any byte
+//                    address, one launch for all images of a call) or the staging arena (qoimi_build_seek_index: 4 bytes per pixel in
+//                    256-byte-aligned slots, one launch per sub-batch): tiles of kSeekTilePx pixels of ONE interval (qoi_dev.h: walk_tiles);
+//                    a lane takes four CONSECUTIVE pixels of its tile - 12 or 16 bytes as the three to five aligned dwords that hold them,
+//                    turned with v_alignbyte (qoi_seekpx_core.h: seekpx_fetch; never a dword that holds no byte of the lane's pixels) -
+//                    hashes them with alpha 255 where the image has none and leaves position + 1 with an LDS atomic maximum in the slot's
+//                    word - a pixel that equals its right neighbour (the next of its own, or the first of the lane to the right) is left
+//                    out, the neighbour's position is larger - then 64 lanes fold the tile's words into the interval's 64 words in global
+//                    memory, atomic maxima as well.  Positions are below 400 000 000: 32 bits.
+//   seekpx_carry     A wavefront per image, a lane per slot: walks the image's intervals and carries "the last position that wrote slot s"
+//                    forward; at every point it reads the pixels at those positions - the table - and pixel P - 1 through the same fetch
+//                    (one dword or two), joins what seek_locate found and writes the point's 272 bytes.
 //   band_assemble    Work is cut over the OUTPUT in aligned 16-byte words, as crop_gather cuts it: consecutive lanes take consecutive words
 //                    of one band stream, a word wholly inside the tail is its 16 source bytes - at any alignment: the aligned dwords that
 //                    hold them, turned with v_alignbyte - and one 16-byte store; the words of the head and the pad run and the words at a
@@ -119,50 +118,7 @@ __global__ __launch_bounds__(256) void seek_locate(const uint8_t* __restrict__ s
     }
 }
 
-__global__ __launch_bounds__(256) void seek_last(const uint8_t* __restrict__ stage, const SeekImage* __restrict__ tab, uint32_t m, uint32_t tiles,
-                                                  uint32_t* __restrict__ last) {
-    __shared__ uint32_t s_last[64];
-    const uint32_t tid = threadIdx.x, lane = lane_id();
-    walk_tiles(tab, m, tiles, [&](const SeekImage& e, uint32_t tile) {
-        const uint32_t iv = tile / e.tpi, sub = tile - iv * e.tpi;
-        const uint32_t* px = reinterpret_cast<const uint32_t*>(stage + e.src_off);
-        const uint32_t p0 = iv * e.ipx;                                  // (an image holds fewer than 400 000 000 pixels)
-        if (tid < 64u) s_last[tid] = 0u;
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < kSeekTilePx / 256u; ++k) {
-            const uint32_t i = sub * kSeekTilePx + k * 256u + tid;
-            const uint32_t v = i < e.ipx ? px[(size_t)p0 + i] : 0u;
-            const uint32_t right = __shfl_down(v, 1u);
-            const bool repeated = lane < 63u && i + 1u < e.ipx && right == v;
-            if (i < e.ipx && !repeated) atomicMax(&s_last[slot_of(v)], p0 + i + 1u);
-        }
-        __syncthreads();
-        if (tid < 64u && s_last[tid] != 0u) atomicMax(&last[(size_t)(e.point_base + iv) * 64u + tid], s_last[tid]);
-        __syncthreads();                                                 // s_last is zeroed again by the next tile
-    });
-}
-
-__global__ __launch_bounds__(256) void seek_carry(const uint8_t* __restrict__ stage, const SeekImage* __restrict__ tab, uint32_t m,
-                                                   const uint32_t* __restrict__ last, const SeekLoc* __restrict__ loc, SeekPoint* __restrict__ points) {
-    const uint32_t lane = lane_id(), i = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (i >= m) return;
-    const SeekImage E = tab[i];
-    const uint32_t* px = reinterpret_cast<const uint32_t*>(stage + E.src_off);
-    uint32_t cur = 0;                                                    // position + 1 of the last pixel so far whose slot is `lane`
-    for (uint32_t j = 0; j < E.np; ++j) {
-        const uint32_t v = last[(size_t)(E.point_base + j) * 64u + lane];
-        cur = v != 0u ? v : cur;
-        SeekPoint* o = points + E.point_base + j;
-        o->table[lane] = cur != 0u ? px[cur - 1u] : 0u;
-        if (lane == 0u) {
-            const SeekLoc L = loc[E.point_base + j];
-            o->byte_off = L.byte_off; o->skip = L.skip; o->prev = px[(size_t)(j + 1u) * E.ipx - 1u]; o->reserved = 0u;
-        }
-    }
-}
-
-struct PxMem {       // an aligned dword of the caller's pixel buffer
+struct PxMem {       // an aligned dword of the pixel buffer
     __device__ __forceinline__ uint32_t load(u64 a) const { return *reinterpret_cast<const uint32_t*>(a); }
 };
 
@@ -247,12 +203,6 @@ void launch_seek_locate(const uint8_t* streams, const InsStream* tab, uint32_t n
                         const uint8_t* entry, const uint16_t* piece_map, u64* blk_px, const SeekJob* jobs, uint32_t n_jobs, SeekLoc* loc, hipStream_t st) {
     hipLaunchKernelGGL(seek_block_scan, dim3((n_streams + 3u) / 4u), dim3(256), 0, st, tab, n_streams, partial, blk_px);
     hipLaunchKernelGGL(seek_locate, dim3((n_jobs + 3u) / 4u), dim3(256), 0, st, streams, tab, blocks, (const u64*)blk_px, entry, piece_map, jobs, n_jobs, loc);
-}
-
-void launch_seek_tables(const uint8_t* stage, const SeekImage* tab, uint32_t m, uint32_t tiles, uint32_t* last, const SeekLoc* loc, SeekPoint* points,
-                        uint32_t grid, hipStream_t st) {
-    hipLaunchKernelGGL(seek_last, dim3(grid), dim3(256), 0, st, stage, tab, m, tiles, last);
-    hipLaunchKernelGGL(seek_carry, dim3((m + 3u) / 4u), dim3(256), 0, st, stage, tab, m, (const uint32_t*)last, loc, points);
 }
 
 void launch_seek_tables_px(const uint8_t* pixels, const SeekPxImage* tab, uint32_t m, uint32_t tiles, uint32_t* last, const SeekLoc* loc, SeekPoint* points,

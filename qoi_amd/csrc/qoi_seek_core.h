@@ -28,7 +28,7 @@ constexpr uint32_t kSeekMaxLoads = 64;            // a point of a stream has tab
 constexpr uint32_t kSeekHeadMost = 14u + 5u * kSeekMaxLoads;
 constexpr uint32_t kSeekHeadSlot = 336;          // bytes of a head in the table band_assemble reads (a multiple of 16)
 constexpr uint32_t kSeekThreads = 256;           // items of a tile: the workgroup of band_assemble
-constexpr uint32_t kSeekTilePx = 1024;           // pixels of a tile of seek_last: four per lane
+constexpr uint32_t kSeekTilePx = 1024;           // pixels of a tile of seekpx_last: four per lane
 constexpr uint32_t kSeekNoPos = 64;              // seek_piece_walk: the count never passed the target
 
 struct SeekPoint { uint32_t byte_off, skip, prev, reserved, table[64]; };      // = qoimi_seek_point
@@ -43,6 +43,9 @@ QOIMI_SEEK_HD int64_t seek_point_count(uint32_t w, uint32_t h, uint32_t K) {
     if (K == 0u || (uint64_t)K * w < kSeekMinIntervalPx) return -1;
     return (int64_t)(((uint64_t)h + K - 1u) / K) - 1;
 }
+
+// tiles of kSeekTilePx pixels per interval of ipx pixels (ipx below 400 000 000: an interval in front of a point lies inside the image)
+QOIMI_SEEK_HD uint32_t seek_interval_tiles(uint32_t ipx) { return (ipx + kSeekTilePx - 1u) / kSeekTilePx; }
 
 // The walk of one piece - plen <= 64 bytes as 16 dwords - that is entered with its first chunk at byte p (0..4: the chunk in front reaches
 // that far in).  A chunk's pixels belong to the piece its tag byte is in.  Returns the pixels of the piece's chunks; pos and before: the byte

@@ -1,5 +1,6 @@
-// qoi_seekpx_core.h — the pixel fetch of qoimi_seek_index_from_pixels: which aligned dwords a lane reads for its pixels of the caller's buffer,
-// how they unpack, and which of a lane's pixels leave their position in the tile's table.
+// qoi_seekpx_core.h — the pixel fetch of both builds of the seek index (seekpx_last, seekpx_carry): which aligned dwords a lane reads for its
+// pixels of a pixel buffer - the caller's (qoimi_seek_index_from_pixels), or the staging arena at 4 bytes per pixel (qoimi_build_seek_index:
+// the ch == 4, 256-byte-aligned case) -, how they unpack, and which of a lane's pixels leave their position in the tile's table.
 //
 // The definition (normative; qoi_amd/seekindex.py: points_from_pixels).  An image of `ch` = 3 or 4 bytes per pixel stands tightly packed at ANY
 // byte address; pixel i is the bytes [base + i * ch, + ch) as r | g << 8 | b << 16 | a << 24, a = 255 where ch == 3.  A lane of seekpx_last takes
