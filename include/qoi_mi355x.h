@@ -519,6 +519,49 @@ size_t qoimi_resize_size(const qoi_desc *desc, const qoimi_resize *item, int cha
  * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] images decoded (the referenced ones). */
 void qoimi_resize_stats(qoimi_ctx *ctx, long long out[4]);
 
+/* qoimi_decode_resized with an antialiased bilinear (triangle) filter in place of the area filter: what torchvision Resize, PIL BILINEAR and DALI
+ * resample with by default.  The area filter is the right one for reducing; enlarging with it is nearest-neighbour with soft edges, so a
+ * random-resized-crop that takes a small part of an image to the sample size, or a tile requested past native zoom, comes out in blocks.  Items
+ * (qoimi_resize as it is), modes (QOIMI_RESIZE_PLAIN, QOIMI_RESIZE_ALPHA_WEIGHTED), flips, outputs, staging, plan and the "not one byte beside an
+ * output" contract are those of qoimi_decode_resized; only the weights differ.
+ * The result (normative; qoi_amd/bilinear.py: bilinear states it in Python): D, R, cw, rh, ow, oh, och as for qoimi_decode_resized; all arithmetic
+ * is integer, every division floors.  One axis, n_src source samples to n_out output samples, on a line of length 2 * n_src * n_out: source
+ * sample k has its centre at (2k + 1) * n_out, output sample X at (2X + 1) * n_src; rad = 2 * max(n_src, n_out) - one source pitch when
+ * enlarging, one output pitch when reducing; t(X, k) = max(0, rad - |(2X + 1) * n_src - (2k + 1) * n_out|) for 0 <= k < n_src;
+ * W(X) = sum over k of t(X, k), at least 1.  Samples outside the rectangle do not exist: the weights are renormalised by W(X), not clamped.
+ * tx, Wx come from (cw, ow), ty, Wy from (rh, oh).  Two axes, ONE rounding: D(X, Y) = Wx(X) * Wy(Y), N_c = sum over r, k of
+ * ty(Y, r) * tx(X, k) * R[r][k].c.
+ *   QOIMI_RESIZE_PLAIN           every channel of output pixel (X, Y) is (N_c + D/2) / D
+ *   QOIMI_RESIZE_ALPHA_WEIGHTED  where och == 4: A = N_a, output alpha is (A + D/2) / D; if A > 0, r, g and b are (sum ty * tx * c * a + A/2) / A,
+ *                                if A == 0 they are the PLAIN value.  With och == 3 this mode is PLAIN.
+ * Flips and layout as for qoimi_decode_resized (the tent is symmetric: this is the resampled mirrored rectangle); ow * oh * och bytes
+ * (qoimi_bilinear_size) at d_out + out_offsets[j].  With out_width x out_height equal to width x height there is a single sample of weight rad:
+ * the call is qoimi_decode_crops byte for byte.  A constant rectangle gives the constant at any size.  When enlarging at most 2 x 2 samples have
+ * a weight: the usual half-pixel-centre bilinear interpolation with replicated borders.  Against a float64 evaluation of the same filter
+ * (torch.nn.functional.interpolate, mode "bilinear", antialias=True, align_corners=False) a value differs by at most 1, and only where the
+ * float result lies at a rounding boundary.
+ * Limits: width <= 32 * out_width and height <= 32 * out_height, so an output pixel has at most 64 x 64 source pixels with a weight; and
+ * max(width, out_width) * max(height, out_height) < 2^30.  Then one weight ty * tx is below 2^32, D < 2^44, N_c < 2^52 and the alpha-weighted sums
+ * are below 2^60.
+ * Arguments, the plan (qoi_amd/bilinear.py: plan - that of qoimi_decode_crops over the items' rectangles), sub-batches and rejections are those
+ * of qoimi_decode_resized, with two differences: QOIMI_E_ARG for width > 32 * out_width or height > 32 * out_height, and for
+ * max(width, out_width) * max(height, out_height) >= 2^30.  Reported before anything is launched, the caller's buffers are untouched;
+ * qoimi_last_error names the cause.  SYNCHRONOUS: returns when every output is written.  The sub-batches count as decode calls of the context.
+ * One call at a time per context, as everywhere. */
+int qoimi_decode_bilinear(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                          const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                          const qoimi_resize *items /* host */, int n_items, int mode,
+                          void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream);
+
+/* out_width * out_height * channels - the bytes of the item's output - or 0 if desc is rejected, item is NULL, has a zero width or height in or
+ * out, leaves the image of desc, reduces by more than 32 in an axis, reaches the product limit of 2^30 or carries an unknown flag bit, or
+ * channels is not 3 / 4 (item->image is not looked at).  Pure host arithmetic: no context, no GPU. */
+size_t qoimi_bilinear_size(const qoi_desc *desc, const qoimi_resize *item, int channels);
+
+/* Of the context's last qoimi_decode_bilinear call: [0] sub-batches decoded, [1] launches of the filter kernel (it has no entry in
+ * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] images decoded (the referenced ones). */
+void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
+
 /* What is in the pixels of rectangles of a pack's images, without the caller ever owning the decoded images: a tile server learns which tiles
  * of a scan are blank (a constant tile need not be stored) and which are fully opaque (they can be re-encoded with 3 channels), a training
  * loader gets the per-channel sums its normalisation needs and can drop empty or single-colour samples.  The referenced streams are decoded as
@@ -722,6 +765,15 @@ int qoimi_decode_resized_indexed(qoimi_ctx *ctx, const void *d_streams, const si
                                  void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream,
                                  const unsigned *interval_rows /* host, n_images */, const qoimi_seek_point *points /* host */,
                                  const size_t *point_firsts /* host, n_images */);
+/* qoimi_decode_bilinear byte for byte, exactly as qoimi_decode_resized_indexed: band assembly over the items' SOURCE rectangles, then the plain
+ * call as it is with `image` renumbered and every y replaced by y - first_row + pad_rows.  The counters of qoimi_bilinear_stats are those of the
+ * inner call; qoimi_seek_stats [1..3] are set as qoimi_decode_crops_indexed sets them.  SYNCHRONOUS. */
+int qoimi_decode_bilinear_indexed(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                                  const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                                  const qoimi_resize *items /* host */, int n_items, int mode,
+                                  void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream,
+                                  const unsigned *interval_rows /* host, n_images */, const qoimi_seek_point *points /* host */,
+                                  const size_t *point_firsts /* host, n_images */);
 int qoimi_pixel_stats_indexed(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
                               const qoi_desc *descs /* host */, int n_images,
                               const qoimi_crop *regions /* host */, int n_regions,
@@ -732,7 +784,7 @@ int qoimi_pixel_stats_indexed(qoimi_ctx *ctx, const void *d_streams, const size_
                               const size_t *point_firsts /* host, n_images */);
 
 /* [0] sub-batches decoded by the context's last qoimi_build_seek_index (qoimi_seek_index_from_pixels: 0), [1] band streams assembled by its
- * last qoimi_make_band_streams or indexed call (qoimi_decode_crops_indexed, qoimi_decode_resized_indexed, qoimi_pixel_stats_indexed), [2] bytes of the band arena that call planned for (qoimi_make_band_streams: 0), [3] stream bytes it copied (the
+ * last qoimi_make_band_streams or indexed call (qoimi_decode_crops_indexed, qoimi_decode_resized_indexed, qoimi_decode_bilinear_indexed, qoimi_pixel_stats_indexed), [2] bytes of the band arena that call planned for (qoimi_make_band_streams: 0), [3] stream bytes it copied (the
  * tails).  The kernels have no entry in qoimi_kernel_name. */
 void qoimi_seek_stats(qoimi_ctx *ctx, long long out[4]);
 
@@ -752,7 +804,7 @@ int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
 /* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace (and the staging arena of
  * qoimi_encode_packed), [1] decode workspace
  * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images,
- * qoimi_decode_thumbnails, qoimi_decode_crops, qoimi_decode_resized, qoimi_pixel_stats and qoimi_build_seek_index, which share them, the tables of
+ * qoimi_decode_thumbnails, qoimi_decode_crops, qoimi_decode_resized, qoimi_decode_bilinear, qoimi_pixel_stats and qoimi_build_seek_index, which share them, the tables of
  * qoimi_build_seek_index and qoimi_seek_index_from_pixels and the band arena of the indexed calls),
  * [2] staging buffers of the host-pointer entry points (qoi_encode / qoi_decode of the calling thread's context). */
 void qoimi_workspace_bytes(qoimi_ctx *ctx, size_t out[3]);

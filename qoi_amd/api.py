@@ -45,6 +45,7 @@ EXPORTS = (
     "qoimi_pixel_stats", "qoimi_pixel_stats_counters",
     "qoimi_seek_points", "qoimi_build_seek_index", "qoimi_band_plan", "qoimi_make_band_streams", "qoimi_decode_crops_indexed", "qoimi_seek_stats",
     "qoimi_seek_index_from_pixels", "qoimi_decode_resized_indexed", "qoimi_pixel_stats_indexed",
+    "qoimi_decode_bilinear", "qoimi_bilinear_size", "qoimi_bilinear_stats", "qoimi_decode_bilinear_indexed",
 )
 
 
@@ -242,6 +243,14 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_seek_index_from_pixels.argtypes = [vp, vp, szp, vp, szp, ctypes.POINTER(ci), dp, ci, up, pp, vp]
     lib.qoimi_decode_resized_indexed.restype = ci
     lib.qoimi_decode_resized_indexed.argtypes = lib.qoimi_decode_resized.argtypes + [up, pp, szp]
+    lib.qoimi_decode_bilinear.restype = ci
+    lib.qoimi_decode_bilinear.argtypes = lib.qoimi_decode_resized.argtypes
+    lib.qoimi_bilinear_size.restype = sz
+    lib.qoimi_bilinear_size.argtypes = [dp, rp, ci]
+    lib.qoimi_bilinear_stats.restype = None
+    lib.qoimi_bilinear_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+    lib.qoimi_decode_bilinear_indexed.restype = ci
+    lib.qoimi_decode_bilinear_indexed.argtypes = lib.qoimi_decode_resized_indexed.argtypes
     lib.qoimi_pixel_stats_indexed.restype = ci
     lib.qoimi_pixel_stats_indexed.argtypes = lib.qoimi_pixel_stats.argtypes + [up, pp, szp]
     _lib = lib
@@ -308,6 +317,15 @@ def resize_size(width: int, height: int, channels_in: int, item, channels: int) 
     if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
         return 0
     return int(load_library().qoimi_resize_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels))
+
+
+def bilinear_size(width: int, height: int, channels_in: int, item, channels: int) -> int:
+    """``qoimi_bilinear_size`` for an image of width x height x channels_in: the bytes of the output of `item` (as for ``resize_size``) with
+    `channels` (3 or 4) bytes per pixel; 0 where the C function returns 0."""
+    arr = _resize_array([item])
+    if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
+        return 0
+    return int(load_library().qoimi_bilinear_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels))
 
 
 def seek_points(width: int, height: int, channels_in: int, interval_rows: int) -> int:
@@ -675,6 +693,38 @@ class Context:
         self._lib.qoimi_resize_stats(self._h, out)
         return tuple(int(x) for x in out)
 
+    def _bilinear_args(self, what: str, stream_offsets, sizes, descs, items, out_offsets):
+        """What decode_bilinear and decode_bilinear_indexed make of their sequences: (n, item array, arrays to keep alive, pointers)."""
+        n = len(sizes)
+        if len(descs) != n or len(stream_offsets) != n:
+            raise QoiError(what + ": one stream offset, size and descriptor per image")
+        if len(out_offsets) != len(items):
+            raise QoiError(what + ": one output offset per item")
+        arr = _resize_array(items)
+        if arr is None:
+            raise QoiError(what + ": an item is not eight unsigned 32-bit fields")
+        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
+        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
+        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        return n, arr, (so, oo, sz), (so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), oo.ctypes.data_as(szp))
+
+    def decode_bilinear(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                        items, mode: int, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
+        """``decode_resized`` with the antialiased bilinear (triangle) filter (``qoimi_decode_bilinear``, synchronous, through bounded
+        staging): the same items, modes, flips and outputs; a rectangle is reduced by at most 32 per axis and
+        max(width, out_width) * max(height, out_height) stays below 2**30; ``qoi_amd/bilinear.py: bilinear`` states the result."""
+        n, arr, keep, (so, sz, oo) = self._bilinear_args("decode_bilinear", stream_offsets, sizes, descs, items, out_offsets)
+        self._check(self._lib.qoimi_decode_bilinear(self._h, d_streams, so, sz, (QoiDesc * n)(*descs), n, channels, arr, len(arr), mode, d_out, oo,
+                                                    staging_bytes, stream), "qoimi_decode_bilinear")
+        del keep
+
+    def bilinear_stats(self) -> Tuple[int, int, int, int]:
+        """Of the last ``decode_bilinear`` call: (sub-batches decoded, launches of the filter kernel, bytes of staging planned, images decoded)."""
+        out = (ctypes.c_longlong * 4)()
+        self._lib.qoimi_bilinear_stats(self._h, out)
+        return tuple(int(x) for x in out)
+
     def pixel_stats(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], regions,
                     d_hist: int = 0, staging_bytes: int = 0, stream: int = 0) -> List[QoimiPixelStat]:
         """Pixel statistics of rectangles of a pack's images (``qoimi_pixel_stats``, synchronous, through bounded staging): one
@@ -847,6 +897,18 @@ class Context:
                                                            staging_bytes, stream, *index), "qoimi_decode_resized_indexed")
         del keep
 
+    def decode_bilinear_indexed(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                                items, mode: int, d_out: int, out_offsets: Sequence[int], interval_rows, points, point_firsts: Sequence[int],
+                                staging_bytes: int = 0, stream: int = 0) -> None:
+        """``decode_bilinear`` byte for byte, decoding every referenced image only from the last seek row at or above its topmost source
+        rectangle (``qoimi_decode_bilinear_indexed``).  interval_rows, points, point_firsts: as ``build_seek_index`` took and returned them;
+        ``bilinear_stats`` then holds the counters of the inner call over the band streams."""
+        n, arr, keep, (so, sz, oo) = self._bilinear_args("decode_bilinear_indexed", stream_offsets, sizes, descs, items, out_offsets)
+        index, keep_index = self._index_args("decode_bilinear_indexed", n, interval_rows, points, point_firsts)
+        self._check(self._lib.qoimi_decode_bilinear_indexed(self._h, d_streams, so, sz, (QoiDesc * n)(*descs), n, channels, arr, len(arr), mode, d_out, oo,
+                                                            staging_bytes, stream, *index), "qoimi_decode_bilinear_indexed")
+        del keep, keep_index
+
     def pixel_stats_indexed(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], regions,
                             interval_rows, points, point_firsts: Sequence[int], d_hist: int = 0, staging_bytes: int = 0,
                             stream: int = 0) -> List[QoimiPixelStat]:
@@ -896,7 +958,7 @@ class Context:
         return {self._lib.qoimi_kernel_name(i).decode(): (ms[i], calls[i]) for i in range(1, n)}
 
     def workspace_bytes(self) -> dict:
-        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops`` / ``decode_resized`` / ``pixel_stats``, the tables of ``build_seek_index`` / ``seek_index_from_pixels`` and the band arena of the indexed calls), staging of the host-pointer entry points."""
+        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops`` / ``decode_resized`` / ``decode_bilinear`` / ``pixel_stats``, the tables of ``build_seek_index`` / ``seek_index_from_pixels`` and the band arena of the indexed calls), staging of the host-pointer entry points."""
         out = (ctypes.c_size_t * 3)()
         self._lib.qoimi_workspace_bytes(self._h, out)
         return {"encode": int(out[0]), "decode": int(out[1]), "staging": int(out[2])}

@@ -111,6 +111,7 @@ struct qoimi_ctx {
     long long thumb_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_thumbnails call: sub-batches decoded, launches of thumb_reduce, bytes of staging planned, 0
     long long crop_stats[4] = {0, 0, 0, 0};    // the last qoimi_decode_crops call: sub-batches decoded, launches of crop_gather, bytes of staging planned, images decoded
     long long resize_stats[4] = {0, 0, 0, 0};  // the last qoimi_decode_resized call: sub-batches decoded, launches of resize_filter, bytes of staging planned, images decoded
+    long long bilinear_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_bilinear call: sub-batches decoded, launches of bilinear_filter, bytes of staging planned, images decoded
     Arena band_arena;           // qoimi_decode_crops_indexed: the band streams of one call (the sum of their sizes, each rounded up to 16, plus a page)
     long long seek_stats[4] = {0, 0, 0, 0};    // sub-batches decoded by the last qoimi_build_seek_index; of the last qoimi_make_band_streams / qoimi_decode_crops_indexed: band streams assembled, bytes of the band arena planned, stream bytes copied
     long long pixel_stats[4] = {0, 0, 0, 0};   // the last qoimi_pixel_stats call: sub-batches decoded, launches of stats_reduce, bytes of staging planned, images decoded

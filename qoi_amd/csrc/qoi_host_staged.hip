@@ -1,12 +1,14 @@
 // qoi_host_staged.hip — the calls of the C-ABI shim that decode a pack's images into bounded staging and run one table-driven kernel over
 // each sub-batch: qoimi_verify_images (and qoimi_compare_images, whose kernels it runs), qoimi_decode_thumbnails, qoimi_decode_crops,
-// qoimi_decode_resized, qoimi_pixel_stats, and the row seek index (qoimi_build_seek_index, qoimi_seek_index_from_pixels - which stages nothing;
+// qoimi_decode_resized, qoimi_decode_bilinear, qoimi_pixel_stats, and the row seek index (qoimi_build_seek_index, qoimi_seek_index_from_pixels - which stages nothing;
 // one kernel pair, seekpx_last + seekpx_carry, serves both builds: over the staging arena and over the caller's pixels -,
-// qoimi_make_band_streams, qoimi_decode_crops_indexed, qoimi_decode_resized_indexed, qoimi_pixel_stats_indexed).
+// qoimi_make_band_streams, qoimi_decode_crops_indexed, qoimi_decode_resized_indexed, qoimi_decode_bilinear_indexed,
+// qoimi_pixel_stats_indexed).
 #include "qoi_ctx.h"
 #include "qoi_thumb_core.h"
 #include "qoi_crop_core.h"
 #include "qoi_resize_core.h"
+#include "qoi_bilinear_core.h"
 #include "qoi_stats_core.h"
 #include "qoi_seek_core.h"
 
@@ -183,8 +185,8 @@ extern "C" int qoimi_verify_images(qoimi_ctx* c, const void* d_pixels, const siz
 }
 
 // ------------------------------------------------------------------------------------
-// decode through staging, then one table-driven kernel per sub-batch: what qoimi_decode_thumbnails, qoimi_decode_crops and
-// qoimi_decode_resized share (their plans: qoi_stage_plan.h)
+// decode through staging, then one table-driven kernel per sub-batch: what qoimi_decode_thumbnails, qoimi_decode_crops,
+// qoimi_decode_resized and qoimi_decode_bilinear share (their plans: qoi_stage_plan.h)
 // ------------------------------------------------------------------------------------
 // Sub-batch k of the plan into the staging arena: one call of the decoder as it is, at 4 output channels (every staged pixel an aligned
 // dword) and with each descriptor's height shortened to the image's rows (the decoder decodes to the descriptor it is given: the prefix of
@@ -206,7 +208,7 @@ static int decode_rows(qoimi_ctx* c, const void* d_streams, const size_t* stream
 // output j; och: the output channel count of the call.
 struct CheckedItems { std::vector<uint32_t> rows; std::vector<size_t> out_bytes; unsigned och = 0; };
 
-// The items of qoimi_decode_crops (`noun` "crop"), of qoimi_decode_resized ("item") and of qoimi_pixel_stats ("region"), looked at in the order
+// The items of qoimi_decode_crops (`noun` "crop"), of qoimi_decode_resized and qoimi_decode_bilinear ("item") and of qoimi_pixel_stats ("region"), looked at in the order
 // that decides which message a call with several faults gets.  wrong(desc, item): nullptr if the item is fine for an accepted descriptor, else
 // what is wrong with it; output(j, item, och): QOIMI_OK, or the failure of item j's output (a call without outputs: always QOIMI_OK).
 template <class Item, class Wrong, class Output>
@@ -481,6 +483,62 @@ extern "C" int qoimi_decode_resized(qoimi_ctx* c, const void* d_streams, const s
         },
         [&](const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
             launch_resize((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
+        }, stream);
+}
+
+// ------------------------------------------------------------------------------------
+// rectangles of a pack's images resampled by the antialiased bilinear filter (qoi_bilinear.hip)
+// ------------------------------------------------------------------------------------
+// nullptr if the item is fine for an accepted descriptor, else what is wrong with it: the checks of resize_item_wrong with the ratio limit of
+// 32 and the product limit (qoi_bilinear_core.h: what keeps a weight in 32 bits and the sums in 64)
+static const char* bilinear_item_wrong(const qoi_desc* d, const qoimi_resize* r) {
+    if (r->width == 0u || r->height == 0u || r->out_width == 0u || r->out_height == 0u) return "zero width or height";
+    if ((r->flags & ~(unsigned)(QOIMI_RESIZE_FLIP_X | QOIMI_RESIZE_FLIP_Y)) != 0u) return "unknown flag bit";
+    if ((uint64_t)r->x + r->width > d->width || (uint64_t)r->y + r->height > d->height) return "the rectangle leaves its image";
+    if (r->width > (uint64_t)kBilinearMaxRatio * r->out_width || r->height > (uint64_t)kBilinearMaxRatio * r->out_height) return "reduced by more than 32 in an axis";
+    const uint64_t mx = r->width > r->out_width ? r->width : r->out_width, my = r->height > r->out_height ? r->height : r->out_height;
+    if (mx * my >= kBilinearMaxArea) return "max(width, out_width) * max(height, out_height) is 2^30 or more";
+    return nullptr;
+}
+
+extern "C" size_t qoimi_bilinear_size(const qoi_desc* desc, const qoimi_resize* item, int channels) {
+    size_t bytes = 0;
+    if (!desc_ok(desc) || !item || (channels != 3 && channels != 4) || bilinear_item_wrong(desc, item) || !resize_bytes(item, (unsigned)channels, &bytes)) return 0;
+    return bytes;
+}
+
+// The plan of qoimi_decode_crops over the items' rectangles (qoi_amd/bilinear.py: plan); run_staged with one launch of bilinear_filter over the
+// sub-batch's items.
+extern "C" int qoimi_decode_bilinear(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                     int n_images, int channels, const qoimi_resize* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
+                                     size_t staging_bytes, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    if (mode != QOIMI_RESIZE_PLAIN && mode != QOIMI_RESIZE_ALPHA_WEIGHTED) return fail(QOIMI_E_ARG, "mode must be QOIMI_RESIZE_PLAIN or QOIMI_RESIZE_ALPHA_WEIGHTED");
+    const size_t n = (size_t)n_items;
+    CheckedItems ok;
+    if (const int rc = check_items("item", sizes, descs, n_images, channels, items, n, d_out, out_offsets, bilinear_item_wrong, resize_bytes, ok)) return rc;
+    const unsigned och = ok.och;
+    const RowsPlan plan = plan_rows(descs, n_images, ok.rows, staging_bytes);
+    std::vector<uint32_t> image_of(n);
+    std::vector<uint64_t> tiles_of(n);
+    for (size_t j = 0; j < n; ++j) { image_of[j] = items[j].image; tiles_of[j] = bilinear_tiles(items[j].width, items[j].out_width, items[j].out_height); }
+    const ItemPlan order = plan_items(image_of, plan.ref_of, plan.firsts, tiles_of);
+    if (order.overflow) return fail(QOIMI_E_ARG, "more than 2^31 tiles of output pixels in one sub-batch");
+    const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
+    return run_staged<ResizeEntry>(c, c->bilinear_stats, (long long)plan.refs.size(), "bilinear_filter", d_streams, stream_offsets, sizes, descs, plan, ok.rows, order,
+        [&](ResizeEntry& t, size_t e) {
+            const size_t j = order.by_ref[e];
+            const qoimi_resize& r = items[j];
+            uint32_t lg, cols;
+            bilinear_split(r.width, r.out_width, lg, cols);
+            t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]]; t.dst_off = (u64)out_offsets[j];
+            t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
+            t.first_tile = order.first_tile[e]; t.cfg = lg | (cols << 8) | (och << 16) | (weighted << 24) | (r.flags << 28); t.reserved = 0u;
+        },
+        [&](const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            launch_bilinear((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
         }, stream);
 }
 
@@ -966,6 +1024,25 @@ extern "C" int qoimi_decode_resized_indexed(qoimi_ctx* c, const void* d_streams,
     if (const int rc = stage_bands(c, d_streams, stream_offsets, sizes, descs, n_images, ok.rows, item_tops(items, n, n_images), interval_rows, points, point_firsts, stream, b)) return rc;
     const std::vector<qoimi_resize> rs = rebase_items(items, n, b);
     return qoimi_decode_resized(c, c->band_arena.base, b.at.data(), b.sz.data(), b.ds.data(), (int)b.sz.size(), channels, rs.data(), n_items, mode, d_out, out_offsets, staging_bytes, stream);
+}
+
+// ... qoimi_decode_bilinear likewise.
+extern "C" int qoimi_decode_bilinear_indexed(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                             int n_images, int channels, const qoimi_resize* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
+                                             size_t staging_bytes, void* stream, const unsigned* interval_rows, const qoimi_seek_point* points,
+                                             const size_t* point_firsts) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || !interval_rows || !points || !point_firsts ||
+        n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    if (mode != QOIMI_RESIZE_PLAIN && mode != QOIMI_RESIZE_ALPHA_WEIGHTED) return fail(QOIMI_E_ARG, "mode must be QOIMI_RESIZE_PLAIN or QOIMI_RESIZE_ALPHA_WEIGHTED");
+    const size_t n = (size_t)n_items;
+    CheckedItems ok;
+    if (const int rc = check_items("item", sizes, descs, n_images, channels, items, n, d_out, out_offsets, bilinear_item_wrong, resize_bytes, ok)) return rc;
+    BandedCall b;
+    if (const int rc = stage_bands(c, d_streams, stream_offsets, sizes, descs, n_images, ok.rows, item_tops(items, n, n_images), interval_rows, points, point_firsts, stream, b)) return rc;
+    const std::vector<qoimi_resize> rs = rebase_items(items, n, b);
+    return qoimi_decode_bilinear(c, c->band_arena.base, b.at.data(), b.sz.data(), b.ds.data(), (int)b.sz.size(), channels, rs.data(), n_items, mode, d_out, out_offsets, staging_bytes, stream);
 }
 
 // ... and qoimi_pixel_stats (`first` is a pixel's value, not its place: the result is the plain call's).
