@@ -623,47 +623,28 @@ class Context:
             raise QoiError("decode_thumbnails: one stream offset, size, descriptor, factor and thumbnail offset per image")
         if any(not 0 <= int(f) < 2 ** 32 for f in factors):
             raise QoiError("decode_thumbnails: a factor outside 1..64")
-        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
-        to = np.ascontiguousarray(thumb_offsets, dtype=np.uintp)
-        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        n, ds, _, (so, sz, to), keep = self._gather_args("decode_thumbnails", stream_offsets, sizes, descs, thumb_offsets)
         fs = np.ascontiguousarray(factors, dtype=np.uintc)
-        szp = ctypes.POINTER(ctypes.c_size_t)
-        self._check(self._lib.qoimi_decode_thumbnails(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                      (QoiDesc * n)(*descs), n, channels, fs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), mode,
-                                                      d_thumbs, to.ctypes.data_as(szp), staging_bytes, stream), "qoimi_decode_thumbnails")
+        self._check(self._lib.qoimi_decode_thumbnails(self._h, d_streams, so, sz, ds, n, channels, fs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), mode,
+                                                      d_thumbs, to, staging_bytes, stream), "qoimi_decode_thumbnails")
+        del keep
 
     def thumbnail_stats(self) -> Tuple[int, int, int, int]:
         """Of the last ``decode_thumbnails`` call: (sub-batches decoded, launches of the reduction kernel, bytes of staging planned, 0)."""
-        out = (ctypes.c_longlong * 4)()
-        self._lib.qoimi_thumbnail_stats(self._h, out)
-        return tuple(int(x) for x in out)
+        return self._four_counters(self._lib.qoimi_thumbnail_stats)
 
     def decode_crops(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
                      crops, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
         """Rectangles of a pack's images (``qoimi_decode_crops``, synchronous, through bounded staging): output j is written tightly packed at
         d_out + out_offsets[j].  crops: ``QoimiCrop`` structures or (image, x, y, width, height, flags) tuples, flags of ``crops.FLIP_X`` /
         ``crops.FLIP_Y``; an image no crop names is not decoded; ``qoi_amd/crops.py: crop`` states the result."""
-        n = len(sizes)
-        if len(descs) != n or len(stream_offsets) != n:
-            raise QoiError("decode_crops: one stream offset, size and descriptor per image")
-        if len(out_offsets) != len(crops):
-            raise QoiError("decode_crops: one output offset per crop")
-        arr = _crop_array(crops)
-        if arr is None:
-            raise QoiError("decode_crops: a crop is not six unsigned 32-bit fields")
-        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
-        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
-        sz = np.ascontiguousarray(sizes, dtype=np.intc)
-        szp = ctypes.POINTER(ctypes.c_size_t)
-        self._check(self._lib.qoimi_decode_crops(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                 (QoiDesc * n)(*descs), n, channels, arr, len(arr), d_out, oo.ctypes.data_as(szp), staging_bytes,
-                                                 stream), "qoimi_decode_crops")
+        n, ds, arr, (so, sz, oo), keep = self._gather_args("decode_crops", stream_offsets, sizes, descs, out_offsets, crops=crops)
+        self._check(self._lib.qoimi_decode_crops(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), d_out, oo, staging_bytes, stream), "qoimi_decode_crops")
+        del keep
 
     def crop_stats(self) -> Tuple[int, int, int, int]:
         """Of the last ``decode_crops`` call: (sub-batches decoded, launches of the gather kernel, bytes of staging planned, images decoded)."""
-        out = (ctypes.c_longlong * 4)()
-        self._lib.qoimi_crop_stats(self._h, out)
-        return tuple(int(x) for x in out)
+        return self._four_counters(self._lib.qoimi_crop_stats)
 
     def decode_resized(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
                        items, mode: int, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
@@ -671,59 +652,54 @@ class Context:
         is written tightly packed at d_out + out_offsets[j].  items: ``QoimiResize`` structures or (image, x, y, width, height, out_width,
         out_height, flags) tuples, flags of ``resize.FLIP_X`` / ``resize.FLIP_Y``; mode: ``resize.PLAIN`` or ``resize.ALPHA_WEIGHTED``; an image
         no item names is not decoded; ``qoi_amd/resize.py: resize`` states the result."""
-        n = len(sizes)
-        if len(descs) != n or len(stream_offsets) != n:
-            raise QoiError("decode_resized: one stream offset, size and descriptor per image")
-        if len(out_offsets) != len(items):
-            raise QoiError("decode_resized: one output offset per item")
-        arr = _resize_array(items)
-        if arr is None:
-            raise QoiError("decode_resized: an item is not eight unsigned 32-bit fields")
-        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
-        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
-        sz = np.ascontiguousarray(sizes, dtype=np.intc)
-        szp = ctypes.POINTER(ctypes.c_size_t)
-        self._check(self._lib.qoimi_decode_resized(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                   (QoiDesc * n)(*descs), n, channels, arr, len(arr), mode, d_out, oo.ctypes.data_as(szp),
-                                                   staging_bytes, stream), "qoimi_decode_resized")
+        n, ds, arr, (so, sz, oo), keep = self._gather_args("decode_resized", stream_offsets, sizes, descs, out_offsets, items=items)
+        self._check(self._lib.qoimi_decode_resized(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), mode, d_out, oo, staging_bytes, stream), "qoimi_decode_resized")
+        del keep
 
     def resize_stats(self) -> Tuple[int, int, int, int]:
         """Of the last ``decode_resized`` call: (sub-batches decoded, launches of the filter kernel, bytes of staging planned, images decoded)."""
-        out = (ctypes.c_longlong * 4)()
-        self._lib.qoimi_resize_stats(self._h, out)
-        return tuple(int(x) for x in out)
+        return self._four_counters(self._lib.qoimi_resize_stats)
 
-    def _bilinear_args(self, what: str, stream_offsets, sizes, descs, items, out_offsets):
-        """What decode_bilinear and decode_bilinear_indexed make of their sequences: (n, item array, arrays to keep alive, pointers)."""
+    def _gather_args(self, what: str, stream_offsets, sizes, descs, out_offsets=None, items=None, crops=None, noun: str = "crop"):
+        """What the gather calls and their indexed forms make of their sequences: (n, descriptor array, item array or None - of ``items``
+        (``QoimiResize``) or of ``crops`` (``QoimiCrop``, called ``noun`` in messages) -, pointers (stream offsets, sizes, output offsets or
+        None), arrays to keep alive)."""
         n = len(sizes)
         if len(descs) != n or len(stream_offsets) != n:
             raise QoiError(what + ": one stream offset, size and descriptor per image")
-        if len(out_offsets) != len(items):
-            raise QoiError(what + ": one output offset per item")
-        arr = _resize_array(items)
-        if arr is None:
-            raise QoiError(what + ": an item is not eight unsigned 32-bit fields")
+        given, noun = (items, "item") if items is not None else (crops, noun)
+        if out_offsets is not None and given is not None and len(out_offsets) != len(given):
+            raise QoiError(what + ": one output offset per " + noun)
+        arr = None
+        if given is not None:
+            arr = _resize_array(items) if items is not None else _crop_array(crops)
+            if arr is None:
+                raise QoiError(what + (": an item is not eight" if items is not None else ": a " + noun + " is not six") + " unsigned 32-bit fields")
         so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
-        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
         sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp) if out_offsets is not None else None
         szp = ctypes.POINTER(ctypes.c_size_t)
-        return n, arr, (so, oo, sz), (so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), oo.ctypes.data_as(szp))
+        return n, (QoiDesc * n)(*descs), arr, (so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                               oo.ctypes.data_as(szp) if oo is not None else None), (so, sz, oo)
+
+    def _four_counters(self, getter) -> Tuple[int, int, int, int]:
+        """The four counters a ``qoimi_*_stats`` function writes for this context."""
+        out = (ctypes.c_longlong * 4)()
+        getter(self._h, out)
+        return tuple(int(x) for x in out)
 
     def decode_bilinear(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
                         items, mode: int, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
         """``decode_resized`` with the antialiased bilinear (triangle) filter (``qoimi_decode_bilinear``, synchronous, through bounded
         staging): the same items, modes, flips and outputs; a rectangle is reduced by at most 32 per axis and
         max(width, out_width) * max(height, out_height) stays below 2**30; ``qoi_amd/bilinear.py: bilinear`` states the result."""
-        n, arr, keep, (so, sz, oo) = self._bilinear_args("decode_bilinear", stream_offsets, sizes, descs, items, out_offsets)
-        self._check(self._lib.qoimi_decode_bilinear(self._h, d_streams, so, sz, (QoiDesc * n)(*descs), n, channels, arr, len(arr), mode, d_out, oo,
-                                                    staging_bytes, stream), "qoimi_decode_bilinear")
+        n, ds, arr, (so, sz, oo), keep = self._gather_args("decode_bilinear", stream_offsets, sizes, descs, out_offsets, items=items)
+        self._check(self._lib.qoimi_decode_bilinear(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), mode, d_out, oo, staging_bytes, stream), "qoimi_decode_bilinear")
         del keep
 
     def bilinear_stats(self) -> Tuple[int, int, int, int]:
         """Of the last ``decode_bilinear`` call: (sub-batches decoded, launches of the filter kernel, bytes of staging planned, images decoded)."""
-        out = (ctypes.c_longlong * 4)()
-        self._lib.qoimi_bilinear_stats(self._h, out)
-        return tuple(int(x) for x in out)
+        return self._four_counters(self._lib.qoimi_bilinear_stats)
 
     def pixel_stats(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], regions,
                     d_hist: int = 0, staging_bytes: int = 0, stream: int = 0) -> List[QoimiPixelStat]:
@@ -731,24 +707,15 @@ class Context:
         ``QoimiPixelStat`` per region.  regions: ``QoimiCrop`` structures or (image, x, y, width, height, flags) tuples; d_hist: 0, or device
         memory of 4096 bytes per region that receives uint32[n_regions][4][256]; an image no region names is not decoded;
         ``qoi_amd/pixelstats.py: stats`` states the result."""
-        n = len(sizes)
-        if len(descs) != n or len(stream_offsets) != n:
-            raise QoiError("pixel_stats: one stream offset, size and descriptor per image")
-        arr = _crop_array(regions)
-        if arr is None:
-            raise QoiError("pixel_stats: a region is not six unsigned 32-bit fields")
-        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
-        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        n, ds, arr, (so, sz, _), keep = self._gather_args("pixel_stats", stream_offsets, sizes, descs, crops=regions, noun="region")
         out = (QoimiPixelStat * max(len(arr), 1))()
-        self._check(self._lib.qoimi_pixel_stats(self._h, d_streams, so.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                (QoiDesc * n)(*descs), n, arr, len(arr), out, d_hist or None, staging_bytes, stream), "qoimi_pixel_stats")
+        self._check(self._lib.qoimi_pixel_stats(self._h, d_streams, so, sz, ds, n, arr, len(arr), out, d_hist or None, staging_bytes, stream), "qoimi_pixel_stats")
+        del keep
         return list(out)[:len(arr)]
 
     def pixel_stats_counters(self) -> Tuple[int, int, int, int]:
         """Of the last ``pixel_stats`` call: (sub-batches decoded, launches of the reduction kernel, bytes of staging planned, images decoded)."""
-        out = (ctypes.c_longlong * 4)()
-        self._lib.qoimi_pixel_stats_counters(self._h, out)
-        return tuple(int(x) for x in out)
+        return self._four_counters(self._lib.qoimi_pixel_stats_counters)
 
     def build_seek_index(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc],
                          interval_rows, staging_bytes: int = 0, stream: int = 0):
@@ -816,22 +783,11 @@ class Context:
             interval_rows = [int(interval_rows)] * n
         if len(descs) != n or len(stream_offsets) != n or len(interval_rows) != n or len(point_firsts) != n:
             raise QoiError("decode_crops_indexed: one stream offset, size, descriptor, interval and first point per image")
-        if len(out_offsets) != len(crops):
-            raise QoiError("decode_crops_indexed: one output offset per crop")
-        arr = _crop_array(crops)
-        if arr is None:
-            raise QoiError("decode_crops_indexed: a crop is not six unsigned 32-bit fields")
-        pts, _ = _point_array(points)
-        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
-        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
-        pf = np.ascontiguousarray(point_firsts, dtype=np.uintp)
-        sz = np.ascontiguousarray(sizes, dtype=np.intc)
-        ks = np.ascontiguousarray(interval_rows, dtype=np.uintc)
-        szp = ctypes.POINTER(ctypes.c_size_t)
-        self._check(self._lib.qoimi_decode_crops_indexed(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                         (QoiDesc * n)(*descs), n, channels, arr, len(arr), d_out, oo.ctypes.data_as(szp), staging_bytes,
-                                                         stream, ks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), pts, pf.ctypes.data_as(szp)),
+        n, ds, arr, (so, sz, oo), keep = self._gather_args("decode_crops_indexed", stream_offsets, sizes, descs, out_offsets, crops=crops)
+        index, keep_index = self._index_args("decode_crops_indexed", n, interval_rows, points, point_firsts)
+        self._check(self._lib.qoimi_decode_crops_indexed(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), d_out, oo, staging_bytes, stream, *index),
                     "qoimi_decode_crops_indexed")
+        del keep, keep_index
 
     def seek_index_from_pixels(self, d_pixels: int, pixel_offsets: Sequence[int], d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int],
                                descs: Sequence[QoiDesc], interval_rows, stream: int = 0):
@@ -879,23 +835,11 @@ class Context:
         """``decode_resized`` byte for byte, decoding every referenced image only from the last seek row at or above its topmost source
         rectangle (``qoimi_decode_resized_indexed``).  interval_rows, points, point_firsts: as ``build_seek_index`` took and returned them;
         ``resize_stats`` then holds the counters of the inner call over the band streams."""
-        n = len(sizes)
-        if len(descs) != n or len(stream_offsets) != n:
-            raise QoiError("decode_resized_indexed: one stream offset, size and descriptor per image")
-        if len(out_offsets) != len(items):
-            raise QoiError("decode_resized_indexed: one output offset per item")
-        arr = _resize_array(items)
-        if arr is None:
-            raise QoiError("decode_resized_indexed: an item is not eight unsigned 32-bit fields")
-        index, keep = self._index_args("decode_resized_indexed", n, interval_rows, points, point_firsts)
-        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
-        oo = np.ascontiguousarray(out_offsets, dtype=np.uintp)
-        sz = np.ascontiguousarray(sizes, dtype=np.intc)
-        szp = ctypes.POINTER(ctypes.c_size_t)
-        self._check(self._lib.qoimi_decode_resized_indexed(self._h, d_streams, so.ctypes.data_as(szp), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                           (QoiDesc * n)(*descs), n, channels, arr, len(arr), mode, d_out, oo.ctypes.data_as(szp),
-                                                           staging_bytes, stream, *index), "qoimi_decode_resized_indexed")
-        del keep
+        n, ds, arr, (so, sz, oo), keep = self._gather_args("decode_resized_indexed", stream_offsets, sizes, descs, out_offsets, items=items)
+        index, keep_index = self._index_args("decode_resized_indexed", n, interval_rows, points, point_firsts)
+        self._check(self._lib.qoimi_decode_resized_indexed(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), mode, d_out, oo, staging_bytes, stream, *index),
+                    "qoimi_decode_resized_indexed")
+        del keep, keep_index
 
     def decode_bilinear_indexed(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
                                 items, mode: int, d_out: int, out_offsets: Sequence[int], interval_rows, points, point_firsts: Sequence[int],
@@ -903,10 +847,10 @@ class Context:
         """``decode_bilinear`` byte for byte, decoding every referenced image only from the last seek row at or above its topmost source
         rectangle (``qoimi_decode_bilinear_indexed``).  interval_rows, points, point_firsts: as ``build_seek_index`` took and returned them;
         ``bilinear_stats`` then holds the counters of the inner call over the band streams."""
-        n, arr, keep, (so, sz, oo) = self._bilinear_args("decode_bilinear_indexed", stream_offsets, sizes, descs, items, out_offsets)
+        n, ds, arr, (so, sz, oo), keep = self._gather_args("decode_bilinear_indexed", stream_offsets, sizes, descs, out_offsets, items=items)
         index, keep_index = self._index_args("decode_bilinear_indexed", n, interval_rows, points, point_firsts)
-        self._check(self._lib.qoimi_decode_bilinear_indexed(self._h, d_streams, so, sz, (QoiDesc * n)(*descs), n, channels, arr, len(arr), mode, d_out, oo,
-                                                            staging_bytes, stream, *index), "qoimi_decode_bilinear_indexed")
+        self._check(self._lib.qoimi_decode_bilinear_indexed(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), mode, d_out, oo, staging_bytes, stream, *index),
+                    "qoimi_decode_bilinear_indexed")
         del keep, keep_index
 
     def pixel_stats_indexed(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], regions,
@@ -915,28 +859,18 @@ class Context:
         """``pixel_stats`` field for field, decoding every referenced image only from the last seek row at or above its topmost region
         (``qoimi_pixel_stats_indexed``).  interval_rows, points, point_firsts: as ``build_seek_index`` took and returned them;
         ``pixel_stats_counters`` then holds the counters of the inner call over the band streams."""
-        n = len(sizes)
-        if len(descs) != n or len(stream_offsets) != n:
-            raise QoiError("pixel_stats_indexed: one stream offset, size and descriptor per image")
-        arr = _crop_array(regions)
-        if arr is None:
-            raise QoiError("pixel_stats_indexed: a region is not six unsigned 32-bit fields")
-        index, keep = self._index_args("pixel_stats_indexed", n, interval_rows, points, point_firsts)
-        so = np.ascontiguousarray(stream_offsets, dtype=np.uintp)
-        sz = np.ascontiguousarray(sizes, dtype=np.intc)
+        n, ds, arr, (so, sz, _), keep = self._gather_args("pixel_stats_indexed", stream_offsets, sizes, descs, crops=regions, noun="region")
+        index, keep_index = self._index_args("pixel_stats_indexed", n, interval_rows, points, point_firsts)
         out = (QoimiPixelStat * max(len(arr), 1))()
-        self._check(self._lib.qoimi_pixel_stats_indexed(self._h, d_streams, so.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
-                                                        sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), (QoiDesc * n)(*descs), n, arr, len(arr), out,
-                                                        d_hist or None, staging_bytes, stream, *index), "qoimi_pixel_stats_indexed")
-        del keep
+        self._check(self._lib.qoimi_pixel_stats_indexed(self._h, d_streams, so, sz, ds, n, arr, len(arr), out, d_hist or None, staging_bytes, stream, *index),
+                    "qoimi_pixel_stats_indexed")
+        del keep, keep_index
         return list(out)[:len(arr)]
 
     def seek_stats(self) -> Tuple[int, int, int, int]:
         """(sub-batches decoded by the last ``build_seek_index``; of the last ``make_band_streams`` / indexed call: band streams
         assembled, bytes of the band arena planned, stream bytes copied)."""
-        out = (ctypes.c_longlong * 4)()
-        self._lib.qoimi_seek_stats(self._h, out)
-        return tuple(int(x) for x in out)
+        return self._four_counters(self._lib.qoimi_seek_stats)
 
     def synth_frames(self, kind: int, seed: int, first_frame: int, n_frames: int, width: int, height: int,
                      d_pixels: int, pixel_stride: int, stream: int = 0) -> None:

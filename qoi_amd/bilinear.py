@@ -1,4 +1,4 @@
-"""``qoimi_decode_bilinear`` as pure functions - the normative statement of the result (what qoi_bilinear.hip computes from the decoded pixels of
+"""``qoimi_decode_bilinear`` as pure functions - the normative statement of the result (what bilinear_filter of qoi_resize.hip computes from the decoded pixels of
 an image), of the staging plan and of the kernel's work items (plain numpy / integer arithmetic, no GPU).
 
 An item is ``(image, x, y, width, height, out_width, out_height, flags)`` - the fields of ``qoimi_resize`` in their order, as for

@@ -24,7 +24,7 @@
 // first column always has a weight - is Wy(Y).
 //
 // Plain sequential code over a memory functor `Mem` (load(pixel index) -> dword, store1 / store4(address, value)), compiled for the device
-// by hipcc (qoi_bilinear.hip) and - by tests/host/bilinear_host.cpp only - for the host, where the functor checks and counts every access.
+// by hipcc (qoi_resize.hip) and - by tests/host/bilinear_host.cpp only - for the host, where the functor checks and counts every access.
 #pragma once
 #include <stdint.h>
 
@@ -78,10 +78,7 @@ QOIMI_RESIZE_HD uint64_t bilinear_tiles(uint32_t cw, uint32_t ow, uint32_t oh) {
 // Only pixels with a weight are loaded: columns below cw, rows below rh of the rectangle.
 template <bool WEIGHTED, class Mem>
 QOIMI_RESIZE_HD void bilinear_lane(const Mem& mem, const ResizeGeom& g, uint32_t X, uint32_t Y, uint32_t l, uint32_t c, BilinearSums& s) {
-    QOIMI_RESIZE_UNROLL
-    for (uint32_t i = 0; i < 4u; ++i) s.v.S[i] = 0u;
-    QOIMI_RESIZE_UNROLL
-    for (uint32_t i = 0; i < 3u; ++i) s.v.W[i] = 0u;
+    resize_zero(s.v);
     s.wx = 0u; s.wy = 0u;
     const uint32_t radx = bilinear_rad(g.cw, g.ow), rady = bilinear_rad(g.rh, g.oh);
     const uint64_t ox = (2ull * X + 1u) * g.cw, oy = (2ull * Y + 1u) * g.rh;
@@ -101,15 +98,7 @@ QOIMI_RESIZE_HD void bilinear_lane(const Mem& mem, const ResizeGeom& g, uint32_t
         QOIMI_RESIZE_UNROLL
         for (uint32_t j = 0; j < kBilinearMaxCols; ++j) {
             if (wx[j] == 0u) continue;
-            const uint32_t px = mem.load(at + j);
-            const uint32_t wgt = wy * wx[j];                   // below 2^32
-            const uint32_t al = px >> 24;
-            s.v.S[0] += (uint64_t)wgt * (px & 255u); s.v.S[1] += (uint64_t)wgt * ((px >> 8) & 255u);
-            s.v.S[2] += (uint64_t)wgt * ((px >> 16) & 255u); s.v.S[3] += (uint64_t)wgt * al;
-            if (WEIGHTED) {
-                s.v.W[0] += (uint64_t)wgt * ((px & 255u) * al); s.v.W[1] += (uint64_t)wgt * (((px >> 8) & 255u) * al);
-                s.v.W[2] += (uint64_t)wgt * (((px >> 16) & 255u) * al);
-            }
+            resize_tap<WEIGHTED>(s.v, mem.load(at + j), wy * wx[j]);   // (the weight is below 2^32)
         }
     }
 }
@@ -117,16 +106,10 @@ QOIMI_RESIZE_HD void bilinear_lane(const Mem& mem, const ResizeGeom& g, uint32_t
 // D(X, Y) from the sums of a pixel: wx added over its lanes, wy of lane 0
 QOIMI_RESIZE_HD uint64_t bilinear_divisor(const BilinearSums& s) { return s.wx * s.wy; }
 
-// Pixel (X, Y) of the unflipped result to its place in the output at q: one dword where the output holds 4 bytes per pixel and the address is
-// aligned, else och bytes - the item's own bytes only, never a word that would have to be read first.
+// The sums of pixel (X, Y) divided by D and stored at its place in the output at q (qoi_resize_core.h: resize_store).
 template <class Mem>
 QOIMI_RESIZE_HD void bilinear_finish(const Mem& mem, const ResizeGeom& g, uint64_t q, uint32_t och, bool weighted, uint32_t X, uint32_t Y, const BilinearSums& s) {
-    const uint32_t px = resize_pixel(s.v, bilinear_divisor(s), weighted);
-    const uint32_t xo = (g.flags & kResizeFlipX) != 0u ? g.ow - 1u - X : X, yo = (g.flags & kResizeFlipY) != 0u ? g.oh - 1u - Y : Y;
-    const uint64_t a = q + ((uint64_t)yo * g.ow + xo) * och;
-    if (och == 4u && (a & 3u) == 0u) { mem.store4(a, px); return; }
-    mem.store1(a, px); mem.store1(a + 1u, px >> 8); mem.store1(a + 2u, px >> 16);
-    if (och == 4u) mem.store1(a + 3u, px >> 24);
+    resize_store(mem, g, q, och, X, Y, resize_pixel(s.v, bilinear_divisor(s), weighted));
 }
 
 }  // namespace qoimi

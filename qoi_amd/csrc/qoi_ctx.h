@@ -106,17 +106,17 @@ struct qoimi_ctx {
     Arena enc_ws, dec_ws;       // kernel workspaces
     Arena enc_stage;            // qoimi_encode_packed: the strided streams of one sub-batch (and the source offsets of a mixed-shape call) on their way into the pack
     Arena insp_ws;              // tables, maps and partial counts of qoimi_inspect_streams (its own: a decode call finds dec_ws as it left it)
-    Arena cmp_ws;               // image table and result table of qoimi_compare_images / qoimi_verify_images
-    Arena ver_stage;            // qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops / qoimi_decode_resized / qoimi_pixel_stats: the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
+    Arena cmp_ws;               // image table and result table of qoimi_compare_images / qoimi_verify_images; the table (and results) of run_staged and of the band assembly
+    Arena ver_stage;            // qoimi_verify_images and every call of run_staged (qoi_staged.h: thumbnails, crops, resized, bilinear, pixel statistics, the seek index build): the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
     long long thumb_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_thumbnails call: sub-batches decoded, launches of thumb_reduce, bytes of staging planned, 0
     long long crop_stats[4] = {0, 0, 0, 0};    // the last qoimi_decode_crops call: sub-batches decoded, launches of crop_gather, bytes of staging planned, images decoded
     long long resize_stats[4] = {0, 0, 0, 0};  // the last qoimi_decode_resized call: sub-batches decoded, launches of resize_filter, bytes of staging planned, images decoded
     long long bilinear_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_bilinear call: sub-batches decoded, launches of bilinear_filter, bytes of staging planned, images decoded
-    Arena band_arena;           // qoimi_decode_crops_indexed: the band streams of one call (the sum of their sizes, each rounded up to 16, plus a page)
-    long long seek_stats[4] = {0, 0, 0, 0};    // sub-batches decoded by the last qoimi_build_seek_index; of the last qoimi_make_band_streams / qoimi_decode_crops_indexed: band streams assembled, bytes of the band arena planned, stream bytes copied
+    Arena band_arena;           // the four *_indexed calls (qoi_host_seek.hip: stage_bands): the band streams of one call (the sum of their sizes, each rounded up to 16, plus a page)
+    long long seek_stats[4] = {0, 0, 0, 0};    // sub-batches decoded by the last qoimi_build_seek_index; of the last qoimi_make_band_streams / *_indexed call: band streams assembled, bytes of the band arena planned, stream bytes copied
     long long pixel_stats[4] = {0, 0, 0, 0};   // the last qoimi_pixel_stats call: sub-batches decoded, launches of stats_reduce, bytes of staging planned, images decoded
-    PinBuf cmp_pin;             // pinned staging of those two calls' tables and results (their own: the decode calls inside
-                                // qoimi_verify_images reuse pin at once)
+    PinBuf cmp_pin;             // pinned staging of the tables and results of qoimi_compare_images, qoimi_verify_images, run_staged and the band assembly
+                                // (their own: the decode calls inside them reuse pin at once)
     Arena dec_scan;             // look-back words of dec_scan_entry (calls of a few images): tagged with dec_epoch, zeroed when allocated / when the tag wraps
     uint32_t dec_epoch = 0;     // number of the last such call (16 bits are compared)
     struct { void* at = nullptr; unsigned gen = 0; bool valid = false; } dec_hdr_zero;   // the counter header the last decode call's dec_fill left zeroed (arena base + generation)
@@ -208,6 +208,18 @@ static const size_t kPixelCap = 400000000u;   // QOI_PIXELS_MAX, qoi.h:332
 static bool desc_ok(const qoi_desc* d) {       // qoi.h:366-369 / 514-518
     return d && d->width != 0 && d->height != 0 && d->channels >= 3 && d->channels <= 4 &&
            d->colorspace <= 1 && d->height < kPixelCap / d->width;
+}
+
+// The output channel count a decoding call takes: 0 (each image's own), 3 or 4.  QOIMI_OK, or the failure.
+static int check_out_channels(int channels) {
+    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    return QOIMI_OK;
+}
+
+// The workgroups of a launch whose workgroups walk `tiles` tiles between them: one per tile, eight per compute unit at the most.
+static uint32_t grid_bound(const qoimi_ctx* c, uint64_t tiles) {
+    const uint32_t most = (uint32_t)c->n_cus * 8u;
+    return tiles < most ? (uint32_t)tiles : most;
 }
 
 static uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }

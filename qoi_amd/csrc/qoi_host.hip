@@ -3,7 +3,7 @@
 // Part 1 (at the end of this file) mirrors the reference's public functions (qoi.h:252,265,278,289): identical
 // argument validation, malloc()-owned results, NULL / 0 on failure; it creates a context per calling thread.  Part 2 is the
 // additive device-resident batch API, one file per family of calls: qoi_host_encode.hip, qoi_host_decode.hip, qoi_host_pack.hip,
-// qoi_host_staged.hip; what they share is qoi_ctx.h.  There is NO CPU codec in this library: every
+// qoi_host_staged.hip, qoi_host_seek.hip; what they share is qoi_ctx.h.  There is NO CPU codec in this library: every
 // pixel/stream byte is produced by the gfx950 kernels, and all entry points fail when
 // no GPU is usable.  Every look at the environment happens in this file, where contexts are created.
 #include "qoi_ctx.h"

@@ -408,7 +408,7 @@ extern "C" int qoimi_decode_batch(qoimi_ctx* c, const void* d_streams, size_t st
                                   const int* sizes, const qoi_desc* descs, int n_images, int channels,
                                   void* d_pixels, size_t pixel_stride, void* stream) {
     if (!c || !d_streams || !sizes || !descs || !d_pixels || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
-    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    if (const int rc = check_out_channels(channels)) return rc;
     for (int i = 1; i < n_images && channels == 0; ++i)
         if (descs[i].channels != descs[0].channels) return fail(QOIMI_E_ARG, "all images of a batch must share the output channel count");
     size_t few[8];                                            // (a call of a few images allocates nothing for its offsets)
@@ -430,7 +430,7 @@ extern "C" int qoimi_decode_images(qoimi_ctx* c, const void* d_streams, const si
                                    const qoi_desc* descs, int n_images, int channels,
                                    void* d_pixels, const size_t* pixel_offsets, void* stream) {
     if (!c || !d_streams || !stream_offsets || !sizes || !descs || !d_pixels || !pixel_offsets || n_images <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
-    if (channels != 0 && channels != 3 && channels != 4) return fail(QOIMI_E_ARG, "channels must be 0, 3 or 4 (qoi.h:499)");
+    if (const int rc = check_out_channels(channels)) return rc;
     // everything the host can see is looked at before anything is launched: a rejected call leaves the caller's buffers as they were
     std::vector<size_t> out_bytes((size_t)n_images);
     for (int i = 0; i < n_images; ++i) {

@@ -18,7 +18,7 @@ extern "C" int qoimi_pack_streams(qoimi_ctx* c, const void* d_streams, size_t st
     hipStream_t st = (hipStream_t)stream;
     if (const int rc = timer_room(c, st)) return rc;
     launch_pack_streams((const uint8_t*)d_streams, stream_stride, d_stream_len, (uint32_t)n_streams, align, (uint8_t*)d_packed, packed_capacity,
-                        (u64*)d_packed_off, (uint32_t)c->n_cus * 8u, st, &c->timer);
+                        (u64*)d_packed_off, grid_bound(c, ~0ull), st, &c->timer);
     HIP_TRY(hipGetLastError());
     return QOIMI_OK;
 }
@@ -70,9 +70,9 @@ static int encode_packed(qoimi_ctx* c, const void* d_pixels, size_t pixel_stride
         if (const int full = timer_room(c, st)) return full;
         // (a stream is no longer than its slot and align is at most 256, so the sub-batch takes no more of the pack than `span` bytes:
         // that many tiles, one more for where the range begins in its first tile and one for the destination's own alignment)
-        const size_t tiles = span / kPackTile + 3u, most = (size_t)c->n_cus * 8u;
+        const size_t tiles = span / kPackTile + 3u;
         launch_pack_append(staging, largest, d_src, d_stream_len, (uint32_t)first, (uint32_t)m, align, (uint8_t*)d_packed, packed_capacity,
-                           (u64*)d_packed_off, (uint32_t)(tiles < most ? tiles : most), st, &c->timer);
+                           (u64*)d_packed_off, grid_bound(c, tiles), st, &c->timer);
         if (hipGetLastError() != hipSuccess) rc = fail(QOIMI_E_INTERNAL, "launch of the pack's append kernels failed");
     }
     // whatever happened, qoimi_encode_status must not encode "the last call" again: it went into staging

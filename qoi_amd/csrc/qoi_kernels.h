@@ -298,7 +298,7 @@ static_assert(sizeof(CmpImage) == 32 && sizeof(CmpDiff) == 32, "table layouts");
 void launch_compare(const uint8_t* a, const uint8_t* b, const CmpImage* tab, uint32_t m, uint32_t tiles, CmpDiff* diffs, uint32_t grid,
                     hipStream_t st, KernelTimer* tm);
 
-// ---- table-driven kernels over staged pixels (qoi_thumb.hip, qoi_crop.hip, qoi_resize.hip, qoi_bilinear.hip, qoi_stats.hip) ------
+// ---- table-driven kernels over staged pixels (qoi_thumb.hip, qoi_crop.hip, qoi_resize.hip, qoi_stats.hip) ------
 // One entry per output (thumbnail, crop, resized item, region); the tile sizes, the largest factors and the arithmetic stand in
 // qoi_*_core.h, which the host tests compile without HIP.  launch_*: the kernel over the m table entries at tab (their tiles: [0, tiles));
 // grid: workgroups, at most `tiles`.  No timer marks: these kernels have no entry in the name table (the calls count their launches).

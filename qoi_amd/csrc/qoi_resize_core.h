@@ -78,14 +78,31 @@ QOIMI_RESIZE_HD uint32_t resize_overlap(uint64_t lo, uint64_t len, uint64_t a, u
     return e > b ? (uint32_t)(e - b) : 0u;
 }
 
-// Lane l's share of output pixel (X, Y) of the unflipped result: c columns from k0 + l * c (lg, c: resize_split), every row with a weight.
-// Only pixels with a weight are loaded: columns below cw, rows below rh of the rectangle.
-template <bool WEIGHTED, class Mem>
-QOIMI_RESIZE_HD void resize_lane(const Mem& mem, const ResizeGeom& g, uint32_t X, uint32_t Y, uint32_t l, uint32_t c, ResizeSums& s) {
+// All sums at zero
+QOIMI_RESIZE_HD void resize_zero(ResizeSums& s) {
     QOIMI_RESIZE_UNROLL
     for (uint32_t i = 0; i < 4u; ++i) s.S[i] = 0u;
     QOIMI_RESIZE_UNROLL
     for (uint32_t i = 0; i < 3u; ++i) s.W[i] = 0u;
+}
+
+// One tap: staged pixel px with the weight wgt (32 bits) into the sums - what every filter over ResizeSums does per pixel it loads.
+template <bool WEIGHTED>
+QOIMI_RESIZE_HD void resize_tap(ResizeSums& s, uint32_t px, uint32_t wgt) {
+    const uint32_t al = px >> 24;
+    s.S[0] += (uint64_t)wgt * (px & 255u); s.S[1] += (uint64_t)wgt * ((px >> 8) & 255u);
+    s.S[2] += (uint64_t)wgt * ((px >> 16) & 255u); s.S[3] += (uint64_t)wgt * al;
+    if (WEIGHTED) {
+        s.W[0] += (uint64_t)wgt * ((px & 255u) * al); s.W[1] += (uint64_t)wgt * (((px >> 8) & 255u) * al);
+        s.W[2] += (uint64_t)wgt * (((px >> 16) & 255u) * al);
+    }
+}
+
+// Lane l's share of output pixel (X, Y) of the unflipped result: c columns from k0 + l * c (lg, c: resize_split), every row with a weight.
+// Only pixels with a weight are loaded: columns below cw, rows below rh of the rectangle.
+template <bool WEIGHTED, class Mem>
+QOIMI_RESIZE_HD void resize_lane(const Mem& mem, const ResizeGeom& g, uint32_t X, uint32_t Y, uint32_t l, uint32_t c, ResizeSums& s) {
+    resize_zero(s);
     const uint64_t xlo = (uint64_t)X * g.cw, ylo = (uint64_t)Y * g.rh;
     const uint32_t k0 = (uint32_t)resize_div(xlo, g.ow) + l * c;
     uint32_t wx[kResizeMaxCols];
@@ -100,15 +117,7 @@ QOIMI_RESIZE_HD void resize_lane(const Mem& mem, const ResizeGeom& g, uint32_t X
         QOIMI_RESIZE_UNROLL
         for (uint32_t j = 0; j < kResizeMaxCols; ++j) {
             if (wx[j] == 0u) continue;
-            const uint32_t px = mem.load(at + j);
-            const uint32_t wgt = wy * wx[j];
-            const uint32_t al = px >> 24;
-            s.S[0] += (uint64_t)wgt * (px & 255u); s.S[1] += (uint64_t)wgt * ((px >> 8) & 255u);
-            s.S[2] += (uint64_t)wgt * ((px >> 16) & 255u); s.S[3] += (uint64_t)wgt * al;
-            if (WEIGHTED) {
-                s.W[0] += (uint64_t)wgt * ((px & 255u) * al); s.W[1] += (uint64_t)wgt * (((px >> 8) & 255u) * al);
-                s.W[2] += (uint64_t)wgt * (((px >> 16) & 255u) * al);
-            }
+            resize_tap<WEIGHTED>(s, mem.load(at + j), wy * wx[j]);
         }
     }
 }
@@ -133,16 +142,21 @@ QOIMI_RESIZE_HD uint32_t resize_pixel(const ResizeSums& s, uint64_t T, bool weig
     return c[0] | (c[1] << 8) | (c[2] << 16) | (a << 24);
 }
 
-// Pixel (X, Y) of the unflipped result to its place in the output at q: one dword where the output holds 4 bytes per pixel and the address is
-// aligned, else och bytes - the item's own bytes only, never a word that would have to be read first.
+// Pixel px = (X, Y) of the unflipped result to its place in the output at q: one dword where the output holds 4 bytes per pixel and the address
+// is aligned, else och bytes - the item's own bytes only, never a word that would have to be read first.
 template <class Mem>
-QOIMI_RESIZE_HD void resize_finish(const Mem& mem, const ResizeGeom& g, uint64_t q, uint32_t och, bool weighted, uint32_t X, uint32_t Y, const ResizeSums& s) {
-    const uint32_t px = resize_pixel(s, (uint64_t)g.cw * g.rh, weighted);
+QOIMI_RESIZE_HD void resize_store(const Mem& mem, const ResizeGeom& g, uint64_t q, uint32_t och, uint32_t X, uint32_t Y, uint32_t px) {
     const uint32_t xo = (g.flags & kResizeFlipX) != 0u ? g.ow - 1u - X : X, yo = (g.flags & kResizeFlipY) != 0u ? g.oh - 1u - Y : Y;
     const uint64_t a = q + ((uint64_t)yo * g.ow + xo) * och;
     if (och == 4u && (a & 3u) == 0u) { mem.store4(a, px); return; }
     mem.store1(a, px); mem.store1(a + 1u, px >> 8); mem.store1(a + 2u, px >> 16);
     if (och == 4u) mem.store1(a + 3u, px >> 24);
+}
+
+// The sums of pixel (X, Y) divided by T = cw * rh and stored (resize_store).
+template <class Mem>
+QOIMI_RESIZE_HD void resize_finish(const Mem& mem, const ResizeGeom& g, uint64_t q, uint32_t och, bool weighted, uint32_t X, uint32_t Y, const ResizeSums& s) {
+    resize_store(mem, g, q, och, X, Y, resize_pixel(s, (uint64_t)g.cw * g.rh, weighted));
 }
 
 }  // namespace qoimi

@@ -1,6 +1,6 @@
 // qoi_seek.hip — the row seek index: where the chunk walk of a stream stands at a pixel (seek_block_scan, seek_locate), the colour table and
 // the previous pixel there (seekpx_last, seekpx_carry), and band streams written from an index (band_assemble).  gfx950, wave64.  The host side:
-// qoi_host_staged.hip (qoi_kernels.h holds the tables and declares the launchers; qoi_seek_core.h the arithmetic; qoi_amd/seekindex.py the
+// qoi_host_seek.hip (qoi_kernels.h holds the tables and declares the launchers; qoi_seek_core.h the arithmetic; qoi_amd/seekindex.py the
 // normative statement).
 //
 //   seek_block_scan  Behind the passes of qoimi_inspect_streams as they are (every block's entry phase, every piece's map, a partial count per

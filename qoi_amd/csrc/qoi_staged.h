@@ -1,0 +1,217 @@
+// qoi_staged.h — what the host files of the calls that decode through bounded staging share (qoi_host_staged.hip: the gather calls,
+// qoi_host_seek.hip: the seek index build and the indexed calls): the checks of a call's items, the plan of a gather call, and run_staged, the
+// driver of "decode a sub-batch into the staging arena, one table-driven launch over it".  Host only; no kernel file includes it.
+#pragma once
+#include "qoi_ctx.h"
+#include "qoi_crop_core.h"
+#include "qoi_resize_core.h"
+#include "qoi_bilinear_core.h"
+
+// ------------------------------------------------------------------------------------
+// the few lines several entry points repeat
+// ------------------------------------------------------------------------------------
+static int check_resize_mode(int mode) {
+    if (mode != QOIMI_RESIZE_PLAIN && mode != QOIMI_RESIZE_ALPHA_WEIGHTED) return fail(QOIMI_E_ARG, "mode must be QOIMI_RESIZE_PLAIN or QOIMI_RESIZE_ALPHA_WEIGHTED");
+    return QOIMI_OK;
+}
+
+// Behind a launch: QOIMI_OK, or - the stream waited for - the failure with `kernel` in its message.
+static int launch_check(const char* kernel, hipStream_t st) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return QOIMI_OK;
+    (void)hipStreamSynchronize(st);
+    return fail(QOIMI_E_INTERNAL, std::string(kernel) + ": " + hipGetErrorString(e));
+}
+
+// ------------------------------------------------------------------------------------
+// a call's items
+// ------------------------------------------------------------------------------------
+// What check_items makes of a call's items.  rows[i]: the rows of image i that are decoded, 0: no item names it; out_bytes[j]: the bytes of
+// output j; och: the output channel count of the call.
+struct CheckedItems { std::vector<uint32_t> rows; std::vector<size_t> out_bytes; unsigned och = 0; };
+
+// The items of qoimi_decode_crops (`noun` "crop"), of qoimi_decode_resized and qoimi_decode_bilinear ("item") and of qoimi_pixel_stats ("region"), looked at in the order
+// that decides which message a call with several faults gets.  wrong(desc, item): nullptr if the item is fine for an accepted descriptor, else
+// what is wrong with it; output(j, item, och): QOIMI_OK, or the failure of item j's output (a call without outputs: always QOIMI_OK).
+template <class Item, class Wrong, class Output>
+static int check_refs(const std::string& noun, const int* sizes, const qoi_desc* descs, int n_images, int channels, const Item* items, size_t n,
+                      Wrong wrong, Output output, CheckedItems& out) {
+    std::vector<uint32_t>& rows = out.rows;
+    rows.assign((size_t)n_images, 0u);
+    unsigned och = (unsigned)channels;
+    for (size_t j = 0; j < n; ++j) {
+        const Item& r = items[j];
+        if (r.image >= (unsigned)n_images) return fail(QOIMI_E_ARG, noun + " " + std::to_string(j) + ": no image " + std::to_string(r.image));
+        const size_t i = r.image;
+        if (rows[i] == 0u) {                                   // (an image no item names is never looked at)
+            if (sizes[i] < kHeaderBytes + kTrailerBytes) return fail(QOIMI_E_ARG, "stream " + std::to_string(i) + " shorter than 22 bytes (qoi.h:500)");
+            if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(i) + " rejected (qoi.h:513-521 rules)");
+        }
+        if (channels == 0) {
+            if (och == 0u) och = descs[i].channels;
+            else if (descs[i].channels != och) return fail(QOIMI_E_ARG, "all referenced images of a call must share the output channel count");
+        }
+        if (const char* what = wrong(&descs[i], &r)) return fail(QOIMI_E_ARG, noun + " " + std::to_string(j) + ": " + what);
+        if (r.y + r.height > rows[i]) rows[i] = r.y + r.height;
+        if (const int rc = output(j, &r, och)) return rc;
+    }
+    out.och = och;
+    return QOIMI_OK;
+}
+
+// check_refs for the calls that write an output per item at d_out + out_offsets[j]: bytes_of(item, och, &bytes): false if the output's size
+// does not fit a size_t; no output may end behind the address space, no two may overlap.
+template <class Item, class Wrong, class Bytes>
+static int check_items(const std::string& noun, const int* sizes, const qoi_desc* descs, int n_images, int channels, const Item* items, size_t n,
+                       const void* d_out, const size_t* out_offsets, Wrong wrong, Bytes bytes_of, CheckedItems& out) {
+    out.out_bytes.resize(n);
+    const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_out;       // (so that no address of an output wraps, whatever the offsets)
+    if (const int rc = check_refs(noun, sizes, descs, n_images, channels, items, n, wrong, [&](size_t j, const Item* r, unsigned och) {
+            if (!bytes_of(r, och, &out.out_bytes[j]) || out_offsets[j] > room || out.out_bytes[j] > room - out_offsets[j]) return fail
+               (QOIMI_E_ARG, noun + " " + std::to_string(j) + ": the output ends behind the address space");
+            return (int)QOIMI_OK;
+        }, out)) return rc;
+    if (ranges_overlap(out_offsets, out.out_bytes)) return fail(QOIMI_E_ARG, "the output ranges of two " + noun + "s overlap");
+    return QOIMI_OK;
+}
+
+// nullptr if the rectangle is fine for an accepted descriptor, else what is wrong with it
+static const char* crop_rect_wrong(const qoi_desc* d, const qoimi_crop* r) {
+    if (r->width == 0u || r->height == 0u) return "zero width or height";
+    if ((r->flags & ~(unsigned)(QOIMI_CROP_FLIP_X | QOIMI_CROP_FLIP_Y)) != 0u) return "unknown flag bit";
+    if ((uint64_t)r->x + r->width > d->width || (uint64_t)r->y + r->height > d->height) return "the rectangle leaves its image";
+    return nullptr;
+}
+
+// width * height * och (a rectangle inside an image: it always fits)
+static bool crop_bytes(const qoimi_crop* r, unsigned och, size_t* bytes) {
+    *bytes = (size_t)r->width * r->height * och;
+    return true;
+}
+
+// What the items of both resampling calls are checked for first, in this order; then the ratio and, for bilinear, the area product last.
+static const char* resample_rect_wrong(const qoi_desc* d, const qoimi_resize* r) {
+    if (r->width == 0u || r->height == 0u || r->out_width == 0u || r->out_height == 0u) return "zero width or height";
+    if ((r->flags & ~(unsigned)(QOIMI_RESIZE_FLIP_X | QOIMI_RESIZE_FLIP_Y)) != 0u) return "unknown flag bit";
+    if ((uint64_t)r->x + r->width > d->width || (uint64_t)r->y + r->height > d->height) return "the rectangle leaves its image";
+    return nullptr;
+}
+
+// nullptr if the item is fine for an accepted descriptor, else what is wrong with it
+static const char* resize_item_wrong(const qoi_desc* d, const qoimi_resize* r) {
+    if (const char* what = resample_rect_wrong(d, r)) return what;
+    if (r->width > (uint64_t)kResizeMaxRatio * r->out_width || r->height > (uint64_t)kResizeMaxRatio * r->out_height) return "reduced by more than 64 in an axis";
+    return nullptr;
+}
+
+// ... with the ratio limit of 32 and the product limit (qoi_bilinear_core.h: what keeps a weight in 32 bits and the sums in 64)
+static const char* bilinear_item_wrong(const qoi_desc* d, const qoimi_resize* r) {
+    if (const char* what = resample_rect_wrong(d, r)) return what;
+    if (r->width > (uint64_t)kBilinearMaxRatio * r->out_width || r->height > (uint64_t)kBilinearMaxRatio * r->out_height) return "reduced by more than 32 in an axis";
+    const uint64_t mx = r->width > r->out_width ? r->width : r->out_width, my = r->height > r->out_height ? r->height : r->out_height;
+    if (mx * my >= kBilinearMaxArea) return "max(width, out_width) * max(height, out_height) is 2^30 or more";
+    return nullptr;
+}
+
+// out_width * out_height * och, false if that does not fit a size_t
+static bool resize_bytes(const qoimi_resize* r, unsigned och, size_t* bytes) {
+    const uint64_t px = (uint64_t)r->out_width * r->out_height;
+    if (px > ~(size_t)0 / och) return false;
+    *bytes = (size_t)px * och;
+    return true;
+}
+
+// The regions of qoimi_pixel_stats: no output per item.
+static int check_regions(const int* sizes, const qoi_desc* descs, int n_images, const qoimi_crop* regions, size_t n, CheckedItems& ok) {
+    return check_refs("region", sizes, descs, n_images, 4, regions, n, crop_rect_wrong, [](size_t, const qoimi_crop*, unsigned) { return (int)QOIMI_OK; }, ok);
+}
+
+// ------------------------------------------------------------------------------------
+// the plan of a gather call
+// ------------------------------------------------------------------------------------
+// rows: plan_rows over the rows of every image that are decoded (qoi_amd/crops.py: plan - a function of descs, the items and staging_bytes
+// alone); items: plan_items over the items, item j of n naming image image_of(j) and taking tiles_of(j) tiles.  `overflow`: the message of
+// a sub-batch with 2^31 - 1 tiles or more.
+struct GatherPlan { RowsPlan rows; ItemPlan items; };
+
+template <class ImageOf, class TilesOf>
+static int plan_gather(const qoi_desc* descs, int n_images, const std::vector<uint32_t>& rows, size_t staging_bytes, size_t n, ImageOf image_of,
+                       TilesOf tiles_of, const char* overflow, GatherPlan& out) {
+    out.rows = plan_rows(descs, n_images, rows, staging_bytes);
+    std::vector<uint32_t> image(n);
+    std::vector<uint64_t> tiles(n);
+    for (size_t j = 0; j < n; ++j) { image[j] = image_of(j); tiles[j] = tiles_of(j); }
+    out.items = plan_items(image, out.rows.ref_of, out.rows.firsts, tiles);
+    if (out.items.overflow) return fail(QOIMI_E_ARG, overflow);
+    return QOIMI_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// decode through staging, then one table-driven kernel per sub-batch
+// ------------------------------------------------------------------------------------
+// Sub-batch k of the plan into the staging arena: one call of the decoder as it is, at 4 output channels (every staged pixel an aligned
+// dword) and with each descriptor's height shortened to the image's rows (the decoder decodes to the descriptor it is given: the prefix of
+// the full decode).
+static int decode_rows(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs, const RowsPlan& p,
+                       const std::vector<uint32_t>& rows, size_t k, void* stream) {
+    const int first = p.firsts[k], m = p.firsts[k + 1] - first;
+    std::vector<size_t> so; std::vector<int> sz; std::vector<qoi_desc> ds;
+    for (int r = first; r < first + m; ++r) {
+        const int i = p.refs[(size_t)r];
+        qoi_desc d = descs[i];
+        d.height = rows[(size_t)i];
+        so.push_back(stream_offsets[i]); sz.push_back(sizes[i]); ds.push_back(d);
+    }
+    return qoimi_decode_images(c, d_streams, so.data(), sz.data(), ds.data(), m, 4, c->ver_stage.base, p.at.data() + first, stream);
+}
+
+// Everything behind "the plan is made and the call is accepted".  One table for the whole call, through pinned staging: fill(entry, e) writes
+// entry e (of item items.by_ref[e]; the entries of a sub-batch stand together, their tiles begin at 0).  Then, sub-batch by sub-batch, one call
+// of the decoder as it is into the staging arena and one launch over the sub-batch's entries on the caller's stream -
+// launch(its entries on the device, m, tiles, workgroups, stream), `kernel` in the message if it fails; the next sub-batch's decoder is ordered
+// behind it by the stream.  stats: sub-batches decoded, launches, bytes of staging planned, `decoded`.
+// extra != 0: that many bytes of results stand behind the table (256-aligned: staged_extra_at) on the device and in the pinned staging;
+// begin(pinned bytes, stream) sets them as they start - they go to the device with the table - and may enqueue more; they are copied back
+// behind the last launch and are the call's when QOIMI_OK is returned.
+static size_t staged_extra_at(size_t n, size_t entry_bytes) { return up256(n * entry_bytes); }
+
+template <class Entry, class Fill, class Launch, class Begin>
+static int run_staged(qoimi_ctx* c, long long (&stats)[4], long long decoded, const char* kernel, const void* d_streams, const size_t* stream_offsets,
+                      const int* sizes, const qoi_desc* descs, const RowsPlan& plan, const std::vector<uint32_t>& rows, const ItemPlan& items,
+                      Fill fill, Launch launch, void* stream, size_t extra, Begin begin) {
+    const size_t n = items.by_ref.size();
+    DeviceGuard guard(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    stats[0] = 0; stats[1] = 0; stats[2] = (long long)plan.need; stats[3] = decoded;
+    if (const int rc = wait_decode_tail(c, stream)) return rc;
+    const size_t tab_bytes = staged_extra_at(n, sizeof(Entry));
+    { const int rc = c->cmp_pin.reserve(tab_bytes + extra); if (rc != QOIMI_OK) return rc; }
+    { const int rc = c->cmp_ws.reserve(tab_bytes + extra); if (rc != QOIMI_OK) return rc; }
+    { const int rc = reserve_exact(c->ver_stage, plan.need); if (rc != QOIMI_OK) return rc; }
+    Entry* h_tab = (Entry*)c->cmp_pin.buf;
+    for (size_t e = 0; e < n; ++e) fill(h_tab[e], e);
+    const Entry* d_tab = (const Entry*)c->cmp_ws.base;
+    if (extra != 0u) { const int rc = begin((uint8_t*)c->cmp_pin.buf + tab_bytes, st); if (rc != QOIMI_OK) return rc; }
+    HIP_TRY(hipMemcpyAsync(c->cmp_ws.base, h_tab, extra != 0u ? tab_bytes + extra : n * sizeof(Entry), hipMemcpyHostToDevice, st));
+    for (size_t k = 0; k < items.subs.size(); ++k) {
+        const ItemSub& s = items.subs[k];
+        const int rc = decode_rows(c, d_streams, stream_offsets, sizes, descs, plan, rows, k, stream);
+        if (rc != QOIMI_OK) { (void)hipStreamSynchronize(st); return rc; }
+        stats[0] += 1;
+        launch(d_tab + s.entry, s.m, s.tiles, grid_bound(c, s.tiles), st);
+        if (const int failed = launch_check(kernel, st)) return failed;
+        stats[1] += 1;
+    }
+    if (extra != 0u) HIP_TRY(hipMemcpyAsync((uint8_t*)c->cmp_pin.buf + tab_bytes, (const uint8_t*)c->cmp_ws.base + tab_bytes, extra, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return QOIMI_OK;
+}
+
+// ... for the calls whose kernels write the caller's device memory and nothing else
+template <class Entry, class Fill, class Launch>
+static int run_staged(qoimi_ctx* c, long long (&stats)[4], long long decoded, const char* kernel, const void* d_streams, const size_t* stream_offsets,
+                      const int* sizes, const qoi_desc* descs, const RowsPlan& plan, const std::vector<uint32_t>& rows, const ItemPlan& items,
+                      Fill fill, Launch launch, void* stream) {
+    return run_staged<Entry>(c, stats, decoded, kernel, d_streams, stream_offsets, sizes, descs, plan, rows, items, fill, launch, stream, (size_t)0,
+                             [](uint8_t*, hipStream_t) { return (int)QOIMI_OK; });
+}

@@ -36,7 +36,7 @@ def test_header_and_bindings(lib):
     assert re.search(r"typedef struct \{ unsigned long long size; qoi_desc desc; unsigned pad_rows; \} qoimi_band_info;", code)
     assert len(lib.qoimi_build_seek_index.argtypes) == 10 and len(lib.qoimi_make_band_streams.argtypes) == 15
     assert len(lib.qoimi_decode_crops_indexed.argtypes) == len(lib.qoimi_decode_crops.argtypes) + 3 and len(lib.qoimi_band_plan.argtypes) == 6
-    assert "seekindex.py" in hdr and "qoimi_decode_crops_indexed" in open(os.path.join(ROOT, "qoi_amd", "csrc", "qoi_host_staged.hip")).read()
+    assert "seekindex.py" in hdr and "qoimi_decode_crops_indexed" in open(os.path.join(ROOT, "qoi_amd", "csrc", "qoi_host_seek.hip")).read()
     for f in ("qoi_seek.hip", "qoi_seek_core.h"):
         assert os.path.exists(os.path.join(ROOT, "qoi_amd", "csrc", f))
 
