@@ -562,6 +562,79 @@ size_t qoimi_bilinear_size(const qoi_desc *desc, const qoimi_resize *item, int c
  * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] images decoded (the referenced ones). */
 void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
 
+/* Rectangles of a pack's images sampled through an affine map, without the caller ever owning the decoded images: the calls above mirror a
+ * rectangle but cannot turn the sampling grid - five of the eight EXIF orientations and every quarter turn of a tile need a transposition, and
+ * rotation, shear and anisotropic scale about a point (the affine augmentation of a training loader, the rotated viewport of a slide or map
+ * viewer) need a general map.  Channels, staging, plan, sub-batches and the "not one byte beside an output" contract are those of
+ * qoimi_decode_resized; the modes are its QOIMI_RESIZE_PLAIN and QOIMI_RESIZE_ALPHA_WEIGHTED.
+ * The result (normative; qoi_amd/warp.py: warp states it in Python): decode stream items[j].image exactly as qoimi_decode_images does (same
+ * leniency, bit-exact for EVERY input stream) to och channels, which gives D; a 3-channel decode has alpha 255.  R = D[y .. y + height) x
+ * [x .. x + width), cw = width, rh = height, ow = out_width, oh = out_height.  All arithmetic is integer, every shift and division floors.
+ * Coordinates are DOUBLED pixel-centre coordinates with 16 fractional bits: the centre of source column k of R lies at (2k + 1) << 16.  Output
+ * pixel (X, Y) has U = 2X + 1, V = 2Y + 1; the item carries the INVERSE map, from the output into R:
+ *   Px = a * U + b * V + c,  Py = d * U + e * V + f       (the identity is a = e = 65536 with everything else 0)
+ * Bilinear over 2 x 2 samples: px = Px - 65536, k0 = px >> 17 (arithmetic, so it floors for negatives), fx = px & 131071; columns k0 and
+ * k0 + 1 have the weights 131072 - fx and fx; rows likewise from Py.  A sample with a weight of 0 counts as not taken.  Samples outside R are
+ * never read, even where the image has pixels there: with QOIMI_WARP_REPLICATE their indices are clamped into R, otherwise they take `fill`
+ * (bytes r, g, b, a little-endian; a 3-channel output ignores its alpha).  N_c = sum of wy * wx * c over the four samples.
+ *   QOIMI_RESIZE_PLAIN           every channel of output pixel (X, Y) is (N_c + 2^33) >> 34: ONE rounding
+ *   QOIMI_RESIZE_ALPHA_WEIGHTED  where och == 4: A = N_a, output alpha as in the plain mode; if A > 0, r, g and b are (sum wy * wx * c * a + A/2) / A,
+ *                                if A == 0 they are the PLAIN value.  With och == 3 this mode is PLAIN.
+ * The oh x ow result is written tightly packed row-major, ow * oh * och bytes (qoimi_warp_size), at d_out + out_offsets[j].
+ * NO ANTIALIASING: a map that reduces still takes four samples per output pixel, as cv::warpAffine and torch's grid_sample do; reduce first with
+ * qoimi_decode_resized or qoimi_decode_bilinear where that matters.  With the identity the call is qoimi_decode_crops byte for byte; with
+ * a = 65536 / s and REPLICATE it is qoimi_decode_bilinear enlarging by the power of two s; a constant rectangle stays the constant under any
+ * map with REPLICATE.  Against a float64 evaluation of the same map (torch affine_grid + grid_sample, bilinear, align_corners=False) a value
+ * differs by at most 1, and only where the float result lies at a rounding boundary.
+ * The rectangle is what is staged and what the border is taken at: rows_i of the plan is the maximum of y + height over the items of image i,
+ * so the caller keeps the rectangle tight around what the map reaches - a rectangle of the whole image under a map that reaches one corner
+ * decodes the whole image.
+ * Limits, checked per item in this order: a zero width, height, out_width or out_height; a rectangle that leaves its image; out_width or
+ * out_height of 2^20 or more; out_width * out_height of 400 000 000 or more; |c| or |f| of 2^56 or more; a flag bit other than
+ * QOIMI_WARP_REPLICATE; reserved != 0.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
+ * 2^57: both positions fit 64 bits with room to spare.  N_c <= 255 * 2^34 < 2^42, the alpha-weighted sums are below 2^50.
+ *   stream_offsets, sizes, descs, channels, out_offsets, staging_bytes  as for qoimi_decode_resized; the plan is that of qoimi_decode_crops
+ *                  over the items' rectangles (normative; qoi_amd/warp.py: plan)
+ *   items          HOST qoimi_warp[n_items], in any order of image; several may name the same image, their rectangles may overlap or coincide
+ * Every sub-batch is one qoimi_decode_images call as it is, at 4 output channels and with each descriptor's height replaced by rows_i, then one
+ * launch of the warp kernel over all items of the sub-batch's images on `stream`.
+ * SYNCHRONOUS: returns when every output is written.  QOIMI_E_ARG for what qoimi_decode_resized rejects (its ratio limit and flag bits apart),
+ * for the limits above, and for a sub-batch of the plan with 2^31 - 1 or more tiles of 16 x 16 output pixels: reported before anything is
+ * launched, the caller's buffers are untouched; qoimi_last_error names the cause.  Output ranges must not overlap.  The sub-batches count as
+ * decode calls of the context.  One call at a time per context, as everywhere. */
+enum { QOIMI_WARP_REPLICATE = 1 };
+typedef struct {                 /* 72 bytes, offsets 0/4/8/12/16/20/24/28/32/36/40/44/48/52/56/64 */
+    unsigned int image;          /* index into the call's images */
+    unsigned int x, y;           /* top-left corner of the source rectangle */
+    unsigned int width, height;  /* both >= 1; x + width <= image width, y + height <= image height */
+    unsigned int out_width, out_height;  /* both >= 1 and below 2^20; their product below 400 000 000 */
+    unsigned int flags;          /* QOIMI_WARP_REPLICATE; no other bit */
+    int a, b, d, e;              /* the linear part of the inverse map, 16 fractional bits */
+    unsigned int fill;           /* r | g << 8 | b << 16 | a << 24: the value of a sample outside the rectangle without REPLICATE */
+    unsigned int reserved;       /* 0 */
+    long long c, f;              /* the offsets of the inverse map, doubled coordinates with 16 fractional bits; |c|, |f| < 2^56 */
+} qoimi_warp;
+int qoimi_decode_warped(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                        const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                        const qoimi_warp *items /* host */, int n_items, int mode,
+                        void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream);
+
+/* out_width * out_height * channels - the bytes of the item's output - or 0 if desc is rejected, item is NULL or breaks one of the limits of
+ * qoimi_decode_warped, or channels is not 3 / 4 (item->image is not looked at).  Pure host arithmetic: no context, no GPU. */
+size_t qoimi_warp_size(const qoi_desc *desc, const qoimi_warp *item, int channels);
+
+/* Of the context's last qoimi_decode_warped call: [0] sub-batches decoded, [1] launches of the warp kernel (it has no entry in
+ * qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch), [3] images decoded (the referenced ones). */
+void qoimi_warp_stats(qoimi_ctx *ctx, long long out[4]);
+
+/* Fills *out with the item that shows the rectangle (x, y, width, height) of an image of desc in the EXIF orientation 1..8, exactly: every
+ * output pixel is one pixel of the rectangle (1 as it is, 2 mirrored left-right, 3 turned by 180 degrees, 4 mirrored top-bottom, 5 transposed,
+ * 6 turned by 90 degrees clockwise, 7 transposed along the other diagonal, 8 turned by 90 degrees counter-clockwise).  out_width x out_height is
+ * width x height, height x width for 5..8; image, flags, fill and reserved are 0: the caller sets image.  0 on success; QOIMI_E_ARG for a NULL or
+ * rejected desc, a NULL out, an orientation outside 1..8, a zero width or height, a rectangle that leaves the image.  Pure host arithmetic. */
+int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned width, unsigned height, int exif_orientation /* 1..8 */,
+                      qoimi_warp *out);
+
 /* What is in the pixels of rectangles of a pack's images, without the caller ever owning the decoded images: a tile server learns which tiles
  * of a scan are blank (a constant tile need not be stored) and which are fully opaque (they can be re-encoded with 3 channels), a training
  * loader gets the per-channel sums its normalisation needs and can drop empty or single-colour samples.  The referenced streams are decoded as
@@ -774,6 +847,16 @@ int qoimi_decode_bilinear_indexed(qoimi_ctx *ctx, const void *d_streams, const s
                                   void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream,
                                   const unsigned *interval_rows /* host, n_images */, const qoimi_seek_point *points /* host */,
                                   const size_t *point_firsts /* host, n_images */);
+/* qoimi_decode_warped byte for byte, exactly as qoimi_decode_resized_indexed: band assembly over the items' SOURCE rectangles, then the plain
+ * call as it is with `image` renumbered and every y replaced by y - first_row + pad_rows (the map is relative to the rectangle and stays).  The
+ * counters of qoimi_warp_stats are those of the inner call; qoimi_seek_stats [1..3] are set as qoimi_decode_crops_indexed sets them.
+ * SYNCHRONOUS. */
+int qoimi_decode_warped_indexed(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                                const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                                const qoimi_warp *items /* host */, int n_items, int mode,
+                                void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream,
+                                const unsigned *interval_rows /* host, n_images */, const qoimi_seek_point *points /* host */,
+                                const size_t *point_firsts /* host, n_images */);
 int qoimi_pixel_stats_indexed(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
                               const qoi_desc *descs /* host */, int n_images,
                               const qoimi_crop *regions /* host */, int n_regions,

@@ -46,6 +46,7 @@ EXPORTS = (
     "qoimi_seek_points", "qoimi_build_seek_index", "qoimi_band_plan", "qoimi_make_band_streams", "qoimi_decode_crops_indexed", "qoimi_seek_stats",
     "qoimi_seek_index_from_pixels", "qoimi_decode_resized_indexed", "qoimi_pixel_stats_indexed",
     "qoimi_decode_bilinear", "qoimi_bilinear_size", "qoimi_bilinear_stats", "qoimi_decode_bilinear_indexed",
+    "qoimi_decode_warped", "qoimi_warp_size", "qoimi_warp_stats", "qoimi_warp_orient", "qoimi_decode_warped_indexed",
 )
 
 
@@ -87,6 +88,18 @@ class QoimiResize(ctypes.Structure):
 
 
 assert ctypes.sizeof(QoimiResize) == 32 and [getattr(QoimiResize, f).offset for f, _ in QoimiResize._fields_] == [0, 4, 8, 12, 16, 20, 24, 28]
+
+
+class QoimiWarp(ctypes.Structure):
+    """``qoimi_warp``: 72 bytes - a rectangle of image ``image``, the size of the output, the inverse affine map from the output into the
+    rectangle (``warp.py`` states it), the border (``warp.REPLICATE`` or ``fill``)."""
+    _fields_ = [("image", ctypes.c_uint), ("x", ctypes.c_uint), ("y", ctypes.c_uint), ("width", ctypes.c_uint), ("height", ctypes.c_uint),
+                ("out_width", ctypes.c_uint), ("out_height", ctypes.c_uint), ("flags", ctypes.c_uint), ("a", ctypes.c_int), ("b", ctypes.c_int),
+                ("d", ctypes.c_int), ("e", ctypes.c_int), ("fill", ctypes.c_uint), ("reserved", ctypes.c_uint), ("c", ctypes.c_longlong),
+                ("f", ctypes.c_longlong)]
+
+
+assert ctypes.sizeof(QoimiWarp) == 72 and [getattr(QoimiWarp, f).offset for f, _ in QoimiWarp._fields_] == [0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 64]
 
 
 class QoimiPixelStat(ctypes.Structure):
@@ -251,6 +264,17 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_bilinear_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     lib.qoimi_decode_bilinear_indexed.restype = ci
     lib.qoimi_decode_bilinear_indexed.argtypes = lib.qoimi_decode_resized_indexed.argtypes
+    wp = ctypes.POINTER(QoimiWarp)
+    lib.qoimi_decode_warped.restype = ci
+    lib.qoimi_decode_warped.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, ci, wp, ci, ci, vp, szp, sz, vp]
+    lib.qoimi_warp_size.restype = sz
+    lib.qoimi_warp_size.argtypes = [dp, wp, ci]
+    lib.qoimi_warp_stats.restype = None
+    lib.qoimi_warp_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+    lib.qoimi_warp_orient.restype = ci
+    lib.qoimi_warp_orient.argtypes = [dp, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ci, wp]
+    lib.qoimi_decode_warped_indexed.restype = ci
+    lib.qoimi_decode_warped_indexed.argtypes = lib.qoimi_decode_warped.argtypes + [up, pp, szp]
     lib.qoimi_pixel_stats_indexed.restype = ci
     lib.qoimi_pixel_stats_indexed.argtypes = lib.qoimi_pixel_stats.argtypes + [up, pp, szp]
     _lib = lib
@@ -326,6 +350,42 @@ def bilinear_size(width: int, height: int, channels_in: int, item, channels: int
     if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
         return 0
     return int(load_library().qoimi_bilinear_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels))
+
+
+_WARP_UNSIGNED = (0, 1, 2, 3, 4, 5, 6, 7, 12, 13)          # of the sixteen fields of a qoimi_warp: unsigned int; 8..11: int; 14, 15: long long
+
+
+def _warp_array(items):
+    """items as a ``QoimiWarp`` array: a sequence of such structures or of the sixteen-field tuples of ``warp.fields``; None if a field does
+    not fit its type."""
+    names = [f for f, _ in QoimiWarp._fields_]
+    rows = [tuple(int(getattr(r, f)) for f in names) if isinstance(r, QoimiWarp) else tuple(int(v) for v in r) for r in items]
+    for r in rows:
+        if len(r) != 16 or any(not 0 <= r[k] < 2 ** 32 for k in _WARP_UNSIGNED) or any(not -2 ** 31 <= r[k] < 2 ** 31 for k in (8, 9, 10, 11)) or \
+                any(not -2 ** 63 <= r[k] < 2 ** 63 for k in (14, 15)):
+            return None
+    return (QoimiWarp * len(rows))(*[QoimiWarp(*r) for r in rows])
+
+
+def warp_size(width: int, height: int, channels_in: int, item, channels: int) -> int:
+    """``qoimi_warp_size`` for an image of width x height x channels_in: the bytes of the output of `item` (a ``QoimiWarp`` or the tuple of
+    ``warp.fields``) with `channels` (3 or 4) bytes per pixel; 0 where the C function returns 0."""
+    arr = _warp_array([item])
+    if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
+        return 0
+    return int(load_library().qoimi_warp_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels))
+
+
+def warp_orient(width: int, height: int, channels_in: int, rect, orientation: int) -> Optional["QoimiWarp"]:
+    """``qoimi_warp_orient`` for an image of width x height x channels_in: the item (image 0) that shows rect (x, y, width, height) in the
+    EXIF orientation 1..8; None where the C function returns an error."""
+    if not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256 and all(0 <= int(v) < 2 ** 32 for v in rect) and
+            -2 ** 31 <= orientation < 2 ** 31):
+        return None
+    out = QoimiWarp()
+    x, y, w, h = (int(v) for v in rect)
+    rc = load_library().qoimi_warp_orient(ctypes.byref(QoiDesc(width, height, channels_in, 0)), x, y, w, h, orientation, ctypes.byref(out))
+    return out if rc == 0 else None
 
 
 def seek_points(width: int, height: int, channels_in: int, interval_rows: int) -> int:
@@ -660,18 +720,22 @@ class Context:
         """Of the last ``decode_resized`` call: (sub-batches decoded, launches of the filter kernel, bytes of staging planned, images decoded)."""
         return self._four_counters(self._lib.qoimi_resize_stats)
 
-    def _gather_args(self, what: str, stream_offsets, sizes, descs, out_offsets=None, items=None, crops=None, noun: str = "crop"):
+    def _gather_args(self, what: str, stream_offsets, sizes, descs, out_offsets=None, items=None, crops=None, noun: str = "crop", warps=None):
         """What the gather calls and their indexed forms make of their sequences: (n, descriptor array, item array or None - of ``items``
-        (``QoimiResize``) or of ``crops`` (``QoimiCrop``, called ``noun`` in messages) -, pointers (stream offsets, sizes, output offsets or
-        None), arrays to keep alive)."""
+        (``QoimiResize``), of ``warps`` (``QoimiWarp``) or of ``crops`` (``QoimiCrop``, called ``noun`` in messages) -, pointers (stream
+        offsets, sizes, output offsets or None), arrays to keep alive)."""
         n = len(sizes)
         if len(descs) != n or len(stream_offsets) != n:
             raise QoiError(what + ": one stream offset, size and descriptor per image")
-        given, noun = (items, "item") if items is not None else (crops, noun)
+        given, noun = (items, "item") if items is not None else (warps, "item") if warps is not None else (crops, noun)
         if out_offsets is not None and given is not None and len(out_offsets) != len(given):
             raise QoiError(what + ": one output offset per " + noun)
         arr = None
-        if given is not None:
+        if warps is not None and items is None:
+            arr = _warp_array(warps)
+            if arr is None:
+                raise QoiError(what + ": an item is not the sixteen fields of a qoimi_warp")
+        elif given is not None:
             arr = _resize_array(items) if items is not None else _crop_array(crops)
             if arr is None:
                 raise QoiError(what + (": an item is not eight" if items is not None else ": a " + noun + " is not six") + " unsigned 32-bit fields")
@@ -700,6 +764,20 @@ class Context:
     def bilinear_stats(self) -> Tuple[int, int, int, int]:
         """Of the last ``decode_bilinear`` call: (sub-batches decoded, launches of the filter kernel, bytes of staging planned, images decoded)."""
         return self._four_counters(self._lib.qoimi_bilinear_stats)
+
+    def decode_warped(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                      items, mode: int, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
+        """Rectangles of a pack's images sampled through an affine map with bilinear weights (``qoimi_decode_warped``, synchronous, through
+        bounded staging): output j is written tightly packed at d_out + out_offsets[j].  items: ``QoimiWarp`` structures or the tuples of
+        ``warp.fields`` (``warp.item`` makes one); mode: ``warp.PLAIN`` or ``warp.ALPHA_WEIGHTED``; an image no item names is not decoded;
+        ``qoi_amd/warp.py: warp`` states the result."""
+        n, ds, arr, (so, sz, oo), keep = self._gather_args("decode_warped", stream_offsets, sizes, descs, out_offsets, warps=items)
+        self._check(self._lib.qoimi_decode_warped(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), mode, d_out, oo, staging_bytes, stream), "qoimi_decode_warped")
+        del keep
+
+    def warp_stats(self) -> Tuple[int, int, int, int]:
+        """Of the last ``decode_warped`` call: (sub-batches decoded, launches of the warp kernel, bytes of staging planned, images decoded)."""
+        return self._four_counters(self._lib.qoimi_warp_stats)
 
     def pixel_stats(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], regions,
                     d_hist: int = 0, staging_bytes: int = 0, stream: int = 0) -> List[QoimiPixelStat]:
@@ -851,6 +929,18 @@ class Context:
         index, keep_index = self._index_args("decode_bilinear_indexed", n, interval_rows, points, point_firsts)
         self._check(self._lib.qoimi_decode_bilinear_indexed(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), mode, d_out, oo, staging_bytes, stream, *index),
                     "qoimi_decode_bilinear_indexed")
+        del keep, keep_index
+
+    def decode_warped_indexed(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                              items, mode: int, d_out: int, out_offsets: Sequence[int], interval_rows, points, point_firsts: Sequence[int],
+                              staging_bytes: int = 0, stream: int = 0) -> None:
+        """``decode_warped`` byte for byte, decoding every referenced image only from the last seek row at or above its topmost source
+        rectangle (``qoimi_decode_warped_indexed``).  interval_rows, points, point_firsts: as ``build_seek_index`` took and returned them;
+        ``warp_stats`` then holds the counters of the inner call over the band streams."""
+        n, ds, arr, (so, sz, oo), keep = self._gather_args("decode_warped_indexed", stream_offsets, sizes, descs, out_offsets, warps=items)
+        index, keep_index = self._index_args("decode_warped_indexed", n, interval_rows, points, point_firsts)
+        self._check(self._lib.qoimi_decode_warped_indexed(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), mode, d_out, oo, staging_bytes, stream, *index),
+                    "qoimi_decode_warped_indexed")
         del keep, keep_index
 
     def pixel_stats_indexed(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], regions,

@@ -107,10 +107,11 @@ struct qoimi_ctx {
     Arena enc_stage;            // qoimi_encode_packed: the strided streams of one sub-batch (and the source offsets of a mixed-shape call) on their way into the pack
     Arena insp_ws;              // tables, maps and partial counts of qoimi_inspect_streams (its own: a decode call finds dec_ws as it left it)
     Arena cmp_ws;               // image table and result table of qoimi_compare_images / qoimi_verify_images; the table (and results) of run_staged and of the band assembly
-    Arena ver_stage;            // qoimi_verify_images and every call of run_staged (qoi_staged.h: thumbnails, crops, resized, bilinear, pixel statistics, the seek index build): the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
+    Arena ver_stage;            // qoimi_verify_images and every call of run_staged (qoi_staged.h: thumbnails, crops, resized, bilinear, warped, pixel statistics, the seek index build): the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)
     long long thumb_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_thumbnails call: sub-batches decoded, launches of thumb_reduce, bytes of staging planned, 0
     long long crop_stats[4] = {0, 0, 0, 0};    // the last qoimi_decode_crops call: sub-batches decoded, launches of crop_gather, bytes of staging planned, images decoded
     long long resize_stats[4] = {0, 0, 0, 0};  // the last qoimi_decode_resized call: sub-batches decoded, launches of resize_filter, bytes of staging planned, images decoded
+    long long warp_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_warped call: sub-batches decoded, launches of warp_gather, bytes of staging planned, images decoded
     long long bilinear_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_bilinear call: sub-batches decoded, launches of bilinear_filter, bytes of staging planned, images decoded
     Arena band_arena;           // the four *_indexed calls (qoi_host_seek.hip: stage_bands): the band streams of one call (the sum of their sizes, each rounded up to 16, plus a page)
     long long seek_stats[4] = {0, 0, 0, 0};    // sub-batches decoded by the last qoimi_build_seek_index; of the last qoimi_make_band_streams / *_indexed call: band streams assembled, bytes of the band arena planned, stream bytes copied

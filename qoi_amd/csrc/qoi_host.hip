@@ -182,6 +182,7 @@ extern "C" void qoimi_thumbnail_stats(qoimi_ctx* c, long long out[4]) { copy_sta
 extern "C" void qoimi_crop_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->crop_stats : nullptr, out); }
 extern "C" void qoimi_resize_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->resize_stats : nullptr, out); }
 extern "C" void qoimi_bilinear_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->bilinear_stats : nullptr, out); }
+extern "C" void qoimi_warp_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->warp_stats : nullptr, out); }
 extern "C" void qoimi_pixel_stats_counters(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->pixel_stats : nullptr, out); }
 extern "C" void qoimi_seek_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->seek_stats : nullptr, out); }
 

@@ -460,6 +460,23 @@ extern "C" int qoimi_decode_bilinear_indexed(qoimi_ctx* c, const void* d_streams
         });
 }
 
+// ... qoimi_decode_warped likewise (the map is relative to the rectangle: only `image` and y change).
+extern "C" int qoimi_decode_warped_indexed(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                           int n_images, int channels, const qoimi_warp* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
+                                           size_t staging_bytes, void* stream, const unsigned* interval_rows, const qoimi_seek_point* points,
+                                           const size_t* point_firsts) {
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || !interval_rows || !points || !point_firsts ||
+        n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (const int rc = check_out_channels(channels)) return rc;
+    if (const int rc = check_resize_mode(mode)) return rc;
+    const size_t n = (size_t)n_items;
+    return run_indexed(c, d_streams, stream_offsets, sizes, descs, n_images, items, n, interval_rows, points, point_firsts, stream,
+        [&](CheckedItems& ok) { return check_items("item", sizes, descs, n_images, channels, items, n, d_out, out_offsets, warp_item_wrong, warp_bytes, ok); },
+        [&](const void* bands, const size_t* at, const int* sz, const qoi_desc* ds, int m, const qoimi_warp* rs) {
+            return qoimi_decode_warped(c, bands, at, sz, ds, m, channels, rs, n_items, mode, d_out, out_offsets, staging_bytes, stream);
+        });
+}
+
 // ... and qoimi_pixel_stats (`first` is a pixel's value, not its place: the result is the plain call's).
 extern "C" int qoimi_pixel_stats_indexed(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                          int n_images, const qoimi_crop* regions, int n_regions, qoimi_pixel_stat* stats_out, unsigned* d_hist,

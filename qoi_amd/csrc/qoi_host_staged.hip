@@ -1,6 +1,6 @@
 // qoi_host_staged.hip — the gather calls of the C-ABI shim: they decode a pack's images into bounded staging and run one table-driven kernel
 // over each sub-batch: qoimi_verify_images (and qoimi_compare_images, whose kernels it runs), qoimi_decode_thumbnails, qoimi_decode_crops,
-// qoimi_decode_resized and qoimi_decode_bilinear (one body, two filter kinds), qoimi_pixel_stats.  What they share with the row seek index
+// qoimi_decode_resized and qoimi_decode_bilinear (one body, two filter kinds), qoimi_decode_warped, qoimi_pixel_stats.  What they share with the row seek index
 // and the indexed calls (qoi_host_seek.hip) - the item checks, the gather plan, run_staged - stands in qoi_staged.h.
 #include "qoi_staged.h"
 #include "qoi_thumb_core.h"
@@ -352,6 +352,77 @@ extern "C" int qoimi_decode_bilinear(qoimi_ctx* c, const void* d_streams, const 
                                      int n_images, int channels, const qoimi_resize* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
                                      size_t staging_bytes, void* stream) {
     return decode_resampled(kTentKind, c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream);
+}
+
+// ------------------------------------------------------------------------------------
+// rectangles of a pack's images sampled through an affine map (qoi_warp.hip)
+// ------------------------------------------------------------------------------------
+static_assert(sizeof(qoimi_warp) == 72 && offsetof(qoimi_warp, image) == 0 && offsetof(qoimi_warp, x) == 4 && offsetof(qoimi_warp, y) == 8 &&
+              offsetof(qoimi_warp, width) == 12 && offsetof(qoimi_warp, height) == 16 && offsetof(qoimi_warp, out_width) == 20 &&
+              offsetof(qoimi_warp, out_height) == 24 && offsetof(qoimi_warp, flags) == 28 && offsetof(qoimi_warp, a) == 32 && offsetof(qoimi_warp, b) == 36 &&
+              offsetof(qoimi_warp, d) == 40 && offsetof(qoimi_warp, e) == 44 && offsetof(qoimi_warp, fill) == 48 && offsetof(qoimi_warp, reserved) == 52 &&
+              offsetof(qoimi_warp, c) == 56 && offsetof(qoimi_warp, f) == 64, "qoimi_warp layout");
+static_assert(QOIMI_WARP_REPLICATE == (int)kWarpReplicate, "the table's flag bit");
+
+extern "C" size_t qoimi_warp_size(const qoi_desc* desc, const qoimi_warp* item, int channels) {
+    size_t bytes = 0;
+    if (!desc_ok(desc) || !item || (channels != 3 && channels != 4) || warp_item_wrong(desc, item) || !warp_bytes(item, (unsigned)channels, &bytes)) return 0;
+    return bytes;
+}
+
+// The map that shows the rectangle in an EXIF orientation (qoi_amd/warp.py: orient): every output pixel's position is a sample's centre, so
+// every blend has one sample of the full weight.  S = 65536: a column k of the rectangle mirrored is cw - 1 - k, 2 * (cw - 1 - k) + 1 =
+// 2 * cw - (2k + 1): the factor -S and the offset 2 * cw * S.
+extern "C" int qoimi_warp_orient(const qoi_desc* desc, unsigned x, unsigned y, unsigned width, unsigned height, int exif_orientation, qoimi_warp* out) {
+    if (!desc_ok(desc) || !out) return fail(QOIMI_E_ARG, "NULL argument or rejected descriptor");
+    if (exif_orientation < 1 || exif_orientation > 8) return fail(QOIMI_E_ARG, "exif_orientation must be 1..8");
+    if (width == 0u || height == 0u) return fail(QOIMI_E_ARG, "zero width or height");
+    if ((uint64_t)x + width > desc->width || (uint64_t)y + height > desc->height) return fail(QOIMI_E_ARG, "the rectangle leaves its image");
+    const bool transposed = exif_orientation >= 5;                 // 5..8: the output's columns run along the rectangle's rows
+    const bool mirror_cols = exif_orientation == 2 || exif_orientation == 3 || exif_orientation == 7 || exif_orientation == 8;
+    const bool mirror_rows = exif_orientation == 3 || exif_orientation == 4 || exif_orientation == 6 || exif_orientation == 7;
+    const int S = 65536;
+    const int sx = mirror_cols ? -S : S, sy = mirror_rows ? -S : S;
+    memset(out, 0, sizeof(*out));
+    out->x = x; out->y = y; out->width = width; out->height = height;
+    out->out_width = transposed ? height : width; out->out_height = transposed ? width : height;
+    out->a = transposed ? 0 : sx; out->b = transposed ? sx : 0;
+    out->d = transposed ? sy : 0; out->e = transposed ? 0 : sy;
+    out->c = mirror_cols ? 2ll * width * S : 0; out->f = mirror_rows ? 2ll * height * S : 0;
+    return QOIMI_OK;
+}
+
+// The plan of qoimi_decode_crops over the items' rectangles (qoi_amd/warp.py: plan); run_staged with one launch of warp_gather over the
+// sub-batch's items.
+extern "C" int qoimi_decode_warped(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                   int n_images, int channels, const qoimi_warp* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
+                                   size_t staging_bytes, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (const int rc = check_out_channels(channels)) return rc;
+    if (const int rc = check_resize_mode(mode)) return rc;
+    const size_t n = (size_t)n_items;
+    CheckedItems ok;
+    if (const int rc = check_items("item", sizes, descs, n_images, channels, items, n, d_out, out_offsets, warp_item_wrong, warp_bytes, ok)) return rc;
+    const unsigned och = ok.och;
+    GatherPlan gp;
+    if (const int rc = plan_gather(descs, n_images, ok.rows, staging_bytes, n, [&](size_t j) { return items[j].image; },
+                                   [&](size_t j) { return warp_tiles(items[j].out_width, items[j].out_height); },
+                                   "more than 2^31 tiles of output pixels in one sub-batch", gp)) return rc;
+    const RowsPlan& plan = gp.rows; const ItemPlan& order = gp.items;
+    const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
+    return run_staged<WarpEntry>(c, c->warp_stats, (long long)plan.refs.size(), "warp_gather", d_streams, stream_offsets, sizes, descs, plan, ok.rows, order,
+        [&](WarpEntry& t, size_t e) {
+            const size_t j = order.by_ref[e];
+            const qoimi_warp& r = items[j];
+            t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]]; t.dst_off = (u64)out_offsets[j];
+            t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
+            t.first_tile = order.first_tile[e]; t.cfg = och | (weighted << 8) | (r.flags << 16); t.fill = r.fill;
+            t.a = r.a; t.b = r.b; t.d = r.d; t.e = r.e; t.c = r.c; t.f = r.f;
+        },
+        [&](const WarpEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            launch_warp((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
+        }, stream);
 }
 
 // ------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@
 #include "qoi_crop_core.h"
 #include "qoi_resize_core.h"
 #include "qoi_bilinear_core.h"
+#include "qoi_warp_core.h"
 
 // ------------------------------------------------------------------------------------
 // the few lines several entry points repeat
@@ -30,7 +31,7 @@ static int launch_check(const char* kernel, hipStream_t st) {
 // output j; och: the output channel count of the call.
 struct CheckedItems { std::vector<uint32_t> rows; std::vector<size_t> out_bytes; unsigned och = 0; };
 
-// The items of qoimi_decode_crops (`noun` "crop"), of qoimi_decode_resized and qoimi_decode_bilinear ("item") and of qoimi_pixel_stats ("region"), looked at in the order
+// The items of qoimi_decode_crops (`noun` "crop"), of qoimi_decode_resized, qoimi_decode_bilinear and qoimi_decode_warped ("item") and of qoimi_pixel_stats ("region"), looked at in the order
 // that decides which message a call with several faults gets.  wrong(desc, item): nullptr if the item is fine for an accepted descriptor, else
 // what is wrong with it; output(j, item, och): QOIMI_OK, or the failure of item j's output (a call without outputs: always QOIMI_OK).
 template <class Item, class Wrong, class Output>
@@ -118,6 +119,25 @@ static bool resize_bytes(const qoimi_resize* r, unsigned och, size_t* bytes) {
     const uint64_t px = (uint64_t)r->out_width * r->out_height;
     if (px > ~(size_t)0 / och) return false;
     *bytes = (size_t)px * och;
+    return true;
+}
+
+// The items of qoimi_decode_warped, in this order: the rectangle rules of resample_rect_wrong (a zero size, then a rectangle that leaves its
+// image), the output's sides, its pixels, the map's offsets (qoi_warp_core.h: what keeps both positions in 64 bits), the flags, reserved.
+static const char* warp_item_wrong(const qoi_desc* d, const qoimi_warp* r) {
+    if (r->width == 0u || r->height == 0u || r->out_width == 0u || r->out_height == 0u) return "zero width or height";
+    if ((uint64_t)r->x + r->width > d->width || (uint64_t)r->y + r->height > d->height) return "the rectangle leaves its image";
+    if (r->out_width >= kWarpMaxOut || r->out_height >= kWarpMaxOut) return "out_width or out_height is 2^20 or more";
+    if ((uint64_t)r->out_width * r->out_height >= kWarpMaxArea) return "out_width * out_height is 400 000 000 or more";
+    if (r->c <= -kWarpMaxOffset || r->c >= kWarpMaxOffset || r->f <= -kWarpMaxOffset || r->f >= kWarpMaxOffset) return "|c| or |f| is 2^56 or more";
+    if ((r->flags & ~(unsigned)QOIMI_WARP_REPLICATE) != 0u) return "unknown flag bit";
+    if (r->reserved != 0u) return "reserved is not 0";
+    return nullptr;
+}
+
+// out_width * out_height * och (fewer than 400 000 000 pixels: it always fits)
+static bool warp_bytes(const qoimi_warp* r, unsigned och, size_t* bytes) {
+    *bytes = (size_t)r->out_width * r->out_height * och;
     return true;
 }
 

@@ -1,0 +1,208 @@
+"""``qoimi_decode_warped`` as pure functions - the normative statement of the result (what warp_gather of qoi_warp.hip computes from the decoded
+pixels of an image), of the staging plan, of ``qoimi_warp_orient`` and of the kernel's tiles (plain numpy / integer arithmetic, no GPU).
+
+An item is ``(image, x, y, width, height, out_width, out_height, flags, a, b, d, e, fill, reserved, c, f)`` - the fields of ``qoimi_warp`` in
+their order; an ``api.QoimiWarp`` is taken as well.  With D the decode of stream ``image`` as ``uint8[h, w, och]`` (a 3-channel decode has
+alpha 255), ``R = D[y:y+height, x:x+width]``, ``cw = width``, ``rh = height``, ``ow = out_width``, ``oh = out_height``; all arithmetic is
+integer, every shift and division floors.
+
+* Coordinates are DOUBLED pixel-centre coordinates with 16 fractional bits: the centre of source column k of R lies at ``(2k + 1) << 16``.
+* Output pixel (X, Y) has ``U = 2X + 1``, ``V = 2Y + 1``.  The item carries the INVERSE map, from the output into R:
+  ``Px = a*U + b*V + c``, ``Py = d*U + e*V + f``.  The identity is ``a = e = 65536`` (``ONE``) with everything else 0.
+* Bilinear over 2 x 2 samples: ``px = Px - 65536``, ``k0 = px >> 17``, ``fx = px & 131071``; columns ``k0`` and ``k0 + 1`` have the weights
+  ``131072 - fx`` and ``fx``; rows likewise from Py.  A sample with a weight of 0 counts as not taken.
+* Samples outside R are never read, even where the image has pixels there: with ``REPLICATE`` their indices are clamped into R, otherwise
+  they take ``fill`` (``r | g << 8 | b << 16 | a << 24``; a 3-channel output ignores its alpha).
+* ``N_c = sum wy * wx * c`` over the four samples; the weights add up to ``2**34``.
+* ``PLAIN``: every channel is ``(N_c + 2**33) >> 34`` - ONE rounding.
+* ``ALPHA_WEIGHTED``, 4 channels only: ``A = N_a``; alpha as in the plain mode; where ``A > 0`` r, g and b are
+  ``(sum wy*wx*c*a + A // 2) // A``, where ``A == 0`` they are the PLAIN value.  With 3 channels this mode is PLAIN.
+* There is no antialiasing: a map that reduces still takes four samples (reduce first with ``resize.resize`` where that matters).
+
+Limits, in the order the C side checks them: a zero size; a rectangle that leaves its image; ``ow, oh < 2**20``; ``ow * oh < 400 000 000``;
+``|c|, |f| < 2**56``; no flag bit but ``REPLICATE``; ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
+``|Px|, |Py| < 2**57``; ``N_c <= 255 * 2**34 < 2**42``; the alpha-weighted sums are below ``2**50``: everything fits int64.
+
+With the identity the result is ``crops.crop``; with ``a = ONE // s`` and REPLICATE it is ``bilinear.bilinear`` enlarging by the power of two s;
+a constant stays the constant under any map with REPLICATE.
+
+The plan is ``crops.plan`` over the items' ``(image, x, y, width, height)``: the caller keeps the rectangle tight around what the map reaches.
+
+The tiles of the kernel: 16 x 16 output pixels, row-major over ``ceil(ow / 16) x ceil(oh / 16)``; work item t of a tile is its pixel
+``(t & 15, t >> 4)`` (``place``), so a wavefront of 64 covers 16 columns x 4 rows at any angle of the map.
+"""
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import crops, resize
+
+REPLICATE = 1
+PLAIN = resize.PLAIN
+ALPHA_WEIGHTED = resize.ALPHA_WEIGHTED
+ONE = 1 << 16                   # a factor of 1; a pixel is 2 * ONE in doubled coordinates
+MAX_OUT = 1 << 20               # out_width, out_height stay below it
+MAX_AREA = 400_000_000          # out_width * out_height stays below it
+MAX_OFFSET = 1 << 56            # |c|, |f| stay below it
+TILE = 16
+IDENTITY = (ONE, 0, 0, 0, ONE, 0)   # (a, b, c, d, e, f)
+
+
+def fields(it) -> Tuple[int, ...]:
+    """The sixteen fields of an item given as such a tuple or as a ``qoimi_warp`` structure, in the structure's order."""
+    names = ("image", "x", "y", "width", "height", "out_width", "out_height", "flags", "a", "b", "d", "e", "fill", "reserved", "c", "f")
+    if hasattr(it, "image"):
+        return tuple(int(getattr(it, n)) for n in names)
+    if len(it) != len(names):
+        raise ValueError("fields: an item has sixteen fields")
+    return tuple(int(v) for v in it)
+
+
+def item(image: int, rect, out_size, matrix=IDENTITY, flags: int = 0, fill: int = 0) -> Tuple[int, ...]:
+    """An item's tuple from rect (x, y, width, height), out_size (out_width, out_height) and matrix (a, b, c, d, e, f)."""
+    x, y, cw, rh = rect
+    ow, oh = out_size
+    a, b, c, d, e, f = matrix
+    return (image, x, y, cw, rh, ow, oh, flags, a, b, d, e, fill, 0, c, f)
+
+
+def as_crop(it) -> Tuple[int, int, int, int, int, int]:
+    """The item's (image, x, y, width, height, 0): what the plan looks at."""
+    image, x, y, w, h = fields(it)[:5]
+    return image, x, y, w, h, 0
+
+
+def _wrong(w: int, h: int, rect, out_size, matrix, flags: int, reserved: int = 0) -> str:
+    x, y, cw, rh = (int(v) for v in rect)
+    ow, oh = (int(v) for v in out_size)
+    a, b, c, d, e, f = (int(v) for v in matrix)
+    if cw < 1 or rh < 1 or ow < 1 or oh < 1:
+        return "zero width or height"
+    if x < 0 or y < 0 or x + cw > w or y + rh > h:
+        return "the rectangle leaves its image"
+    if ow >= MAX_OUT or oh >= MAX_OUT:
+        return "out_width or out_height from 2**20"
+    if ow * oh >= MAX_AREA:
+        return "out_width * out_height from 400 000 000"
+    if abs(c) >= MAX_OFFSET or abs(f) >= MAX_OFFSET:
+        return "|c| or |f| from 2**56"
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in (a, b, d, e)):
+        return "a, b, d, e are 32-bit"
+    if flags & ~REPLICATE:
+        return "unknown flag bit"
+    if reserved:
+        return "reserved is not 0"
+    return ""
+
+
+def _axis(P: np.ndarray, n: int, replicate: bool):
+    """(indices int64[..., 2] inside [0, n), weights int64[..., 2], taken-from-R bool[..., 2]) of the positions P on an axis of n samples."""
+    p = P - ONE
+    k0 = p >> 17
+    fr = p & (2 * ONE - 1)
+    k = np.stack([k0, k0 + 1], axis=-1)
+    wgt = np.stack([2 * ONE - fr, fr], axis=-1)
+    inside = (k >= 0) & (k < n)
+    if replicate:
+        inside = np.ones_like(inside)
+    return np.clip(k, 0, n - 1), wgt, inside
+
+
+def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, int], matrix=IDENTITY, flags: int = 0, fill: int = 0,
+         mode: int = PLAIN) -> np.ndarray:
+    """D uint8[h, w, och] (och 3 or 4), rect (x, y, width, height) inside it, out_size (out_width, out_height), matrix (a, b, c, d, e, f)
+    -> uint8[out_height, out_width, och]."""
+    D = np.asarray(D)
+    if D.ndim != 3 or D.shape[2] not in (3, 4) or D.dtype != np.uint8:
+        raise ValueError("warp: D must be uint8[h, w, 3 or 4]")
+    if mode not in (PLAIN, ALPHA_WEIGHTED):
+        raise ValueError("warp: mode must be PLAIN or ALPHA_WEIGHTED")
+    wrong = _wrong(D.shape[1], D.shape[0], rect, out_size, matrix, flags)
+    if wrong:
+        raise ValueError("warp: " + wrong)
+    if not 0 <= fill < 2 ** 32:
+        raise ValueError("warp: fill is 32-bit")
+    x, y, cw, rh = (int(v) for v in rect)
+    ow, oh = (int(v) for v in out_size)
+    a, b, c, d, e, f = (int(v) for v in matrix)
+    och = D.shape[2]
+    weighted = mode == ALPHA_WEIGHTED and och == 4
+    R = D[y:y + rh, x:x + cw].astype(np.int64)
+    if och == 3:
+        R = np.concatenate([R, np.full((rh, cw, 1), 255, dtype=np.int64)], axis=2)
+    F = np.array([(fill >> (8 * k)) & 255 for k in range(4)], dtype=np.int64)
+    U = (2 * np.arange(ow, dtype=np.int64) + 1)[None, :]
+    V = (2 * np.arange(oh, dtype=np.int64) + 1)[:, None]
+    kx, wx, inx = _axis(a * U + b * V + c, cw, bool(flags & REPLICATE))
+    ky, wy, iny = _axis(d * U + e * V + f, rh, bool(flags & REPLICATE))
+    N = np.zeros((oh, ow, 4), dtype=np.int64)
+    M = np.zeros((oh, ow, 3), dtype=np.int64)
+    for r in range(2):
+        for k in range(2):
+            v = np.where((iny[..., r] & inx[..., k])[..., None], R[ky[..., r], kx[..., k]], F[None, None, :])
+            wgt = (wy[..., r] * wx[..., k])[..., None]                   # at most 2**34; a sample without a weight adds nothing
+            N += wgt * v                                                 # below 2**42
+            M += wgt * v[..., :3] * v[..., 3:4]                          # below 2**50
+    out = (N + (1 << 33)) >> 34
+    if weighted:
+        A = N[..., 3:4]
+        out[..., :3] = np.where(A > 0, (M + A // 2) // np.maximum(A, 1), out[..., :3])
+    return np.ascontiguousarray(out[..., :och].astype(np.uint8))
+
+
+def size(w: int, h: int, it, och: int) -> int:
+    """Bytes of the item's output for an image of w x h: out_width * out_height * och, or 0 where ``qoimi_warp_size`` returns 0 for an
+    accepted descriptor."""
+    _, x, y, cw, rh, ow, oh, flags, a, b, d, e, _, reserved, c, f = fields(it)
+    if och not in (3, 4) or _wrong(w, h, (x, y, cw, rh), (ow, oh), (a, b, c, d, e, f), flags, reserved):
+        return 0
+    return ow * oh * och
+
+
+def plan(descs, items, staging_bytes: int):
+    """``crops.plan`` over the items' (image, x, y, width, height): (images, slots, subs, largest); ``len(subs)`` is what
+    ``qoimi_warp_stats`` reports as [0] and [1], ``largest`` as [2], ``len(images)`` as [3]."""
+    return crops.plan(descs, [as_crop(it) for it in items], staging_bytes)
+
+
+def orient(w: int, h: int, rect: Tuple[int, int, int, int], orientation: int) -> Optional[Tuple[int, ...]]:
+    """The item (image 0) that shows rect of an image of w x h in the EXIF orientation 1..8, as ``qoimi_warp_orient`` fills it; None where
+    that returns an error.  1 as it is, 2 mirrored left-right, 3 turned by 180 degrees, 4 mirrored top-bottom, 5 transposed, 6 turned by 90
+    degrees clockwise, 7 transposed along the other diagonal, 8 turned by 90 degrees counter-clockwise."""
+    x, y, cw, rh = (int(v) for v in rect)
+    if orientation not in range(1, 9) or cw < 1 or rh < 1 or x < 0 or y < 0 or x + cw > w or y + rh > h:
+        return None
+    transposed = orientation >= 5
+    sx = -ONE if orientation in (2, 3, 7, 8) else ONE                   # the rectangle's columns run backwards
+    sy = -ONE if orientation in (3, 4, 6, 7) else ONE                   # ... its rows
+    c = 2 * cw * ONE if sx < 0 else 0                                   # 2 * (cw - 1 - k) + 1 = 2 * cw - (2k + 1)
+    f = 2 * rh * ONE if sy < 0 else 0
+    matrix = (0, sx, c, sy, 0, f) if transposed else (sx, 0, c, 0, sy, f)
+    return item(0, rect, (rh, cw) if transposed else (cw, rh), matrix)
+
+
+def rotation(rect_size: Tuple[int, int], out_size: Tuple[int, int], degrees: float, scale: float = 1.0) -> Tuple[int, ...]:
+    """(a, b, c, d, e, f) quantised to 2**-16: the output shows the rectangle turned by `degrees` counter-clockwise about its centre and
+    enlarged by `scale`, the rectangle's centre at the output's centre."""
+    import math
+    cw, rh = rect_size
+    ow, oh = out_size
+    t = math.radians(degrees)
+    co, si = math.cos(t) / scale, math.sin(t) / scale
+    a, b, d, e = (int(round(v * ONE)) for v in (co, -si, si, co))
+    # the output's centre (U, V) = (ow, oh) in doubled coordinates goes to the rectangle's centre (cw, rh) << 16
+    return (a, b, cw * ONE - a * ow - b * oh, d, e, rh * ONE - d * ow - e * oh)
+
+
+# ---------------------------------------------------------------------------------- the kernel's tiles
+def tiles(ow: int, oh: int) -> int:
+    """Tiles of 16 x 16 output pixels of an item."""
+    return -(-ow // TILE) * -(-oh // TILE)
+
+
+def place(tile: int, t: int, ow: int, oh: int) -> Optional[Tuple[int, int]]:
+    """(X, Y) of work item t (0..255) of a tile, None beyond an edge of the output."""
+    across = -(-ow // TILE)
+    ty, tx = divmod(tile, across)
+    X, Y = tx * TILE + (t & 15), ty * TILE + (t >> 4)
+    return (X, Y) if X < ow and Y < oh else None
