@@ -635,6 +635,69 @@ void qoimi_warp_stats(qoimi_ctx *ctx, long long out[4]);
 int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned width, unsigned height, int exif_orientation /* 1..8 */,
                       qoimi_warp *out);
 
+/* The outputs of qoimi_decode_resized, qoimi_decode_bilinear and qoimi_decode_warped as TENSORS: what a training loader feeds a model is not
+ * 8-bit interleaved pixels but N x C x H x W (or N x H x W x C) in binary32, binary16 or bfloat16, each channel normalised -
+ * (p / 255 - mean) / std is scale = 1 / (255 * std), bias = -mean / std.  The conversion happens where the filter's rounded pixel still is in a
+ * register: no second kernel of the caller's reads the bytes back, and nothing but the tensor is written.  Items (qoimi_resize, qoimi_warp as
+ * they are), channels, modes, flips, border, staging, plan, sub-batches, the tile limits and the "not one byte beside an output" contract are
+ * those of the underlying call: qoimi_decode_resized for QOIMI_FILTER_AREA, qoimi_decode_bilinear for QOIMI_FILTER_BILINEAR, qoimi_decode_warped
+ * for qoimi_decode_warped_tensors.
+ * The result (normative; qoi_amd/tensors.py: convert states it in Python): let P be the oh x ow x och u8 result of the underlying call with the
+ * same items, channels and mode, byte for byte, flips included.  Element (Y, X, c) of output j has the value v = P[Y][X][c], an integer 0..255.
+ *   QOIMI_TENSOR_U8    the element is v; scale must be all 1.0f and bias all +0.0f
+ *   QOIMI_TENSOR_F32   t = (float)v; m = t * scale[c], rounded to nearest even in binary32; s = m + bias[c], rounded to nearest even in
+ *                      binary32: TWO roundings, never a fused multiply-add; the element is s
+ *   QOIMI_TENSOR_F16, QOIMI_TENSOR_BF16   s converted to binary16 / bfloat16, round to nearest even
+ * Subnormals are kept, not flushed, in every format; a result too large for its format becomes infinity.  scale and bias are per channel r, g,
+ * b, a; a 3-channel output ignores the fourth.  The element is stored at element index (Y * ow + X) * och + c for QOIMI_TENSOR_HWC, at
+ * (c * oh + Y) * ow + X for QOIMI_TENSOR_CHW, from d_out + out_offsets[j]; an output is tightly packed, ow * oh * och * element size bytes
+ * (qoimi_tensor_size, qoimi_warp_tensor_size).  QOIMI_TENSOR_U8 with QOIMI_TENSOR_HWC therefore is the underlying call byte for byte, and every
+ * other format a pure function of its bytes: the exact-integer definitions of the three filters stand as they are.
+ * Only whole, naturally aligned elements are stored (u8 HWC: as the underlying call stores): no word is read and written back, two outputs
+ * may share one.
+ *   filter         QOIMI_FILTER_AREA or QOIMI_FILTER_BILINEAR (qoimi_decode_tensors only)
+ *   format         HOST; one for the whole call
+ *   d_out, out_offsets   every d_out + out_offsets[j] a multiple of the element size (1 / 2 / 2 / 4)
+ *   everything else      as for the underlying call
+ * SYNCHRONOUS: returns when every output is written.  QOIMI_E_ARG, looked for in this order: an unknown filter; a NULL or empty argument
+ * (format apart); channels; mode; the format - NULL, an unknown dtype, an unknown layout, reserved != 0, a scale or bias that is not finite,
+ * QOIMI_TENSOR_U8 with a scale other than 1 or a bias other than +0; then everything the underlying call rejects, with its messages, item by
+ * item - an output whose size in BYTES does not fit a size_t or that ends behind the address space among them -, output ranges that overlap,
+ * in bytes; an output address that is not a multiple of the element size; a sub-batch of the plan with 2^31 - 1 tiles or more.  All are
+ * reported before anything is launched, the caller's buffers are untouched; qoimi_last_error names the cause.  The sub-batches count as decode
+ * calls of the context.  One call at a time per context, as everywhere.
+ * Not here: indexed forms, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
+ * size of its rectangle, or divides it, is those), anything on the encode side. */
+enum { QOIMI_TENSOR_U8 = 0, QOIMI_TENSOR_F16 = 1, QOIMI_TENSOR_BF16 = 2, QOIMI_TENSOR_F32 = 3 };   /* element sizes 1 / 2 / 2 / 4 */
+enum { QOIMI_TENSOR_HWC = 0, QOIMI_TENSOR_CHW = 1 };
+enum { QOIMI_FILTER_AREA = 0, QOIMI_FILTER_BILINEAR = 1 };
+typedef struct {                 /* 48 bytes, offsets 0/4/8/24/40 */
+    unsigned int dtype;          /* QOIMI_TENSOR_* */
+    unsigned int layout;         /* QOIMI_TENSOR_HWC / _CHW */
+    float scale[4];              /* per channel r, g, b, a */
+    float bias[4];
+    unsigned int reserved[2];    /* 0 */
+} qoimi_tensor_format;
+int qoimi_decode_tensors(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                         const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                         const qoimi_resize *items /* host */, int n_items, int filter, int mode, const qoimi_tensor_format *format /* host */,
+                         void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream);
+int qoimi_decode_warped_tensors(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
+                                const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,
+                                const qoimi_warp *items /* host */, int n_items, int mode, const qoimi_tensor_format *format /* host */,
+                                void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream);
+
+/* out_width * out_height * channels * element size - the bytes of the item's output - or 0 if filter is unknown, the format is one the calls
+ * reject, qoimi_resize_size / qoimi_bilinear_size (by filter) or qoimi_warp_size would return 0, or the product does not fit a size_t.  Pure
+ * host arithmetic: no context, no GPU. */
+size_t qoimi_tensor_size(const qoi_desc *desc, const qoimi_resize *item, int filter, int channels, const qoimi_tensor_format *format);
+size_t qoimi_warp_tensor_size(const qoi_desc *desc, const qoimi_warp *item, int channels, const qoimi_tensor_format *format);
+
+/* Of the context's last qoimi_decode_tensors or qoimi_decode_warped_tensors call, whichever came last: [0] sub-batches decoded, [1] launches
+ * of its tensor kernel (it has no entry in qoimi_kernel_name), [2] bytes of the staging the call planned for (its largest sub-batch),
+ * [3] images decoded (the referenced ones). */
+void qoimi_tensor_stats(qoimi_ctx *ctx, long long out[4]);
+
 /* What is in the pixels of rectangles of a pack's images, without the caller ever owning the decoded images: a tile server learns which tiles
  * of a scan are blank (a constant tile need not be stored) and which are fully opaque (they can be re-encoded with 3 channels), a training
  * loader gets the per-channel sums its normalisation needs and can drop empty or single-colour samples.  The referenced streams are decoded as

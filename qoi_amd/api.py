@@ -47,6 +47,7 @@ EXPORTS = (
     "qoimi_seek_index_from_pixels", "qoimi_decode_resized_indexed", "qoimi_pixel_stats_indexed",
     "qoimi_decode_bilinear", "qoimi_bilinear_size", "qoimi_bilinear_stats", "qoimi_decode_bilinear_indexed",
     "qoimi_decode_warped", "qoimi_warp_size", "qoimi_warp_stats", "qoimi_warp_orient", "qoimi_decode_warped_indexed",
+    "qoimi_decode_tensors", "qoimi_decode_warped_tensors", "qoimi_tensor_size", "qoimi_warp_tensor_size", "qoimi_tensor_stats",
 )
 
 
@@ -100,6 +101,16 @@ class QoimiWarp(ctypes.Structure):
 
 
 assert ctypes.sizeof(QoimiWarp) == 72 and [getattr(QoimiWarp, f).offset for f, _ in QoimiWarp._fields_] == [0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 64]
+
+
+class QoimiTensorFormat(ctypes.Structure):
+    """``qoimi_tensor_format``: 48 bytes - the element type (``tensors.U8`` / ``F16`` / ``BF16`` / ``F32``), the layout (``tensors.HWC`` /
+    ``CHW``) and the scale and bias of each channel (``tensors.py`` states the result)."""
+    _fields_ = [("dtype", ctypes.c_uint), ("layout", ctypes.c_uint), ("scale", ctypes.c_float * 4), ("bias", ctypes.c_float * 4),
+                ("reserved", ctypes.c_uint * 2)]
+
+
+assert ctypes.sizeof(QoimiTensorFormat) == 48 and [getattr(QoimiTensorFormat, f).offset for f, _ in QoimiTensorFormat._fields_] == [0, 4, 8, 24, 40]
 
 
 class QoimiPixelStat(ctypes.Structure):
@@ -275,6 +286,17 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_warp_orient.argtypes = [dp, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ci, wp]
     lib.qoimi_decode_warped_indexed.restype = ci
     lib.qoimi_decode_warped_indexed.argtypes = lib.qoimi_decode_warped.argtypes + [up, pp, szp]
+    tp = ctypes.POINTER(QoimiTensorFormat)
+    lib.qoimi_decode_tensors.restype = ci
+    lib.qoimi_decode_tensors.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, ci, rp, ci, ci, ci, tp, vp, szp, sz, vp]
+    lib.qoimi_decode_warped_tensors.restype = ci
+    lib.qoimi_decode_warped_tensors.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, ci, wp, ci, ci, tp, vp, szp, sz, vp]
+    lib.qoimi_tensor_size.restype = sz
+    lib.qoimi_tensor_size.argtypes = [dp, rp, ci, ci, tp]
+    lib.qoimi_warp_tensor_size.restype = sz
+    lib.qoimi_warp_tensor_size.argtypes = [dp, wp, ci, tp]
+    lib.qoimi_tensor_stats.restype = None
+    lib.qoimi_tensor_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     lib.qoimi_pixel_stats_indexed.restype = ci
     lib.qoimi_pixel_stats_indexed.argtypes = lib.qoimi_pixel_stats.argtypes + [up, pp, szp]
     _lib = lib
@@ -374,6 +396,34 @@ def warp_size(width: int, height: int, channels_in: int, item, channels: int) ->
     if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
         return 0
     return int(load_library().qoimi_warp_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels))
+
+
+def tensor_format(f) -> "QoimiTensorFormat":
+    """f as a ``QoimiTensorFormat``: such a structure, or the (dtype, layout, scale[4], bias[4]) of ``tensors.fmt``."""
+    if isinstance(f, QoimiTensorFormat):
+        return f
+    dtype, layout, scale, bias = f
+    if not (0 <= int(dtype) < 2 ** 32 and 0 <= int(layout) < 2 ** 32 and len(scale) == 4 and len(bias) == 4):
+        raise QoiError("tensor_format: (dtype, layout, scale[4], bias[4])")
+    return QoimiTensorFormat(int(dtype), int(layout), (ctypes.c_float * 4)(*[float(v) for v in scale]), (ctypes.c_float * 4)(*[float(v) for v in bias]))
+
+
+def tensor_size(width: int, height: int, channels_in: int, item, filter: int, channels: int, f) -> int:
+    """``qoimi_tensor_size`` for an image of width x height x channels_in: the bytes of the output of `item` (as for ``resize_size``) under
+    `filter` (``tensors.FILTER_AREA`` / ``FILTER_BILINEAR``) with `channels` (3 or 4) elements per pixel in the format f; 0 where the C
+    function returns 0."""
+    arr = _resize_array([item])
+    if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
+        return 0
+    return int(load_library().qoimi_tensor_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, filter, channels, ctypes.byref(tensor_format(f))))
+
+
+def warp_tensor_size(width: int, height: int, channels_in: int, item, channels: int, f) -> int:
+    """``qoimi_warp_tensor_size``: as ``tensor_size`` for an item of ``decode_warped_tensors`` (a ``QoimiWarp`` or the tuple of ``warp.fields``)."""
+    arr = _warp_array([item])
+    if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
+        return 0
+    return int(load_library().qoimi_warp_tensor_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels, ctypes.byref(tensor_format(f))))
 
 
 def warp_orient(width: int, height: int, channels_in: int, rect, orientation: int) -> Optional["QoimiWarp"]:
@@ -778,6 +828,33 @@ class Context:
     def warp_stats(self) -> Tuple[int, int, int, int]:
         """Of the last ``decode_warped`` call: (sub-batches decoded, launches of the warp kernel, bytes of staging planned, images decoded)."""
         return self._four_counters(self._lib.qoimi_warp_stats)
+
+    def decode_tensors(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                       items, filter: int, mode: int, f, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
+        """``decode_resized`` (filter ``tensors.FILTER_AREA``) or ``decode_bilinear`` (``tensors.FILTER_BILINEAR``) with the outputs written
+        as tensors (``qoimi_decode_tensors``, synchronous, through bounded staging): f is a ``QoimiTensorFormat`` or the tuple of
+        ``tensors.fmt`` - u8, f16, bf16 or f32 elements, HWC or CHW, each channel scaled and shifted; every d_out + out_offsets[j] is a
+        multiple of the element size; ``qoi_amd/tensors.py: tensors`` states the result."""
+        n, ds, arr, (so, sz, oo), keep = self._gather_args("decode_tensors", stream_offsets, sizes, descs, out_offsets, items=items)
+        tf = tensor_format(f)
+        self._check(self._lib.qoimi_decode_tensors(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), filter, mode, ctypes.byref(tf), d_out, oo, staging_bytes, stream),
+                    "qoimi_decode_tensors")
+        del keep
+
+    def decode_warped_tensors(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], channels: int,
+                              items, mode: int, f, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
+        """``decode_warped`` with the outputs written as tensors (``qoimi_decode_warped_tensors``): f and the outputs as for
+        ``decode_tensors``; ``qoi_amd/tensors.py: warped_tensors`` states the result."""
+        n, ds, arr, (so, sz, oo), keep = self._gather_args("decode_warped_tensors", stream_offsets, sizes, descs, out_offsets, warps=items)
+        tf = tensor_format(f)
+        self._check(self._lib.qoimi_decode_warped_tensors(self._h, d_streams, so, sz, ds, n, channels, arr, len(arr), mode, ctypes.byref(tf), d_out, oo, staging_bytes, stream),
+                    "qoimi_decode_warped_tensors")
+        del keep
+
+    def tensor_stats(self) -> Tuple[int, int, int, int]:
+        """Of the last ``decode_tensors`` or ``decode_warped_tensors`` call: (sub-batches decoded, launches of the tensor kernel, bytes of
+        staging planned, images decoded)."""
+        return self._four_counters(self._lib.qoimi_tensor_stats)
 
     def pixel_stats(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], descs: Sequence[QoiDesc], regions,
                     d_hist: int = 0, staging_bytes: int = 0, stream: int = 0) -> List[QoimiPixelStat]:

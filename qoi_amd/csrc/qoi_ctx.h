@@ -112,6 +112,7 @@ struct qoimi_ctx {
     long long crop_stats[4] = {0, 0, 0, 0};    // the last qoimi_decode_crops call: sub-batches decoded, launches of crop_gather, bytes of staging planned, images decoded
     long long resize_stats[4] = {0, 0, 0, 0};  // the last qoimi_decode_resized call: sub-batches decoded, launches of resize_filter, bytes of staging planned, images decoded
     long long warp_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_warped call: sub-batches decoded, launches of warp_gather, bytes of staging planned, images decoded
+    long long tensor_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_tensors or qoimi_decode_warped_tensors call: sub-batches decoded, launches of its tensor kernel, bytes of staging planned, images decoded
     long long bilinear_stats[4] = {0, 0, 0, 0};   // the last qoimi_decode_bilinear call: sub-batches decoded, launches of bilinear_filter, bytes of staging planned, images decoded
     Arena band_arena;           // the four *_indexed calls (qoi_host_seek.hip: stage_bands): the band streams of one call (the sum of their sizes, each rounded up to 16, plus a page)
     long long seek_stats[4] = {0, 0, 0, 0};    // sub-batches decoded by the last qoimi_build_seek_index; of the last qoimi_make_band_streams / *_indexed call: band streams assembled, bytes of the band arena planned, stream bytes copied

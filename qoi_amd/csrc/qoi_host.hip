@@ -183,6 +183,7 @@ extern "C" void qoimi_crop_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c 
 extern "C" void qoimi_resize_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->resize_stats : nullptr, out); }
 extern "C" void qoimi_bilinear_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->bilinear_stats : nullptr, out); }
 extern "C" void qoimi_warp_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->warp_stats : nullptr, out); }
+extern "C" void qoimi_tensor_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->tensor_stats : nullptr, out); }
 extern "C" void qoimi_pixel_stats_counters(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->pixel_stats : nullptr, out); }
 extern "C" void qoimi_seek_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->seek_stats : nullptr, out); }
 

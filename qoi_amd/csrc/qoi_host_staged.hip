@@ -285,57 +285,21 @@ static_assert(sizeof(qoimi_resize) == 32 && offsetof(qoimi_resize, image) == 0 &
 static_assert(QOIMI_RESIZE_FLIP_X == (int)kResizeFlipX && QOIMI_RESIZE_FLIP_Y == (int)kResizeFlipY, "the table's flag bits");
 static_assert(QOIMI_RESIZE_PLAIN == 0 && QOIMI_RESIZE_ALPHA_WEIGHTED == 1, "the table's mode bit");
 
-// A resampling filter: what is wrong with an item (qoi_staged.h), how an output pixel's columns are split over lanes and the tiles of an item
-// (its core header), its launcher, the context's counters of its last call, and its kernel's name for a launch failure.
-struct ResampleKind {
-    const char* (*wrong)(const qoi_desc*, const qoimi_resize*);
-    void (*split)(uint32_t cw, uint32_t ow, uint32_t& lg, uint32_t& c);
-    uint64_t (*tiles)(uint32_t cw, uint32_t ow, uint32_t oh);
-    void (*launch)(const uint8_t*, const ResizeEntry*, uint32_t, uint32_t, uint8_t*, uint32_t, hipStream_t);
-    long long (qoimi_ctx::*stats)[4];
-    const char* kernel;
-};
-static const ResampleKind kAreaKind = {resize_item_wrong, resize_split, resize_tiles, launch_resize, &qoimi_ctx::resize_stats, "resize_filter"};
-static const ResampleKind kTentKind = {bilinear_item_wrong, bilinear_split, bilinear_tiles, launch_bilinear, &qoimi_ctx::bilinear_stats, "bilinear_filter"};
-
 static size_t resample_size(const ResampleKind& kind, const qoi_desc* desc, const qoimi_resize* item, int channels) {
     size_t bytes = 0;
     if (!desc_ok(desc) || !item || (channels != 3 && channels != 4) || kind.wrong(desc, item) || !resize_bytes(item, (unsigned)channels, &bytes)) return 0;
     return bytes;
 }
 
-// The plan of qoimi_decode_crops over the items' rectangles (qoi_amd/resize.py: plan, qoi_amd/bilinear.py: plan); run_staged with one launch of
-// the filter's kernel over the sub-batch's items.
+// gather_resampled (qoi_staged.h) with bytes as the output: one launch of the filter's kernel over the sub-batch's items.
 static int decode_resampled(const ResampleKind& kind, qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                             int n_images, int channels, const qoimi_resize* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
                             size_t staging_bytes, void* stream) {
-    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
-    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
-    if (const int rc = check_out_channels(channels)) return rc;
-    if (const int rc = check_resize_mode(mode)) return rc;
-    const size_t n = (size_t)n_items;
-    CheckedItems ok;
-    if (const int rc = check_items("item", sizes, descs, n_images, channels, items, n, d_out, out_offsets, kind.wrong, resize_bytes, ok)) return rc;
-    const unsigned och = ok.och;
-    GatherPlan gp;
-    if (const int rc = plan_gather(descs, n_images, ok.rows, staging_bytes, n, [&](size_t j) { return items[j].image; },
-                                   [&](size_t j) { return kind.tiles(items[j].width, items[j].out_width, items[j].out_height); },
-                                   "more than 2^31 tiles of output pixels in one sub-batch", gp)) return rc;
-    const RowsPlan& plan = gp.rows; const ItemPlan& order = gp.items;
-    const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
-    return run_staged<ResizeEntry>(c, c->*kind.stats, (long long)plan.refs.size(), kind.kernel, d_streams, stream_offsets, sizes, descs, plan, ok.rows, order,
-        [&](ResizeEntry& t, size_t e) {
-            const size_t j = order.by_ref[e];
-            const qoimi_resize& r = items[j];
-            uint32_t lg, cols;
-            kind.split(r.width, r.out_width, lg, cols);
-            t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]]; t.dst_off = (u64)out_offsets[j];
-            t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
-            t.first_tile = order.first_tile[e]; t.cfg = lg | (cols << 8) | (och << 16) | (weighted << 24) | (r.flags << 28); t.reserved = 0u;
-        },
+    return gather_resampled(kind, c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
+                            accept_any, resize_bytes, accept_outputs, kind.stats, kind.kernel,
         [&](const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
             kind.launch((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
-        }, stream);
+        });
 }
 
 extern "C" size_t qoimi_resize_size(const qoi_desc* desc, const qoimi_resize* item, int channels) { return resample_size(kAreaKind, desc, item, channels); }
@@ -392,37 +356,15 @@ extern "C" int qoimi_warp_orient(const qoi_desc* desc, unsigned x, unsigned y, u
     return QOIMI_OK;
 }
 
-// The plan of qoimi_decode_crops over the items' rectangles (qoi_amd/warp.py: plan); run_staged with one launch of warp_gather over the
-// sub-batch's items.
+// gather_warped (qoi_staged.h) with bytes as the output: one launch of warp_gather over the sub-batch's items.
 extern "C" int qoimi_decode_warped(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                    int n_images, int channels, const qoimi_warp* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
                                    size_t staging_bytes, void* stream) {
-    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
-    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
-    if (const int rc = check_out_channels(channels)) return rc;
-    if (const int rc = check_resize_mode(mode)) return rc;
-    const size_t n = (size_t)n_items;
-    CheckedItems ok;
-    if (const int rc = check_items("item", sizes, descs, n_images, channels, items, n, d_out, out_offsets, warp_item_wrong, warp_bytes, ok)) return rc;
-    const unsigned och = ok.och;
-    GatherPlan gp;
-    if (const int rc = plan_gather(descs, n_images, ok.rows, staging_bytes, n, [&](size_t j) { return items[j].image; },
-                                   [&](size_t j) { return warp_tiles(items[j].out_width, items[j].out_height); },
-                                   "more than 2^31 tiles of output pixels in one sub-batch", gp)) return rc;
-    const RowsPlan& plan = gp.rows; const ItemPlan& order = gp.items;
-    const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
-    return run_staged<WarpEntry>(c, c->warp_stats, (long long)plan.refs.size(), "warp_gather", d_streams, stream_offsets, sizes, descs, plan, ok.rows, order,
-        [&](WarpEntry& t, size_t e) {
-            const size_t j = order.by_ref[e];
-            const qoimi_warp& r = items[j];
-            t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]]; t.dst_off = (u64)out_offsets[j];
-            t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
-            t.first_tile = order.first_tile[e]; t.cfg = och | (weighted << 8) | (r.flags << 16); t.fill = r.fill;
-            t.a = r.a; t.b = r.b; t.d = r.d; t.e = r.e; t.c = r.c; t.f = r.f;
-        },
+    return gather_warped(c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
+                         accept_any, warp_bytes, accept_outputs, &qoimi_ctx::warp_stats, "warp_gather",
         [&](const WarpEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
             launch_warp((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
-        }, stream);
+        });
 }
 
 // ------------------------------------------------------------------------------------

@@ -1,0 +1,114 @@
+// qoi_host_tensor.hip — the tensor calls of the C-ABI shim: qoimi_decode_tensors (the area filter or the antialiased bilinear filter) and
+// qoimi_decode_warped_tensors, with qoimi_tensor_size and qoimi_warp_tensor_size.  They are gather_resampled and gather_warped of qoi_staged.h -
+// the checks of the items, the plan, the table entries and run_staged of qoimi_decode_resized / _bilinear / _warped - with the checks of the
+// format in front, output sizes in bytes of elements, the alignment of the outputs behind, and the tensor kernels of qoi_tensor.hip as the
+// launch.
+#include "qoi_staged.h"
+#include "qoi_tensor_core.h"
+
+#include <math.h>
+#include <stddef.h>
+
+static_assert(sizeof(qoimi_tensor_format) == 48 && offsetof(qoimi_tensor_format, dtype) == 0 && offsetof(qoimi_tensor_format, layout) == 4 &&
+              offsetof(qoimi_tensor_format, scale) == 8 && offsetof(qoimi_tensor_format, bias) == 24 && offsetof(qoimi_tensor_format, reserved) == 40,
+              "qoimi_tensor_format layout");
+static_assert(sizeof(TensorFormat) == 40, "the format is ten dwords of kernel arguments");
+static_assert(QOIMI_TENSOR_U8 == (int)kTensorU8 && QOIMI_TENSOR_F16 == (int)kTensorF16 && QOIMI_TENSOR_BF16 == (int)kTensorBF16 && QOIMI_TENSOR_F32 == (int)kTensorF32 &&
+              QOIMI_TENSOR_HWC == (int)kTensorHWC && QOIMI_TENSOR_CHW == (int)kTensorCHW, "the kernels take dtype and layout as numbers");
+
+// nullptr if the format is fine, else what is wrong with it - in the order the header gives
+static const char* tensor_format_wrong(const qoimi_tensor_format* f) {
+    if (!f) return "format is NULL";
+    if (f->dtype > (unsigned)QOIMI_TENSOR_F32) return "unknown dtype";
+    if (f->layout > (unsigned)QOIMI_TENSOR_CHW) return "unknown layout";
+    if (f->reserved[0] != 0u || f->reserved[1] != 0u) return "format reserved is not 0";
+    for (int k = 0; k < 4; ++k) {
+        if (!isfinite(f->scale[k]) || !isfinite(f->bias[k])) return "scale or bias is not finite";
+    }
+    if (f->dtype == (unsigned)QOIMI_TENSOR_U8) {
+        for (int k = 0; k < 4; ++k) {
+            if (f->scale[k] != 1.0f || f->bias[k] != 0.0f || signbit(f->bias[k])) return "QOIMI_TENSOR_U8 takes scale 1 and bias +0 only";
+        }
+    }
+    return nullptr;
+}
+
+static int check_tensor_format(const qoimi_tensor_format* f) {
+    if (const char* what = tensor_format_wrong(f)) return fail(QOIMI_E_ARG, what);
+    return QOIMI_OK;
+}
+
+static TensorFormat kernel_format(const qoimi_tensor_format* f) {
+    TensorFormat t;
+    t.dtype = f->dtype; t.layout = f->layout;
+    for (int k = 0; k < 4; ++k) { t.scale[k] = f->scale[k]; t.bias[k] = f->bias[k]; }
+    return t;
+}
+
+// pixel_bytes (resize_bytes, warp_bytes: the u8 output) times the element size, false if that does not fit a size_t
+template <class Item>
+static bool tensor_bytes(bool (*pixel_bytes)(const Item*, unsigned, size_t*), const Item* r, unsigned och, size_t elem, size_t* bytes) {
+    size_t b = 0;
+    if (!pixel_bytes(r, och, &b) || b > ~(size_t)0 / elem) return false;
+    *bytes = b * elem;
+    return true;
+}
+
+// Every output begins at a multiple of the element size
+static int check_tensor_alignment(const void* d_out, const size_t* out_offsets, size_t n, size_t elem) {
+    for (size_t j = 0; j < n; ++j) {
+        if (((uintptr_t)d_out + out_offsets[j]) % elem != 0u)
+            return fail(QOIMI_E_ARG, "item " + std::to_string(j) + ": the output address is not a multiple of the element size");
+    }
+    return QOIMI_OK;
+}
+
+static const ResampleKind* tensor_kind(int filter) {
+    return filter == QOIMI_FILTER_AREA ? &kAreaKind : (filter == QOIMI_FILTER_BILINEAR ? &kTentKind : nullptr);
+}
+
+extern "C" size_t qoimi_tensor_size(const qoi_desc* desc, const qoimi_resize* item, int filter, int channels, const qoimi_tensor_format* format) {
+    const ResampleKind* kind = tensor_kind(filter);
+    size_t bytes = 0;
+    if (!kind || !desc_ok(desc) || !item || (channels != 3 && channels != 4) || tensor_format_wrong(format) || kind->wrong(desc, item) ||
+        !tensor_bytes(resize_bytes, item, (unsigned)channels, tensor_elem(format->dtype), &bytes)) return 0;
+    return bytes;
+}
+
+extern "C" size_t qoimi_warp_tensor_size(const qoi_desc* desc, const qoimi_warp* item, int channels, const qoimi_tensor_format* format) {
+    size_t bytes = 0;
+    if (!desc_ok(desc) || !item || (channels != 3 && channels != 4) || tensor_format_wrong(format) || warp_item_wrong(desc, item) ||
+        !tensor_bytes(warp_bytes, item, (unsigned)channels, tensor_elem(format->dtype), &bytes)) return 0;
+    return bytes;
+}
+
+extern "C" int qoimi_decode_tensors(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                    int n_images, int channels, const qoimi_resize* items, int n_items, int filter, int mode,
+                                    const qoimi_tensor_format* format, void* d_out, const size_t* out_offsets, size_t staging_bytes, void* stream) {
+    const ResampleKind* kind = tensor_kind(filter);
+    if (!kind) return fail(QOIMI_E_ARG, "filter must be QOIMI_FILTER_AREA or QOIMI_FILTER_BILINEAR");
+    const size_t elem = (format && format->dtype <= (unsigned)QOIMI_TENSOR_F32) ? tensor_elem(format->dtype) : 1u;   // (used behind the format's check only)
+    const bool area = filter == QOIMI_FILTER_AREA;
+    return gather_resampled(*kind, c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
+        [&]() { return check_tensor_format(format); },
+        [&](const qoimi_resize* r, unsigned och, size_t* bytes) { return tensor_bytes(resize_bytes, r, och, elem, bytes); },
+        [&](const CheckedItems&) { return check_tensor_alignment(d_out, out_offsets, (size_t)n_items, elem); },
+        &qoimi_ctx::tensor_stats, area ? "tensor_area" : "tensor_tent",
+        [&](const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            (area ? launch_tensor_area : launch_tensor_tent)((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, kernel_format(format), grid, st);
+        });
+}
+
+extern "C" int qoimi_decode_warped_tensors(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                                           int n_images, int channels, const qoimi_warp* items, int n_items, int mode,
+                                           const qoimi_tensor_format* format, void* d_out, const size_t* out_offsets, size_t staging_bytes, void* stream) {
+    const size_t elem = (format && format->dtype <= (unsigned)QOIMI_TENSOR_F32) ? tensor_elem(format->dtype) : 1u;   // (used behind the format's check only)
+    return gather_warped(c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
+        [&]() { return check_tensor_format(format); },
+        [&](const qoimi_warp* r, unsigned och, size_t* bytes) { return tensor_bytes(warp_bytes, r, och, elem, bytes); },
+        [&](const CheckedItems&) { return check_tensor_alignment(d_out, out_offsets, (size_t)n_items, elem); },
+        &qoimi_ctx::tensor_stats, "tensor_warp",
+        [&](const WarpEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            launch_tensor_warp((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, kernel_format(format), grid, st);
+        });
+}

@@ -153,6 +153,15 @@ QOIMI_RESIZE_HD void resize_store(const Mem& mem, const ResizeGeom& g, uint64_t 
     if (och == 4u) mem.store1(a + 3u, px >> 24);
 }
 
+// The finish step of a filter tile as a sink - pixel px = (X, Y) of the unflipped result to the output at q - for the calls that write bytes
+// (qoi_tensor_core.h: TensorSink is the other one).
+struct ResizeByteSink {
+    template <class Mem>
+    QOIMI_RESIZE_HD void operator()(const Mem& mem, const ResizeGeom& g, uint64_t q, uint32_t och, uint32_t X, uint32_t Y, uint32_t px) const {
+        resize_store(mem, g, q, och, X, Y, px);
+    }
+};
+
 // The sums of pixel (X, Y) divided by T = cw * rh and stored (resize_store).
 template <class Mem>
 QOIMI_RESIZE_HD void resize_finish(const Mem& mem, const ResizeGeom& g, uint64_t q, uint32_t och, bool weighted, uint32_t X, uint32_t Y, const ResizeSums& s) {

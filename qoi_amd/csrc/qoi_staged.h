@@ -1,6 +1,7 @@
 // qoi_staged.h — what the host files of the calls that decode through bounded staging share (qoi_host_staged.hip: the gather calls,
-// qoi_host_seek.hip: the seek index build and the indexed calls): the checks of a call's items, the plan of a gather call, and run_staged, the
-// driver of "decode a sub-batch into the staging arena, one table-driven launch over it".  Host only; no kernel file includes it.
+// qoi_host_tensor.hip: the tensor calls, qoi_host_seek.hip: the seek index build and the indexed calls): the checks of a call's items, the
+// plan of a gather call, run_staged - the driver of "decode a sub-batch into the staging arena, one table-driven launch over it" - and the
+// bodies of the resampling and warp calls.  Host only; no kernel file includes it.
 #pragma once
 #include "qoi_ctx.h"
 #include "qoi_crop_core.h"
@@ -234,4 +235,94 @@ static int run_staged(qoimi_ctx* c, long long (&stats)[4], long long decoded, co
                       Fill fill, Launch launch, void* stream) {
     return run_staged<Entry>(c, stats, decoded, kernel, d_streams, stream_offsets, sizes, descs, plan, rows, items, fill, launch, stream, (size_t)0,
                              [](uint8_t*, hipStream_t) { return (int)QOIMI_OK; });
+}
+
+// ------------------------------------------------------------------------------------
+// the resampling calls and the warp call, whatever their kernels write (qoi_host_staged.hip: bytes, qoi_host_tensor.hip: tensors)
+// ------------------------------------------------------------------------------------
+// A resampling filter: what is wrong with an item, how an output pixel's columns are split over lanes and the tiles of an item (its core
+// header); and of the call that writes bytes: its launcher, the context's counters of its last call, its kernel's name for a launch failure.
+struct ResampleKind {
+    const char* (*wrong)(const qoi_desc*, const qoimi_resize*);
+    void (*split)(uint32_t cw, uint32_t ow, uint32_t& lg, uint32_t& c);
+    uint64_t (*tiles)(uint32_t cw, uint32_t ow, uint32_t oh);
+    void (*launch)(const uint8_t*, const ResizeEntry*, uint32_t, uint32_t, uint8_t*, uint32_t, hipStream_t);
+    long long (qoimi_ctx::*stats)[4];
+    const char* kernel;
+};
+static const ResampleKind kAreaKind = {resize_item_wrong, resize_split, resize_tiles, launch_resize, &qoimi_ctx::resize_stats, "resize_filter"};
+static const ResampleKind kTentKind = {bilinear_item_wrong, bilinear_split, bilinear_tiles, launch_bilinear, &qoimi_ctx::bilinear_stats, "bilinear_filter"};
+
+// The hooks of a call that has nothing to add to the checks
+static int accept_any() { return QOIMI_OK; }
+static int accept_outputs(const CheckedItems&) { return QOIMI_OK; }
+
+// A resampling call from its arguments to its last launch.  The checks, in this order: NULL / empty arguments, channels, mode, before() - what
+// the call checks of arguments of its own -, the items (check_items with bytes_of(item, och, &bytes), the size of an output),
+// after(checked items) - what it checks of the accepted outputs.  Then the plan of qoimi_decode_crops over the items' rectangles
+// (qoi_amd/resize.py: plan, qoi_amd/bilinear.py: plan) and run_staged with launch(entries, m, tiles, workgroups, stream) once per sub-batch;
+// stats: the context's counters of the call, kernel: the name in the message of a failed launch.
+template <class Before, class Bytes, class After, class Launch>
+static int gather_resampled(const ResampleKind& kind, qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
+                            int n_images, int channels, const qoimi_resize* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
+                            size_t staging_bytes, void* stream, Before before, Bytes bytes_of, After after, long long (qoimi_ctx::*stats)[4], const char* kernel,
+                            Launch launch) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (const int rc = check_out_channels(channels)) return rc;
+    if (const int rc = check_resize_mode(mode)) return rc;
+    if (const int rc = before()) return rc;
+    const size_t n = (size_t)n_items;
+    CheckedItems ok;
+    if (const int rc = check_items("item", sizes, descs, n_images, channels, items, n, d_out, out_offsets, kind.wrong, bytes_of, ok)) return rc;
+    if (const int rc = after(ok)) return rc;
+    const unsigned och = ok.och;
+    GatherPlan gp;
+    if (const int rc = plan_gather(descs, n_images, ok.rows, staging_bytes, n, [&](size_t j) { return items[j].image; },
+                                   [&](size_t j) { return kind.tiles(items[j].width, items[j].out_width, items[j].out_height); },
+                                   "more than 2^31 tiles of output pixels in one sub-batch", gp)) return rc;
+    const RowsPlan& plan = gp.rows; const ItemPlan& order = gp.items;
+    const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
+    return run_staged<ResizeEntry>(c, c->*stats, (long long)plan.refs.size(), kernel, d_streams, stream_offsets, sizes, descs, plan, ok.rows, order,
+        [&](ResizeEntry& t, size_t e) {
+            const size_t j = order.by_ref[e];
+            const qoimi_resize& r = items[j];
+            uint32_t lg, cols;
+            kind.split(r.width, r.out_width, lg, cols);
+            t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]]; t.dst_off = (u64)out_offsets[j];
+            t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
+            t.first_tile = order.first_tile[e]; t.cfg = lg | (cols << 8) | (och << 16) | (weighted << 24) | (r.flags << 28); t.reserved = 0u;
+        }, launch, stream);
+}
+
+// ... and the warp call (the plan: qoi_amd/warp.py: plan).
+template <class Before, class Bytes, class After, class Launch>
+static int gather_warped(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs, int n_images, int channels,
+                         const qoimi_warp* items, int n_items, int mode, void* d_out, const size_t* out_offsets, size_t staging_bytes, void* stream,
+                         Before before, Bytes bytes_of, After after, long long (qoimi_ctx::*stats)[4], const char* kernel, Launch launch) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (const int rc = check_out_channels(channels)) return rc;
+    if (const int rc = check_resize_mode(mode)) return rc;
+    if (const int rc = before()) return rc;
+    const size_t n = (size_t)n_items;
+    CheckedItems ok;
+    if (const int rc = check_items("item", sizes, descs, n_images, channels, items, n, d_out, out_offsets, warp_item_wrong, bytes_of, ok)) return rc;
+    if (const int rc = after(ok)) return rc;
+    const unsigned och = ok.och;
+    GatherPlan gp;
+    if (const int rc = plan_gather(descs, n_images, ok.rows, staging_bytes, n, [&](size_t j) { return items[j].image; },
+                                   [&](size_t j) { return warp_tiles(items[j].out_width, items[j].out_height); },
+                                   "more than 2^31 tiles of output pixels in one sub-batch", gp)) return rc;
+    const RowsPlan& plan = gp.rows; const ItemPlan& order = gp.items;
+    const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
+    return run_staged<WarpEntry>(c, c->*stats, (long long)plan.refs.size(), kernel, d_streams, stream_offsets, sizes, descs, plan, ok.rows, order,
+        [&](WarpEntry& t, size_t e) {
+            const size_t j = order.by_ref[e];
+            const qoimi_warp& r = items[j];
+            t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]]; t.dst_off = (u64)out_offsets[j];
+            t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
+            t.first_tile = order.first_tile[e]; t.cfg = och | (weighted << 8) | (r.flags << 16); t.fill = r.fill;
+            t.a = r.a; t.b = r.b; t.d = r.d; t.e = r.e; t.c = r.c; t.f = r.f;
+        }, launch, stream);
 }

@@ -22,28 +22,14 @@
 //                 shift (the weights of a pixel add up to 2^34) and stores the pixel (qoi_warp_core.h: warp_store): one dword where the
 //                 output holds 4 bytes per pixel and the address is aligned, else 3 or 4 bytes - never a word it would have to read first,
 //                 two outputs may share one.  No LDS, no barrier, no atomics; not one byte outside an item's output is written.
-#include "qoi_dev.h"
-#include "qoi_warp_core.h"
+#include "qoi_gather_tiles.h"
 
 namespace qoimi {
 
-struct WarpMem {
-    const uint32_t* src;
-    __device__ __forceinline__ uint32_t load(u64 i) const { return src[i]; }
-    __device__ __forceinline__ void store1(u64 a, uint32_t v) const { *reinterpret_cast<uint8_t*>(a) = (uint8_t)v; }
-    __device__ __forceinline__ void store4(u64 a, uint32_t v) const { *reinterpret_cast<uint32_t*>(a) = v; }
-};
-
+// (the tile walk: qoi_gather_tiles.h: warp_walk - tensor_warp of qoi_tensor.hip runs it too, with another finish step)
 __global__ __launch_bounds__(kWarpThreads) void warp_gather(const uint8_t* __restrict__ stage, const WarpEntry* __restrict__ tab, uint32_t m, uint32_t tiles,
                                                              uint8_t* out) {
-    walk_tiles(tab, m, tiles, [&](const WarpEntry& e, uint32_t tile) {
-        const WarpMem mem = {reinterpret_cast<const uint32_t*>(stage + e.src_off)};
-        const u64 q = (u64)reinterpret_cast<uintptr_t>(out) + e.dst_off;
-        const WarpGeom g = {e.w, e.x, e.y, e.cw, e.rh, e.ow, e.oh, e.cfg >> 16, e.a, e.b, e.d, e.e, e.fill, e.c, e.f};
-        const uint32_t och = e.cfg & 255u;
-        if ((e.cfg >> 8) & 1u) warp_work<true>(mem, g, q, och, tile, threadIdx.x);
-        else warp_work<false>(mem, g, q, och, tile, threadIdx.x);
-    });
+    warp_walk(stage, tab, m, tiles, out, WarpByteSink());
 }
 
 void launch_warp(const uint8_t* stage, const WarpEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, uint32_t grid, hipStream_t st) {

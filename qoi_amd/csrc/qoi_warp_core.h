@@ -123,12 +123,27 @@ QOIMI_RESIZE_HD void warp_store(const Mem& mem, uint64_t q, uint32_t ow, uint32_
     if (och == 4u) mem.store1(a + 3u, px >> 24);
 }
 
-// Work item t of tile `tile` of the item: its pixel computed and stored, or nothing beyond an edge.
-template <bool WEIGHTED, class Mem>
-QOIMI_RESIZE_HD void warp_work(const Mem& mem, const WarpGeom& g, uint64_t q, uint32_t och, uint32_t tile, uint32_t t) {
+// The finish step of the warp tile as a sink - pixel px = (X, Y) to the output at q - for the call that writes bytes (qoi_tensor_core.h:
+// TensorSink is the other one).
+struct WarpByteSink {
+    template <class Mem>
+    QOIMI_RESIZE_HD void operator()(const Mem& mem, const WarpGeom& g, uint64_t q, uint32_t och, uint32_t X, uint32_t Y, uint32_t px) const {
+        warp_store(mem, q, g.ow, och, X, Y, px);
+    }
+};
+
+// Work item t of tile `tile` of the item: its pixel computed and handed to the sink, or nothing beyond an edge.
+template <bool WEIGHTED, class Mem, class Sink>
+QOIMI_RESIZE_HD void warp_work(const Mem& mem, const WarpGeom& g, uint64_t q, uint32_t och, uint32_t tile, uint32_t t, const Sink& sink) {
     uint32_t X, Y;
     if (!warp_place(tile, t, g.ow, g.oh, X, Y)) return;
-    warp_store(mem, q, g.ow, och, X, Y, warp_pixel<WEIGHTED>(mem, g, X, Y));
+    sink(mem, g, q, och, X, Y, warp_pixel<WEIGHTED>(mem, g, X, Y));
+}
+
+// ... stored as bytes (warp_store)
+template <bool WEIGHTED, class Mem>
+QOIMI_RESIZE_HD void warp_work(const Mem& mem, const WarpGeom& g, uint64_t q, uint32_t och, uint32_t tile, uint32_t t) {
+    warp_work<WEIGHTED>(mem, g, q, och, tile, t, WarpByteSink());
 }
 
 }  // namespace qoimi
