@@ -252,6 +252,75 @@ int qoimi_encode_images_packed(qoimi_ctx *ctx, const void *d_pixels, const size_
                                unsigned long long *d_packed_off, int *d_stream_len, size_t staging_bytes,
                                unsigned long long *packed_off_out, int *stream_len_out, void *stream);
 
+/* Tiles and pyramid levels of device images as a pack: the ingest side of the tile server the gather calls below serve.  The caller holds
+ * images in device memory, tightly packed as qoimi_encode_images takes them, and names TILES; it never owns a tile's pixels or a strided stream.
+ * The result (normative; qoi_amd/tiles.py: tile states it in Python by composing the models of the calls below).  For tile j, S is image
+ * tiles[j].image as the caller holds it, sch = descs[image].channels bytes per pixel; R = S[y .. y + height) x [x .. x + width); T is the
+ * qoimi_decode_thumbnails reduction of R by `factor` in `mode` at sch channels (with 3 channels QOIMI_THUMB_ALPHA_WEIGHTED is PLAIN, as
+ * everywhere), tw = ceil(width / factor) by th = ceil(height / factor) pixels; T is mirrored as qoimi_decode_crops mirrors (QOIMI_CROP_FLIP_X /
+ * _Y), then converted to och = channels, or sch when channels is 0 (tiles of 3- and 4-channel images then mix in one call): 4 to 3 drops
+ * alpha - after the reduction, so an alpha-weighted reduction keeps its colours -, 3 to 4 sets alpha to 255.  Stream j is the reference
+ * encoder's stream, byte for byte, of T with the descriptor {tw, th, och, descs[image].colorspace}.  The pack, d_packed_off[0 .. n_tiles],
+ * d_stream_len and the two host tables are exactly what qoimi_encode_images_packed gives over the n_tiles images T in tile order: align, the
+ * "a stream that does not fit WHOLLY is not copied, not in part" rule, packed_capacity 0, an overflow returning QOIMI_OK and "nothing at or
+ * behind d_packed + packed_capacity is written" included.  A tile with factor 1, no flip and och == sch is the rectangle itself; a tile
+ * that is a whole image gives qoimi_encode_images' stream.
+ *   d_pixels, pixel_offsets, descs   as for qoimi_encode_images: ANY byte offsets, odd ones for 4-channel images too.  d_pixels is only read;
+ *                  of an image nothing is read but the aligned 4-byte words that hold one of its bytes; an image that no tile names is not
+ *                  read and its descs[i] is not even checked
+ *   tiles          HOST qoimi_tile[n_tiles], in any order of image; they may overlap or coincide
+ *   tile_descs_out HOST qoi_desc[n_tiles], may be NULL: the tiles' descriptors - with packed_off_out and stream_len_out all that
+ *                  qoimi_decode_images and the gather calls need to serve the pack
+ *   staging_bytes  device memory the call may hold for gathered pixels and strided streams: the staging arena of qoimi_encode_packed, counted in
+ *                  qoimi_workspace_bytes [0] (56 + 8 bytes per tile for two tables beside it).  0: 1 GiB.  The plan (normative; qoi_amd/tiles.py:
+ *                  plan): tile j's slot is tw * th * och rounded up to 256 plus qoimi_encode_bound of its descriptor rounded up to 256; sub-batches
+ *                  are cut by qoi_amd/packplan.py: plan over those slots in tile order (a request smaller than one slot is raised to that slot).
+ * Every sub-batch is one launch of the gather kernel over its tiles on `stream`, which writes them tightly packed into the pixel parts of their
+ * slots, one qoimi_encode_images call as it is from there into the stream parts, qoimi_encode_status, and the pack's append - the loop of
+ * qoimi_encode_images_packed.  SYNCHRONOUS, and as there: each sub-batch counts as ONE encode call for the LDS-order self-test; afterwards
+ * qoimi_encode_status returns QOIMI_OK and never encodes again.
+ * QOIMI_E_ARG, reported before anything is launched (the caller's buffers are untouched, qoimi_last_error names the cause): NULL ctx, d_pixels,
+ * pixel_offsets, descs, tiles, d_packed_off or d_stream_len; n_images <= 0 or n_tiles <= 0; d_packed == NULL with a non-zero capacity; align not
+ * a power of two in 1..256; channels not 0 / 3 / 4; a mode that is neither of the two; tiles[j].image >= n_images; a rejected referenced
+ * descriptor; a zero width or height; a rectangle that leaves its image; a factor outside 1..64; a flag bit other than the two flips;
+ * reserved != 0; a referenced image whose last byte's address does not fit in a pointer; a referenced image whose bytes overlap [d_packed,
+ * + packed_capacity); a sub-batch of the plan with 2^31 - 1 or more tiles of 256 work items of the gather kernel (an item is one aligned
+ * 16-byte word of a tile's pixels at factor 1, else 1 to 16 per output pixel).  One call at a time per context, as everywhere.
+ * Not here: sources that are a pack (decode once with qoimi_decode_images), other filters, row-pitched sources, a channel count per tile. */
+typedef struct {                 /* 32 bytes, offsets 0/4/8/12/16/20/24/28 */
+    unsigned int image;          /* index into the call's images */
+    unsigned int x, y;           /* top-left corner of the source rectangle */
+    unsigned int width, height;  /* both >= 1; the rectangle lies inside the image */
+    unsigned int factor;         /* 1..64 */
+    unsigned int flags;          /* QOIMI_CROP_FLIP_X / _Y; no other bit */
+    unsigned int reserved;       /* 0 */
+} qoimi_tile;
+int qoimi_encode_tiles(qoimi_ctx *ctx, const void *d_pixels, const size_t *pixel_offsets /* host */, const qoi_desc *descs /* host */, int n_images,
+                       int channels /* 0, 3, 4 */, const qoimi_tile *tiles /* host */, int n_tiles, int mode /* QOIMI_THUMB_PLAIN / _ALPHA_WEIGHTED */,
+                       unsigned align, void *d_packed, size_t packed_capacity,
+                       unsigned long long *d_packed_off /* device, n_tiles + 1 */, int *d_stream_len /* device, n_tiles */, size_t staging_bytes,
+                       unsigned long long *packed_off_out /* host, may be NULL */, int *stream_len_out /* host, may be NULL */,
+                       qoi_desc *tile_descs_out /* host, n_tiles, may be NULL */, void *stream);
+
+/* tw = ceil(tile->width / factor), th = ceil(tile->height / factor); returns tw * th * och (och = channels, or desc->channels when channels is
+ * 0) - the bytes of the tile's pixels - or 0 if desc is rejected, tile is NULL, has a zero width or height, leaves the image of desc, has a
+ * factor outside 1..64, an unknown flag bit or reserved != 0, or channels is not 0 / 3 / 4 (tw / th are then left alone; tile->image is not
+ * looked at).  Pure host arithmetic: no context, no GPU.  tw / th may be NULL. */
+size_t qoimi_tile_size(const qoi_desc *desc, const qoimi_tile *tile, int channels, unsigned *tw, unsigned *th);
+
+/* The tiles of a pyramid of `levels` levels over one image, in the order level, row, column.  Level l = 0 .. levels - 1 has f = 2^l; its
+ * image is Lw = ceil(w / f) by Lh = ceil(h / f) and is cut into ceil(Lh / tile_h) rows of ceil(Lw / tile_w) tiles; tile (l, row, col) is
+ * x = col * tile_w * f, y = row * tile_h * f, width = min(tile_w * f, w - x), height = min(tile_h * f, h - y), factor = f, image, flags and
+ * reserved 0.  Every x and y is a multiple of f, so the tiles of level l are exactly the qoimi_decode_thumbnails reduction of the whole image
+ * at 2^l cut on the grid: each level is ONE rounding from the full-resolution pixels, not a chain of halvings.  Returns the number of tiles
+ * and fills out[0 .. that) when out is not NULL; QOIMI_E_ARG for a rejected descriptor, tile_w or tile_h of 0 or above 2^24, levels outside
+ * 1..7, a non-NULL out with cap too small, more than 2^31 - 1 tiles.  Pure host arithmetic: no context, no GPU. */
+int qoimi_tile_pyramid(const qoi_desc *desc, unsigned tile_w, unsigned tile_h, unsigned levels, qoimi_tile *out /* may be NULL */, int cap);
+
+/* Of the context's last qoimi_encode_tiles call: [0] sub-batches, [1] launches of the gather kernel (it has no entry in qoimi_kernel_name),
+ * [2] bytes of the staging the call planned for (its largest sub-batch), [3] images referenced. */
+void qoimi_tile_stats(qoimi_ctx *ctx, long long out[4]);
+
 /* What makes a pack self-describing: the header of every stream, read on the device and parsed by the rules of qoi.h:497-521.
  *   stream_offsets, sizes  HOST arrays as for qoimi_decode_images
  *   descs_out      HOST qoi_desc[n_streams]: filled for every stream of 22 bytes or more, valid or not (as qoi_decode fills *desc before
@@ -667,7 +736,7 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * reported before anything is launched, the caller's buffers are untouched; qoimi_last_error names the cause.  The sub-batches count as decode
  * calls of the context.  One call at a time per context, as everywhere.
  * Not here: indexed forms, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
- * size of its rectangle, or divides it, is those), anything on the encode side. */
+ * size of its rectangle, or divides it, is those), tensors as the source of an encode (qoimi_encode_tiles takes bytes). */
 enum { QOIMI_TENSOR_U8 = 0, QOIMI_TENSOR_F16 = 1, QOIMI_TENSOR_BF16 = 2, QOIMI_TENSOR_F32 = 3 };   /* element sizes 1 / 2 / 2 / 4 */
 enum { QOIMI_TENSOR_HWC = 0, QOIMI_TENSOR_CHW = 1 };
 enum { QOIMI_FILTER_AREA = 0, QOIMI_FILTER_BILINEAR = 1 };
@@ -948,7 +1017,7 @@ int qoimi_hash_streams(qoimi_ctx *ctx, const void *d_streams, size_t stream_stri
                        unsigned long long *d_hash, void *stream);
 
 /* Device memory the context's growable arenas hold at the moment (bytes): [0] encode workspace (and the staging arena of
- * qoimi_encode_packed), [1] decode workspace
+ * qoimi_encode_packed and qoimi_encode_tiles, which holds the gathered tiles, their strided streams and the tile table), [1] decode workspace
  * (and the tables of qoimi_inspect_streams, the tables of qoimi_compare_images, the tables and the staging arena of qoimi_verify_images,
  * qoimi_decode_thumbnails, qoimi_decode_crops, qoimi_decode_resized, qoimi_decode_bilinear, qoimi_pixel_stats and qoimi_build_seek_index, which share them, the tables of
  * qoimi_build_seek_index and qoimi_seek_index_from_pixels and the band arena of the indexed calls),

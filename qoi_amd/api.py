@@ -48,6 +48,7 @@ EXPORTS = (
     "qoimi_decode_bilinear", "qoimi_bilinear_size", "qoimi_bilinear_stats", "qoimi_decode_bilinear_indexed",
     "qoimi_decode_warped", "qoimi_warp_size", "qoimi_warp_stats", "qoimi_warp_orient", "qoimi_decode_warped_indexed",
     "qoimi_decode_tensors", "qoimi_decode_warped_tensors", "qoimi_tensor_size", "qoimi_warp_tensor_size", "qoimi_tensor_stats",
+    "qoimi_encode_tiles", "qoimi_tile_size", "qoimi_tile_pyramid", "qoimi_tile_stats",
 )
 
 
@@ -79,6 +80,16 @@ class QoimiCrop(ctypes.Structure):
 
 
 assert ctypes.sizeof(QoimiCrop) == 24 and [getattr(QoimiCrop, f).offset for f, _ in QoimiCrop._fields_] == [0, 4, 8, 12, 16, 20]
+
+
+class QoimiTile(ctypes.Structure):
+    """``qoimi_tile``: 32 bytes - a rectangle of image ``image``, the factor it is box-reduced by and how the result is mirrored
+    (``tiles.FLIP_X`` / ``tiles.FLIP_Y``); ``reserved`` is 0."""
+    _fields_ = [("image", ctypes.c_uint), ("x", ctypes.c_uint), ("y", ctypes.c_uint), ("width", ctypes.c_uint), ("height", ctypes.c_uint),
+                ("factor", ctypes.c_uint), ("flags", ctypes.c_uint), ("reserved", ctypes.c_uint)]
+
+
+assert ctypes.sizeof(QoimiTile) == 32 and [getattr(QoimiTile, f).offset for f, _ in QoimiTile._fields_] == [0, 4, 8, 12, 16, 20, 24, 28]
 
 
 class QoimiResize(ctypes.Structure):
@@ -239,6 +250,15 @@ def load_library() -> ctypes.CDLL:
     lib.qoimi_crop_size.argtypes = [dp, cp, ci]
     lib.qoimi_crop_stats.restype = None
     lib.qoimi_crop_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+    tp = ctypes.POINTER(QoimiTile)
+    lib.qoimi_encode_tiles.restype = ci
+    lib.qoimi_encode_tiles.argtypes = [vp, vp, szp, dp, ci, ci, tp, ci, ci, ctypes.c_uint, vp, sz, vp, vp, sz, ullp, ctypes.POINTER(ci), dp, vp]
+    lib.qoimi_tile_size.restype = sz
+    lib.qoimi_tile_size.argtypes = [dp, tp, ci, up, up]
+    lib.qoimi_tile_pyramid.restype = ci
+    lib.qoimi_tile_pyramid.argtypes = [dp, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, tp, ci]
+    lib.qoimi_tile_stats.restype = None
+    lib.qoimi_tile_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
     rp = ctypes.POINTER(QoimiResize)
     lib.qoimi_decode_resized.restype = ci
     lib.qoimi_decode_resized.argtypes = [vp, vp, szp, ctypes.POINTER(ci), dp, ci, ci, rp, ci, ci, vp, szp, sz, vp]
@@ -344,6 +364,42 @@ def crop_size(width: int, height: int, channels_in: int, crop, channels: int) ->
     if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
         return 0
     return int(load_library().qoimi_crop_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels))
+
+
+def _tile_array(tiles):
+    """tiles as a ``QoimiTile`` array: a sequence of such structures or of (image, x, y, width, height, factor[, flags[, reserved]]) tuples;
+    None if a tuple has another length or a field does not fit an unsigned int."""
+    rows = [tuple(getattr(t, f) for f, _ in QoimiTile._fields_) if isinstance(t, QoimiTile) else tuple(int(v) for v in t) for t in tiles]
+    if any(not 6 <= len(r) <= 8 or any(not 0 <= v < 2 ** 32 for v in r) for r in rows):
+        return None
+    return (QoimiTile * len(rows))(*[QoimiTile(*r) for r in rows])
+
+
+def tile_size(width: int, height: int, channels_in: int, tile, channels: int = 0):
+    """``qoimi_tile_size`` for an image of width x height x channels_in: (bytes, tw, th) of the pixels of `tile` (a ``QoimiTile`` or an
+    (image, x, y, width, height, factor[, flags[, reserved]]) tuple) at `channels` (0: channels_in) bytes per pixel; (0, 0, 0) where the C
+    function returns 0."""
+    arr = _tile_array([tile])
+    if arr is None or not (0 <= width < 2 ** 32 and 0 <= height < 2 ** 32 and 0 <= channels_in < 256):
+        return 0, 0, 0
+    tw, th = ctypes.c_uint(0), ctypes.c_uint(0)
+    n = int(load_library().qoimi_tile_size(ctypes.byref(QoiDesc(width, height, channels_in, 0)), arr, channels, ctypes.byref(tw), ctypes.byref(th)))
+    return n, tw.value, th.value
+
+
+def tile_pyramid(width: int, height: int, channels_in: int, tile_w: int, tile_h: int, levels: int):
+    """``qoimi_tile_pyramid``: the tiles of a pyramid of `levels` levels over one image as a list of ``QoimiTile`` (image 0), in the order
+    level, row, column; ``tiles.pyramid`` states them.  Raises ``QoiError`` where the C function returns QOIMI_E_ARG."""
+    ok = all(0 <= int(v) < 2 ** 32 for v in (width, height, tile_w, tile_h, levels)) and 0 <= channels_in < 256
+    lib = load_library()
+    desc = QoiDesc(width, height, channels_in, 0) if ok else QoiDesc(0, 0, 0, 0)
+    n = lib.qoimi_tile_pyramid(ctypes.byref(desc), tile_w if ok else 0, tile_h if ok else 0, levels if ok else 0, None, 0)
+    if n < 0:
+        raise QoiError("qoimi_tile_pyramid: " + last_error())
+    arr = (QoimiTile * n)()
+    if lib.qoimi_tile_pyramid(ctypes.byref(desc), tile_w, tile_h, levels, arr, n) != n:
+        raise QoiError("qoimi_tile_pyramid: " + last_error())
+    return list(arr)
 
 
 def _resize_array(items):
@@ -650,6 +706,32 @@ class Context:
                                                          d_packed_off, d_stream_len, staging_bytes, off.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)),
                                                          sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), stream), "qoimi_encode_images_packed")
         return off, sizes
+
+    def encode_tiles(self, d_pixels: int, pixel_offsets: Sequence[int], descs: Sequence[QoiDesc], channels: int, tiles, mode: int, align: int,
+                     d_packed: int, packed_capacity: int, d_packed_off: int, d_stream_len: int, staging_bytes: int = 0, stream: int = 0):
+        """Tiles and pyramid levels of device images -> pack in one call through bounded staging (``qoimi_encode_tiles``, synchronous):
+        (offsets uint64[n + 1], sizes int32[n], tile descriptors) - what ``decode_images`` and the gather calls take to serve the pack.
+        tiles: ``QoimiTile`` structures or (image, x, y, width, height, factor[, flags]) tuples; mode: ``tiles.PLAIN`` /
+        ``tiles.ALPHA_WEIGHTED``; channels 0: every tile keeps its image's channel count; ``qoi_amd/tiles.py: tile`` states the pixels."""
+        n_images = len(descs)
+        if len(pixel_offsets) != n_images:
+            raise QoiError("encode_tiles: one pixel offset per descriptor")
+        arr = _tile_array(tiles)
+        if arr is None:
+            raise QoiError("encode_tiles: a tile is (image, x, y, width, height, factor[, flags[, reserved]]) of unsigned 32-bit values")
+        n = len(arr)
+        po = (ctypes.c_size_t * max(n_images, 1))(*[int(x) for x in pixel_offsets])
+        off, sizes = np.zeros(n + 1, dtype=np.uint64), np.zeros(n, dtype=np.intc)
+        tds = (QoiDesc * max(n, 1))()
+        self._check(self._lib.qoimi_encode_tiles(self._h, d_pixels, po, (QoiDesc * max(n_images, 1))(*descs), n_images, channels, arr, n, mode, align,
+                                                 d_packed, packed_capacity, d_packed_off, d_stream_len, staging_bytes,
+                                                 off.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                 tds, stream), "qoimi_encode_tiles")
+        return off, sizes, list(tds)[:n]
+
+    def tile_stats(self) -> Tuple[int, int, int, int]:
+        """Of the last ``encode_tiles`` call: (sub-batches, launches of the gather kernel, bytes of staging planned, images referenced)."""
+        return self._four_counters(self._lib.qoimi_tile_stats)
 
     def read_descs(self, d_streams: int, stream_offsets: Sequence[int], sizes: Sequence[int], stream: int = 0):
         """The headers of the streams of a pack: (descs, first_bad) - first_bad is None when every stream passes the rules of
@@ -1059,7 +1141,7 @@ class Context:
         return {self._lib.qoimi_kernel_name(i).decode(): (ms[i], calls[i]) for i in range(1, n)}
 
     def workspace_bytes(self) -> dict:
-        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops`` / ``decode_resized`` / ``decode_bilinear`` / ``pixel_stats``, the tables of ``build_seek_index`` / ``seek_index_from_pixels`` and the band arena of the indexed calls), staging of the host-pointer entry points."""
+        """Device bytes the context's arenas hold: encode workspace (with the staging of ``encode_packed`` and ``encode_tiles``), decode workspace (with the tables of ``inspect_streams`` and ``compare_images`` and the staging of ``verify_images`` / ``decode_thumbnails`` / ``decode_crops`` / ``decode_resized`` / ``decode_bilinear`` / ``pixel_stats``, the tables of ``build_seek_index`` / ``seek_index_from_pixels`` and the band arena of the indexed calls), staging of the host-pointer entry points."""
         out = (ctypes.c_size_t * 3)()
         self._lib.qoimi_workspace_bytes(self._h, out)
         return {"encode": int(out[0]), "decode": int(out[1]), "staging": int(out[2])}

@@ -169,7 +169,7 @@ extern "C" int qoimi_set_encode_small_call_order(qoimi_ctx* c, int by_workgroup_
     return QOIMI_OK;
 }
 
-// device memory the context holds: [0] encode workspace (and the staging of qoimi_encode_packed), [1] decode workspace (and the tables of
+// device memory the context holds: [0] encode workspace (and the staging of qoimi_encode_packed and qoimi_encode_tiles), [1] decode workspace (and the tables of
 // qoimi_inspect_streams, the tables and the staging of qoimi_compare_images / qoimi_verify_images / qoimi_decode_thumbnails / qoimi_decode_crops / qoimi_decode_resized, the band arena of qoimi_decode_crops_indexed), [2] staging of the
 // host-pointer entry points
 extern "C" void qoimi_workspace_bytes(qoimi_ctx* c, size_t out[3]) {
@@ -186,6 +186,7 @@ extern "C" void qoimi_warp_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c 
 extern "C" void qoimi_tensor_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->tensor_stats : nullptr, out); }
 extern "C" void qoimi_pixel_stats_counters(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->pixel_stats : nullptr, out); }
 extern "C" void qoimi_seek_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->seek_stats : nullptr, out); }
+extern "C" void qoimi_tile_stats(qoimi_ctx* c, long long out[4]) { copy_stats(c ? c->tile_stats : nullptr, out); }
 
 // ------------------------------------------------------------------------------------
 // synthetic frames

@@ -1,6 +1,7 @@
 // qoi_host_pack.hip — packs of streams in the C-ABI shim: qoimi_pack_streams, qoimi_encode_packed / qoimi_encode_images_packed,
-// qoimi_read_descs, qoimi_inspect_streams.
+// qoimi_encode_tiles / qoimi_tile_size / qoimi_tile_pyramid, qoimi_read_descs, qoimi_inspect_streams.
 #include "qoi_ctx.h"
+#include "qoi_tile_core.h"
 
 // ------------------------------------------------------------------------------------
 // packed streams
@@ -27,44 +28,54 @@ extern "C" int qoimi_pack_streams(qoimi_ctx* c, const void* d_streams, size_t st
 // encode into a pack through bounded staging
 // ------------------------------------------------------------------------------------
 // (the sub-batch plan: qoi_stage_plan.h: stage_plan)
-// Both entry points: descs holds one descriptor (pixel_offsets == nullptr: image i at i * pixel_stride) or n_images of them.  Every sub-batch
-// is one call of the encoder as it is into the staging arena, qoimi_encode_status (which waits for it and encodes it again order-free if a
-// placement wait gave up: the pack never takes bytes of a sub-batch whose status has not been looked at), then the append scan and copy on the
-// caller's stream; the next sub-batch's encoder is ordered behind that copy by the stream.
-static int encode_packed(qoimi_ctx* c, const void* d_pixels, size_t pixel_stride, const size_t* pixel_offsets, const qoi_desc* descs, int n_images,
+// What a call's sub-batches are encoded from: the caller's pixels as the entry points take them (pixel_offsets == nullptr: image i at
+// i * pixel_stride, descs holds one descriptor; else n_images of each) - or, px_part != nullptr (qoimi_encode_tiles), images that the
+// call itself puts into the staging: image i's pixels then stand at the front of its slot, px_part[i] bytes (a multiple of 256), and
+// its stream goes behind them.  extra: bytes of a table of the call's own that travels with the source offsets (256-aligned behind
+// them in the pinned staging and in the arena).
+struct PackPixels { const void* d_pixels; size_t pixel_stride; const size_t* pixel_offsets; const qoi_desc* descs; const size_t* px_part; size_t extra; };
+
+// The loop both calls share.  slots, plan: the staging slot of every image and stage_plan over them.  begin(pinned table, its copy's
+// address on the device) fills the call's own table before it is sent; front(k, first, m, staging, stream) runs in front of sub-batch
+// k's encoder - images [first, first + m) - on the caller's stream.  Then every sub-batch is one call of the encoder as it is into the
+// staging arena, qoimi_encode_status (which waits for it and encodes it again order-free if a placement wait gave up: the pack never takes
+// bytes of a sub-batch whose status has not been looked at), then the append scan and copy on the caller's stream; the next sub-batch's
+// front and encoder are ordered behind that copy by the stream.
+template <class Begin, class Front>
+static int encode_packed(qoimi_ctx* c, const PackPixels& px, int n_images, const std::vector<size_t>& slots, const StagePlan& plan,
                          unsigned align, void* d_packed, size_t packed_capacity, unsigned long long* d_packed_off, int* d_stream_len,
-                         size_t staging_bytes, unsigned long long* packed_off_out, int* stream_len_out, void* stream) {
-    const bool mixed = pixel_offsets != nullptr;
+                         unsigned long long* packed_off_out, int* stream_len_out, void* stream, Begin begin, Front front) {
+    const bool staged = px.px_part != nullptr, mixed = staged || px.pixel_offsets != nullptr;
     const size_t n = (size_t)n_images;
-    std::vector<size_t> slots(n);
     size_t largest = 0;
-    for (size_t i = 0; i < n; ++i) {
-        slots[i] = up256(qoimi_encode_bound(&descs[mixed ? i : 0]));
-        if (slots[i] > largest) largest = slots[i];
-    }
-    const StagePlan plan = stage_plan(slots, staging_bytes);
+    for (size_t i = 0; i < n; ++i) if (slots[i] > largest) largest = slots[i];
     const std::vector<int>& firsts = plan.firsts;
-    const std::vector<size_t>& src = plan.at;                // where stream i lies in the staging of its sub-batch
+    std::vector<size_t> src(plan.at);                        // where stream i lies in the staging of its sub-batch
+    if (staged) for (size_t i = 0; i < n; ++i) src[i] += px.px_part[i];
     const size_t need = plan.need;
     DeviceGuard guard(c->device);
     hipStream_t st = (hipStream_t)stream;
     if (const int rc = wait_decode_tail(c, stream)) return rc;
-    const size_t table_bytes = mixed ? (n * sizeof(u64) + 255u) & ~(size_t)255u : 0;
+    const size_t table_bytes = (mixed ? up256(n * sizeof(u64)) : 0) + px.extra;
     { int rc = c->enc_stage.reserve(table_bytes + need); if (rc) return rc; }
-    { int rc = c->pin.reserve((n + 1u) * sizeof(u64) + n * sizeof(int) + 256u); if (rc) return rc; }
+    { int rc = c->pin.reserve(std::max(table_bytes, (n + 1u) * sizeof(u64) + n * sizeof(int)) + 256u); if (rc) return rc; }
     u64* const d_src = mixed ? (u64*)c->enc_stage.base : nullptr;
     uint8_t* const staging = (uint8_t*)c->enc_stage.base + table_bytes;
     if (mixed) {                                             // where stream j lies in the staging of its sub-batch: one table for the whole call
         for (size_t i = 0; i < n; ++i) ((u64*)c->pin.buf)[i] = (u64)src[i];
-        HIP_TRY(hipMemcpyAsync(d_src, c->pin.buf, n * sizeof(u64), hipMemcpyHostToDevice, st));
+        if (px.extra != 0u) { const int rc = begin((uint8_t*)c->pin.buf + (table_bytes - px.extra), (uint8_t*)c->enc_stage.base + (table_bytes - px.extra)); if (rc) return rc; }
+        HIP_TRY(hipMemcpyAsync(d_src, c->pin.buf, px.extra != 0u ? table_bytes : n * sizeof(u64), hipMemcpyHostToDevice, st));
     }
     int rc = QOIMI_OK;
     for (size_t k = 0; k + 1 < firsts.size() && rc == QOIMI_OK; ++k) {
         const int first = firsts[k], m = firsts[k + 1] - first;
         size_t span = 0;
-        for (int i = first; i < first + m; ++i) span += slots[(size_t)i];
-        rc = mixed ? qoimi_encode_images(c, d_pixels, pixel_offsets + first, descs + first, m, staging, src.data() + first, d_stream_len + first, stream)
-                   : qoimi_encode_batch(c, (const uint8_t*)d_pixels + (size_t)first * pixel_stride, pixel_stride, descs, m, staging, largest, d_stream_len + first, stream);
+        for (int i = first; i < first + m; ++i) span += slots[(size_t)i] - (staged ? px.px_part[(size_t)i] : 0u);
+        rc = front(k, first, m, staging, st);
+        if (rc != QOIMI_OK) break;
+        rc = staged ? qoimi_encode_images(c, staging, plan.at.data() + first, px.descs + first, m, staging, src.data() + first, d_stream_len + first, stream)
+           : mixed  ? qoimi_encode_images(c, px.d_pixels, px.pixel_offsets + first, px.descs + first, m, staging, src.data() + first, d_stream_len + first, stream)
+                    : qoimi_encode_batch(c, (const uint8_t*)px.d_pixels + (size_t)first * px.pixel_stride, px.pixel_stride, px.descs, m, staging, largest, d_stream_len + first, stream);
         if (rc == QOIMI_OK) rc = qoimi_encode_status(c, stream);
         if (rc != QOIMI_OK) break;
         if (const int full = timer_room(c, st)) return full;
@@ -85,6 +96,19 @@ static int encode_packed(qoimi_ctx* c, const void* d_pixels, size_t pixel_stride
     if (packed_off_out) memcpy(packed_off_out, h_off, (n + 1u) * sizeof(u64));
     if (stream_len_out) memcpy(stream_len_out, h_len, n * sizeof(int));
     return QOIMI_OK;
+}
+
+// Both entry points of the caller's own pixels: descs holds one descriptor (pixel_offsets == nullptr) or n_images of them; a slot is the
+// image's encode bound rounded up to 256.
+static int encode_packed(qoimi_ctx* c, const void* d_pixels, size_t pixel_stride, const size_t* pixel_offsets, const qoi_desc* descs, int n_images,
+                         unsigned align, void* d_packed, size_t packed_capacity, unsigned long long* d_packed_off, int* d_stream_len,
+                         size_t staging_bytes, unsigned long long* packed_off_out, int* stream_len_out, void* stream) {
+    std::vector<size_t> slots((size_t)n_images);
+    for (size_t i = 0; i < slots.size(); ++i) slots[i] = up256(qoimi_encode_bound(&descs[pixel_offsets ? i : 0]));
+    const StagePlan plan = stage_plan(slots, staging_bytes);
+    const PackPixels px = {d_pixels, pixel_stride, pixel_offsets, descs, nullptr, 0u};
+    return encode_packed(c, px, n_images, slots, plan, align, d_packed, packed_capacity, d_packed_off, d_stream_len, packed_off_out, stream_len_out, stream,
+                         [](uint8_t*, uint8_t*) { return (int)QOIMI_OK; }, [](size_t, int, int, uint8_t*, hipStream_t) { return (int)QOIMI_OK; });
 }
 
 static int encode_packed_args(qoimi_ctx* c, const void* d_pixels, int n_images, unsigned align, void* d_packed, size_t packed_capacity,
@@ -112,6 +136,146 @@ extern "C" int qoimi_encode_images_packed(qoimi_ctx* c, const void* d_pixels, co
     for (int i = 0; i < n_images; ++i) if (!desc_ok(&descs[i])) return fail(QOIMI_E_ARG, "descriptor rejected (qoi.h:364-372 rules)");
     return encode_packed(c, d_pixels, 0, pixel_offsets, descs, n_images, align, d_packed, packed_capacity, d_packed_off, d_stream_len,
                          staging_bytes, packed_off_out, stream_len_out, stream);
+}
+
+// ------------------------------------------------------------------------------------
+// tiles and pyramid levels of device images as a pack (qoi_tile.hip)
+// ------------------------------------------------------------------------------------
+static_assert(sizeof(qoimi_tile) == 32 && offsetof(qoimi_tile, image) == 0 && offsetof(qoimi_tile, x) == 4 && offsetof(qoimi_tile, y) == 8 &&
+              offsetof(qoimi_tile, width) == 12 && offsetof(qoimi_tile, height) == 16 && offsetof(qoimi_tile, factor) == 20 &&
+              offsetof(qoimi_tile, flags) == 24 && offsetof(qoimi_tile, reserved) == 28, "qoimi_tile layout");
+static_assert(QOIMI_CROP_FLIP_X == (int)kCropFlipX && QOIMI_CROP_FLIP_Y == (int)kCropFlipY, "the table's flag bits");
+
+// nullptr if the tile is fine for an accepted descriptor, else what is wrong with it
+static const char* tile_wrong(const qoi_desc* d, const qoimi_tile* t) {
+    if (t->width == 0u || t->height == 0u) return "zero width or height";
+    if ((uint64_t)t->x + t->width > d->width || (uint64_t)t->y + t->height > d->height) return "the rectangle leaves its image";
+    if (t->factor < 1u || t->factor > kThumbMaxFactor) return "factor outside 1..64";
+    if ((t->flags & ~(unsigned)(QOIMI_CROP_FLIP_X | QOIMI_CROP_FLIP_Y)) != 0u) return "unknown flag bit";
+    if (t->reserved != 0u) return "reserved is not 0";
+    return nullptr;
+}
+
+extern "C" size_t qoimi_tile_size(const qoi_desc* desc, const qoimi_tile* tile, int channels, unsigned* tw, unsigned* th) {
+    if (!desc_ok(desc) || !tile || (channels != 0 && channels != 3 && channels != 4) || tile_wrong(desc, tile)) return 0;
+    const uint32_t x = thumb_extent(tile->width, tile->factor), y = thumb_extent(tile->height, tile->factor);
+    if (tw) *tw = x;
+    if (th) *th = y;
+    return (size_t)x * y * (size_t)(channels ? channels : desc->channels);
+}
+
+extern "C" int qoimi_tile_pyramid(const qoi_desc* desc, unsigned tile_w, unsigned tile_h, unsigned levels, qoimi_tile* out, int cap) {
+    if (!desc_ok(desc)) return fail(QOIMI_E_ARG, "descriptor rejected (qoi.h:364-372 rules)");
+    if (tile_w == 0u || tile_h == 0u || tile_w > (1u << 24) || tile_h > (1u << 24)) return fail(QOIMI_E_ARG, "tile_w and tile_h must be 1..2^24");
+    if (levels < 1u || levels > 7u) return fail(QOIMI_E_ARG, "levels must be 1..7");
+    uint64_t total = 0;
+    for (unsigned l = 0; l < levels; ++l) {
+        const uint32_t f = 1u << l;
+        total += (uint64_t)thumb_extent(thumb_extent(desc->height, f), tile_h) * thumb_extent(thumb_extent(desc->width, f), tile_w);
+    }
+    if (total > 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 - 1 tiles");
+    if (!out) return (int)total;
+    if (cap < 0 || (uint64_t)cap < total) return fail(QOIMI_E_ARG, "cap is smaller than the number of tiles");
+    qoimi_tile* t = out;
+    for (unsigned l = 0; l < levels; ++l) {
+        const uint32_t f = 1u << l, sw = tile_w * f, sh = tile_h * f;        // (2^24 * 64: the source side of a tile fits 32 bits)
+        const uint32_t rows = thumb_extent(thumb_extent(desc->height, f), tile_h), cols = thumb_extent(thumb_extent(desc->width, f), tile_w);
+        for (uint32_t r = 0; r < rows; ++r)
+            for (uint32_t col = 0; col < cols; ++col, ++t) {
+                t->image = 0u; t->x = col * sw; t->y = r * sh;               // (both inside the image: col * tile_w < ceil(w / f))
+                t->width = desc->width - t->x < sw ? desc->width - t->x : sw;
+                t->height = desc->height - t->y < sh ? desc->height - t->y : sh;
+                t->factor = f; t->flags = 0u; t->reserved = 0u;
+            }
+    }
+    return (int)total;
+}
+
+// Tile j's slot: up256 of its pixels, then up256 of its encode bound; sub-batches by stage_plan over those slots in tile order
+// (qoi_amd/tiles.py: plan).  Every sub-batch: one launch of tile_gather over its tiles, then the loop of encode_packed as it is.
+extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size_t* pixel_offsets, const qoi_desc* descs, int n_images, int channels,
+                                  const qoimi_tile* tiles, int n_tiles, int mode, unsigned align, void* d_packed, size_t packed_capacity,
+                                  unsigned long long* d_packed_off, int* d_stream_len, size_t staging_bytes, unsigned long long* packed_off_out,
+                                  int* stream_len_out, qoi_desc* tile_descs_out, void* stream) {
+    // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
+    if (!c || !d_pixels || !pixel_offsets || !descs || !tiles || !d_packed_off || !d_stream_len || n_images <= 0 || n_tiles <= 0 ||
+        (!d_packed && packed_capacity != 0)) return fail(QOIMI_E_ARG, "NULL/empty argument");
+    if (align == 0 || align > 256u || (align & (align - 1u)) != 0) return fail(QOIMI_E_ARG, "align must be a power of two, 1..256");
+    if (const int rc = check_out_channels(channels)) return rc;
+    if (mode != QOIMI_THUMB_PLAIN && mode != QOIMI_THUMB_ALPHA_WEIGHTED) return fail(QOIMI_E_ARG, "mode must be QOIMI_THUMB_PLAIN or QOIMI_THUMB_ALPHA_WEIGHTED");
+    const size_t n = (size_t)n_tiles;
+    std::vector<uint8_t> named((size_t)n_images, 0);
+    for (size_t j = 0; j < n; ++j) {
+        const qoimi_tile& t = tiles[j];
+        if (t.image >= (unsigned)n_images) return fail(QOIMI_E_ARG, "tile " + std::to_string(j) + ": no image " + std::to_string(t.image));
+        if (!named[t.image]) {                                 // (an image no tile names is never looked at)
+            if (!desc_ok(&descs[t.image])) return fail(QOIMI_E_ARG, "descriptor " + std::to_string(t.image) + " rejected (qoi.h:364-372 rules)");
+            named[t.image] = 1;
+        }
+        if (const char* what = tile_wrong(&descs[t.image], &t)) return fail(QOIMI_E_ARG, "tile " + std::to_string(j) + ": " + what);
+    }
+    long long referenced = 0;
+    for (size_t i = 0; i < named.size(); ++i) {
+        if (!named[i]) continue;
+        ++referenced;
+        const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_pixels;
+        const size_t last = (size_t)descs[i].width * descs[i].height * descs[i].channels - 1u;     // the image's last byte from its first
+        if (pixel_offsets[i] > room || last > room - pixel_offsets[i]) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + " ends behind the address space");
+        const uintptr_t s0 = (uintptr_t)d_pixels + pixel_offsets[i], p0 = (uintptr_t)d_packed;
+        if (packed_capacity != 0 && s0 <= p0 + (packed_capacity - 1u) && p0 <= s0 + last) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + " and the pack overlap");
+    }
+    // the tiles' descriptors, slots and plan
+    std::vector<qoi_desc> td(n);
+    std::vector<size_t> px_part(n), slots(n);
+    for (size_t j = 0; j < n; ++j) {
+        const qoimi_tile& t = tiles[j];
+        const qoi_desc& d = descs[t.image];
+        td[j].width = thumb_extent(t.width, t.factor); td[j].height = thumb_extent(t.height, t.factor);
+        td[j].channels = (unsigned char)(channels ? channels : d.channels); td[j].colorspace = d.colorspace;
+        px_part[j] = up256((size_t)td[j].width * td[j].height * td[j].channels);
+        slots[j] = px_part[j] + up256(qoimi_encode_bound(&td[j]));
+    }
+    const StagePlan plan = stage_plan(slots, staging_bytes);
+    std::vector<uint32_t> first_tile(n), sub_tiles(plan.firsts.size() - 1u);
+    for (size_t k = 0; k + 1 < plan.firsts.size(); ++k) {
+        uint64_t sum = 0;
+        for (int j = plan.firsts[k]; j < plan.firsts[k + 1]; ++j) {
+            if (sum >= 0x7FFFFFFFull) break;
+            first_tile[(size_t)j] = (uint32_t)sum;
+            sum += tile_tiles(tiles[j].width, tiles[j].height, tiles[j].factor, td[(size_t)j].channels);
+        }
+        if (sum >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of work items of the gather kernel in one sub-batch");
+        sub_tiles[k] = (uint32_t)sum;
+    }
+    long long (&stats)[4] = c->tile_stats;
+    stats[0] = 0; stats[1] = 0; stats[2] = (long long)plan.need; stats[3] = referenced;
+    const TileEntry* d_tab = nullptr;
+    const PackPixels px = {d_pixels, 0, nullptr, td.data(), px_part.data(), up256(n * sizeof(TileEntry))};
+    const int rc = encode_packed(c, px, n_tiles, slots, plan, align, d_packed, packed_capacity, d_packed_off, d_stream_len, packed_off_out, stream_len_out, stream,
+        [&](uint8_t* h_extra, uint8_t* d_extra) {
+            TileEntry* tab = (TileEntry*)h_extra;
+            for (size_t j = 0; j < n; ++j) {
+                const qoimi_tile& t = tiles[j];
+                const qoi_desc& d = descs[t.image];
+                TileEntry& e = tab[j];
+                e.src_off = (u64)pixel_offsets[t.image]; e.dst_off = (u64)plan.at[j];
+                e.w = d.width; e.x = t.x; e.y = t.y; e.cw = t.width; e.ch = t.height; e.tw = td[j].width; e.th = td[j].height; e.f = t.factor;
+                e.first_tile = first_tile[j];
+                e.cfg = tile_cfg(t.factor, d.channels, td[j].channels, mode == QOIMI_THUMB_ALPHA_WEIGHTED && d.channels == 4u, t.flags);   // with 3 source channels the mode is PLAIN
+            }
+            d_tab = (const TileEntry*)d_extra;
+            return (int)QOIMI_OK;
+        },
+        [&](size_t k, int first, int m, uint8_t* staging, hipStream_t st) {
+            stats[0] += 1;
+            launch_tile_gather((const uint8_t*)d_pixels, d_tab + first, (uint32_t)m, sub_tiles[k], staging, grid_bound(c, sub_tiles[k]), st);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return fail(QOIMI_E_INTERNAL, std::string("tile_gather: ") + hipGetErrorString(e));
+            stats[1] += 1;
+            return (int)QOIMI_OK;
+        });
+    if (rc == QOIMI_OK && tile_descs_out) memcpy(tile_descs_out, td.data(), n * sizeof(qoi_desc));
+    return rc;
 }
 
 extern "C" int qoimi_read_descs(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, int n_streams,

@@ -331,6 +331,12 @@ void launch_tensor_warp(const uint8_t* stage, const WarpEntry* tab, uint32_t m, 
 // hist: NULL or the call's histograms
 void launch_stats(const uint8_t* stage, const StatsEntry* tab, uint32_t m, uint32_t tiles, StatsAcc* res, unsigned* hist, uint32_t grid, hipStream_t st);
 
+// ---- tiles of device images on their way into the encoder (qoi_tile.hip; the entry and the arithmetic: qoi_tile_core.h) ----------
+// tile_gather over the m table entries at tab (their tiles: [0, tiles)): from the caller's images at `pixels` into the pixel parts of the
+// slots at `stage`.  grid: workgroups, at most `tiles`.  No timer mark: the kernel has no entry in the name table (the call counts its launches).
+struct TileEntry;
+void launch_tile_gather(const uint8_t* pixels, const TileEntry* tab, uint32_t m, uint32_t tiles, uint8_t* stage, uint32_t grid, hipStream_t st);
+
 // ---- row seek index (qoi_seek.hip; the arithmetic: qoi_seek_core.h) ------------------
 struct SeekPoint;                                       // = qoimi_seek_point (qoi_seek_core.h)
 struct SeekJob { uint32_t stream, point, P, reserved; };   // seek point `point` of the call: pixel P of stream `stream` of the inspect tables
