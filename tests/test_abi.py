@@ -29,6 +29,73 @@ def test_header_symbols_exported(lib):
         assert hasattr(lib, name), name
 
 
+def _header():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "qoi_mi355x.h")).read(), flags=re.S)
+
+
+_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "size_t": ctypes.c_size_t,
+            "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong, "unsigned char": ctypes.c_ubyte,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+_STRUCTS = {"qoi_desc": "QoiDesc", "qoimi_stream_info": "StreamInfo", "qoimi_image_diff": "ImageDiff", "qoimi_crop": "QoimiCrop",
+            "qoimi_tile": "QoimiTile", "qoimi_resize": "QoimiResize", "qoimi_warp": "QoimiWarp", "qoimi_tensor_format": "QoimiTensorFormat",
+            "qoimi_pixel_stat": "QoimiPixelStat", "qoimi_seek_point": "QoimiSeekPoint", "qoimi_band": "QoimiBand",
+            "qoimi_band_info": "QoimiBandInfo"}
+
+
+def _value_type(c_type):
+    """The ctypes type of a C scalar or structure type of the header."""
+    return _SCALARS[c_type] if c_type in _SCALARS else getattr(api, _STRUCTS[c_type])
+
+
+def _accepted(c_type):
+    """The ctypes types a binding may give a parameter (or return value) the header declares as c_type, declarator included
+    (``const size_t *``, ``long long [4]``): a scalar exactly its own type; a pointer or array c_void_p or the pointer to its element."""
+    base = " ".join(c_type.replace("const", " ").replace("*", " ").split())
+    base, array = re.match(r"(.*?)\s*(\[\d*\])?$", base).groups()
+    depth = c_type.count("*") + (1 if array else 0)
+    if depth == 0:
+        return {None} if base == "void" else {_value_type(base)}
+    if (base, depth) == ("char", 1):
+        return {ctypes.c_char_p}
+    if base == "qoimi_ctx":
+        return {ctypes.c_void_p} if depth == 1 else {ctypes.POINTER(ctypes.c_void_p)}
+    assert depth == 1, c_type
+    return {ctypes.c_void_p} if base == "void" else {ctypes.c_void_p, ctypes.POINTER(_value_type(base))}
+
+
+def test_prototypes_match_the_header(lib):
+    """Return type, parameter count and every parameter type the binding gives a function (what ``load_library`` has set on it) against
+    its declaration in the header: a swapped size_t / int or a missing trailing argument fails here, not as a garbage pointer on the GPU."""
+    declared = re.findall(r"(?m)^([A-Za-z_ ]+?[ \*]+)(qoi_[a-z]+|qoimi_[a-z_]+)\s*\(([^()]*)\)\s*;", _header())
+    assert sorted(name for _, name, _ in declared) == sorted(api.EXPORTS) and len(declared) == 70
+    spellings = set()
+    for ret, name, params in declared:
+        fn = getattr(lib, name)
+        assert fn.restype in _accepted(ret.strip()), (name, ret, fn.restype)
+        params = [" ".join(p.split()) for p in params.split(",")]
+        params = [] if params == ["void"] else [re.sub(r"\w+(\[\d*\])?$", lambda m: m.group(1) or "", p).strip() for p in params]
+        spellings.update(params)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), (name, len(params), fn.argtypes)
+        for k, (p, got) in enumerate(zip(params, fn.argtypes)):
+            assert got in _accepted(p), (name, k, p, got)
+    assert len(spellings) == 34, sorted(spellings)
+
+
+def test_structures_match_the_header():
+    """Every ``typedef struct { ... } name;`` of the header against the Python structure: the field names in order, and of every field
+    the element type and the array length."""
+    found = re.findall(r"typedef struct\s*\{(.*?)\}\s*(\w+)\s*;", _header(), flags=re.S)
+    assert sorted(name for _, name in found) == sorted(_STRUCTS)
+    for body, name in found:
+        want = []
+        for decl in (" ".join(d.split()) for d in body.split(";") if d.strip()):
+            c_type, first = re.match(r"(.*?)\s*(\w+(?:\[\d+\])?)$", decl.split(",")[0]).groups()
+            for field in [first] + [f.strip() for f in decl.split(",")[1:]]:
+                fname, length = re.match(r"(\w+)(?:\[(\d+)\])?$", field).groups()
+                want.append((fname, _value_type(c_type) * int(length) if length else _value_type(c_type)))
+        assert getattr(api, _STRUCTS[name])._fields_ == want, (name, want)
+
+
 def test_nothing_else_is_exported():
     """-fvisibility=hidden (qoi_amd/csrc/Makefile): the dynamic symbol table of every flavour holds the functions the header declares
     and nothing of the implementation (no mangled qoimi:: kernels or launchers, no helper classes)."""
