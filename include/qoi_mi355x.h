@@ -710,7 +710,8 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * register: no second kernel of the caller's reads the bytes back, and nothing but the tensor is written.  Items (qoimi_resize, qoimi_warp as
  * they are), channels, modes, flips, border, staging, plan, sub-batches, the tile limits and the "not one byte beside an output" contract are
  * those of the underlying call: qoimi_decode_resized for QOIMI_FILTER_AREA, qoimi_decode_bilinear for QOIMI_FILTER_BILINEAR, qoimi_decode_warped
- * for qoimi_decode_warped_tensors.
+ * for qoimi_decode_warped_tensors.  QOIMI_FILTER_BICUBIC has no call of its own - its "underlying call" is the definition below, everything
+ * but the filter and its limits as for qoimi_decode_bilinear; QOIMI_TENSOR_U8 with QOIMI_TENSOR_HWC gives its plain interleaved bytes.
  * The result (normative; qoi_amd/tensors.py: convert states it in Python): let P be the oh x ow x och u8 result of the underlying call with the
  * same items, channels and mode, byte for byte, flips included.  Element (Y, X, c) of output j has the value v = P[Y][X][c], an integer 0..255.
  *   QOIMI_TENSOR_U8    the element is v; scale must be all 1.0f and bias all +0.0f
@@ -724,7 +725,31 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * other format a pure function of its bytes: the exact-integer definitions of the three filters stand as they are.
  * Only whole, naturally aligned elements are stored (u8 HWC: as the underlying call stores): no word is read and written back, two outputs
  * may share one.
- *   filter         QOIMI_FILTER_AREA or QOIMI_FILTER_BILINEAR (qoimi_decode_tensors only)
+ * QOIMI_FILTER_BICUBIC (normative; qoi_amd/bicubic.py: bicubic states it in Python) is the antialiased bicubic filter - Keys' cubic with
+ * a = -1/2, stretched by the reduction factor when reducing: PIL BICUBIC, torchvision Resize(BICUBIC, antialias=True).  D, R, cw, rh, ow, oh,
+ * och, the items, flips, modes and the plan as for qoimi_decode_bilinear; all arithmetic is integer, every division and every shift floors,
+ * for negative numbers too.  One axis, n_src source samples to n_out output samples, on the line of the tent filter: source sample k has its
+ * centre at (2k + 1) * n_out, output sample X at (2X + 1) * n_src; u = 2 * max(n_src, n_out); for 0 <= k < n_src,
+ * d = |(2X + 1) * n_src - (2k + 1) * n_out| and
+ *   c(X, k) = 3d^3 - 5u d^2 + 2u^3               for d <= u
+ *   c(X, k) = -d^3 + 5u d^2 - 8u^2 d + 4u^3      for u < d < 2u    (negative)
+ *   c(X, k) = 0                                  from 2u on
+ * - 2u^3 times Keys' kernel at d / u.  W(X) = sum_k c(X, k) > 0: samples outside the rectangle do not exist, the weights are renormalised,
+ * not clamped.  q(X, k) = (c(X, k) * 2^15 + W / 2) / W; the deficit 2^15 - sum_k q(X, k) is added to the tap with the largest c, the lowest
+ * such k on a tie, so sum_k q(X, k) = 2^15 for every X.  qx from (cw, ow), qy from (rh, oh); two axes, ONE rounding:
+ * N_c = sum_{r,k} qy(Y, r) * qx(X, k) * R[r][k].c.
+ *   QOIMI_RESIZE_PLAIN            every channel is clamp((N_c + 2^29) >> 30, 0, 255)
+ *   QOIMI_RESIZE_ALPHA_WEIGHTED   och == 4: A = N_a; alpha is the PLAIN value; where A > 0 r, g and b are
+ *                                 clamp((sum qy*qx*c*a + A / 2) / A, 0, 255), where A <= 0 the PLAIN value.  och == 3: PLAIN
+ * The clamp is part of the definition: the negative lobes overshoot at edges.  The flips are those of the tent filter (the kernel is
+ * symmetric).  With out_width x out_height equal to width x height the only tap with c != 0 is k = X, q = 2^15: the rectangle byte for
+ * byte; a constant rectangle gives the constant at any size; enlarging touches at most 4 x 4 samples.  Against a float64 evaluation of the
+ * same renormalised filter, rounded and clamped, a PLAIN value differs by at most 1 for every geometry accepted (qoi_amd/bicubic.py derives
+ * it from the quantisation of q, the deficit tap and the one rounding: below 1.24 from the exact real value with 64 taps in both axes).
+ * Its limits, each a QOIMI_E_ARG item by item where the other filters have their ratio limit: width <= 16 * out_width and
+ * height <= 16 * out_height (at most 64 taps per axis); max(width, out_width) <= 16384 and max(height, out_height) <= 16384 (|c| <= 2^46,
+ * W < 2^52, |N_c| < 2^40, the alpha-weighted sums below 2^48: signed 64 bits hold everything).
+ *   filter         QOIMI_FILTER_AREA, QOIMI_FILTER_BILINEAR or QOIMI_FILTER_BICUBIC (qoimi_decode_tensors only)
  *   format         HOST; one for the whole call
  *   d_out, out_offsets   every d_out + out_offsets[j] a multiple of the element size (1 / 2 / 2 / 4)
  *   everything else      as for the underlying call
@@ -735,11 +760,11 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * in bytes; an output address that is not a multiple of the element size; a sub-batch of the plan with 2^31 - 1 tiles or more.  All are
  * reported before anything is launched, the caller's buffers are untouched; qoimi_last_error names the cause.  The sub-batches count as decode
  * calls of the context.  One call at a time per context, as everywhere.
- * Not here: indexed forms, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
+ * Not here: indexed forms, a u8 entry point or a stats function of the bicubic filter's own, other cubic kernels (a = -3/4, Lanczos), a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
  * size of its rectangle, or divides it, is those), tensors as the source of an encode (qoimi_encode_tiles takes bytes). */
 enum { QOIMI_TENSOR_U8 = 0, QOIMI_TENSOR_F16 = 1, QOIMI_TENSOR_BF16 = 2, QOIMI_TENSOR_F32 = 3 };   /* element sizes 1 / 2 / 2 / 4 */
 enum { QOIMI_TENSOR_HWC = 0, QOIMI_TENSOR_CHW = 1 };
-enum { QOIMI_FILTER_AREA = 0, QOIMI_FILTER_BILINEAR = 1 };
+enum { QOIMI_FILTER_AREA = 0, QOIMI_FILTER_BILINEAR = 1, QOIMI_FILTER_BICUBIC = 3 };   /* 2 is not a filter */
 typedef struct {                 /* 48 bytes, offsets 0/4/8/24/40 */
     unsigned int dtype;          /* QOIMI_TENSOR_* */
     unsigned int layout;         /* QOIMI_TENSOR_HWC / _CHW */
@@ -757,7 +782,8 @@ int qoimi_decode_warped_tensors(qoimi_ctx *ctx, const void *d_streams, const siz
                                 void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream);
 
 /* out_width * out_height * channels * element size - the bytes of the item's output - or 0 if filter is unknown, the format is one the calls
- * reject, qoimi_resize_size / qoimi_bilinear_size (by filter) or qoimi_warp_size would return 0, or the product does not fit a size_t.  Pure
+ * reject, qoimi_resize_size / qoimi_bilinear_size (by filter) or qoimi_warp_size would return 0, the item is beyond the limits of
+ * QOIMI_FILTER_BICUBIC with that filter, or the product does not fit a size_t.  Pure
  * host arithmetic: no context, no GPU. */
 size_t qoimi_tensor_size(const qoi_desc *desc, const qoimi_resize *item, int filter, int channels, const qoimi_tensor_format *format);
 size_t qoimi_warp_tensor_size(const qoi_desc *desc, const qoimi_warp *item, int channels, const qoimi_tensor_format *format);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """qoitensor for the MI355X path: a set of .qoi files as ONE .npy tensor, N x C x H x W or N x H x W x C, normalised.
 
-    python tools/qoitensor_mi355x.py FILE_OR_DIR... --size WxH -o OUT.npy [--filter area|bilinear] [--dtype u8|f16|bf16|f32] [--layout chw|hwc]
+    python tools/qoitensor_mi355x.py FILE_OR_DIR... --size WxH -o OUT.npy [--filter area|bilinear|bicubic] [--dtype u8|f16|bf16|f32] [--layout chw|hwc]
                                      [--mean M[,M,M[,M]]] [--std S[,S,S[,S]]] [--fit whole|crop] [--channels 3|4] [--staging-mb M]
 
 Loads the .qoi files (directories are walked), uploads them as ONE pack and makes ONE qoimi_decode_tensors call: every stream is decoded on the
@@ -11,7 +11,7 @@ scale = 1 / (255 * std) and bias = -mean / std are computed in float64 and round
 float32(p) * scale + bias with two roundings and narrows once (qoi_amd/tensors.py states it).  Without --mean / --std the elements are
 p / 255; --dtype u8 takes neither and stores p.  One value of --mean / --std serves every channel; a fourth (alpha) defaults to mean 0, std 1.
 --channels defaults to 3.  bf16 is stored as the uint16 of its bits (NumPy has no bfloat16).  A file that is no QOI stream or whose
-rectangle the filter cannot reduce to the target (64 times in an axis, 32 for bilinear) is reported and left out; exit status 1 if there was
+rectangle the filter cannot reduce to the target (64 times in an axis, 32 for bilinear, 16 for bicubic) is reported and left out; exit status 1 if there was
 one, else 0.  Needs torch for device memory, as tools/qoicheck_mi355x.py does.
 """
 from __future__ import annotations
@@ -62,7 +62,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("paths", nargs="+", metavar="FILE_OR_DIR")
     ap.add_argument("--size", required=True, metavar="WxH")
     ap.add_argument("-o", "--out", required=True, metavar="OUT.npy")
-    ap.add_argument("--filter", choices=("area", "bilinear"), default="bilinear")
+    ap.add_argument("--filter", choices=("area", "bilinear", "bicubic"), default="bilinear")
     ap.add_argument("--dtype", choices=("u8", "f16", "bf16", "f32"), default="f32")
     ap.add_argument("--layout", choices=("chw", "hwc"), default="chw")
     ap.add_argument("--mean", default=None, metavar="M[,M,M[,M]]")
@@ -96,13 +96,13 @@ def main(argv, out=print) -> int:
             return 2
     ow, oh = size
     import torch  # first: the library then binds to the HIP runtime torch already loaded
-    from qoi_amd import api, bilinear, resize, tensors
+    from qoi_amd import api, bicubic, bilinear, resize, tensors
 
     files = collect(a.paths)
     if not files:
         out("no .qoi files")
         return 2
-    tent = a.filter == "bilinear"
+    model, filt = {"area": (resize, tensors.FILTER_AREA), "bilinear": (bilinear, tensors.FILTER_BILINEAR), "bicubic": (bicubic, tensors.FILTER_BICUBIC)}[a.filter]
     blobs = [open(f, "rb").read() for f in files]
     heads = [parse_header(b) for b in blobs]
     good = []
@@ -111,7 +111,7 @@ def main(argv, out=print) -> int:
             out(f"{os.path.basename(files[i])}: not a QOI stream, left out")
             continue
         rect = fit_rect(hd[0], hd[1], ow, oh, a.fit)
-        if (bilinear.size if tent else resize.size)(hd[0], hd[1], rect, (ow, oh), 0, och) == 0:
+        if model.size(hd[0], hd[1], rect, (ow, oh), 0, och) == 0:
             out(f"{os.path.basename(files[i])}: {rect[2]}x{rect[3]} to {ow}x{oh} is beyond the {a.filter} filter's limits, left out")
             continue
         good.append(i)
@@ -130,7 +130,7 @@ def main(argv, out=print) -> int:
     d_out = torch.zeros(len(good) * one, dtype=torch.uint8, device="cuda")
     ctx = api.Context(0)
     try:
-        ctx.decode_tensors(pack.data_ptr(), offsets, sizes, descs, och, items, tensors.FILTER_BILINEAR if tent else tensors.FILTER_AREA, tensors.PLAIN, f,
+        ctx.decode_tensors(pack.data_ptr(), offsets, sizes, descs, och, items, filt, tensors.PLAIN, f,
                            d_out.data_ptr(), [k * one for k in range(len(good))], a.staging_mb << 20)
         subs = ctx.tensor_stats()[0]
     finally:
