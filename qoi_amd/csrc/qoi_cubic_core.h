@@ -52,12 +52,14 @@ constexpr uint32_t kCubicRowSlots = 16384;         // ... of its row table
 
 QOIMI_RESIZE_HD uint32_t cubic_unit(uint32_t n_src, uint32_t n_out) { return 2u * (n_src > n_out ? n_src : n_out); }
 
-// The first source sample that may have a weight for output sample Z: the smallest k >= 0 with (2k+1) * n_out > (2Z+1) * n_src - 2u, which
-// is floor(((2Z+1) * n_src + n_out - 2u) / (2 * n_out)) where that numerator is positive and 0 else.
-QOIMI_RESIZE_HD uint32_t cubic_first(uint32_t Z, uint32_t n_src, uint32_t n_out) {
-    const uint32_t a = (2u * Z + 1u) * n_src + n_out, u2 = 2u * cubic_unit(n_src, n_out);
-    return a > u2 ? (a - u2) / (2u * n_out) : 0u;
+// The first source sample that may have a weight for output sample Z under a kernel that is 0 from `lobes` * u on (2: this filter, 3:
+// qoi_lanczos_core.h): the smallest k >= 0 with (2k+1) * n_out > (2Z+1) * n_src - lobes * u, which is
+// floor(((2Z+1) * n_src + n_out - lobes * u) / (2 * n_out)) where that numerator is positive and 0 else.
+QOIMI_RESIZE_HD uint32_t filter_first(uint32_t Z, uint32_t n_src, uint32_t n_out, uint32_t lobes) {
+    const uint32_t a = (2u * Z + 1u) * n_src + n_out, ul = lobes * cubic_unit(n_src, n_out);
+    return a > ul ? (a - ul) / (2u * n_out) : 0u;
 }
+QOIMI_RESIZE_HD uint32_t cubic_first(uint32_t Z, uint32_t n_src, uint32_t n_out) { return filter_first(Z, n_src, n_out, 2u); }
 
 // c for an output centre o = (2Z+1) * n_src and source sample k (the caller keeps k below n_src)
 QOIMI_RESIZE_HD int64_t cubic_weight(uint32_t o, uint32_t k, uint32_t n_out, uint32_t u) {
@@ -73,19 +75,22 @@ QOIMI_RESIZE_HD uint32_t cubic_taps(uint32_t n_src, uint32_t n_out) {
     return n_src <= n_out ? 4u : (4u * n_src + n_out - 1u) / n_out;
 }
 
-// How an output pixel's columns are split over lanes: lg = log2(L), c = columns per lane (at most 4 under the cap of 16).
-QOIMI_RESIZE_HD void cubic_split(uint32_t cw, uint32_t ow, uint32_t& lg, uint32_t& c) {
-    const uint32_t t = cubic_taps(cw, ow);
+// How the t columns of an output pixel are split over lanes: lg = log2(L), c = columns per lane (at most max_cols under the cap of 16).
+QOIMI_RESIZE_HD void filter_split(uint32_t t, uint32_t max_cols, uint32_t& lg, uint32_t& c) {
     lg = 0;
-    while (lg < kResizeMaxLg && ((t + (1u << lg) - 1u) >> lg) > kCubicMaxCols) ++lg;
+    while (lg < kResizeMaxLg && ((t + (1u << lg) - 1u) >> lg) > max_cols) ++lg;
     c = (t + (1u << lg) - 1u) >> lg;
 }
+QOIMI_RESIZE_HD void cubic_split(uint32_t cw, uint32_t ow, uint32_t& lg, uint32_t& c) { filter_split(cubic_taps(cw, ow), kCubicMaxCols, lg, c); }
 
-// Tiles of kResizeThreads work items of an item (ow * oh * L of them); an accepted item has at most 2^28 output pixels.
+// Tiles of kResizeThreads work items of an item (ow * oh << lg of them); an accepted item has at most 2^28 output pixels.
+QOIMI_RESIZE_HD uint64_t split_tiles(uint32_t lg, uint32_t ow, uint32_t oh) {
+    return ((((uint64_t)ow * oh) << lg) + kResizeThreads - 1u) / kResizeThreads;
+}
 QOIMI_RESIZE_HD uint64_t cubic_tiles(uint32_t cw, uint32_t ow, uint32_t oh) {
     uint32_t lg, c;
     cubic_split(cw, ow, lg, c);
-    return ((((uint64_t)ow * oh) << lg) + kResizeThreads - 1u) / kResizeThreads;
+    return split_tiles(lg, ow, oh);
 }
 
 // floor(n / W) for 0 < W < 2^53 and |n / W| < 2^17: the quotient of two doubles is off by far less than 1, so one step either way mends it
@@ -121,9 +126,10 @@ QOIMI_RESIZE_HD void cubic_norm(uint32_t Z, uint32_t n_src, uint32_t n_out, uint
 
 // What a tile normalises.  o0: its first output pixel, px: its pixels; nx columns of sx entries - column slot i is output column
 // cubic_tile_column(i), pixel o at column X reads slot cubic_tile_slot(o, X) -, ny rows of sy entries from output row Y0.
+// (The bookkeeping does not know the filter: table_tile takes sy, the entries of a row - qoi_lanczos_core.h uses it with its own.)
 struct CubicTile { uint64_t o0; uint32_t px, X0, Y0, nx, ny, sx, sy, wrap; };
 
-QOIMI_RESIZE_HD CubicTile cubic_tile(const ResizeGeom& g, uint32_t lg, uint32_t c, uint64_t tile) {
+QOIMI_RESIZE_HD CubicTile table_tile(const ResizeGeom& g, uint32_t lg, uint32_t c, uint32_t sy, uint64_t tile) {
     CubicTile t;
     const uint32_t per = kResizeThreads >> lg;
     const uint64_t all = (uint64_t)g.ow * g.oh;
@@ -135,9 +141,10 @@ QOIMI_RESIZE_HD CubicTile cubic_tile(const ResizeGeom& g, uint32_t lg, uint32_t 
     t.wrap = g.ow > per ? 1u : 0u;
     t.nx = t.wrap ? t.px : g.ow;
     t.sx = c << lg;
-    t.sy = cubic_taps(g.rh, g.oh);
+    t.sy = sy;
     return t;
 }
+QOIMI_RESIZE_HD CubicTile cubic_tile(const ResizeGeom& g, uint32_t lg, uint32_t c, uint64_t tile) { return table_tile(g, lg, c, cubic_taps(g.rh, g.oh), tile); }
 
 QOIMI_RESIZE_HD uint32_t cubic_tile_column(const CubicTile& t, const ResizeGeom& g, uint32_t i) {
     if (!t.wrap) return i;
@@ -152,11 +159,10 @@ QOIMI_RESIZE_HD void cubic_tile_norm(const CubicTile& t, const ResizeGeom& g, ui
     else cubic_norm(t.Y0 + (i - t.nx), g.rh, g.oh, t.sy, qy + (i - t.nx) * t.sy);
 }
 
-// One tap: staged pixel px with the signed weight wgt into the sums (two's complement in ResizeSums).
+// One tap: staged pixel px with the signed weight w = qy * qx into the sums (two's complement in ResizeSums).
 template <bool WEIGHTED>
-QOIMI_RESIZE_HD void cubic_tap(ResizeSums& s, uint32_t px, int32_t wgt) {
+QOIMI_RESIZE_HD void cubic_tap(ResizeSums& s, uint32_t px, int64_t w) {
     const int32_t al = (int32_t)(px >> 24);
-    const int64_t w = wgt;
     s.S[0] += (uint64_t)(w * (int32_t)(px & 255u)); s.S[1] += (uint64_t)(w * (int32_t)((px >> 8) & 255u));
     s.S[2] += (uint64_t)(w * (int32_t)((px >> 16) & 255u)); s.S[3] += (uint64_t)(w * al);
     if (WEIGHTED) {
@@ -166,30 +172,38 @@ QOIMI_RESIZE_HD void cubic_tap(ResizeSums& s, uint32_t px, int32_t wgt) {
 }
 
 // Lane l's share of output pixel (X, Y) of the unflipped result: c columns from k0 + l * c, every row.  qx: the sx entries of the pixel's
-// column, qy: the sy entries of its row.  Only pixels with a weight are loaded: q is 0 for columns from cw and rows from rh on.
-template <bool WEIGHTED, class Mem>
-QOIMI_RESIZE_HD void cubic_lane(const Mem& mem, const ResizeGeom& g, const uint16_t* qx, const uint16_t* qy, uint32_t sy, uint32_t X, uint32_t Y,
-                                uint32_t l, uint32_t c, ResizeSums& s) {
+// column, qy: the sy entries of its row, each q + BIAS.  Only pixels with a weight are loaded: q is 0 for columns from cw and rows from rh on.
+// LOBES: filter_first's; COLS: the most columns of a lane; Prod: the type qy * qx is formed in.
+template <bool WEIGHTED, uint32_t LOBES, uint32_t COLS, int32_t BIAS, class Prod, class Mem>
+QOIMI_RESIZE_HD void filter_lane(const Mem& mem, const ResizeGeom& g, const uint16_t* qx, const uint16_t* qy, uint32_t sy, uint32_t X, uint32_t Y,
+                                 uint32_t l, uint32_t c, ResizeSums& s) {
     resize_zero(s);
-    const uint32_t k0 = cubic_first(X, g.cw, g.ow) + l * c;
-    int32_t wx[kCubicMaxCols], any = 0;
+    const uint32_t k0 = filter_first(X, g.cw, g.ow, LOBES) + l * c;
+    int32_t wx[COLS], any = 0;
     QOIMI_RESIZE_UNROLL
-    for (uint32_t j = 0; j < kCubicMaxCols; ++j) {
-        wx[j] = j < c ? (int32_t)qx[l * c + j] - kCubicBias : 0;
+    for (uint32_t j = 0; j < COLS; ++j) {
+        wx[j] = j < c ? (int32_t)qx[l * c + j] - BIAS : 0;
         any |= wx[j];
     }
     if (any == 0) return;
-    const uint64_t at0 = (uint64_t)(g.y + cubic_first(Y, g.rh, g.oh)) * g.w + g.x + k0;
+    const uint64_t at0 = (uint64_t)(g.y + filter_first(Y, g.rh, g.oh, LOBES)) * g.w + g.x + k0;
     for (uint32_t i = 0; i < sy; ++i) {
-        const int32_t wy = (int32_t)qy[i] - kCubicBias;
+        const int32_t wy = (int32_t)qy[i] - BIAS;
         if (wy == 0) continue;                                 // (a weight may be 0 inside the support: d = u)
         const uint64_t at = at0 + (uint64_t)i * g.w;
         QOIMI_RESIZE_UNROLL
-        for (uint32_t j = 0; j < kCubicMaxCols; ++j) {
+        for (uint32_t j = 0; j < COLS; ++j) {
             if (wx[j] == 0) continue;
-            cubic_tap<WEIGHTED>(s, mem.load(at + j), wy * wx[j]);   // (|qy * qx| <= 25 * 2^26 < 2^31)
+            cubic_tap<WEIGHTED>(s, mem.load(at + j), (Prod)wy * wx[j]);
         }
     }
+}
+
+// ... of this filter: |qy * qx| <= 25 * 2^26 < 2^31
+template <bool WEIGHTED, class Mem>
+QOIMI_RESIZE_HD void cubic_lane(const Mem& mem, const ResizeGeom& g, const uint16_t* qx, const uint16_t* qy, uint32_t sy, uint32_t X, uint32_t Y,
+                                uint32_t l, uint32_t c, ResizeSums& s) {
+    filter_lane<WEIGHTED, 2u, kCubicMaxCols, kCubicBias, int32_t>(mem, g, qx, qy, sy, X, Y, l, c, s);
 }
 
 QOIMI_RESIZE_HD uint32_t cubic_clamp(int64_t v) { return v < 0 ? 0u : (v > 255 ? 255u : (uint32_t)v); }

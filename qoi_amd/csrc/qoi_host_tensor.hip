@@ -1,10 +1,10 @@
 // qoi_host_tensor.hip — the tensor calls of the C-ABI shim: qoimi_decode_tensors (the area filter, the antialiased bilinear filter or the
-// antialiased bicubic filter, which only this call has) and qoimi_decode_warped_tensors, with qoimi_tensor_size and qoimi_warp_tensor_size.  They are gather_resampled and gather_warped of qoi_staged.h -
+// antialiased bicubic and Lanczos filters, which only this call has) and qoimi_decode_warped_tensors, with qoimi_tensor_size and qoimi_warp_tensor_size.  They are gather_resampled and gather_warped of qoi_staged.h -
 // the checks of the items, the plan, the table entries and run_staged of qoimi_decode_resized / _bilinear / _warped - with the checks of the
 // format in front, output sizes in bytes of elements, the alignment of the outputs behind, and the tensor kernels of qoi_tensor.hip as the
 // launch.
 #include "qoi_staged.h"
-#include "qoi_cubic_core.h"
+#include "qoi_lanczos_core.h"
 #include "qoi_tensor_core.h"
 
 #include <math.h>
@@ -64,9 +64,11 @@ static int check_tensor_alignment(const void* d_out, const size_t* out_offsets, 
     return QOIMI_OK;
 }
 
-static_assert(QOIMI_FILTER_AREA == 0 && QOIMI_FILTER_BILINEAR == 1 && QOIMI_FILTER_BICUBIC == 3, "2 is not a filter");
+static_assert(QOIMI_FILTER_AREA == 0 && QOIMI_FILTER_BILINEAR == 1 && QOIMI_FILTER_BICUBIC == 3 && QOIMI_FILTER_LANCZOS == 6, "2, 4, 5 and 7 are not filters");
+static_assert(kLanczosMaxRatio == kCubicMaxRatio && kLanczosMaxSize == kCubicMaxSize, "the two filters share their limits: cubic_item_wrong");
 
-// ... with the ratio limit of 16 and the size limit (qoi_cubic_core.h: what keeps the weights in 64 bits and a tile's tables in their LDS)
+// ... with the ratio limit of 16 and the size limit (qoi_cubic_core.h, qoi_lanczos_core.h: what keeps the weights in 64 bits and a tile's tables
+// in their LDS)
 static const char* cubic_item_wrong(const qoi_desc* d, const qoimi_resize* r) {
     if (const char* what = resample_rect_wrong(d, r)) return what;
     if (r->width > (uint64_t)kCubicMaxRatio * r->out_width || r->height > (uint64_t)kCubicMaxRatio * r->out_height) return "reduced by more than 16 in an axis";
@@ -74,15 +76,29 @@ static const char* cubic_item_wrong(const qoi_desc* d, const qoimi_resize* r) {
     return nullptr;
 }
 
-// The bicubic filter writes tensors only: no launcher of a byte kernel, the counters and the name are the tensor call's.
+// The bicubic and the Lanczos filter write tensors only: no launcher of a byte kernel, the counters and the name are the tensor call's.
 static const ResampleKind kCubicKind = {cubic_item_wrong, cubic_split, cubic_tiles, nullptr, &qoimi_ctx::tensor_stats, "tensor_cubic"};
+static const ResampleKind kLanczosKind = {cubic_item_wrong, lanczos_split, lanczos_tiles, nullptr, &qoimi_ctx::tensor_stats, "tensor_lanczos"};
 
-static const ResampleKind* tensor_kind(int filter) {
-    return filter == QOIMI_FILTER_AREA ? &kAreaKind : (filter == QOIMI_FILTER_BILINEAR ? &kTentKind : (filter == QOIMI_FILTER_BICUBIC ? &kCubicKind : nullptr));
+// A filter of qoimi_decode_tensors: its kind, the launcher of its tensor kernel and that kernel's name for a launch failure
+struct TensorFilter {
+    const ResampleKind* kind;
+    void (*launch)(const uint8_t*, const ResizeEntry*, uint32_t, uint32_t, uint8_t*, const TensorFormat&, uint32_t, hipStream_t);
+    const char* kernel;
+};
+
+static TensorFilter tensor_filter(int filter) {
+    switch (filter) {
+    case QOIMI_FILTER_AREA: return {&kAreaKind, launch_tensor_area, "tensor_area"};
+    case QOIMI_FILTER_BILINEAR: return {&kTentKind, launch_tensor_tent, "tensor_tent"};
+    case QOIMI_FILTER_BICUBIC: return {&kCubicKind, launch_tensor_cubic, kCubicKind.kernel};
+    case QOIMI_FILTER_LANCZOS: return {&kLanczosKind, launch_tensor_lanczos, kLanczosKind.kernel};
+    default: return {nullptr, nullptr, nullptr};
+    }
 }
 
 extern "C" size_t qoimi_tensor_size(const qoi_desc* desc, const qoimi_resize* item, int filter, int channels, const qoimi_tensor_format* format) {
-    const ResampleKind* kind = tensor_kind(filter);
+    const ResampleKind* kind = tensor_filter(filter).kind;
     size_t bytes = 0;
     if (!kind || !desc_ok(desc) || !item || (channels != 3 && channels != 4) || tensor_format_wrong(format) || kind->wrong(desc, item) ||
         !tensor_bytes(resize_bytes, item, (unsigned)channels, tensor_elem(format->dtype), &bytes)) return 0;
@@ -99,17 +115,16 @@ extern "C" size_t qoimi_warp_tensor_size(const qoi_desc* desc, const qoimi_warp*
 extern "C" int qoimi_decode_tensors(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                     int n_images, int channels, const qoimi_resize* items, int n_items, int filter, int mode,
                                     const qoimi_tensor_format* format, void* d_out, const size_t* out_offsets, size_t staging_bytes, void* stream) {
-    const ResampleKind* kind = tensor_kind(filter);
-    if (!kind) return fail(QOIMI_E_ARG, "filter must be QOIMI_FILTER_AREA, QOIMI_FILTER_BILINEAR or QOIMI_FILTER_BICUBIC");
+    const TensorFilter tf = tensor_filter(filter);
+    if (!tf.kind) return fail(QOIMI_E_ARG, "filter must be QOIMI_FILTER_LANCZOS, QOIMI_FILTER_AREA, QOIMI_FILTER_BILINEAR or QOIMI_FILTER_BICUBIC");
     const size_t elem = (format && format->dtype <= (unsigned)QOIMI_TENSOR_F32) ? tensor_elem(format->dtype) : 1u;   // (used behind the format's check only)
-    const auto launch_filter = filter == QOIMI_FILTER_AREA ? launch_tensor_area : (filter == QOIMI_FILTER_BILINEAR ? launch_tensor_tent : launch_tensor_cubic);
-    return gather_resampled(*kind, c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
+    return gather_resampled(*tf.kind, c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
         [&]() { return check_tensor_format(format); },
         [&](const qoimi_resize* r, unsigned och, size_t* bytes) { return tensor_bytes(resize_bytes, r, och, elem, bytes); },
         [&](const CheckedItems&) { return check_tensor_alignment(d_out, out_offsets, (size_t)n_items, elem); },
-        &qoimi_ctx::tensor_stats, filter == QOIMI_FILTER_AREA ? "tensor_area" : (filter == QOIMI_FILTER_BILINEAR ? "tensor_tent" : "tensor_cubic"),
+        &qoimi_ctx::tensor_stats, tf.kernel,
         [&](const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
-            launch_filter((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, kernel_format(format), grid, st);
+            tf.launch((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, kernel_format(format), grid, st);
         });
 }
 

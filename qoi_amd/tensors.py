@@ -2,7 +2,7 @@
 header repeats it; qoi_amd/csrc/qoi_tensor_core.h holds the arithmetic of the kernels).
 
 Let P be the uint8[oh, ow, och] result of the underlying call - ``resize.resize`` for ``FILTER_AREA``, ``bilinear.bilinear`` for
-``FILTER_BILINEAR``, ``bicubic.bicubic`` for ``FILTER_BICUBIC`` (which has no u8 call of its own), ``warp.warp`` for the warp call - with the same item, channels and mode, byte for byte, flips included.  A format is
+``FILTER_BILINEAR``, ``bicubic.bicubic`` for ``FILTER_BICUBIC`` and ``lanczos.lanczos`` for ``FILTER_LANCZOS`` (which have no u8 call of their own), ``warp.warp`` for the warp call - with the same item, channels and mode, byte for byte, flips included.  A format is
 (dtype, layout, scale, bias): scale and bias are four binary32 numbers, per channel r, g, b, a.  Element (Y, X, c) has the value v = P[Y][X][c]:
 
     U8      the element is v; scale must be all 1 and bias all +0
@@ -25,13 +25,14 @@ from typing import Sequence, Tuple
 
 import numpy as np
 
-from . import bicubic, bilinear, crops, resize, warp
+from . import bicubic, bilinear, crops, lanczos, resize, warp
 
 U8, F16, BF16, F32 = 0, 1, 2, 3
 HWC, CHW = 0, 1
 FILTER_AREA, FILTER_BILINEAR = 0, 1
 FILTER_BICUBIC = 3              # (2 is not a filter)
-_FILTERS = {FILTER_AREA: resize.resize, FILTER_BILINEAR: bilinear.bilinear, FILTER_BICUBIC: bicubic.bicubic}
+FILTER_LANCZOS = 6              # (nor are 4, 5 and 7)
+_FILTERS = {FILTER_AREA: resize.resize, FILTER_BILINEAR: bilinear.bilinear, FILTER_BICUBIC: bicubic.bicubic, FILTER_LANCZOS: lanczos.lanczos}
 ELEM = {U8: 1, F16: 2, BF16: 2, F32: 4}
 DTYPE_NAMES = {"u8": U8, "f16": F16, "bf16": BF16, "f32": F32}
 PLAIN = resize.PLAIN
@@ -106,13 +107,13 @@ def convert(P: np.ndarray, f) -> np.ndarray:
 
 
 def size(u8_bytes: int, dtype: int) -> int:
-    """Bytes of an output whose u8 form takes u8_bytes (``resize.size``, ``bilinear.size``, ``bicubic.size``, ``warp.size``; 0 stays 0)."""
+    """Bytes of an output whose u8 form takes u8_bytes (``resize.size``, ``bilinear.size``, ``bicubic.size``, ``lanczos.size``, ``warp.size``; 0 stays 0)."""
     return u8_bytes * ELEM[dtype]
 
 
 def tensors(D: np.ndarray, rect, out_size, flags: int = 0, filter: int = FILTER_AREA, mode: int = PLAIN, f=None) -> np.ndarray:
-    """One item of qoimi_decode_tensors: ``convert`` of ``resize.resize``, ``bilinear.bilinear`` or ``bicubic.bicubic`` of the same
-    arguments."""
+    """One item of qoimi_decode_tensors: ``convert`` of ``resize.resize``, ``bilinear.bilinear``, ``bicubic.bicubic`` or ``lanczos.lanczos`` of
+    the same arguments."""
     if filter not in _FILTERS:
         raise ValueError("tensors: unknown filter")
     P = _FILTERS[filter](D, rect, out_size, flags, mode)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """qoitensor for the MI355X path: a set of .qoi files as ONE .npy tensor, N x C x H x W or N x H x W x C, normalised.
 
-    python tools/qoitensor_mi355x.py FILE_OR_DIR... --size WxH -o OUT.npy [--filter area|bilinear|bicubic] [--dtype u8|f16|bf16|f32] [--layout chw|hwc]
+    python tools/qoitensor_mi355x.py FILE_OR_DIR... --size WxH -o OUT.npy [--filter area|bilinear|bicubic|lanczos] [--dtype u8|f16|bf16|f32] [--layout chw|hwc]
                                      [--mean M[,M,M[,M]]] [--std S[,S,S[,S]]] [--fit whole|crop] [--channels 3|4] [--staging-mb M]
 
 Loads the .qoi files (directories are walked), uploads them as ONE pack and makes ONE qoimi_decode_tensors call: every stream is decoded on the
@@ -11,7 +11,7 @@ scale = 1 / (255 * std) and bias = -mean / std are computed in float64 and round
 float32(p) * scale + bias with two roundings and narrows once (qoi_amd/tensors.py states it).  Without --mean / --std the elements are
 p / 255; --dtype u8 takes neither and stores p.  One value of --mean / --std serves every channel; a fourth (alpha) defaults to mean 0, std 1.
 --channels defaults to 3.  bf16 is stored as the uint16 of its bits (NumPy has no bfloat16).  A file that is no QOI stream or whose
-rectangle the filter cannot reduce to the target (64 times in an axis, 32 for bilinear, 16 for bicubic) is reported and left out; exit status 1 if there was
+rectangle the filter cannot reduce to the target (64 times in an axis, 32 for bilinear, 16 for bicubic and lanczos) is reported and left out; exit status 1 if there was
 one, else 0.  Needs torch for device memory, as tools/qoicheck_mi355x.py does.
 """
 from __future__ import annotations
@@ -62,7 +62,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("paths", nargs="+", metavar="FILE_OR_DIR")
     ap.add_argument("--size", required=True, metavar="WxH")
     ap.add_argument("-o", "--out", required=True, metavar="OUT.npy")
-    ap.add_argument("--filter", choices=("area", "bilinear", "bicubic"), default="bilinear")
+    ap.add_argument("--filter", choices=("area", "bilinear", "bicubic", "lanczos"), default="bilinear")
     ap.add_argument("--dtype", choices=("u8", "f16", "bf16", "f32"), default="f32")
     ap.add_argument("--layout", choices=("chw", "hwc"), default="chw")
     ap.add_argument("--mean", default=None, metavar="M[,M,M[,M]]")
@@ -96,13 +96,14 @@ def main(argv, out=print) -> int:
             return 2
     ow, oh = size
     import torch  # first: the library then binds to the HIP runtime torch already loaded
-    from qoi_amd import api, bicubic, bilinear, resize, tensors
+    from qoi_amd import api, bicubic, bilinear, lanczos, resize, tensors
 
     files = collect(a.paths)
     if not files:
         out("no .qoi files")
         return 2
-    model, filt = {"area": (resize, tensors.FILTER_AREA), "bilinear": (bilinear, tensors.FILTER_BILINEAR), "bicubic": (bicubic, tensors.FILTER_BICUBIC)}[a.filter]
+    model, filt = {"area": (resize, tensors.FILTER_AREA), "bilinear": (bilinear, tensors.FILTER_BILINEAR), "bicubic": (bicubic, tensors.FILTER_BICUBIC),
+                   "lanczos": (lanczos, tensors.FILTER_LANCZOS)}[a.filter]
     blobs = [open(f, "rb").read() for f in files]
     heads = [parse_header(b) for b in blobs]
     good = []
