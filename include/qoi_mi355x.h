@@ -655,6 +655,16 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * a = 65536 / s and REPLICATE it is qoimi_decode_bilinear enlarging by the power of two s; a constant rectangle stays the constant under any
  * map with REPLICATE.  Against a float64 evaluation of the same map (torch affine_grid + grid_sample, bilinear, align_corners=False) a value
  * differs by at most 1, and only where the float result lies at a rounding boundary.
+ * QOIMI_WARP_NEAREST (a flag of the item, combinable with QOIMI_WARP_REPLICATE; normative; qoi_amd/warp.py: warp states it in Python) replaces
+ * the 2 x 2 bilinear taps with ONE sample - selection, for label maps that take the geometry of their photograph: Px and Py are exactly as
+ * above; column k = Px >> 17 and row r = Py >> 17 (arithmetic shifts: they floor for negative values); column k covers
+ * [k << 17, (k + 1) << 17), with its centre at (2k + 1) << 16.  If k is outside [0, cw) or r is outside [0, rh): with REPLICATE the index is
+ * clamped into R, without it the output pixel is `fill` (a 3-channel output ignores its alpha); samples outside R are never read.  The output
+ * pixel is the sample, byte for byte, and both modes give the same bytes.  With the identity the call is qoimi_decode_crops; with any
+ * qoimi_warp_orient item it equals the bilinear warp byte for byte, because every position is a pixel centre.  Limits, plan, staging and every
+ * rejection are those of the bilinear warp; the flag rule reads: a bit other than QOIMI_WARP_REPLICATE and QOIMI_WARP_NEAREST (2 is not a
+ * flag, nor is any bit from 8 on).  The flag applies unchanged to qoimi_decode_warped_tensors and qoimi_decode_warped_indexed, and
+ * qoimi_warp_size and qoimi_warp_tensor_size accept it.  Items with and without the flag mix freely in one call.
  * The rectangle is what is staged and what the border is taken at: rows_i of the plan is the maximum of y + height over the items of image i,
  * so the caller keeps the rectangle tight around what the map reaches - a rectangle of the whole image under a map that reaches one corner
  * decodes the whole image.
@@ -671,13 +681,13 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * for the limits above, and for a sub-batch of the plan with 2^31 - 1 or more tiles of 16 x 16 output pixels: reported before anything is
  * launched, the caller's buffers are untouched; qoimi_last_error names the cause.  Output ranges must not overlap.  The sub-batches count as
  * decode calls of the context.  One call at a time per context, as everywhere. */
-enum { QOIMI_WARP_REPLICATE = 1 };
+enum { QOIMI_WARP_REPLICATE = 1, QOIMI_WARP_NEAREST = 4 };   /* 2 is not a flag */
 typedef struct {                 /* 72 bytes, offsets 0/4/8/12/16/20/24/28/32/36/40/44/48/52/56/64 */
     unsigned int image;          /* index into the call's images */
     unsigned int x, y;           /* top-left corner of the source rectangle */
     unsigned int width, height;  /* both >= 1; x + width <= image width, y + height <= image height */
     unsigned int out_width, out_height;  /* both >= 1 and below 2^20; their product below 400 000 000 */
-    unsigned int flags;          /* QOIMI_WARP_REPLICATE; no other bit */
+    unsigned int flags;          /* QOIMI_WARP_REPLICATE, QOIMI_WARP_NEAREST; no other bit */
     int a, b, d, e;              /* the linear part of the inverse map, 16 fractional bits */
     unsigned int fill;           /* r | g << 8 | b << 16 | a << 24: the value of a sample outside the rectangle without REPLICATE */
     unsigned int reserved;       /* 0 */
@@ -776,7 +786,8 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * in bytes; an output address that is not a multiple of the element size; a sub-batch of the plan with 2^31 - 1 tiles or more.  All are
  * reported before anything is launched, the caller's buffers are untouched; qoimi_last_error names the cause.  The sub-batches count as decode
  * calls of the context.  One call at a time per context, as everywhere.
- * Not here: indexed forms, a u8 entry point or a stats function of the bicubic or the Lanczos filter's own, other cubic kernels (a = -3/4), other Lanczos windows, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
+ * Not here: indexed forms, a nearest-neighbour FILTER of qoimi_decode_tensors (for label maps the warp has QOIMI_WARP_NEAREST: an item
+ * whose map is a scale is that filter), integer class-index dtypes (int32, int64) for label maps, a u8 entry point or a stats function of the bicubic or the Lanczos filter's own, other cubic kernels (a = -3/4), other Lanczos windows, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
  * size of its rectangle, or divides it, is those), tensors as the source of an encode (qoimi_encode_tiles takes bytes). */
 enum { QOIMI_TENSOR_U8 = 0, QOIMI_TENSOR_F16 = 1, QOIMI_TENSOR_BF16 = 2, QOIMI_TENSOR_F32 = 3 };   /* element sizes 1 / 2 / 2 / 4 */
 enum { QOIMI_TENSOR_HWC = 0, QOIMI_TENSOR_CHW = 1 };

@@ -326,7 +326,7 @@ static_assert(sizeof(qoimi_warp) == 72 && offsetof(qoimi_warp, image) == 0 && of
               offsetof(qoimi_warp, out_height) == 24 && offsetof(qoimi_warp, flags) == 28 && offsetof(qoimi_warp, a) == 32 && offsetof(qoimi_warp, b) == 36 &&
               offsetof(qoimi_warp, d) == 40 && offsetof(qoimi_warp, e) == 44 && offsetof(qoimi_warp, fill) == 48 && offsetof(qoimi_warp, reserved) == 52 &&
               offsetof(qoimi_warp, c) == 56 && offsetof(qoimi_warp, f) == 64, "qoimi_warp layout");
-static_assert(QOIMI_WARP_REPLICATE == (int)kWarpReplicate, "the table's flag bit");
+static_assert(QOIMI_WARP_REPLICATE == (int)kWarpReplicate && QOIMI_WARP_NEAREST == (int)kWarpNearest, "the table's flag bits: 2 is not a flag, nor is a bit from 8 on");
 
 extern "C" size_t qoimi_warp_size(const qoi_desc* desc, const qoimi_warp* item, int channels) {
     size_t bytes = 0;

@@ -311,7 +311,7 @@ struct CropEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, ch, first_tile, c
 struct ResizeEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, rh, ow, oh, first_tile, cfg, reserved; };
 // StatsEntry::index: the region's entry in the result table (and its histogram); cfg: the region's flags
 struct StatsEntry { u64 src_off; uint32_t w, x, y, cw, ch, first_tile, index, cfg, reserved[2]; };
-// WarpEntry::cfg: och | (alpha weighted ? 1 : 0) << 8 | flags << 16; a, b, c, d, e, f: the item's map (qoi_warp_core.h), fill: its fill colour
+// WarpEntry::cfg: och | (alpha weighted ? 1 : 0) << 8 | flags << 16 (kWarpReplicate, kWarpNearest); a, b, c, d, e, f: the item's map (qoi_warp_core.h), fill: its fill colour
 struct WarpEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, rh, ow, oh, first_tile, cfg, fill; int32_t a, b, d, e; long long c, f; };
 static_assert(sizeof(ThumbImage) == 48 && sizeof(CropEntry) == 48 && sizeof(ResizeEntry) == 56 && sizeof(StatsEntry) == 48, "table layouts");
 static_assert(sizeof(WarpEntry) == 88 && offsetof(WarpEntry, first_tile) == 44 && offsetof(WarpEntry, a) == 56 && offsetof(WarpEntry, c) == 72, "table layouts");

@@ -131,7 +131,7 @@ static const char* warp_item_wrong(const qoi_desc* d, const qoimi_warp* r) {
     if (r->out_width >= kWarpMaxOut || r->out_height >= kWarpMaxOut) return "out_width or out_height is 2^20 or more";
     if ((uint64_t)r->out_width * r->out_height >= kWarpMaxArea) return "out_width * out_height is 400 000 000 or more";
     if (r->c <= -kWarpMaxOffset || r->c >= kWarpMaxOffset || r->f <= -kWarpMaxOffset || r->f >= kWarpMaxOffset) return "|c| or |f| is 2^56 or more";
-    if ((r->flags & ~(unsigned)QOIMI_WARP_REPLICATE) != 0u) return "unknown flag bit";
+    if ((r->flags & ~(unsigned)(QOIMI_WARP_REPLICATE | QOIMI_WARP_NEAREST)) != 0u) return "unknown flag bit";
     if (r->reserved != 0u) return "reserved is not 0";
     return nullptr;
 }

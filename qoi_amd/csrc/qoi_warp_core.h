@@ -14,6 +14,11 @@
 //   ALPHA_WEIGHTED  alpha likewise; with A = N_3 > 0 the colours are (M_c + A/2) / A; with A == 0 they are the PLAIN value
 // Pixel (X, Y) is written at pixel (X, Y) of the output, och = 3 or 4 bytes per pixel, tightly packed from the absolute address q.  There is no
 // antialiasing: a map that reduces still takes four samples.
+// With kWarpNearest (a flag of the item, so the same for every work item of a tile) the 2 x 2 taps are replaced by ONE sample - selection, for
+// label maps: column k = Px >> 17, row r = Py >> 17 (arithmetic: they floor; column k covers [k << 17, (k + 1) << 17), its centre at
+// (2k + 1) << 16).  Outside the rectangle the index is clamped into it with kWarpReplicate, else the pixel is `fill`; the output pixel is the
+// sample byte for byte in both modes (warp_nearest).  At a pixel centre - the identity, every qoimi_warp_orient item - that is the bilinear
+// result, whose one sample with a weight has all of it.
 // Bounds.  ow, oh < 2^20, so U, V < 2^21 and |a * U|, |b * V| <= 2^31 * 2^21 = 2^52; |c| < 2^56: |P| < 2^56 + 2^53 < 2^57 - both positions and
 // the indices made of them are 64-bit, and the border is tested on the 64-bit index before anything is narrowed.  A horizontal blend
 // wx0 * v0 + wx1 * v1 <= 255 * 2^17 is 32-bit; N_c <= 255 * 2^34 < 2^42.  With alpha a value is at most 255 * 255, its horizontal blend
@@ -35,13 +40,14 @@ namespace qoimi {
 constexpr uint32_t kWarpTile = 16;                              // a tile is kWarpTile x kWarpTile output pixels
 constexpr uint32_t kWarpThreads = kWarpTile * kWarpTile;        // its work items: the workgroup of warp_gather
 constexpr uint32_t kWarpReplicate = 1;
+constexpr uint32_t kWarpNearest = 4;                            // (2 is not a flag)
 constexpr uint32_t kWarpMaxOut = 1u << 20;                      // ow, oh stay below it
 constexpr uint64_t kWarpMaxArea = 400000000ull;                 // ow * oh stays below it
 constexpr int64_t kWarpMaxOffset = 1ll << 56;                   // |c|, |f| stay below it
 constexpr uint32_t kWarpHalf = 1u << 16, kWarpOne = 1u << 17;   // half a pixel and a pixel in doubled coordinates with 16 fractional bits
 constexpr uint64_t kWarpTotal = 1ull << 34;                     // the weights of a pixel
 
-// w: pixels per staged row; (x, y, cw, rh): the rectangle; ow x oh: the output; flags: kWarpReplicate; the map; fill
+// w: pixels per staged row; (x, y, cw, rh): the rectangle; ow x oh: the output; flags: kWarpReplicate, kWarpNearest; the map; fill
 struct WarpGeom { uint32_t w, x, y, cw, rh, ow, oh, flags; int32_t a, b, d, e; uint32_t fill; int64_t c, f; };
 // The two samples of one axis: i[j] the index inside the rectangle where in[j], wgt[j] the weight (0: not taken)
 struct WarpAxis { uint32_t i[2], wgt[2]; bool in[2]; };
@@ -113,6 +119,19 @@ QOIMI_RESIZE_HD uint32_t warp_pixel(const Mem& mem, const WarpGeom& g, uint32_t 
     return resize_pixel(s, kWarpTotal, WEIGHTED);
 }
 
+// Output pixel (X, Y) under kWarpNearest: one load, none where the pixel takes the fill.
+template <class Mem>
+QOIMI_RESIZE_HD uint32_t warp_nearest(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
+    int64_t k = warp_position(g.a, g.b, g.c, X, Y) >> 17, r = warp_position(g.d, g.e, g.f, X, Y) >> 17;   // (64-bit: the border test comes before the narrowing)
+    bool in = k >= 0 && k < (int64_t)g.cw && r >= 0 && r < (int64_t)g.rh;
+    if ((g.flags & kWarpReplicate) != 0u) {
+        k = k < 0 ? 0 : (k < (int64_t)g.cw ? k : (int64_t)g.cw - 1);
+        r = r < 0 ? 0 : (r < (int64_t)g.rh ? r : (int64_t)g.rh - 1);
+        in = true;
+    }
+    return in ? mem.load((uint64_t)(g.y + (uint32_t)r) * g.w + g.x + (uint32_t)k) : g.fill;
+}
+
 // Pixel (X, Y) to its place in the output at q: one dword where the output holds 4 bytes per pixel and the address is aligned, else och
 // bytes - the item's own bytes only, never a word that would have to be read first.
 template <class Mem>
@@ -137,7 +156,7 @@ template <bool WEIGHTED, class Mem, class Sink>
 QOIMI_RESIZE_HD void warp_work(const Mem& mem, const WarpGeom& g, uint64_t q, uint32_t och, uint32_t tile, uint32_t t, const Sink& sink) {
     uint32_t X, Y;
     if (!warp_place(tile, t, g.ow, g.oh, X, Y)) return;
-    sink(mem, g, q, och, X, Y, warp_pixel<WEIGHTED>(mem, g, X, Y));
+    sink(mem, g, q, och, X, Y, (g.flags & kWarpNearest) != 0u ? warp_nearest(mem, g, X, Y) : warp_pixel<WEIGHTED>(mem, g, X, Y));
 }
 
 // ... stored as bytes (warp_store)

@@ -13,6 +13,11 @@ integer, every shift and division floors.
   ``131072 - fx`` and ``fx``; rows likewise from Py.  A sample with a weight of 0 counts as not taken.
 * Samples outside R are never read, even where the image has pixels there: with ``REPLICATE`` their indices are clamped into R, otherwise
   they take ``fill`` (``r | g << 8 | b << 16 | a << 24``; a 3-channel output ignores its alpha).
+* With ``NEAREST`` (a flag, combinable with ``REPLICATE``) the 2 x 2 taps are replaced by ONE sample - selection, for label maps: column
+  ``k = Px >> 17``, row ``r = Py >> 17`` (they floor for negative values); column k covers ``[k << 17, (k + 1) << 17)``, its centre at
+  ``(2k + 1) << 16``.  Where k is outside ``[0, cw)`` or r outside ``[0, rh)`` the index is clamped into R with ``REPLICATE``, else the output
+  pixel is ``fill`` (a 3-channel output ignores its alpha).  The output pixel is the sample, byte for byte, in both modes.  With the
+  identity that is ``crops.crop``; with any ``orient`` item it equals the bilinear result, every position being a pixel centre.
 * ``N_c = sum wy * wx * c`` over the four samples; the weights add up to ``2**34``.
 * ``PLAIN``: every channel is ``(N_c + 2**33) >> 34`` - ONE rounding.
 * ``ALPHA_WEIGHTED``, 4 channels only: ``A = N_a``; alpha as in the plain mode; where ``A > 0`` r, g and b are
@@ -20,7 +25,7 @@ integer, every shift and division floors.
 * There is no antialiasing: a map that reduces still takes four samples (reduce first with ``resize.resize`` where that matters).
 
 Limits, in the order the C side checks them: a zero size; a rectangle that leaves its image; ``ow, oh < 2**20``; ``ow * oh < 400 000 000``;
-``|c|, |f| < 2**56``; no flag bit but ``REPLICATE``; ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
+``|c|, |f| < 2**56``; no flag bit but ``REPLICATE`` and ``NEAREST`` (2 is not a flag); ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
 ``|Px|, |Py| < 2**57``; ``N_c <= 255 * 2**34 < 2**42``; the alpha-weighted sums are below ``2**50``: everything fits int64.
 
 With the identity the result is ``crops.crop``; with ``a = ONE // s`` and REPLICATE it is ``bilinear.bilinear`` enlarging by the power of two s;
@@ -38,6 +43,7 @@ import numpy as np
 from . import crops, resize
 
 REPLICATE = 1
+NEAREST = 4                     # one sample, not 2 x 2 taps (2 is not a flag)
 PLAIN = resize.PLAIN
 ALPHA_WEIGHTED = resize.ALPHA_WEIGHTED
 ONE = 1 << 16                   # a factor of 1; a pixel is 2 * ONE in doubled coordinates
@@ -88,7 +94,7 @@ def _wrong(w: int, h: int, rect, out_size, matrix, flags: int, reserved: int = 0
         return "|c| or |f| from 2**56"
     if any(not -2 ** 31 <= v < 2 ** 31 for v in (a, b, d, e)):
         return "a, b, d, e are 32-bit"
-    if flags & ~REPLICATE:
+    if flags & ~(REPLICATE | NEAREST):
         return "unknown flag bit"
     if reserved:
         return "reserved is not 0"
@@ -133,6 +139,13 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
     F = np.array([(fill >> (8 * k)) & 255 for k in range(4)], dtype=np.int64)
     U = (2 * np.arange(ow, dtype=np.int64) + 1)[None, :]
     V = (2 * np.arange(oh, dtype=np.int64) + 1)[:, None]
+    if flags & NEAREST:
+        k, r = (a * U + b * V + c) >> 17, (d * U + e * V + f) >> 17
+        inside = (k >= 0) & (k < cw) & (r >= 0) & (r < rh)
+        if flags & REPLICATE:
+            inside = np.ones_like(inside)
+        out = np.where(inside[..., None], R[np.clip(r, 0, rh - 1), np.clip(k, 0, cw - 1)], F[None, None, :])
+        return np.ascontiguousarray(out[..., :och].astype(np.uint8))
     kx, wx, inx = _axis(a * U + b * V + c, cw, bool(flags & REPLICATE))
     ky, wy, iny = _axis(d * U + e * V + f, rh, bool(flags & REPLICATE))
     N = np.zeros((oh, ow, 4), dtype=np.int64)
