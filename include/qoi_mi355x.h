@@ -722,17 +722,23 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * those of the underlying call: qoimi_decode_resized for QOIMI_FILTER_AREA, qoimi_decode_bilinear for QOIMI_FILTER_BILINEAR, qoimi_decode_warped
  * for qoimi_decode_warped_tensors.  QOIMI_FILTER_BICUBIC has no call of its own - its "underlying call" is the definition below, everything
  * but the filter and its limits as for qoimi_decode_bilinear; QOIMI_TENSOR_U8 with QOIMI_TENSOR_HWC gives its plain interleaved bytes.
- * QOIMI_FILTER_LANCZOS likewise.
+ * QOIMI_FILTER_LANCZOS and QOIMI_FILTER_NEAREST likewise.
  * The result (normative; qoi_amd/tensors.py: convert states it in Python): let P be the oh x ow x och u8 result of the underlying call with the
  * same items, channels and mode, byte for byte, flips included.  Element (Y, X, c) of output j has the value v = P[Y][X][c], an integer 0..255.
  *   QOIMI_TENSOR_U8    the element is v; scale must be all 1.0f and bias all +0.0f
  *   QOIMI_TENSOR_F32   t = (float)v; m = t * scale[c], rounded to nearest even in binary32; s = m + bias[c], rounded to nearest even in
  *                      binary32: TWO roundings, never a fused multiply-add; the element is s
  *   QOIMI_TENSOR_F16, QOIMI_TENSOR_BF16   s converted to binary16 / bfloat16, round to nearest even
+ *   QOIMI_TENSOR_I32, QOIMI_TENSOR_I64   the element is v as a little-endian two's-complement integer of 4 / 8 bytes - the integer class-index dtypes
+ *                      a loss function takes; scale must be all 1.0f and bias all +0.0f, as for QOIMI_TENSOR_U8
  * Subnormals are kept, not flushed, in every format; a result too large for its format becomes infinity.  scale and bias are per channel r, g,
  * b, a; a 3-channel output ignores the fourth.  The element is stored at element index (Y * ow + X) * och + c for QOIMI_TENSOR_HWC, at
  * (c * oh + Y) * ow + X for QOIMI_TENSOR_CHW, from d_out + out_offsets[j]; an output is tightly packed, ow * oh * och * element size bytes
- * (qoimi_tensor_size, qoimi_warp_tensor_size).  QOIMI_TENSOR_U8 with QOIMI_TENSOR_HWC therefore is the underlying call byte for byte, and every
+ * (qoimi_tensor_size, qoimi_warp_tensor_size).  With QOIMI_TENSOR_HW only the FIRST channel (r) of each pixel is stored, as one plane: element
+ * index Y * ow + X, scale[0] and bias[0] (the others are ignored but must still be finite), an output of ow * oh * element size bytes - the
+ * sizes, the overlap check and the alignment check count it that way; `channels` still says how the image is decoded, the layout only chooses
+ * what is stored.  Every layout goes with every dtype, every filter and the warp: QOIMI_TENSOR_I64 with QOIMI_TENSOR_HW is the N x H x W of
+ * class indices a loss function takes.  QOIMI_TENSOR_U8 with QOIMI_TENSOR_HWC therefore is the underlying call byte for byte, and every
  * other format a pure function of its bytes: the exact-integer definitions of the three filters stand as they are.
  * Only whole, naturally aligned elements are stored (u8 HWC: as the underlying call stores): no word is read and written back, two outputs
  * may share one.
@@ -775,26 +781,44 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * the largest difference the tests see is 1).  PIL rounds between its two passes and differs from this by a few units.
  * Its limits are those of QOIMI_FILTER_BICUBIC, each a QOIMI_E_ARG item by item: width <= 16 * out_width and height <= 16 * out_height (at
  * most 96 taps per axis); max(width, out_width) <= 16384 and max(height, out_height) <= 16384.
- *   filter         QOIMI_FILTER_LANCZOS, QOIMI_FILTER_AREA, QOIMI_FILTER_BILINEAR or QOIMI_FILTER_BICUBIC (qoimi_decode_tensors only)
+ * QOIMI_FILTER_NEAREST (normative; qoi_amd/nearest.py: nearest states it in Python) is selection, not a filter that averages - for label
+ * maps: segmentation masks, instance ids, palette indices, whose values must not be mixed.  D, R, cw, rh, ow, oh and och as for
+ * qoimi_decode_resized; all arithmetic is integer and floors.  Output pixel (X, Y) is R[r][k] byte for byte, with
+ *   k = ((2X + 1) * cw) / (2 * ow),  r = ((2Y + 1) * rh) / (2 * oh)
+ * - the source pixel whose cell holds the output pixel's centre, on the line the tent filter uses (a centre on the boundary of two cells
+ * belongs to the upper one).  k < cw always holds: nothing outside R is read.  Both modes give the same bytes of it; a 3-channel decode has
+ * alpha 255, och 3 drops alpha.  QOIMI_RESIZE_FLIP_X / _Y reverse the columns / rows of that result.  With the output the size of the rectangle
+ * it is qoimi_decode_crops; with cw = f * ow it takes column X * f + f / 2; and it equals qoimi_decode_warped with QOIMI_WARP_NEAREST and the map
+ * a = 65536 * cw / ow, e = 65536 * rh / oh, everything else 0, wherever both quotients are whole.  torch's interpolate(mode="nearest-exact")
+ * computes the same index in float and is one lower at some of the positions where (2X + 1) * cw is a multiple of 2 * ow; there the integer
+ * definition is the exact one.
+ * Its limits, each a QOIMI_E_ARG item by item, in this order: the rectangle rules of the other filters (a zero size, an unknown flag bit, a
+ * rectangle that leaves its image); then max(width, out_width) <= 16384 and max(height, out_height) <= 16384 - the size limit of
+ * QOIMI_FILTER_BICUBIC ((2X + 1) * cw < 2^29: no 64-bit division).  There is NO ratio limit: every output pixel is one load.
+ *   filter         QOIMI_FILTER_LANCZOS, QOIMI_FILTER_AREA, QOIMI_FILTER_BILINEAR or QOIMI_FILTER_BICUBIC, or QOIMI_FILTER_NEAREST
+ *                  (qoimi_decode_tensors only)
  *   format         HOST; one for the whole call
- *   d_out, out_offsets   every d_out + out_offsets[j] a multiple of the element size (1 / 2 / 2 / 4)
+ *   d_out, out_offsets   every d_out + out_offsets[j] a multiple of the element size (1 / 2 / 2 / 4, 4 / 8 for QOIMI_TENSOR_I32 / _I64)
  *   everything else      as for the underlying call
  * SYNCHRONOUS: returns when every output is written.  QOIMI_E_ARG, looked for in this order: an unknown filter; a NULL or empty argument
  * (format apart); channels; mode; the format - NULL, an unknown dtype, an unknown layout, reserved != 0, a scale or bias that is not finite,
- * QOIMI_TENSOR_U8 with a scale other than 1 or a bias other than +0; then everything the underlying call rejects, with its messages, item by
+ * QOIMI_TENSOR_U8, QOIMI_TENSOR_I32 or QOIMI_TENSOR_I64 with a scale other than 1 or a bias other than +0; then everything the underlying call rejects, with its messages, item by
  * item - an output whose size in BYTES does not fit a size_t or that ends behind the address space among them -, output ranges that overlap,
  * in bytes; an output address that is not a multiple of the element size; a sub-batch of the plan with 2^31 - 1 tiles or more.  All are
  * reported before anything is launched, the caller's buffers are untouched; qoimi_last_error names the cause.  The sub-batches count as decode
  * calls of the context.  One call at a time per context, as everywhere.
- * Not here: indexed forms, a nearest-neighbour FILTER of qoimi_decode_tensors (for label maps the warp has QOIMI_WARP_NEAREST: an item
- * whose map is a scale is that filter), integer class-index dtypes (int32, int64) for label maps, a u8 entry point or a stats function of the bicubic or the Lanczos filter's own, other cubic kernels (a = -3/4), other Lanczos windows, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
+ * Not here: indexed forms, a majority (mode) filter for REDUCING label maps (QOIMI_FILTER_NEAREST takes one pixel of each cell, whatever its
+ * neighbours hold), 16-bit or signed label sources (a label is a byte of the image), a remapping table from byte to class index, a single
+ * 8-byte store per QOIMI_TENSOR_I64 element (it is two dword stores), a u8 entry point or a stats function of the bicubic, the Lanczos or the nearest filter's own, other cubic kernels (a = -3/4), other Lanczos windows, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
  * size of its rectangle, or divides it, is those), tensors as the source of an encode (qoimi_encode_tiles takes bytes). */
 enum { QOIMI_TENSOR_U8 = 0, QOIMI_TENSOR_F16 = 1, QOIMI_TENSOR_BF16 = 2, QOIMI_TENSOR_F32 = 3 };   /* element sizes 1 / 2 / 2 / 4 */
-enum { QOIMI_TENSOR_HWC = 0, QOIMI_TENSOR_CHW = 1 };
+enum { QOIMI_TENSOR_I32 = 5, QOIMI_TENSOR_I64 = 6 };   /* element sizes 4 / 8; 4 is not a dtype */
+enum { QOIMI_TENSOR_HWC = 0, QOIMI_TENSOR_CHW = 1, QOIMI_TENSOR_HW = 3 };   /* 2 is not a layout */
 enum { QOIMI_FILTER_AREA = 0, QOIMI_FILTER_BILINEAR = 1, QOIMI_FILTER_BICUBIC = 3, QOIMI_FILTER_LANCZOS = 6 };   /* 2 is not a filter, nor are 4, 5 and 7 */
+enum { QOIMI_FILTER_NEAREST = 9 };   /* 8 is not a filter */
 typedef struct {                 /* 48 bytes, offsets 0/4/8/24/40 */
     unsigned int dtype;          /* QOIMI_TENSOR_* */
-    unsigned int layout;         /* QOIMI_TENSOR_HWC / _CHW */
+    unsigned int layout;         /* QOIMI_TENSOR_HWC / _CHW / _HW */
     float scale[4];              /* per channel r, g, b, a */
     float bias[4];
     unsigned int reserved[2];    /* 0 */
@@ -808,9 +832,10 @@ int qoimi_decode_warped_tensors(qoimi_ctx *ctx, const void *d_streams, const siz
                                 const qoimi_warp *items /* host */, int n_items, int mode, const qoimi_tensor_format *format /* host */,
                                 void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream);
 
-/* out_width * out_height * channels * element size - the bytes of the item's output - or 0 if filter is unknown, the format is one the calls
- * reject, qoimi_resize_size / qoimi_bilinear_size (by filter) or qoimi_warp_size would return 0, the item is beyond the limits of
- * QOIMI_FILTER_BICUBIC or QOIMI_FILTER_LANCZOS with that filter, or the product does not fit a size_t.  Pure
+/* out_width * out_height * channels * element size (QOIMI_TENSOR_HW: out_width * out_height * element size) - the bytes of the item's output -
+ * or 0 if filter is unknown, the format is one the calls reject, qoimi_resize_size / qoimi_bilinear_size (by filter) or qoimi_warp_size would
+ * return 0, the item is beyond the limits of QOIMI_FILTER_BICUBIC, QOIMI_FILTER_LANCZOS or QOIMI_FILTER_NEAREST with that filter, or the
+ * product does not fit a size_t.  Pure
  * host arithmetic: no context, no GPU. */
 size_t qoimi_tensor_size(const qoi_desc *desc, const qoimi_resize *item, int filter, int channels, const qoimi_tensor_format *format);
 size_t qoimi_warp_tensor_size(const qoi_desc *desc, const qoimi_warp *item, int channels, const qoimi_tensor_format *format);

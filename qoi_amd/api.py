@@ -202,7 +202,8 @@ def tensor_format(f) -> "QoimiTensorFormat":
 
 def tensor_size(width: int, height: int, channels_in: int, item, filter: int, channels: int, f) -> int:
     """``qoimi_tensor_size`` for an image of width x height x channels_in: the bytes of the output of `item` (as for ``resize_size``) under
-    `filter` (``tensors.FILTER_AREA`` / ``FILTER_BILINEAR`` / ``FILTER_BICUBIC`` / ``FILTER_LANCZOS``) with `channels` (3 or 4) elements per pixel in the format f; 0 where the C
+    `filter` (``tensors.FILTER_AREA`` / ``FILTER_BILINEAR`` / ``FILTER_BICUBIC`` / ``FILTER_LANCZOS`` / ``FILTER_NEAREST``) with `channels` (3 or 4) elements per pixel
+    (``tensors.HW``: one) in the format f; 0 where the C
     function returns 0."""
     args = _size_args(QoimiResize, width, height, channels_in, item)
     return int(load_library().qoimi_tensor_size(*args, filter, channels, ctypes.byref(tensor_format(f)))) if args else 0
@@ -678,9 +679,11 @@ class Context:
                        items, filter: int, mode: int, f, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
         """``decode_resized`` (filter ``tensors.FILTER_AREA``), ``decode_bilinear`` (``tensors.FILTER_BILINEAR``) or the antialiased bicubic
         filter ``qoi_amd/bicubic.py`` states (``tensors.FILTER_BICUBIC``; it has no u8 call: U8 with HWC gives its bytes) or the Lanczos filter of
-        ``qoi_amd/lanczos.py`` (``tensors.FILTER_LANCZOS``, likewise) with the outputs written
+        ``qoi_amd/lanczos.py`` (``tensors.FILTER_LANCZOS``, likewise) or the nearest filter of ``qoi_amd/nearest.py`` for label maps
+        (``tensors.FILTER_NEAREST``, likewise) with the outputs written
         as tensors (``qoimi_decode_tensors``, synchronous, through bounded staging): f is a ``QoimiTensorFormat`` or the tuple of
-        ``tensors.fmt`` - u8, f16, bf16 or f32 elements, HWC or CHW, each channel scaled and shifted; every d_out + out_offsets[j] is a
+        ``tensors.fmt`` - u8, f16, bf16 or f32 elements, HWC or CHW, each channel scaled and shifted, or i32 / i64 class indices, and HW: the
+        first channel as one plane; every d_out + out_offsets[j] is a
         multiple of the element size; ``qoi_amd/tensors.py: tensors`` states the result."""
         self._gather("decode_tensors", QoimiResize, d_streams, stream_offsets, sizes, descs, channels, items, (filter, mode), d_out, out_offsets, staging_bytes,
                      stream, f=f)

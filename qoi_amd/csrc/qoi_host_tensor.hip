@@ -1,10 +1,11 @@
 // qoi_host_tensor.hip — the tensor calls of the C-ABI shim: qoimi_decode_tensors (the area filter, the antialiased bilinear filter or the
-// antialiased bicubic and Lanczos filters, which only this call has) and qoimi_decode_warped_tensors, with qoimi_tensor_size and qoimi_warp_tensor_size.  They are gather_resampled and gather_warped of qoi_staged.h -
+// antialiased bicubic and Lanczos filters and the nearest filter, which only this call has) and qoimi_decode_warped_tensors, with qoimi_tensor_size and qoimi_warp_tensor_size.  They are gather_resampled and gather_warped of qoi_staged.h -
 // the checks of the items, the plan, the table entries and run_staged of qoimi_decode_resized / _bilinear / _warped - with the checks of the
 // format in front, output sizes in bytes of elements, the alignment of the outputs behind, and the tensor kernels of qoi_tensor.hip as the
 // launch.
 #include "qoi_staged.h"
 #include "qoi_lanczos_core.h"
+#include "qoi_nearest_core.h"
 #include "qoi_tensor_core.h"
 
 #include <math.h>
@@ -15,20 +16,27 @@ static_assert(sizeof(qoimi_tensor_format) == 48 && offsetof(qoimi_tensor_format,
               "qoimi_tensor_format layout");
 static_assert(sizeof(TensorFormat) == 40, "the format is ten dwords of kernel arguments");
 static_assert(QOIMI_TENSOR_U8 == (int)kTensorU8 && QOIMI_TENSOR_F16 == (int)kTensorF16 && QOIMI_TENSOR_BF16 == (int)kTensorBF16 && QOIMI_TENSOR_F32 == (int)kTensorF32 &&
-              QOIMI_TENSOR_HWC == (int)kTensorHWC && QOIMI_TENSOR_CHW == (int)kTensorCHW, "the kernels take dtype and layout as numbers");
+              QOIMI_TENSOR_I32 == (int)kTensorI32 && QOIMI_TENSOR_I64 == (int)kTensorI64 &&
+              QOIMI_TENSOR_HWC == (int)kTensorHWC && QOIMI_TENSOR_CHW == (int)kTensorCHW && QOIMI_TENSOR_HW == (int)kTensorHW, "the kernels take dtype and layout as numbers");
+static_assert(QOIMI_TENSOR_I32 == 5 && QOIMI_TENSOR_I64 == 6 && QOIMI_TENSOR_HW == 3, "4 is not a dtype, 2 is not a layout");
+
+static bool tensor_dtype_known(unsigned dtype) { return dtype <= (unsigned)QOIMI_TENSOR_F32 || dtype == (unsigned)QOIMI_TENSOR_I32 || dtype == (unsigned)QOIMI_TENSOR_I64; }
+static bool tensor_layout_known(unsigned layout) { return layout <= (unsigned)QOIMI_TENSOR_CHW || layout == (unsigned)QOIMI_TENSOR_HW; }
 
 // nullptr if the format is fine, else what is wrong with it - in the order the header gives
 static const char* tensor_format_wrong(const qoimi_tensor_format* f) {
     if (!f) return "format is NULL";
-    if (f->dtype > (unsigned)QOIMI_TENSOR_F32) return "unknown dtype";
-    if (f->layout > (unsigned)QOIMI_TENSOR_CHW) return "unknown layout";
+    if (!tensor_dtype_known(f->dtype)) return "unknown dtype";
+    if (!tensor_layout_known(f->layout)) return "unknown layout";
     if (f->reserved[0] != 0u || f->reserved[1] != 0u) return "format reserved is not 0";
     for (int k = 0; k < 4; ++k) {
         if (!isfinite(f->scale[k]) || !isfinite(f->bias[k])) return "scale or bias is not finite";
     }
-    if (f->dtype == (unsigned)QOIMI_TENSOR_U8) {
+    if (tensor_integer(f->dtype)) {                                // (the element is the byte's value: nothing is scaled)
         for (int k = 0; k < 4; ++k) {
-            if (f->scale[k] != 1.0f || f->bias[k] != 0.0f || signbit(f->bias[k])) return "QOIMI_TENSOR_U8 takes scale 1 and bias +0 only";
+            if (f->scale[k] != 1.0f || f->bias[k] != 0.0f || signbit(f->bias[k]))
+                return f->dtype == (unsigned)QOIMI_TENSOR_U8 ? "QOIMI_TENSOR_U8 takes scale 1 and bias +0 only"
+                     : f->dtype == (unsigned)QOIMI_TENSOR_I32 ? "QOIMI_TENSOR_I32 takes scale 1 and bias +0 only" : "QOIMI_TENSOR_I64 takes scale 1 and bias +0 only";
         }
     }
     return nullptr;
@@ -46,11 +54,18 @@ static TensorFormat kernel_format(const qoimi_tensor_format* f) {
     return t;
 }
 
-// pixel_bytes (resize_bytes, warp_bytes: the u8 output) times the element size, false if that does not fit a size_t
+// Bytes of an element of the format; 1 for a format the check rejects (used behind the format's check only)
+static size_t format_elem(const qoimi_tensor_format* f) { return (f && tensor_dtype_known(f->dtype)) ? tensor_elem(f->dtype) : 1u; }
+// Elements of a pixel of an output with och channels: one under QOIMI_TENSOR_HW
+static unsigned format_channels(const qoimi_tensor_format* f, unsigned och) { return (f && f->layout == (unsigned)QOIMI_TENSOR_HW) ? 1u : och; }
+
+// pixel_bytes (resize_bytes, warp_bytes: the u8 output) at the format's elements per pixel times the element size, false if that does not
+// fit a size_t
 template <class Item>
-static bool tensor_bytes(bool (*pixel_bytes)(const Item*, unsigned, size_t*), const Item* r, unsigned och, size_t elem, size_t* bytes) {
+static bool tensor_bytes(bool (*pixel_bytes)(const Item*, unsigned, size_t*), const Item* r, unsigned och, const qoimi_tensor_format* f, size_t* bytes) {
     size_t b = 0;
-    if (!pixel_bytes(r, och, &b) || b > ~(size_t)0 / elem) return false;
+    const size_t elem = format_elem(f);
+    if (!pixel_bytes(r, format_channels(f, och), &b) || b > ~(size_t)0 / elem) return false;
     *bytes = b * elem;
     return true;
 }
@@ -64,7 +79,9 @@ static int check_tensor_alignment(const void* d_out, const size_t* out_offsets, 
     return QOIMI_OK;
 }
 
-static_assert(QOIMI_FILTER_AREA == 0 && QOIMI_FILTER_BILINEAR == 1 && QOIMI_FILTER_BICUBIC == 3 && QOIMI_FILTER_LANCZOS == 6, "2, 4, 5 and 7 are not filters");
+static_assert(QOIMI_FILTER_AREA == 0 && QOIMI_FILTER_BILINEAR == 1 && QOIMI_FILTER_BICUBIC == 3 && QOIMI_FILTER_LANCZOS == 6 && QOIMI_FILTER_NEAREST == 9,
+              "2, 4, 5, 7 and 8 are not filters");
+static_assert(kNearestMaxSize == kCubicMaxSize, "the nearest filter has the bicubic filter's size limit");
 static_assert(kLanczosMaxRatio == kCubicMaxRatio && kLanczosMaxSize == kCubicMaxSize, "the two filters share their limits: cubic_item_wrong");
 
 // ... with the ratio limit of 16 and the size limit (qoi_cubic_core.h, qoi_lanczos_core.h: what keeps the weights in 64 bits and a tile's tables
@@ -76,9 +93,17 @@ static const char* cubic_item_wrong(const qoi_desc* d, const qoimi_resize* r) {
     return nullptr;
 }
 
-// The bicubic and the Lanczos filter write tensors only: no launcher of a byte kernel, the counters and the name are the tensor call's.
+// ... with the size limit alone (qoi_nearest_core.h: what keeps an index in one 32-bit division): no ratio limit, every output pixel is one load
+static const char* nearest_item_wrong(const qoi_desc* d, const qoimi_resize* r) {
+    if (const char* what = resample_rect_wrong(d, r)) return what;
+    if (r->width > kNearestMaxSize || r->out_width > kNearestMaxSize || r->height > kNearestMaxSize || r->out_height > kNearestMaxSize) return "a width or height above 16384";
+    return nullptr;
+}
+
+// The bicubic, the Lanczos and the nearest filter write tensors only: no launcher of a byte kernel, the counters and the name are the tensor call's.
 static const ResampleKind kCubicKind = {cubic_item_wrong, cubic_split, cubic_tiles, nullptr, &qoimi_ctx::tensor_stats, "tensor_cubic"};
 static const ResampleKind kLanczosKind = {cubic_item_wrong, lanczos_split, lanczos_tiles, nullptr, &qoimi_ctx::tensor_stats, "tensor_lanczos"};
+static const ResampleKind kNearestKind = {nearest_item_wrong, nearest_split, nearest_tiles, nullptr, &qoimi_ctx::tensor_stats, "tensor_nearest"};
 
 // A filter of qoimi_decode_tensors: its kind, the launcher of its tensor kernel and that kernel's name for a launch failure
 struct TensorFilter {
@@ -93,6 +118,7 @@ static TensorFilter tensor_filter(int filter) {
     case QOIMI_FILTER_BILINEAR: return {&kTentKind, launch_tensor_tent, "tensor_tent"};
     case QOIMI_FILTER_BICUBIC: return {&kCubicKind, launch_tensor_cubic, kCubicKind.kernel};
     case QOIMI_FILTER_LANCZOS: return {&kLanczosKind, launch_tensor_lanczos, kLanczosKind.kernel};
+    case QOIMI_FILTER_NEAREST: return {&kNearestKind, launch_tensor_nearest, kNearestKind.kernel};
     default: return {nullptr, nullptr, nullptr};
     }
 }
@@ -101,14 +127,14 @@ extern "C" size_t qoimi_tensor_size(const qoi_desc* desc, const qoimi_resize* it
     const ResampleKind* kind = tensor_filter(filter).kind;
     size_t bytes = 0;
     if (!kind || !desc_ok(desc) || !item || (channels != 3 && channels != 4) || tensor_format_wrong(format) || kind->wrong(desc, item) ||
-        !tensor_bytes(resize_bytes, item, (unsigned)channels, tensor_elem(format->dtype), &bytes)) return 0;
+        !tensor_bytes(resize_bytes, item, (unsigned)channels, format, &bytes)) return 0;
     return bytes;
 }
 
 extern "C" size_t qoimi_warp_tensor_size(const qoi_desc* desc, const qoimi_warp* item, int channels, const qoimi_tensor_format* format) {
     size_t bytes = 0;
     if (!desc_ok(desc) || !item || (channels != 3 && channels != 4) || tensor_format_wrong(format) || warp_item_wrong(desc, item) ||
-        !tensor_bytes(warp_bytes, item, (unsigned)channels, tensor_elem(format->dtype), &bytes)) return 0;
+        !tensor_bytes(warp_bytes, item, (unsigned)channels, format, &bytes)) return 0;
     return bytes;
 }
 
@@ -116,12 +142,11 @@ extern "C" int qoimi_decode_tensors(qoimi_ctx* c, const void* d_streams, const s
                                     int n_images, int channels, const qoimi_resize* items, int n_items, int filter, int mode,
                                     const qoimi_tensor_format* format, void* d_out, const size_t* out_offsets, size_t staging_bytes, void* stream) {
     const TensorFilter tf = tensor_filter(filter);
-    if (!tf.kind) return fail(QOIMI_E_ARG, "filter must be QOIMI_FILTER_LANCZOS, QOIMI_FILTER_AREA, QOIMI_FILTER_BILINEAR or QOIMI_FILTER_BICUBIC");
-    const size_t elem = (format && format->dtype <= (unsigned)QOIMI_TENSOR_F32) ? tensor_elem(format->dtype) : 1u;   // (used behind the format's check only)
+    if (!tf.kind) return fail(QOIMI_E_ARG, "filter must be QOIMI_FILTER_LANCZOS, QOIMI_FILTER_AREA, QOIMI_FILTER_BILINEAR or QOIMI_FILTER_BICUBIC, or QOIMI_FILTER_NEAREST");
     return gather_resampled(*tf.kind, c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
         [&]() { return check_tensor_format(format); },
-        [&](const qoimi_resize* r, unsigned och, size_t* bytes) { return tensor_bytes(resize_bytes, r, och, elem, bytes); },
-        [&](const CheckedItems&) { return check_tensor_alignment(d_out, out_offsets, (size_t)n_items, elem); },
+        [&](const qoimi_resize* r, unsigned och, size_t* bytes) { return tensor_bytes(resize_bytes, r, och, format, bytes); },
+        [&](const CheckedItems&) { return check_tensor_alignment(d_out, out_offsets, (size_t)n_items, format_elem(format)); },
         &qoimi_ctx::tensor_stats, tf.kernel,
         [&](const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
             tf.launch((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, kernel_format(format), grid, st);
@@ -131,11 +156,10 @@ extern "C" int qoimi_decode_tensors(qoimi_ctx* c, const void* d_streams, const s
 extern "C" int qoimi_decode_warped_tensors(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                            int n_images, int channels, const qoimi_warp* items, int n_items, int mode,
                                            const qoimi_tensor_format* format, void* d_out, const size_t* out_offsets, size_t staging_bytes, void* stream) {
-    const size_t elem = (format && format->dtype <= (unsigned)QOIMI_TENSOR_F32) ? tensor_elem(format->dtype) : 1u;   // (used behind the format's check only)
     return gather_warped(c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
         [&]() { return check_tensor_format(format); },
-        [&](const qoimi_warp* r, unsigned och, size_t* bytes) { return tensor_bytes(warp_bytes, r, och, elem, bytes); },
-        [&](const CheckedItems&) { return check_tensor_alignment(d_out, out_offsets, (size_t)n_items, elem); },
+        [&](const qoimi_warp* r, unsigned och, size_t* bytes) { return tensor_bytes(warp_bytes, r, och, format, bytes); },
+        [&](const CheckedItems&) { return check_tensor_alignment(d_out, out_offsets, (size_t)n_items, format_elem(format)); },
         &qoimi_ctx::tensor_stats, "tensor_warp",
         [&](const WarpEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
             launch_tensor_warp((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, kernel_format(format), grid, st);

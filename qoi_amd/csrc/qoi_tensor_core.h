@@ -1,6 +1,6 @@
 // qoi_tensor_core.h — the store end of qoimi_decode_tensors and qoimi_decode_warped_tensors: one rounded pixel of a filter tile or of the warp
 // tile, still in a register, to the elements of a tensor - u8, binary16, bfloat16 or binary32, interleaved or planar, scaled and shifted per
-// channel.
+// channel; or, for label maps, 32- or 64-bit integers, and the first channel alone as one plane.
 //
 // The definition (normative; qoi_amd/tensors.py: convert states it in Python).  px = r | g << 8 | b << 16 | a << 24 is the pixel the u8 call
 // would store at pixel (xo, yo) of an ow x oh output with och = 3 or 4 channels; v = channel c of it, an integer 0..255.
@@ -8,10 +8,13 @@
 //   F32             t = float(v); m = t * scale[c], rounded to nearest even in binary32; s = m + bias[c], rounded to nearest even in binary32 -
 //                   TWO roundings, never a fused multiply-add; the element is s
 //   F16, BF16       s converted to binary16 / bfloat16, round to nearest even
+//   I32, I64        the element is v as a little-endian two's-complement integer of 4 / 8 bytes (the host accepts only scale 1 and bias +0)
 // Subnormals are kept in every format, a result too large becomes infinity; scale and bias are finite, so no NaN arises.
 // The element is stored at element index (yo * ow + xo) * och + c (HWC) or (c * oh + yo) * ow + xo (CHW) from the absolute address q, which is a
 // multiple of the element size: every store is one whole, naturally aligned element - the item's own bytes only, never a word that would have
 // to be read first.  Where u8 HWC holds 4 bytes per pixel and the address is aligned the pixel is one dword, as resize_store writes it.
+// With HW only channel 0 (r) of a pixel is stored, at element index yo * ow + xo: one plane of ow * oh elements; och still says how the image
+// was decoded.  An 8-byte element is two aligned dword stores, the value at a and 0 at a + 4 (Mem has no 8-byte store).
 //
 // Plain sequential code over a memory functor `Mem` (store1 / store2 / store4(address, value)), compiled for the device by hipcc
 // (qoi_tensor.hip: the conversions are the hardware's) and - by tests/host/tensor_host.cpp only - for the host, where the narrowing is integer
@@ -23,14 +26,20 @@
 
 namespace qoimi {
 
-constexpr uint32_t kTensorU8 = 0, kTensorF16 = 1, kTensorBF16 = 2, kTensorF32 = 3;
-constexpr uint32_t kTensorHWC = 0, kTensorCHW = 1;
+constexpr uint32_t kTensorU8 = 0, kTensorF16 = 1, kTensorBF16 = 2, kTensorF32 = 3, kTensorI32 = 5, kTensorI64 = 6;   // (4 is not a dtype)
+constexpr uint32_t kTensorHWC = 0, kTensorCHW = 1, kTensorHW = 3;                                                    // (2 is not a layout)
 
 // What the kernels take by value: ten dwords (qoimi_tensor_format without its reserved words)
 struct TensorFormat { uint32_t dtype, layout; float scale[4], bias[4]; };
 
 // Bytes of an element
-QOIMI_RESIZE_HD uint32_t tensor_elem(uint32_t dtype) { return dtype == kTensorU8 ? 1u : (dtype == kTensorF32 ? 4u : 2u); }
+QOIMI_RESIZE_HD uint32_t tensor_elem(uint32_t dtype) {
+    if (dtype == kTensorI64) return 8u;
+    return dtype == kTensorU8 ? 1u : ((dtype == kTensorF32 || dtype == kTensorI32) ? 4u : 2u);
+}
+
+// The integer dtypes: the element is the channel value itself
+QOIMI_RESIZE_HD bool tensor_integer(uint32_t dtype) { return dtype == kTensorU8 || dtype == kTensorI32 || dtype == kTensorI64; }
 
 QOIMI_RESIZE_HD uint32_t tensor_bits(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
 
@@ -71,7 +80,7 @@ QOIMI_RESIZE_HD uint32_t tensor_f16(uint32_t x) {
 
 // The bits to store for the channel value v = 0..255
 QOIMI_RESIZE_HD uint32_t tensor_value(uint32_t v, float scale, float bias, uint32_t dtype) {
-    if (dtype == kTensorU8) return v;
+    if (tensor_integer(dtype)) return v;                           // (I64: the low dword; the high one is 0)
     const float s = tensor_affine(v, scale, bias);
     if (dtype == kTensorF32) return tensor_bits(s);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -95,12 +104,14 @@ QOIMI_RESIZE_HD void tensor_store(const Mem& mem, const TensorFormat& fmt, uint6
     }
     const uint32_t elem = tensor_elem(fmt.dtype);
     const uint64_t plane = (uint64_t)ow * oh;
+    const uint32_t n = fmt.layout == kTensorHW ? 1u : och;         // elements of a pixel
     QOIMI_RESIZE_UNROLL
     for (uint32_t c = 0; c < 4u; ++c) {                            // (unrolled: scale[c] and bias[c] are named registers)
-        if (c >= och) break;
+        if (c >= n) break;
         const uint32_t bits = tensor_value((px >> (8u * c)) & 255u, fmt.scale[c], fmt.bias[c], fmt.dtype);
-        const uint64_t a = q + (fmt.layout == kTensorCHW ? c * plane + at : at * och + c) * elem;
-        if (elem == 4u) mem.store4(a, bits);
+        const uint64_t a = q + (fmt.layout == kTensorCHW ? c * plane + at : at * n + c) * elem;
+        if (elem == 8u) { mem.store4(a, bits); mem.store4(a + 4u, 0u); }
+        else if (elem == 4u) mem.store4(a, bits);
         else if (elem == 2u) mem.store2(a, bits);
         else mem.store1(a, bits);
     }

@@ -2,7 +2,7 @@
 header repeats it; qoi_amd/csrc/qoi_tensor_core.h holds the arithmetic of the kernels).
 
 Let P be the uint8[oh, ow, och] result of the underlying call - ``resize.resize`` for ``FILTER_AREA``, ``bilinear.bilinear`` for
-``FILTER_BILINEAR``, ``bicubic.bicubic`` for ``FILTER_BICUBIC`` and ``lanczos.lanczos`` for ``FILTER_LANCZOS`` (which have no u8 call of their own), ``warp.warp`` for the warp call - with the same item, channels and mode, byte for byte, flips included.  A format is
+``FILTER_BILINEAR``, ``bicubic.bicubic`` for ``FILTER_BICUBIC``, ``lanczos.lanczos`` for ``FILTER_LANCZOS`` and ``nearest.nearest`` for ``FILTER_NEAREST`` (which have no u8 call of their own), ``warp.warp`` for the warp call - with the same item, channels and mode, byte for byte, flips included.  A format is
 (dtype, layout, scale, bias): scale and bias are four binary32 numbers, per channel r, g, b, a.  Element (Y, X, c) has the value v = P[Y][X][c]:
 
     U8      the element is v; scale must be all 1 and bias all +0
@@ -10,9 +10,13 @@ Let P be the uint8[oh, ow, och] result of the underlying call - ``resize.resize`
             TWO roundings, never a fused multiply-add; the element is s
     F16     s converted to binary16, round to nearest even
     BF16    s converted to bfloat16, round to nearest even: on the bits of s, (bits + 0x7FFF + (bits >> 16 & 1)) >> 16
+    I32     the element is v as a little-endian two's-complement integer of 4 bytes; scale must be all 1 and bias all +0, as for U8
+    I64     ... of 8 bytes: the class indices a loss function takes
 
 Subnormals are kept in every format; a result too large becomes infinity; scale and bias are finite, so no NaN arises.  The layout is
-``HWC`` - [oh, ow, och], P's own - or ``CHW`` - [och, oh, ow] -, tightly packed.  U8 with HWC is P itself; everything else is a pure function
+``HWC`` - [oh, ow, och], P's own -, ``CHW`` - [och, oh, ow] - or ``HW`` - [oh, ow]: only the FIRST channel (r) of each pixel, as one plane, with
+scale[0] and bias[0] (the others are ignored but must still be finite); och still says how the image is decoded -, tightly packed.  Every
+layout goes with every dtype.  U8 with HWC is P itself; everything else is a pure function
 of P, so the exact-integer definitions of the filters stand as they are.
 
 NumPy has no bfloat16: ``convert`` returns BF16 as uint16 holding the bits (``numpy_dtype`` says what an output's array is).
@@ -25,16 +29,23 @@ from typing import Sequence, Tuple
 
 import numpy as np
 
-from . import bicubic, bilinear, crops, lanczos, resize, warp
+from . import bicubic, bilinear, crops, lanczos, nearest, resize, warp
 
 U8, F16, BF16, F32 = 0, 1, 2, 3
+I32, I64 = 5, 6                 # (4 is not a dtype)
 HWC, CHW = 0, 1
+HW = 3                          # (2 is not a layout)
 FILTER_AREA, FILTER_BILINEAR = 0, 1
 FILTER_BICUBIC = 3              # (2 is not a filter)
 FILTER_LANCZOS = 6              # (nor are 4, 5 and 7)
-_FILTERS = {FILTER_AREA: resize.resize, FILTER_BILINEAR: bilinear.bilinear, FILTER_BICUBIC: bicubic.bicubic, FILTER_LANCZOS: lanczos.lanczos}
+FILTER_NEAREST = 9              # (nor is 8)
+_FILTERS = {FILTER_AREA: resize.resize, FILTER_BILINEAR: bilinear.bilinear, FILTER_BICUBIC: bicubic.bicubic, FILTER_LANCZOS: lanczos.lanczos,
+            FILTER_NEAREST: nearest.nearest}
 ELEM = {U8: 1, F16: 2, BF16: 2, F32: 4}
-DTYPE_NAMES = {"u8": U8, "f16": F16, "bf16": BF16, "f32": F32}
+INT_ELEM = {I32: 4, I64: 8}     # the integer class-index dtypes, beside ELEM
+DTYPE_NAMES = {"u8": U8, "f16": F16, "bf16": BF16, "f32": F32, "i32": I32, "i64": I64}
+LAYOUT_NAMES = {"hwc": HWC, "chw": CHW, "hw": HW}
+_INT_NAMES = {U8: "QOIMI_TENSOR_U8", I32: "QOIMI_TENSOR_I32", I64: "QOIMI_TENSOR_I64"}
 PLAIN = resize.PLAIN
 ALPHA_WEIGHTED = resize.ALPHA_WEIGHTED
 
@@ -60,24 +71,29 @@ def normalise(mean: Sequence[float], std: Sequence[float]) -> Tuple[np.ndarray, 
     return (1.0 / (255.0 * s)).astype(np.float32), (-m / s).astype(np.float32)
 
 
+def elem(dtype: int) -> int:
+    """Bytes of an element: ``ELEM`` or ``INT_ELEM``."""
+    return ELEM[dtype] if dtype in ELEM else INT_ELEM[dtype]
+
+
 def wrong(f) -> str:
     """"" if the calls accept the format, else what is wrong with it - in the order the calls look."""
     dtype, layout, scale, bias = f
-    if dtype not in ELEM:
+    if dtype not in ELEM and dtype not in INT_ELEM:
         return "unknown dtype"
-    if layout not in (HWC, CHW):
+    if layout not in (HWC, CHW, HW):
         return "unknown layout"
     scale, bias = np.asarray(scale, np.float32), np.asarray(bias, np.float32)
     if scale.shape != (4,) or bias.shape != (4,) or not (np.isfinite(scale).all() and np.isfinite(bias).all()):
         return "scale or bias is not finite"
-    if dtype == U8 and not ((scale == 1.0).all() and (bias.view(np.uint32) == 0).all()):
-        return "QOIMI_TENSOR_U8 takes scale 1 and bias +0 only"
+    if dtype in _INT_NAMES and not ((scale == 1.0).all() and (bias.view(np.uint32) == 0).all()):
+        return _INT_NAMES[dtype] + " takes scale 1 and bias +0 only"
     return ""
 
 
 def numpy_dtype(dtype: int):
     """The dtype of the array ``convert`` returns: BF16 as the uint16 of its bits."""
-    return {U8: np.uint8, F16: np.float16, BF16: np.uint16, F32: np.float32}[dtype]
+    return {U8: np.uint8, F16: np.float16, BF16: np.uint16, F32: np.float32, I32: np.dtype("<i4"), I64: np.dtype("<i8")}[dtype]
 
 
 def bf16_bits(s: np.ndarray) -> np.ndarray:
@@ -87,7 +103,8 @@ def bf16_bits(s: np.ndarray) -> np.ndarray:
 
 
 def convert(P: np.ndarray, f) -> np.ndarray:
-    """P uint8[oh, ow, och] (och 3 or 4), f a format -> [oh, ow, och] (HWC) or [och, oh, ow] (CHW) of ``numpy_dtype(dtype)``, contiguous."""
+    """P uint8[oh, ow, och] (och 3 or 4), f a format -> [oh, ow, och] (HWC), [och, oh, ow] (CHW) or [oh, ow] (HW: channel 0) of
+    ``numpy_dtype(dtype)``, contiguous."""
     P = np.asarray(P)
     if P.ndim != 3 or P.shape[2] not in (3, 4) or P.dtype != np.uint8:
         raise ValueError("convert: P is uint8[oh, ow, 3 or 4]")
@@ -98,22 +115,31 @@ def convert(P: np.ndarray, f) -> np.ndarray:
     och = P.shape[2]
     if dtype == U8:
         out = P
+    elif dtype in INT_ELEM:
+        out = P.astype(numpy_dtype(dtype))
     else:
         with np.errstate(over="ignore", under="ignore"):
             m = P.astype(np.float32) * np.asarray(scale, np.float32)[:och]      # (one float32 operation per line: two roundings)
             s = m + np.asarray(bias, np.float32)[:och]
             out = s if dtype == F32 else (s.astype(np.float16) if dtype == F16 else bf16_bits(s))
+    if layout == HW:
+        return np.ascontiguousarray(out[:, :, 0])
     return np.ascontiguousarray(out.transpose(2, 0, 1) if layout == CHW else out)
 
 
 def size(u8_bytes: int, dtype: int) -> int:
     """Bytes of an output whose u8 form takes u8_bytes (``resize.size``, ``bilinear.size``, ``bicubic.size``, ``lanczos.size``, ``warp.size``; 0 stays 0)."""
-    return u8_bytes * ELEM[dtype]
+    return u8_bytes * elem(dtype)
+
+
+def size_hw(u8_bytes: int, och: int, dtype: int) -> int:
+    """... under ``HW``: one element per pixel, u8_bytes / och of them."""
+    return u8_bytes // och * elem(dtype)
 
 
 def tensors(D: np.ndarray, rect, out_size, flags: int = 0, filter: int = FILTER_AREA, mode: int = PLAIN, f=None) -> np.ndarray:
-    """One item of qoimi_decode_tensors: ``convert`` of ``resize.resize``, ``bilinear.bilinear``, ``bicubic.bicubic`` or ``lanczos.lanczos`` of
-    the same arguments."""
+    """One item of qoimi_decode_tensors: ``convert`` of ``resize.resize``, ``bilinear.bilinear``, ``bicubic.bicubic``, ``lanczos.lanczos`` or
+    ``nearest.nearest`` of the same arguments."""
     if filter not in _FILTERS:
         raise ValueError("tensors: unknown filter")
     P = _FILTERS[filter](D, rect, out_size, flags, mode)

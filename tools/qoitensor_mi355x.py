@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """qoitensor for the MI355X path: a set of .qoi files as ONE .npy tensor, N x C x H x W or N x H x W x C, normalised.
 
-    python tools/qoitensor_mi355x.py FILE_OR_DIR... --size WxH -o OUT.npy [--filter area|bilinear|bicubic|lanczos] [--dtype u8|f16|bf16|f32] [--layout chw|hwc]
+    python tools/qoitensor_mi355x.py FILE_OR_DIR... --size WxH -o OUT.npy [--filter area|bilinear|bicubic|lanczos|nearest] [--dtype u8|f16|bf16|f32|i32|i64]
+                                     [--layout chw|hwc|hw]
                                      [--mean M[,M,M[,M]]] [--std S[,S,S[,S]]] [--fit whole|crop] [--channels 3|4] [--staging-mb M]
 
 Loads the .qoi files (directories are walked), uploads them as ONE pack and makes ONE qoimi_decode_tensors call: every stream is decoded on the
@@ -9,9 +10,10 @@ GPU into a bounded staging arena, resampled there to W x H (tools/qoiresize_mi35
 of the tensor straight from the filter's registers - 8-bit interleaved pixels never exist.  Element = (p / 255 - mean) / std per channel:
 scale = 1 / (255 * std) and bias = -mean / std are computed in float64 and rounded once to float32 (scale_bias); the library then computes
 float32(p) * scale + bias with two roundings and narrows once (qoi_amd/tensors.py states it).  Without --mean / --std the elements are
-p / 255; --dtype u8 takes neither and stores p.  One value of --mean / --std serves every channel; a fourth (alpha) defaults to mean 0, std 1.
+p / 255; --dtype u8, i32 and i64 take neither and store p.  --filter nearest --dtype i64 --layout hw makes N x H x W class indices of label maps:
+one pixel of the source per element, nothing averaged, the first channel alone.  One value of --mean / --std serves every channel; a fourth (alpha) defaults to mean 0, std 1.
 --channels defaults to 3.  bf16 is stored as the uint16 of its bits (NumPy has no bfloat16).  A file that is no QOI stream or whose
-rectangle the filter cannot reduce to the target (64 times in an axis, 32 for bilinear, 16 for bicubic and lanczos) is reported and left out; exit status 1 if there was
+rectangle the filter cannot reduce to the target (64 times in an axis, 32 for bilinear, 16 for bicubic and lanczos, no limit but a side of 16384 for nearest) is reported and left out; exit status 1 if there was
 one, else 0.  Needs torch for device memory, as tools/qoicheck_mi355x.py does.
 """
 from __future__ import annotations
@@ -62,9 +64,9 @@ def main(argv, out=print) -> int:
     ap.add_argument("paths", nargs="+", metavar="FILE_OR_DIR")
     ap.add_argument("--size", required=True, metavar="WxH")
     ap.add_argument("-o", "--out", required=True, metavar="OUT.npy")
-    ap.add_argument("--filter", choices=("area", "bilinear", "bicubic", "lanczos"), default="bilinear")
-    ap.add_argument("--dtype", choices=("u8", "f16", "bf16", "f32"), default="f32")
-    ap.add_argument("--layout", choices=("chw", "hwc"), default="chw")
+    ap.add_argument("--filter", choices=("area", "bilinear", "bicubic", "lanczos", "nearest"), default="bilinear")
+    ap.add_argument("--dtype", choices=("u8", "f16", "bf16", "f32", "i32", "i64"), default="f32")
+    ap.add_argument("--layout", choices=("chw", "hwc", "hw"), default="chw")
     ap.add_argument("--mean", default=None, metavar="M[,M,M[,M]]")
     ap.add_argument("--std", default=None, metavar="S[,S,S[,S]]")
     ap.add_argument("--fit", choices=("whole", "crop"), default="whole")
@@ -82,9 +84,9 @@ def main(argv, out=print) -> int:
         out("--staging-mb must not be negative")
         return 2
     och = a.channels
-    if a.dtype == "u8":
+    if a.dtype in ("u8", "i32", "i64"):
         if a.mean is not None or a.std is not None:
-            out("--dtype u8 stores the pixel values: it takes no --mean / --std")
+            out(f"--dtype {a.dtype} stores the pixel values: it takes no --mean / --std")
             return 2
         sb = (np.ones(4, np.float32), np.zeros(4, np.float32))
     else:
@@ -96,14 +98,14 @@ def main(argv, out=print) -> int:
             return 2
     ow, oh = size
     import torch  # first: the library then binds to the HIP runtime torch already loaded
-    from qoi_amd import api, bicubic, bilinear, lanczos, resize, tensors
+    from qoi_amd import api, bicubic, bilinear, lanczos, nearest, resize, tensors
 
     files = collect(a.paths)
     if not files:
         out("no .qoi files")
         return 2
     model, filt = {"area": (resize, tensors.FILTER_AREA), "bilinear": (bilinear, tensors.FILTER_BILINEAR), "bicubic": (bicubic, tensors.FILTER_BICUBIC),
-                   "lanczos": (lanczos, tensors.FILTER_LANCZOS)}[a.filter]
+                   "lanczos": (lanczos, tensors.FILTER_LANCZOS), "nearest": (nearest, tensors.FILTER_NEAREST)}[a.filter]
     blobs = [open(f, "rb").read() for f in files]
     heads = [parse_header(b) for b in blobs]
     good = []
@@ -118,8 +120,8 @@ def main(argv, out=print) -> int:
         good.append(i)
     if not good:
         return 1
-    f = (tensors.DTYPE_NAMES[a.dtype], tensors.CHW if a.layout == "chw" else tensors.HWC, sb[0], sb[1])
-    one = ow * oh * och * tensors.ELEM[f[0]]
+    f = (tensors.DTYPE_NAMES[a.dtype], tensors.LAYOUT_NAMES[a.layout], sb[0], sb[1])
+    one = ow * oh * (1 if a.layout == "hw" else och) * tensors.elem(f[0])
     offsets, sizes, descs, items = [], [], [], []
     pos = 0
     for k, i in enumerate(good):
@@ -136,7 +138,7 @@ def main(argv, out=print) -> int:
         subs = ctx.tensor_stats()[0]
     finally:
         ctx.close()
-    shape = (len(good), och, oh, ow) if a.layout == "chw" else (len(good), oh, ow, och)
+    shape = {"chw": (len(good), och, oh, ow), "hwc": (len(good), oh, ow, och), "hw": (len(good), oh, ow)}[a.layout]
     res = d_out.cpu().numpy().view(tensors.numpy_dtype(f[0])).reshape(shape)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     np.save(a.out, res)
