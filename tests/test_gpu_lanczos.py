@@ -3,7 +3,8 @@ definition - the oracle decodes the stream at the call's output channel count, q
 makes the tensor (each u8 model is computed once and shared).  The pack is small: 67 x 45 with soft alpha and runs of alpha 0, 67 x 45 with 3
 channels, 1 x 1, 130 x 34, a 70 x 66 checkerboard of 0 / 255 whose alpha alternates in blocks of two - for it the model is first shown to
 clamp at 0, to clamp at 255 and to meet A <= 0, the paths a wrong sign or a missing clamp would break - and a column 4 x 4160, whose reduction
-by 16 to one column fills the row table of a tile: 256 rows of 96 entries.  The outputs of a call lie at element-aligned but otherwise odd
+by 16 to one column fills the row table of a tile: 256 rows of 96 entries.  The images of 16384 x 1 and 1 x 16384 for the far end of the size
+limits are a pack of their own (tests/table_tiles.py).  The outputs of a call lie at element-aligned but otherwise odd
 addresses with guard bytes between them (test_gpu_tensors.py: layout_of, run); every guard byte is checked after every call.  The items use
 1, 2, 4, 8 and 16 lanes per pixel, 6 to 96 taps, tiles that hold whole rows and tiles that wrap one."""
 import ctypes
@@ -11,6 +12,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import table_tiles as tt
 from qoi_amd import lanczos, tensors
 from qoi_amd.lanczos import ALPHA_WEIGHTED, PLAIN
 from qoi_amd.tensors import BF16, CHW, F16, F32, FILTER_LANCZOS, HWC, U8
@@ -67,6 +69,11 @@ def pack(api, ctx, oracle):
     return Pack(ctx, oracle, batch_of(api, oracle, SHAPES, pixels()))
 
 
+@pytest.fixture(scope="module")
+def limits(api, ctx, oracle):
+    return Pack(ctx, oracle, batch_of(api, oracle, tt.LIMIT_SHAPES, tt.limit_pixels()))
+
+
 # (image, x, y, width, height, out_width, out_height, flags); the flips take turns
 ENLARGE = (SOFT, 10, 7, 7, 5, 19, 11, 1)             # 6 taps, one lane
 IDENTITY = (SOFT, 3, 2, 40, 30, 40, 30, 2)
@@ -91,8 +98,8 @@ _MODELS = {}
 
 
 def model(p, it, och, mode):
-    """the u8 result P of one item: computed once, never changed"""
-    key = (tuple(it), och, mode)
+    """the u8 result P of one item of pack p: computed once, never changed"""
+    key = (p, tuple(it), och, mode)
     if key not in _MODELS:
         i, x, y, cw, rh, ow, oh, flags = it
         P = lanczos.lanczos(p.decoded(i, och), (x, y, cw, rh), (ow, oh), flags, mode)
@@ -172,6 +179,16 @@ def test_the_size_limit_is_accepted(ctx, pack):
     items = [(ONE, 0, 0, 1, 1, 16384, 1, 1)]
     got = run(ctx, pack, FILTER_LANCZOS, 4, items, PLAIN, (F16, CHW, *IMAGENET))
     assert_items(pack, got, items, 4, PLAIN, (F16, CHW, *IMAGENET), "16384")
+
+
+def test_the_other_end_of_the_limits(ctx, limits):
+    """16384 x 1 -> 1024 x 1 flipped in x (exactly 16 : 1, 96 taps, sixteen lanes), 1 x 16384 -> 1 x 1024 flipped in y (four tiles of 256 rows
+    of 96 entries, row offsets up to the last row of the stage) and 1 x 3 -> 1 x 16384 (64 tiles of 256 rows)"""
+    for mode, items in ((PLAIN, tt.LIMIT_ITEMS), (ALPHA_WEIGHTED, tt.LIMIT_ITEMS[:1])):
+        for f in ((F16, CHW, *IMAGENET), tensors.fmt(U8, HWC)):
+            got = run(ctx, limits, FILTER_LANCZOS, 4, items, mode, f)
+            assert ctx.tensor_stats()[:2] == (1, 1)
+            assert_items(limits, got, items, 4, mode, f, ("limits", mode, f[0]))
 
 
 def test_sub_batches(api, pack):
