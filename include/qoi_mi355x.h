@@ -722,7 +722,7 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * those of the underlying call: qoimi_decode_resized for QOIMI_FILTER_AREA, qoimi_decode_bilinear for QOIMI_FILTER_BILINEAR, qoimi_decode_warped
  * for qoimi_decode_warped_tensors.  QOIMI_FILTER_BICUBIC has no call of its own - its "underlying call" is the definition below, everything
  * but the filter and its limits as for qoimi_decode_bilinear; QOIMI_TENSOR_U8 with QOIMI_TENSOR_HWC gives its plain interleaved bytes.
- * QOIMI_FILTER_LANCZOS and QOIMI_FILTER_NEAREST likewise.
+ * QOIMI_FILTER_LANCZOS and QOIMI_FILTER_NEAREST likewise, and QOIMI_FILTER_MODE.
  * The result (normative; qoi_amd/tensors.py: convert states it in Python): let P be the oh x ow x och u8 result of the underlying call with the
  * same items, channels and mode, byte for byte, flips included.  Element (Y, X, c) of output j has the value v = P[Y][X][c], an integer 0..255.
  *   QOIMI_TENSOR_U8    the element is v; scale must be all 1.0f and bias all +0.0f
@@ -795,8 +795,27 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * Its limits, each a QOIMI_E_ARG item by item, in this order: the rectangle rules of the other filters (a zero size, an unknown flag bit, a
  * rectangle that leaves its image); then max(width, out_width) <= 16384 and max(height, out_height) <= 16384 - the size limit of
  * QOIMI_FILTER_BICUBIC ((2X + 1) * cw < 2^29: no 64-bit division).  There is NO ratio limit: every output pixel is one load.
+ * QOIMI_FILTER_MODE (normative; qoi_amd/mode.py: mode states it in Python) is a majority vote - for REDUCING label maps, where
+ * QOIMI_FILTER_NEAREST looks at one pixel of each cell and thin classes come and go with the sampling phase.  D, R, cw, rh, ow, oh and och
+ * as for qoimi_decode_resized; the image is decoded to 4 channels, a 3-channel stream has alpha 255; all arithmetic is integer and floors.
+ * On an axis of n_src source and n_out output samples the cell of output sample Z is [first(Z), first(Z + 1)) with
+ *   first(Z) = (2 * Z * n_src + n_out - 1) / (2 * n_out)
+ * - the source samples whose centre lies in the output sample's extent, on the line QOIMI_FILTER_NEAREST uses.  An empty cell (only when
+ * enlarging on that axis) is replaced by the single sample ((2Z + 1) * n_src) / (2 * n_out), the nearest one.  The non-empty cells of an axis
+ * partition [0, n_src) in order; the nearest sample lies in every non-empty cell.  Output pixel (X, Y) looks at the pixels of R in columns
+ * cell(X) x rows cell(Y), at most 16 x 16 of them.  A pixel votes as a whole, all four bytes as decoded: colour-coded masks and 24-bit
+ * instance ids survive, no colour is invented.  The count of a value is the number of pixels equal to it; the winners are the values with the
+ * largest count.  One winner is the output.  Of several winners the output is the pixel QOIMI_FILTER_NEAREST would take - R[r][k] with
+ * that filter's k and r - if it is a winner, else the winner with the lowest key = r << 24 | g << 16 | b << 8 | a.  (At 2 : 1 every straight
+ * class boundary makes 2-2 ties; the lowest key alone would grow class 0 along each of them.)  Both modes give the same bytes; och 3 drops
+ * alpha after the vote (two colours of a 4-channel stream that differ in alpha alone vote apart); QOIMI_RESIZE_FLIP_X / _Y reverse the columns / rows of that result.  With the output the size of the rectangle or larger on both axes
+ * it is QOIMI_FILTER_NEAREST byte for byte; an image whose pixels are all distinct gives QOIMI_FILTER_NEAREST at any size; a constant
+ * rectangle gives the constant; with cw = f * ow and rh = g * oh the cells are the f x g blocks.
+ * Its limits, each a QOIMI_E_ARG item by item, in this order: the rectangle rules of the other filters; then width <= 16 * out_width and
+ * height <= 16 * out_height (a cell is at most 16 x 16 pixels); then max(width, out_width) <= 16384 and max(height, out_height) <= 16384
+ * (2 * Z * n_src + n_out < 2^30: no 64-bit division).
  *   filter         QOIMI_FILTER_LANCZOS, QOIMI_FILTER_AREA, QOIMI_FILTER_BILINEAR or QOIMI_FILTER_BICUBIC, or QOIMI_FILTER_NEAREST
- *                  (qoimi_decode_tensors only)
+ *                  or QOIMI_FILTER_MODE (qoimi_decode_tensors only)
  *   format         HOST; one for the whole call
  *   d_out, out_offsets   every d_out + out_offsets[j] a multiple of the element size (1 / 2 / 2 / 4, 4 / 8 for QOIMI_TENSOR_I32 / _I64)
  *   everything else      as for the underlying call
@@ -807,15 +826,16 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * in bytes; an output address that is not a multiple of the element size; a sub-batch of the plan with 2^31 - 1 tiles or more.  All are
  * reported before anything is launched, the caller's buffers are untouched; qoimi_last_error names the cause.  The sub-batches count as decode
  * calls of the context.  One call at a time per context, as everywhere.
- * Not here: indexed forms, a majority (mode) filter for REDUCING label maps (QOIMI_FILTER_NEAREST takes one pixel of each cell, whatever its
- * neighbours hold), 16-bit or signed label sources (a label is a byte of the image), a remapping table from byte to class index, a single
- * 8-byte store per QOIMI_TENSOR_I64 element (it is two dword stores), a u8 entry point or a stats function of the bicubic, the Lanczos or the nearest filter's own, other cubic kernels (a = -3/4), other Lanczos windows, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
+ * Not here: indexed forms, a majority (mode) filter per channel, with weights or over cells above 16 x 16 (QOIMI_FILTER_MODE votes on whole
+ * pixels of cells up to that), the mode filter in the warp, 16-bit or signed label sources (a label is a byte of the image), a remapping table from byte to class index, a single
+ * 8-byte store per QOIMI_TENSOR_I64 element (it is two dword stores), a u8 entry point or a stats function of the bicubic, the Lanczos, the nearest or the mode filter's own, other cubic kernels (a = -3/4), other Lanczos windows, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
  * size of its rectangle, or divides it, is those), tensors as the source of an encode (qoimi_encode_tiles takes bytes). */
 enum { QOIMI_TENSOR_U8 = 0, QOIMI_TENSOR_F16 = 1, QOIMI_TENSOR_BF16 = 2, QOIMI_TENSOR_F32 = 3 };   /* element sizes 1 / 2 / 2 / 4 */
 enum { QOIMI_TENSOR_I32 = 5, QOIMI_TENSOR_I64 = 6 };   /* element sizes 4 / 8; 4 is not a dtype */
 enum { QOIMI_TENSOR_HWC = 0, QOIMI_TENSOR_CHW = 1, QOIMI_TENSOR_HW = 3 };   /* 2 is not a layout */
 enum { QOIMI_FILTER_AREA = 0, QOIMI_FILTER_BILINEAR = 1, QOIMI_FILTER_BICUBIC = 3, QOIMI_FILTER_LANCZOS = 6 };   /* 2 is not a filter, nor are 4, 5 and 7 */
 enum { QOIMI_FILTER_NEAREST = 9 };   /* 8 is not a filter */
+enum { QOIMI_FILTER_MODE = 11 };   /* 10 is not a filter */
 typedef struct {                 /* 48 bytes, offsets 0/4/8/24/40 */
     unsigned int dtype;          /* QOIMI_TENSOR_* */
     unsigned int layout;         /* QOIMI_TENSOR_HWC / _CHW / _HW */
@@ -834,7 +854,7 @@ int qoimi_decode_warped_tensors(qoimi_ctx *ctx, const void *d_streams, const siz
 
 /* out_width * out_height * channels * element size (QOIMI_TENSOR_HW: out_width * out_height * element size) - the bytes of the item's output -
  * or 0 if filter is unknown, the format is one the calls reject, qoimi_resize_size / qoimi_bilinear_size (by filter) or qoimi_warp_size would
- * return 0, the item is beyond the limits of QOIMI_FILTER_BICUBIC, QOIMI_FILTER_LANCZOS or QOIMI_FILTER_NEAREST with that filter, or the
+ * return 0, the item is beyond the limits of QOIMI_FILTER_BICUBIC, QOIMI_FILTER_LANCZOS, QOIMI_FILTER_NEAREST or QOIMI_FILTER_MODE with that filter, or the
  * product does not fit a size_t.  Pure
  * host arithmetic: no context, no GPU. */
 size_t qoimi_tensor_size(const qoi_desc *desc, const qoimi_resize *item, int filter, int channels, const qoimi_tensor_format *format);

@@ -202,7 +202,7 @@ def tensor_format(f) -> "QoimiTensorFormat":
 
 def tensor_size(width: int, height: int, channels_in: int, item, filter: int, channels: int, f) -> int:
     """``qoimi_tensor_size`` for an image of width x height x channels_in: the bytes of the output of `item` (as for ``resize_size``) under
-    `filter` (``tensors.FILTER_AREA`` / ``FILTER_BILINEAR`` / ``FILTER_BICUBIC`` / ``FILTER_LANCZOS`` / ``FILTER_NEAREST``) with `channels` (3 or 4) elements per pixel
+    `filter` (``tensors.FILTER_AREA`` / ``FILTER_BILINEAR`` / ``FILTER_BICUBIC`` / ``FILTER_LANCZOS`` / ``FILTER_NEAREST`` / ``FILTER_MODE``) with `channels` (3 or 4) elements per pixel
     (``tensors.HW``: one) in the format f; 0 where the C
     function returns 0."""
     args = _size_args(QoimiResize, width, height, channels_in, item)
@@ -680,7 +680,8 @@ class Context:
         """``decode_resized`` (filter ``tensors.FILTER_AREA``), ``decode_bilinear`` (``tensors.FILTER_BILINEAR``) or the antialiased bicubic
         filter ``qoi_amd/bicubic.py`` states (``tensors.FILTER_BICUBIC``; it has no u8 call: U8 with HWC gives its bytes) or the Lanczos filter of
         ``qoi_amd/lanczos.py`` (``tensors.FILTER_LANCZOS``, likewise) or the nearest filter of ``qoi_amd/nearest.py`` for label maps
-        (``tensors.FILTER_NEAREST``, likewise) with the outputs written
+        (``tensors.FILTER_NEAREST``, likewise) or the majority vote of ``qoi_amd/mode.py`` for reducing them (``tensors.FILTER_MODE`` = 11,
+        likewise) with the outputs written
         as tensors (``qoimi_decode_tensors``, synchronous, through bounded staging): f is a ``QoimiTensorFormat`` or the tuple of
         ``tensors.fmt`` - u8, f16, bf16 or f32 elements, HWC or CHW, each channel scaled and shifted, or i32 / i64 class indices, and HW: the
         first channel as one plane; every d_out + out_offsets[j] is a

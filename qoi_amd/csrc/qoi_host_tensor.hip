@@ -1,10 +1,11 @@
 // qoi_host_tensor.hip — the tensor calls of the C-ABI shim: qoimi_decode_tensors (the area filter, the antialiased bilinear filter or the
-// antialiased bicubic and Lanczos filters and the nearest filter, which only this call has) and qoimi_decode_warped_tensors, with qoimi_tensor_size and qoimi_warp_tensor_size.  They are gather_resampled and gather_warped of qoi_staged.h -
+// antialiased bicubic and Lanczos filters, the nearest filter and the mode filter, which only this call has) and qoimi_decode_warped_tensors, with qoimi_tensor_size and qoimi_warp_tensor_size.  They are gather_resampled and gather_warped of qoi_staged.h -
 // the checks of the items, the plan, the table entries and run_staged of qoimi_decode_resized / _bilinear / _warped - with the checks of the
 // format in front, output sizes in bytes of elements, the alignment of the outputs behind, and the tensor kernels of qoi_tensor.hip as the
 // launch.
 #include "qoi_staged.h"
 #include "qoi_lanczos_core.h"
+#include "qoi_mode_core.h"
 #include "qoi_nearest_core.h"
 #include "qoi_tensor_core.h"
 
@@ -79,8 +80,8 @@ static int check_tensor_alignment(const void* d_out, const size_t* out_offsets, 
     return QOIMI_OK;
 }
 
-static_assert(QOIMI_FILTER_AREA == 0 && QOIMI_FILTER_BILINEAR == 1 && QOIMI_FILTER_BICUBIC == 3 && QOIMI_FILTER_LANCZOS == 6 && QOIMI_FILTER_NEAREST == 9,
-              "2, 4, 5, 7 and 8 are not filters");
+static_assert(QOIMI_FILTER_AREA == 0 && QOIMI_FILTER_BILINEAR == 1 && QOIMI_FILTER_BICUBIC == 3 && QOIMI_FILTER_LANCZOS == 6 && QOIMI_FILTER_NEAREST == 9 &&
+              QOIMI_FILTER_MODE == 11, "2, 4, 5, 7 and 8 are not filters, nor is 10");
 static_assert(kNearestMaxSize == kCubicMaxSize, "the nearest filter has the bicubic filter's size limit");
 static_assert(kLanczosMaxRatio == kCubicMaxRatio && kLanczosMaxSize == kCubicMaxSize, "the two filters share their limits: cubic_item_wrong");
 
@@ -100,10 +101,20 @@ static const char* nearest_item_wrong(const qoi_desc* d, const qoimi_resize* r) 
     return nullptr;
 }
 
-// The bicubic, the Lanczos and the nearest filter write tensors only: no launcher of a byte kernel, the counters and the name are the tensor call's.
-static const ResampleKind kCubicKind = {cubic_item_wrong, cubic_split, cubic_tiles, nullptr, &qoimi_ctx::tensor_stats, "tensor_cubic"};
-static const ResampleKind kLanczosKind = {cubic_item_wrong, lanczos_split, lanczos_tiles, nullptr, &qoimi_ctx::tensor_stats, "tensor_lanczos"};
-static const ResampleKind kNearestKind = {nearest_item_wrong, nearest_split, nearest_tiles, nullptr, &qoimi_ctx::tensor_stats, "tensor_nearest"};
+// ... with a ratio limit of 16 and the size limit (qoi_mode_core.h: what keeps a cell within 16 x 16 pixels - four a lane of a wavefront - and
+// its ends in one 32-bit division each)
+static const char* mode_item_wrong(const qoi_desc* d, const qoimi_resize* r) {
+    if (const char* what = resample_rect_wrong(d, r)) return what;
+    if (r->width > (uint64_t)kModeMaxRatio * r->out_width || r->height > (uint64_t)kModeMaxRatio * r->out_height) return "reduced by more than 16 in an axis";
+    if (r->width > kModeMaxSize || r->out_width > kModeMaxSize || r->height > kModeMaxSize || r->out_height > kModeMaxSize) return "a width or height above 16384";
+    return nullptr;
+}
+
+// The bicubic, the Lanczos, the nearest and the mode filter write tensors only: no launcher of a byte kernel, the counters and the name are the tensor call's.
+static const ResampleKind kCubicKind = {cubic_item_wrong, split_columns<cubic_split>, tiles_columns<cubic_tiles>, nullptr, &qoimi_ctx::tensor_stats, "tensor_cubic"};
+static const ResampleKind kLanczosKind = {cubic_item_wrong, split_columns<lanczos_split>, tiles_columns<lanczos_tiles>, nullptr, &qoimi_ctx::tensor_stats, "tensor_lanczos"};
+static const ResampleKind kNearestKind = {nearest_item_wrong, split_columns<nearest_split>, tiles_columns<nearest_tiles>, nullptr, &qoimi_ctx::tensor_stats, "tensor_nearest"};
+static const ResampleKind kModeKind = {mode_item_wrong, mode_split, mode_tiles, nullptr, &qoimi_ctx::tensor_stats, "tensor_mode"};
 
 // A filter of qoimi_decode_tensors: its kind, the launcher of its tensor kernel and that kernel's name for a launch failure
 struct TensorFilter {
@@ -119,6 +130,7 @@ static TensorFilter tensor_filter(int filter) {
     case QOIMI_FILTER_BICUBIC: return {&kCubicKind, launch_tensor_cubic, kCubicKind.kernel};
     case QOIMI_FILTER_LANCZOS: return {&kLanczosKind, launch_tensor_lanczos, kLanczosKind.kernel};
     case QOIMI_FILTER_NEAREST: return {&kNearestKind, launch_tensor_nearest, kNearestKind.kernel};
+    case QOIMI_FILTER_MODE: return {&kModeKind, launch_tensor_mode, kModeKind.kernel};
     default: return {nullptr, nullptr, nullptr};
     }
 }
@@ -142,7 +154,7 @@ extern "C" int qoimi_decode_tensors(qoimi_ctx* c, const void* d_streams, const s
                                     int n_images, int channels, const qoimi_resize* items, int n_items, int filter, int mode,
                                     const qoimi_tensor_format* format, void* d_out, const size_t* out_offsets, size_t staging_bytes, void* stream) {
     const TensorFilter tf = tensor_filter(filter);
-    if (!tf.kind) return fail(QOIMI_E_ARG, "filter must be QOIMI_FILTER_LANCZOS, QOIMI_FILTER_AREA, QOIMI_FILTER_BILINEAR or QOIMI_FILTER_BICUBIC, or QOIMI_FILTER_NEAREST");
+    if (!tf.kind) return fail(QOIMI_E_ARG, "filter must be QOIMI_FILTER_LANCZOS, QOIMI_FILTER_AREA, QOIMI_FILTER_BILINEAR or QOIMI_FILTER_BICUBIC, or QOIMI_FILTER_NEAREST or QOIMI_FILTER_MODE");
     return gather_resampled(*tf.kind, c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
         [&]() { return check_tensor_format(format); },
         [&](const qoimi_resize* r, unsigned och, size_t* bytes) { return tensor_bytes(resize_bytes, r, och, format, bytes); },

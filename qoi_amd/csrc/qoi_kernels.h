@@ -298,7 +298,7 @@ static_assert(sizeof(CmpImage) == 32 && sizeof(CmpDiff) == 32, "table layouts");
 void launch_compare(const uint8_t* a, const uint8_t* b, const CmpImage* tab, uint32_t m, uint32_t tiles, CmpDiff* diffs, uint32_t grid,
                     hipStream_t st, KernelTimer* tm);
 
-// ---- table-driven kernels over staged pixels (qoi_thumb.hip, qoi_crop.hip, qoi_resize.hip, qoi_warp.hip, qoi_tensor.hip, qoi_cubic.hip, qoi_lanczos.hip, qoi_nearest.hip, qoi_stats.hip) ------
+// ---- table-driven kernels over staged pixels (qoi_thumb.hip, qoi_crop.hip, qoi_resize.hip, qoi_warp.hip, qoi_tensor.hip, qoi_cubic.hip, qoi_lanczos.hip, qoi_nearest.hip, qoi_mode.hip, qoi_stats.hip) ------
 // One entry per output (thumbnail, crop, resized item, region); the tile sizes, the largest factors and the arithmetic stand in
 // qoi_*_core.h, which the host tests compile without HIP.  launch_*: the kernel over the m table entries at tab (their tiles: [0, tiles));
 // grid: workgroups, at most `tiles`.  No timer marks: these kernels have no entry in the name table (the calls count their launches).
@@ -333,6 +333,8 @@ void launch_tensor_cubic(const uint8_t* stage, const ResizeEntry* tab, uint32_t 
 void launch_tensor_lanczos(const uint8_t* stage, const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, const TensorFormat& fmt, uint32_t grid, hipStream_t st);
 // ... and the nearest filter, for label maps (qoi_nearest.hip; one lane per pixel: nearest_split of qoi_nearest_core.h)
 void launch_tensor_nearest(const uint8_t* stage, const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, const TensorFormat& fmt, uint32_t grid, hipStream_t st);
+// ... and the mode filter, a majority vote for reducing label maps (qoi_mode.hip; L lanes share a pixel's cell: mode_split of qoi_mode_core.h)
+void launch_tensor_mode(const uint8_t* stage, const ResizeEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, const TensorFormat& fmt, uint32_t grid, hipStream_t st);
 void launch_tensor_warp(const uint8_t* stage, const WarpEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, const TensorFormat& fmt, uint32_t grid, hipStream_t st);
 // hist: NULL or the call's histograms
 void launch_stats(const uint8_t* stage, const StatsEntry* tab, uint32_t m, uint32_t tiles, StatsAcc* res, unsigned* hist, uint32_t grid, hipStream_t st);

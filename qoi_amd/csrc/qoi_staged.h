@@ -240,18 +240,24 @@ static int run_staged(qoimi_ctx* c, long long (&stats)[4], long long decoded, co
 // ------------------------------------------------------------------------------------
 // the resampling calls and the warp call, whatever their kernels write (qoi_host_staged.hip: bytes, qoi_host_tensor.hip: tensors)
 // ------------------------------------------------------------------------------------
-// A resampling filter: what is wrong with an item, how an output pixel's columns are split over lanes and the tiles of an item (its core
-// header); and of the call that writes bytes: its launcher, the context's counters of its last call, its kernel's name for a launch failure.
+// A resampling filter: what is wrong with an item, how an output pixel's source pixels are split over lanes and the tiles of an item (its
+// core header); and of the call that writes bytes: its launcher, the context's counters of its last call, its kernel's name for a launch
+// failure.
 struct ResampleKind {
     const char* (*wrong)(const qoi_desc*, const qoimi_resize*);
-    void (*split)(uint32_t cw, uint32_t ow, uint32_t& lg, uint32_t& c);
-    uint64_t (*tiles)(uint32_t cw, uint32_t ow, uint32_t oh);
+    void (*split)(uint32_t cw, uint32_t rh, uint32_t ow, uint32_t oh, uint32_t& lg, uint32_t& c);
+    uint64_t (*tiles)(uint32_t cw, uint32_t rh, uint32_t ow, uint32_t oh);
     void (*launch)(const uint8_t*, const ResizeEntry*, uint32_t, uint32_t, uint8_t*, uint32_t, hipStream_t);
     long long (qoimi_ctx::*stats)[4];
     const char* kernel;
 };
-static const ResampleKind kAreaKind = {resize_item_wrong, resize_split, resize_tiles, launch_resize, &qoimi_ctx::resize_stats, "resize_filter"};
-static const ResampleKind kTentKind = {bilinear_item_wrong, bilinear_split, bilinear_tiles, launch_bilinear, &qoimi_ctx::bilinear_stats, "bilinear_filter"};
+// The filters that split an output pixel's COLUMNS over lanes and loop over its rows: their split and tiles take no heights
+template <void (*Split)(uint32_t, uint32_t, uint32_t&, uint32_t&)>
+static void split_columns(uint32_t cw, uint32_t, uint32_t ow, uint32_t, uint32_t& lg, uint32_t& c) { Split(cw, ow, lg, c); }
+template <uint64_t (*Tiles)(uint32_t, uint32_t, uint32_t)>
+static uint64_t tiles_columns(uint32_t cw, uint32_t, uint32_t ow, uint32_t oh) { return Tiles(cw, ow, oh); }
+static const ResampleKind kAreaKind = {resize_item_wrong, split_columns<resize_split>, tiles_columns<resize_tiles>, launch_resize, &qoimi_ctx::resize_stats, "resize_filter"};
+static const ResampleKind kTentKind = {bilinear_item_wrong, split_columns<bilinear_split>, tiles_columns<bilinear_tiles>, launch_bilinear, &qoimi_ctx::bilinear_stats, "bilinear_filter"};
 
 // The hooks of a call that has nothing to add to the checks
 static int accept_any() { return QOIMI_OK; }
@@ -279,7 +285,7 @@ static int gather_resampled(const ResampleKind& kind, qoimi_ctx* c, const void* 
     const unsigned och = ok.och;
     GatherPlan gp;
     if (const int rc = plan_gather(descs, n_images, ok.rows, staging_bytes, n, [&](size_t j) { return items[j].image; },
-                                   [&](size_t j) { return kind.tiles(items[j].width, items[j].out_width, items[j].out_height); },
+                                   [&](size_t j) { return kind.tiles(items[j].width, items[j].height, items[j].out_width, items[j].out_height); },
                                    "more than 2^31 tiles of output pixels in one sub-batch", gp)) return rc;
     const RowsPlan& plan = gp.rows; const ItemPlan& order = gp.items;
     const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
@@ -288,7 +294,7 @@ static int gather_resampled(const ResampleKind& kind, qoimi_ctx* c, const void* 
             const size_t j = order.by_ref[e];
             const qoimi_resize& r = items[j];
             uint32_t lg, cols;
-            kind.split(r.width, r.out_width, lg, cols);
+            kind.split(r.width, r.height, r.out_width, r.out_height, lg, cols);
             t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]]; t.dst_off = (u64)out_offsets[j];
             t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
             t.first_tile = order.first_tile[e]; t.cfg = lg | (cols << 8) | (och << 16) | (weighted << 24) | (r.flags << 28); t.reserved = 0u;

@@ -2,7 +2,7 @@
 header repeats it; qoi_amd/csrc/qoi_tensor_core.h holds the arithmetic of the kernels).
 
 Let P be the uint8[oh, ow, och] result of the underlying call - ``resize.resize`` for ``FILTER_AREA``, ``bilinear.bilinear`` for
-``FILTER_BILINEAR``, ``bicubic.bicubic`` for ``FILTER_BICUBIC``, ``lanczos.lanczos`` for ``FILTER_LANCZOS`` and ``nearest.nearest`` for ``FILTER_NEAREST`` (which have no u8 call of their own), ``warp.warp`` for the warp call - with the same item, channels and mode, byte for byte, flips included.  A format is
+``FILTER_BILINEAR``, ``bicubic.bicubic`` for ``FILTER_BICUBIC``, ``lanczos.lanczos`` for ``FILTER_LANCZOS``, ``nearest.nearest`` for ``FILTER_NEAREST`` and ``mode.mode`` for ``FILTER_MODE`` (which have no u8 call of their own), ``warp.warp`` for the warp call - with the same item, channels and mode, byte for byte, flips included.  A format is
 (dtype, layout, scale, bias): scale and bias are four binary32 numbers, per channel r, g, b, a.  Element (Y, X, c) has the value v = P[Y][X][c]:
 
     U8      the element is v; scale must be all 1 and bias all +0
@@ -29,7 +29,7 @@ from typing import Sequence, Tuple
 
 import numpy as np
 
-from . import bicubic, bilinear, crops, lanczos, nearest, resize, warp
+from . import bicubic, bilinear, crops, lanczos, mode, nearest, resize, warp
 
 U8, F16, BF16, F32 = 0, 1, 2, 3
 I32, I64 = 5, 6                 # (4 is not a dtype)
@@ -39,8 +39,9 @@ FILTER_AREA, FILTER_BILINEAR = 0, 1
 FILTER_BICUBIC = 3              # (2 is not a filter)
 FILTER_LANCZOS = 6              # (nor are 4, 5 and 7)
 FILTER_NEAREST = 9              # (nor is 8)
+FILTER_MODE = 11                # (nor is 10)
 _FILTERS = {FILTER_AREA: resize.resize, FILTER_BILINEAR: bilinear.bilinear, FILTER_BICUBIC: bicubic.bicubic, FILTER_LANCZOS: lanczos.lanczos,
-            FILTER_NEAREST: nearest.nearest}
+            FILTER_NEAREST: nearest.nearest, FILTER_MODE: mode.mode}
 ELEM = {U8: 1, F16: 2, BF16: 2, F32: 4}
 INT_ELEM = {I32: 4, I64: 8}     # the integer class-index dtypes, beside ELEM
 DTYPE_NAMES = {"u8": U8, "f16": F16, "bf16": BF16, "f32": F32, "i32": I32, "i64": I64}
@@ -138,8 +139,8 @@ def size_hw(u8_bytes: int, och: int, dtype: int) -> int:
 
 
 def tensors(D: np.ndarray, rect, out_size, flags: int = 0, filter: int = FILTER_AREA, mode: int = PLAIN, f=None) -> np.ndarray:
-    """One item of qoimi_decode_tensors: ``convert`` of ``resize.resize``, ``bilinear.bilinear``, ``bicubic.bicubic``, ``lanczos.lanczos`` or
-    ``nearest.nearest`` of the same arguments."""
+    """One item of qoimi_decode_tensors: ``convert`` of ``resize.resize``, ``bilinear.bilinear``, ``bicubic.bicubic``, ``lanczos.lanczos``,
+    ``nearest.nearest`` or ``mode.mode`` of the same arguments."""
     if filter not in _FILTERS:
         raise ValueError("tensors: unknown filter")
     P = _FILTERS[filter](D, rect, out_size, flags, mode)

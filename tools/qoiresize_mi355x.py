@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """qoiresize for the MI355X path: a set of .qoi files as PNGs of one fixed size.
 
-    python tools/qoiresize_mi355x.py FILE_OR_DIR... --size WxH -o DIR [--fit whole|crop] [--mode plain|weighted] [--flip x|y|xy] [--filter area|bilinear|bicubic|lanczos|nearest]
+    python tools/qoiresize_mi355x.py FILE_OR_DIR... --size WxH -o DIR [--fit whole|crop] [--mode plain|weighted] [--flip x|y|xy] [--filter area|bilinear|bicubic|lanczos|nearest|mode]
                                      [--staging-mb M]
 
 Loads the .qoi files (directories are walked), uploads them as ONE pack and makes ONE qoimi_decode_resized call: every stream is decoded on
@@ -14,7 +14,9 @@ states, the one to enlarge with; its rectangles are at most 32 times the target 
 --filter bicubic is the antialiased bicubic filter qoi_amd/bicubic.py states, through qoimi_decode_tensors as u8 HWC (it has no call of its own): at
 most 16 times the target in an axis, no side above 16384.  --filter lanczos is the Lanczos filter with three lobes qoi_amd/lanczos.py states, by
 the same call and with the same limits.  --filter nearest is the selection qoi_amd/nearest.py states, for label maps - one pixel of the source per
-output pixel, nothing averaged -, by the same call: no side above 16384, no ratio limit.
+output pixel, nothing averaged -, by the same call: no side above 16384, no ratio limit.  --filter mode is the majority vote qoi_amd/mode.py
+states, for REDUCING label maps - the most frequent pixel of each output pixel's cell -, by the same call: at most 16 times the target in an
+axis, no side above 16384.
 A file that is no QOI stream (size, magic, header rules of qoi.h:497-521) or whose rectangle is more than 64 (32, 16)
 times the target in an axis is reported and left out; exit status 1 if there was one, else 0.  Needs torch for device memory, as
 tools/qoicheck_mi355x.py does.
@@ -65,7 +67,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("--fit", choices=("whole", "crop"), default="whole")
     ap.add_argument("--mode", choices=("plain", "weighted"), default="plain")
     ap.add_argument("--flip", choices=("none", "x", "y", "xy"), default="none")
-    ap.add_argument("--filter", choices=("area", "bilinear", "bicubic", "lanczos", "nearest"), default="area")
+    ap.add_argument("--filter", choices=("area", "bilinear", "bicubic", "lanczos", "nearest", "mode"), default="area")
     ap.add_argument("--staging-mb", type=int, default=0, metavar="M", help="device memory for decoded pixels (0: 1 GiB)")
     try:
         a = ap.parse_args(argv)
@@ -81,6 +83,7 @@ def main(argv, out=print) -> int:
     ow, oh = size
     import torch  # first: the library then binds to the HIP runtime torch already loaded
     from qoi_amd import api, bicubic, bilinear, lanczos, nearest, resize, tensors
+    from qoi_amd import mode as mode_filter
     from tools import png_io
 
     files = collect(a.paths)
@@ -96,14 +99,14 @@ def main(argv, out=print) -> int:
             out(f"{os.path.basename(files[i])}: not a QOI stream, left out")
             continue
         x, y, cw, rh = fit_rect(hd[0], hd[1], ow, oh, a.fit)
-        cap = {"area": resize.MAX_RATIO, "bilinear": bilinear.MAX_RATIO, "bicubic": bicubic.MAX_RATIO, "lanczos": lanczos.MAX_RATIO, "nearest": None}[a.filter]
+        cap = {"area": resize.MAX_RATIO, "bilinear": bilinear.MAX_RATIO, "bicubic": bicubic.MAX_RATIO, "lanczos": lanczos.MAX_RATIO, "nearest": None, "mode": mode_filter.MAX_RATIO}[a.filter]
         if cap is not None and (cw > cap * ow or rh > cap * oh):
             out(f"{os.path.basename(files[i])}: {cw}x{rh} is more than {cap} times {ow}x{oh} in an axis, left out")
             continue
         if a.filter == "bilinear" and max(cw, ow) * max(rh, oh) >= bilinear.MAX_AREA:
             out(f"{os.path.basename(files[i])}: {cw}x{rh} to {ow}x{oh} is beyond the bilinear filter's size limit, left out")
             continue
-        if a.filter in ("bicubic", "lanczos", "nearest") and max(cw, ow, rh, oh) > (nearest.MAX_SIZE if a.filter == "nearest" else bicubic.MAX_SIZE):
+        if a.filter in ("bicubic", "lanczos", "nearest", "mode") and max(cw, ow, rh, oh) > {"nearest": nearest.MAX_SIZE, "mode": mode_filter.MAX_SIZE}.get(a.filter, bicubic.MAX_SIZE):
             out(f"{os.path.basename(files[i])}: {cw}x{rh} to {ow}x{oh} is beyond the {a.filter} filter's size limit, left out")
             continue
         good.append(i)
@@ -123,8 +126,8 @@ def main(argv, out=print) -> int:
     ctx = api.Context(0)
     try:
         mode = resize.ALPHA_WEIGHTED if a.mode == "weighted" else resize.PLAIN
-        if a.filter in ("bicubic", "lanczos", "nearest"):
-            filt = {"bicubic": tensors.FILTER_BICUBIC, "lanczos": tensors.FILTER_LANCZOS, "nearest": tensors.FILTER_NEAREST}[a.filter]
+        if a.filter in ("bicubic", "lanczos", "nearest", "mode"):
+            filt = {"bicubic": tensors.FILTER_BICUBIC, "lanczos": tensors.FILTER_LANCZOS, "nearest": tensors.FILTER_NEAREST, "mode": tensors.FILTER_MODE}[a.filter]
             ctx.decode_tensors(pack.data_ptr(), offsets, sizes, descs, och, items, filt, mode, tensors.fmt(), d_out.data_ptr(), o_off,
                                a.staging_mb << 20)
             stats = ctx.tensor_stats

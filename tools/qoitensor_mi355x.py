@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """qoitensor for the MI355X path: a set of .qoi files as ONE .npy tensor, N x C x H x W or N x H x W x C, normalised.
 
-    python tools/qoitensor_mi355x.py FILE_OR_DIR... --size WxH -o OUT.npy [--filter area|bilinear|bicubic|lanczos|nearest] [--dtype u8|f16|bf16|f32|i32|i64]
+    python tools/qoitensor_mi355x.py FILE_OR_DIR... --size WxH -o OUT.npy [--filter area|bilinear|bicubic|lanczos|nearest|mode] [--dtype u8|f16|bf16|f32|i32|i64]
                                      [--layout chw|hwc|hw]
                                      [--mean M[,M,M[,M]]] [--std S[,S,S[,S]]] [--fit whole|crop] [--channels 3|4] [--staging-mb M]
 
@@ -11,9 +11,10 @@ of the tensor straight from the filter's registers - 8-bit interleaved pixels ne
 scale = 1 / (255 * std) and bias = -mean / std are computed in float64 and rounded once to float32 (scale_bias); the library then computes
 float32(p) * scale + bias with two roundings and narrows once (qoi_amd/tensors.py states it).  Without --mean / --std the elements are
 p / 255; --dtype u8, i32 and i64 take neither and store p.  --filter nearest --dtype i64 --layout hw makes N x H x W class indices of label maps:
-one pixel of the source per element, nothing averaged, the first channel alone.  One value of --mean / --std serves every channel; a fourth (alpha) defaults to mean 0, std 1.
+one pixel of the source per element, nothing averaged, the first channel alone; --filter mode instead takes the most frequent pixel of each
+element's cell (qoi_amd/mode.py: a majority vote, for REDUCING label maps).  One value of --mean / --std serves every channel; a fourth (alpha) defaults to mean 0, std 1.
 --channels defaults to 3.  bf16 is stored as the uint16 of its bits (NumPy has no bfloat16).  A file that is no QOI stream or whose
-rectangle the filter cannot reduce to the target (64 times in an axis, 32 for bilinear, 16 for bicubic and lanczos, no limit but a side of 16384 for nearest) is reported and left out; exit status 1 if there was
+rectangle the filter cannot reduce to the target (64 times in an axis, 32 for bilinear, 16 for bicubic and lanczos, no limit but a side of 16384 for nearest, 16 and a side of 16384 for mode) is reported and left out; exit status 1 if there was
 one, else 0.  Needs torch for device memory, as tools/qoicheck_mi355x.py does.
 """
 from __future__ import annotations
@@ -64,7 +65,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("paths", nargs="+", metavar="FILE_OR_DIR")
     ap.add_argument("--size", required=True, metavar="WxH")
     ap.add_argument("-o", "--out", required=True, metavar="OUT.npy")
-    ap.add_argument("--filter", choices=("area", "bilinear", "bicubic", "lanczos", "nearest"), default="bilinear")
+    ap.add_argument("--filter", choices=("area", "bilinear", "bicubic", "lanczos", "nearest", "mode"), default="bilinear")
     ap.add_argument("--dtype", choices=("u8", "f16", "bf16", "f32", "i32", "i64"), default="f32")
     ap.add_argument("--layout", choices=("chw", "hwc", "hw"), default="chw")
     ap.add_argument("--mean", default=None, metavar="M[,M,M[,M]]")
@@ -99,13 +100,14 @@ def main(argv, out=print) -> int:
     ow, oh = size
     import torch  # first: the library then binds to the HIP runtime torch already loaded
     from qoi_amd import api, bicubic, bilinear, lanczos, nearest, resize, tensors
+    from qoi_amd import mode as mode_filter
 
     files = collect(a.paths)
     if not files:
         out("no .qoi files")
         return 2
     model, filt = {"area": (resize, tensors.FILTER_AREA), "bilinear": (bilinear, tensors.FILTER_BILINEAR), "bicubic": (bicubic, tensors.FILTER_BICUBIC),
-                   "lanczos": (lanczos, tensors.FILTER_LANCZOS), "nearest": (nearest, tensors.FILTER_NEAREST)}[a.filter]
+                   "lanczos": (lanczos, tensors.FILTER_LANCZOS), "nearest": (nearest, tensors.FILTER_NEAREST), "mode": (mode_filter, tensors.FILTER_MODE)}[a.filter]
     blobs = [open(f, "rb").read() for f in files]
     heads = [parse_header(b) for b in blobs]
     good = []
