@@ -663,14 +663,45 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * pixel is the sample, byte for byte, and both modes give the same bytes.  With the identity the call is qoimi_decode_crops; with any
  * qoimi_warp_orient item it equals the bilinear warp byte for byte, because every position is a pixel centre.  Limits, plan, staging and every
  * rejection are those of the bilinear warp; the flag rule reads: a bit other than QOIMI_WARP_REPLICATE and QOIMI_WARP_NEAREST (2 is not a
- * flag, nor is any bit from 8 on).  The flag applies unchanged to qoimi_decode_warped_tensors and qoimi_decode_warped_indexed, and
+ * flag, nor is 8; QOIMI_WARP_BICUBIC, below, is the third flag).  The flag applies unchanged to qoimi_decode_warped_tensors and qoimi_decode_warped_indexed, and
  * qoimi_warp_size and qoimi_warp_tensor_size accept it.  Items with and without the flag mix freely in one call.
+ * QOIMI_WARP_BICUBIC (a flag of the item, combinable with QOIMI_WARP_REPLICATE, never with QOIMI_WARP_NEAREST; normative; qoi_amd/warp.py: warp
+ * states it in Python, qoi_amd/csrc/qoi_warp_cubic_core.h holds it in C++) replaces the 2 x 2 taps with 4 x 4 samples under Keys' cubic with
+ * a = -1/2: the kernel of QOIMI_FILTER_BICUBIC and of PIL's BICUBIC, so both halves of the library give the same picture.  cv2.INTER_CUBIC and
+ * torch's grid_sample(mode="bicubic") use a = -3/4 and therefore differ.  Px, Py, the limits and their order, the plan and the staging are
+ * exactly those of the bilinear warp.  One axis, with u = 2^17: p = P - 65536, k0 = p >> 17 (arithmetic), fr = p & 131071; the four samples are
+ * k0 - 1, k0, k0 + 1, k0 + 2 at the distances d = u + fr, fr, u - fr, 2u - fr, and c(d) is the formula of QOIMI_FILTER_BICUBIC:
+ * 3d^3 - 5u d^2 + 2u^3 for d <= u, -d^3 + 5u d^2 - 8u^2 d + 4u^3 for u < d < 2u, 0 from 2u on (every term is below 2^56).  The four c add up to
+ * W = 2u^3 = 2^52 for every fr.  q_j = (c_j + 2^36) >> 37 (arithmetic) - c_j * 2^15 / W rounded; the deficit 2^15 - sum q_j goes to the tap with
+ * the largest c, the lowest j on a tie: the weights of an axis add up to exactly 2^15.  A tap with q == 0 counts as not taken and is never
+ * read.  Samples outside R are never read, even where the image has pixels there: with QOIMI_WARP_REPLICATE each of the four indices is clamped
+ * into R (the 64-bit index is tested before it is narrowed), without it the sample has the value `fill` and keeps its weight - there is no
+ * renormalisation, as in the bilinear warp.  Two axes, one rounding: N_c = sum of qy * qx * c over the 4 x 4 samples.
+ *   QOIMI_RESIZE_PLAIN           every channel is clamp((N_c + 2^29) >> 30, 0, 255): the negative lobes overshoot, the clamp is part of the definition
+ *   QOIMI_RESIZE_ALPHA_WEIGHTED  where och == 4: A = N_a, alpha is the PLAIN value; if A > 0, r, g and b are clamp((sum qy * qx * c * a + A/2) / A, 0, 255)
+ *                                with a flooring division; if A <= 0 - the negative lobes make that possible - they are the PLAIN value.  With
+ *                                och == 3 this mode is PLAIN.
+ * The |q| of an axis sum to at most 5 * 2^13 = 1.25 * 2^15 (at fr = u / 2 the weights are -1/16, 9/16, 9/16, -1/16), so a horizontal blend is
+ * below 2^24 in magnitude, |N_c| < 2^40 and the alpha-weighted sums are below 2^48.
+ * At a pixel centre, fr = 0 on both axes, the weights are (0, 2^15, 0, 0): the identity map gives qoimi_decode_crops byte for byte and every
+ * qoimi_warp_orient item gives the bilinear warp byte for byte.  A constant rectangle stays the constant under any map with REPLICATE.  With
+ * a = e = 65536 / s, s a power of two, b = c = d = f = 0 and an output of s times the rectangle, every output pixel whose 4 x 4 taps all lie
+ * inside R equals QOIMI_FILTER_BICUBIC of qoimi_decode_tensors (U8, HWC) enlarging by s, byte for byte: the two definitions give the same
+ * rational weights there and differ only at the border, where the filter renormalises and the warp replicates.  Against a float64 evaluation
+ * of the same Keys kernel at the same positions with the same border rule, clamped and rounded, a PLAIN value differs by at most 1, and only
+ * where the float result lies at a rounding boundary (qoi_amd/warp.py derives it from the quantisation of q, the deficit tap and the one
+ * rounding: E < 0.036).  NO ANTIALIASING here either: a map that reduces takes sixteen samples.  The flag rule reads: a bit other than 1, 4 and
+ * 16 is an unknown flag bit (2 and 8 are not flags); then QOIMI_WARP_NEAREST and QOIMI_WARP_BICUBIC together are rejected with a message of
+ * their own.  The flag applies unchanged to qoimi_decode_warped_tensors and qoimi_decode_warped_indexed, and qoimi_warp_size and
+ * qoimi_warp_tensor_size accept it.  Items with and without the flag mix freely in one call; a call with such an item runs a kernel of its own
+ * that serves all its items, a call without one runs what it always ran.
+ * Not here: other cubic kernels (a = -3/4), Lanczos in the warp, antialiasing of reducing maps, projective maps.
  * The rectangle is what is staged and what the border is taken at: rows_i of the plan is the maximum of y + height over the items of image i,
  * so the caller keeps the rectangle tight around what the map reaches - a rectangle of the whole image under a map that reaches one corner
  * decodes the whole image.
  * Limits, checked per item in this order: a zero width, height, out_width or out_height; a rectangle that leaves its image; out_width or
  * out_height of 2^20 or more; out_width * out_height of 400 000 000 or more; |c| or |f| of 2^56 or more; a flag bit other than
- * QOIMI_WARP_REPLICATE; reserved != 0.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
+ * QOIMI_WARP_REPLICATE, QOIMI_WARP_NEAREST and QOIMI_WARP_BICUBIC, then the last two together; reserved != 0.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
  * 2^57: both positions fit 64 bits with room to spare.  N_c <= 255 * 2^34 < 2^42, the alpha-weighted sums are below 2^50.
  *   stream_offsets, sizes, descs, channels, out_offsets, staging_bytes  as for qoimi_decode_resized; the plan is that of qoimi_decode_crops
  *                  over the items' rectangles (normative; qoi_amd/warp.py: plan)
@@ -681,13 +712,13 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * for the limits above, and for a sub-batch of the plan with 2^31 - 1 or more tiles of 16 x 16 output pixels: reported before anything is
  * launched, the caller's buffers are untouched; qoimi_last_error names the cause.  Output ranges must not overlap.  The sub-batches count as
  * decode calls of the context.  One call at a time per context, as everywhere. */
-enum { QOIMI_WARP_REPLICATE = 1, QOIMI_WARP_NEAREST = 4 };   /* 2 is not a flag */
+enum { QOIMI_WARP_REPLICATE = 1, QOIMI_WARP_NEAREST = 4, QOIMI_WARP_BICUBIC = 16 };   /* 2 and 8 are not flags */
 typedef struct {                 /* 72 bytes, offsets 0/4/8/12/16/20/24/28/32/36/40/44/48/52/56/64 */
     unsigned int image;          /* index into the call's images */
     unsigned int x, y;           /* top-left corner of the source rectangle */
     unsigned int width, height;  /* both >= 1; x + width <= image width, y + height <= image height */
     unsigned int out_width, out_height;  /* both >= 1 and below 2^20; their product below 400 000 000 */
-    unsigned int flags;          /* QOIMI_WARP_REPLICATE, QOIMI_WARP_NEAREST; no other bit */
+    unsigned int flags;          /* QOIMI_WARP_REPLICATE, QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC; no other bit */
     int a, b, d, e;              /* the linear part of the inverse map, 16 fractional bits */
     unsigned int fill;           /* r | g << 8 | b << 16 | a << 24: the value of a sample outside the rectangle without REPLICATE */
     unsigned int reserved;       /* 0 */

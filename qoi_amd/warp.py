@@ -18,6 +18,26 @@ integer, every shift and division floors.
   ``(2k + 1) << 16``.  Where k is outside ``[0, cw)`` or r outside ``[0, rh)`` the index is clamped into R with ``REPLICATE``, else the output
   pixel is ``fill`` (a 3-channel output ignores its alpha).  The output pixel is the sample, byte for byte, in both modes.  With the
   identity that is ``crops.crop``; with any ``orient`` item it equals the bilinear result, every position being a pixel centre.
+* With ``BICUBIC`` (a flag, combinable with ``REPLICATE``, never with ``NEAREST``) the 2 x 2 taps are replaced by 4 x 4 samples under Keys' cubic
+  with a = -1/2 - the kernel of ``bicubic.py`` (PIL ``BICUBIC``), not the a = -3/4 of ``cv2.INTER_CUBIC`` and torch's ``grid_sample``.  The
+  position is the bilinear warp's.  One axis, ``u = 2**17``: ``p = P - 65536``, ``k0 = p >> 17``, ``fr = p & 131071``; the samples are
+  ``k0 - 1, k0, k0 + 1, k0 + 2`` at the distances ``d = u + fr, fr, u - fr, 2u - fr``; ``c(d) = 3d^3 - 5u*d^2 + 2u^3`` for ``d <= u``,
+  ``-d^3 + 5u*d^2 - 8u^2*d + 4u^3`` for ``u < d < 2u``, 0 from ``2u`` on (every term below ``2**56``).  The four c add up to
+  ``W = 2u^3 = 2**52`` for every fr (asserted here).  ``q_j = (c_j + 2**36) >> 37``; the deficit ``2**15 - sum q_j`` goes to the tap with
+  the largest c, the lowest j on a tie: the weights of an axis add up to ``2**15``.  A tap with ``q == 0`` counts as not taken.  With
+  ``REPLICATE`` each of the four indices is clamped into R, else a sample outside R has the value ``fill`` and KEEPS its weight (no
+  renormalisation, as in the bilinear warp).  ``N_c = sum qy * qx * c`` over the 4 x 4 samples - two axes, one rounding.  ``PLAIN``: every
+  channel is ``clamp((N_c + 2**29) >> 30, 0, 255)``.  ``ALPHA_WEIGHTED``, 4 channels only: ``A = N_a``, alpha is the PLAIN value; where
+  ``A > 0`` r, g and b are ``clamp((sum qy*qx*c*a + A // 2) // A, 0, 255)``, where ``A <= 0`` (the negative lobes make that possible) they
+  are the PLAIN value.  ``sum |q|`` of an axis is at most ``5 * 2**13`` (1.25 * 2**15, reached at fr = u / 2; asserted here), so a
+  horizontal blend is below ``2**24``, ``|N_c| < 2**40`` and the alpha-weighted sums are below ``2**48``.
+  At a pixel centre (fr = 0 on both axes) the weights are ``(0, 2**15, 0, 0)``: the identity is ``crops.crop`` and every ``orient`` item
+  equals the bilinear result.  A constant stays the constant under any map with ``REPLICATE``.  With ``a = e = ONE // s``, s a power of two,
+  everything else 0 and an output of s times the rectangle, every output pixel whose 4 x 4 taps lie inside R equals ``bicubic.bicubic``
+  enlarging by s (the same rational weights; at the border the filter renormalises and the warp replicates).
+  Against a float64 evaluation of the same kernel with the same border rule (``cubic_reference``), PLAIN: the derivation of ``bicubic.py``
+  with T = 4 taps and L = sum |w| <= 3/2 per axis gives ``E = 255 / 2**16 * 9 + 255 * 9 / 2**31 < 0.036``: a byte differs from the rounded,
+  clamped reference by at most ``floor(1 + E) = 1`` (``cubic_bound``), and only at a rounding boundary.
 * ``N_c = sum wy * wx * c`` over the four samples; the weights add up to ``2**34``.
 * ``PLAIN``: every channel is ``(N_c + 2**33) >> 34`` - ONE rounding.
 * ``ALPHA_WEIGHTED``, 4 channels only: ``A = N_a``; alpha as in the plain mode; where ``A > 0`` r, g and b are
@@ -25,7 +45,7 @@ integer, every shift and division floors.
 * There is no antialiasing: a map that reduces still takes four samples (reduce first with ``resize.resize`` where that matters).
 
 Limits, in the order the C side checks them: a zero size; a rectangle that leaves its image; ``ow, oh < 2**20``; ``ow * oh < 400 000 000``;
-``|c|, |f| < 2**56``; no flag bit but ``REPLICATE`` and ``NEAREST`` (2 is not a flag); ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
+``|c|, |f| < 2**56``; no flag bit but ``REPLICATE``, ``NEAREST`` and ``BICUBIC`` (2 and 8 are not flags), then not ``NEAREST`` and ``BICUBIC`` together; ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
 ``|Px|, |Py| < 2**57``; ``N_c <= 255 * 2**34 < 2**42``; the alpha-weighted sums are below ``2**50``: everything fits int64.
 
 With the identity the result is ``crops.crop``; with ``a = ONE // s`` and REPLICATE it is ``bilinear.bilinear`` enlarging by the power of two s;
@@ -40,10 +60,13 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import crops, resize
+from . import bicubic, crops, resize
 
 REPLICATE = 1
 NEAREST = 4                     # one sample, not 2 x 2 taps (2 is not a flag)
+BICUBIC = 16                    # 4 x 4 samples under Keys' cubic, a = -1/2 (8 is not a flag)
+CUBIC_ONE = bicubic.ONE         # the weights of an axis add up to it
+CUBIC_L1_MAX = 5 << 13          # sum |q| of an axis stays at or below it
 PLAIN = resize.PLAIN
 ALPHA_WEIGHTED = resize.ALPHA_WEIGHTED
 ONE = 1 << 16                   # a factor of 1; a pixel is 2 * ONE in doubled coordinates
@@ -94,8 +117,10 @@ def _wrong(w: int, h: int, rect, out_size, matrix, flags: int, reserved: int = 0
         return "|c| or |f| from 2**56"
     if any(not -2 ** 31 <= v < 2 ** 31 for v in (a, b, d, e)):
         return "a, b, d, e are 32-bit"
-    if flags & ~(REPLICATE | NEAREST):
+    if flags & ~(REPLICATE | NEAREST | BICUBIC):
         return "unknown flag bit"
+    if flags & NEAREST and flags & BICUBIC:
+        return "NEAREST and BICUBIC together"
     if reserved:
         return "reserved is not 0"
     return ""
@@ -112,6 +137,73 @@ def _axis(P: np.ndarray, n: int, replicate: bool):
     if replicate:
         inside = np.ones_like(inside)
     return np.clip(k, 0, n - 1), wgt, inside
+
+
+def cubic_weights(fr) -> np.ndarray:
+    """int64[..., 4]: the q of the samples k0 - 1 .. k0 + 2 for the fractions fr (0 .. 2**17 - 1); every last axis sums to 2**15."""
+    fr = np.asarray(fr, dtype=np.int64)
+    u = 2 * ONE
+    d = np.stack([u + fr, fr, u - fr, 2 * u - fr], axis=-1)
+    c = np.where(d <= u, 3 * d ** 3 - 5 * u * d ** 2 + 2 * u ** 3, -d ** 3 + 5 * u * d ** 2 - 8 * u * u * d + 4 * u ** 3)   # (c(2u) = 0)
+    if not (c.sum(axis=-1) == 1 << 52).all():
+        raise AssertionError("cubic_weights: the four c do not add up to 2**52")
+    q = (c + (1 << 36)) >> 37
+    best = np.argmax(c, axis=-1)[..., None]                              # (argmax: the lowest j of the largest c)
+    np.put_along_axis(q, best, np.take_along_axis(q, best, axis=-1) + (CUBIC_ONE - q.sum(axis=-1))[..., None], axis=-1)
+    if np.abs(q).sum(axis=-1).max(initial=0) > CUBIC_L1_MAX:
+        raise AssertionError("cubic_weights: sum |q| above its bound")
+    return q
+
+
+def _cubic_axis(P: np.ndarray, n: int, replicate: bool):
+    """(indices int64[..., 4] inside [0, n), weights int64[..., 4], taken-from-R bool[..., 4]) of the positions P on an axis of n samples."""
+    p = P - ONE
+    k = (p >> 17)[..., None] + np.arange(-1, 3, dtype=np.int64)
+    inside = (k >= 0) & (k < n)
+    if replicate:
+        inside = np.ones_like(inside)
+    return np.clip(k, 0, n - 1), cubic_weights(p & (2 * ONE - 1)), inside
+
+
+def _clamp(v: np.ndarray) -> np.ndarray:
+    return np.minimum(np.maximum(v, 0), 255)
+
+
+def cubic_reference(D: np.ndarray, rect, out_size, matrix=IDENTITY, flags: int = 0, fill: int = 0) -> np.ndarray:
+    """float64[out_height, out_width, och]: Keys' kernel (a = -1/2) at the same positions with the same border rule, evaluated in
+    float64, PLAIN, neither rounded nor clamped (positions below 2**53 are exact there)."""
+    D = np.asarray(D)
+    x, y, cw, rh = (int(v) for v in rect)
+    ow, oh = (int(v) for v in out_size)
+    a, b, c, d, e, f = (int(v) for v in matrix)
+    och = D.shape[2]
+    R = D[y:y + rh, x:x + cw].astype(np.float64)
+    F = np.array([(fill >> (8 * k)) & 255 for k in range(och)], dtype=np.float64)
+    U = (2 * np.arange(ow, dtype=np.int64) + 1)[None, :]
+    V = (2 * np.arange(oh, dtype=np.int64) + 1)[:, None]
+
+    def axis(P, n):
+        p = P - ONE
+        k = (p >> 17)[..., None] + np.arange(-1, 3, dtype=np.int64)
+        t = np.abs((p & (2 * ONE - 1)).astype(np.float64)[..., None] / (2 * ONE) - np.arange(-1, 3, dtype=np.float64))
+        w = np.where(t <= 1, 1.5 * t ** 3 - 2.5 * t ** 2 + 1, np.where(t < 2, -0.5 * t ** 3 + 2.5 * t ** 2 - 4 * t + 2, 0.0))
+        inside = (k >= 0) & (k < n) if not flags & REPLICATE else np.ones(k.shape, dtype=bool)
+        return np.clip(k, 0, n - 1), w, inside
+
+    kx, wx, inx = axis(a * U + b * V + c, cw)
+    ky, wy, iny = axis(d * U + e * V + f, rh)
+    out = np.zeros((oh, ow, och), dtype=np.float64)
+    for r in range(4):
+        for k in range(4):
+            v = np.where((iny[..., r] & inx[..., k])[..., None], R[ky[..., r], kx[..., k]], F[None, None, :])
+            out += (wy[..., r] * wx[..., k])[..., None] * v
+    return out
+
+
+def cubic_bound() -> int:
+    """The most a PLAIN byte of a ``BICUBIC`` item differs from ``round(clamp(cubic_reference))``: floor(1 + E) of the docstring."""
+    e_num = 255 * 3 * (3 + 3) * (1 << 14) + 255 * 3 * 3                  # E * 2**31 with T = 4 and L = 3/2 in both axes
+    return 1 + e_num // (1 << 31)
 
 
 def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, int], matrix=IDENTITY, flags: int = 0, fill: int = 0,
@@ -145,6 +237,22 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
         if flags & REPLICATE:
             inside = np.ones_like(inside)
         out = np.where(inside[..., None], R[np.clip(r, 0, rh - 1), np.clip(k, 0, cw - 1)], F[None, None, :])
+        return np.ascontiguousarray(out[..., :och].astype(np.uint8))
+    if flags & BICUBIC:
+        kx, qx, inx = _cubic_axis(a * U + b * V + c, cw, bool(flags & REPLICATE))
+        ky, qy, iny = _cubic_axis(d * U + e * V + f, rh, bool(flags & REPLICATE))
+        N = np.zeros((oh, ow, 4), dtype=np.int64)
+        M = np.zeros((oh, ow, 3), dtype=np.int64)
+        for r in range(4):
+            for k in range(4):
+                v = np.where((iny[..., r] & inx[..., k])[..., None], R[ky[..., r], kx[..., k]], F[None, None, :])
+                wgt = (qy[..., r] * qx[..., k])[..., None]               # signed; a sample without a weight adds nothing
+                N += wgt * v                                             # below 2**40 in magnitude
+                M += wgt * v[..., :3] * v[..., 3:4]                      # below 2**48
+        out = _clamp((N + (1 << 29)) >> 30)
+        if weighted:
+            A = N[..., 3:4]
+            out[..., :3] = np.where(A > 0, _clamp((M + A // 2) // np.maximum(A, 1)), out[..., :3])
         return np.ascontiguousarray(out[..., :och].astype(np.uint8))
     kx, wx, inx = _axis(a * U + b * V + c, cw, bool(flags & REPLICATE))
     ky, wy, iny = _axis(d * U + e * V + f, rh, bool(flags & REPLICATE))

@@ -2,7 +2,7 @@
 """qoiwarp for the MI355X path: a set of .qoi files as PNGs, re-oriented or turned about their centre.
 
     python tools/qoiwarp_mi355x.py FILE_OR_DIR... -o DIR (--orient N | --rotate DEG [--scale S]) [--size WxH] [--border fill|replicate]
-                                   [--sample bilinear|nearest]
+                                   [--sample bilinear|nearest|bicubic]
                                    [--fill RRGGBBAA] [--mode plain|weighted] [--staging-mb M]
 
 Loads the .qoi files (directories are walked), uploads them as ONE pack and makes ONE qoimi_decode_warped call: every stream is decoded on the
@@ -11,7 +11,7 @@ images do not exist outside that arena.  --orient N shows every image in the EXI
 every output pixel one source pixel: qoimi_warp_orient).  --rotate DEG turns the image counter-clockwise about its centre, enlarged by
 --scale (default 1), into an output of --size (default: the image's own size); the matrix is quantised to 2**-16 here on the host
 (rotation_matrix).  Samples outside the image take --fill (default 00000000) or, with --border replicate, the nearest pixel.  --sample nearest takes
-one source pixel per output pixel instead of the 2 x 2 bilinear taps (warp.NEAREST): for label maps, whose values must not be averaged.  There is no
+one source pixel per output pixel instead of the 2 x 2 bilinear taps (warp.NEAREST): for label maps, whose values must not be averaged; --sample bicubic takes 4 x 4 under Keys' cubic with a = -1/2 (warp.BICUBIC): sharper photographs under a turn.  There is no
 antialiasing: a scale well below 1 wants tools/qoiresize_mi355x.py first.  Outputs hold 4 channels if any file does, else 3, and are
 written as DIR/<name>.png through tools/png_io.py.  One row per file: w x h x channels, the map, the output size.  A file that is no QOI
 stream (size, magic, header rules of qoi.h:497-521) is reported and left out; exit status 1 if there was one, else 0.  Needs torch for device
@@ -70,7 +70,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("--scale", type=float, default=1.0, metavar="S")
     ap.add_argument("--size", default=None, metavar="WxH")
     ap.add_argument("--border", choices=("fill", "replicate"), default="fill")
-    ap.add_argument("--sample", choices=("bilinear", "nearest"), default="bilinear")
+    ap.add_argument("--sample", choices=("bilinear", "nearest", "bicubic"), default="bilinear")
     ap.add_argument("--fill", default="00000000", metavar="RRGGBBAA")
     ap.add_argument("--mode", choices=("plain", "weighted"), default="plain")
     ap.add_argument("--staging-mb", type=int, default=0, metavar="M", help="device memory for decoded pixels (0: 1 GiB)")
@@ -108,7 +108,7 @@ def main(argv, out=print) -> int:
     if not files:
         out("no .qoi files")
         return 2
-    flags = (warp.REPLICATE if a.border == "replicate" else 0) | (warp.NEAREST if a.sample == "nearest" else 0)
+    flags = (warp.REPLICATE if a.border == "replicate" else 0) | {"bilinear": 0, "nearest": warp.NEAREST, "bicubic": warp.BICUBIC}[a.sample]
     blobs = [open(f, "rb").read() for f in files]
     heads = [parse_header(b) for b in blobs]
     good, items = [], []
