@@ -4,13 +4,16 @@ Part 1, the arenas.  B32 = 2^32.  Two device allocations of B32 + 96 MiB: `src` 
 The pointer a call gets is always the allocation's own start and every offset lies below the allocation's size, so an offset o >= B32 has
 its alias o - B32 inside the same allocation: a kernel or marshaller that dropped a high half would read or write the alias - a failed
 assertion, not a fault (`layout` asserts this for every offset the file uses).  Each offset array gets three placements in ONE call: control
-(wholly below B32), straddling (from B32 - k, k odd - an odd number of elements for f16 / f32 outputs - and 0 < k < the item's size) and
-beyond (wholly beyond, at B32 + an odd number of elements).  After each call the expected output ranges are read back and filled with 0xA5
+(wholly below B32), straddling (from B32 - k, k an odd number of elements for tensor outputs of every element size, i64 included - an output
+is element-aligned and B32 a multiple of 8, so it is the item that lies across byte B32, an element ends at it - and 0 < k < the item's size)
+and beyond (wholly beyond, at B32 + an odd number of elements).  After each call the expected output ranges are read back and filled with 0xA5
 again, then the WHOLE of `dst` is compared with the guard pattern on the device (one comparison through an int64 view).  What is read from a
 high offset has a decoy of the same shape - real streams of the oracle, or pixels, of other content - at its alias; every decoy's result is
 asserted to differ from the true one, and the touched windows of `src` are compared with their host-side construction after the calls.  Where
 two arrays of one call lie in `src`, only one range can hold byte B32: such calls run twice, the straddling item in either array in turn.
 Every expectation is the existing definition (the oracle, then the models of qoi_amd/); every comparison is exact and covers whole outputs.
+That the decoy of every item of the newer filters and samplings resamples to other bytes than the true image is asserted without a GPU
+(test_the_decoys_of_the_newer_items_differ).
 
     call                                            moved past 2^32
     qoimi_encode_images                             pixel_offsets, stream_offsets
@@ -21,9 +24,15 @@ Every expectation is the existing definition (the oracle, then the models of qoi
     qoimi_encode_tiles                              pixel_offsets (f = 1, 3, 64; both modes)
     qoimi_decode_thumbnails                         stream_offsets, thumb_offsets
     qoimi_decode_crops / _resized / _bilinear / _warped                 stream_offsets, out_offsets
-    qoimi_decode_tensors (both filters), qoimi_decode_warped_tensors    stream_offsets, out_offsets (f16 and f32, HWC and CHW)
+    qoimi_decode_tensors, all six filters (tensor_area, tensor_tent, tensor_cubic, tensor_lanczos, tensor_nearest, tensor_mode)
+                                                    stream_offsets, out_offsets (FORMATS: every dtype - u8, f16, bf16, f32, i32, i64 - and
+                                                    every layout - HWC, CHW, HW - lies across byte B32 and beyond it at least once)
+    qoimi_decode_warped_tensors                     stream_offsets, out_offsets, three lists of items (below)
     qoimi_decode_crops_indexed / _resized_indexed / _bilinear_indexed / _warped_indexed
                                                     stream_offsets, out_offsets, the index built over the high pack
+    the warp calls (u8, tensors, indexed) take three lists: WARPS (bilinear items alone: warp_gather / tensor_warp), WARPS_NEAREST (nearest
+    and bilinear items, none bicubic: the nearest branch of the same kernels) and WARPS_CUBIC (bicubic, bilinear and nearest items in one
+    call: warp_bicubic_bytes / warp_bicubic_tensor serve all of them)
     qoimi_build_seek_index                          stream_offsets
     qoimi_seek_index_from_pixels                    pixel_offsets, stream_offsets
     qoimi_make_band_streams                         stream_offsets, out_offsets
@@ -43,12 +52,16 @@ import numpy as np
 import pytest
 
 from gpu_util import GuardedRegion
+from mode_cases import IMAGES as LABEL_MAPS
+from mode_cases import label_map
 from qoi_amd import bilinear, crops, resize, tensors, thumbs, tiles, warp
+from qoi_amd import mode as mode_filter
 from qoi_amd import pixelstats as ps
 from qoi_amd.imagediff import DIFF_DTYPE, DIFF_PIXELS, NONE, diff
-from qoi_amd.tensors import CHW, F16, F32, FILTER_AREA, FILTER_BILINEAR, HWC
+from qoi_amd.tensors import (BF16, CHW, F16, F32, FILTER_AREA, FILTER_BICUBIC, FILTER_BILINEAR, FILTER_LANCZOS, FILTER_MODE, FILTER_NEAREST, HW, HWC, I32, I64,
+                             U8)
 from seek_cases import cases as seek_cases
-from test_gpu_encode_packed import Batch, filled
+from test_gpu_encode_packed import filled, image
 from test_gpu_thumbnails import Pack, batch_of
 from test_packed_api import offsets as pack_offsets
 
@@ -289,9 +302,10 @@ def dst(arenas):
         arenas[1].t.fill_(GUARD)
 
 
-SHAPES = [(1, 1, 4), (1, 97, 4), (37, 29, 3), (130, 70, 4), (64, 48, 4)]
-TINY, COLUMN, RGB, SPRITE, NOISE = range(5)
-INTERVALS = [128, 128, 4, 8, 6]                       # seek rows: none, none, every 4th, 8th, 6th
+SHAPES = [(1, 1, 4), (1, 97, 4), (37, 29, 3), (130, 70, 4), (64, 48, 4), (37, 29, 3), (70, 45, 4)]
+TINY, COLUMN, RGB, SPRITE, NOISE, LABEL3, LABEL = range(7)
+INTERVALS = [128, 128, 4, 8, 6, 128, 128]             # seek rows: none, none, every 4th, 8th, 6th, none, none
+KINDS_OF = ["noise", "photo", "photo", "sprite_alpha", "noise"]
 
 
 def other(px):
@@ -299,10 +313,20 @@ def other(px):
     return flat(px) ^ 0x5A
 
 
+def pack_pixels():
+    """the images of the pack: the content classes of tests/test_gpu_encode_packed.py, then the two label maps of tests/mode_cases.py - three
+    classes in 3 channels, five in 4 - for the vote of FILTER_MODE: the other images have no majority anywhere.  Two, so that `layout` places
+    the stream of one of them below B32 and that of the other beyond it"""
+    return [image(k, w, h, ch, frame=i) for i, ((w, h, ch), k) in enumerate(zip(SHAPES, KINDS_OF))] + [label_map(*im).reshape(-1) for im in LABEL_MAPS]
+
+
 @pytest.fixture(scope="module")
 def pack(api, ctx, oracle):
-    """the shapes of the mixed packs with 3 and 4 channels; the decoy of every image and its stream by the oracle"""
-    p = Pack(ctx, oracle, Batch(api, oracle, SHAPES, ["noise", "photo", "photo", "sprite_alpha", "noise"]))
+    """the shapes of the mixed packs with 3 and 4 channels and a label map; the decoy of every image and its stream by the oracle"""
+    b = batch_of(api, oracle, SHAPES, pack_pixels())
+    b.want = [oracle.encode(px, w, h, ch) for px, (w, h, ch) in zip(b.px, SHAPES)]
+    b.lens = [len(s) for s in b.want]
+    p = Pack(ctx, oracle, b)
     p.streams = [p.host[o:o + n].copy() for o, n in zip(p.so, p.sizes)]
     assert [s.tobytes() for s in p.streams] == p.b.want
     p.decoy_px = [other(px) for px in p.b.px]
@@ -390,7 +414,8 @@ def test_strides_past_4gib(api, ctx, oracle, pack, src, dst):
 
 
 TILES = [(SPRITE, 0, 0, 130, 70, 1, 0), (SPRITE, 3, 5, 120, 64, 3, 1), (SPRITE, 0, 0, 130, 70, 64, 2), (RGB, 0, 0, 37, 29, 1, 3), (RGB, 1, 2, 30, 21, 3, 0),
-         (NOISE, 0, 0, 64, 48, 64, 0), (NOISE, 8, 1, 48, 40, 3, 2), (COLUMN, 0, 0, 1, 97, 1, 1), (COLUMN, 0, 1, 1, 96, 64, 0), (TINY, 0, 0, 1, 1, 1, 0)]
+         (NOISE, 0, 0, 64, 48, 64, 0), (NOISE, 8, 1, 48, 40, 3, 2), (COLUMN, 0, 0, 1, 97, 1, 1), (COLUMN, 0, 1, 1, 96, 64, 0), (TINY, 0, 0, 1, 1, 1, 0),
+         (LABEL3, 0, 2, 37, 27, 3, 1), (LABEL, 1, 0, 69, 45, 1, 2)]
 
 
 @gpu
@@ -420,37 +445,71 @@ def test_encode_tiles(ctx, oracle, pack, src, dst):
 
 
 # ------------------------------------------------------------------ 2: the gather family
-FACTORS = [1, 5, 3, 2, 64]
+FACTORS = [1, 5, 3, 2, 64, 3, 4]
 CROPS = [(SPRITE, 5, 17, 101, 50, 1), (RGB, 0, 9, 37, 20, 2), (NOISE, 8, 13, 33, 30, 3), (COLUMN, 0, 3, 1, 90, 0), (TINY, 0, 0, 1, 1, 0), (SPRITE, 0, 40, 130, 30, 0)]
 ITEMS = [(SPRITE, 0, 17, 130, 53, 43, 23, 1), (RGB, 0, 9, 37, 20, 50, 40, 2), (NOISE, 3, 13, 40, 30, 40, 30, 3), (COLUMN, 0, 0, 1, 97, 1, 13, 0),
          (TINY, 0, 0, 1, 1, 3, 2, 0), (SPRITE, 20, 20, 64, 32, 9, 5, 0)]
 WARPS = [warp.item(SPRITE, (20, 17, 100, 50), (33, 18), warp.rotation((100, 50), (33, 18), 30.0, 0.3), 0, FILL),
          warp.item(RGB, (3, 9, 30, 20), (17, 16), warp.rotation((30, 20), (17, 16), 30.0, 0.9), warp.REPLICATE, 0),
          warp.item(NOISE, (0, 13, 64, 35), (70, 40), warp.IDENTITY, 0, FILL), warp.item(TINY, (0, 0, 1, 1), (2, 2), warp.IDENTITY, warp.REPLICATE, 0)]
+# The second and third warp lists.  WARPS_CUBIC: bicubic, bilinear and nearest items in ONE call - one bicubic item sends the whole call to
+# warp_bicubic_bytes / warp_bicubic_tensor, which then serve the items that are not bicubic as well.  WARPS_NEAREST: no bicubic item - the call
+# stays with warp_gather / tensor_warp and takes their nearest branch.  In both every image with seek rows has an item that begins below one.
+WARPS_CUBIC = [warp.item(SPRITE, (20, 17, 100, 50), (33, 18), warp.rotation((100, 50), (33, 18), 30.0, 0.3), warp.BICUBIC, FILL),
+               warp.item(RGB, (3, 9, 30, 20), (17, 16), warp.rotation((30, 20), (17, 16), 30.0, 0.9), warp.BICUBIC | warp.REPLICATE, 0),
+               warp.item(NOISE, (0, 13, 64, 35), (70, 40), warp.IDENTITY, warp.NEAREST, FILL),
+               warp.item(LABEL, (5, 3, 63, 41), (33, 18), warp.rotation((63, 41), (33, 18), 30.0, 0.9), warp.NEAREST | warp.REPLICATE, 0),
+               warp.item(SPRITE, (0, 40, 130, 30), (41, 29), warp.rotation((130, 30), (41, 29), -20.0, 0.4), 0, FILL),
+               warp.item(NOISE, (8, 13, 33, 30), (23, 40), warp.rotation((33, 30), (23, 40), 90.0, 0.8), warp.REPLICATE, 0),
+               warp.item(TINY, (0, 0, 1, 1), (2, 2), warp.IDENTITY, warp.BICUBIC | warp.REPLICATE, 0),
+               warp.item(COLUMN, (0, 3, 1, 90), (5, 31), warp.rotation((1, 90), (5, 31), 10.0, 0.4), warp.BICUBIC, FILL),
+               warp.item(LABEL3, (2, 1, 33, 25), (40, 30), warp.rotation((33, 25), (40, 30), -15.0, 1.3), warp.NEAREST, FILL)]
+WARPS_NEAREST = [warp.item(SPRITE, (20, 17, 100, 50), (33, 18), warp.rotation((100, 50), (33, 18), 30.0, 0.3), warp.NEAREST, FILL),
+                 warp.item(RGB, (3, 9, 30, 20), (17, 16), warp.rotation((30, 20), (17, 16), 30.0, 0.9), warp.NEAREST | warp.REPLICATE, 0),
+                 warp.item(NOISE, (0, 13, 64, 35), (70, 40), warp.IDENTITY, 0, FILL),
+                 warp.item(LABEL, (5, 3, 63, 41), (66, 36), warp.rotation((63, 41), (66, 36), -30.0, 1.8), warp.NEAREST, FILL),
+                 warp.item(TINY, (0, 0, 1, 1), (2, 2), warp.IDENTITY, warp.NEAREST | warp.REPLICATE, 0),
+                 warp.item(COLUMN, (0, 3, 1, 90), (5, 31), warp.rotation((1, 90), (5, 31), 10.0, 0.4), warp.NEAREST, FILL),
+                 warp.item(LABEL3, (2, 1, 33, 25), (40, 30), warp.rotation((33, 25), (40, 30), -15.0, 1.3), warp.NEAREST | warp.REPLICATE, 0)]
+assert {it[7] for it in WARPS} == {0, warp.REPLICATE} and not any(it[7] & warp.BICUBIC for it in WARPS_NEAREST)
+assert {it[7] & ~warp.REPLICATE for it in WARPS_CUBIC} == {0, warp.NEAREST, warp.BICUBIC} and {it[7] & ~warp.REPLICATE for it in WARPS_NEAREST} == {0, warp.NEAREST}
+assert {warp.BICUBIC, warp.BICUBIC | warp.REPLICATE, warp.NEAREST, warp.NEAREST | warp.REPLICATE} <= {it[7] for it in WARPS_CUBIC}
+# The items of the newer filters of qoimi_decode_tensors: ITEMS whole - no filter's `size` rejects one of them: the largest reduction is
+# 97 to 13 (the filters stop at 16), the largest side 130 (they stop at 16384) - and rectangles of the label maps, where FILTER_MODE has
+# majorities and ties in cells of 1 to 16 x 15 pixels (the items of tests/mode_cases.py among them)
+LABEL_ITEMS = [(LABEL, 0, 0, 70, 45, 16, 11, 1), (LABEL, 3, 5, 31, 23, 7, 20, 2), (LABEL, 1, 0, 64, 45, 4, 3, 0), (LABEL3, 0, 0, 37, 29, 9, 7, 3), (LABEL3, 0, 0, 37, 29, 50, 7, 0)]
+FILTERS = {"resized": FILTER_AREA, "bilinear": FILTER_BILINEAR, "bicubic": FILTER_BICUBIC, "lanczos": FILTER_LANCZOS, "nearest": FILTER_NEAREST, "mode": FILTER_MODE}
+NEWER = {"bicubic": ITEMS + LABEL_ITEMS, "lanczos": ITEMS + LABEL_ITEMS, "nearest": ITEMS + LABEL_ITEMS, "mode": ITEMS + LABEL_ITEMS,
+         "warped_cubic": WARPS_CUBIC, "warped_nearest": WARPS_NEAREST}
 _MODELS = {}
+
+
+def resample(decoded, kind, it, och, mode):
+    """the u8 result of one item by the definition; decoded(i, och) is the oracle's decode of image i as uint8[h, w, och]"""
+    if kind == "mode":                                                # the vote is over the 4-channel decode; och 3 drops alpha afterwards
+        return mode_filter.mode(decoded(it[0], 4), it[1:5], it[5:7], it[7], och=och)
+    D = decoded(it[0], och)
+    if kind == "thumbnails":
+        return thumbs.thumbnail(D, it[1], mode)
+    if kind == "crops":
+        return crops.crop(D, it[1:5], it[5])
+    if kind.startswith("warped"):
+        _, x, y, cw, rh, ow, oh, flags, a, b, d, e, fill, _, c, f = it
+        return warp.warp(D, (x, y, cw, rh), (ow, oh), (a, b, c, d, e, f), flags, fill, mode)
+    return tensors.tensors(D, it[1:5], it[5:7], it[7], FILTERS[kind], mode)      # (U8, HWC: the filter's own bytes)
 
 
 def model(p, kind, it, och, mode):
     """the u8 result of one item by the definition: computed once, shared, never changed"""
     key = (kind, tuple(it), och, mode)
     if key not in _MODELS:
-        D = p.decoded(it[0], och)
-        if kind == "thumbnails":
-            P = thumbs.thumbnail(D, it[1], mode)
-        elif kind == "crops":
-            P = crops.crop(D, it[1:5], it[5])
-        elif kind == "warped":
-            _, x, y, cw, rh, ow, oh, flags, a, b, d, e, fill, _, c, f = it
-            P = warp.warp(D, (x, y, cw, rh), (ow, oh), (a, b, c, d, e, f), flags, fill, mode)
-        else:
-            P = (resize.resize if kind == "resized" else bilinear.bilinear)(D, it[1:5], it[5:7], it[7], mode)
-        P = np.ascontiguousarray(P)
+        P = np.ascontiguousarray(resample(p.decoded, kind, it, och, mode))
         P.setflags(write=False)
         _MODELS[key] = P
     return _MODELS[key]
 
 
-GATHERS = {"crops": CROPS, "resized": ITEMS, "bilinear": ITEMS, "warped": WARPS}
+GATHERS = {"crops": CROPS, "resized": ITEMS, "bilinear": ITEMS, "warped": WARPS, "warped_cubic": WARPS_CUBIC, "warped_nearest": WARPS_NEAREST}
 
 
 def gather_call(ctx, kind, streams, so, p, och, mode, index=None):
@@ -460,14 +519,48 @@ def gather_call(ctx, kind, streams, so, p, och, mode, index=None):
         if index is None:
             return lambda out, oo: ctx.decode_crops(streams, so, p.sizes, p.descs, och, items, out, oo)
         return lambda out, oo: ctx.decode_crops_indexed(streams, so, p.sizes, p.descs, och, items, out, oo, *index)
-    f = getattr(ctx, "decode_" + kind + ("_indexed" if index is not None else ""))
+    f = getattr(ctx, "decode_" + kind.split("_")[0] + ("_indexed" if index is not None else ""))
     return lambda out, oo: f(streams, so, p.sizes, p.descs, och, items, mode, out, oo, *(index or ()))
+
+
+def test_the_decoys_of_the_newer_items_differ(oracle):
+    """(no GPU) At the alias of a stream beyond B32 stands the oracle's stream of the decoy pixels.  For every item of the newer filters and
+    warp samplings, at every channel count and alpha mode its calls use: the decoy's decode resamples to other bytes than the true decode,
+    so a reader that dropped the high half of a stream offset fails a comparison whichever image lies beyond B32."""
+    px = pack_pixels()
+    decodes = {}
+
+    def decoder(pixels):
+        def decoded(i, och):
+            if (id(pixels), i, och) not in decodes:
+                w, h, ch = SHAPES[i]
+                decodes[(id(pixels), i, och)] = oracle.decode(oracle.encode(pixels[i], w, h, ch), och)[0].reshape(h, w, och)
+            return decodes[(id(pixels), i, och)]
+        return decoded
+
+    true, decoy = decoder(px), decoder([other(a) for a in px])
+    assert all(np.array_equal(true(i, ch).reshape(-1), px[i]) for i, (_, _, ch) in enumerate(SHAPES))
+    checked = 0
+    for kind, items in NEWER.items():
+        combos = {(och, mode) for _, _, och, mode in FORMATS[kind]} | ({(4, 1), (3, 0)} if kind in GATHERS else set())
+        assert {it[0] for it in items} == set(range(len(SHAPES)))                      # whichever image straddles or lies beyond: it has an item
+        for och, mode in sorted(combos):
+            for j, it in enumerate(items):
+                assert not np.array_equal(resample(true, kind, it, och, mode), resample(decoy, kind, it, och, mode)), (kind, och, mode, j)
+                checked += 1
+    assert checked >= 4 * 2 * len(ITEMS + LABEL_ITEMS) + 2 * (len(WARPS_CUBIC) + len(WARPS_NEAREST))
+
+
+def assert_streams_high(so, sizes):
+    """stream_offsets of the call: one stream lies across byte B32, others begin beyond it"""
+    assert any(o >= B32 for o in so) and any(o < B32 < o + n for o, n in zip(so, sizes))
 
 
 @gpu
 def test_u8_gathers(ctx, oracle, pack, src, dst):
     p = pack
     so = place_pack(src, oracle, p)
+    assert_streams_high(so, p.sizes)
     base = src.t.data_ptr()
     for och, mode in ((4, 1), (3, 0)):
         want = [model(p, "thumbnails", (i, f), och, mode) for i, f in enumerate(FACTORS)]
@@ -477,21 +570,46 @@ def test_u8_gathers(ctx, oracle, pack, src, dst):
     src.check()
 
 
+OLDER_FORMATS = ((F16, HWC, 4, 1), (F32, CHW, 3, 0), (F16, CHW, 3, 0), (F32, HWC, 4, 1))
+# (dtype, layout, output channels, alpha mode) of the calls of each kind; every call has a straddling output and outputs beyond B32.  All
+# filters and both warp kernels take every dtype with every layout and either channel count (qoi_host_tensor.hip: tensor_format_wrong looks
+# at the format alone; the integer dtypes want scale 1 and bias +0), so the formats are spread: four a kind, and over the newer kinds every
+# dtype and every layout
+FORMATS = {"resized": OLDER_FORMATS, "bilinear": OLDER_FORMATS, "warped": OLDER_FORMATS,
+           "bicubic": ((F16, HWC, 4, 1), (F32, CHW, 3, 0), (BF16, HW, 4, 0), (I64, CHW, 3, 0)),
+           "lanczos": ((BF16, HWC, 4, 1), (F32, CHW, 3, 0), (I32, HW, 3, 0), (U8, HWC, 4, 0)),
+           "nearest": ((I64, HW, 4, 0), (I32, CHW, 3, 0), (U8, HWC, 3, 0), (F16, CHW, 4, 1)),
+           "mode": ((I64, HW, 3, 0), (I32, HWC, 4, 0), (U8, CHW, 4, 1), (BF16, HWC, 3, 0)),
+           "warped_cubic": ((F16, HWC, 4, 1), (F32, CHW, 3, 0), (I64, HW, 4, 1), (U8, CHW, 3, 0)),
+           "warped_nearest": ((I64, HW, 4, 0), (I32, CHW, 3, 0), (BF16, HWC, 4, 1), (U8, HW, 3, 0))}
+assert {f[0] for k in ("bicubic", "lanczos", "nearest", "mode") for f in FORMATS[k]} == {U8, F16, BF16, F32, I32, I64}
+assert {f[0] for k in ("warped_cubic", "warped_nearest") for f in FORMATS[k]} == {U8, F16, BF16, F32, I32, I64}
+assert all({f[1] for f in FORMATS[k]} == {HWC, CHW, HW} for k in NEWER) and all({f[2] for f in FORMATS[k]} == {3, 4} for k in FORMATS)
+
+
+def format_of(dtype, order):
+    return tensors.fmt(dtype, order) if dtype in (U8, I32, I64) else (dtype, order, *IMAGENET)
+
+
 @gpu
-@pytest.mark.parametrize("kind", ["resized", "bilinear", "warped"])
+@pytest.mark.parametrize("kind", list(FORMATS))
 def test_tensors(ctx, oracle, pack, src, dst, kind):
-    p, items = pack, GATHERS[kind]
+    p, items = pack, NEWER[kind] if kind in NEWER else GATHERS[kind]
     so = place_pack(src, oracle, p)
     base = src.t.data_ptr()
-    for dtype, order, och, mode in ((F16, HWC, 4, 1), (F32, CHW, 3, 0), (F16, CHW, 3, 0), (F32, HWC, 4, 1)):
-        f = (dtype, order, *IMAGENET)
+    assert_streams_high(so, p.sizes)
+    for dtype, order, och, mode in FORMATS[kind]:
+        f = format_of(dtype, order)
         want = [tensors.convert(model(p, kind, it, och, mode), f) for it in items]
-        if kind == "warped":
+        if kind.startswith("warped"):
             call = lambda out, oo: ctx.decode_warped_tensors(base, so, p.sizes, p.descs, och, items, mode, f, out, oo)      # noqa: E731
         else:
-            call = lambda out, oo: ctx.decode_tensors(base, so, p.sizes, p.descs, och, items, FILTER_AREA if kind == "resized" else FILTER_BILINEAR,      # noqa: E731
-                                                      mode, f, out, oo)
-        into_dst(dst, want, call, (kind, "tensors", dtype, order, och), elem=tensors.ELEM[dtype])
+            call = lambda out, oo: ctx.decode_tensors(base, so, p.sizes, p.descs, och, items, FILTERS[kind], mode, f, out, oo)      # noqa: E731
+        elem = tensors.elem(dtype)
+        oo = layout([flat(w).size for w in want], elem)                # what into_dst lays out: asserted here where a reviewer looks for it
+        assert any(o >= B32 for o in oo) and any(o < B32 < o + flat(w).size and (B32 - o) % elem == 0 and (B32 - o) // elem % 2 == 1 for o, w in zip(oo, want))
+        into_dst(dst, want, call, (kind, "tensors", dtype, order, och), elem=elem)
+        assert ctx.tensor_stats()[:2] == (1, 1)
     src.check()
 
 
@@ -502,10 +620,11 @@ def test_indexed_gathers(ctx, oracle, pack, src, dst):
     from qoi_amd import seekindex as si
     p = pack
     so = place_pack(src, oracle, p)
+    assert_streams_high(so, p.sizes)
     base = src.t.data_ptr()
     points, firsts = ctx.build_seek_index(base, so, p.sizes, p.descs, INTERVALS)
     want = [si.points(p.streams[i].tobytes(), w, h, K, p.decoded(i, 4)) for i, ((w, h, _), K) in enumerate(zip(SHAPES, INTERVALS))]
-    assert [len(x) for x in want] == [0, 0, 7, 8, 7] and firsts == [0, 0, 0, 7, 15] and points.tobytes() == np.concatenate(want).tobytes()
+    assert [len(x) for x in want] == [0, 0, 7, 8, 7, 0, 0] and firsts == [0, 0, 0, 7, 15, 22, 22] and points.tobytes() == np.concatenate(want).tobytes()
     assert all(any(it[0] == i and it[2] >= INTERVALS[i] for it in items) for items in GATHERS.values() for i in (RGB, SPRITE, NOISE))
     index = (INTERVALS, points, firsts)
     for och, mode in ((4, 1), (3, 0)):

@@ -12,8 +12,11 @@ from qoi_amd.packplan import slot
 from qoi_amd.tensors import CHW, F16, F32, HW, HWC, I32, U8
 from qoi_amd.warp import ALPHA_WEIGHTED, BICUBIC, NEAREST, ONE, PLAIN, REPLICATE
 from test_gpu_labels import IMAGENET, run as run_tensors
+from test_gpu_encode_packed import Batch
 from test_gpu_thumbnails import Pack, batch_of
+from test_gpu_warp import assert_items
 from test_gpu_warp import run as run_warp
+from test_gpu_warp import want as want_warp
 
 pytestmark = pytest.mark.gpu
 GUARD = 0xA5
@@ -221,3 +224,64 @@ def test_indexed_band_at_the_bottom(ctx, pack):
     assert_bytes(p, got, items, 4, ALPHA_WEIGHTED, "indexed")
     assert all(np.array_equal(a, b) for a, b in zip(plain, got))
     assert ctx.warp_stats()[2] < plain_stats[2]                          # the bands are shorter than the images' heads
+
+
+# ------------------------------------------------------------------ the tile walk and positions past 2^32 (the counterparts of test_gpu_warp.py)
+SAMPLINGS = (BICUBIC, BICUBIC | REPLICATE, NEAREST, 0)
+
+
+def test_tile_walk_regimes(api, ctx, oracle, pack):
+    """(qoi_dev.h: walk_tiles, as warp_cubic_walk calls it) a launch with ONE table entry, a bicubic one, its 12 tiles spread over as many
+    workgroups; and more tiles than the grid's clamp of 8 workgroups per compute unit - 37 more items of one tile each, their samplings in
+    turn bicubic with fill, bicubic with REPLICATE, nearest and bilinear - so that a workgroup takes two tiles and steps from an entry of one
+    sampling to an entry of another.  The 3-byte outputs stand back to back at an odd front: neighbours share aligned words."""
+    import torch
+    one = warp.item(BIG, (0, 0, 130, 70), (61, 47), warp.rotation((130, 70), (61, 47), 30.0, 0.5), BICUBIC, FILL)
+    assert warp.tiles(61, 47) == 12 and warp.tiles(1, 1) == 1
+    assert_bytes(pack, run_warp(ctx, pack, 4, [one], ALPHA_WEIGHTED), [one], 4, ALPHA_WEIGHTED, "one entry")
+    assert ctx.warp_stats()[:2] == (1, 1)
+    n = 8 * torch.cuda.get_device_properties(0).multi_processor_count + 37
+    p = Pack(ctx, oracle, Batch(api, oracle, [(8, 8, 4)], ["noise"]))
+    items = [warp.item(0, (j % 7, (j // 7) % 7, 2, 2), (1, 1), (ONE, 0, (j % 5) * 9000, 0, ONE, (j % 3) * 20000), SAMPLINGS[j & 3], FILL) for j in range(n)]
+    assert all(items[j][7] != items[j + 1][7] for j in range(n - 1)) and {it[7] for it in items} == set(SAMPLINGS)
+    for channels, mode in ((3, PLAIN), (4, ALPHA_WEIGHTED)):
+        assert_items(p, run_warp(ctx, p, channels, items, mode, front=64 + 5), items, channels, mode, ("many", channels))
+        assert ctx.warp_stats()[:2] == (1, 1)
+
+
+def wide_maps():
+    """the three maps of test_gpu_warp.py: test_positions_past_32_bits over the 33000 x 3 image - the 9 columns from 32990 on, the same turned
+    by 180 degrees, an enlargement by 3 and 2 that begins half a row above the image - and a fourth whose 20 output columns walk a quarter
+    of a pixel each across the right edge: k0 goes from 32997 to 33001, so that in turn k0 + 2, k0 + 1, k0 and k0 - 1 leave the rectangle"""
+    return [((9, 3), (ONE, 0, 2 * 32990 * ONE, 0, ONE, 0)), ((9, 3), (-ONE, 0, 2 * 32999 * ONE + 777, 0, -ONE, 2 * 3 * ONE - 999)),
+            ((40, 5), (ONE // 3, 0, 2 * 32985 * ONE + 4321, 0, ONE // 2, -ONE)), ((20, 3), (ONE // 4, 0, 2 * 32997 * ONE + ONE, 0, ONE, 0))]
+
+
+def test_positions_past_32_bits(api, ctx, oracle):
+    """an image of 33000 x 3, a rectangle over all its columns: Px passes 2**32 on the device (column 32768 lies at 2**32 + 2**16).  Every map
+    with BICUBIC and with BICUBIC | REPLICATE - warp_cubic_axis tests the border on the 64-bit index before it narrows, in the fill form and
+    in the clamp form - and with NEAREST; the nearest items also alone, in a call that stays with warp_gather.  As bytes and as tensors."""
+    cw = 33000
+    p = Pack(ctx, oracle, Batch(api, oracle, [(cw, 3, 4)], ["noise"]))
+    rect = (0, 0, cw, 3)
+    cubic = [warp.item(0, rect, out, m, flags, FILL) for out, m in wide_maps() for flags in (BICUBIC, BICUBIC | REPLICATE)]
+    near = [warp.item(0, rect, out, m, NEAREST | (j & 1), FILL) for j, (out, m) in enumerate(wide_maps())] + [warp.item(0, rect, (20, 3), wide_maps()[3][1], NEAREST, FILL)]
+    assert all(it[14] > 2 ** 32 for it in cubic + near)
+    # the border item: an output column whose k0 - 1 is the last column of the rectangle while k0 + 2 lies outside, and every stage before it
+    a, _, c, _, _, _ = wide_maps()[3][1]
+    k0 = [(a * (2 * X + 1) + c - ONE) >> 17 for X in range(20)]
+    assert sorted(set(k0)) == [32997, 32998, 32999, 33000, 33001] and any(k - 1 == cw - 1 and k + 2 >= cw for k in k0) and any(k + 2 == cw for k in k0)
+    for items, what in ((cubic + near, "bicubic and nearest"), (near, "nearest alone")):
+        for channels, mode in ((4, ALPHA_WEIGHTED), (3, PLAIN)):
+            got = run_warp(ctx, p, channels, items, mode, front=64 + 1)
+            assert_items(p, got, items, channels, mode, ("wide", what, channels))
+            assert ctx.warp_stats()[:2] == (1, 1)
+        f = (F16, CHW, *IMAGENET) if items is near else tensors.fmt(I32, HWC)
+        got = run_tensors(ctx, p, "warp", 4, items, ALPHA_WEIGHTED, f)
+        for j, it in enumerate(items):
+            w = tensors.convert(want_warp(p, it, 4, ALPHA_WEIGHTED).reshape(it[6], it[5], 4), f).view(np.uint8).reshape(-1)
+            assert got[j].size == w.size and np.array_equal(got[j], w), ("wide tensors", what, j)
+    # the first map is a crop: the rectangle's columns from 32990 on, byte for byte, under either sampling
+    crop = p.decoded(0, 4)[:, 32990:32999].reshape(-1)
+    got = run_warp(ctx, p, 4, [cubic[0], cubic[1], near[0]], PLAIN)
+    assert all(np.array_equal(g, crop) for g in got)
