@@ -1,48 +1,13 @@
 // bilinear_host.cpp — the arithmetic of qoimi_decode_bilinear (qoi_amd/csrc/qoi_bilinear_core.h) compiled for the host: the walk of
-// bilinear_filter over an item, tile by tile and lane by lane, over a synthetic staging array and a memory functor that checks and counts every
-// access, so that tests/test_bilinear_core_host.py can compare it with the Python model without a GPU.  The sums of a pixel's lanes are added
+// bilinear_filter over an item, tile by tile and lane by lane, over a synthetic staging array and the checking memory functors of host_mem.h
+// (StagedMem, SynthMem), so that tests/test_bilinear_core_host.py can compare it with the Python model without a GPU.  The sums of a pixel's lanes are added
 // here where the kernel takes its butterfly steps.  bilinear_host_pixel computes single output pixels of geometries no array can hold: its
 // functor makes a staged pixel from its index.  With -DBILINEAR_HOST_MAIN the same source is a stand-alone program that walks a grid of items
 // against a plain loop over all taps (the test builds it with -fsanitize=address,undefined and runs it).  Not part of the library.
-#include <stddef.h>
-#include <stdint.h>
-
 #include "../../qoi_amd/csrc/qoi_bilinear_core.h"
+#include "host_mem.h"
 
 namespace {
-
-// Addresses are virtual: `base` (a multiple of 16) stands for out[0], so the test chooses every alignment of q.
-struct HostMem {
-    const uint32_t* stage; uint64_t stage_px;
-    uint8_t* out; uint8_t* writes; uint64_t out_len, base;
-    long long* bad;                      // accesses outside an array or not naturally aligned
-    long long* loads;
-    uint32_t load(uint64_t i) const {
-        ++*loads;
-        if (i >= stage_px) { ++*bad; return 0u; }
-        return stage[i];
-    }
-    void put(uint64_t a, uint32_t v, uint32_t bytes) const {
-        if (a % bytes != 0u || a < base || a - base + bytes > out_len) { ++*bad; return; }
-        for (uint32_t k = 0; k < bytes; ++k) { out[a - base + k] = (uint8_t)(v >> (8u * k)); ++writes[a - base + k]; }
-    }
-    void store1(uint64_t a, uint32_t v) const { put(a, v, 1u); }
-    void store4(uint64_t a, uint32_t v) const { put(a, v, 4u); }
-};
-
-// The staged pixel at index i is bilinear_host_synth(i); loads from stage_px on are counted as bad.  One store4 lands in *px.
-struct SynthMem {
-    uint64_t stage_px; uint32_t* px; long long* bad; long long* loads; long long* stores;
-    uint32_t load(uint64_t i) const {
-        ++*loads;
-        if (i >= stage_px) { ++*bad; return 0u; }
-        uint64_t z = (i + 1u) * 0x9E3779B97F4A7C15ull;
-        z ^= z >> 29;
-        return (uint32_t)(z >> 16);
-    }
-    void store1(uint64_t, uint32_t) const { ++*bad; }
-    void store4(uint64_t a, uint32_t v) const { ++*stores; if (a % 4u != 0u) ++*bad; *px = v; }
-};
 
 template <class Mem>
 void pixel_sums(const Mem& mem, const qoimi::ResizeGeom& g, uint32_t X, uint32_t Y, bool wgt, qoimi::BilinearSums& sum) {
@@ -71,7 +36,7 @@ long long bilinear_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w
                             uint32_t flags, uint32_t och, int weighted, uint64_t q, uint64_t base, uint8_t* out, uint8_t* writes, uint64_t out_len,
                             unsigned long long* tiles_walked) {
     long long bad = 0, loads = 0;
-    const HostMem mem = {stage, stage_px, out, writes, out_len, base, &bad, &loads};
+    const hostmem::StagedMem mem = {{out, writes, out_len, base, &bad}, stage, stage_px, &loads};
     const qoimi::ResizeGeom g = {w, x, y, cw, rh, ow, oh, flags};
     uint32_t lg, c;
     qoimi::bilinear_split(cw, ow, lg, c);
@@ -87,7 +52,7 @@ long long bilinear_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w
             qoimi::bilinear_finish(mem, g, q, och, wgt, X, Y, sum);
         }
     if (tiles_walked) *tiles_walked = tiles;
-    return bad ? -1 - bad : loads;
+    return hostmem::checked(bad, loads);
 }
 
 // Output pixel (X, Y) of the unflipped result of an item over synthetic staged pixels (rows of w, stage_px of them), 4 channels, written as
@@ -95,7 +60,7 @@ long long bilinear_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w
 long long bilinear_host_pixel(uint64_t stage_px, uint32_t w, uint32_t x, uint32_t y, uint32_t cw, uint32_t rh, uint32_t ow, uint32_t oh, int weighted,
                               uint32_t X, uint32_t Y, uint32_t* px, uint64_t* sums) {
     long long bad = 0, loads = 0, stores = 0;
-    const SynthMem mem = {stage_px, px, &bad, &loads, &stores};
+    const hostmem::SynthMem mem = {stage_px, px, &bad, &loads, &stores};
     const qoimi::ResizeGeom g = {w, x, y, cw, rh, ow, oh, 0u};
     qoimi::BilinearSums sum;
     pixel_sums(mem, g, X, Y, weighted != 0, sum);
@@ -104,15 +69,10 @@ long long bilinear_host_pixel(uint64_t stage_px, uint32_t w, uint32_t x, uint32_
     for (int k = 0; k < 3; ++k) sums[4 + k] = sum.v.W[k];
     sums[7] = sum.wx; sums[8] = sum.wy;
     if (stores != 1) ++bad;
-    return bad ? -1 - bad : loads;
+    return hostmem::checked(bad, loads);
 }
 
-uint32_t bilinear_host_synth(uint64_t i) {
-    long long bad = 0, loads = 0, stores = 0;
-    uint32_t px = 0;
-    const SynthMem mem = {~0ull, &px, &bad, &loads, &stores};
-    return mem.load(i);
-}
+uint32_t bilinear_host_synth(uint64_t i) { return hostmem::SynthMem::synth(i); }
 
 void bilinear_host_split(uint32_t cw, uint32_t ow, uint32_t* lg, uint32_t* c) { qoimi::bilinear_split(cw, ow, *lg, *c); }
 uint32_t bilinear_host_taps(uint32_t cw, uint32_t ow) { return qoimi::bilinear_taps(cw, ow); }
@@ -126,7 +86,6 @@ unsigned long long bilinear_host_tiles(uint32_t cw, uint32_t ow, uint32_t oh) { 
 
 #ifdef BILINEAR_HOST_MAIN
 #include <stdio.h>
-#include <vector>
 
 static uint64_t tent(uint64_t Z, uint64_t k, uint64_t n_src, uint64_t n_out) {
     const uint64_t rad = 2 * (n_src > n_out ? n_src : n_out), o = (2 * Z + 1) * n_src, c = (2 * k + 1) * n_out, d = o > c ? o - c : c - o;
@@ -153,16 +112,14 @@ int main() {
                             if (i % 5u == 0u) stage[i] &= 0x00FFFFFFu;                       // some transparent pixels
                         }
                         const uint64_t B = (uint64_t)ow * oh * och;
-                        std::vector<uint8_t> out(guard + a + B + guard, 0xA5), writes(out.size(), 0);
+                        std::vector<uint8_t> out(guard + a + B + guard, hostmem::kGuard), writes(out.size(), 0);
                         const uint64_t q = base + guard + a;
                         unsigned long long tiles = 0;
                         const long long rc = bilinear_host_run(stage.data(), stage.size(), w, x, y, cw, rh, ow, oh, flags, och, weighted, q, base, out.data(),
                                                                writes.data(), out.size(), &tiles);
                         if (rc < 0) { printf("bad access: och %u a %u flags %u %ux%u -> %ux%u: %lld\n", och, a, flags, cw, rh, ow, oh, rc); return 1; }
-                        for (size_t i = 0; i < out.size(); ++i) {
-                            const bool inside = i >= guard + a && i < guard + a + B;
-                            if (writes[i] != (inside ? 1 : 0) || (!inside && out[i] != 0xA5)) { printf("byte %zu written %u times\n", i, writes[i]); return 1; }
-                        }
+                        const long long off = hostmem::first_miswritten(out, writes, guard + a, B);
+                        if (off >= 0) { printf("byte %lld written %u times\n", off, writes[off]); return 1; }
                         for (uint32_t Y = 0; Y < oh; ++Y)
                             for (uint32_t X = 0; X < ow; ++X) {
                                 uint64_t N[4] = {0, 0, 0, 0}, M[3] = {0, 0, 0}, Wx = 0, Wy = 0;
@@ -176,11 +133,10 @@ int main() {
                                         for (int ch = 0; ch < 3; ++ch) M[ch] += wt * ((px >> (8 * ch)) & 255u) * (px >> 24);
                                     }
                                 const uint64_t D = Wx * Wy;
-                                const uint32_t xo = (flags & 1u) ? ow - 1u - X : X, yo = (flags & 2u) ? oh - 1u - Y : Y;
                                 for (uint32_t ch = 0; ch < och; ++ch) {
                                     uint64_t v = (N[ch] + D / 2) / D;
                                     if (weighted && och == 4u && ch < 3u && N[3] > 0) v = (M[ch] + N[3] / 2) / N[3];
-                                    if (out[guard + a + ((size_t)yo * ow + xo) * och + ch] != (uint8_t)v) {
+                                    if (out[guard + a + hostmem::element_index(false, flags, ow, oh, och, X, Y, ch)] != (uint8_t)v) {
                                         printf("wrong byte: och %u mode %d a %u flags %u %ux%u -> %ux%u at (%u, %u).%u\n", och, weighted, a, flags, cw, rh, ow, oh, X, Y, ch);
                                         return 1;
                                     }

@@ -1,37 +1,9 @@
 // crop_host.cpp — the item arithmetic of qoimi_decode_crops (qoi_amd/csrc/qoi_crop_core.h) compiled for the host: the item loop of crop_gather,
-// tile by tile, over a synthetic staging array and a memory functor that checks and counts every access, so that tests/test_crop_core_host.py
+// tile by tile, over a synthetic staging array and the checking memory functor of host_mem.h (StagedMem), so that tests/test_crop_core_host.py
 // can compare it with the Python model without a GPU.  With -DCROP_HOST_MAIN the same source is a stand-alone program that walks a grid of
 // crops against a plain per-byte loop (the test builds it with -fsanitize=address,undefined and runs it).  Not part of the library.
-#include <stddef.h>
-#include <stdint.h>
-
 #include "../../qoi_amd/csrc/qoi_crop_core.h"
-
-namespace {
-
-// Addresses are virtual: `base` (a multiple of 16) stands for out[0], so the test chooses every alignment of q.
-struct HostMem {
-    const uint32_t* stage; uint64_t stage_px;
-    uint8_t* out; uint8_t* writes; uint64_t out_len, base;
-    long long* bad;                      // accesses outside an array or not naturally aligned
-    uint32_t load(uint64_t i) const {
-        if (i >= stage_px) { ++*bad; return 0u; }
-        return stage[i];
-    }
-    void put(uint64_t a, uint32_t v, uint32_t bytes) const {
-        if (a % bytes != 0u || a < base || a - base + bytes > out_len) { ++*bad; return; }
-        for (uint32_t k = 0; k < bytes; ++k) { out[a - base + k] = (uint8_t)(v >> (8u * k)); ++writes[a - base + k]; }
-    }
-    void store1(uint64_t a, uint32_t v) const { put(a, v, 1u); }
-    void store2(uint64_t a, uint32_t v) const { put(a, v, 2u); }
-    void store4(uint64_t a, uint32_t v) const { put(a, v, 4u); }
-    void store16(uint64_t a, const uint32_t (&W)[4]) const {
-        if (a % 16u != 0u) { ++*bad; return; }
-        for (uint32_t k = 0; k < 4u; ++k) put(a + 4u * k, W[k], 4u);
-    }
-};
-
-}  // namespace
+#include "host_mem.h"
 
 extern "C" {
 
@@ -39,8 +11,8 @@ extern "C" {
 // writes[i] counts the stores to out[i].  Returns the items walked, or -1 - the number of bad accesses if there was one.
 long long crop_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w, uint32_t x, uint32_t y, uint32_t cw, uint32_t ch, uint32_t flags,
                         uint32_t och, uint64_t q, uint64_t base, uint8_t* out, uint8_t* writes, uint64_t out_len) {
-    long long bad = 0, walked = 0;
-    const HostMem mem = {stage, stage_px, out, writes, out_len, base, &bad};
+    long long bad = 0, walked = 0, loads = 0;                            // (nobody reads the loads: an item loads what it stores)
+    const hostmem::StagedMem mem = {{out, writes, out_len, base, &bad}, stage, stage_px, &loads};
     const qoimi::CropRect g = {w, x, y, cw, ch, flags};
     const uint32_t B = cw * ch * och;
     const uint64_t items = qoimi::crop_items(q, B), tiles = qoimi::crop_tiles(q, B);
@@ -52,7 +24,7 @@ long long crop_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w, ui
             else qoimi::crop_item<4u>(mem, g, q, B, (uint32_t)k);
             ++walked;
         }
-    return bad ? -1 - bad : walked;
+    return hostmem::checked(bad, walked);
 }
 
 unsigned long long crop_host_items(uint64_t q, uint64_t B) { return qoimi::crop_items(q, B); }
@@ -62,7 +34,6 @@ unsigned long long crop_host_tiles(uint64_t q, uint64_t B) { return qoimi::crop_
 
 #ifdef CROP_HOST_MAIN
 #include <stdio.h>
-#include <vector>
 
 // Every och, alignment, flag value and the small widths and heights, plus one crop of more than 256 items, in arrays of exactly the size the
 // walk may touch: the staging ends with the crop's last row, the output with its guard band.
@@ -80,14 +51,12 @@ int main() {
                         std::vector<uint32_t> stage((size_t)w * (y + ch));
                         for (size_t i = 0; i < stage.size(); ++i) stage[i] = (uint32_t)(i * 2654435761u + 12345u);
                         const uint32_t B = cw * ch * och;
-                        std::vector<uint8_t> out(guard + a + B + guard, 0xA5), writes(out.size(), 0);
+                        std::vector<uint8_t> out(guard + a + B + guard, hostmem::kGuard), writes(out.size(), 0);
                         const uint64_t q = base + guard + a;
                         const long long rc = crop_host_run(stage.data(), stage.size(), w, x, y, cw, ch, flags, och, q, base, out.data(), writes.data(), out.size());
                         if (rc != (long long)qoimi::crop_items(q, B)) { printf("bad access: och %u a %u flags %u %u x %u: %lld\n", och, a, flags, cw, ch, rc); return 1; }
-                        for (size_t i = 0; i < out.size(); ++i) {
-                            const bool inside = i >= guard + a && i < guard + a + B;
-                            if (writes[i] != (inside ? 1 : 0) || (!inside && out[i] != 0xA5)) { printf("byte %zu written %u times\n", i, writes[i]); return 1; }
-                        }
+                        const long long off = hostmem::first_miswritten(out, writes, guard + a, B);
+                        if (off >= 0) { printf("byte %lld written %u times\n", off, writes[off]); return 1; }
                         for (uint32_t b = 0; b < B; ++b) {
                             const uint32_t p = b / och, r = p / cw, c = p % cw;
                             const uint32_t sy = (flags & 2u) ? y + ch - 1u - r : y + r, sx = (flags & 1u) ? x + cw - 1u - c : x + c;

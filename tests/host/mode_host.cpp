@@ -1,43 +1,18 @@
 // mode_host.cpp — qoimi_decode_tensors with QOIMI_FILTER_MODE (qoi_amd/csrc/qoi_mode_core.h: mode_hold, mode_meet, mode_best, mode_pick; the
 // store end: qoi_tensor_core.h: TensorSink) compiled for the host: the walk of tensor_mode over an item, tile by tile, with the lanes of a
 // tile walked in a loop - where the kernel moves pixels between lanes (__shfl of width L, __shfl_xor) this file reads the other lane's
-// entry of an array of 256 - over a synthetic staging array and a memory functor that checks and counts every access: every load an aligned
-// dword of the rectangle in the staged image, every store a whole aligned one inside the item's output.  tests/test_mode_core_host.py
-// compares it with the Python models without a GPU.  With -DMODE_HOST_MAIN the same source is a stand-alone program that walks a grid of
+// entry of an array of 256 - over a synthetic staging array and the checking memory functor of host_mem.h (RectMem).
+// tests/test_mode_core_host.py compares it with the Python models without a GPU.  With -DMODE_HOST_MAIN the same source is a stand-alone program that walks a grid of
 // items against a plain counting loop (the test builds it with -fsanitize=address,undefined and runs it).  Not part of the library.
-#include <stddef.h>
-#include <stdint.h>
-
 #include "../../qoi_amd/csrc/qoi_mode_core.h"
-#include "../../qoi_amd/csrc/qoi_tensor_core.h"
+#include "host_mem.h"
+#include "host_sink.h"
 
 namespace {
 
-// Addresses are virtual: `base` (a multiple of 16) stands for out[0], so the test chooses every alignment of q.
-struct HostMem {
-    const uint32_t* stage; uint64_t stage_px;
-    uint32_t w, x, y, cw, rh;            // the rectangle: a load of any other staged pixel is bad
-    uint8_t* out; uint8_t* writes; uint64_t out_len, base;
-    long long* bad;                      // accesses outside an array or the rectangle, or not naturally aligned
-    long long* loads;
-    uint32_t load(uint64_t i) const {
-        ++*loads;
-        const uint64_t r = i / w, k = i % w;
-        if (i >= stage_px || r < y || r >= (uint64_t)y + rh || k < x || k >= (uint64_t)x + cw) { ++*bad; return 0u; }
-        return stage[i];
-    }
-    void put(uint64_t a, uint32_t v, uint32_t bytes) const {
-        if (a % bytes != 0u || a < base || a - base + bytes > out_len) { ++*bad; return; }
-        for (uint32_t k = 0; k < bytes; ++k) { out[a - base + k] = (uint8_t)(v >> (8u * k)); ++writes[a - base + k]; }
-    }
-    void store1(uint64_t a, uint32_t v) const { put(a, v, 1u); }
-    void store2(uint64_t a, uint32_t v) const { put(a, v, 2u); }
-    void store4(uint64_t a, uint32_t v) const { put(a, v, 4u); }
-};
-
 // One tile as the kernel runs it: every one of the 256 lanes takes every step, whether its output pixel exists or not.
 template <class Sink>
-void mode_tile(const HostMem& mem, const qoimi::ResizeGeom& g, uint64_t q, uint32_t och, uint32_t lg, uint64_t tile, const Sink& sink) {
+void mode_tile(const hostmem::RectMem& mem, const qoimi::ResizeGeom& g, uint64_t q, uint32_t och, uint32_t lg, uint64_t tile, const Sink& sink) {
     using namespace qoimi;
     const uint32_t L = 1u << lg;
     ModeHeld h[kResizeThreads];
@@ -79,14 +54,12 @@ long long mode_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w, ui
                         uint32_t flags, uint32_t och, uint32_t lg, uint32_t dtype, uint32_t layout, const float* scale, const float* bias, uint64_t q, uint64_t base,
                         uint8_t* out, uint8_t* writes, uint64_t out_len) {
     long long bad = 0, loads = 0;
-    const HostMem mem = {stage, stage_px, w, x, y, cw, rh, out, writes, out_len, base, &bad, &loads};
-    qoimi::TensorSink sink;
-    sink.fmt.dtype = dtype; sink.fmt.layout = layout;
-    for (int k = 0; k < 4; ++k) { sink.fmt.scale[k] = scale[k]; sink.fmt.bias[k] = bias[k]; }
+    const hostmem::RectMem mem = {{out, writes, out_len, base, &bad}, stage, stage_px, w, x, y, cw, rh, &loads};
+    const qoimi::TensorSink sink = hostmem::tensor_sink(dtype, layout, scale, bias);
     const qoimi::ResizeGeom g = {w, x, y, cw, rh, ow, oh, flags};
     const uint64_t tiles = ((((uint64_t)ow * oh) << lg) + qoimi::kResizeThreads - 1u) / qoimi::kResizeThreads;
     for (uint64_t tile = 0; tile < tiles; ++tile) mode_tile(mem, g, q, och, lg, tile, sink);
-    return bad ? -1 - bad : loads;
+    return hostmem::checked(bad, loads);
 }
 
 uint64_t mode_host_tiles(uint32_t cw, uint32_t rh, uint32_t ow, uint32_t oh) { return qoimi::mode_tiles(cw, rh, ow, oh); }
@@ -103,8 +76,6 @@ uint32_t mode_host_max_size() { return qoimi::kModeMaxSize; }
 #ifdef MODE_HOST_MAIN
 #include <stdio.h>
 #include <string.h>
-
-#include <vector>
 
 // The winner of a cell by plain counting over the cell's pixels, the cell found by the centre inequality and not by first()
 static uint32_t plain_vote(const std::vector<uint32_t>& stage, uint32_t w, uint32_t x, uint32_t y, uint32_t cw, uint32_t rh, uint32_t ow, uint32_t oh, uint32_t X, uint32_t Y) {
@@ -134,7 +105,7 @@ static uint32_t plain_vote(const std::vector<uint32_t>& stage, uint32_t w, uint3
 // chooses and one above it, both flips, both och, a set of dtypes, layouts and alignments - in arrays of exactly the size the walk may
 // touch: the staging ends with the rectangle's last row, the output with its guard band.
 int main() {
-    struct Case { uint32_t w, h, x, y, cw, rh, ow, oh; };
+    using hostmem::Case;
     const Case cases[] = {{1, 1, 0, 0, 1, 1, 1, 1}, {1, 1, 0, 0, 1, 1, 7, 5}, {37, 29, 0, 0, 37, 29, 9, 7}, {37, 29, 3, 5, 31, 23, 50, 7}, {37, 29, 1, 2, 33, 25, 5, 41},
                           {70, 45, 0, 0, 70, 45, 16, 11}, {70, 45, 5, 3, 64, 40, 32, 20}, {70, 45, 3, 1, 64, 44, 4, 3}, {64, 48, 0, 0, 64, 48, 4, 3}, {130, 3, 1, 0, 129, 3, 9, 1},
                           {3, 130, 0, 1, 3, 129, 1, 9}, {40, 40, 1, 1, 37, 37, 37, 37}, {300, 2, 0, 0, 300, 2, 19, 1}};
@@ -155,21 +126,18 @@ int main() {
                     for (uint32_t flags = 0; flags < 4; ++flags) {
                         const uint32_t dtype = f[0], layout = f[1], elem = qoimi::tensor_elem(dtype), n = layout == 3u ? 1u : och, a = elem * (flags + 1u) % 16u;
                         const uint64_t B = (uint64_t)c.ow * c.oh * n * elem;
-                        std::vector<uint8_t> out(guard + a + B + guard, 0xA5), writes(out.size(), 0);
+                        std::vector<uint8_t> out(guard + a + B + guard, hostmem::kGuard), writes(out.size(), 0);
                         const long long rc = mode_host_run(stage.data(), stage.size(), c.w, c.x, c.y, c.cw, c.rh, c.ow, c.oh, flags, och, lg, dtype, layout, one, zero,
                                                            base + guard + a, base, out.data(), writes.data(), out.size());
                         if (rc < 0) { printf("%lld bad accesses: %ux%u -> %ux%u lg %u dtype %u layout %u\n", -1 - rc, c.cw, c.rh, c.ow, c.oh, lg, dtype, layout); return 1; }
-                        for (size_t i = 0; i < out.size(); ++i) {
-                            const bool inside = i >= guard + a && i < guard + a + B;
-                            if (writes[i] != (inside ? 1 : 0) || (!inside && out[i] != 0xA5)) { printf("byte %zu written %u times\n", i, writes[i]); return 1; }
-                        }
+                        const long long off = hostmem::first_miswritten(out, writes, guard + a, B);
+                        if (off >= 0) { printf("byte %lld written %u times\n", off, writes[off]); return 1; }
                         if (dtype == 1u) { ++items; continue; }         // (binary16: the stores are checked, the values by the Python test)
                         for (uint32_t Y = 0; Y < c.oh; ++Y)
                             for (uint32_t X = 0; X < c.ow; ++X) {
                                 const uint32_t px = plain_vote(stage, c.w, c.x, c.y, c.cw, c.rh, c.ow, c.oh, X, Y);
-                                const uint32_t xo = (flags & 1u) ? c.ow - 1u - X : X, yo = (flags & 2u) ? c.oh - 1u - Y : Y;
                                 for (uint32_t ch = 0; ch < n; ++ch) {
-                                    const size_t idx = layout == 1u ? ((size_t)ch * c.oh + yo) * c.ow + xo : ((size_t)yo * c.ow + xo) * n + ch;
+                                    const size_t idx = hostmem::element_index(layout == 1u, flags, c.ow, c.oh, n, X, Y, ch);
                                     uint64_t got = 0;
                                     memcpy(&got, &out[guard + a + idx * elem], elem);
                                     if (got != ((px >> (8u * ch)) & 255u)) {

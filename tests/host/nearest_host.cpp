@@ -1,41 +1,12 @@
 // nearest_host.cpp — qoimi_decode_tensors with QOIMI_FILTER_NEAREST (qoi_amd/csrc/qoi_nearest_core.h: nearest_work; the store end:
 // qoi_tensor_core.h: TensorSink with the integer dtypes and the one-plane layout) compiled for the host: the walk of tensor_nearest over an
-// item, tile by tile and work item by work item, over a synthetic staging array and a memory functor that checks and counts every access -
-// every load an aligned dword of the rectangle in the staged image, every store a whole aligned one inside the item's output -, so that
-// tests/test_labels_core_host.py can compare it with the Python models without a GPU.  With -DNEAREST_HOST_MAIN the same source is a
+// item, tile by tile and work item by work item, over a synthetic staging array and the checking memory functor of host_mem.h (RectMem), so
+// that tests/test_labels_core_host.py can compare it with the Python models without a GPU.  With -DNEAREST_HOST_MAIN the same source is a
 // stand-alone program that walks a grid of items against a plain double loop (the test builds it with -fsanitize=address,undefined and runs
 // it).  Not part of the library.
-#include <stddef.h>
-#include <stdint.h>
-
 #include "../../qoi_amd/csrc/qoi_nearest_core.h"
-#include "../../qoi_amd/csrc/qoi_tensor_core.h"
-
-namespace {
-
-// Addresses are virtual: `base` (a multiple of 16) stands for out[0], so the test chooses every alignment of q.
-struct HostMem {
-    const uint32_t* stage; uint64_t stage_px;
-    uint32_t w, x, y, cw, rh;            // the rectangle: a load of any other staged pixel is bad
-    uint8_t* out; uint8_t* writes; uint64_t out_len, base;
-    long long* bad;                      // accesses outside an array or the rectangle, or not naturally aligned
-    long long* loads;
-    uint32_t load(uint64_t i) const {
-        ++*loads;
-        const uint64_t r = i / w, k = i % w;
-        if (i >= stage_px || r < y || r >= (uint64_t)y + rh || k < x || k >= (uint64_t)x + cw) { ++*bad; return 0u; }
-        return stage[i];
-    }
-    void put(uint64_t a, uint32_t v, uint32_t bytes) const {
-        if (a % bytes != 0u || a < base || a - base + bytes > out_len) { ++*bad; return; }
-        for (uint32_t k = 0; k < bytes; ++k) { out[a - base + k] = (uint8_t)(v >> (8u * k)); ++writes[a - base + k]; }
-    }
-    void store1(uint64_t a, uint32_t v) const { put(a, v, 1u); }
-    void store2(uint64_t a, uint32_t v) const { put(a, v, 2u); }
-    void store4(uint64_t a, uint32_t v) const { put(a, v, 4u); }
-};
-
-}  // namespace
+#include "host_mem.h"
+#include "host_sink.h"
 
 extern "C" {
 
@@ -46,15 +17,13 @@ long long nearest_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w,
                            uint32_t flags, uint32_t och, uint32_t dtype, uint32_t layout, const float* scale, const float* bias, uint64_t q, uint64_t base,
                            uint8_t* out, uint8_t* writes, uint64_t out_len) {
     long long bad = 0, loads = 0;
-    const HostMem mem = {stage, stage_px, w, x, y, cw, rh, out, writes, out_len, base, &bad, &loads};
-    qoimi::TensorSink sink;
-    sink.fmt.dtype = dtype; sink.fmt.layout = layout;
-    for (int k = 0; k < 4; ++k) { sink.fmt.scale[k] = scale[k]; sink.fmt.bias[k] = bias[k]; }
+    const hostmem::RectMem mem = {{out, writes, out_len, base, &bad}, stage, stage_px, w, x, y, cw, rh, &loads};
+    const qoimi::TensorSink sink = hostmem::tensor_sink(dtype, layout, scale, bias);
     const qoimi::ResizeGeom g = {w, x, y, cw, rh, ow, oh, flags};
     const uint64_t tiles = qoimi::nearest_tiles(cw, ow, oh);
     for (uint64_t tile = 0; tile < tiles; ++tile)
         for (uint32_t t = 0; t < qoimi::kResizeThreads; ++t) qoimi::nearest_work(mem, g, q, och, tile * qoimi::kResizeThreads + t, sink);
-    return bad ? -1 - bad : loads;
+    return hostmem::checked(bad, loads);
 }
 
 uint64_t nearest_host_tiles(uint32_t cw, uint32_t ow, uint32_t oh) { return qoimi::nearest_tiles(cw, ow, oh); }
@@ -67,8 +36,6 @@ uint32_t nearest_host_max_size() { return qoimi::kNearestMaxSize; }
 #ifdef NEAREST_HOST_MAIN
 #include <stdio.h>
 #include <string.h>
-
-#include <vector>
 
 // The element of the value v = 0..255 under scale 1 and bias 0, another way: every such value is exact in all four float formats
 static uint64_t plain_element(uint32_t v, uint32_t dtype) {
@@ -85,7 +52,7 @@ static uint64_t plain_element(uint32_t v, uint32_t dtype) {
 // boundaries; every flip, och, dtype and layout, a set of alignments - in arrays of exactly the size the walk may touch: the staging ends
 // with the rectangle's last row, the output with its guard band.
 int main() {
-    struct Case { uint32_t w, h, x, y, cw, rh, ow, oh; };
+    using hostmem::Case;
     const Case cases[] = {{1, 1, 0, 0, 1, 1, 1, 1}, {1, 1, 0, 0, 1, 1, 7, 5}, {1, 130, 0, 3, 1, 127, 1, 1}, {1, 130, 0, 0, 1, 130, 3, 257}, {130, 1, 1, 0, 129, 1, 1, 1},
                           {37, 29, 3, 5, 31, 23, 50, 41}, {37, 29, 1, 1, 2, 14, 41, 23}, {37, 29, 0, 0, 37, 29, 37, 29}, {70, 45, 5, 3, 63, 41, 3, 2},
                           {70, 45, 7, 1, 60, 40, 20, 8}, {16384, 1, 1, 0, 16383, 1, 2, 1}, {300, 2, 0, 0, 300, 2, 3, 1}};
@@ -103,21 +70,18 @@ int main() {
                         const uint32_t elem = nearest_host_elem(dtype), n = layout == 3u ? 1u : och;
                         for (uint32_t a = 0; a < 16u; a += (elem == 1u ? 3u : elem) * ((dtype + flags) % 3u + 1u)) {
                             const uint64_t B = (uint64_t)c.ow * c.oh * n * elem;
-                            std::vector<uint8_t> out(guard + a + B + guard, 0xA5), writes(out.size(), 0);
+                            std::vector<uint8_t> out(guard + a + B + guard, hostmem::kGuard), writes(out.size(), 0);
                             const long long rc = nearest_host_run(stage.data(), stage.size(), c.w, c.x, c.y, c.cw, c.rh, c.ow, c.oh, flags, och, dtype, layout, one, zero,
                                                                   base + guard + a, base, out.data(), writes.data(), out.size());
                             if (rc != (long long)c.ow * c.oh) { printf("%lld loads or bad accesses: %ux%u -> %ux%u dtype %u layout %u\n", rc, c.cw, c.rh, c.ow, c.oh, dtype, layout); return 1; }
-                            for (size_t i = 0; i < out.size(); ++i) {
-                                const bool inside = i >= guard + a && i < guard + a + B;
-                                if (writes[i] != (inside ? 1 : 0) || (!inside && out[i] != 0xA5)) { printf("byte %zu written %u times\n", i, writes[i]); return 1; }
-                            }
+                            const long long off = hostmem::first_miswritten(out, writes, guard + a, B);
+                            if (off >= 0) { printf("byte %lld written %u times\n", off, writes[off]); return 1; }
                             for (uint32_t Y = 0; Y < c.oh; ++Y)
                                 for (uint32_t X = 0; X < c.ow; ++X) {
                                     const uint64_t k = ((2ull * X + 1u) * c.cw) / (2ull * c.ow), r = ((2ull * Y + 1u) * c.rh) / (2ull * c.oh);
                                     const uint32_t px = stage[(size_t)(c.y + r) * c.w + c.x + k];
-                                    const uint32_t xo = (flags & 1u) ? c.ow - 1u - X : X, yo = (flags & 2u) ? c.oh - 1u - Y : Y;
                                     for (uint32_t ch = 0; ch < n; ++ch) {
-                                        const size_t idx = layout == 1u ? ((size_t)ch * c.oh + yo) * c.ow + xo : ((size_t)yo * c.ow + xo) * n + ch;
+                                        const size_t idx = hostmem::element_index(layout == 1u, flags, c.ow, c.oh, n, X, Y, ch);
                                         uint64_t got = 0;
                                         memcpy(&got, &out[guard + a + idx * elem], elem);
                                         if (got != plain_element((px >> (8u * ch)) & 255u, dtype)) {

@@ -1,35 +1,10 @@
 // resize_host.cpp — the arithmetic of qoimi_decode_resized (qoi_amd/csrc/qoi_resize_core.h) compiled for the host: the walk of resize_filter over
-// an item, tile by tile and lane by lane, over a synthetic staging array and a memory functor that checks and counts every access, so that
+// an item, tile by tile and lane by lane, over a synthetic staging array and the checking memory functor of host_mem.h (StagedMem), so that
 // tests/test_resize_core_host.py can compare it with the Python model without a GPU.  The sums of a pixel's lanes are added here where the
 // kernel takes its butterfly steps.  With -DRESIZE_HOST_MAIN the same source is a stand-alone program that walks a grid of items against a
 // plain loop over all taps (the test builds it with -fsanitize=address,undefined and runs it).  Not part of the library.
-#include <stddef.h>
-#include <stdint.h>
-
 #include "../../qoi_amd/csrc/qoi_resize_core.h"
-
-namespace {
-
-// Addresses are virtual: `base` (a multiple of 16) stands for out[0], so the test chooses every alignment of q.
-struct HostMem {
-    const uint32_t* stage; uint64_t stage_px;
-    uint8_t* out; uint8_t* writes; uint64_t out_len, base;
-    long long* bad;                      // accesses outside an array or not naturally aligned
-    long long* loads;
-    uint32_t load(uint64_t i) const {
-        ++*loads;
-        if (i >= stage_px) { ++*bad; return 0u; }
-        return stage[i];
-    }
-    void put(uint64_t a, uint32_t v, uint32_t bytes) const {
-        if (a % bytes != 0u || a < base || a - base + bytes > out_len) { ++*bad; return; }
-        for (uint32_t k = 0; k < bytes; ++k) { out[a - base + k] = (uint8_t)(v >> (8u * k)); ++writes[a - base + k]; }
-    }
-    void store1(uint64_t a, uint32_t v) const { put(a, v, 1u); }
-    void store4(uint64_t a, uint32_t v) const { put(a, v, 4u); }
-};
-
-}  // namespace
+#include "host_mem.h"
 
 extern "C" {
 
@@ -40,7 +15,7 @@ long long resize_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w, 
                           uint32_t flags, uint32_t och, int weighted, uint64_t q, uint64_t base, uint8_t* out, uint8_t* writes, uint64_t out_len,
                           unsigned long long* tiles_walked) {
     long long bad = 0, loads = 0;
-    const HostMem mem = {stage, stage_px, out, writes, out_len, base, &bad, &loads};
+    const hostmem::StagedMem mem = {{out, writes, out_len, base, &bad}, stage, stage_px, &loads};
     const qoimi::ResizeGeom g = {w, x, y, cw, rh, ow, oh, flags};
     uint32_t lg, c;
     qoimi::resize_split(cw, ow, lg, c);
@@ -62,7 +37,7 @@ long long resize_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w, 
             qoimi::resize_finish(mem, g, q, och, wgt, X, Y, sum);
         }
     if (tiles_walked) *tiles_walked = tiles;
-    return bad ? -1 - bad : loads;
+    return hostmem::checked(bad, loads);
 }
 
 void resize_host_split(uint32_t cw, uint32_t ow, uint32_t* lg, uint32_t* c) { qoimi::resize_split(cw, ow, *lg, *c); }
@@ -74,7 +49,6 @@ uint32_t resize_host_div_round(uint64_t n, uint64_t d) { return qoimi::resize_di
 
 #ifdef RESIZE_HOST_MAIN
 #include <stdio.h>
-#include <vector>
 
 static uint64_t overlap(uint64_t X, uint64_t n_src, uint64_t k, uint64_t n_out) {
     const uint64_t lo = X * n_src > k * n_out ? X * n_src : k * n_out, hi = (X + 1) * n_src < (k + 1) * n_out ? (X + 1) * n_src : (k + 1) * n_out;
@@ -100,16 +74,14 @@ int main() {
                             if (i % 5u == 0u) stage[i] &= 0x00FFFFFFu;                       // some transparent pixels
                         }
                         const uint64_t B = (uint64_t)ow * oh * och, T = (uint64_t)cw * rh;
-                        std::vector<uint8_t> out(guard + a + B + guard, 0xA5), writes(out.size(), 0);
+                        std::vector<uint8_t> out(guard + a + B + guard, hostmem::kGuard), writes(out.size(), 0);
                         const uint64_t q = base + guard + a;
                         unsigned long long tiles = 0;
                         const long long rc = resize_host_run(stage.data(), stage.size(), w, x, y, cw, rh, ow, oh, flags, och, weighted, q, base, out.data(),
                                                              writes.data(), out.size(), &tiles);
                         if (rc < 0) { printf("bad access: och %u a %u flags %u %ux%u -> %ux%u: %lld\n", och, a, flags, cw, rh, ow, oh, rc); return 1; }
-                        for (size_t i = 0; i < out.size(); ++i) {
-                            const bool inside = i >= guard + a && i < guard + a + B;
-                            if (writes[i] != (inside ? 1 : 0) || (!inside && out[i] != 0xA5)) { printf("byte %zu written %u times\n", i, writes[i]); return 1; }
-                        }
+                        const long long off = hostmem::first_miswritten(out, writes, guard + a, B);
+                        if (off >= 0) { printf("byte %lld written %u times\n", off, writes[off]); return 1; }
                         for (uint32_t Y = 0; Y < oh; ++Y)
                             for (uint32_t X = 0; X < ow; ++X) {
                                 uint64_t N[4] = {0, 0, 0, 0}, M[3] = {0, 0, 0};
@@ -120,11 +92,10 @@ int main() {
                                         for (int ch = 0; ch < 4; ++ch) N[ch] += wt * ((px >> (8 * ch)) & 255u);
                                         for (int ch = 0; ch < 3; ++ch) M[ch] += wt * ((px >> (8 * ch)) & 255u) * (px >> 24);
                                     }
-                                const uint32_t xo = (flags & 1u) ? ow - 1u - X : X, yo = (flags & 2u) ? oh - 1u - Y : Y;
                                 for (uint32_t ch = 0; ch < och; ++ch) {
                                     uint64_t v = (N[ch] + T / 2) / T;
                                     if (weighted && och == 4u && ch < 3u && N[3] > 0) v = (M[ch] + N[3] / 2) / N[3];
-                                    if (out[guard + a + ((size_t)yo * ow + xo) * och + ch] != (uint8_t)v) {
+                                    if (out[guard + a + hostmem::element_index(false, flags, ow, oh, och, X, Y, ch)] != (uint8_t)v) {
                                         printf("wrong byte: och %u mode %d a %u flags %u %ux%u -> %ux%u at (%u, %u).%u\n", och, weighted, a, flags, cw, rh, ow, oh, X, Y, ch);
                                         return 1;
                                     }

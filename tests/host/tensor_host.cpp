@@ -1,38 +1,10 @@
 // tensor_host.cpp — the store end of qoimi_decode_tensors / qoimi_decode_warped_tensors (qoi_amd/csrc/qoi_tensor_core.h) compiled for the host:
-// every pixel of an output handed to TensorSink as the filter tiles and the warp tile hand it over, with a memory functor that checks and counts
+// every pixel of an output handed to TensorSink as the filter tiles and the warp tile hand it over, with the store half of host_mem.h (StoreMem), which checks and counts
 // every store, so that tests/test_tensor_core_host.py can compare it with qoi_amd/tensors.py without a GPU.  With -DTENSOR_HOST_MAIN the same
 // source is a stand-alone program that walks a grid of formats against a plain loop (the test builds it with -fsanitize=address,undefined and
 // runs it).  Not part of the library.
-#include <stddef.h>
-#include <stdint.h>
-
-#include "../../qoi_amd/csrc/qoi_tensor_core.h"
-
-namespace {
-
-// Addresses are virtual: `base` (a multiple of 16) stands for out[0], so the test chooses every alignment of q.
-struct HostMem {
-    uint8_t* out; uint8_t* writes; uint64_t out_len, base;
-    long long* bad;                      // stores outside the array or not naturally aligned
-    long long* stores;
-    void put(uint64_t a, uint32_t v, uint32_t bytes) const {
-        ++*stores;
-        if (a % bytes != 0u || a < base || a - base + bytes > out_len) { ++*bad; return; }
-        for (uint32_t k = 0; k < bytes; ++k) { out[a - base + k] = (uint8_t)(v >> (8u * k)); ++writes[a - base + k]; }
-    }
-    void store1(uint64_t a, uint32_t v) const { put(a, v, 1u); }
-    void store2(uint64_t a, uint32_t v) const { put(a, v, 2u); }
-    void store4(uint64_t a, uint32_t v) const { put(a, v, 4u); }
-};
-
-qoimi::TensorFormat format_of(uint32_t dtype, uint32_t layout, const float* scale, const float* bias) {
-    qoimi::TensorFormat f;
-    f.dtype = dtype; f.layout = layout;
-    for (int k = 0; k < 4; ++k) { f.scale[k] = scale[k]; f.bias[k] = bias[k]; }
-    return f;
-}
-
-}  // namespace
+#include "host_mem.h"
+#include "host_sink.h"
 
 extern "C" {
 
@@ -42,8 +14,8 @@ extern "C" {
 long long tensor_host_run(const uint32_t* px, uint32_t ow, uint32_t oh, uint32_t och, uint32_t flags, int warp, uint32_t dtype, uint32_t layout,
                           const float* scale, const float* bias, uint64_t q, uint64_t base, uint8_t* out, uint8_t* writes, uint64_t out_len) {
     long long bad = 0, stores = 0;
-    const HostMem mem = {out, writes, out_len, base, &bad, &stores};
-    const qoimi::TensorSink sink = {format_of(dtype, layout, scale, bias)};
+    const hostmem::StoreMem mem = {out, writes, out_len, base, &bad, &stores};
+    const qoimi::TensorSink sink = hostmem::tensor_sink(dtype, layout, scale, bias);
     const qoimi::ResizeGeom rg = {ow, 0u, 0u, ow, oh, ow, oh, flags};
     const qoimi::WarpGeom wg = {ow, 0u, 0u, ow, oh, ow, oh, 0u, 65536, 0, 0, 65536, 0u, 0, 0};
     for (uint32_t Y = 0; Y < oh; ++Y)
@@ -51,7 +23,7 @@ long long tensor_host_run(const uint32_t* px, uint32_t ow, uint32_t oh, uint32_t
             if (warp) sink(mem, wg, q, och, X, Y, px[(uint64_t)Y * ow + X]);
             else sink(mem, rg, q, och, X, Y, px[(uint64_t)Y * ow + X]);
         }
-    return bad ? -1 - bad : stores;
+    return hostmem::checked(bad, stores);
 }
 
 // The bits tensor_value stores for the channel value v
@@ -67,8 +39,6 @@ uint32_t tensor_host_elem(uint32_t dtype) { return qoimi::tensor_elem(dtype); }
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
-
-#include <vector>
 
 // The value another way: the product through a volatile, binary16 through the math library
 static uint32_t plain_value(uint32_t v, float scale, float bias, uint32_t dtype) {
@@ -109,19 +79,16 @@ int main() {
                                 for (size_t i = 0; i < px.size(); ++i) px[i] = (uint32_t)(i * 2654435761u + 12345u * k);
                                 const size_t B = (size_t)ow * oh * och * elem, band = 32;
                                 for (uint32_t a = 0; a < 16u; a += elem) {
-                                    std::vector<uint8_t> out(band + a + B + band, 0xA5), writes(out.size(), 0);
+                                    std::vector<uint8_t> out(band + a + B + band, hostmem::kGuard), writes(out.size(), 0);
                                     const uint64_t base = 1u << 20;
                                     if (tensor_host_run(px.data(), ow, oh, och, flags, warp, dtype, layout, scales[k], biases[k], base + band + a, base, out.data(),
                                                         writes.data(), out.size()) < 0) { printf("bad store\n"); return 1; }
-                                    for (size_t i = 0; i < out.size(); ++i) {
-                                        const bool inside = i >= band + a && i < band + a + B;
-                                        if (writes[i] != (inside ? 1 : 0) || (!inside && out[i] != 0xA5)) { printf("byte %zu written %d times\n", i, writes[i]); return 1; }
-                                    }
+                                    const long long off = hostmem::first_miswritten(out, writes, band + a, B);
+                                    if (off >= 0) { printf("byte %lld written %u times\n", off, writes[off]); return 1; }
                                     for (uint32_t Y = 0; Y < oh; ++Y)
                                         for (uint32_t X = 0; X < ow; ++X)
                                             for (uint32_t c = 0; c < och; ++c) {
-                                                const uint32_t xo = (!warp && (flags & 1u)) ? ow - 1u - X : X, yo = (!warp && (flags & 2u)) ? oh - 1u - Y : Y;
-                                                const size_t idx = layout ? ((size_t)c * oh + yo) * ow + xo : ((size_t)yo * ow + xo) * och + c;
+                                                const size_t idx = hostmem::element_index(layout != 0u, warp ? 0u : flags, ow, oh, och, X, Y, c);
                                                 uint32_t got = 0;
                                                 memcpy(&got, &out[band + a + idx * elem], elem);
                                                 const uint32_t want = plain_value((px[(size_t)Y * ow + X] >> (8u * c)) & 255u, scales[k][c], biases[k][c], dtype);
@@ -131,7 +98,7 @@ int main() {
                                 }
                             }
                         }
-    printf("%lld items ok\n", items);
+    printf("tensor_host: %lld items ok\n", items);
     return 0;
 }
 #endif

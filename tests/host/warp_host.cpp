@@ -1,37 +1,10 @@
 // warp_host.cpp — the arithmetic of qoimi_decode_warped (qoi_amd/csrc/qoi_warp_core.h) compiled for the host: the walk of warp_gather over an
-// item, tile by tile and work item by work item, over a synthetic staging array and a memory functor that checks and counts every access, so
+// item, tile by tile and work item by work item, over a synthetic staging array and the checking memory functor of host_mem.h (RectMem), so
 // that tests/test_warp_core_host.py can compare it with the Python model without a GPU.  With -DWARP_HOST_MAIN the same source is a
 // stand-alone program that walks a grid of items against a plain loop over the four samples (the test builds it with
 // -fsanitize=address,undefined and runs it).  Not part of the library.
-#include <stddef.h>
-#include <stdint.h>
-
 #include "../../qoi_amd/csrc/qoi_warp_core.h"
-
-namespace {
-
-// Addresses are virtual: `base` (a multiple of 16) stands for out[0], so the test chooses every alignment of q.
-struct HostMem {
-    const uint32_t* stage; uint64_t stage_px;
-    uint32_t w, x, y, cw, rh;            // the rectangle: a load of any other staged pixel is bad
-    uint8_t* out; uint8_t* writes; uint64_t out_len, base;
-    long long* bad;                      // accesses outside an array or the rectangle, or not naturally aligned
-    long long* loads;
-    uint32_t load(uint64_t i) const {
-        ++*loads;
-        const uint64_t r = i / w, k = i % w;
-        if (i >= stage_px || r < y || r >= (uint64_t)y + rh || k < x || k >= (uint64_t)x + cw) { ++*bad; return 0u; }
-        return stage[i];
-    }
-    void put(uint64_t a, uint32_t v, uint32_t bytes) const {
-        if (a % bytes != 0u || a < base || a - base + bytes > out_len) { ++*bad; return; }
-        for (uint32_t k = 0; k < bytes; ++k) { out[a - base + k] = (uint8_t)(v >> (8u * k)); ++writes[a - base + k]; }
-    }
-    void store1(uint64_t a, uint32_t v) const { put(a, v, 1u); }
-    void store4(uint64_t a, uint32_t v) const { put(a, v, 4u); }
-};
-
-}  // namespace
+#include "host_mem.h"
 
 extern "C" {
 
@@ -42,7 +15,7 @@ long long warp_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w, ui
                         uint32_t flags, const long long* m, uint32_t fill, uint32_t och, int weighted, uint64_t q, uint64_t base, uint8_t* out, uint8_t* writes,
                         uint64_t out_len, unsigned long long* tiles_walked) {
     long long bad = 0, loads = 0;
-    const HostMem mem = {stage, stage_px, w, x, y, cw, rh, out, writes, out_len, base, &bad, &loads};
+    const hostmem::RectMem mem = {{out, writes, out_len, base, &bad}, stage, stage_px, w, x, y, cw, rh, &loads};
     const qoimi::WarpGeom g = {w, x, y, cw, rh, ow, oh, flags, (int32_t)m[0], (int32_t)m[1], (int32_t)m[3], (int32_t)m[4], fill, m[2], m[5]};
     const uint64_t tiles = qoimi::warp_tiles(ow, oh);
     const bool wgt = weighted != 0 && och == 4u;
@@ -52,7 +25,7 @@ long long warp_host_run(const uint32_t* stage, uint64_t stage_px, uint32_t w, ui
             else qoimi::warp_work<false>(mem, g, q, och, (uint32_t)tile, t);
         }
     if (tiles_walked) *tiles_walked = tiles;
-    return bad ? -1 - bad : loads;
+    return hostmem::checked(bad, loads);
 }
 
 unsigned long long warp_host_tiles(uint32_t ow, uint32_t oh) { return qoimi::warp_tiles(ow, oh); }
@@ -64,7 +37,6 @@ int warp_host_place(uint32_t tile, uint32_t t, uint32_t ow, uint32_t oh, uint32_
 
 #ifdef WARP_HOST_MAIN
 #include <stdio.h>
-#include <vector>
 
 // floor(p / 2^17) and the remainder without shifting a negative number
 static void split17(long long P, long long& k0, long long& fr) {
@@ -102,16 +74,14 @@ int main() {
                                 if (i % 5u == 0u) stage[i] &= 0x00FFFFFFu;                       // some transparent pixels
                             }
                             const uint64_t B = (uint64_t)ow * oh * och;
-                            std::vector<uint8_t> out(guard + a + B + guard, 0xA5), writes(out.size(), 0);
+                            std::vector<uint8_t> out(guard + a + B + guard, hostmem::kGuard), writes(out.size(), 0);
                             const uint64_t q = base + guard + a;
                             unsigned long long tiles = 0;
                             const long long rc = warp_host_run(stage.data(), stage.size(), w, x, y, cw, rh, ow, oh, flags, m, fill, och, weighted, q, base, out.data(),
                                                                writes.data(), out.size(), &tiles);
                             if (rc < 0) { printf("bad access: och %u a %u flags %u map %d %ux%u -> %ux%u: %lld\n", och, a, flags, map, cw, rh, ow, oh, rc); return 1; }
-                            for (size_t i = 0; i < out.size(); ++i) {
-                                const bool inside = i >= guard + a && i < guard + a + B;
-                                if (writes[i] != (inside ? 1 : 0) || (!inside && out[i] != 0xA5)) { printf("byte %zu written %u times\n", i, writes[i]); return 1; }
-                            }
+                            const long long off = hostmem::first_miswritten(out, writes, guard + a, B);
+                            if (off >= 0) { printf("byte %lld written %u times\n", off, writes[off]); return 1; }
                             for (uint32_t Y = 0; Y < oh; ++Y)
                                 for (uint32_t X = 0; X < ow; ++X) {
                                     const long long U = 2ll * X + 1, V = 2ll * Y + 1;

@@ -9,48 +9,29 @@ Single output pixels at the size limits are compared with Python `int` arithmeti
 built as a stand-alone program with the address and undefined-behaviour sanitizers and run (a program of its own: nothing sanitized is
 loaded into this process)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import cint, cintp, i64, i64p, u32, u32p, u64, u8p, ull, ullp
 from qoi_amd import bicubic
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "bicubic_host.cpp")
-GUARD = 0xA5
-BASE = 1 << 20                      # the virtual address of out[0]: a multiple of 16
-BAND = 48
+SRC = "bicubic_host.cpp"
 
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("bicubichost") / "libbicubic_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
-    u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    lib.bicubic_host_run.restype = ctypes.c_longlong
-    lib.bicubic_host_run.argtypes = [ctypes.POINTER(u32), u64, u32, u32, u32, u32, u32, u32, u32, u32, u32, ctypes.c_int, u64, u64, u8p, u8p, u64,
-                                     ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
-    lib.bicubic_host_pixel.restype = ctypes.c_longlong
-    lib.bicubic_host_pixel.argtypes = [u64, u32, u32, u32, u32, u32, u32, u32, ctypes.c_int, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_longlong)]
-    lib.bicubic_host_synth.restype = u32
-    lib.bicubic_host_synth.argtypes = [u64]
-    lib.bicubic_host_split.restype = None
-    lib.bicubic_host_split.argtypes = [u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
-    lib.bicubic_host_taps.restype = u32
-    lib.bicubic_host_taps.argtypes = [u32, u32]
-    lib.bicubic_host_first.restype = u32
-    lib.bicubic_host_first.argtypes = [u32, u32, u32]
-    lib.bicubic_host_weight.restype = ctypes.c_longlong
-    lib.bicubic_host_weight.argtypes = [u32, u32, u32, u32]
-    lib.bicubic_host_norm.restype = None
-    lib.bicubic_host_norm.argtypes = [u32, u32, u32, u32, ctypes.POINTER(ctypes.c_int)]
-    lib.bicubic_host_tiles.restype = ctypes.c_ulonglong
-    lib.bicubic_host_tiles.argtypes = [u32, u32, u32]
-    return lib
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "bicubic_host_run": (i64, [u32p, u64, u32, u32, u32, u32, u32, u32, u32, u32, u32, cint, u64, u64, u8p, u8p, u64, ullp, ullp]),
+        "bicubic_host_pixel": (i64, [u64, u32, u32, u32, u32, u32, u32, u32, cint, u32, u32, u32p, i64p]),
+        "bicubic_host_synth": (u32, [u64]),
+        "bicubic_host_split": (None, [u32, u32, u32p, u32p]),
+        "bicubic_host_taps": (u32, [u32, u32]),
+        "bicubic_host_first": (u32, [u32, u32, u32]),
+        "bicubic_host_weight": (i64, [u32, u32, u32, u32]),
+        "bicubic_host_norm": (None, [u32, u32, u32, u32, cintp]),
+        "bicubic_host_tiles": (ull, [u32, u32, u32])})
 
 
 def staged(w, rows, seed):
@@ -68,22 +49,15 @@ def staged(w, rows, seed):
 
 def run(lib, px, dwords, x, y, cw, rh, ow, oh, flags, och, mode, a):
     """one item written at BASE + BAND + a; returns (tiles walked, loads, output bytes); asserts guards, write counts and the normalisations"""
-    B = ow * oh * och
-    out = np.full(BAND + a + B + BAND, GUARD, dtype=np.uint8)
-    writes = np.zeros(out.size, dtype=np.uint8)
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    q = BASE + BAND + a
+    band = hostbuild.Banded(ow * oh * och, a)
     tiles, norm = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
-    loads = lib.bicubic_host_run(dwords.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), dwords.size, px.shape[1], x, y, cw, rh, ow, oh, flags, och, mode, q, BASE,
-                                 out.ctypes.data_as(u8p), writes.ctypes.data_as(u8p), out.size, ctypes.byref(tiles), ctypes.byref(norm))
+    loads = lib.bicubic_host_run(dwords.ctypes.data_as(u32p), dwords.size, px.shape[1], x, y, cw, rh, ow, oh, flags, och, mode, *band.args,
+                                 ctypes.byref(tiles), ctypes.byref(norm))
     what = (och, mode, a, flags, cw, rh, ow, oh)
     assert loads >= ow * oh, (what, loads)                          # (negative: a load outside the staged rows, a store out of bounds or misaligned, a table not written exactly)
     assert tiles.value == bicubic.tiles(cw, ow, oh) == lib.bicubic_host_tiles(cw, ow, oh), what
     assert norm.value == sum(len(c) + len(r) for c, r in (bicubic.tile(t, cw, ow, oh) for t in range(tiles.value))), what
-    lo, hi = BAND + a, BAND + a + B
-    assert np.all(writes[lo:hi] == 1) and not writes[:lo].any() and not writes[hi:].any(), what
-    assert np.all(out[:lo] == GUARD) and np.all(out[hi:] == GUARD), what
-    return tiles.value, loads, out[lo:hi]
+    return tiles.value, loads, band.inside(what)
 
 
 def check(lib, cw, rh, ow, oh, och, mode, alignments=range(16), flag_values=range(4), x=3, y=2, seed=0):
@@ -214,11 +188,4 @@ def test_single_pixels_at_the_limits(host_lib, weighted):
 
 
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main(), built with -fsanitize=address,undefined and the sanitizer runtimes linked statically: a program
-    of its own that needs nothing from its environment"""
-    exe = str(tmp_path / "bicubic_host_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                    "-DBICUBIC_HOST_MAIN", "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "items ok" in r.stdout and "runtime error" not in r.stderr
+    assert hostbuild.sanitized(SRC, "BICUBIC_HOST_MAIN", tmp_path) == "bicubic_host: 896 items ok\n"

@@ -4,36 +4,22 @@ output channel counts, every alignment of the output, all four flag values, widt
 tile.  The output equals crops.crop, a guard band around it stays untouched, every output byte is written exactly once, no load leaves the
 rows the crop needs and every store is naturally aligned.  The same source is built as a stand-alone program with the address and
 undefined-behaviour sanitizers and run (a program of its own: nothing sanitized is loaded into this process)."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import BAND, BASE, i64, u32, u32p, u64, u8p, ull
 from qoi_amd import crops
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "crop_host.cpp")
-GUARD = 0xA5
-BASE = 1 << 20                      # the virtual address of out[0]: a multiple of 16
-BAND = 48
+SRC = "crop_host.cpp"
 
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("crophost") / "libcrop_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
-    u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    lib.crop_host_run.restype = ctypes.c_longlong
-    lib.crop_host_run.argtypes = [ctypes.POINTER(u32), u64, u32, u32, u32, u32, u32, u32, u32, u64, u64, u8p, u8p, u64]
-    lib.crop_host_items.restype = ctypes.c_ulonglong
-    lib.crop_host_items.argtypes = [u64, u64]
-    lib.crop_host_tiles.restype = ctypes.c_ulonglong
-    lib.crop_host_tiles.argtypes = [u64, u64]
-    return lib
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "crop_host_run": (i64, [u32p, u64, u32, u32, u32, u32, u32, u32, u32, u64, u64, u8p, u8p, u64]),
+        "crop_host_items": (ull, [u64, u64]),
+        "crop_host_tiles": (ull, [u64, u64])})
 
 
 def staged(w, rows, seed):
@@ -45,18 +31,11 @@ def staged(w, rows, seed):
 def run(lib, px, dwords, x, y, cw, ch, flags, och, a):
     """one crop written at BASE + BAND + a; returns (items walked, output bytes); asserts guards and the write counts"""
     B = cw * ch * och
-    out = np.full(BAND + a + B + BAND, GUARD, dtype=np.uint8)
-    writes = np.zeros(out.size, dtype=np.uint8)
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    q = BASE + BAND + a
-    walked = lib.crop_host_run(dwords.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), dwords.size, px.shape[1], x, y, cw, ch, flags, och, q, BASE,
-                               out.ctypes.data_as(u8p), writes.ctypes.data_as(u8p), out.size)
+    band = hostbuild.Banded(B, a)
+    walked = lib.crop_host_run(dwords.ctypes.data_as(u32p), dwords.size, px.shape[1], x, y, cw, ch, flags, och, *band.args)
     what = (och, a, flags, cw, ch)
-    assert walked == len(crops.items(q, B)) == lib.crop_host_items(q, B), (what, walked)     # (negative: a load or store out of bounds / misaligned)
-    lo, hi = BAND + a, BAND + a + B
-    assert np.all(writes[lo:hi] == 1) and not writes[:lo].any() and not writes[hi:].any(), what
-    assert np.all(out[:lo] == GUARD) and np.all(out[hi:] == GUARD), what
-    return walked, out[lo:hi]
+    assert walked == len(crops.items(band.q, B)) == lib.crop_host_items(band.q, B), (what, walked)     # (negative: a load or store out of bounds / misaligned)
+    return walked, band.inside(what)
 
 
 @pytest.mark.parametrize("och", [3, 4])
@@ -92,11 +71,4 @@ def test_items_and_tiles(host_lib):
 
 
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main(), built with -fsanitize=address,undefined and the sanitizer runtimes linked statically: a program
-    of its own that needs nothing from its environment"""
-    exe = str(tmp_path / "crop_host_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-DCROP_HOST_MAIN",
-                    "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "crops ok" in r.stdout and "runtime error" not in r.stderr
+    assert hostbuild.sanitized(SRC, "CROP_HOST_MAIN", tmp_path) == "crop_host: 2432 crops ok\n"

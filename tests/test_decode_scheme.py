@@ -6,30 +6,23 @@ for EVERY stream, at every segment size — including streams that defeat the sl
 speculation and go through the restart loop.
 """
 import ctypes
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import cases
+import hostbuild
 from qoi_amd import synth
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("hostlib") / "libdecode_host.so")
-    src = os.path.join(ROOT, "tests", "host", "decode_host.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out, src], check=True)
-    lib = ctypes.CDLL(out)
-    for fn in (lib.host_decode_pipeline_g, lib.host_decode_pipeline_fast, lib.host_decode_pipeline_rec):
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
-                       ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
-    return lib
+    pipeline = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                               ctypes.POINTER(ctypes.c_longlong)])
+    # (decode_host.cpp does not build under -Wall -Werror: no warning flags)
+    return hostbuild.shared("decode_host.cpp", tmp_path_factory, {"host_decode_pipeline_g": pipeline, "host_decode_pipeline_fast": pipeline,
+                                                                  "host_decode_pipeline_rec": pipeline}, warnings=())
 
 
 def run(lib, stream: bytes, och: int, B: int, grp: int = 64, fast=False):

@@ -7,24 +7,16 @@ the middle of a tile (groups that straddle the end of an item), rectangles at od
 A guard band around the output stays untouched, every output byte is written exactly once, every load is a dword of the rectangle - one
 per pixel of every cell -, every store a whole aligned one inside the output.  The same source is also built as a stand-alone program with
 the address and undefined-behaviour sanitizers and run (a program of its own: nothing sanitized is loaded into this process)."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import hostbuild
 import mode_cases as MC
+from hostbuild import f32p, i64, u32, u32p, u64, u8p
 from qoi_amd import mode, tensors
 from qoi_amd.tensors import CHW, F16, F32, HW, HWC, I32, I64, U8
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "mode_host.cpp")
-GUARD = 0xA5
-BASE = 1 << 20                      # the virtual address of out[0]: a multiple of 16
-BAND = 48
-u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-u8p, f32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_float)
+SRC = "mode_host.cpp"
 IMAGENET = tensors.normalise((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
 FORMATS = [(U8, HWC), (I64, HW), (I32, CHW), (F16, HWC), (F32, CHW), (U8, HW)]
 # (w, h) of the staged image, classes, the rectangle, the outputs - with the lg the split chooses for each
@@ -39,21 +31,16 @@ CASES = [((1, 1), 2, (0, 0, 1, 1), [((1, 1), 0), ((7, 5), 0)]),
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("modehost") / "libmode_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
-    lib.mode_host_run.restype = ctypes.c_longlong
-    lib.mode_host_run.argtypes = [ctypes.POINTER(u32), u64, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, f32p, f32p, u64, u64, u8p, u8p, u64]
-    lib.mode_host_tiles.restype = u64
-    lib.mode_host_tiles.argtypes = [u32] * 4
-    lib.mode_host_word.restype = u64
-    lib.mode_host_word.argtypes = [u32] * 3
-    lib.mode_host_pick.argtypes = [u64]
-    for f in (lib.mode_host_split, lib.mode_host_first, lib.mode_host_range, lib.mode_host_pick, lib.mode_host_max_ratio, lib.mode_host_max_size):
-        f.restype = u32
-    lib.mode_host_split.argtypes = [u32] * 4
-    lib.mode_host_first.argtypes = lib.mode_host_range.argtypes = [u32] * 3
-    return lib
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "mode_host_run": (i64, [u32p, u64, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, f32p, f32p, u64, u64, u8p, u8p, u64]),
+        "mode_host_tiles": (u64, [u32] * 4),
+        "mode_host_split": (u32, [u32] * 4),
+        "mode_host_first": (u32, [u32] * 3),
+        "mode_host_range": (u32, [u32] * 3),
+        "mode_host_word": (u64, [u32] * 3),
+        "mode_host_pick": (u32, [u64]),
+        "mode_host_max_ratio": (u32, []),
+        "mode_host_max_size": (u32, [])})
 
 
 def staged(w, rows, classes, seed):
@@ -72,17 +59,13 @@ def run(lib, px, dwords, rect, out_size, flags, och, lg, f, a):
     dtype, layout, scale, bias = f
     elem = tensors.elem(dtype)
     B = ow * oh * (1 if layout == HW else och) * elem
-    out = np.full(BAND + a + B + BAND, GUARD, dtype=np.uint8)
-    writes = np.zeros(out.size, dtype=np.uint8)
+    band = hostbuild.Banded(B, a)
     s, b = np.ascontiguousarray(scale, np.float32), np.ascontiguousarray(bias, np.float32)
-    loads = lib.mode_host_run(dwords.ctypes.data_as(ctypes.POINTER(u32)), dwords.size, px.shape[1], x, y, cw, rh, ow, oh, flags, och, lg, dtype, layout,
-                              s.ctypes.data_as(f32p), b.ctypes.data_as(f32p), BASE + BAND + a, BASE, out.ctypes.data_as(u8p), writes.ctypes.data_as(u8p), out.size)
+    loads = lib.mode_host_run(dwords.ctypes.data_as(u32p), dwords.size, px.shape[1], x, y, cw, rh, ow, oh, flags, och, lg, dtype, layout,
+                              s.ctypes.data_as(f32p), b.ctypes.data_as(f32p), *band.args)
     what = (rect, out_size, flags, och, lg, dtype, layout, a)
     assert loads == cell_pixels(cw, rh, ow, oh), (what, loads)           # one load per pixel of every cell, none outside the rectangle, no bad store
-    lo, hi = BAND + a, BAND + a + B
-    assert np.all(writes[lo:hi] == 1) and not writes[:lo].any() and not writes[hi:].any(), what
-    assert np.all(out[:lo] == GUARD) and np.all(out[hi:] == GUARD), what
-    return out[lo:hi]
+    return band.inside(what)
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "%dx%d-%dx%d" % (c[0] + c[2][2:]))
@@ -156,11 +139,4 @@ def test_the_arithmetic_of_the_core(host_lib):
 
 
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main() and its own counting loop, built with -fsanitize=address,undefined and the sanitizer runtimes
-    linked statically, and run directly: a program of its own that needs nothing from its environment"""
-    exe = str(tmp_path / "mode_host_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                    "-DMODE_HOST_MAIN", "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "items ok" in r.stdout and "runtime error" not in r.stderr
+    assert hostbuild.sanitized(SRC, "MODE_HOST_MAIN", tmp_path) == "mode_host: 768 items ok\n"

@@ -7,33 +7,22 @@ rectangle, there is at most one load per output pixel, every store is a whole al
 as a stand-alone program with the address and undefined-behaviour sanitizers and run (a program of its own: nothing sanitized is loaded
 into this process)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import cint, cuint, i64, i64p, u32, u32p, u64, u8p
 from qoi_amd import warp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WARP_SRC = os.path.join(ROOT, "tests", "host", "warp_nearest_host.cpp")
-GUARD = 0xA5
-BASE = 1 << 20                      # the virtual address of out[0]: a multiple of 16
-BAND = 48
-u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-u8p = ctypes.POINTER(ctypes.c_uint8)
+WARP_SRC = "warp_nearest_host.cpp"
 
 
 @pytest.fixture(scope="module")
 def warp_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("warpnearesthost") / "libwarp_nearest_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, WARP_SRC], check=True)
-    lib = ctypes.CDLL(out)
-    lib.warp_nearest_host_run.restype = ctypes.c_longlong
-    lib.warp_nearest_host_run.argtypes = [ctypes.POINTER(u32), u64, u32, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_longlong), u32, u32, ctypes.c_int,
-                                          u64, u64, u8p, u8p, u64]
-    lib.warp_nearest_host_flag.restype = ctypes.c_uint
-    return lib
+    return hostbuild.shared(WARP_SRC, tmp_path_factory, {
+        "warp_nearest_host_run": (i64, [u32p, u64, u32, u32, u32, u32, u32, u32, u32, u32, i64p, u32, u32, cint, u64, u64, u8p, u8p, u64]),
+        "warp_nearest_host_flag": (cuint, [])})
 
 
 def staged(w, rows, seed):
@@ -46,18 +35,12 @@ def staged(w, rows, seed):
 def warp_run(lib, px, dwords, rect, out_size, matrix, flags, fill, och, mode, a):
     x, y, cw, rh = rect
     ow, oh = out_size
-    B = ow * oh * och
-    out = np.full(BAND + a + B + BAND, GUARD, dtype=np.uint8)
-    writes = np.zeros(out.size, dtype=np.uint8)
+    band = hostbuild.Banded(ow * oh * och, a)
     m = (ctypes.c_longlong * 6)(*matrix)
-    loads = lib.warp_nearest_host_run(dwords.ctypes.data_as(ctypes.POINTER(u32)), dwords.size, px.shape[1], x, y, cw, rh, ow, oh, flags, m, fill, och, mode, BASE + BAND + a,
-                                      BASE, out.ctypes.data_as(u8p), writes.ctypes.data_as(u8p), out.size)
+    loads = lib.warp_nearest_host_run(dwords.ctypes.data_as(u32p), dwords.size, px.shape[1], x, y, cw, rh, ow, oh, flags, m, fill, och, mode, *band.args)
     what = (rect, out_size, matrix, flags, och, mode, a)
     assert 0 <= loads <= ow * oh, (what, loads)                       # one load per pixel at most, none outside the rectangle
-    lo, hi = BAND + a, BAND + a + B
-    assert np.all(writes[lo:hi] == 1) and not writes[:lo].any() and not writes[hi:].any(), what
-    assert np.all(out[:lo] == GUARD) and np.all(out[hi:] == GUARD), what
-    return loads, out[lo:hi]
+    return loads, band.inside(what)
 
 
 @pytest.mark.parametrize("mode", [warp.PLAIN, warp.ALPHA_WEIGHTED])
@@ -86,16 +69,5 @@ def test_warp_nearest_walk_against_the_model(warp_lib, och, mode):
     assert np.array_equal(warp_run(warp_lib, px, dwords, (x, y, cw, rh), (33, 18), maps[2], 0, fill, och, mode, 1)[1], want)
 
 
-def build_and_run(tmp_path, src, define, name):
-    exe = str(tmp_path / name)
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                    "-D" + define, "-o", exe, src], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "items ok" in r.stdout and "runtime error" not in r.stderr
-
-
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main(), built with -fsanitize=address,undefined and the sanitizer runtimes linked statically: a program
-    of its own that needs nothing from its environment"""
-    build_and_run(tmp_path, WARP_SRC, "WARP_NEAREST_HOST_MAIN", "warp_nearest_host_main")
+    assert hostbuild.sanitized(WARP_SRC, "WARP_NEAREST_HOST_MAIN", tmp_path) == "warp_nearest_host: 2304 items ok\n"

@@ -5,33 +5,25 @@ byte for byte; the walk of one 64-byte piece that seek_locate runs equals the ch
 The same source is built as a stand-alone program with the address and undefined-behaviour sanitizers and run (a program of its own: nothing
 sanitized is loaded into this process)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import GUARD, cuint, i64, u32, u32p, u64
 from qoi_amd import seekindex as si
 from test_seekindex_model import END, alpha_image, header, index_image, runs_image
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "seek_host.cpp")
-GUARD = 0xA5
+SRC = "seek_host.cpp"
 
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("seekhost") / "libseek_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
-    u32, u64, bp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_char_p
-    lib.seek_host_points.restype = ctypes.c_longlong
-    lib.seek_host_points.argtypes = [u32, u32, u32]
-    lib.seek_host_piece.restype = ctypes.c_uint
-    lib.seek_host_piece.argtypes = [bp, u32, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
-    lib.seek_host_band.restype = ctypes.c_longlong
-    lib.seek_host_band.argtypes = [ctypes.c_void_p, u32, u32, u32, u32, bp, u32, ctypes.c_void_p, u64, u64, ctypes.POINTER(u32)]
-    return lib
+    bp, vp = ctypes.c_char_p, ctypes.c_void_p
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "seek_host_points": (i64, [u32, u32, u32]),
+        "seek_host_piece": (cuint, [bp, u32, u32, u32, u32p, u32p]),
+        "seek_host_band": (i64, [vp, u32, u32, u32, u32, bp, u32, vp, u64, u64, u32p])})
 
 
 def test_point_counts(host_lib):
@@ -132,11 +124,4 @@ def test_a_point_with_64_distinct_table_words(host_lib):
 
 
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main(), built with -fsanitize=address,undefined and the sanitizer runtimes linked statically: a program
-    of its own that needs nothing from its environment"""
-    exe = str(tmp_path / "seek_host_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-DSEEK_HOST_MAIN",
-                    "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "bands ok" in r.stdout and "runtime error" not in r.stderr
+    assert hostbuild.sanitized(SRC, "SEEK_HOST_MAIN", tmp_path) == "seek_host: 7344 bands ok\n"

@@ -5,31 +5,25 @@ tiles and a tail), through a memory functor that counts every load of a dword th
 stand-alone program with the address and undefined-behaviour sanitizers over heap buffers of exactly the image's dwords and run (a program
 of its own: nothing sanitized is loaded into this process)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import cuint, i64, u32, u64
 from qoi_amd import seekindex as si
 from test_seekindex_model import END, header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "seekpx_host.cpp")
+SRC = "seekpx_host.cpp"
 INTERVALS = [1, 3, 255, 256, 1023, 1024, 1025, 2064]
 
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("seekpxhost") / "libseekpx_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
-    u32, u64, vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p
-    lib.seekpx_host_points.restype = ctypes.c_longlong
-    lib.seekpx_host_points.argtypes = [vp, u64, u32, u32, u32, u32, vp, vp, vp, vp]
-    lib.seekpx_host_dwords.restype = ctypes.c_uint
-    lib.seekpx_host_dwords.argtypes = [u64, u32]
-    return lib
+    vp = ctypes.c_void_p
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "seekpx_host_points": (i64, [vp, u64, u32, u32, u32, u32, vp, vp, vp, vp]),
+        "seekpx_host_dwords": (cuint, [u64, u32])})
 
 
 def image(ipx, np_, ch, seed):
@@ -120,11 +114,4 @@ def test_dword_counts(host_lib):
 
 
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main(), built with -fsanitize=address,undefined and the sanitizer runtimes linked statically: a program
-    of its own that needs nothing from its environment; its heap buffers end with the image's last dword"""
-    exe = str(tmp_path / "seekpx_host_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                    "-DSEEKPX_HOST_MAIN", "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "tiles ok" in r.stdout and "runtime error" not in r.stderr
+    assert hostbuild.sanitized(SRC, "SEEKPX_HOST_MAIN", tmp_path) == "seekpx_host: 352 tiles ok\n"

@@ -4,15 +4,13 @@ for the sub-batches, qoi_amd/crops.py: plan for the rows.  The order of the tabl
 to what defines them.  The same source is built as a stand-alone program with the address and undefined-behaviour sanitizers and run (a
 program of its own: nothing sanitized is loaded into this process)."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
+import hostbuild
 from qoi_amd import crops, packplan
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "plan_host.cpp")
+SRC = "plan_host.cpp"
 DEFAULT = 1 << 30
 ONE = 64 * 48 * 4                                   # the slot of the GPU suites' 13 equal images
 EQUAL = [ONE] * 13
@@ -28,18 +26,14 @@ def arr(t, values):
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("planhost") / "libplan_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
     P = ctypes.POINTER
-    lib.plan_host_up256.restype = u64
-    lib.plan_host_up256.argtypes = [u64]
-    lib.plan_host_pack.argtypes = [P(u64), ci, u64, P(ci)]
-    lib.plan_host_stage.argtypes = [P(u64), ci, u64, P(ci), P(u64), P(u64)]
-    lib.plan_host_rows.argtypes = [P(u32), ci, P(u32), u64, P(ci), P(ci), P(u64), P(ci), P(ci), P(u64), P(u64)]
-    lib.plan_host_items.argtypes = [P(u32), ci, P(ci), ci, P(ci), ci, P(u64), P(u64), P(u32), P(u32), P(u32), P(u32)]
-    lib.plan_host_overlap.argtypes = [P(u64), P(u64), ci]
-    return lib
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "plan_host_up256": (u64, [u64]),
+        "plan_host_pack": (ci, [P(u64), ci, u64, P(ci)]),
+        "plan_host_stage": (ci, [P(u64), ci, u64, P(ci), P(u64), P(u64)]),
+        "plan_host_rows": (ci, [P(u32), ci, P(u32), u64, P(ci), P(ci), P(u64), P(ci), P(ci), P(u64), P(u64)]),
+        "plan_host_items": (ci, [P(u32), ci, P(ci), ci, P(ci), ci, P(u64), P(u64), P(u32), P(u32), P(u32), P(u32)]),
+        "plan_host_overlap": (ci, [P(u64), P(u64), ci])})
 
 
 def stage(lib, slots, staging):
@@ -185,11 +179,4 @@ def test_ranges_overlap(host_lib):
 
 
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main(), built with -fsanitize=address,undefined and the sanitizer runtimes linked statically: a program
-    of its own that needs nothing from its environment"""
-    exe = str(tmp_path / "plan_host_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-DPLAN_HOST_MAIN",
-                    "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "plans ok" in r.stdout and "runtime error" not in r.stderr
+    assert hostbuild.sanitized(SRC, "PLAN_HOST_MAIN", tmp_path) == "plan_host: 2001 plans ok\n"

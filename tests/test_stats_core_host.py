@@ -5,16 +5,15 @@ policy counts every load outside the region), every number of tiles per workgrou
 and inside it.  The same source is built as a stand-alone program with the address and undefined-behaviour sanitizers and run (a program of its
 own: nothing sanitized is loaded into this process)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import cuint, i64, u32, u32p, u64, u64p, ull
 from qoi_amd import pixelstats as ps
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "stats_host.cpp")
+SRC = "stats_host.cpp"
 T = ps.TILE_PX
 
 
@@ -26,20 +25,14 @@ class Acc(ctypes.Structure):
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("statshost") / "libstats_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
-    u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-    lib.stats_host_run.restype = ctypes.c_longlong
-    lib.stats_host_run.argtypes = [ctypes.POINTER(u32), u64, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(Acc), ctypes.POINTER(u32), ctypes.POINTER(u64)]
-    lib.stats_host_init.argtypes = [ctypes.POINTER(Acc)]
-    lib.stats_host_flags.restype = ctypes.c_uint
-    lib.stats_host_flags.argtypes = [ctypes.POINTER(Acc), u64]
-    lib.stats_host_tiles.restype = ctypes.c_ulonglong
-    lib.stats_host_tiles.argtypes = [u32, u32]
-    lib.stats_host_tile_px.restype = ctypes.c_uint
+    accp = ctypes.POINTER(Acc)
     assert ctypes.sizeof(Acc) == 128
-    return lib
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "stats_host_run": (i64, [u32p, u64, u32, u32, u32, u32, u32, u32, u32, accp, u32p, u64p]),
+        "stats_host_init": (None, [accp]),
+        "stats_host_flags": (cuint, [accp, u64]),
+        "stats_host_tiles": (ull, [u32, u32]),
+        "stats_host_tile_px": (cuint, [])})
 
 
 def run(lib, px, x, y, cw, ch, flags, per_wg, with_hist):
@@ -140,11 +133,4 @@ def test_a_lane_passes_32_bits(host_lib):
 
 
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main(), built with -fsanitize=address,undefined and the sanitizer runtimes linked statically: a program
-    of its own that needs nothing from its environment"""
-    exe = str(tmp_path / "stats_host_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-DSTATS_HOST_MAIN",
-                    "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "regions ok" in r.stdout and "runtime error" not in r.stderr
+    assert hostbuild.sanitized(SRC, "STATS_HOST_MAIN", tmp_path) == "stats_host: 72 regions ok\n"

@@ -5,22 +5,15 @@ sink, outputs of 1 x 1, 5 x 3 and 17 x 16, the output at every multiple of the e
 checks that each output byte is written exactly once, that no byte beside an output is written and that every store is naturally aligned.
 The narrowing to binary16 is compared with NumPy's over every exponent and around every tie.  The same source is built as a stand-alone
 program with the address and undefined-behaviour sanitizers and run (a program of its own: nothing sanitized is loaded into this process)."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import cint, f32, f32p, i64, u32, u32p, u64, u8p
 from qoi_amd import tensors
 from qoi_amd.tensors import BF16, CHW, F16, F32, HWC, U8
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "tensor_host.cpp")
-GUARD = 0xA5
-BASE = 1 << 20                      # the virtual address of out[0]: a multiple of 16
-BAND = 48
-
+SRC = "tensor_host.cpp"
 IMAGENET = tensors.normalise((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
 FORMATS = {"imagenet": IMAGENET, "unit": (np.full(4, 1 / 255, np.float32), np.zeros(4, np.float32)),
            "wild": (np.array([300.0, 1e-6, 2.4e-8, 1e-40], np.float32), np.array([-300.0, 6e-8, -1e-41, -0.0], np.float32)),
@@ -29,19 +22,12 @@ FORMATS = {"imagenet": IMAGENET, "unit": (np.full(4, 1 / 255, np.float32), np.ze
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("tensorhost") / "libtensor_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
-    u32, u64, f32 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float
-    u8p, fp = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_float)
-    lib.tensor_host_run.restype = ctypes.c_longlong
-    lib.tensor_host_run.argtypes = [ctypes.POINTER(u32), u32, u32, u32, u32, ctypes.c_int, u32, u32, fp, fp, u64, u64, u8p, u8p, u64]
-    lib.tensor_host_value.restype = u32
-    lib.tensor_host_value.argtypes = [u32, f32, f32, u32]
-    for f in (lib.tensor_host_f16, lib.tensor_host_bf16, lib.tensor_host_elem):
-        f.restype = u32
-        f.argtypes = [u32]
-    return lib
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "tensor_host_run": (i64, [u32p, u32, u32, u32, u32, cint, u32, u32, f32p, f32p, u64, u64, u8p, u8p, u64]),
+        "tensor_host_value": (u32, [u32, f32, f32, u32]),
+        "tensor_host_f16": (u32, [u32]),
+        "tensor_host_bf16": (u32, [u32]),
+        "tensor_host_elem": (u32, [u32])})
 
 
 def walk(lib, P, och, flags, warp, f, a):
@@ -49,18 +35,11 @@ def walk(lib, P, och, flags, warp, f, a):
     oh, ow = P.shape[:2]
     dtype, layout, scale, bias = f
     words = np.ascontiguousarray(P).view(np.uint32).reshape(-1)
-    B = ow * oh * och * tensors.ELEM[dtype]
-    out = np.full(BAND + a + B + BAND, GUARD, dtype=np.uint8)
-    writes = np.zeros(out.size, dtype=np.uint8)
-    u8p, fp = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_float)
-    stores = lib.tensor_host_run(words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ow, oh, och, flags, warp, dtype, layout, scale.ctypes.data_as(fp),
-                                 bias.ctypes.data_as(fp), BASE + BAND + a, BASE, out.ctypes.data_as(u8p), writes.ctypes.data_as(u8p), out.size)
+    band = hostbuild.Banded(ow * oh * och * tensors.ELEM[dtype], a)
+    stores = lib.tensor_host_run(words.ctypes.data_as(u32p), ow, oh, och, flags, warp, dtype, layout, scale.ctypes.data_as(f32p), bias.ctypes.data_as(f32p), *band.args)
     what = (dtype, layout, och, flags, warp, a, (ow, oh))
     assert stores >= 0, (what, stores)      # (negative: a store out of bounds or misaligned)
-    lo, hi = BAND + a, BAND + a + B
-    assert np.all(writes[lo:hi] == 1) and not writes[:lo].any() and not writes[hi:].any(), what
-    assert np.all(out[:lo] == GUARD) and np.all(out[hi:] == GUARD), what
-    return stores, out[lo:hi]
+    return stores, band.inside(what)
 
 
 @pytest.mark.parametrize("layout", [HWC, CHW])
@@ -118,11 +97,4 @@ def test_values_against_numpy(host_lib):
 
 
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main(), built with -fsanitize=address,undefined and the sanitizer runtimes linked statically: a program
-    of its own that needs nothing from its environment"""
-    exe = str(tmp_path / "tensor_host_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                    "-DTENSOR_HOST_MAIN", "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "items ok" in r.stdout and "runtime error" not in r.stderr
+    assert hostbuild.sanitized(SRC, "TENSOR_HOST_MAIN", tmp_path) == "tensor_host: 9216 items ok\n"

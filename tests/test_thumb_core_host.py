@@ -2,36 +2,24 @@
 (tests/host/thumb_host.cpp) and compared with the Python model qoi_amd/thumbs.py on the CPU: every cnt the factors 1..64 can produce, the
 extremes of the sums, random weighted blocks.  Every comparison is exact."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import cint, i64, u32, u32p, u8p
 from qoi_amd import thumbs
 from qoi_amd.thumbs import ALPHA_WEIGHTED, PLAIN
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("thumbhost") / "libthumb_host.so")
-    src = os.path.join(ROOT, "tests", "host", "thumb_host.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, src], check=True)
-    lib = ctypes.CDLL(out)
-    u32p = ctypes.POINTER(ctypes.c_uint32)
-    lib.thumb_host_pixels.restype = None
-    lib.thumb_host_pixels.argtypes = [u32p, u32p, ctypes.c_size_t, ctypes.c_int, u32p]
-    lib.thumb_host_div_round.restype = None
-    lib.thumb_host_div_round.argtypes = [u32p, u32p, ctypes.c_size_t, u32p]
-    lib.thumb_host_extent.restype = ctypes.c_uint32
-    lib.thumb_host_extent.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
-    lib.thumb_host_split.restype = None
-    lib.thumb_host_split.argtypes = [ctypes.c_uint32, u32p, u32p]
-    lib.thumb_host_cover.restype = ctypes.c_longlong
-    lib.thumb_host_cover.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8), u32p, u32p]
-    return lib
+    return hostbuild.shared("thumb_host.cpp", tmp_path_factory, {
+        "thumb_host_pixels": (None, [u32p, u32p, ctypes.c_size_t, cint, u32p]),
+        "thumb_host_div_round": (None, [u32p, u32p, ctypes.c_size_t, u32p]),
+        "thumb_host_extent": (u32, [u32, u32]),
+        "thumb_host_split": (None, [u32, u32p, u32p]),
+        "thumb_host_cover": (i64, [u32, u32, u32, u8p, u32p, u32p])})
 
 
 def ptr(a):

@@ -2,18 +2,17 @@
 and compared with the Python model qoi_amd/tiles.py on the CPU: every item of every tile of small sources at odd byte offsets, both channel
 counts in and out, both modes, all four flips, factors with every lane split.  The host's memory functor checks every address: a 4-byte load
 is aligned and holds a byte of the image, a 16-byte load lies inside it, a store is an aligned word of the slot.  Every comparison is exact.
-The same file with a main of its own is built with -fsanitize=address,undefined and run directly over the same cases."""
+The same file with a main of its own is built with the address and undefined-behaviour sanitizers and run directly over the same cases."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import cint, i64, u32, u64, u8p
 from qoi_amd import tiles
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "tile_host.cpp")
+SRC = "tile_host.cpp"
 FACTORS = (1, 2, 3, 4, 5, 8, 13, 16, 33, 64)
 # (w, h, sch, byte offset of the image from a 16-aligned address)
 SOURCES = [(1, 1, 3, 0), (1, 1, 4, 2), (1, 130, 3, 2), (1, 130, 4, 0), (37, 29, 3, 1), (70, 45, 4, 3), (64, 40, 4, 0)]
@@ -21,15 +20,9 @@ SOURCES = [(1, 1, 3, 0), (1, 1, 4, 2), (1, 130, 3, 2), (1, 130, 4, 0), (37, 29, 
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("tilehost") / "libtile_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
-    u8p, u32 = ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint32
-    lib.tile_host_run.restype = ctypes.c_longlong
-    lib.tile_host_run.argtypes = [ctypes.c_void_p, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, ctypes.c_int, u8p]
-    lib.tile_host_tiles.restype = ctypes.c_uint64
-    lib.tile_host_tiles.argtypes = [u32, u32, u32, u32]
-    return lib
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "tile_host_run": (i64, [ctypes.c_void_p, u32, u32, u32, u32, u32, u32, u32, u32, u32, u32, cint, u8p]),
+        "tile_host_tiles": (u64, [u32, u32, u32, u32])})
 
 
 def aligned(nbytes, align=256):
@@ -122,8 +115,4 @@ def test_sum_extremes(host_lib):
 
 def test_standalone_program_under_sanitizers(tmp_path):
     """tile_host.cpp with its own main and its own double-loop model, built with AddressSanitizer and UndefinedBehaviorSanitizer, run directly"""
-    exe = str(tmp_path / "tile_host_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-DTILE_HOST_MAIN", "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and "tiles ok" in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-2000:])
+    assert hostbuild.sanitized(SRC, "TILE_HOST_MAIN", tmp_path) == "tile_host: 3360 tiles ok\n"

@@ -9,36 +9,24 @@ exactly once.  Items without the flag walk warp_pixel / warp_nearest through the
 stand-alone program with the address and undefined-behaviour sanitizers and run (a program of its own: nothing sanitized is loaded into
 this process)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import cint, cuint, i64, i64p, u32, u32p, u64, u8p
 from qoi_amd import warp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "warp_bicubic_host.cpp")
-GUARD = 0xA5
+SRC = "warp_bicubic_host.cpp"
 SENTINEL = 0x5A
-BASE = 1 << 20                      # the virtual address of out[0]: a multiple of 16
-BAND = 48
-u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-u8p = ctypes.POINTER(ctypes.c_uint8)
 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("warpbicubichost") / "libwarp_bicubic_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
-    lib.warp_bicubic_host_run.restype = ctypes.c_longlong
-    lib.warp_bicubic_host_run.argtypes = [ctypes.POINTER(u32), u64, u32, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_longlong), u32, u32, ctypes.c_int,
-                                          u64, u64, u8p, u8p, u64]
-    lib.warp_bicubic_host_flag.restype = ctypes.c_uint
-    lib.warp_bicubic_host_weights.argtypes = [u32, ctypes.POINTER(ctypes.c_int32)]
-    lib.warp_bicubic_host_weights.restype = None
-    return lib
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "warp_bicubic_host_run": (i64, [u32p, u64, u32, u32, u32, u32, u32, u32, u32, u32, i64p, u32, u32, cint, u64, u64, u8p, u8p, u64]),
+        "warp_bicubic_host_flag": (cuint, []),
+        "warp_bicubic_host_weights": (None, [u32, ctypes.POINTER(ctypes.c_int32)])})
 
 
 def staged(rect, margin, seed):
@@ -56,18 +44,12 @@ def staged(rect, margin, seed):
 def run(lib, px, dwords, rect, out_size, matrix, flags, fill, och, mode, a):
     x, y, cw, rh = rect
     ow, oh = out_size
-    B = ow * oh * och
-    out = np.full(BAND + a + B + BAND, GUARD, dtype=np.uint8)
-    writes = np.zeros(out.size, dtype=np.uint8)
+    band = hostbuild.Banded(ow * oh * och, a)
     m = (ctypes.c_longlong * 6)(*matrix)
-    loads = lib.warp_bicubic_host_run(dwords.ctypes.data_as(ctypes.POINTER(u32)), dwords.size, px.shape[1], x, y, cw, rh, ow, oh, flags, m, fill, och, mode,
-                                      BASE + BAND + a, BASE, out.ctypes.data_as(u8p), writes.ctypes.data_as(u8p), out.size)
+    loads = lib.warp_bicubic_host_run(dwords.ctypes.data_as(u32p), dwords.size, px.shape[1], x, y, cw, rh, ow, oh, flags, m, fill, och, mode, *band.args)
     what = (rect, out_size, matrix, flags, och, mode, a)
     assert loads >= 0, (what, loads)                                  # no load outside the rectangle, no store outside the output or unaligned
-    lo, hi = BAND + a, BAND + a + B
-    assert np.all(writes[lo:hi] == 1) and not writes[:lo].any() and not writes[hi:].any(), what
-    assert np.all(out[:lo] == GUARD) and np.all(out[hi:] == GUARD), what
-    return loads, out[lo:hi]
+    return loads, band.inside(what)
 
 
 def loads_of(rect, out_size, matrix, flags):
@@ -139,16 +121,5 @@ def test_items_without_the_flag_walk_as_before(lib, mode):
             assert loads <= (1 if flags & warp.NEAREST else 4) * 33 * 18
 
 
-def build_and_run(tmp_path, src, define, name):
-    exe = str(tmp_path / name)
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                    "-D" + define, "-o", exe, src], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "items ok" in r.stdout and "runtime error" not in r.stderr
-
-
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main(), built with -fsanitize=address,undefined and the sanitizer runtimes linked statically: a program
-    of its own that needs nothing from its environment"""
-    build_and_run(tmp_path, SRC, "WARP_BICUBIC_HOST_MAIN", "warp_bicubic_host_main")
+    assert hostbuild.sanitized(SRC, "WARP_BICUBIC_HOST_MAIN", tmp_path) == "warp_bicubic_host: 2688 items ok\n"

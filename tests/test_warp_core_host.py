@@ -7,38 +7,25 @@ written, that every store is naturally aligned and that no load falls outside th
 source is built as a stand-alone program with the address and undefined-behaviour sanitizers and run (a program of its own: nothing
 sanitized is loaded into this process)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+from hostbuild import cint, i64, i64p, u32, u32p, u64, u8p, ull, ullp
 from qoi_amd import warp
 from qoi_amd.warp import ALPHA_WEIGHTED, ONE, PLAIN, REPLICATE
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "warp_host.cpp")
-GUARD = 0xA5
-BASE = 1 << 20                      # the virtual address of out[0]: a multiple of 16
-BAND = 48
+SRC = "warp_host.cpp"
 FILL = 0x40C08020
 
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("warphost") / "libwarp_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
-    u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    lib.warp_host_run.restype = ctypes.c_longlong
-    lib.warp_host_run.argtypes = [ctypes.POINTER(u32), u64, u32, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_longlong), u32, u32, ctypes.c_int, u64, u64,
-                                  u8p, u8p, u64, ctypes.POINTER(ctypes.c_ulonglong)]
-    lib.warp_host_tiles.restype = ctypes.c_ulonglong
-    lib.warp_host_tiles.argtypes = [u32, u32]
-    lib.warp_host_place.restype = ctypes.c_int
-    lib.warp_host_place.argtypes = [u32, u32, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
-    return lib
+    return hostbuild.shared(SRC, tmp_path_factory, {
+        "warp_host_run": (i64, [u32p, u64, u32, u32, u32, u32, u32, u32, u32, u32, i64p, u32, u32, cint, u64, u64, u8p, u8p, u64, ullp]),
+        "warp_host_tiles": (ull, [u32, u32]),
+        "warp_host_place": (cint, [u32, u32, u32, u32, u32p, u32p])})
 
 
 def staged(w, rows, seed):
@@ -55,21 +42,14 @@ def run(lib, px, dwords, rect, out_size, m, flags, och, mode, a):
     """one item written at BASE + BAND + a; returns (tiles walked, loads, output bytes); asserts guards and the write counts"""
     x, y, cw, rh = rect
     ow, oh = out_size
-    B = ow * oh * och
-    out = np.full(BAND + a + B + BAND, GUARD, dtype=np.uint8)
-    writes = np.zeros(out.size, dtype=np.uint8)
-    u8p = ctypes.POINTER(ctypes.c_uint8)
+    band = hostbuild.Banded(ow * oh * och, a)
     tiles = ctypes.c_ulonglong(0)
-    loads = lib.warp_host_run(dwords.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), dwords.size, px.shape[1], x, y, cw, rh, ow, oh, flags,
-                              (ctypes.c_longlong * 6)(*m), FILL, och, mode, BASE + BAND + a, BASE, out.ctypes.data_as(u8p), writes.ctypes.data_as(u8p), out.size,
-                              ctypes.byref(tiles))
+    loads = lib.warp_host_run(dwords.ctypes.data_as(u32p), dwords.size, px.shape[1], x, y, cw, rh, ow, oh, flags, (ctypes.c_longlong * 6)(*m), FILL, och, mode,
+                              *band.args, ctypes.byref(tiles))
     what = (och, mode, a, flags, rect, out_size, m)
     assert loads >= 0, (what, loads)      # (negative: a load outside the rectangle, a store out of bounds or misaligned)
     assert tiles.value == warp.tiles(ow, oh) == lib.warp_host_tiles(ow, oh), what
-    lo, hi = BAND + a, BAND + a + B
-    assert np.all(writes[lo:hi] == 1) and not writes[:lo].any() and not writes[hi:].any(), what
-    assert np.all(out[:lo] == GUARD) and np.all(out[hi:] == GUARD), what
-    return tiles.value, loads, out[lo:hi]
+    return tiles.value, loads, band.inside(what)
 
 
 def maps(cw, rh, ow, oh):
@@ -131,11 +111,4 @@ def test_place_and_tiles(host_lib):
 
 
 def test_sanitized_stand_alone_program(tmp_path):
-    """the same source with its own main(), built with -fsanitize=address,undefined and the sanitizer runtimes linked statically: a program
-    of its own that needs nothing from its environment"""
-    exe = str(tmp_path / "warp_host_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                    "-DWARP_HOST_MAIN", "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout, r.stderr)
-    assert "items ok" in r.stdout and "runtime error" not in r.stderr
+    assert hostbuild.sanitized(SRC, "WARP_HOST_MAIN", tmp_path) == "warp_host: 2016 items ok\n"
