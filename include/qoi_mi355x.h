@@ -281,12 +281,34 @@ int qoimi_encode_images_packed(qoimi_ctx *ctx, const void *d_pixels, const size_
  * qoimi_encode_status returns QOIMI_OK and never encodes again.
  * QOIMI_E_ARG, reported before anything is launched (the caller's buffers are untouched, qoimi_last_error names the cause): NULL ctx, d_pixels,
  * pixel_offsets, descs, tiles, d_packed_off or d_stream_len; n_images <= 0 or n_tiles <= 0; d_packed == NULL with a non-zero capacity; align not
- * a power of two in 1..256; channels not 0 / 3 / 4; a mode that is neither of the two; tiles[j].image >= n_images; a rejected referenced
+ * a power of two in 1..256; channels not 0 / 3 / 4; a mode that is none of the four; tiles[j].image >= n_images; a rejected referenced
  * descriptor; a zero width or height; a rectangle that leaves its image; a factor outside 1..64; a flag bit other than the two flips;
- * reserved != 0; a referenced image whose last byte's address does not fit in a pointer; a referenced image whose bytes overlap [d_packed,
+ * reserved != 0; a factor above 16 with QOIMI_TILE_MODE; a referenced image whose last byte's address does not fit in a pointer; a referenced image whose bytes overlap [d_packed,
  * + packed_capacity); a sub-batch of the plan with 2^31 - 1 or more tiles of 256 work items of the gather kernel (an item is one aligned
  * 16-byte word of a tile's pixels at factor 1, else 1 to 16 per output pixel).  One call at a time per context, as everywhere.
- * Not here: sources that are a pack (decode once with qoimi_decode_images), other filters, row-pitched sources, a channel count per tile. */
+ * Label maps (segmentation masks, instance ids, palette indices) - the mean of class 3 and class 7 is class 5 - take one of two further
+ * values of `mode`, which this call alone accepts (qoimi_decode_thumbnails keeps rejecting them, and 2, 3 and every other value stay no
+ * mode).  The definition (normative; qoi_amd/tiles.py: tile states it in Python).  S, R, width = cw, height = ch, f = factor, tw = ceil(cw /
+ * f) and th = ceil(ch / f) are as above; R is taken at 4 bytes per pixel: a 3-channel source has alpha 255, and that alpha takes part.  The
+ * block of output pixel (X, Y) is the box filter's, partial blocks at the right and bottom edge included: columns [X*f, min((X+1)*f, cw)),
+ * nx of them, rows [Y*f, min((Y+1)*f, ch)), ny of them.  The block's centre pixel is column X*f + nx/2, row Y*f + ny/2 (the divisions floor).
+ *   QOIMI_TILE_NEAREST  the output pixel is the centre pixel, byte for byte: a selection, at any factor 1..64
+ *   QOIMI_TILE_MODE     the vote of QOIMI_FILTER_MODE (qoi_amd/mode.py: vote) over the block: whole pixels vote, all four bytes; the largest
+ *                       count wins; of several winners the centre pixel wins if it is one of them, otherwise the lowest r << 24 | g << 16 |
+ *                       b << 8 | a.  A tile with factor > 16 is QOIMI_E_ARG (a block holds at most 16 x 16 pixels, the limit of
+ *                       QOIMI_FILTER_MODE), reported per tile behind the reserved != 0 check, before anything is launched
+ * What follows the reduction is what follows the box filter: the flips, the conversion to och - 4 to 3 drops alpha AFTER the vote, so two
+ * colours that differ in alpha alone vote apart; 3 to 4 sets 255 -, the reference encoder's stream byte for byte, the pack, the tables,
+ * the capacity rules and the plan (the modes change no size: qoimi_tile_size has no mode argument).  factor == 1 is the rectangle itself
+ * in both modes; a constant block gives the constant.  With f dividing cw and ch, a 4-channel source and och 4, a QOIMI_TILE_MODE tile is
+ * what qoimi_decode_tensors gives with QOIMI_FILTER_MODE (u8, HWC) for the same rectangle at tw x th, byte for byte - its cells are then
+ * the f-blocks and its nearest sample is Z*f + f/2 -, and a QOIMI_TILE_NEAREST tile is what QOIMI_FILTER_NEAREST gives.  Of the seven
+ * levels of qoimi_tile_pyramid five (f = 1 .. 16) can vote; levels 5 and 6 (f = 32, 64) need QOIMI_TILE_NEAREST.  The two modes run a
+ * gather kernel of their own over the same table; qoimi_tile_stats counts its launches in [1].
+ * Not here: sources that are a pack (decode once with qoimi_decode_images), filters other than the box average, the selection and the vote,
+ * a vote over blocks above 16 x 16, a vote per channel, a mode per tile, QOIMI_TILE_NEAREST / QOIMI_TILE_MODE in qoimi_decode_thumbnails
+ * (qoimi_decode_tensors serves them), row-pitched sources, a channel count per tile. */
+enum { QOIMI_TILE_NEAREST = 4, QOIMI_TILE_MODE = 5 };   /* 2 and 3 are not modes */
 typedef struct {                 /* 32 bytes, offsets 0/4/8/12/16/20/24/28 */
     unsigned int image;          /* index into the call's images */
     unsigned int x, y;           /* top-left corner of the source rectangle */
@@ -296,7 +318,7 @@ typedef struct {                 /* 32 bytes, offsets 0/4/8/12/16/20/24/28 */
     unsigned int reserved;       /* 0 */
 } qoimi_tile;
 int qoimi_encode_tiles(qoimi_ctx *ctx, const void *d_pixels, const size_t *pixel_offsets /* host */, const qoi_desc *descs /* host */, int n_images,
-                       int channels /* 0, 3, 4 */, const qoimi_tile *tiles /* host */, int n_tiles, int mode /* QOIMI_THUMB_PLAIN / _ALPHA_WEIGHTED */,
+                       int channels /* 0, 3, 4 */, const qoimi_tile *tiles /* host */, int n_tiles, int mode /* QOIMI_THUMB_PLAIN / _ALPHA_WEIGHTED, QOIMI_TILE_NEAREST / _MODE */,
                        unsigned align, void *d_packed, size_t packed_capacity,
                        unsigned long long *d_packed_off /* device, n_tiles + 1 */, int *d_stream_len /* device, n_tiles */, size_t staging_bytes,
                        unsigned long long *packed_off_out /* host, may be NULL */, int *stream_len_out /* host, may be NULL */,

@@ -496,7 +496,9 @@ class Context:
         """Tiles and pyramid levels of device images -> pack in one call through bounded staging (``qoimi_encode_tiles``, synchronous):
         (offsets uint64[n + 1], sizes int32[n], tile descriptors) - what ``decode_images`` and the gather calls take to serve the pack.
         tiles: ``QoimiTile`` structures or (image, x, y, width, height, factor[, flags]) tuples; mode: ``tiles.PLAIN`` /
-        ``tiles.ALPHA_WEIGHTED``; channels 0: every tile keeps its image's channel count; ``qoi_amd/tiles.py: tile`` states the pixels."""
+        ``tiles.ALPHA_WEIGHTED`` (the box average) or, for label maps, ``tiles.NEAREST`` (the centre pixel of every block) / ``tiles.MODE`` (the
+        majority vote of ``FILTER_MODE`` over every block; factor <= 16); channels 0: every tile keeps its image's channel count;
+        ``qoi_amd/tiles.py: tile`` states the pixels."""
         n_images = len(descs)
         seqs = self._per_image("encode_tiles", "pixel offset per descriptor", n_images, pixel_offsets=pixel_offsets, descs=descs)
         shortest, longest, noun, malformed = _ITEMS[QoimiTile]

@@ -106,7 +106,7 @@ struct qoimi_ctx {
     Arena enc_ws, dec_ws;       // kernel workspaces
     Arena enc_stage;            // qoimi_encode_packed: the strided streams of one sub-batch (and the source offsets of a mixed-shape call) on their way into the pack;
                                 // qoimi_encode_tiles: the same, every stream behind the gathered pixels of its tile, and the tile table
-    long long tile_stats[4] = {0, 0, 0, 0};    // the last qoimi_encode_tiles call: sub-batches, launches of tile_gather, bytes of staging planned, images referenced
+    long long tile_stats[4] = {0, 0, 0, 0};    // the last qoimi_encode_tiles call: sub-batches, launches of tile_gather (of tile_select in the label modes), bytes of staging planned, images referenced
     Arena insp_ws;              // tables, maps and partial counts of qoimi_inspect_streams (its own: a decode call finds dec_ws as it left it)
     Arena cmp_ws;               // image table and result table of qoimi_compare_images / qoimi_verify_images; the table (and results) of run_staged and of the band assembly
     Arena ver_stage;            // qoimi_verify_images and every call of run_staged (qoi_staged.h: thumbnails, crops, resized, bilinear, warped, pixel statistics, the seek index build): the decoded pixels of one sub-batch (sized to the plan's largest sub-batch plus a page: no slack)

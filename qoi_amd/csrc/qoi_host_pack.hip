@@ -145,6 +145,7 @@ static_assert(sizeof(qoimi_tile) == 32 && offsetof(qoimi_tile, image) == 0 && of
               offsetof(qoimi_tile, width) == 12 && offsetof(qoimi_tile, height) == 16 && offsetof(qoimi_tile, factor) == 20 &&
               offsetof(qoimi_tile, flags) == 24 && offsetof(qoimi_tile, reserved) == 28, "qoimi_tile layout");
 static_assert(QOIMI_CROP_FLIP_X == (int)kCropFlipX && QOIMI_CROP_FLIP_Y == (int)kCropFlipY, "the table's flag bits");
+static_assert(QOIMI_TILE_NEAREST == 4 && QOIMI_TILE_MODE == 5 && kTileModeMaxFactor == 16u, "2 and 3 are not modes; a block votes over at most 16 x 16 pixels");
 
 // nullptr if the tile is fine for an accepted descriptor, else what is wrong with it
 static const char* tile_wrong(const qoi_desc* d, const qoimi_tile* t) {
@@ -192,7 +193,8 @@ extern "C" int qoimi_tile_pyramid(const qoi_desc* desc, unsigned tile_w, unsigne
 }
 
 // Tile j's slot: up256 of its pixels, then up256 of its encode bound; sub-batches by stage_plan over those slots in tile order
-// (qoi_amd/tiles.py: plan).  Every sub-batch: one launch of tile_gather over its tiles, then the loop of encode_packed as it is.
+// (qoi_amd/tiles.py: plan).  Every sub-batch: one launch of tile_gather - of tile_select in QOIMI_TILE_NEAREST / QOIMI_TILE_MODE, which
+// change the reduction and the count of work items, no size - over its tiles, then the loop of encode_packed as it is.
 extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size_t* pixel_offsets, const qoi_desc* descs, int n_images, int channels,
                                   const qoimi_tile* tiles, int n_tiles, int mode, unsigned align, void* d_packed, size_t packed_capacity,
                                   unsigned long long* d_packed_off, int* d_stream_len, size_t staging_bytes, unsigned long long* packed_off_out,
@@ -202,7 +204,10 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
         (!d_packed && packed_capacity != 0)) return fail(QOIMI_E_ARG, "NULL/empty argument");
     if (align == 0 || align > 256u || (align & (align - 1u)) != 0) return fail(QOIMI_E_ARG, "align must be a power of two, 1..256");
     if (const int rc = check_out_channels(channels)) return rc;
-    if (mode != QOIMI_THUMB_PLAIN && mode != QOIMI_THUMB_ALPHA_WEIGHTED) return fail(QOIMI_E_ARG, "mode must be QOIMI_THUMB_PLAIN or QOIMI_THUMB_ALPHA_WEIGHTED");
+    if (mode != QOIMI_THUMB_PLAIN && mode != QOIMI_THUMB_ALPHA_WEIGHTED && mode != QOIMI_TILE_NEAREST && mode != QOIMI_TILE_MODE)
+        return fail(QOIMI_E_ARG, "mode must be QOIMI_THUMB_PLAIN, QOIMI_THUMB_ALPHA_WEIGHTED, QOIMI_TILE_NEAREST or QOIMI_TILE_MODE");
+    // the kind of every entry of the call's table: the label modes run tile_select, the box filter tile_gather as ever
+    const uint32_t kind = mode == QOIMI_TILE_NEAREST ? kTileKindNearest : mode == QOIMI_TILE_MODE ? kTileKindMode : kTileKindBox;
     const size_t n = (size_t)n_tiles;
     std::vector<uint8_t> named((size_t)n_images, 0);
     for (size_t j = 0; j < n; ++j) {
@@ -213,6 +218,8 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
             named[t.image] = 1;
         }
         if (const char* what = tile_wrong(&descs[t.image], &t)) return fail(QOIMI_E_ARG, "tile " + std::to_string(j) + ": " + what);
+        if (kind == kTileKindMode && t.factor > kTileModeMaxFactor)
+            return fail(QOIMI_E_ARG, "tile " + std::to_string(j) + ": factor above 16 with QOIMI_TILE_MODE (a block votes over at most 16 x 16 pixels; QOIMI_TILE_NEAREST has no such limit)");
     }
     long long referenced = 0;
     for (size_t i = 0; i < named.size(); ++i) {
@@ -242,7 +249,8 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
         for (int j = plan.firsts[k]; j < plan.firsts[k + 1]; ++j) {
             if (sum >= 0x7FFFFFFFull) break;
             first_tile[(size_t)j] = (uint32_t)sum;
-            sum += tile_tiles(tiles[j].width, tiles[j].height, tiles[j].factor, td[(size_t)j].channels);
+            sum += kind == kTileKindBox ? tile_tiles(tiles[j].width, tiles[j].height, tiles[j].factor, td[(size_t)j].channels)
+                                        : tile_select_tiles(kind, tiles[j].width, tiles[j].height, tiles[j].factor, td[(size_t)j].channels);
         }
         if (sum >= 0x7FFFFFFFull) return fail(QOIMI_E_ARG, "more than 2^31 tiles of work items of the gather kernel in one sub-batch");
         sub_tiles[k] = (uint32_t)sum;
@@ -261,16 +269,17 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
                 e.src_off = (u64)pixel_offsets[t.image]; e.dst_off = (u64)plan.at[j];
                 e.w = d.width; e.x = t.x; e.y = t.y; e.cw = t.width; e.ch = t.height; e.tw = td[j].width; e.th = td[j].height; e.f = t.factor;
                 e.first_tile = first_tile[j];
-                e.cfg = tile_cfg(t.factor, d.channels, td[j].channels, mode == QOIMI_THUMB_ALPHA_WEIGHTED && d.channels == 4u, t.flags);   // with 3 source channels the mode is PLAIN
+                e.cfg = kind == kTileKindBox ? tile_cfg(t.factor, d.channels, td[j].channels, mode == QOIMI_THUMB_ALPHA_WEIGHTED && d.channels == 4u, t.flags)   // with 3 source channels the mode is PLAIN
+                                             : tile_select_cfg(kind, t.factor, d.channels, td[j].channels, t.flags);
             }
             d_tab = (const TileEntry*)d_extra;
             return (int)QOIMI_OK;
         },
         [&](size_t k, int first, int m, uint8_t* staging, hipStream_t st) {
             stats[0] += 1;
-            launch_tile_gather((const uint8_t*)d_pixels, d_tab + first, (uint32_t)m, sub_tiles[k], staging, grid_bound(c, sub_tiles[k]), st);
+            (kind == kTileKindBox ? launch_tile_gather : launch_tile_select)((const uint8_t*)d_pixels, d_tab + first, (uint32_t)m, sub_tiles[k], staging, grid_bound(c, sub_tiles[k]), st);
             const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(QOIMI_E_INTERNAL, std::string("tile_gather: ") + hipGetErrorString(e));
+            if (e != hipSuccess) return fail(QOIMI_E_INTERNAL, std::string(kind == kTileKindBox ? "tile_gather: " : "tile_select: ") + hipGetErrorString(e));
             stats[1] += 1;
             return (int)QOIMI_OK;
         });

@@ -16,6 +16,7 @@
 //            the place of the image.
 // A pixel at the byte address A is read as the aligned dword that holds A and - only where the pixel reaches into it - the next one: never
 // a word that holds no byte of the image.
+// The two reductions for label maps - a selection and a majority vote in the place of the box average - stand at the end of this file.
 //
 // Plain sequential code over a memory functor `Mem` (load4(aligned address) -> dword, load16(16-aligned address, dwords), store16(address,
 // dwords)), compiled for the device by hipcc (qoi_tile.hip) and - by tests/host/tile_host.cpp only - for the host, where the functor checks
@@ -24,6 +25,7 @@
 #include <stdint.h>
 
 #include "qoi_crop_core.h"
+#include "qoi_mode_core.h"
 #include "qoi_thumb_core.h"
 
 namespace qoimi {
@@ -132,6 +134,86 @@ QOIMI_CROP_HD uint32_t tile_dest(const TileEntry& e, uint32_t o) {
     const uint32_t flags = e.cfg >> 28;
     const uint32_t Y = o / e.tw, X = o - Y * e.tw;
     return ((flags & kCropFlipY) != 0u ? e.th - 1u - Y : Y) * e.tw + ((flags & kCropFlipX) != 0u ? e.tw - 1u - X : X);
+}
+
+// ---- QOIMI_TILE_NEAREST / QOIMI_TILE_MODE: label maps (the kernel tile_select) ----
+//
+// The definition (normative; qoi_amd/tiles.py: tile states it in Python).  The rectangle is taken at 4 bytes per pixel - a 3-byte pixel has
+// alpha 255, and that alpha takes part.  The block of output pixel (X, Y) is the box filter's: columns [X * f, min((X + 1) * f, cw)), nx of
+// them, rows [Y * f, min((Y + 1) * f, ch)), ny of them; its centre pixel is column X * f + nx / 2, row Y * f + ny / 2 (the divisions
+// floor).  NEAREST: the output pixel is the centre pixel.  MODE: the vote of qoi_mode_core.h over the block - whole pixels vote, the largest
+// count wins, of several winners the centre pixel if it is one, else the lowest r << 24 | g << 16 | b << 8 | a -, f <= kTileModeMaxFactor:
+// a block is at most 16 x 16.  Flips, och and the slot as above; 4 to 3 drops alpha after the vote.
+//
+// The kind stands in bits 25..27 of cfg (0: the box filter above; bit 24 is its alone), and for the two kinds here bits 0..15 hold the
+// vote's split, mode_split(f, f, 1, 1), in the place of thumb_split's: L = 2^lg neighbouring lanes share an output pixel, item i of the entry
+// is lane i % L of output pixel i / L (row-major, unflipped) and holds the pixels p = l, l + L, l + 2L, l + 3L below nx * ny of its block,
+// p being column p % nx and row p / nx.  NEAREST and f == 1 have lg = 0, c = 1.  f == 1 is tile_copy_item in both kinds.
+constexpr uint32_t kTileKindBox = 0, kTileKindNearest = 1, kTileKindMode = 2;
+constexpr uint32_t kTileModeMaxFactor = kModeMaxRatio;
+
+QOIMI_CROP_HD uint32_t tile_select_cfg(uint32_t kind, uint32_t f, uint32_t sch, uint32_t och, uint32_t flags) {
+    uint32_t lg = 0u, c = 1u;
+    if (kind == kTileKindMode) mode_split(f, f, 1u, 1u, lg, c);
+    return lg | (c << 8) | (sch << 16) | (och << 20) | (kind << 25) | (flags << 28);
+}
+
+// Items of a tile of the two kinds (f == 1: the copy's) and the tiles of kTileThreads items they take.  (cw * ch < 400 000 000 and f >= 2:
+// fewer than 2^28 output pixels of at most 64 lanes; the kernel numbers items in 64 bits.)
+QOIMI_CROP_HD uint64_t tile_select_items(uint32_t kind, uint32_t cw, uint32_t ch, uint32_t f, uint32_t och) {
+    if (f == 1u) return tile_items(cw, ch, 1u, och);
+    return ((uint64_t)thumb_extent(cw, f) * thumb_extent(ch, f)) << (tile_select_cfg(kind, f, 0u, 0u, 0u) & 255u);
+}
+QOIMI_CROP_HD uint64_t tile_select_tiles(uint32_t kind, uint32_t cw, uint32_t ch, uint32_t f, uint32_t och) {
+    return (tile_select_items(kind, cw, ch, f, och) + kTileThreads - 1u) / kTileThreads;
+}
+
+// The block of pixel o (row-major) of the reduced rectangle: its first column and row within the rectangle and its extent.
+struct TileBlock { uint32_t x0, y0, nx, ny; };
+QOIMI_CROP_HD TileBlock tile_block(const TileEntry& e, uint32_t o) {
+    const uint32_t Y = o / e.tw, X = o - Y * e.tw;
+    const uint32_t x0 = X * e.f, y0 = Y * e.f;
+    return {x0, y0, e.cw - x0 < e.f ? e.cw - x0 : e.f, e.ch - y0 < e.f ? e.ch - y0 : e.f};
+}
+
+// The pixel at column k, row r of the rectangle.
+template <uint32_t SCH, class Mem>
+QOIMI_CROP_HD uint32_t tile_rect_pixel(const Mem& mem, const TileEntry& e, uint64_t base, uint32_t k, uint32_t r) {
+    return tile_fetch<SCH>(mem, base + ((uint64_t)(e.y + r) * e.w + e.x + k) * SCH);
+}
+
+// NEAREST: the centre pixel of the block of pixel o < tw * th.
+template <uint32_t SCH, class Mem>
+QOIMI_CROP_HD uint32_t tile_centre_pixel(const Mem& mem, const TileEntry& e, uint64_t base, uint32_t o) {
+    const TileBlock b = tile_block(e, o);
+    return tile_rect_pixel<SCH>(mem, e, base, b.x0 + b.nx / 2u, b.y0 + b.ny / 2u);
+}
+
+// MODE: what lane l of 2^lg holds of the block of pixel o < tw * th (mode_hold over the block).
+template <uint32_t SCH, class Mem>
+QOIMI_CROP_HD void tile_vote_hold(const Mem& mem, const TileEntry& e, uint64_t base, uint32_t o, uint32_t l, uint32_t lg, ModeHeld& h) {
+    const TileBlock b = tile_block(e, o);
+    const uint32_t pc = (b.ny / 2u) * b.nx + b.nx / 2u;
+    mode_none(h);
+    QOIMI_CROP_UNROLL
+    for (uint32_t j = 0; j < kModeHold; ++j) {
+        const uint32_t p = l + (j << lg);
+        if (p < b.nx * b.ny) {
+            const uint32_t pr = p / b.nx, pk = p - pr * b.nx;
+            h.v[j] = tile_rect_pixel<SCH>(mem, e, base, b.x0 + pk, b.y0 + pr);
+            h.n = j + 1u;
+            if (p == pc) h.centre = j;
+        }
+    }
+}
+
+// The store of pixel o of the reduced rectangle into the output at the address q (4-aligned): a dword at och == 4, three bytes at och == 3.
+template <class Mem>
+QOIMI_CROP_HD void tile_put(const Mem& mem, const TileEntry& e, uint64_t q, uint32_t o, uint32_t px) {
+    const uint32_t och = (e.cfg >> 20) & 15u;
+    const uint64_t a = q + (uint64_t)tile_dest(e, o) * och;
+    if (och == 4u) mem.store4(a, px);
+    else { mem.store1(a, px & 255u); mem.store1(a + 1u, (px >> 8) & 255u); mem.store1(a + 2u, (px >> 16) & 255u); }
 }
 
 }  // namespace qoimi

@@ -8,6 +8,24 @@ as well.  With S the image as ``uint8[h, w, sch]``: ``R = S[y:y+height, x:x+widt
 0): 4 to 3 drops alpha - after the reduction -, 3 to 4 sets alpha to 255.  Stream j of the call is the reference encoder's stream of T with
 the descriptor ``(tw, th, och, colorspace of the image)``.
 
+Label maps (the mean of class 3 and class 7 is class 5) take ``mode = NEAREST`` or ``mode = MODE`` in the place of the box average - values
+``qoimi_encode_tiles`` alone accepts.  R is taken at 4 bytes per pixel: a 3-channel source has alpha 255, and that alpha takes part.  The block
+of output pixel (X, Y) is the box filter's, partial blocks at the right and bottom edge included: columns ``[X*f, min((X+1)*f, cw))``, nx of
+them, rows ``[Y*f, min((Y+1)*f, ch))``, ny of them; its centre pixel is column ``X*f + nx // 2``, row ``Y*f + ny // 2``.
+
+* ``NEAREST``: the output pixel is the centre pixel, byte for byte; any factor 1..64.
+* ``MODE``: ``mode.vote`` over the block - whole pixels vote, all four bytes; the largest count wins; of several winners the centre pixel wins
+  if it is one of them, otherwise the lowest ``r << 24 | g << 16 | b << 8 | a``.  ``factor <= MODE_MAX_FACTOR = 16``: a block holds at most
+  16 x 16 pixels, the limit of ``FILTER_MODE``.
+
+The flips and the conversion to och follow as above (4 to 3 drops alpha after the vote).  ``factor == 1`` is the rectangle itself in both
+modes; a constant block gives the constant.  With f dividing cw and ch, a 4-channel source and och 4, a ``MODE`` tile is
+``mode.mode(S, rect, (tw, th))`` byte for byte (for ``n_src = f * n_out`` its cells are the f-blocks and its nearest index is ``Z*f + f // 2``),
+and a ``NEAREST`` tile is ``nearest.nearest``.  ``pyramid`` is unchanged: five levels (f = 1..16) can vote, levels 5 and 6 need ``NEAREST``.
+The modes change no size: ``size`` and ``plan`` take no mode.
+
+The work items of the kernel tile_select, which these two modes run in the place of tile_gather: ``select_split`` and ``select_tiles`` below.
+
 The plan: tile j's slot is ``tw * th * och`` rounded up to 256 plus the encode bound of its descriptor rounded up to 256; sub-batches are cut
 by ``packplan.plan`` over those slots, in tile order.
 """
@@ -15,13 +33,17 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from . import crops, packplan, thumbs
+from . import crops, mode as _mode, packplan, thumbs
 
 FLIP_X = crops.FLIP_X
 FLIP_Y = crops.FLIP_Y
 PLAIN = thumbs.PLAIN
 ALPHA_WEIGHTED = thumbs.ALPHA_WEIGHTED
+NEAREST = 4                     # QOIMI_TILE_NEAREST (2 and 3 are not modes)
+MODE = 5                        # QOIMI_TILE_MODE
 MAX_FACTOR = thumbs.MAX_FACTOR
+MODE_MAX_FACTOR = _mode.MAX_RATIO   # a block votes over at most 16 x 16 pixels
+THREADS = 256                   # work items of a tile of the gather kernels
 MAX_LEVELS = 7
 MAX_TILE_SIDE = 1 << 24
 STAGING_DEFAULT = 1 << 30
@@ -60,6 +82,30 @@ def size(w: int, h: int, sch: int, t, channels: int = 0) -> Tuple[int, int, int]
     return tw * th * (channels or sch), tw, th
 
 
+def select(R: np.ndarray, f: int, mode: int) -> np.ndarray:
+    """R uint8[ch, cw, sch] -> uint8[th, tw, sch]: of every f-block (the box filter's partition) the centre pixel (``NEAREST``) or the winner of
+    ``mode.vote`` (``MODE``, f <= 16), taken at 4 bytes per pixel - alpha 255 behind a 3-channel R - and given back with R's channels."""
+    if mode not in (NEAREST, MODE):
+        raise ValueError("select: mode must be NEAREST or MODE")
+    if mode == MODE and f > MODE_MAX_FACTOR:
+        raise ValueError("select: factor above 16 with MODE")
+    ch, cw, sch = R.shape
+    tw, th = thumbs.size(cw, ch, f)
+    R4 = np.full((ch, cw, 4), 255, dtype=np.uint8)
+    R4[:, :, :sch] = R
+    x0, y0 = np.arange(tw) * f, np.arange(th) * f
+    nx, ny = np.minimum(f, cw - x0), np.minimum(f, ch - y0)
+    cx, cy = x0 + nx // 2, y0 + ny // 2
+    out = R4[cy[:, None], cx[None, :]].copy()                          # the centre pixels: NEAREST - and a constant block gives the constant
+    if mode == MODE:
+        word = R4.view(np.uint32)[:, :, 0]                             # (pixels are equal where these are)
+        lo = np.minimum.reduceat(np.minimum.reduceat(word, y0, axis=0), x0, axis=1)
+        hi = np.maximum.reduceat(np.maximum.reduceat(word, y0, axis=0), x0, axis=1)
+        for Y, X in np.argwhere(lo != hi):                             # the blocks that hold more than one value vote
+            out[Y, X] = _mode.vote(R4, (int(x0[X]), int(nx[X])), (int(y0[Y]), int(ny[Y])), (int(cx[X]), int(cy[Y])))
+    return out[:, :, :sch]
+
+
 def tile(S: np.ndarray, t, channels: int = 0, mode: int = PLAIN) -> np.ndarray:
     """S uint8[h, w, sch] (sch 3 or 4), t a tile of it -> uint8[th, tw, och]: the pixels stream j encodes."""
     S = np.asarray(S)
@@ -68,7 +114,8 @@ def tile(S: np.ndarray, t, channels: int = 0, mode: int = PLAIN) -> np.ndarray:
     _, x, y, cw, ch, f, flags, _ = fields(t)
     if size(S.shape[1], S.shape[0], S.shape[2], t, channels)[0] == 0:
         raise ValueError("tile: the tile or the channel count is one qoimi_encode_tiles rejects")
-    T = thumbs.thumbnail(S[y:y + ch, x:x + cw], f, mode)
+    R = S[y:y + ch, x:x + cw]
+    T = select(R, f, mode) if mode in (NEAREST, MODE) else thumbs.thumbnail(R, f, mode)
     T = crops.crop(T, (0, 0, T.shape[1], T.shape[0]), flags)
     och = channels or S.shape[2]
     if och == 3:
@@ -128,3 +175,23 @@ def plan(descs: Sequence, tiles: Sequence, channels: int, staging_bytes: int):
     subs = packplan.plan(slots, staging_bytes if staging_bytes else STAGING_DEFAULT)      # (a slot is a multiple of 256 already)
     largest = max((sum(slots[first:first + count]) for first, count in subs), default=0)
     return slots, subs, largest, len(named)
+
+
+# ---------------------------------------------------------------------------------- the work items of tile_select (NEAREST / MODE)
+def select_split(f: int, mode: int) -> Tuple[int, int]:
+    """(lg, c): L = 2**lg neighbouring lanes share an output pixel and hold at most c <= 4 pixels of its block each - ``mode.split(f, f, 1, 1)``
+    for ``MODE``, (0, 1) for ``NEAREST`` (a lane per output pixel) and for f == 1 (the copy).  Work item ``(Y * tw + X) * L + l`` of a tile's
+    entry is lane l of pixel (X, Y) of the unflipped result and holds ``mode.held(l, lg, nx, ny)`` of its block."""
+    if mode not in (NEAREST, MODE) or not 1 <= f <= (MODE_MAX_FACTOR if mode == MODE else MAX_FACTOR):
+        raise ValueError("select_split: a mode or factor tile_select does not run")
+    return _mode.split(f, f, 1, 1) if mode == MODE else (0, 1)
+
+
+def select_tiles(cw: int, ch: int, f: int, och: int, mode: int) -> int:
+    """Tiles of 256 work items of a tile of the call in ``NEAREST`` or ``MODE``: f == 1 has one item per aligned 16-byte word of its
+    ``cw * ch * och`` bytes (the copy of tile_gather), else ``tw * th * L`` items."""
+    lg = select_split(f, mode)[0]
+    if f == 1:
+        return -(-(-(-cw * ch * och // 16)) // THREADS)
+    tw, th = thumbs.size(cw, ch, f)
+    return -(-((tw * th) << lg) // THREADS)

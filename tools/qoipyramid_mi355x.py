@@ -2,12 +2,14 @@
 """qoipyramid for the MI355X path: one .qoi file as a tiled, multi-resolution pyramid - L levels, level l at 1 / 2^l of the size, each cut
 into tiles of T x T pixels (the tiles at the right and lower edge are smaller).
 
-    python tools/qoipyramid_mi355x.py FILE.qoi --tile T --levels L -o DIR [--staging-mb M] [--alpha-weighted]
+    python tools/qoipyramid_mi355x.py FILE.qoi --tile T --levels L -o DIR [--staging-mb M] [--alpha-weighted] [--filter box|nearest|mode]
 
 Uploads the file, decodes it ONCE with qoimi_decode_images, makes ONE qoimi_encode_tiles call over qoimi_tile_pyramid - every tile of every
 level is gathered and box-reduced on the GPU from the full-resolution pixels (one rounding, not a chain of halvings), encoded and appended
 to a pack; no tile's pixels and no strided stream ever exist outside the context's staging arena - and writes
-DIR/<level>/tile_<row>_<col>.qoi with the file's channel count and colorspace.  The grid is `pyramid_grid`, a pure function.  Exit status 0,
+DIR/<level>/tile_<row>_<col>.qoi with the file's channel count and colorspace.  --filter nearest / mode is for label maps (segmentation
+masks, instance ids, palette indices), whose classes an average would invent: every block gives its centre pixel (QOIMI_TILE_NEAREST) or
+the winner of a majority vote (QOIMI_TILE_MODE; a block votes over at most 16 x 16 pixels, so at most five levels - use nearest beyond).  The grid is `pyramid_grid`, a pure function.  Exit status 0,
 1 if the file is no QOI stream (size, magic, header rules of qoi.h:497-521), 2 for a bad command line.  Needs torch for device memory, as
 tools/qoitile_mi355x.py does.
 """
@@ -40,6 +42,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("-o", "--out", required=True, metavar="DIR")
     ap.add_argument("--staging-mb", type=int, default=0, metavar="M", help="device memory for gathered tiles and their streams (0: 1 GiB)")
     ap.add_argument("--alpha-weighted", action="store_true", help="weight the colours of a block by alpha (4-channel files)")
+    ap.add_argument("--filter", choices=("box", "nearest", "mode"), default="box", help="label maps: the centre pixel of every block, or its majority vote (at most 5 levels)")
     try:
         a = ap.parse_args(argv)
     except SystemExit:
@@ -52,6 +55,12 @@ def main(argv, out=print) -> int:
         return 2
     if a.staging_mb < 0:
         out("--staging-mb must not be negative")
+        return 2
+    if a.filter != "box" and a.alpha_weighted:
+        out("--alpha-weighted belongs to --filter box")
+        return 2
+    if a.filter == "mode" and (1 << (a.levels - 1)) > tiles.MODE_MAX_FACTOR:
+        out("--filter mode votes over blocks of at most 16 x 16 pixels: --levels must be 1..5 (use --filter nearest for more)")
         return 2
     import torch  # first: the library then binds to the HIP runtime torch already loaded
     from qoi_amd import api
@@ -74,7 +83,7 @@ def main(argv, out=print) -> int:
         n = len(pyr)
         d_off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
         d_len = torch.zeros(n, dtype=torch.int32, device="cuda")
-        mode = tiles.ALPHA_WEIGHTED if a.alpha_weighted else tiles.PLAIN
+        mode = {"box": tiles.ALPHA_WEIGHTED if a.alpha_weighted else tiles.PLAIN, "nearest": tiles.NEAREST, "mode": tiles.MODE}[a.filter]
         # the pack's capacity: the sum of the tiles' encode bounds - every stream fits
         cap = sum(tiles.encode_bound(*tiles.size(w, h, ch, g[3])[1:], ch) for g in grid)
         d_pack = torch.zeros(cap, dtype=torch.uint8, device="cuda")
