@@ -717,13 +717,39 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * their own.  The flag applies unchanged to qoimi_decode_warped_tensors and qoimi_decode_warped_indexed, and qoimi_warp_size and
  * qoimi_warp_tensor_size accept it.  Items with and without the flag mix freely in one call; a call with such an item runs a kernel of its own
  * that serves all its items, a call without one runs what it always ran.
- * Not here: other cubic kernels (a = -3/4), Lanczos in the warp, antialiasing of reducing maps, projective maps.
+ * QOIMI_WARP_REFLECT = 64, QOIMI_WARP_REFLECT_101 = 128 and QOIMI_WARP_WRAP = 256 (flags of the item; normative; qoi_amd/warp.py: warp and fold
+ * state them in Python, qoi_amd/csrc/qoi_warp_border_core.h holds them in C++) are, with QOIMI_WARP_REPLICATE, THE BORDER: at most one of the
+ * four may be set, and each of them combines with QOIMI_WARP_NEAREST or with QOIMI_WARP_BICUBIC.  Px, Py, k0, the fractions, the weights - the
+ * bicubic deficit tap included -, the one rounding, the clamp, the alpha-weighted mode and the rule that a tap with the weight 0 is not taken
+ * and never read stay exactly as they are for all three samplings: only the INDEX of a tap changes.  Every 64-bit tap index k on an axis of n
+ * samples (n = cw for columns, rh for rows) is folded into [0, n) before anything is narrowed, and `fill` is not used, as with REPLICATE.
+ * With `mod` the flooring modulo, 0 <= m < P for negative k too:
+ *   QOIMI_WARP_REFLECT      "dcba|abcd|dcba" (numpy "symmetric", cv2.BORDER_REFLECT, torch grid_sample "reflection" with align_corners=False):
+ *                           P = 2n, m = k mod P, the index is m < n ? m : P - 1 - m
+ *   QOIMI_WARP_REFLECT_101  "dcb|abcd|cba" (numpy "reflect", cv2.BORDER_REFLECT_101 - the default of cv2.warpAffine pipelines and of
+ *                           albumentations -, torchvision Pad "reflect"): if n == 1 the index is 0, else P = 2n - 2, m = k mod P, the index is
+ *                           m < n ? m : P - m
+ *   QOIMI_WARP_WRAP         "abcd|abcd|abcd" (numpy "wrap", cv2.BORDER_WRAP; panoramas, tiling textures): the index is k mod n
+ * EACH TAP IS FOLDED ON ITS OWN - the 2 of the bilinear sampling, the 4 of the bicubic, the one of NEAREST - which is what cv2.warpAffine does
+ * and, for REFLECT, equals torch's reflection of the coordinate.  The rectangle is still what is staged and what the border is taken at:
+ * nothing outside R is ever read.  With the identity plus a whole-pixel translation into a larger output each border gives numpy.pad of R
+ * with its mode, byte for byte, in all three samplings, for pads larger than n and for n == 1 too; a constant rectangle stays the constant;
+ * every output pixel whose taps all lie inside R equals the call without the flag; against a float64 evaluation with the same border rule
+ * the bounds of the bilinear and the bicubic warp hold unchanged (the arithmetic is theirs).  The flag rule reads, in this order: a bit other
+ * than 1, 4, 16, 64, 128 and 256 is an unknown flag bit (2, 8 and 32 are not flags); QOIMI_WARP_NEAREST and QOIMI_WARP_BICUBIC together; more
+ * than one of the four border flags, with a message of its own; reserved.  Limits, plan, staging and stats are untouched.  The flags apply
+ * unchanged to qoimi_decode_warped_tensors and qoimi_decode_warped_indexed, and qoimi_warp_size and qoimi_warp_tensor_size accept them (0 for
+ * two borders).  Items with and without a border flag, and of every sampling, mix freely in one call; a call with an item that carries one of
+ * the three runs a kernel of its own that serves all its items, a call without one runs what it always ran.
+ * Not here: other cubic kernels (a = -3/4), Lanczos in the warp, antialiasing of reducing maps, projective maps, a border per axis,
+ * mixing reflect with a fill.
  * The rectangle is what is staged and what the border is taken at: rows_i of the plan is the maximum of y + height over the items of image i,
  * so the caller keeps the rectangle tight around what the map reaches - a rectangle of the whole image under a map that reaches one corner
  * decodes the whole image.
  * Limits, checked per item in this order: a zero width, height, out_width or out_height; a rectangle that leaves its image; out_width or
  * out_height of 2^20 or more; out_width * out_height of 400 000 000 or more; |c| or |f| of 2^56 or more; a flag bit other than
- * QOIMI_WARP_REPLICATE, QOIMI_WARP_NEAREST and QOIMI_WARP_BICUBIC, then the last two together; reserved != 0.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
+ * QOIMI_WARP_REPLICATE, QOIMI_WARP_NEAREST, QOIMI_WARP_BICUBIC, QOIMI_WARP_REFLECT, QOIMI_WARP_REFLECT_101 and QOIMI_WARP_WRAP, then NEAREST and
+ * BICUBIC together, then more than one of the four border flags; reserved != 0.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
  * 2^57: both positions fit 64 bits with room to spare.  N_c <= 255 * 2^34 < 2^42, the alpha-weighted sums are below 2^50.
  *   stream_offsets, sizes, descs, channels, out_offsets, staging_bytes  as for qoimi_decode_resized; the plan is that of qoimi_decode_crops
  *                  over the items' rectangles (normative; qoi_amd/warp.py: plan)
@@ -734,15 +760,16 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * for the limits above, and for a sub-batch of the plan with 2^31 - 1 or more tiles of 16 x 16 output pixels: reported before anything is
  * launched, the caller's buffers are untouched; qoimi_last_error names the cause.  Output ranges must not overlap.  The sub-batches count as
  * decode calls of the context.  One call at a time per context, as everywhere. */
-enum { QOIMI_WARP_REPLICATE = 1, QOIMI_WARP_NEAREST = 4, QOIMI_WARP_BICUBIC = 16 };   /* 2 and 8 are not flags */
+enum { QOIMI_WARP_REPLICATE = 1, QOIMI_WARP_NEAREST = 4, QOIMI_WARP_BICUBIC = 16,      /* 2, 8 and 32 are not flags */
+       QOIMI_WARP_REFLECT = 64, QOIMI_WARP_REFLECT_101 = 128, QOIMI_WARP_WRAP = 256 };  /* at most one of these three and REPLICATE */
 typedef struct {                 /* 72 bytes, offsets 0/4/8/12/16/20/24/28/32/36/40/44/48/52/56/64 */
     unsigned int image;          /* index into the call's images */
     unsigned int x, y;           /* top-left corner of the source rectangle */
     unsigned int width, height;  /* both >= 1; x + width <= image width, y + height <= image height */
     unsigned int out_width, out_height;  /* both >= 1 and below 2^20; their product below 400 000 000 */
-    unsigned int flags;          /* QOIMI_WARP_REPLICATE, QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC; no other bit */
+    unsigned int flags;          /* one border at most (REPLICATE, REFLECT, REFLECT_101, WRAP), QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC; no other bit */
     int a, b, d, e;              /* the linear part of the inverse map, 16 fractional bits */
-    unsigned int fill;           /* r | g << 8 | b << 16 | a << 24: the value of a sample outside the rectangle without REPLICATE */
+    unsigned int fill;           /* r | g << 8 | b << 16 | a << 24: the value of a sample outside the rectangle without a border flag */
     unsigned int reserved;       /* 0 */
     long long c, f;              /* the offsets of the inverse map, doubled coordinates with 16 fractional bits; |c|, |f| < 2^56 */
 } qoimi_warp;

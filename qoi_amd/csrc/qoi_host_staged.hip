@@ -326,8 +326,9 @@ static_assert(sizeof(qoimi_warp) == 72 && offsetof(qoimi_warp, image) == 0 && of
               offsetof(qoimi_warp, out_height) == 24 && offsetof(qoimi_warp, flags) == 28 && offsetof(qoimi_warp, a) == 32 && offsetof(qoimi_warp, b) == 36 &&
               offsetof(qoimi_warp, d) == 40 && offsetof(qoimi_warp, e) == 44 && offsetof(qoimi_warp, fill) == 48 && offsetof(qoimi_warp, reserved) == 52 &&
               offsetof(qoimi_warp, c) == 56 && offsetof(qoimi_warp, f) == 64, "qoimi_warp layout");
-static_assert(QOIMI_WARP_REPLICATE == (int)kWarpReplicate && QOIMI_WARP_NEAREST == (int)kWarpNearest && QOIMI_WARP_BICUBIC == (int)kWarpBicubic,
-              "the table's flag bits: 2 and 8 are not flags, nor is a bit from 32 on");
+static_assert(QOIMI_WARP_REPLICATE == (int)kWarpReplicate && QOIMI_WARP_NEAREST == (int)kWarpNearest && QOIMI_WARP_BICUBIC == (int)kWarpBicubic &&
+              QOIMI_WARP_REFLECT == (int)kWarpReflect && QOIMI_WARP_REFLECT_101 == (int)kWarpReflect101 && QOIMI_WARP_WRAP == (int)kWarpWrap,
+              "the table's flag bits: 2, 8 and 32 are not flags, nor is a bit from 512 on");
 
 extern "C" size_t qoimi_warp_size(const qoi_desc* desc, const qoimi_warp* item, int channels) {
     size_t bytes = 0;
@@ -358,14 +359,16 @@ extern "C" int qoimi_warp_orient(const qoi_desc* desc, unsigned x, unsigned y, u
 }
 
 // gather_warped (qoi_staged.h) with bytes as the output: one launch of warp_gather over the sub-batch's items - of warp_bicubic_bytes
-// (qoi_warp_cubic.hip) where an item of the call carries QOIMI_WARP_BICUBIC.
+// (qoi_warp_cubic.hip) where an item of the call carries QOIMI_WARP_BICUBIC, of warp_border_bytes (qoi_warp_border.hip) where one carries
+// QOIMI_WARP_REFLECT, QOIMI_WARP_REFLECT_101 or QOIMI_WARP_WRAP.
 extern "C" int qoimi_decode_warped(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                    int n_images, int channels, const qoimi_warp* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
                                    size_t staging_bytes, void* stream) {
     return gather_warped(c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
-                         accept_any, warp_bytes, accept_outputs, &qoimi_ctx::warp_stats, "warp_gather", "warp_bicubic_bytes",
-        [&](bool cubic, const WarpEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
-            (cubic ? launch_warp_cubic : launch_warp)((const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
+                         accept_any, warp_bytes, accept_outputs, &qoimi_ctx::warp_stats, {"warp_gather", "warp_bicubic_bytes", "warp_border_bytes"},
+        [&](WarpKernel kind, const WarpEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
+            (kind == kWarpKernelBorder ? launch_warp_border : (kind == kWarpKernelCubic ? launch_warp_cubic : launch_warp))(
+                (const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
         });
 }
 

@@ -47,7 +47,7 @@ constexpr int64_t kWarpMaxOffset = 1ll << 56;                   // |c|, |f| stay
 constexpr uint32_t kWarpHalf = 1u << 16, kWarpOne = 1u << 17;   // half a pixel and a pixel in doubled coordinates with 16 fractional bits
 constexpr uint64_t kWarpTotal = 1ull << 34;                     // the weights of a pixel
 
-// w: pixels per staged row; (x, y, cw, rh): the rectangle; ow x oh: the output; flags: kWarpReplicate, kWarpNearest; the map; fill
+// w: pixels per staged row; (x, y, cw, rh): the rectangle; ow x oh: the output; flags: the item's (kWarpReplicate, kWarpNearest; qoi_warp_cubic_core.h and qoi_warp_border_core.h have more); the map; fill
 struct WarpGeom { uint32_t w, x, y, cw, rh, ow, oh, flags; int32_t a, b, d, e; uint32_t fill; int64_t c, f; };
 // The two samples of one axis: i[j] the index inside the rectangle where in[j], wgt[j] the weight (0: not taken)
 struct WarpAxis { uint32_t i[2], wgt[2]; bool in[2]; };
@@ -85,13 +85,10 @@ QOIMI_RESIZE_HD void warp_axis(int64_t P, uint32_t n, bool replicate, WarpAxis& 
     }
 }
 
-// Output pixel (X, Y) as r | g << 8 | b << 16 | a << 24: up to four loads, none for a sample that is not taken or takes the fill.
+// The blend of the 2 x 2 samples of the axes ax (columns) and ay (rows) as r | g << 8 | b << 16 | a << 24: up to four loads, none for a
+// sample that is not taken or takes the fill (whatever made the axes: warp_axis here, warp_border_axis of qoi_warp_border_core.h).
 template <bool WEIGHTED, class Mem>
-QOIMI_RESIZE_HD uint32_t warp_pixel(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
-    const bool replicate = (g.flags & kWarpReplicate) != 0u;
-    WarpAxis ax, ay;
-    warp_axis(warp_position(g.a, g.b, g.c, X, Y), g.cw, replicate, ax);
-    warp_axis(warp_position(g.d, g.e, g.f, X, Y), g.rh, replicate, ay);
+QOIMI_RESIZE_HD uint32_t warp_blend(const Mem& mem, const WarpGeom& g, const WarpAxis& ax, const WarpAxis& ay) {
     uint32_t v[2][2];
     QOIMI_RESIZE_UNROLL
     for (uint32_t r = 0; r < 2u; ++r) {
@@ -117,6 +114,16 @@ QOIMI_RESIZE_HD uint32_t warp_pixel(const Mem& mem, const WarpGeom& g, uint32_t 
         } else s.W[ch] = 0u;
     }
     return resize_pixel(s, kWarpTotal, WEIGHTED);
+}
+
+// Output pixel (X, Y): the axes with the border by kWarpReplicate or the fill, and their blend.
+template <bool WEIGHTED, class Mem>
+QOIMI_RESIZE_HD uint32_t warp_pixel(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
+    const bool replicate = (g.flags & kWarpReplicate) != 0u;
+    WarpAxis ax, ay;
+    warp_axis(warp_position(g.a, g.b, g.c, X, Y), g.cw, replicate, ax);
+    warp_axis(warp_position(g.d, g.e, g.f, X, Y), g.rh, replicate, ay);
+    return warp_blend<WEIGHTED>(mem, g, ax, ay);
 }
 
 // Output pixel (X, Y) under kWarpNearest: one load, none where the pixel takes the fill.

@@ -76,14 +76,11 @@ QOIMI_RESIZE_HD void warp_cubic_axis(int64_t P, uint32_t n, bool replicate, Warp
     }
 }
 
-// Output pixel (X, Y) as r | g << 8 | b << 16 | a << 24: up to sixteen loads, four at a time, none for a sample that is not taken or takes
-// the fill.
+// The blend of the 4 x 4 samples of the axes ax (columns) and ay (rows) as r | g << 8 | b << 16 | a << 24: up to sixteen loads, four at a
+// time, none for a sample that is not taken or takes the fill (whatever made the axes: warp_cubic_axis here, warp_border_cubic_axis of
+// qoi_warp_border_core.h).
 template <bool WEIGHTED, class Mem>
-QOIMI_RESIZE_HD uint32_t warp_cubic_pixel(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
-    const bool replicate = (g.flags & kWarpReplicate) != 0u;
-    WarpCubicAxis ax, ay;
-    warp_cubic_axis(warp_position(g.a, g.b, g.c, X, Y), g.cw, replicate, ax);
-    warp_cubic_axis(warp_position(g.d, g.e, g.f, X, Y), g.rh, replicate, ay);
+QOIMI_RESIZE_HD uint32_t warp_cubic_blend(const Mem& mem, const WarpGeom& g, const WarpCubicAxis& ax, const WarpCubicAxis& ay) {
     ResizeSums s;
     resize_zero(s);
     QOIMI_RESIZE_UNROLL
@@ -114,6 +111,16 @@ QOIMI_RESIZE_HD uint32_t warp_cubic_pixel(const Mem& mem, const WarpGeom& g, uin
         }
     }
     return cubic_pixel(s, WEIGHTED);
+}
+
+// Output pixel (X, Y): the axes with the border by kWarpReplicate or the fill, and their blend.
+template <bool WEIGHTED, class Mem>
+QOIMI_RESIZE_HD uint32_t warp_cubic_pixel(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
+    const bool replicate = (g.flags & kWarpReplicate) != 0u;
+    WarpCubicAxis ax, ay;
+    warp_cubic_axis(warp_position(g.a, g.b, g.c, X, Y), g.cw, replicate, ax);
+    warp_cubic_axis(warp_position(g.d, g.e, g.f, X, Y), g.rh, replicate, ay);
+    return warp_cubic_blend<WEIGHTED>(mem, g, ax, ay);
 }
 
 // Work item t of tile `tile` of the item: its pixel computed - 4 x 4 samples for an item with kWarpBicubic, warp_nearest / warp_pixel as they

@@ -38,6 +38,21 @@ integer, every shift and division floors.
   Against a float64 evaluation of the same kernel with the same border rule (``cubic_reference``), PLAIN: the derivation of ``bicubic.py``
   with T = 4 taps and L = sum |w| <= 3/2 per axis gives ``E = 255 / 2**16 * 9 + 255 * 9 / 2**31 < 0.036``: a byte differs from the rounded,
   clamped reference by at most ``floor(1 + E) = 1`` (``cubic_bound``), and only at a rounding boundary.
+* With ``REFLECT`` = 64, ``REFLECT_101`` = 128 or ``WRAP`` = 256 (flags; with ``REPLICATE`` they are THE BORDER: at most one of the four, each
+  combinable with ``NEAREST`` or with ``BICUBIC``) positions, ``k0``, fractions, weights (the bicubic deficit tap too), the one rounding, the
+  clamp, the alpha-weighted mode and "a tap with weight 0 is not taken and never read" stay exactly as they are for all three samplings:
+  only the INDEX of a tap changes.  Every 64-bit tap index k on an axis of n samples is folded into ``[0, n)`` before anything is narrowed
+  (``fold``); ``fill`` is not used, as with ``REPLICATE``.  ``mod`` floors: ``0 <= m < P`` for negative k too.
+  ``REFLECT`` ("dcba|abcd|dcba"; numpy ``symmetric``, ``cv2.BORDER_REFLECT``, torch ``reflection`` with ``align_corners=False``):
+  ``P = 2n``, ``m = k mod P``, index ``m if m < n else P - 1 - m``.
+  ``REFLECT_101`` ("dcb|abcd|cba"; numpy ``reflect``, ``cv2.BORDER_REFLECT_101``, torchvision ``Pad`` "reflect"): index 0 if ``n == 1``,
+  else ``P = 2n - 2``, ``m = k mod P``, index ``m if m < n else P - m``.
+  ``WRAP`` ("abcd|abcd|abcd"; numpy ``wrap``): index ``k mod n``.
+  Each tap is folded on its own - the 2 of the bilinear sampling, the 4 of the bicubic, the one of ``NEAREST`` -, as ``cv2.warpAffine``
+  does; for ``REFLECT`` that equals torch's reflection of the coordinate.  R is still what is staged and what the border is taken at:
+  nothing outside R is ever read.  With the identity plus a whole-pixel translation into a larger output each border gives
+  ``np.pad(R, mode=...)`` byte for byte in all three samplings, for pads larger than n and for ``n == 1`` too; a constant stays the
+  constant; every pixel whose taps all lie inside R equals the call without the flag; the bounds against float64 are the unflagged ones.
 * ``N_c = sum wy * wx * c`` over the four samples; the weights add up to ``2**34``.
 * ``PLAIN``: every channel is ``(N_c + 2**33) >> 34`` - ONE rounding.
 * ``ALPHA_WEIGHTED``, 4 channels only: ``A = N_a``; alpha as in the plain mode; where ``A > 0`` r, g and b are
@@ -45,7 +60,8 @@ integer, every shift and division floors.
 * There is no antialiasing: a map that reduces still takes four samples (reduce first with ``resize.resize`` where that matters).
 
 Limits, in the order the C side checks them: a zero size; a rectangle that leaves its image; ``ow, oh < 2**20``; ``ow * oh < 400 000 000``;
-``|c|, |f| < 2**56``; no flag bit but ``REPLICATE``, ``NEAREST`` and ``BICUBIC`` (2 and 8 are not flags), then not ``NEAREST`` and ``BICUBIC`` together; ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
+``|c|, |f| < 2**56``; no flag bit but ``REPLICATE``, ``NEAREST``, ``BICUBIC``, ``REFLECT``, ``REFLECT_101`` and ``WRAP`` (2, 8 and 32 are not
+flags), then not ``NEAREST`` and ``BICUBIC`` together, then not more than one of the four borders; ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
 ``|Px|, |Py| < 2**57``; ``N_c <= 255 * 2**34 < 2**42``; the alpha-weighted sums are below ``2**50``: everything fits int64.
 
 With the identity the result is ``crops.crop``; with ``a = ONE // s`` and REPLICATE it is ``bilinear.bilinear`` enlarging by the power of two s;
@@ -65,6 +81,10 @@ from . import bicubic, crops, resize
 REPLICATE = 1
 NEAREST = 4                     # one sample, not 2 x 2 taps (2 is not a flag)
 BICUBIC = 16                    # 4 x 4 samples under Keys' cubic, a = -1/2 (8 is not a flag)
+REFLECT = 64                    # "dcba|abcd|dcba" (32 is not a flag)
+REFLECT_101 = 128               # "dcb|abcd|cba"
+WRAP = 256                      # "abcd|abcd|abcd"
+BORDERS = REPLICATE | REFLECT | REFLECT_101 | WRAP   # at most one of them
 CUBIC_ONE = bicubic.ONE         # the weights of an axis add up to it
 CUBIC_L1_MAX = 5 << 13          # sum |q| of an axis stays at or below it
 PLAIN = resize.PLAIN
@@ -117,26 +137,53 @@ def _wrong(w: int, h: int, rect, out_size, matrix, flags: int, reserved: int = 0
         return "|c| or |f| from 2**56"
     if any(not -2 ** 31 <= v < 2 ** 31 for v in (a, b, d, e)):
         return "a, b, d, e are 32-bit"
-    if flags & ~(REPLICATE | NEAREST | BICUBIC):
+    if flags & ~(BORDERS | NEAREST | BICUBIC):
         return "unknown flag bit"
     if flags & NEAREST and flags & BICUBIC:
         return "NEAREST and BICUBIC together"
+    if (flags & BORDERS) & ((flags & BORDERS) - 1):
+        return "more than one border of REPLICATE, REFLECT, REFLECT_101 and WRAP"
     if reserved:
         return "reserved is not 0"
     return ""
 
 
-def _axis(P: np.ndarray, n: int, replicate: bool):
-    """(indices int64[..., 2] inside [0, n), weights int64[..., 2], taken-from-R bool[..., 2]) of the positions P on an axis of n samples."""
+def fold(k, n: int, border: int) -> np.ndarray:
+    """int64 like k: the tap indices k (any integers) on an axis of n samples folded into [0, n) under the border ``REFLECT``,
+    ``REFLECT_101`` or ``WRAP``."""
+    k = np.asarray(k, dtype=np.int64)
+    if n < 1 or border not in (REFLECT, REFLECT_101, WRAP):
+        raise ValueError("fold: n >= 1 and one of REFLECT, REFLECT_101, WRAP")
+    if border == WRAP:
+        return k % n                                                     # (numpy's % floors)
+    if border == REFLECT:
+        m = k % (2 * n)
+        return np.where(m < n, m, 2 * n - 1 - m)
+    if n == 1:
+        return np.zeros_like(k)
+    m = k % (2 * n - 2)
+    return np.where(m < n, m, 2 * n - 2 - m)
+
+
+def _border(k: np.ndarray, n: int, flags: int):
+    """(indices inside [0, n), taken-from-R) of the tap indices k under the item's border: folded, clamped, or the fill where outside."""
+    if flags & (BORDERS & ~REPLICATE):
+        return fold(k, n, flags & BORDERS), np.ones(k.shape, dtype=bool)
+    if flags & REPLICATE:
+        return np.clip(k, 0, n - 1), np.ones(k.shape, dtype=bool)
+    return np.clip(k, 0, n - 1), (k >= 0) & (k < n)
+
+
+def _axis(P: np.ndarray, n: int, flags: int):
+    """(indices int64[..., 2] inside [0, n), weights int64[..., 2], taken-from-R bool[..., 2]) of the positions P on an axis of n samples
+    (flags: the item's, of which the border counts; a bool is taken as ``REPLICATE`` or not)."""
     p = P - ONE
     k0 = p >> 17
     fr = p & (2 * ONE - 1)
     k = np.stack([k0, k0 + 1], axis=-1)
     wgt = np.stack([2 * ONE - fr, fr], axis=-1)
-    inside = (k >= 0) & (k < n)
-    if replicate:
-        inside = np.ones_like(inside)
-    return np.clip(k, 0, n - 1), wgt, inside
+    i, inside = _border(k, n, int(flags))
+    return i, wgt, inside
 
 
 def cubic_weights(fr) -> np.ndarray:
@@ -155,14 +202,13 @@ def cubic_weights(fr) -> np.ndarray:
     return q
 
 
-def _cubic_axis(P: np.ndarray, n: int, replicate: bool):
-    """(indices int64[..., 4] inside [0, n), weights int64[..., 4], taken-from-R bool[..., 4]) of the positions P on an axis of n samples."""
+def _cubic_axis(P: np.ndarray, n: int, flags: int):
+    """(indices int64[..., 4] inside [0, n), weights int64[..., 4], taken-from-R bool[..., 4]) of the positions P on an axis of n samples
+    (flags: as for ``_axis``)."""
     p = P - ONE
     k = (p >> 17)[..., None] + np.arange(-1, 3, dtype=np.int64)
-    inside = (k >= 0) & (k < n)
-    if replicate:
-        inside = np.ones_like(inside)
-    return np.clip(k, 0, n - 1), cubic_weights(p & (2 * ONE - 1)), inside
+    i, inside = _border(k, n, int(flags))
+    return i, cubic_weights(p & (2 * ONE - 1)), inside
 
 
 def _clamp(v: np.ndarray) -> np.ndarray:
@@ -170,7 +216,8 @@ def _clamp(v: np.ndarray) -> np.ndarray:
 
 
 def cubic_reference(D: np.ndarray, rect, out_size, matrix=IDENTITY, flags: int = 0, fill: int = 0) -> np.ndarray:
-    """float64[out_height, out_width, och]: Keys' kernel (a = -1/2) at the same positions with the same border rule, evaluated in
+    """float64[out_height, out_width, och]: Keys' kernel (a = -1/2) at the same positions with the same border rule (``fill``, ``REPLICATE``
+    or a folding border), evaluated in
     float64, PLAIN, neither rounded nor clamped (positions below 2**53 are exact there)."""
     D = np.asarray(D)
     x, y, cw, rh = (int(v) for v in rect)
@@ -187,8 +234,8 @@ def cubic_reference(D: np.ndarray, rect, out_size, matrix=IDENTITY, flags: int =
         k = (p >> 17)[..., None] + np.arange(-1, 3, dtype=np.int64)
         t = np.abs((p & (2 * ONE - 1)).astype(np.float64)[..., None] / (2 * ONE) - np.arange(-1, 3, dtype=np.float64))
         w = np.where(t <= 1, 1.5 * t ** 3 - 2.5 * t ** 2 + 1, np.where(t < 2, -0.5 * t ** 3 + 2.5 * t ** 2 - 4 * t + 2, 0.0))
-        inside = (k >= 0) & (k < n) if not flags & REPLICATE else np.ones(k.shape, dtype=bool)
-        return np.clip(k, 0, n - 1), w, inside
+        i, inside = _border(k, n, flags)
+        return i, w, inside
 
     kx, wx, inx = axis(a * U + b * V + c, cw)
     ky, wy, iny = axis(d * U + e * V + f, rh)
@@ -232,15 +279,13 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
     U = (2 * np.arange(ow, dtype=np.int64) + 1)[None, :]
     V = (2 * np.arange(oh, dtype=np.int64) + 1)[:, None]
     if flags & NEAREST:
-        k, r = (a * U + b * V + c) >> 17, (d * U + e * V + f) >> 17
-        inside = (k >= 0) & (k < cw) & (r >= 0) & (r < rh)
-        if flags & REPLICATE:
-            inside = np.ones_like(inside)
-        out = np.where(inside[..., None], R[np.clip(r, 0, rh - 1), np.clip(k, 0, cw - 1)], F[None, None, :])
+        k, ink = _border((a * U + b * V + c) >> 17, cw, flags)
+        r, inr = _border((d * U + e * V + f) >> 17, rh, flags)
+        out = np.where((ink & inr)[..., None], R[r, k], F[None, None, :])
         return np.ascontiguousarray(out[..., :och].astype(np.uint8))
     if flags & BICUBIC:
-        kx, qx, inx = _cubic_axis(a * U + b * V + c, cw, bool(flags & REPLICATE))
-        ky, qy, iny = _cubic_axis(d * U + e * V + f, rh, bool(flags & REPLICATE))
+        kx, qx, inx = _cubic_axis(a * U + b * V + c, cw, flags)
+        ky, qy, iny = _cubic_axis(d * U + e * V + f, rh, flags)
         N = np.zeros((oh, ow, 4), dtype=np.int64)
         M = np.zeros((oh, ow, 3), dtype=np.int64)
         for r in range(4):
@@ -254,8 +299,8 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
             A = N[..., 3:4]
             out[..., :3] = np.where(A > 0, _clamp((M + A // 2) // np.maximum(A, 1)), out[..., :3])
         return np.ascontiguousarray(out[..., :och].astype(np.uint8))
-    kx, wx, inx = _axis(a * U + b * V + c, cw, bool(flags & REPLICATE))
-    ky, wy, iny = _axis(d * U + e * V + f, rh, bool(flags & REPLICATE))
+    kx, wx, inx = _axis(a * U + b * V + c, cw, flags)
+    ky, wy, iny = _axis(d * U + e * V + f, rh, flags)
     N = np.zeros((oh, ow, 4), dtype=np.int64)
     M = np.zeros((oh, ow, 3), dtype=np.int64)
     for r in range(2):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """qoiwarp for the MI355X path: a set of .qoi files as PNGs, re-oriented or turned about their centre.
 
-    python tools/qoiwarp_mi355x.py FILE_OR_DIR... -o DIR (--orient N | --rotate DEG [--scale S]) [--size WxH] [--border fill|replicate]
+    python tools/qoiwarp_mi355x.py FILE_OR_DIR... -o DIR (--orient N | --rotate DEG [--scale S]) [--size WxH] [--border fill|replicate|reflect|reflect101|wrap]
                                    [--sample bilinear|nearest|bicubic]
                                    [--fill RRGGBBAA] [--mode plain|weighted] [--staging-mb M]
 
@@ -10,7 +10,9 @@ GPU into a bounded staging arena and sampled there through the affine map with t
 images do not exist outside that arena.  --orient N shows every image in the EXIF orientation N (1..8; the output is w x h, h x w for 5..8,
 every output pixel one source pixel: qoimi_warp_orient).  --rotate DEG turns the image counter-clockwise about its centre, enlarged by
 --scale (default 1), into an output of --size (default: the image's own size); the matrix is quantised to 2**-16 here on the host
-(rotation_matrix).  Samples outside the image take --fill (default 00000000) or, with --border replicate, the nearest pixel.  --sample nearest takes
+(rotation_matrix).  Samples outside the image take --fill (default 00000000) or, with --border replicate, the nearest pixel; --border reflect
+mirrors the image about its edges ("dcba|abcd|dcba", warp.REFLECT), --border reflect101 about its edge pixels ("dcb|abcd|cba", warp.REFLECT_101: the
+border cv2.warpAffine pipelines default to) and --border wrap repeats it (warp.WRAP) - --fill is then not used.  --sample nearest takes
 one source pixel per output pixel instead of the 2 x 2 bilinear taps (warp.NEAREST): for label maps, whose values must not be averaged; --sample bicubic takes 4 x 4 under Keys' cubic with a = -1/2 (warp.BICUBIC): sharper photographs under a turn.  There is no
 antialiasing: a scale well below 1 wants tools/qoiresize_mi355x.py first.  Outputs hold 4 channels if any file does, else 3, and are
 written as DIR/<name>.png through tools/png_io.py.  One row per file: w x h x channels, the map, the output size.  A file that is no QOI
@@ -35,6 +37,8 @@ from tools.qoiresize_mi355x import parse_size  # noqa: E402
 from tools.qoithumb_mi355x import parse_header  # noqa: E402
 
 ONE = 1 << 16
+BORDERS = {"fill": 0, "replicate": 1, "reflect": 64, "reflect101": 128, "wrap": 256}          # --border -> warp.REPLICATE, REFLECT, REFLECT_101, WRAP
+SAMPLES = {"bilinear": 0, "nearest": 4, "bicubic": 16}                                        # --sample -> warp.NEAREST, BICUBIC
 
 
 def parse_fill(text: str):
@@ -69,8 +73,8 @@ def main(argv, out=print) -> int:
     ap.add_argument("--rotate", type=float, default=None, metavar="DEG")
     ap.add_argument("--scale", type=float, default=1.0, metavar="S")
     ap.add_argument("--size", default=None, metavar="WxH")
-    ap.add_argument("--border", choices=("fill", "replicate"), default="fill")
-    ap.add_argument("--sample", choices=("bilinear", "nearest", "bicubic"), default="bilinear")
+    ap.add_argument("--border", choices=tuple(BORDERS), default="fill")
+    ap.add_argument("--sample", choices=tuple(SAMPLES), default="bilinear")
     ap.add_argument("--fill", default="00000000", metavar="RRGGBBAA")
     ap.add_argument("--mode", choices=("plain", "weighted"), default="plain")
     ap.add_argument("--staging-mb", type=int, default=0, metavar="M", help="device memory for decoded pixels (0: 1 GiB)")
@@ -108,7 +112,7 @@ def main(argv, out=print) -> int:
     if not files:
         out("no .qoi files")
         return 2
-    flags = (warp.REPLICATE if a.border == "replicate" else 0) | {"bilinear": 0, "nearest": warp.NEAREST, "bicubic": warp.BICUBIC}[a.sample]
+    flags = BORDERS[a.border] | SAMPLES[a.sample]
     blobs = [open(f, "rb").read() for f in files]
     heads = [parse_header(b) for b in blobs]
     good, items = [], []
