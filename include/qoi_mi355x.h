@@ -673,7 +673,7 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  *                                if A == 0 they are the PLAIN value.  With och == 3 this mode is PLAIN.
  * The oh x ow result is written tightly packed row-major, ow * oh * och bytes (qoimi_warp_size), at d_out + out_offsets[j].
  * NO ANTIALIASING: a map that reduces still takes four samples per output pixel, as cv::warpAffine and torch's grid_sample do; reduce first with
- * qoimi_decode_resized or qoimi_decode_bilinear where that matters.  With the identity the call is qoimi_decode_crops byte for byte; with
+ * qoimi_decode_resized or qoimi_decode_bilinear where that matters, or set QOIMI_WARP_SUPER2 / QOIMI_WARP_SUPER4 (below) for ratios up to 4 : 1.  With the identity the call is qoimi_decode_crops byte for byte; with
  * a = 65536 / s and REPLICATE it is qoimi_decode_bilinear enlarging by the power of two s; a constant rectangle stays the constant under any
  * map with REPLICATE.  Against a float64 evaluation of the same map (torch affine_grid + grid_sample, bilinear, align_corners=False) a value
  * differs by at most 1, and only where the float result lies at a rounding boundary.
@@ -741,15 +741,46 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * unchanged to qoimi_decode_warped_tensors and qoimi_decode_warped_indexed, and qoimi_warp_size and qoimi_warp_tensor_size accept them (0 for
  * two borders).  Items with and without a border flag, and of every sampling, mix freely in one call; a call with an item that carries one of
  * the three runs a kernel of its own that serves all its items, a call without one runs what it always ran.
- * Not here: other cubic kernels (a = -3/4), Lanczos in the warp, antialiasing of reducing maps, projective maps, a border per axis,
- * mixing reflect with a fill.
+ * QOIMI_WARP_SUPER2 = 1024 (s = 2, L = 1) and QOIMI_WARP_SUPER4 = 2048 (s = 4, L = 2) (flags of the item; normative; qoi_amd/warp.py: warp states
+ * them in Python, qoi_amd/csrc/qoi_warp_super_core.h holds them in C++) SUPERSAMPLE a reducing map: an item carries at most one of the two,
+ * with the bilinear sampling only; 512 is not a flag.  Everything about the item that is not named here stays as it is: R, cw, rh, U = 2X + 1,
+ * V = 2Y + 1, the modes, the fill, the four borders, the plan, staging, limits, and the rule that a tap of weight 0 is not taken and never
+ * read.  Output pixel (X, Y) is the mean of s x s bilinear samples laid on a regular grid inside the pixel, with ONE rounding.  For
+ * 0 <= i, j < s:
+ *   Us = s * U + 2i + 1 - s,   Vs = s * V + 2j + 1 - s        (the sub-sample's centre in coordinates s times finer)
+ *   Px = ((a * Us + b * Vs) >> L) + c,   Py = ((d * Us + e * Vs) >> L) + f     (arithmetic shift: it floors)
+ * From (Px, Py) the 2 x 2 taps, their weights (131072 - fx, fx and likewise for rows), their indices and the border are exactly those of the
+ * bilinear warp today.  A tap outside R takes `fill`.  Under QOIMI_WARP_REPLICATE its index is clamped; under REFLECT / REFLECT_101 / WRAP it
+ * is folded.  Each tap is treated on its own.  N_c = sum over all s^2 sub-samples and their four taps of wy * wx * c.
+ *   QOIMI_RESIZE_PLAIN           every channel is (N_c + 2^(33 + 2L)) >> (34 + 2L)
+ *   QOIMI_RESIZE_ALPHA_WEIGHTED  with och == 4: A = N_a, alpha is the PLAIN value.  If A > 0, r, g and b are (M_c + A / 2) / A, where M_c is the
+ *                                same sum of wy * wx * c * a.  If A == 0 they are the PLAIN value.  With och == 3 this mode is PLAIN.
+ * Bounds: Us, Vs < 2^23, so |a * Us + b * Vs| < 2^55; |Px|, |Py| < 2^57, as now, so the fold's preconditions hold unchanged;
+ * N_c <= 255 * 2^38 < 2^46; M_c < 2^54.
+ * With a = e = s * 65536, b = c = d = f = 0 and an output of (cw / s) x (rh / s), where s divides both, every sub-sample is a pixel centre.
+ * The item is then the exact s x s box average with one rounding.  It equals qoimi_decode_thumbnails at factor s and qoimi_decode_resized of
+ * the same rectangle byte for byte, in both modes: the rounding (S + cnt / 2) / cnt and the weighted (W + A / 2) / A of those calls come out
+ * identical after the common factor 2^34 cancels.  A constant rectangle stays the constant under any map with any of the four borders.  The
+ * result differs by at most 1 from a float64 evaluation of the same s^2 positions (taken from the integer Px, Py), bilinear, same border
+ * rule, averaged and rounded once; it differs only where the float value lies at a rounding boundary, because N_c is exact.  There is NO
+ * adaptivity: the flag takes s^2 sub-samples whether or not the map reduces.  Beyond 4 : 1 the result still aliases.
+ * The flag rule reads, in this order: a bit other than 1, 4, 16, 64, 128, 256, 1024 and 2048 is an unknown flag bit (2, 8, 32 and 512 are not
+ * flags); QOIMI_WARP_NEAREST and QOIMI_WARP_BICUBIC together; more than one of the four border flags; both SUPER flags together, with a message
+ * of its own; a SUPER flag with QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC, with a message of its own - supersampling is defined for the bilinear
+ * sampling only; reserved != 0.  qoimi_warp_size and qoimi_warp_tensor_size accept the flags and return 0 for the two new rejections.  Items
+ * with and without a SUPER flag, of every sampling and border, mix freely in one call; a call with a SUPER item runs a kernel of its own that
+ * serves all its items, a call without one launches exactly what it launches today.  The flags apply unchanged to
+ * qoimi_decode_warped_tensors and qoimi_decode_warped_indexed.
+ * Not here: other cubic kernels (a = -3/4), Lanczos in the warp, adaptive antialiasing of reducing maps, supersampling beyond 4 x 4,
+ * supersampled bicubic or nearest, projective maps, a border per axis, mixing reflect with a fill.
  * The rectangle is what is staged and what the border is taken at: rows_i of the plan is the maximum of y + height over the items of image i,
  * so the caller keeps the rectangle tight around what the map reaches - a rectangle of the whole image under a map that reaches one corner
  * decodes the whole image.
  * Limits, checked per item in this order: a zero width, height, out_width or out_height; a rectangle that leaves its image; out_width or
  * out_height of 2^20 or more; out_width * out_height of 400 000 000 or more; |c| or |f| of 2^56 or more; a flag bit other than
  * QOIMI_WARP_REPLICATE, QOIMI_WARP_NEAREST, QOIMI_WARP_BICUBIC, QOIMI_WARP_REFLECT, QOIMI_WARP_REFLECT_101 and QOIMI_WARP_WRAP, then NEAREST and
- * BICUBIC together, then more than one of the four border flags; reserved != 0.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
+ * BICUBIC together, then more than one of the four border flags (QOIMI_WARP_SUPER2 and QOIMI_WARP_SUPER4 are flags too; then both of them
+ * together, then one of them with NEAREST or BICUBIC); reserved != 0.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
  * 2^57: both positions fit 64 bits with room to spare.  N_c <= 255 * 2^34 < 2^42, the alpha-weighted sums are below 2^50.
  *   stream_offsets, sizes, descs, channels, out_offsets, staging_bytes  as for qoimi_decode_resized; the plan is that of qoimi_decode_crops
  *                  over the items' rectangles (normative; qoi_amd/warp.py: plan)
@@ -761,13 +792,14 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * launched, the caller's buffers are untouched; qoimi_last_error names the cause.  Output ranges must not overlap.  The sub-batches count as
  * decode calls of the context.  One call at a time per context, as everywhere. */
 enum { QOIMI_WARP_REPLICATE = 1, QOIMI_WARP_NEAREST = 4, QOIMI_WARP_BICUBIC = 16,      /* 2, 8 and 32 are not flags */
-       QOIMI_WARP_REFLECT = 64, QOIMI_WARP_REFLECT_101 = 128, QOIMI_WARP_WRAP = 256 };  /* at most one of these three and REPLICATE */
+       QOIMI_WARP_REFLECT = 64, QOIMI_WARP_REFLECT_101 = 128, QOIMI_WARP_WRAP = 256,    /* at most one of these three and REPLICATE */
+       QOIMI_WARP_SUPER2 = 1024, QOIMI_WARP_SUPER4 = 2048 };                            /* at most one; bilinear only; 512 is not a flag */
 typedef struct {                 /* 72 bytes, offsets 0/4/8/12/16/20/24/28/32/36/40/44/48/52/56/64 */
     unsigned int image;          /* index into the call's images */
     unsigned int x, y;           /* top-left corner of the source rectangle */
     unsigned int width, height;  /* both >= 1; x + width <= image width, y + height <= image height */
     unsigned int out_width, out_height;  /* both >= 1 and below 2^20; their product below 400 000 000 */
-    unsigned int flags;          /* one border at most (REPLICATE, REFLECT, REFLECT_101, WRAP), QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC; no other bit */
+    unsigned int flags;          /* one border at most (REPLICATE, REFLECT, REFLECT_101, WRAP), QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC, or QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4; no other bit */
     int a, b, d, e;              /* the linear part of the inverse map, 16 fractional bits */
     unsigned int fill;           /* r | g << 8 | b << 16 | a << 24: the value of a sample outside the rectangle without a border flag */
     unsigned int reserved;       /* 0 */

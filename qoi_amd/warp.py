@@ -57,11 +57,32 @@ integer, every shift and division floors.
 * ``PLAIN``: every channel is ``(N_c + 2**33) >> 34`` - ONE rounding.
 * ``ALPHA_WEIGHTED``, 4 channels only: ``A = N_a``; alpha as in the plain mode; where ``A > 0`` r, g and b are
   ``(sum wy*wx*c*a + A // 2) // A``, where ``A == 0`` they are the PLAIN value.  With 3 channels this mode is PLAIN.
-* There is no antialiasing: a map that reduces still takes four samples (reduce first with ``resize.resize`` where that matters).
+* There is no antialiasing: a map that reduces still takes four samples (reduce first with ``resize.resize`` where that matters) - unless the
+  item asks for supersampling:
+* With ``SUPER2`` = 1024 (s = 2, L = 1) or ``SUPER4`` = 2048 (s = 4, L = 2) (flags; at most one of the two, with the bilinear sampling only -
+  never with ``NEAREST`` or ``BICUBIC`` -, with the fill or any of the four borders; 512 is not a flag) output pixel (X, Y) is the mean of
+  s x s bilinear samples laid on a regular grid inside the pixel, with ONE rounding.  For ``0 <= i, j < s``:
+  ``Us = s*U + 2i + 1 - s``, ``Vs = s*V + 2j + 1 - s`` (the sub-sample's centre in coordinates s times finer),
+  ``Px = ((a*Us + b*Vs) >> L) + c``, ``Py = ((d*Us + e*Vs) >> L) + f`` (the shift floors).  From (Px, Py) the 2 x 2 taps, their weights, their
+  indices and the border are exactly those of the bilinear warp: a tap outside R takes ``fill``, under ``REPLICATE`` its index is clamped,
+  under ``REFLECT`` / ``REFLECT_101`` / ``WRAP`` it is folded, each tap on its own; a tap of weight 0 is not taken and never read.
+  ``N_c`` is the sum over all s**2 sub-samples and their four taps of ``wy * wx * c``.  ``PLAIN``: every channel is
+  ``(N_c + 2**(33 + 2L)) >> (34 + 2L)``.  ``ALPHA_WEIGHTED`` with 4 channels: ``A = N_a``, alpha is the PLAIN value; where ``A > 0`` r, g and
+  b are ``(M_c + A // 2) // A`` with ``M_c`` the same sum of ``wy * wx * c * a``; where ``A == 0`` they are the PLAIN value.  With 3 channels
+  this mode is PLAIN.  Bounds: ``Us, Vs < 2**23``, so ``|a*Us + b*Vs| < 2**55``; ``|Px|, |Py| < 2**57`` as without the flag, so the fold's
+  preconditions hold unchanged; ``N_c <= 255 * 2**38 < 2**46``; ``M_c < 2**54``.
+  With ``a = e = s * ONE``, ``b = c = d = f = 0`` and an output of ``(cw / s) x (rh / s)``, s dividing both, every sub-sample is a pixel
+  centre: the item is the exact s x s box average with one rounding and equals ``thumbs.thumbnail`` at factor s and ``resize.resize`` of the
+  same rectangle byte for byte in both modes (the common factor ``2**34`` cancels in ``(S + cnt // 2) // cnt`` and ``(W + A // 2) // A``).
+  A constant rectangle stays the constant under any map with any of the four borders.  The result differs by at most 1 from a float64
+  evaluation of the same s**2 positions (``super_reference``: taken from the integer Px, Py, bilinear, same border rule, averaged, rounded
+  once), and only where the float value lies at a rounding boundary, because ``N_c`` is exact.  There is NO adaptivity: the flag takes s**2
+  sub-samples whether or not the map reduces, and beyond 4 : 1 the result still aliases.
 
 Limits, in the order the C side checks them: a zero size; a rectangle that leaves its image; ``ow, oh < 2**20``; ``ow * oh < 400 000 000``;
-``|c|, |f| < 2**56``; no flag bit but ``REPLICATE``, ``NEAREST``, ``BICUBIC``, ``REFLECT``, ``REFLECT_101`` and ``WRAP`` (2, 8 and 32 are not
-flags), then not ``NEAREST`` and ``BICUBIC`` together, then not more than one of the four borders; ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
+``|c|, |f| < 2**56``; no flag bit but ``REPLICATE``, ``NEAREST``, ``BICUBIC``, ``REFLECT``, ``REFLECT_101``, ``WRAP``, ``SUPER2`` and ``SUPER4``
+(2, 8, 32 and 512 are not flags), then not ``NEAREST`` and ``BICUBIC`` together, then not more than one of the four borders, then not both
+``SUPER`` flags, then no ``SUPER`` flag with ``NEAREST`` or ``BICUBIC``; ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
 ``|Px|, |Py| < 2**57``; ``N_c <= 255 * 2**34 < 2**42``; the alpha-weighted sums are below ``2**50``: everything fits int64.
 
 With the identity the result is ``crops.crop``; with ``a = ONE // s`` and REPLICATE it is ``bilinear.bilinear`` enlarging by the power of two s;
@@ -85,6 +106,9 @@ REFLECT = 64                    # "dcba|abcd|dcba" (32 is not a flag)
 REFLECT_101 = 128               # "dcb|abcd|cba"
 WRAP = 256                      # "abcd|abcd|abcd"
 BORDERS = REPLICATE | REFLECT | REFLECT_101 | WRAP   # at most one of them
+SUPER2 = 1024                   # 2 x 2 bilinear sub-samples per output pixel, one rounding (512 is not a flag)
+SUPER4 = 2048                   # 4 x 4
+SUPERS = SUPER2 | SUPER4        # at most one of them, with the bilinear sampling only
 CUBIC_ONE = bicubic.ONE         # the weights of an axis add up to it
 CUBIC_L1_MAX = 5 << 13          # sum |q| of an axis stays at or below it
 PLAIN = resize.PLAIN
@@ -137,12 +161,16 @@ def _wrong(w: int, h: int, rect, out_size, matrix, flags: int, reserved: int = 0
         return "|c| or |f| from 2**56"
     if any(not -2 ** 31 <= v < 2 ** 31 for v in (a, b, d, e)):
         return "a, b, d, e are 32-bit"
-    if flags & ~(BORDERS | NEAREST | BICUBIC):
+    if flags & ~(BORDERS | NEAREST | BICUBIC | SUPERS):
         return "unknown flag bit"
     if flags & NEAREST and flags & BICUBIC:
         return "NEAREST and BICUBIC together"
     if (flags & BORDERS) & ((flags & BORDERS) - 1):
         return "more than one border of REPLICATE, REFLECT, REFLECT_101 and WRAP"
+    if flags & SUPERS == SUPERS:
+        return "SUPER2 and SUPER4 together"
+    if flags & SUPERS and flags & (NEAREST | BICUBIC):
+        return "supersampling is defined for the bilinear sampling only: a SUPER flag with NEAREST or BICUBIC"
     if reserved:
         return "reserved is not 0"
     return ""
@@ -299,21 +327,59 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
             A = N[..., 3:4]
             out[..., :3] = np.where(A > 0, _clamp((M + A // 2) // np.maximum(A, 1)), out[..., :3])
         return np.ascontiguousarray(out[..., :och].astype(np.uint8))
-    kx, wx, inx = _axis(a * U + b * V + c, cw, flags)
-    ky, wy, iny = _axis(d * U + e * V + f, rh, flags)
+    L = super_log2(flags)                                                # 0 without a SUPER flag: one sample, Us = U, Vs = V, no shift
+    s = 1 << L
     N = np.zeros((oh, ow, 4), dtype=np.int64)
     M = np.zeros((oh, ow, 3), dtype=np.int64)
-    for r in range(2):
-        for k in range(2):
-            v = np.where((iny[..., r] & inx[..., k])[..., None], R[ky[..., r], kx[..., k]], F[None, None, :])
-            wgt = (wy[..., r] * wx[..., k])[..., None]                   # at most 2**34; a sample without a weight adds nothing
-            N += wgt * v                                                 # below 2**42
-            M += wgt * v[..., :3] * v[..., 3:4]                          # below 2**50
-    out = (N + (1 << 33)) >> 34
+    for j in range(s):
+        for i in range(s):
+            Us, Vs = s * U + (2 * i + 1 - s), s * V + (2 * j + 1 - s)    # below 2**23; the sums below are under 2**55
+            kx, wx, inx = _axis(((a * Us + b * Vs) >> L) + c, cw, flags)
+            ky, wy, iny = _axis(((d * Us + e * Vs) >> L) + f, rh, flags)
+            for r in range(2):
+                for k in range(2):
+                    v = np.where((iny[..., r] & inx[..., k])[..., None], R[ky[..., r], kx[..., k]], F[None, None, :])
+                    wgt = (wy[..., r] * wx[..., k])[..., None]           # at most 2**34; a sample without a weight adds nothing
+                    N += wgt * v                                         # below 2**42, 2**46 over 4 x 4 sub-samples
+                    M += wgt * v[..., :3] * v[..., 3:4]                  # below 2**50, 2**54
+    out = (N + (1 << (33 + 2 * L))) >> (34 + 2 * L)
     if weighted:
         A = N[..., 3:4]
         out[..., :3] = np.where(A > 0, (M + A // 2) // np.maximum(A, 1), out[..., :3])
     return np.ascontiguousarray(out[..., :och].astype(np.uint8))
+
+
+def super_log2(flags: int) -> int:
+    """L of the item's flags: 1 for ``SUPER2``, 2 for ``SUPER4``, 0 without; s = 1 << L sub-samples along each axis of an output pixel."""
+    return 2 if flags & SUPER4 else (1 if flags & SUPER2 else 0)
+
+
+def super_reference(D: np.ndarray, rect, out_size, matrix=IDENTITY, flags: int = 0, fill: int = 0) -> np.ndarray:
+    """float64[out_height, out_width, och]: the mean of the bilinear samples at the s**2 integer positions (Px, Py) of every output pixel
+    with the item's border rule (``fill``, ``REPLICATE`` or a folding border), evaluated in float64, PLAIN, not rounded (weights and values
+    are exact doubles; only the sums round)."""
+    D = np.asarray(D)
+    x, y, cw, rh = (int(v) for v in rect)
+    ow, oh = (int(v) for v in out_size)
+    a, b, c, d, e, f = (int(v) for v in matrix)
+    och = D.shape[2]
+    R = D[y:y + rh, x:x + cw].astype(np.float64)
+    F = np.array([(fill >> (8 * k)) & 255 for k in range(och)], dtype=np.float64)
+    U = (2 * np.arange(ow, dtype=np.int64) + 1)[None, :]
+    V = (2 * np.arange(oh, dtype=np.int64) + 1)[:, None]
+    L = super_log2(flags)
+    s = 1 << L
+    out = np.zeros((oh, ow, och), dtype=np.float64)
+    for j in range(s):
+        for i in range(s):
+            Us, Vs = s * U + (2 * i + 1 - s), s * V + (2 * j + 1 - s)
+            kx, wx, inx = _axis(((a * Us + b * Vs) >> L) + c, cw, flags)
+            ky, wy, iny = _axis(((d * Us + e * Vs) >> L) + f, rh, flags)
+            for r in range(2):
+                for k in range(2):
+                    v = np.where((iny[..., r] & inx[..., k])[..., None], R[ky[..., r], kx[..., k]], F[None, None, :])
+                    out += ((wy[..., r] / (2.0 * ONE)) * (wx[..., k] / (2.0 * ONE)))[..., None] * v
+    return out / (s * s)
 
 
 def size(w: int, h: int, it, och: int) -> int:

@@ -2,7 +2,7 @@
 """qoiwarp for the MI355X path: a set of .qoi files as PNGs, re-oriented or turned about their centre.
 
     python tools/qoiwarp_mi355x.py FILE_OR_DIR... -o DIR (--orient N | --rotate DEG [--scale S]) [--size WxH] [--border fill|replicate|reflect|reflect101|wrap]
-                                   [--sample bilinear|nearest|bicubic]
+                                   [--sample bilinear|nearest|bicubic] [--supersample 1|2|4]
                                    [--fill RRGGBBAA] [--mode plain|weighted] [--staging-mb M]
 
 Loads the .qoi files (directories are walked), uploads them as ONE pack and makes ONE qoimi_decode_warped call: every stream is decoded on the
@@ -14,7 +14,9 @@ every output pixel one source pixel: qoimi_warp_orient).  --rotate DEG turns the
 mirrors the image about its edges ("dcba|abcd|dcba", warp.REFLECT), --border reflect101 about its edge pixels ("dcb|abcd|cba", warp.REFLECT_101: the
 border cv2.warpAffine pipelines default to) and --border wrap repeats it (warp.WRAP) - --fill is then not used.  --sample nearest takes
 one source pixel per output pixel instead of the 2 x 2 bilinear taps (warp.NEAREST): for label maps, whose values must not be averaged; --sample bicubic takes 4 x 4 under Keys' cubic with a = -1/2 (warp.BICUBIC): sharper photographs under a turn.  There is no
-antialiasing: a scale well below 1 wants tools/qoiresize_mi355x.py first.  Outputs hold 4 channels if any file does, else 3, and are
+adaptive antialiasing: --supersample 2 or 4 (warp.SUPER2, warp.SUPER4; default 1; with --sample bilinear only) averages 2 x 2 or 4 x 4 bilinear
+sub-samples per output pixel with one rounding, which serves scales down to about 1/4; a scale well below that wants
+tools/qoiresize_mi355x.py first.  Outputs hold 4 channels if any file does, else 3, and are
 written as DIR/<name>.png through tools/png_io.py.  One row per file: w x h x channels, the map, the output size.  A file that is no QOI
 stream (size, magic, header rules of qoi.h:497-521) is reported and left out; exit status 1 if there was one, else 0.  Needs torch for device
 memory, as tools/qoicheck_mi355x.py does.
@@ -39,6 +41,7 @@ from tools.qoithumb_mi355x import parse_header  # noqa: E402
 ONE = 1 << 16
 BORDERS = {"fill": 0, "replicate": 1, "reflect": 64, "reflect101": 128, "wrap": 256}          # --border -> warp.REPLICATE, REFLECT, REFLECT_101, WRAP
 SAMPLES = {"bilinear": 0, "nearest": 4, "bicubic": 16}                                        # --sample -> warp.NEAREST, BICUBIC
+SUPERSAMPLES = {1: 0, 2: 1024, 4: 2048}                                                       # --supersample -> warp.SUPER2, SUPER4
 
 
 def parse_fill(text: str):
@@ -75,6 +78,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("--size", default=None, metavar="WxH")
     ap.add_argument("--border", choices=tuple(BORDERS), default="fill")
     ap.add_argument("--sample", choices=tuple(SAMPLES), default="bilinear")
+    ap.add_argument("--supersample", type=int, choices=tuple(SUPERSAMPLES), default=1)
     ap.add_argument("--fill", default="00000000", metavar="RRGGBBAA")
     ap.add_argument("--mode", choices=("plain", "weighted"), default="plain")
     ap.add_argument("--staging-mb", type=int, default=0, metavar="M", help="device memory for decoded pixels (0: 1 GiB)")
@@ -94,6 +98,9 @@ def main(argv, out=print) -> int:
         if size is None or max(size) >= 1 << 20 or size[0] * size[1] >= 400_000_000:
             out("--size must be WxH, both at least 1 and below 2**20, fewer than 400 000 000 pixels")
             return 2
+    if a.supersample != 1 and a.sample != "bilinear":
+        out("--supersample 2 or 4 goes with --sample bilinear only")
+        return 2
     fill = parse_fill(a.fill)
     if fill is None:
         out("--fill must be RRGGBBAA in hexadecimal")
@@ -112,7 +119,7 @@ def main(argv, out=print) -> int:
     if not files:
         out("no .qoi files")
         return 2
-    flags = BORDERS[a.border] | SAMPLES[a.sample]
+    flags = BORDERS[a.border] | SAMPLES[a.sample] | SUPERSAMPLES[a.supersample]
     blobs = [open(f, "rb").read() for f in files]
     heads = [parse_header(b) for b in blobs]
     good, items = [], []
