@@ -6,7 +6,12 @@ between small ones, encoded by the oracle and decoded by it for the expectation 
 index is at least 2**24: a block of noise (the flat pieces of the image would forgive a misplaced sample) and a label map of five classes
 (ordinary image content has no majority for FILTER_MODE).  Every expectation is the existing definition - the oracle's decode at the call's
 output channel count, the model of qoi_amd/, tensors.convert -, every comparison is exact and covers the whole output, and every byte around
-the outputs is a guard (0xA5) checked after every call (tests/test_gpu_labels.py: run; tests/test_gpu_warp.py: run)."""
+the outputs is a guard (0xA5) checked after every call (tests/test_gpu_labels.py: run; tests/test_gpu_warp.py: run).
+Part 3 holds the kernels of the folding borders and of supersampling to the same two regimes: warp_border_bytes and warp_border_tensor walk
+border_walk_table - more tiles than workgroups, a map that spans six and a half periods of the rectangle, so that tiles take either branch of
+warp_fold_position and some both (test_warp_border_walks_many_tiles_per_workgroup, test_warp_border_and_super_tensor_kernels_walk_many_tiles)
+- and border_items_beyond (test_border_items_beyond_2_24); warp_super_tensor walks super_walk_table, the table tests/test_gpu_warp_super.py
+runs through warp_super_bytes."""
 import numpy as np
 import pytest
 
@@ -14,7 +19,7 @@ import resize_window as rw
 from mode_cases import label_map
 from qoi_amd import mode, nearest, tensors, warp
 from qoi_amd.tensors import CHW, F16, F32, FILTER_BICUBIC, FILTER_LANCZOS, FILTER_MODE, FILTER_NEAREST, HW, HWC, I32, I64, U8
-from qoi_amd.warp import ALPHA_WEIGHTED, BICUBIC, NEAREST, ONE, PLAIN, REPLICATE
+from qoi_amd.warp import ALPHA_WEIGHTED, BICUBIC, NEAREST, ONE, PLAIN, REFLECT, REFLECT_101, REPLICATE, SUPER2, SUPER4, WRAP
 from test_gpu_encode_packed import KINDS, image
 from test_gpu_labels import IMAGENET
 from test_gpu_labels import run as run_tensors
@@ -229,3 +234,200 @@ def test_warp_bicubic_walks_many_tiles_per_workgroup(ctx, pack, cus):
     assert_equal(np.ascontiguousarray(got[1].reshape(oh, ow, 4)[5::17]).reshape(-1), warped(p, rows_of(big, 5, 17), 4, ALPHA_WEIGHTED), "every 17th row of the big entry")
     for j in (0, 2, 3, 4, 5, 6, 7):
         assert_equal(got[j], warped(p, items[j], 4, ALPHA_WEIGHTED), ("a one-tile entry", j))
+
+
+# ------------------------------------------------------------------ 3: the border kernels and the super tensor kernel in both regimes
+_WARPED = {}
+NOISE_RECT = (100, 3652, 400, 180)
+F16_CHW = (F16, CHW, *IMAGENET)
+
+
+def warped_once(p, it, och, alpha_mode):
+    """`warped`, computed once per item and shared between the tests below; never changed"""
+    key = (tuple(it), och, alpha_mode)
+    if key not in _WARPED:
+        P = warped(p, it, och, alpha_mode)
+        P.setflags(write=False)
+        _WARPED[key] = P
+    return _WARPED[key]
+
+
+def walk_shape(cus):
+    """(ow, oh, across, down) of an output of more than 3 * 8 * cus tiles of 16 x 16 whose last tile column and row are partial"""
+    across = 80
+    down = (3 * 8 * cus) // across + 1
+    return 16 * across - 3, 16 * down - 5, across, down
+
+
+def window_of(it, X0, Y0, ow, oh):
+    """the item whose output is the ow x oh window at (X0, Y0) of `it`'s: U = U' + 2 * X0 and V = V' + 2 * Y0 move every sub-sample's sum by
+    2 * s * (a * X0 + b * Y0), a multiple of s, so the shift passes it on exactly: c' = c + 2 * (a * X0 + b * Y0), f' likewise"""
+    i, x, y, cw, rh, _, _, flags, a, b, d, e, fill, _, c, f = it
+    return warp.item(i, (x, y, cw, rh), (ow, oh), (a, b, c + 2 * (a * X0 + b * Y0), d, e, f + 2 * (d * X0 + e * Y0)), flags, fill)
+
+
+def super_walk_table(cus):
+    """(items, big's index) of tests/test_gpu_warp_super.py: test_many_tiles_per_workgroup_beyond_2_24 - [small, big, small x 5, small]: big shears
+    the planted noise under SUPER2 | REFLECT into more than 3 * 8 * cus tiles, the five behind it are one-tile items of `huge` of both flags and
+    the older samplings"""
+    ow, oh, _, _ = walk_shape(cus)
+    rect = NOISE_RECT
+    a, b, d, e = round(ONE * 1.1 * rect[2] / ow), round(ONE * 0.12 * rect[2] / oh), round(-ONE * 0.1 * rect[3] / ow), round(ONE * 1.1 * rect[3] / oh)
+    big = warp.item(HUGE, rect, (ow, oh), (a, b, rect[2] * ONE - a * ow - b * oh, d, e, rect[3] * ONE - d * ow - e * oh), SUPER2 | REFLECT, FILL)     # a shear about the centre
+    kinds = (SUPER4 | REPLICATE, NEAREST, SUPER2, BICUBIC | WRAP, SUPER4 | REFLECT_101)
+    inner = [warp.item(HUGE, (HW_ - 19 - j, HH - 17 - j, 19, 17), (11 + j, 5), warp.rotation((19, 17), (11 + j, 5), 25.0 * j, 0.4), s, FILL) for j, s in enumerate(kinds)]
+    return [warp.item(DOT, (0, 0, 1, 1), (5, 4), (ONE // 3, 0, 0, 0, ONE // 3, 0), SUPER4, FILL), big] + inner + [warp.item(SPRITE, (100, 40, 30, 30), (7, 7), (4 * ONE, 0, 0, 0, 4 * ONE, 0), SUPER4)]
+
+
+def super_windows(ow, oh):
+    """the four 45 x 27 windows of the big entry of super_walk_table that are compared with the model: the corners of the walk"""
+    return ((0, 0), (ow - 45, 3), (5, oh - 27), (ow - 45, oh - 27))
+
+
+BIG_BORDERS = {"bilinear, reflect": REFLECT, "bicubic, wrap": BICUBIC | WRAP}
+
+
+def period_of(n, flags):
+    return {REFLECT: 2 * n, REFLECT_101: max(2 * n - 2, 1), WRAP: n}[flags & warp.BORDERS]
+
+
+def border_walk_table(cus, flags):
+    """[small, big, small x 5, small] for one launch of warp_border_bytes / warp_border_tensor: big samples the planted noise under the border
+    of `flags` and a shear about the rectangle's centre that spans six and a half periods of the rectangle on either axis, into more than
+    3 * 8 * cus tiles of 16 x 16 (the last column and row of tiles partial); the five behind it are one-tile items of the last rows of `huge`
+    that cover the three borders and the three samplings; a one-tile item of a small image stands on either side"""
+    ow, oh, _, _ = walk_shape(cus)
+    rect = NOISE_RECT
+    Px, Py = period_of(rect[2], flags), period_of(rect[3], flags)
+    a, b, d, e = round(ONE * 6.5 * Px / ow), round(ONE * 0.4 * Px / oh), round(-ONE * 0.4 * Py / ow), round(ONE * 6.5 * Py / oh)
+    big = warp.item(HUGE, rect, (ow, oh), (a, b, rect[2] * ONE - a * ow - b * oh, d, e, rect[3] * ONE - d * ow - e * oh), flags, FILL)
+    kinds = (REFLECT | NEAREST, REFLECT_101 | BICUBIC, WRAP, REFLECT_101 | NEAREST, REFLECT | BICUBIC)
+    inner = [warp.item(HUGE, (HW_ - 9 - j, HH - 7 - j, 9, 7), (11 + j, 5), warp.rotation((9, 7), (11 + j, 5), 25.0 * j, 0.3), s, FILL) for j, s in enumerate(kinds)]
+    items = [warp.item(DOT, (0, 0, 1, 1), (5, 4), (ONE // 3, 0, 0, 0, ONE // 3, 0), WRAP | BICUBIC, FILL), big] + inner
+    items.append(warp.item(SPRITE, (120, 60, 10, 10), (7, 7), (3 * ONE, 0, -40 * ONE, 0, 3 * ONE, 55 * ONE), REFLECT_101 | NEAREST))
+    assert {s & warp.BORDERS for s in kinds} == {REFLECT, REFLECT_101, WRAP} and {s & ~warp.BORDERS for s in kinds} == {0, NEAREST, BICUBIC}
+    assert not any(it[7] & (SUPER2 | SUPER4) for it in items)
+    return items
+
+
+def first_taps(it, X, Y):
+    """(kx, ky): the first tap index of each axis that warp_fold_position folds for the output pixels (X, Y) (arrays) of a bilinear or bicubic
+    item - the bicubic one a sample before the bilinear one"""
+    _, _, _, _, _, _, _, flags, a, b, d, e, _, _, c, f = it
+    U, V = 2 * np.asarray(X, dtype=np.int64) + 1, 2 * np.asarray(Y, dtype=np.int64) + 1
+    back = 1 if flags & BICUBIC else 0
+    return ((a * U + b * V + c - ONE) >> 17) - back, ((d * U + e * V + f - ONE) >> 17) - back
+
+
+def assert_the_fold_takes_both_branches(big):
+    """from the item's coefficients, at the corner pixels of every tile: on either axis the map spans at least five periods; the first and the
+    last tile lie wholly in the estimate branch of warp_fold_position (k < -P or k >= 2P), a tile in the middle wholly in the conditional
+    one, and there are tiles whose corners lie on either side of k = -P and of k = 2P - lanes of one workgroup in different branches"""
+    _, _, _, cw, rh, ow, oh, flags = big[:8]
+    x0, y0 = np.arange(0, ow, 16), np.arange(0, oh, 16)
+    x1, y1 = np.minimum(x0 + 15, ow - 1), np.minimum(y0 + 15, oh - 1)
+    corners = [first_taps(big, X[None, :], Y[:, None]) for X in (x0, x1) for Y in (y0, y1)]             # [corner][axis][tile row, tile column]
+    for axis, n in ((0, cw), (1, rh)):
+        P = period_of(n, flags)
+        k = np.stack([c[axis] for c in corners])
+        assert int(k.max()) - int(k.min()) >= 5 * P, (axis, int(k.min()), int(k.max()), P)
+        estimate = (k < -P) | (k >= 2 * P)
+        assert estimate[:, 0, 0].all() and estimate[:, -1, -1].all()                                     # the first and the last tile
+        assert (~estimate).all(axis=0)[len(y0) // 2, len(x0) // 2]                                       # the tile in the middle
+        for edge in (-P, 2 * P):
+            across = (k < edge).any(axis=0) & (k >= edge).any(axis=0)
+            assert across.any(), (axis, edge)
+        assert estimate.all(axis=0).sum() > 10 and (~estimate).all(axis=0).sum() > 10
+
+
+@pytest.mark.parametrize("flags", list(BIG_BORDERS.values()), ids=list(BIG_BORDERS))
+def test_warp_border_walks_many_tiles_per_workgroup(ctx, pack, cus, flags):
+    """[small, big, small x 5, small] in one launch of warp_border_bytes (border_walk_table).  big's map reaches three periods to either side
+    of the rectangle, so whole tiles take the conditional branch of the fold, whole tiles its quotient estimate, and tiles between them both
+    (assert_the_fold_takes_both_branches, on the CPU); the bicubic big folds its first tap at k - 1.  The big output is compared WHOLE with
+    the same item alone in its own call, every 17th row of it - every phase of a tile's 16 rows - with the model (rows_of), the small items
+    with the model."""
+    p = pack
+    ow, oh, across, down = walk_shape(cus)
+    items = border_walk_table(cus, flags)
+    big = items[1]
+    tiles = [warp.tiles(it[5], it[6]) for it in items]
+    assert tiles[1] == across * down > 3 * 8 * cus and tiles[:1] + tiles[2:] == [1] * 7 and past_2_24(items) and ow * oh < warp.MAX_AREA
+    assert ow % 16 and oh % 16
+    assert_the_fold_takes_both_branches(big)
+    small = warp.item(HUGE, NOISE_RECT, (40, 60), warp.rotation(NOISE_RECT[2:], (40, 60), 30.0, 0.05), flags, FILL)
+    assert np.array_equal(warped(p, rows_of(small, 5, 17), 4, ALPHA_WEIGHTED), warped(p, small, 4, ALPHA_WEIGHTED)[5::17])
+    got = run_warp(ctx, p, 4, items, ALPHA_WEIGHTED, front=64 + 3)
+    assert ctx.warp_stats()[:2] == (1, 1)
+    alone = run_warp(ctx, p, 4, [big], ALPHA_WEIGHTED)
+    assert np.array_equal(got[1], alone[0]), ("the big entry differs from its own call", int(np.argmax(got[1] != alone[0])))
+    assert_equal(np.ascontiguousarray(got[1].reshape(oh, ow, 4)[5::17]).reshape(-1), warped_once(p, rows_of(big, 5, 17), 4, ALPHA_WEIGHTED), "every 17th row of the big entry")
+    for j in (0, 2, 3, 4, 5, 6, 7):
+        assert_equal(got[j], warped_once(p, items[j], 4, ALPHA_WEIGHTED), ("a one-tile entry", j))
+
+
+@pytest.mark.parametrize("table", list(BIG_BORDERS) + ["super2, reflect"])
+def test_warp_border_and_super_tensor_kernels_walk_many_tiles(ctx, pack, cus, table):
+    """The tables of the test above and of tests/test_gpu_warp_super.py: test_many_tiles_per_workgroup_beyond_2_24 as f16 CHW tensors: one launch
+    of warp_border_tensor or warp_super_tensor over more tiles than it has workgroups and staged pixel indices from 2**24 on.  The small
+    items, and the rows (border) or windows (super) of big that the u8 tests compare with the model, are tensors.convert of the model; the
+    whole of big is what the item alone gives in its own tensor call."""
+    p = pack
+    ow, oh, across, down = walk_shape(cus)
+    items = super_walk_table(cus) if table.startswith("super") else border_walk_table(cus, BIG_BORDERS[table])
+    big = items[1]
+    assert warp.tiles(ow, oh) == across * down > 3 * 8 * cus and big[5:7] == (ow, oh) and past_2_24(items)
+    assert any(it[7] & (SUPER2 | SUPER4) for it in items) == table.startswith("super")
+    got = run_tensors(ctx, p, "warp", 4, items, ALPHA_WEIGHTED, F16_CHW)
+    assert ctx.tensor_stats()[:2] == (1, 1)
+    alone = run_tensors(ctx, p, "warp", 4, [big], ALPHA_WEIGHTED, F16_CHW)
+    assert ctx.tensor_stats()[:2] == (1, 1)
+    assert np.array_equal(got[1], alone[0]), ("the big entry differs from its own call", int(np.argmax(got[1] != alone[0])) // 2)
+    whole = got[1].view(np.uint16).reshape(4, oh, ow)
+
+    def halves(u8):
+        return tensors.convert(u8, F16_CHW).view(np.uint16)
+
+    if table.startswith("super"):
+        for X0, Y0 in super_windows(ow, oh):
+            want = halves(warped_once(p, window_of(big, X0, Y0, 45, 27), 4, ALPHA_WEIGHTED))
+            assert np.array_equal(whole[:, Y0:Y0 + 27, X0:X0 + 45], want), ("a window of the big entry", X0, Y0)
+    else:
+        assert np.array_equal(whole[:, 5::17], halves(warped_once(p, rows_of(big, 5, 17), 4, ALPHA_WEIGHTED))), "every 17th row of the big entry"
+    for j in (0, 2, 3, 4, 5, 6, 7):
+        assert_equal(got[j], tensors.convert(warped_once(p, items[j], 4, ALPHA_WEIGHTED), F16_CHW), ("a one-tile entry", j))
+    # A consistency check only, not an expectation: the tensor of big is the conversion of what the u8 kernel writes for the same item.  The
+    # sampling is shared, so a failure here and not above localises to the sink, not to the sampling.
+    u8 = run_warp(ctx, p, 4, [big], ALPHA_WEIGHTED)[0].reshape(oh, ow, 4)
+    assert np.array_equal(whole, halves(u8)), "consistency: the tensor sink and the byte sink disagree on the big entry"
+
+
+def border_items_beyond():
+    """warp_items with a border on every item over `huge`: the planted noise turned and reduced by 10 - the output reaches about a period to either
+    side of the rectangle - and the image's bottom right corner turned and reduced by 2 - about two periods -, each border with each sampling
+    between them; a bordered item of a small image in front, an item without a border behind"""
+    a, b = NOISE_RECT, (HW_ - 37, HH - 29, 37, 29)
+    ma, mb = warp.rotation(a[2:], (64, 64), 30.0, 0.1), warp.rotation(b[2:], (50, 41), -20.0, 0.5)
+    flags = (REFLECT, REFLECT_101 | BICUBIC, WRAP | NEAREST, WRAP, REFLECT | BICUBIC, REFLECT_101 | NEAREST, REFLECT_101, WRAP | BICUBIC, REFLECT | NEAREST)
+    over = [warp.item(HUGE, r, s, m, fl, FILL) for fl, (r, s, m) in zip(flags, [(a, (64, 64), ma), (b, (50, 41), mb)] * 5)]
+    return [warp.item(ODD, (2, 3, 30, 17), (20, 11), warp.rotation((30, 17), (20, 11), 10.0, 0.3), REFLECT | BICUBIC, FILL)] + over + \
+           [warp.item(SPRITE, (5, 7, 100, 50), (33, 21), warp.rotation((100, 50), (33, 21), 45.0, 0.4), 0, FILL)]
+
+
+def test_border_items_beyond_2_24(ctx, pack):
+    """qoimi_decode_warped and qoimi_decode_warped_tensors with REFLECT, REFLECT_101 and WRAP in every sampling over rectangles whose every staged
+    pixel index is at least 2**24 (warp_border_bytes, warp_border_tensor)"""
+    p = pack
+    items = border_items_beyond()
+    over = [it for it in items if it[0] == HUGE]
+    assert past_2_24(items) and len(over) == 9 and {(it[7] & warp.BORDERS, it[7] & ~warp.BORDERS) for it in over} == {(b, s) for b in (REFLECT, REFLECT_101, WRAP) for s in (0, NEAREST, BICUBIC)}
+    assert not any(it[7] & (SUPER2 | SUPER4) for it in items)
+    for channels, alpha_mode in ((4, ALPHA_WEIGHTED), (3, PLAIN)):
+        got = run_warp(ctx, p, channels, items, alpha_mode, front=64 + 1)
+        assert ctx.warp_stats()[:2] == (1, 1)
+        for j, it in enumerate(items):
+            assert_equal(got[j], warped_once(p, it, channels, alpha_mode), ("warped", channels, j))
+    got = run_tensors(ctx, p, "warp", 4, items, ALPHA_WEIGHTED, F16_CHW)
+    assert ctx.tensor_stats()[:2] == (1, 1)
+    for j, it in enumerate(items):
+        assert_equal(got[j], tensors.convert(warped_once(p, it, 4, ALPHA_WEIGHTED), F16_CHW), ("warped tensors", j))

@@ -21,18 +21,22 @@ That the decoy of every item of the newer filters and samplings resamples to oth
     qoimi_encode_batch                              pixel stride, stream stride (two images, the second wholly beyond)
     qoimi_encode_packed                             pixel stride
     qoimi_decode_batch                              pixel stride
-    qoimi_encode_tiles                              pixel_offsets (f = 1, 3, 64; both modes)
+    qoimi_encode_tiles                              pixel_offsets (f = 1, 3, 64; PLAIN and ALPHA_WEIGHTED: tile_gather; NEAREST, and MODE with
+                                                    f = 1, 3, 16: tile_select; each at channels 0, 4, 3; one launch per sub-batch)
     qoimi_decode_thumbnails                         stream_offsets, thumb_offsets
     qoimi_decode_crops / _resized / _bilinear / _warped                 stream_offsets, out_offsets
     qoimi_decode_tensors, all six filters (tensor_area, tensor_tent, tensor_cubic, tensor_lanczos, tensor_nearest, tensor_mode)
                                                     stream_offsets, out_offsets (FORMATS: every dtype - u8, f16, bf16, f32, i32, i64 - and
                                                     every layout - HWC, CHW, HW - lies across byte B32 and beyond it at least once)
-    qoimi_decode_warped_tensors                     stream_offsets, out_offsets, three lists of items (below)
+    qoimi_decode_warped_tensors                     stream_offsets, out_offsets, five lists of items (below)
     qoimi_decode_crops_indexed / _resized_indexed / _bilinear_indexed / _warped_indexed
                                                     stream_offsets, out_offsets, the index built over the high pack
-    the warp calls (u8, tensors, indexed) take three lists: WARPS (bilinear items alone: warp_gather / tensor_warp), WARPS_NEAREST (nearest
-    and bilinear items, none bicubic: the nearest branch of the same kernels) and WARPS_CUBIC (bicubic, bilinear and nearest items in one
-    call: warp_bicubic_bytes / warp_bicubic_tensor serve all of them)
+    the warp calls (u8, tensors, indexed) take five lists: WARPS (bilinear items alone: warp_gather / tensor_warp), WARPS_NEAREST (nearest
+    and bilinear items, none bicubic: the nearest branch of the same kernels), WARPS_CUBIC (bicubic, bilinear and nearest items in one
+    call: warp_bicubic_bytes / warp_bicubic_tensor serve all of them), WARPS_BORDER (REFLECT, REFLECT_101 and WRAP with each sampling, and
+    fill, REPLICATE and bicubic items, in one call: warp_border_bytes / warp_border_tensor; two maps several periods away) and WARPS_SUPER
+    (SUPER2 and SUPER4 with the fill and every border, and bilinear, nearest, bicubic and bordered items, in one call: warp_super_bytes /
+    warp_super_tensor); the tensor formats of the last two cover every dtype between them and every layout each
     qoimi_build_seek_index                          stream_offsets
     qoimi_seek_index_from_pixels                    pixel_offsets, stream_offsets
     qoimi_make_band_streams                         stream_offsets, out_offsets
@@ -418,29 +422,44 @@ TILES = [(SPRITE, 0, 0, 130, 70, 1, 0), (SPRITE, 3, 5, 120, 64, 3, 1), (SPRITE, 
          (LABEL3, 0, 2, 37, 27, 3, 1), (LABEL, 1, 0, 69, 45, 1, 2)]
 
 
+# the label modes (tile_select): MODE votes over blocks of at most 16 x 16 pixels, so its list has the 64-fold tiles of TILES 16-fold
+TILES_MODE = [t[:5] + (16 if t[5] == 64 else t[5],) + t[6:] for t in TILES]
+BOX_MODES = ((0, tiles.PLAIN), (4, tiles.ALPHA_WEIGHTED), (3, tiles.PLAIN))
+LABEL_MODES = tuple((channels, mode) for mode in (tiles.NEAREST, tiles.MODE) for channels in (0, 4, 3))
+assert {t[5] for t in TILES} == {1, 3, 64} and {t[5] for t in TILES_MODE} == {1, 3, 16} and tiles.MODE_MAX_FACTOR == 16
+assert [t[:5] + t[6:] for t in TILES_MODE] == [t[:5] + t[6:] for t in TILES] and TILES[2][5] == 64 and TILES_MODE[2][5] == 16
+
+
 @gpu
 def test_encode_tiles(ctx, oracle, pack, src, dst):
+    """tile_gather in both box modes, then tile_select in NEAREST and MODE - a kernel of its own that reads `pixels + e.src_off` itself -, each
+    at channels 0, 4 and 3 over the same pixel_offsets: control, straddling and beyond"""
     import torch
     b = pack.b
-    assert {t[5] for t in TILES} == {1, 3, 64} and {t[0] for t in TILES} == set(range(b.n))
+    assert {t[0] for t in TILES} == set(range(b.n))
     po = layout([px.size for px in b.px], lane=1)
     src.place(po, b.px, pack.decoy_px)
+    assert any(o >= B32 for o in po) and any(o < B32 < o + px.size for o, px in zip(po, b.px))
     images = [px.reshape(h, w, ch) for px, (w, h, ch) in zip(b.px, SHAPES)]
-    for channels, mode in ((0, tiles.PLAIN), (4, tiles.ALPHA_WEIGHTED), (3, tiles.PLAIN)):
-        px = [tiles.tile(images[t[0]], t, channels, mode) for t in TILES]
+    for channels, mode in BOX_MODES + LABEL_MODES:
+        ts = TILES_MODE if mode == tiles.MODE else TILES
+        assert {t[5] for t in ts} == ({1, 3, 16} if mode == tiles.MODE else {1, 3, 64})
+        px = [tiles.tile(images[t[0]], t, channels, mode) for t in ts]
         want = [oracle.encode(p.reshape(-1), p.shape[1], p.shape[0], p.shape[2], 0) for p in px]
-        decoy = tiles.tile(pack.decoy_px[SPRITE].reshape(70, 130, 4), TILES[2], channels, mode)
-        assert not np.array_equal(decoy, px[2])                    # even the 64-fold reduction tells the decoy
+        decoy = tiles.tile(pack.decoy_px[SPRITE].reshape(70, 130, 4), ts[2], channels, mode)
+        assert not np.array_equal(decoy, px[2])                    # even the 64-fold (MODE: 16-fold) reduction tells the decoy
         lens = [len(s) for s in want]
         want_off = pack_offsets(lens, 1)
-        off = torch.full((len(TILES) + 1,), -1, dtype=torch.int64, device="cuda")
-        d_len = torch.full((len(TILES),), -1, dtype=torch.int32, device="cuda")
-        got_off, got_len, got_descs = ctx.encode_tiles(src.t.data_ptr(), po, b.descs, channels, TILES, mode, 1, dst.t.data_ptr(), int(want_off[-1]),
+        off = torch.full((len(ts) + 1,), -1, dtype=torch.int64, device="cuda")
+        d_len = torch.full((len(ts),), -1, dtype=torch.int32, device="cuda")
+        got_off, got_len, got_descs = ctx.encode_tiles(src.t.data_ptr(), po, b.descs, channels, ts, mode, 1, dst.t.data_ptr(), int(want_off[-1]),
                                                        off.data_ptr(), d_len.data_ptr())
         what = ("encode_tiles", channels, mode)
         assert np.array_equal(got_off, want_off) and got_len.tolist() == lens and d_len.cpu().numpy().tolist() == lens, what
         assert [(d.width, d.height, d.channels) for d in got_descs] == [(p.shape[1], p.shape[0], p.shape[2]) for p in px], what
         assert_bytes(dst.take([int(o) for o in want_off[:-1]], lens, what), want, what)
+        subs = tiles.plan(SHAPES, ts, channels, 0)[1]
+        assert ctx.tile_stats()[:2] == (len(subs), len(subs)), what       # one launch (tile_gather, or tile_select) per sub-batch
     src.check()
 
 
@@ -474,13 +493,71 @@ WARPS_NEAREST = [warp.item(SPRITE, (20, 17, 100, 50), (33, 18), warp.rotation((1
 assert {it[7] for it in WARPS} == {0, warp.REPLICATE} and not any(it[7] & warp.BICUBIC for it in WARPS_NEAREST)
 assert {it[7] & ~warp.REPLICATE for it in WARPS_CUBIC} == {0, warp.NEAREST, warp.BICUBIC} and {it[7] & ~warp.REPLICATE for it in WARPS_NEAREST} == {0, warp.NEAREST}
 assert {warp.BICUBIC, warp.BICUBIC | warp.REPLICATE, warp.NEAREST, warp.NEAREST | warp.REPLICATE} <= {it[7] for it in WARPS_CUBIC}
+# The fourth and fifth warp lists.  WARPS_BORDER: every folding border with every sampling, and items without such a border - fill, REPLICATE,
+# bicubic - in ONE call, none with a SUPER flag: one bordered item sends the whole call to warp_border_bytes / warp_border_tensor.  Two of its
+# maps lie several periods away from their rectangles (the quotient estimate of warp_fold_position), the others within one (its conditional
+# branch).  WARPS_SUPER: both SUPER flags with the fill and each of the four borders, and one item of each older kind - bilinear, nearest,
+# bicubic, bordered -: one SUPER item sends the whole call to warp_super_bytes / warp_super_tensor.  In both every image of the pack has an
+# item, every image with seek rows one that begins below a seek row, and no output is larger than 41 x 29.
+FOLDING = (warp.REFLECT, warp.REFLECT_101, warp.WRAP)
+SAMPLINGS = (0, warp.NEAREST, warp.BICUBIC)
+ONE = warp.ONE
+WARPS_BORDER = [warp.item(SPRITE, (20, 17, 100, 50), (33, 18), warp.rotation((100, 50), (33, 18), 30.0, 0.2), warp.REFLECT, FILL),
+                warp.item(RGB, (3, 9, 30, 20), (17, 16), warp.rotation((30, 20), (17, 16), 30.0, 0.5), warp.REFLECT | warp.NEAREST, FILL),
+                warp.item(NOISE, (0, 13, 64, 35), (41, 29), warp.rotation((64, 35), (41, 29), -20.0, 0.4), warp.REFLECT | warp.BICUBIC, FILL),
+                warp.item(LABEL, (5, 3, 63, 41), (33, 18), warp.rotation((63, 41), (33, 18), 30.0, 0.3), warp.REFLECT_101 | warp.NEAREST, FILL),
+                warp.item(COLUMN, (0, 3, 1, 90), (5, 29), warp.rotation((1, 90), (5, 29), 10.0, 0.2), warp.REFLECT_101, FILL),
+                warp.item(SPRITE, (0, 40, 130, 30), (41, 29), warp.rotation((130, 30), (41, 29), -20.0, 0.25), warp.REFLECT_101 | warp.BICUBIC, FILL),
+                warp.item(LABEL3, (2, 1, 33, 25), (40, 29), warp.rotation((33, 25), (40, 29), -15.0, 0.6), warp.WRAP | warp.NEAREST, FILL),
+                warp.item(NOISE, (8, 13, 33, 30), (23, 29), (ONE + 300, 4000, 2 * ONE * 33 * 5 + 777, -2500, ONE - 200, -2 * ONE * 30 * 7 - 999), warp.WRAP, FILL),
+                warp.item(RGB, (1, 4, 35, 24), (19, 18), (ONE, 23000, -2 * ONE * 35 * 40 - 40000, -9000, ONE + 700, 2 * ONE * 24 * 9 + 12345), warp.WRAP | warp.BICUBIC, FILL),
+                warp.item(TINY, (0, 0, 1, 1), (2, 2), warp.IDENTITY, warp.REFLECT_101, 0),
+                warp.item(SPRITE, (20, 17, 100, 50), (33, 18), warp.rotation((100, 50), (33, 18), 30.0, 0.3), 0, FILL),
+                warp.item(NOISE, (8, 13, 33, 30), (23, 29), warp.rotation((33, 30), (23, 29), 90.0, 0.8), warp.REPLICATE, 0),
+                warp.item(RGB, (3, 9, 30, 20), (17, 16), warp.rotation((30, 20), (17, 16), 30.0, 0.9), warp.BICUBIC, FILL)]
+WARPS_SUPER = [warp.item(SPRITE, (20, 17, 100, 50), (33, 18), warp.rotation((100, 50), (33, 18), 30.0, 0.3), warp.SUPER2, FILL),
+               warp.item(SPRITE, (0, 40, 130, 30), (41, 29), warp.rotation((130, 30), (41, 29), -20.0, 0.25), warp.SUPER4, FILL),
+               warp.item(RGB, (3, 9, 30, 20), (17, 16), warp.rotation((30, 20), (17, 16), 30.0, 0.5), warp.SUPER2 | warp.REPLICATE, 0),
+               warp.item(NOISE, (0, 13, 64, 35), (41, 29), warp.rotation((64, 35), (41, 29), -20.0, 0.4), warp.SUPER4 | warp.REPLICATE, 0),
+               warp.item(NOISE, (8, 13, 33, 30), (23, 29), warp.rotation((33, 30), (23, 29), 90.0, 0.4), warp.SUPER2 | warp.REFLECT, FILL),
+               warp.item(LABEL, (5, 3, 63, 41), (33, 18), warp.rotation((63, 41), (33, 18), 30.0, 0.3), warp.SUPER4 | warp.REFLECT, FILL),
+               warp.item(COLUMN, (0, 3, 1, 90), (5, 29), warp.rotation((1, 90), (5, 29), 10.0, 0.2), warp.SUPER2 | warp.REFLECT_101, FILL),
+               warp.item(LABEL3, (2, 1, 33, 25), (20, 15), warp.rotation((33, 25), (20, 15), -15.0, 0.3), warp.SUPER4 | warp.REFLECT_101, FILL),
+               warp.item(RGB, (1, 4, 35, 24), (19, 18), (3 * ONE, 23000, -2 * ONE * 35 * 40 - 40000, -9000, 3 * ONE + 700, 2 * ONE * 24 * 9 + 12345), warp.SUPER2 | warp.WRAP, FILL),
+               warp.item(TINY, (0, 0, 1, 1), (2, 2), warp.IDENTITY, warp.SUPER4 | warp.WRAP, 0),
+               warp.item(SPRITE, (20, 17, 100, 50), (33, 18), warp.rotation((100, 50), (33, 18), -30.0, 0.3), 0, FILL),
+               warp.item(LABEL, (1, 0, 64, 45), (33, 18), warp.rotation((64, 45), (33, 18), 30.0, 0.9), warp.NEAREST | warp.REPLICATE, 0),
+               warp.item(NOISE, (3, 6, 40, 30), (17, 16), warp.rotation((40, 30), (17, 16), 45.0, 0.7), warp.BICUBIC, FILL),
+               warp.item(RGB, (3, 9, 30, 20), (17, 16), warp.rotation((30, 20), (17, 16), 30.0, 0.4), warp.REFLECT | warp.BICUBIC, FILL)]
+
+
+def leaves_by_periods(it):
+    """how many periods of its border the farthest tap of an item lies from the rectangle, the larger of the two axes: above 2 the fold takes its
+    quotient estimate (qoi_warp_border_core.h: warp_fold_position), up to 1 its conditional add or subtract alone"""
+    _, _, _, cw, rh, ow, oh, flags, a, b, d, e, _, _, c, f = it
+    U, V = (2 * np.arange(ow, dtype=np.int64) + 1)[None, :], (2 * np.arange(oh, dtype=np.int64) + 1)[:, None]
+    worst = 0
+    for P, n in ((a * U + b * V + c, cw), (d * U + e * V + f, rh)):
+        period = {warp.REFLECT: 2 * n, warp.REFLECT_101: max(2 * n - 2, 1), warp.WRAP: n}[flags & warp.BORDERS]
+        k = (P - (0 if flags & warp.NEAREST else ONE)) >> 17
+        worst = max(worst, int(-k.min()) // period, int(k.max()) // period)
+    return worst
+
+
+assert {(it[7] & warp.BORDERS, it[7] & ~warp.BORDERS) for it in WARPS_BORDER} >= {(b, s) for b in FOLDING for s in SAMPLINGS}
+assert {0, warp.REPLICATE, warp.BICUBIC} <= {it[7] for it in WARPS_BORDER} and not any(it[7] & warp.SUPERS for it in WARPS_BORDER)
+_far = [leaves_by_periods(it) for it in WARPS_BORDER if it[7] & warp.BORDERS & ~warp.REPLICATE]
+assert sum(n > 2 for n in _far) >= 2 and sum(n <= 1 for n in _far) >= 2, _far         # (the column of width 1 has a period of 1 or 2: far as well)
+assert {(it[7] & warp.SUPERS, it[7] & warp.BORDERS) for it in WARPS_SUPER if it[7] & warp.SUPERS} == {(s, b) for s in (warp.SUPER2, warp.SUPER4) for b in (0, warp.REPLICATE) + FOLDING}
+assert {it[7] for it in WARPS_SUPER if not it[7] & warp.SUPERS} == {0, warp.NEAREST | warp.REPLICATE, warp.BICUBIC, warp.REFLECT | warp.BICUBIC}
+assert all(it[5] <= 41 and it[6] <= 29 for it in WARPS_BORDER + WARPS_SUPER)
 # The items of the newer filters of qoimi_decode_tensors: ITEMS whole - no filter's `size` rejects one of them: the largest reduction is
 # 97 to 13 (the filters stop at 16), the largest side 130 (they stop at 16384) - and rectangles of the label maps, where FILTER_MODE has
 # majorities and ties in cells of 1 to 16 x 15 pixels (the items of tests/mode_cases.py among them)
 LABEL_ITEMS = [(LABEL, 0, 0, 70, 45, 16, 11, 1), (LABEL, 3, 5, 31, 23, 7, 20, 2), (LABEL, 1, 0, 64, 45, 4, 3, 0), (LABEL3, 0, 0, 37, 29, 9, 7, 3), (LABEL3, 0, 0, 37, 29, 50, 7, 0)]
 FILTERS = {"resized": FILTER_AREA, "bilinear": FILTER_BILINEAR, "bicubic": FILTER_BICUBIC, "lanczos": FILTER_LANCZOS, "nearest": FILTER_NEAREST, "mode": FILTER_MODE}
 NEWER = {"bicubic": ITEMS + LABEL_ITEMS, "lanczos": ITEMS + LABEL_ITEMS, "nearest": ITEMS + LABEL_ITEMS, "mode": ITEMS + LABEL_ITEMS,
-         "warped_cubic": WARPS_CUBIC, "warped_nearest": WARPS_NEAREST}
+         "warped_cubic": WARPS_CUBIC, "warped_nearest": WARPS_NEAREST, "warped_border": WARPS_BORDER, "warped_super": WARPS_SUPER}
 _MODELS = {}
 
 
@@ -509,7 +586,8 @@ def model(p, kind, it, och, mode):
     return _MODELS[key]
 
 
-GATHERS = {"crops": CROPS, "resized": ITEMS, "bilinear": ITEMS, "warped": WARPS, "warped_cubic": WARPS_CUBIC, "warped_nearest": WARPS_NEAREST}
+GATHERS = {"crops": CROPS, "resized": ITEMS, "bilinear": ITEMS, "warped": WARPS, "warped_cubic": WARPS_CUBIC, "warped_nearest": WARPS_NEAREST,
+           "warped_border": WARPS_BORDER, "warped_super": WARPS_SUPER}
 
 
 def gather_call(ctx, kind, streams, so, p, och, mode, index=None):
@@ -548,7 +626,7 @@ def test_the_decoys_of_the_newer_items_differ(oracle):
             for j, it in enumerate(items):
                 assert not np.array_equal(resample(true, kind, it, och, mode), resample(decoy, kind, it, och, mode)), (kind, och, mode, j)
                 checked += 1
-    assert checked >= 4 * 2 * len(ITEMS + LABEL_ITEMS) + 2 * (len(WARPS_CUBIC) + len(WARPS_NEAREST))
+    assert checked >= 4 * 2 * len(ITEMS + LABEL_ITEMS) + 2 * (len(WARPS_CUBIC) + len(WARPS_NEAREST) + len(WARPS_BORDER) + len(WARPS_SUPER))
 
 
 def assert_streams_high(so, sizes):
@@ -581,9 +659,13 @@ FORMATS = {"resized": OLDER_FORMATS, "bilinear": OLDER_FORMATS, "warped": OLDER_
            "nearest": ((I64, HW, 4, 0), (I32, CHW, 3, 0), (U8, HWC, 3, 0), (F16, CHW, 4, 1)),
            "mode": ((I64, HW, 3, 0), (I32, HWC, 4, 0), (U8, CHW, 4, 1), (BF16, HWC, 3, 0)),
            "warped_cubic": ((F16, HWC, 4, 1), (F32, CHW, 3, 0), (I64, HW, 4, 1), (U8, CHW, 3, 0)),
-           "warped_nearest": ((I64, HW, 4, 0), (I32, CHW, 3, 0), (BF16, HWC, 4, 1), (U8, HW, 3, 0))}
+           "warped_nearest": ((I64, HW, 4, 0), (I32, CHW, 3, 0), (BF16, HWC, 4, 1), (U8, HW, 3, 0)),
+           "warped_border": ((BF16, HWC, 4, 1), (U8, CHW, 3, 0), (I32, HW, 4, 0), (F32, CHW, 3, 0)),
+           "warped_super": ((I64, HW, 3, 0), (F16, CHW, 4, 1), (BF16, HWC, 3, 0), (I32, CHW, 4, 1))}
 assert {f[0] for k in ("bicubic", "lanczos", "nearest", "mode") for f in FORMATS[k]} == {U8, F16, BF16, F32, I32, I64}
 assert {f[0] for k in ("warped_cubic", "warped_nearest") for f in FORMATS[k]} == {U8, F16, BF16, F32, I32, I64}
+assert {f[0] for k in ("warped_border", "warped_super") for f in FORMATS[k]} == {U8, F16, BF16, F32, I32, I64}
+assert all(len(FORMATS[k]) == 4 for k in ("warped_border", "warped_super"))
 assert all({f[1] for f in FORMATS[k]} == {HWC, CHW, HW} for k in NEWER) and all({f[2] for f in FORMATS[k]} == {3, 4} for k in FORMATS)
 
 

@@ -18,7 +18,7 @@ from qoi_amd.tensors import CHW, F16, F32, HWC
 from qoi_amd.warp import ALPHA_WEIGHTED, BICUBIC, NEAREST, ONE, PLAIN, REFLECT, REFLECT_101, REPLICATE, SUPER2, SUPER4, WRAP
 from test_gpu_encode_packed import KINDS, filled, image
 from test_gpu_labels import IMAGENET, run as run_tensors
-from test_gpu_newer_wide import huge_with_plantings, past_2_24
+from test_gpu_newer_wide import huge_with_plantings, past_2_24, super_walk_table, super_windows, walk_shape, window_of
 from test_gpu_resize_wide import OraclePack
 from test_gpu_thumbnails import Pack, batch_of
 from test_gpu_warp import run as run_warp
@@ -270,13 +270,6 @@ def wide(api, oracle):
     return OraclePack(api, oracle, WIDE_SHAPES, px)
 
 
-def window_of(it, X0, Y0, ow, oh):
-    """the item whose output is the ow x oh window at (X0, Y0) of `it`'s: U = U' + 2 * X0 and V = V' + 2 * Y0 move every sub-sample's sum by
-    2 * s * (a * X0 + b * Y0), a multiple of s, so the shift passes it on exactly: c' = c + 2 * (a * X0 + b * Y0), f' likewise"""
-    i, x, y, cw, rh, _, _, flags, a, b, d, e, fill, _, c, f = it
-    return warp.item(i, (x, y, cw, rh), (ow, oh), (a, b, c + 2 * (a * X0 + b * Y0), d, e, f + 2 * (d * X0 + e * Y0)), flags, fill)
-
-
 def test_many_tiles_per_workgroup_beyond_2_24(ctx, wide):
     """[small, big, small x 5, small] in one launch of warp_super_bytes: big shears a rectangle of the last rows of the 17.7 Mpx image - every
     staged pixel index at least 2**24 - under SUPER2 into more than 3 * 8 * cu tiles of 16 x 16 (the last column and row of tiles partial),
@@ -286,15 +279,11 @@ def test_many_tiles_per_workgroup_beyond_2_24(ctx, wide):
     import torch
     p = wide
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    across = 80
-    down = (3 * 8 * cus) // across + 1
-    ow, oh = 16 * across - 3, 16 * down - 5
+    ow, oh, across, down = walk_shape(cus)
     rect = (100, 3652, 400, 180)
-    a, b, d, e = round(ONE * 1.1 * rect[2] / ow), round(ONE * 0.12 * rect[2] / oh), round(-ONE * 0.1 * rect[3] / ow), round(ONE * 1.1 * rect[3] / oh)
-    big = warp.item(HUGE, rect, (ow, oh), (a, b, rect[2] * ONE - a * ow - b * oh, d, e, rect[3] * ONE - d * ow - e * oh), SUPER2 | REFLECT, FILL)     # a shear about the centre
-    kinds = (SUPER4 | REPLICATE, NEAREST, SUPER2, BICUBIC | WRAP, SUPER4 | REFLECT_101)
-    inner = [warp.item(HUGE, (HW_ - 19 - j, HH - 17 - j, 19, 17), (11 + j, 5), warp.rotation((19, 17), (11 + j, 5), 25.0 * j, 0.4), s, FILL) for j, s in enumerate(kinds)]
-    items = [warp.item(DOT, (0, 0, 1, 1), (5, 4), (ONE // 3, 0, 0, 0, ONE // 3, 0), SUPER4, FILL), big] + inner + [warp.item(SPRITE, (100, 40, 30, 30), (7, 7), (4 * ONE, 0, 0, 0, 4 * ONE, 0), SUPER4)]
+    items = super_walk_table(cus)                                  # (tests/test_gpu_newer_wide.py runs the same table through warp_super_tensor)
+    big = items[1]
+    assert big[:8] == (HUGE,) + rect + (ow, oh, SUPER2 | REFLECT)
     tiles = [warp.tiles(it[5], it[6]) for it in items]
     assert tiles[1] == across * down > 3 * 8 * cus and tiles[:1] + tiles[2:] == [1] * 7 and past_2_24(items) and ow * oh < warp.MAX_AREA
     small = warp.item(HUGE, rect, (40, 60), warp.rotation(rect[2:], (40, 60), 30.0, 0.1), SUPER4 | REFLECT, FILL)
@@ -304,7 +293,7 @@ def test_many_tiles_per_workgroup_beyond_2_24(ctx, wide):
     alone = run_warp(ctx, p, 4, [big], ALPHA_WEIGHTED)
     assert np.array_equal(got[1], alone[0]), ("the big entry differs from its own call", int(np.argmax(got[1] != alone[0])))
     whole = got[1].reshape(oh, ow, 4)
-    for X0, Y0 in ((0, 0), (ow - 45, 3), (5, oh - 27), (ow - 45, oh - 27)):
+    for X0, Y0 in super_windows(ow, oh):
         want = model(p, window_of(big, X0, Y0, 45, 27), 4, ALPHA_WEIGHTED)
         assert np.array_equal(whole[Y0:Y0 + 27, X0:X0 + 45], want), ("a window of the big entry", X0, Y0)
     for j in (0, 2, 3, 4, 5, 6, 7):

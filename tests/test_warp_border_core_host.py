@@ -3,6 +3,7 @@ item's sampling -> the first tap of each axis folded into the border's period, t
 store), compiled with g++ (tests/host/warp_border_host.cpp) and compared with the Python model qoi_amd/warp.py on the CPU, bit for bit:
 every border, sampling, output channel count and mode, odd output addresses, rectangles of 1 x 1, 1 x 7, 7 x 1, 5 x 3 and 17 x 9, maps that
 pad, turn, shear, lie hundreds of periods away and stand near +-2**56, so that the fold's ordinary path and its quotient estimate both run.
+The fold alone also takes every (k, n, border) of the device sweep of tests/test_gpu_warp_fold.py (tests/warp_fold_cases.py: host_triples).
 The staging outside the rectangle holds a sentinel and every load is checked to lie inside the rectangle; the loads are counted: exactly one
 per tap that has a weight - none for a tap with the weight 0.  A guard band around the output stays untouched and every output byte is
 written exactly once.  Items without a border flag walk warp_cubic_pixel / warp_pixel / warp_nearest through the same work item.  The same
@@ -79,6 +80,21 @@ def test_the_flags_and_the_fold_are_the_model_s(lib):
             ks = list(range(-40, 41)) + [top, -top, top - 1, 1 - top]
             ks += [s * (q * P + dk) for q in (1, 2, 3, 1000, top // P, top // P - 1) for dk in (-1, 0, 1, n - 1, n) for s in (1, -1)]
             ks = [k for k in ks if abs(k) <= top]
+            want = warp.fold(np.array(ks, dtype=np.int64), n, border).tolist()
+            for k, wk in zip(ks, want):
+                assert lib.warp_border_host_fold(k, n, border) == wk, (border, n, k)
+
+
+def test_the_fold_over_the_sweep_of_the_device_test(lib):
+    """every (k, n, border) that tests/test_gpu_warp_fold.py folds on the device - the builder's own list -, through the host build of the same
+    function: a failure there and not here is the device's code, one here is the arithmetic"""
+    import warp_fold_cases
+    triples = warp_fold_cases.host_triples()
+    assert len(triples) == 3722 and {n for _, n, _ in triples} == set(warp_fold_cases.SIZES) and {b for _, _, b in triples} == set(BORDERS)
+    assert min(k for k, _, _ in triples) < -(2 ** 39) + 64 and max(k for k, _, _ in triples) > 2 ** 39 - 64
+    for border in BORDERS:
+        for n in warp_fold_cases.SIZES:
+            ks = [k for k, m, b in triples if m == n and b == border]
             want = warp.fold(np.array(ks, dtype=np.int64), n, border).tolist()
             for k, wk in zip(ks, want):
                 assert lib.warp_border_host_fold(k, n, border) == wk, (border, n, k)
