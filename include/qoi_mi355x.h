@@ -771,6 +771,42 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * with and without a SUPER flag, of every sampling and border, mix freely in one call; a call with a SUPER item runs a kernel of its own that
  * serves all its items, a call without one launches exactly what it launches today.  The flags apply unchanged to
  * qoimi_decode_warped_tensors and qoimi_decode_warped_indexed.
+ * QOIMI_WARP_VOTE2 = 8192 (s = 2, L = 1) and QOIMI_WARP_VOTE4 = 16384 (s = 4, L = 2) (flags of the item; normative; qoi_amd/warp.py: warp states
+ * them in Python, qoi_amd/csrc/qoi_warp_vote_core.h holds them in C++) take a MAJORITY VOTE under a reducing map, for label maps
+ * (segmentation masks, instance ids, palette indices), where QOIMI_WARP_NEAREST looks at one source pixel per output pixel and thin classes
+ * come and go with the sampling phase.  The flags are a fourth sampling: an item carries at most one of the two; neither combines with
+ * QOIMI_WARP_NEAREST, QOIMI_WARP_BICUBIC, QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4; either combines with the fill (no border flag) or with any
+ * one of the four borders; 4096 is not a flag.  Everything about the item that is not named here stays as it is: R, cw, rh, U = 2X + 1,
+ * V = 2Y + 1, limits and their order, plan, staging, stats, tiles.  Output pixel (X, Y) is the majority vote of s x s nearest sub-samples
+ * on the grid QOIMI_WARP_SUPER2 / QOIMI_WARP_SUPER4 lays inside the pixel: for 0 <= i, j < s, Us, Vs, Px and Py are exactly those above,
+ * with the arithmetic shift and the bounds |Px|, |Py| < 2^57.  The value of a sub-sample is that of QOIMI_WARP_NEAREST at (Px, Py): column
+ * k = Px >> 17, row r = Py >> 17, the 64-bit index tested before it is narrowed; inside R it is R[r][k], all four bytes of the 4-channel
+ * decode (a 3-channel stream has alpha 255).  Outside R each index is clamped under QOIMI_WARP_REPLICATE; under QOIMI_WARP_REFLECT,
+ * QOIMI_WARP_REFLECT_101 or QOIMI_WARP_WRAP each index is folded on its own; without a border flag the value is the dword `fill` as given,
+ * all four bytes, and nothing is read.  Nothing outside R is ever read.
+ * The vote: a value votes as a whole dword.  The count of a value is the number of the s^2 sub-samples equal to it; the winners are the
+ * values with the largest count.  One winner is the output; of several winners the output is the centre value if it is a winner, otherwise
+ * the winner with the lowest key r << 24 | g << 16 | b << 8 | a - the vote and the tie rule of QOIMI_FILTER_MODE.  The centre value is what
+ * QOIMI_WARP_NEAREST gives this output pixel with the same border or fill, from Px = a * U + b * V + c, Py = d * U + e * V + f; it does not
+ * vote, and like any sub-sample it is the dword `fill`, with nothing read, where its position lies outside R and no border flag is set.
+ * Both modes give the same bytes; och 3 drops alpha after the vote.
+ * Consequences.  No invented value: every output pixel is one of its sub-sample values.  Identity and orientations: with the identity map,
+ * and with every qoimi_warp_orient item, all s^2 sub-samples fall into the pixel the centre falls into (the offsets are at most 49152 < 65536
+ * from a pixel centre, and a * Us is a multiple of 2^L), so the item is qoimi_decode_crops, respectively the QOIMI_WARP_NEAREST warp, byte
+ * for byte.  Whole-factor reduction: with a = e = s * 65536, b = c = d = f = 0 and an output of (cw / s) x (rh / s), where s divides both,
+ * sub-sample (i, j) is the centre of source pixel (sX + i, sY + j) and the centre value is pixel (sX + s/2, sY + s/2); the item then equals
+ * QOIMI_FILTER_MODE of qoimi_decode_tensors (U8, HWC) for that rectangle and size and QOIMI_TILE_MODE at factor s, byte for byte, in both
+ * modes and both channel counts.  A constant rectangle stays the constant under any map with any of the four borders.  There is NO
+ * adaptivity: the flag takes s^2 sub-samples and the centre whether or not the map reduces, and beyond 4 : 1 the result still skips pixels.
+ * The flag rule reads, in this order: a bit other than 1, 4, 16, 64, 128, 256, 1024, 2048, 8192 and 16384 is an unknown flag bit (2, 8, 32,
+ * 512 and 4096 are not flags); QOIMI_WARP_NEAREST and QOIMI_WARP_BICUBIC together; more than one of the four border flags; both SUPER flags
+ * together; a SUPER flag with QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC; both VOTE flags together, with a message of its own; a VOTE flag with
+ * QOIMI_WARP_NEAREST, QOIMI_WARP_BICUBIC, QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4, with a message of its own - the vote is a sampling of its
+ * own; reserved != 0.  qoimi_warp_size and qoimi_warp_tensor_size accept the flags and return 0 for the two new rejections.  Items with and
+ * without a VOTE flag, of every sampling and border, mix freely in one call; a call with a VOTE item runs a kernel of its own that serves
+ * all its items, a call without one launches exactly what it launches today.  The flags apply unchanged to qoimi_decode_warped_tensors and
+ * qoimi_decode_warped_indexed: QOIMI_TENSOR_I64 with QOIMI_TENSOR_HW is the N x H x W a loss function takes.
+ * Not here (of the vote): votes over more than 4 x 4 sub-samples, weighted or per-channel votes, adaptive sub-sample counts.
  * Not here: other cubic kernels (a = -3/4), Lanczos in the warp, adaptive antialiasing of reducing maps, supersampling beyond 4 x 4,
  * supersampled bicubic or nearest, projective maps, a border per axis, mixing reflect with a fill.
  * The rectangle is what is staged and what the border is taken at: rows_i of the plan is the maximum of y + height over the items of image i,
@@ -780,7 +816,8 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * out_height of 2^20 or more; out_width * out_height of 400 000 000 or more; |c| or |f| of 2^56 or more; a flag bit other than
  * QOIMI_WARP_REPLICATE, QOIMI_WARP_NEAREST, QOIMI_WARP_BICUBIC, QOIMI_WARP_REFLECT, QOIMI_WARP_REFLECT_101 and QOIMI_WARP_WRAP, then NEAREST and
  * BICUBIC together, then more than one of the four border flags (QOIMI_WARP_SUPER2 and QOIMI_WARP_SUPER4 are flags too; then both of them
- * together, then one of them with NEAREST or BICUBIC); reserved != 0.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
+ * together, then one of them with NEAREST or BICUBIC; QOIMI_WARP_VOTE2 and QOIMI_WARP_VOTE4 likewise; then both of them together, then one
+ * of them with NEAREST, BICUBIC or a SUPER flag); reserved != 0.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
  * 2^57: both positions fit 64 bits with room to spare.  N_c <= 255 * 2^34 < 2^42, the alpha-weighted sums are below 2^50.
  *   stream_offsets, sizes, descs, channels, out_offsets, staging_bytes  as for qoimi_decode_resized; the plan is that of qoimi_decode_crops
  *                  over the items' rectangles (normative; qoi_amd/warp.py: plan)
@@ -793,13 +830,14 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * decode calls of the context.  One call at a time per context, as everywhere. */
 enum { QOIMI_WARP_REPLICATE = 1, QOIMI_WARP_NEAREST = 4, QOIMI_WARP_BICUBIC = 16,      /* 2, 8 and 32 are not flags */
        QOIMI_WARP_REFLECT = 64, QOIMI_WARP_REFLECT_101 = 128, QOIMI_WARP_WRAP = 256,    /* at most one of these three and REPLICATE */
-       QOIMI_WARP_SUPER2 = 1024, QOIMI_WARP_SUPER4 = 2048 };                            /* at most one; bilinear only; 512 is not a flag */
+       QOIMI_WARP_SUPER2 = 1024, QOIMI_WARP_SUPER4 = 2048,                              /* at most one; bilinear only; 512 is not a flag */
+       QOIMI_WARP_VOTE2 = 8192, QOIMI_WARP_VOTE4 = 16384 };                             /* at most one; a sampling of its own; 4096 is not a flag */
 typedef struct {                 /* 72 bytes, offsets 0/4/8/12/16/20/24/28/32/36/40/44/48/52/56/64 */
     unsigned int image;          /* index into the call's images */
     unsigned int x, y;           /* top-left corner of the source rectangle */
     unsigned int width, height;  /* both >= 1; x + width <= image width, y + height <= image height */
     unsigned int out_width, out_height;  /* both >= 1 and below 2^20; their product below 400 000 000 */
-    unsigned int flags;          /* one border at most (REPLICATE, REFLECT, REFLECT_101, WRAP), QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC, or QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4; no other bit */
+    unsigned int flags;          /* one border at most (REPLICATE, REFLECT, REFLECT_101, WRAP), QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC, or QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4, or QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4; no other bit */
     int a, b, d, e;              /* the linear part of the inverse map, 16 fractional bits */
     unsigned int fill;           /* r | g << 8 | b << 16 | a << 24: the value of a sample outside the rectangle without a border flag */
     unsigned int reserved;       /* 0 */
@@ -939,7 +977,7 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * reported before anything is launched, the caller's buffers are untouched; qoimi_last_error names the cause.  The sub-batches count as decode
  * calls of the context.  One call at a time per context, as everywhere.
  * Not here: indexed forms, a majority (mode) filter per channel, with weights or over cells above 16 x 16 (QOIMI_FILTER_MODE votes on whole
- * pixels of cells up to that), the mode filter in the warp, 16-bit or signed label sources (a label is a byte of the image), a remapping table from byte to class index, a single
+ * pixels of cells up to that; the warp has QOIMI_WARP_VOTE2 / QOIMI_WARP_VOTE4), 16-bit or signed label sources (a label is a byte of the image), a remapping table from byte to class index, a single
  * 8-byte store per QOIMI_TENSOR_I64 element (it is two dword stores), a u8 entry point or a stats function of the bicubic, the Lanczos, the nearest or the mode filter's own, other cubic kernels (a = -3/4), other Lanczos windows, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
  * size of its rectangle, or divides it, is those), tensors as the source of an encode (qoimi_encode_tiles takes bytes). */
 enum { QOIMI_TENSOR_U8 = 0, QOIMI_TENSOR_F16 = 1, QOIMI_TENSOR_BF16 = 2, QOIMI_TENSOR_F32 = 3 };   /* element sizes 1 / 2 / 2 / 4 */

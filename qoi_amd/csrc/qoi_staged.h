@@ -11,6 +11,7 @@
 #include "qoi_warp_border_core.h"
 #include "qoi_warp_cubic_core.h"
 #include "qoi_warp_super_core.h"
+#include "qoi_warp_vote_core.h"
 
 // ------------------------------------------------------------------------------------
 // the few lines several entry points repeat
@@ -129,7 +130,7 @@ static bool resize_bytes(const qoimi_resize* r, unsigned och, size_t* bytes) {
 // The items of qoimi_decode_warped, in this order: the rectangle rules of resample_rect_wrong (a zero size, then a rectangle that leaves its
 // image), the output's sides, its pixels, the map's offsets (qoi_warp_core.h: what keeps both positions in 64 bits), the flags (a bit that is
 // none, then the two samplings together, then more than one of the four borders, then both SUPER flags, then a SUPER flag with a sampling
-// that is not the bilinear one), reserved.
+// that is not the bilinear one, then both VOTE flags, then a VOTE flag with another sampling or a SUPER flag), reserved.
 static const char* warp_item_wrong(const qoi_desc* d, const qoimi_warp* r) {
     if (r->width == 0u || r->height == 0u || r->out_width == 0u || r->out_height == 0u) return "zero width or height";
     if ((uint64_t)r->x + r->width > d->width || (uint64_t)r->y + r->height > d->height) return "the rectangle leaves its image";
@@ -138,7 +139,8 @@ static const char* warp_item_wrong(const qoi_desc* d, const qoimi_warp* r) {
     if (r->c <= -kWarpMaxOffset || r->c >= kWarpMaxOffset || r->f <= -kWarpMaxOffset || r->f >= kWarpMaxOffset) return "|c| or |f| is 2^56 or more";
     const unsigned supers = r->flags & (QOIMI_WARP_SUPER2 | QOIMI_WARP_SUPER4);
     const unsigned known = QOIMI_WARP_REPLICATE | QOIMI_WARP_NEAREST | QOIMI_WARP_BICUBIC | QOIMI_WARP_REFLECT | QOIMI_WARP_REFLECT_101 | QOIMI_WARP_WRAP |
-                           QOIMI_WARP_SUPER2 | QOIMI_WARP_SUPER4;
+                           QOIMI_WARP_SUPER2 | QOIMI_WARP_SUPER4 | QOIMI_WARP_VOTE2 | QOIMI_WARP_VOTE4;
+    const unsigned votes = r->flags & (QOIMI_WARP_VOTE2 | QOIMI_WARP_VOTE4);
     const unsigned borders = r->flags & (QOIMI_WARP_REPLICATE | QOIMI_WARP_REFLECT | QOIMI_WARP_REFLECT_101 | QOIMI_WARP_WRAP);
     if ((r->flags & ~known) != 0u) return "unknown flag bit";
     if ((r->flags & QOIMI_WARP_NEAREST) != 0u && (r->flags & QOIMI_WARP_BICUBIC) != 0u) return "QOIMI_WARP_NEAREST and QOIMI_WARP_BICUBIC together";
@@ -147,6 +149,9 @@ static const char* warp_item_wrong(const qoi_desc* d, const qoimi_warp* r) {
     if ((supers & (supers - 1u)) != 0u) return "QOIMI_WARP_SUPER2 and QOIMI_WARP_SUPER4 together";
     if (supers != 0u && (r->flags & (QOIMI_WARP_NEAREST | QOIMI_WARP_BICUBIC)) != 0u)
         return "supersampling is defined for the bilinear sampling only: QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4 with QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC";
+    if ((votes & (votes - 1u)) != 0u) return "QOIMI_WARP_VOTE2 and QOIMI_WARP_VOTE4 together";
+    if (votes != 0u && (r->flags & (QOIMI_WARP_NEAREST | QOIMI_WARP_BICUBIC | QOIMI_WARP_SUPER2 | QOIMI_WARP_SUPER4)) != 0u)
+        return "the vote is a sampling of its own: QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4 with QOIMI_WARP_NEAREST, QOIMI_WARP_BICUBIC, QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4";
     if (r->reserved != 0u) return "reserved is not 0";
     return nullptr;
 }
@@ -316,18 +321,19 @@ static int gather_resampled(const ResampleKind& kind, qoimi_ctx* c, const void* 
         }, launch, stream);
 }
 
-// ... and the warp call (the plan: qoi_amd/warp.py: plan).  launch(kind, entries, m, tiles, workgroups, stream): kind is kWarpKernelSuper
-// where an item of the CALL carries QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4 - then every sub-batch runs the kernel of qoi_warp_super.hip, which
-// serves every other item as well -, else kWarpKernelBorder
+// ... and the warp call (the plan: qoi_amd/warp.py: plan).  launch(kind, entries, m, tiles, workgroups, stream): kind is kWarpKernelVote
+// where an item of the CALL carries QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4 - then every sub-batch runs the kernel of qoi_warp_vote.hip, which
+// serves every other item as well -, else kWarpKernelSuper
+// where one carries QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4 - the kernel of qoi_warp_super.hip, likewise -, else kWarpKernelBorder
 // where one carries QOIMI_WARP_REFLECT, QOIMI_WARP_REFLECT_101 or QOIMI_WARP_WRAP - the kernel of
 // qoi_warp_border.hip, likewise -, else kWarpKernelCubic where one carries QOIMI_WARP_BICUBIC - the kernel of
 // qoi_warp_cubic.hip, likewise -, else kWarpKernelPlain: a call without those flags launches what it always launched.  kernels[kind] is the
 // name in the message of a failed launch.
-enum WarpKernel { kWarpKernelPlain = 0, kWarpKernelCubic = 1, kWarpKernelBorder = 2, kWarpKernelSuper = 3 };
+enum WarpKernel { kWarpKernelPlain = 0, kWarpKernelCubic = 1, kWarpKernelBorder = 2, kWarpKernelSuper = 3, kWarpKernelVote = 4 };
 template <class Before, class Bytes, class After, class Launch>
 static int gather_warped(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs, int n_images, int channels,
                          const qoimi_warp* items, int n_items, int mode, void* d_out, const size_t* out_offsets, size_t staging_bytes, void* stream,
-                         Before before, Bytes bytes_of, After after, long long (qoimi_ctx::*stats)[4], const char* const (&kernels)[4], Launch launch) {
+                         Before before, Bytes bytes_of, After after, long long (qoimi_ctx::*stats)[4], const char* const (&kernels)[5], Launch launch) {
     // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
     if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
     if (const int rc = check_out_channels(channels)) return rc;
@@ -346,8 +352,9 @@ static int gather_warped(qoimi_ctx* c, const void* d_streams, const size_t* stre
     const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
     unsigned any = 0u;
     for (size_t j = 0; j < n; ++j) any |= items[j].flags;
-    const WarpKernel kind = (any & kWarpSupers) != 0u ? kWarpKernelSuper
-                          : ((any & kWarpBorders) != 0u ? kWarpKernelBorder : ((any & QOIMI_WARP_BICUBIC) != 0u ? kWarpKernelCubic : kWarpKernelPlain));
+    const WarpKernel kind = (any & kWarpVotes) != 0u ? kWarpKernelVote
+                          : ((any & kWarpSupers) != 0u ? kWarpKernelSuper
+                          : ((any & kWarpBorders) != 0u ? kWarpKernelBorder : ((any & QOIMI_WARP_BICUBIC) != 0u ? kWarpKernelCubic : kWarpKernelPlain)));
     return run_staged<WarpEntry>(c, c->*stats, (long long)plan.refs.size(), kernels[kind], d_streams, stream_offsets, sizes, descs, plan, ok.rows, order,
         [&](WarpEntry& t, size_t e) {
             const size_t j = order.by_ref[e];

@@ -78,11 +78,30 @@ integer, every shift and division floors.
   evaluation of the same s**2 positions (``super_reference``: taken from the integer Px, Py, bilinear, same border rule, averaged, rounded
   once), and only where the float value lies at a rounding boundary, because ``N_c`` is exact.  There is NO adaptivity: the flag takes s**2
   sub-samples whether or not the map reduces, and beyond 4 : 1 the result still aliases.
+* With ``VOTE2`` = 8192 (s = 2, L = 1) or ``VOTE4`` = 16384 (s = 4, L = 2) (flags; a fourth sampling: at most one of the two, never with
+  ``NEAREST``, ``BICUBIC``, ``SUPER2`` or ``SUPER4``, with the fill or any one of the four borders; 4096 is not a flag) output pixel (X, Y) is
+  the MAJORITY VOTE of s x s nearest sub-samples - for label maps under a map that reduces, where ``NEAREST`` looks at one source pixel per
+  output pixel.  For ``0 <= i, j < s`` the positions ``Us``, ``Vs``, ``Px``, ``Py`` are exactly those of ``SUPER2`` / ``SUPER4``, with their
+  bounds.  The value of a sub-sample is that of ``NEAREST`` at (Px, Py): column ``k = Px >> 17``, row ``r = Py >> 17``; inside R it is
+  ``R[r][k]``, all four bytes of the 4-channel decode (a 3-channel stream has alpha 255); outside R each index is clamped under
+  ``REPLICATE``, folded on its own under ``REFLECT`` / ``REFLECT_101`` / ``WRAP``, and without a border flag the value is the dword ``fill``
+  as given, all four bytes.  A value votes as a whole dword; the count of a value is the number of the s**2 sub-samples equal to it; the
+  winners are the values with the largest count.  One winner is the output; of several the centre value if it is a winner, otherwise the
+  winner with the lowest key ``r << 24 | g << 16 | b << 8 | a`` - the vote and the tie rule of ``mode.mode``.  The centre value is what
+  ``NEAREST`` gives this output pixel with the same border or fill, from ``Px = a*U + b*V + c``, ``Py = d*U + e*V + f``; it does not vote.
+  Both modes give the same bytes; och 3 drops alpha after the vote.  Consequences: every output pixel is one of its sub-sample values;
+  with the identity and every ``orient`` item all s**2 sub-samples fall into the pixel the centre falls into (at most 49152 < 65536 from a
+  pixel centre), so the item is ``crops.crop``, respectively the ``NEAREST`` warp; with ``a = e = s * ONE``, ``b = c = d = f = 0`` and an
+  output of ``(cw / s) x (rh / s)``, s dividing both, sub-sample (i, j) is source pixel (sX + i, sY + j) and the centre value pixel
+  (sX + s/2, sY + s/2): the item is ``mode.mode`` for that rectangle and size and the MODE tile of ``tiles.py`` at factor s, byte for
+  byte; a constant rectangle stays the constant under any map with any of the four borders; there is no adaptivity, and beyond 4 : 1 the
+  result still skips pixels.  ``vote_reference`` is the same statement as a naive loop.
 
 Limits, in the order the C side checks them: a zero size; a rectangle that leaves its image; ``ow, oh < 2**20``; ``ow * oh < 400 000 000``;
-``|c|, |f| < 2**56``; no flag bit but ``REPLICATE``, ``NEAREST``, ``BICUBIC``, ``REFLECT``, ``REFLECT_101``, ``WRAP``, ``SUPER2`` and ``SUPER4``
-(2, 8, 32 and 512 are not flags), then not ``NEAREST`` and ``BICUBIC`` together, then not more than one of the four borders, then not both
-``SUPER`` flags, then no ``SUPER`` flag with ``NEAREST`` or ``BICUBIC``; ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
+``|c|, |f| < 2**56``; no flag bit but ``REPLICATE``, ``NEAREST``, ``BICUBIC``, ``REFLECT``, ``REFLECT_101``, ``WRAP``, ``SUPER2``, ``SUPER4``,
+``VOTE2`` and ``VOTE4`` (2, 8, 32, 512 and 4096 are not flags), then not ``NEAREST`` and ``BICUBIC`` together, then not more than one of the
+four borders, then not both ``SUPER`` flags, then no ``SUPER`` flag with ``NEAREST`` or ``BICUBIC``, then not both ``VOTE`` flags, then no
+``VOTE`` flag with ``NEAREST``, ``BICUBIC`` or a ``SUPER`` flag; ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
 ``|Px|, |Py| < 2**57``; ``N_c <= 255 * 2**34 < 2**42``; the alpha-weighted sums are below ``2**50``: everything fits int64.
 
 With the identity the result is ``crops.crop``; with ``a = ONE // s`` and REPLICATE it is ``bilinear.bilinear`` enlarging by the power of two s;
@@ -109,6 +128,9 @@ BORDERS = REPLICATE | REFLECT | REFLECT_101 | WRAP   # at most one of them
 SUPER2 = 1024                   # 2 x 2 bilinear sub-samples per output pixel, one rounding (512 is not a flag)
 SUPER4 = 2048                   # 4 x 4
 SUPERS = SUPER2 | SUPER4        # at most one of them, with the bilinear sampling only
+VOTE2 = 8192                    # the majority vote of 2 x 2 nearest sub-samples per output pixel: for label maps (4096 is not a flag)
+VOTE4 = 16384                   # 4 x 4
+VOTES = VOTE2 | VOTE4           # at most one of them, a sampling of its own: with no other sampling and no SUPER flag
 CUBIC_ONE = bicubic.ONE         # the weights of an axis add up to it
 CUBIC_L1_MAX = 5 << 13          # sum |q| of an axis stays at or below it
 PLAIN = resize.PLAIN
@@ -161,7 +183,7 @@ def _wrong(w: int, h: int, rect, out_size, matrix, flags: int, reserved: int = 0
         return "|c| or |f| from 2**56"
     if any(not -2 ** 31 <= v < 2 ** 31 for v in (a, b, d, e)):
         return "a, b, d, e are 32-bit"
-    if flags & ~(BORDERS | NEAREST | BICUBIC | SUPERS):
+    if flags & ~(BORDERS | NEAREST | BICUBIC | SUPERS | VOTES):
         return "unknown flag bit"
     if flags & NEAREST and flags & BICUBIC:
         return "NEAREST and BICUBIC together"
@@ -171,6 +193,10 @@ def _wrong(w: int, h: int, rect, out_size, matrix, flags: int, reserved: int = 0
         return "SUPER2 and SUPER4 together"
     if flags & SUPERS and flags & (NEAREST | BICUBIC):
         return "supersampling is defined for the bilinear sampling only: a SUPER flag with NEAREST or BICUBIC"
+    if flags & VOTES == VOTES:
+        return "VOTE2 and VOTE4 together"
+    if flags & VOTES and flags & (NEAREST | BICUBIC | SUPERS):
+        return "the vote is a sampling of its own: a VOTE flag with NEAREST, BICUBIC, SUPER2 or SUPER4"
     if reserved:
         return "reserved is not 0"
     return ""
@@ -282,9 +308,11 @@ def cubic_bound() -> int:
 
 
 def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, int], matrix=IDENTITY, flags: int = 0, fill: int = 0,
-         mode: int = PLAIN) -> np.ndarray:
-    """D uint8[h, w, och] (och 3 or 4), rect (x, y, width, height) inside it, out_size (out_width, out_height), matrix (a, b, c, d, e, f)
-    -> uint8[out_height, out_width, och]."""
+         mode: int = PLAIN, och: int = 0) -> np.ndarray:
+    """D uint8[h, w, 3 or 4], rect (x, y, width, height) inside it, out_size (out_width, out_height), matrix (a, b, c, d, e, f)
+    -> uint8[out_height, out_width, och]; och 0 is D's own channel count.  D with 3 channels is a decode whose alpha is 255; a 4-channel
+    stream decoded with och 3 under a ``VOTE`` flag is stated by its 4-channel decode as D and och = 3: its alpha votes, the output lacks it
+    (``mode.mode`` likewise; every other sampling gives the bytes of the 3-channel decode either way)."""
     D = np.asarray(D)
     if D.ndim != 3 or D.shape[2] not in (3, 4) or D.dtype != np.uint8:
         raise ValueError("warp: D must be uint8[h, w, 3 or 4]")
@@ -298,18 +326,38 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
     x, y, cw, rh = (int(v) for v in rect)
     ow, oh = (int(v) for v in out_size)
     a, b, c, d, e, f = (int(v) for v in matrix)
-    och = D.shape[2]
+    if och not in (0, 3, 4):
+        raise ValueError("warp: och must be 3 or 4")
+    och = och or D.shape[2]
     weighted = mode == ALPHA_WEIGHTED and och == 4
     R = D[y:y + rh, x:x + cw].astype(np.int64)
-    if och == 3:
+    if D.shape[2] == 3:
         R = np.concatenate([R, np.full((rh, cw, 1), 255, dtype=np.int64)], axis=2)
     F = np.array([(fill >> (8 * k)) & 255 for k in range(4)], dtype=np.int64)
     U = (2 * np.arange(ow, dtype=np.int64) + 1)[None, :]
     V = (2 * np.arange(oh, dtype=np.int64) + 1)[:, None]
+    def select(Px, Py):
+        """the one sample of NEAREST at the positions: R[Py >> 17][Px >> 17], brought inside by the border, or the fill"""
+        k, ink = _border(Px >> 17, cw, flags)
+        r, inr = _border(Py >> 17, rh, flags)
+        return np.where((ink & inr)[..., None], R[r, k], F[None, None, :])
+
     if flags & NEAREST:
-        k, ink = _border((a * U + b * V + c) >> 17, cw, flags)
-        r, inr = _border((d * U + e * V + f) >> 17, rh, flags)
-        out = np.where((ink & inr)[..., None], R[r, k], F[None, None, :])
+        return np.ascontiguousarray(select(a * U + b * V + c, d * U + e * V + f)[..., :och].astype(np.uint8))
+    if flags & VOTES:
+        L = vote_log2(flags)
+        s = 1 << L
+        keys = []                                                        # of every sub-sample: r << 24 | g << 16 | b << 8 | a
+        for j in range(s):
+            for i in range(s):
+                Us, Vs = s * U + (2 * i + 1 - s), s * V + (2 * j + 1 - s)
+                keys.append(_key(select(((a * Us + b * Vs) >> L) + c, ((d * Us + e * Vs) >> L) + f)))
+        keys = np.stack(keys, axis=-1)                                   # int64[oh, ow, s * s]
+        centre = _key(select(a * U + b * V + c, d * U + e * V + f))     # decides a tie where it is a winner; it does not vote
+        count = (keys[..., :, None] == keys[..., None, :]).sum(axis=-1)
+        word = (count << 33) | ((keys == centre[..., None]).astype(np.int64) << 32) | (0xFFFFFFFF - keys)   # the largest: count, centre, lowest key
+        win = np.take_along_axis(keys, np.argmax(word, axis=-1)[..., None], axis=-1)[..., 0]
+        out = np.stack([(win >> sh) & 255 for sh in (24, 16, 8, 0)], axis=-1)
         return np.ascontiguousarray(out[..., :och].astype(np.uint8))
     if flags & BICUBIC:
         kx, qx, inx = _cubic_axis(a * U + b * V + c, cw, flags)
@@ -347,6 +395,66 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
         A = N[..., 3:4]
         out[..., :3] = np.where(A > 0, (M + A // 2) // np.maximum(A, 1), out[..., :3])
     return np.ascontiguousarray(out[..., :och].astype(np.uint8))
+
+
+def _key(px: np.ndarray) -> np.ndarray:
+    """int64[...]: r << 24 | g << 16 | b << 8 | a of the pixels int64[..., 4] (``mode.key``)"""
+    return px[..., 0] << 24 | px[..., 1] << 16 | px[..., 2] << 8 | px[..., 3]
+
+
+def vote_log2(flags: int) -> int:
+    """L of the item's flags: 1 for ``VOTE2``, 2 for ``VOTE4``, 0 without; s = 1 << L nearest sub-samples along each axis of an output pixel."""
+    return 2 if flags & VOTE4 else (1 if flags & VOTE2 else 0)
+
+
+def vote_reference(D: np.ndarray, rect, out_size, matrix=IDENTITY, flags: int = 0, fill: int = 0, census=None, och: int = 0) -> np.ndarray:
+    """uint8[out_height, out_width, och]: a ``VOTE2`` / ``VOTE4`` item by the words of the definition, pixel by pixel in Python integers
+    with a ``collections.Counter`` - deliberately naive, sharing with ``warp`` only ``fold`` for the three folding borders.  census, a dict,
+    counts the output pixels by how they were decided: 'unique', 'centre' (a tie the centre value wins), 'lowest' (a tie in which the centre
+    value is no winner).  och as for ``warp``."""
+    from collections import Counter
+    D = np.asarray(D)
+    x, y, cw, rh = (int(v) for v in rect)
+    ow, oh = (int(v) for v in out_size)
+    a, b, c, d, e, f = (int(v) for v in matrix)
+    sch, och = D.shape[2], och or D.shape[2]
+    L = vote_log2(flags)
+    s = 1 << L
+    border = flags & BORDERS
+    F = tuple((fill >> (8 * k)) & 255 for k in range(4))
+
+    def index(k, n):
+        if border == 0:
+            return k if 0 <= k < n else None
+        if border == REPLICATE:
+            return min(max(k, 0), n - 1)
+        return int(fold(k, n, border))
+
+    def value(Px, Py):
+        k, r = index(Px >> 17, cw), index(Py >> 17, rh)
+        if k is None or r is None:
+            return F                                                     # the fill as given, all four bytes; nothing is read
+        px = tuple(int(v) for v in D[y + r, x + k])
+        return px + ((255,) if sch == 3 else ())
+
+    out = np.zeros((oh, ow, och), dtype=np.uint8)
+    for Y in range(oh):
+        for X in range(ow):
+            Uo, Vo = 2 * X + 1, 2 * Y + 1
+            votes = Counter()
+            for j in range(s):
+                for i in range(s):
+                    Us, Vs = s * Uo + 2 * i + 1 - s, s * Vo + 2 * j + 1 - s
+                    votes[value(((a * Us + b * Vs) >> L) + c, ((d * Us + e * Vs) >> L) + f)] += 1
+            top = max(votes.values())
+            winners = sorted(v for v, n in votes.items() if n == top)   # (r, g, b, a) ascending: by key
+            centre = value(a * Uo + b * Vo + c, d * Uo + e * Vo + f)
+            win = centre if centre in winners else winners[0]
+            if census is not None:
+                kind = "unique" if len(winners) == 1 else ("centre" if centre in winners else "lowest")
+                census[kind] = census.get(kind, 0) + 1
+            out[Y, X] = win[:och]
+    return out
 
 
 def super_log2(flags: int) -> int:

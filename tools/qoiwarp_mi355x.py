@@ -2,7 +2,7 @@
 """qoiwarp for the MI355X path: a set of .qoi files as PNGs, re-oriented or turned about their centre.
 
     python tools/qoiwarp_mi355x.py FILE_OR_DIR... -o DIR (--orient N | --rotate DEG [--scale S]) [--size WxH] [--border fill|replicate|reflect|reflect101|wrap]
-                                   [--sample bilinear|nearest|bicubic] [--supersample 1|2|4]
+                                   [--sample bilinear|nearest|bicubic|vote2|vote4] [--supersample 1|2|4]
                                    [--fill RRGGBBAA] [--mode plain|weighted] [--staging-mb M]
 
 Loads the .qoi files (directories are walked), uploads them as ONE pack and makes ONE qoimi_decode_warped call: every stream is decoded on the
@@ -13,7 +13,7 @@ every output pixel one source pixel: qoimi_warp_orient).  --rotate DEG turns the
 (rotation_matrix).  Samples outside the image take --fill (default 00000000) or, with --border replicate, the nearest pixel; --border reflect
 mirrors the image about its edges ("dcba|abcd|dcba", warp.REFLECT), --border reflect101 about its edge pixels ("dcb|abcd|cba", warp.REFLECT_101: the
 border cv2.warpAffine pipelines default to) and --border wrap repeats it (warp.WRAP) - --fill is then not used.  --sample nearest takes
-one source pixel per output pixel instead of the 2 x 2 bilinear taps (warp.NEAREST): for label maps, whose values must not be averaged; --sample bicubic takes 4 x 4 under Keys' cubic with a = -1/2 (warp.BICUBIC): sharper photographs under a turn.  There is no
+one source pixel per output pixel instead of the 2 x 2 bilinear taps (warp.NEAREST): for label maps, whose values must not be averaged; --sample bicubic takes 4 x 4 under Keys' cubic with a = -1/2 (warp.BICUBIC): sharper photographs under a turn; --sample vote2 or vote4 takes the majority vote of 2 x 2 or 4 x 4 nearest sub-samples per output pixel (warp.VOTE2, warp.VOTE4): label maps under a scale down to about 1/4, where nearest skips pixels.  There is no
 adaptive antialiasing: --supersample 2 or 4 (warp.SUPER2, warp.SUPER4; default 1; with --sample bilinear only) averages 2 x 2 or 4 x 4 bilinear
 sub-samples per output pixel with one rounding, which serves scales down to about 1/4; a scale well below that wants
 tools/qoiresize_mi355x.py first.  Outputs hold 4 channels if any file does, else 3, and are
@@ -42,6 +42,7 @@ ONE = 1 << 16
 BORDERS = {"fill": 0, "replicate": 1, "reflect": 64, "reflect101": 128, "wrap": 256}          # --border -> warp.REPLICATE, REFLECT, REFLECT_101, WRAP
 SAMPLES = {"bilinear": 0, "nearest": 4, "bicubic": 16}                                        # --sample -> warp.NEAREST, BICUBIC
 SUPERSAMPLES = {1: 0, 2: 1024, 4: 2048}                                                       # --supersample -> warp.SUPER2, SUPER4
+VOTE_SAMPLES = {"vote2": 8192, "vote4": 16384}                                                # --sample, beside SAMPLES -> warp.VOTE2, VOTE4
 
 
 def parse_fill(text: str):
@@ -77,7 +78,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("--scale", type=float, default=1.0, metavar="S")
     ap.add_argument("--size", default=None, metavar="WxH")
     ap.add_argument("--border", choices=tuple(BORDERS), default="fill")
-    ap.add_argument("--sample", choices=tuple(SAMPLES), default="bilinear")
+    ap.add_argument("--sample", choices=tuple(SAMPLES) + tuple(VOTE_SAMPLES), default="bilinear")
     ap.add_argument("--supersample", type=int, choices=tuple(SUPERSAMPLES), default=1)
     ap.add_argument("--fill", default="00000000", metavar="RRGGBBAA")
     ap.add_argument("--mode", choices=("plain", "weighted"), default="plain")
@@ -119,7 +120,7 @@ def main(argv, out=print) -> int:
     if not files:
         out("no .qoi files")
         return 2
-    flags = BORDERS[a.border] | SAMPLES[a.sample] | SUPERSAMPLES[a.supersample]
+    flags = BORDERS[a.border] | {**SAMPLES, **VOTE_SAMPLES}[a.sample] | SUPERSAMPLES[a.supersample]
     blobs = [open(f, "rb").read() for f in files]
     heads = [parse_header(b) for b in blobs]
     good, items = [], []
