@@ -807,8 +807,40 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * all its items, a call without one launches exactly what it launches today.  The flags apply unchanged to qoimi_decode_warped_tensors and
  * qoimi_decode_warped_indexed: QOIMI_TENSOR_I64 with QOIMI_TENSOR_HW is the N x H x W a loss function takes.
  * Not here (of the vote): votes over more than 4 x 4 sub-samples, weighted or per-channel votes, adaptive sub-sample counts.
+ * QOIMI_WARP_PROJECTIVE = 131072 (1 << 17) (a flag of the item; normative; qoi_amd/warp.py: positions states it in Python,
+ * qoi_amd/csrc/qoi_warp_proj_core.h holds it in C++) makes the map a PERSPECTIVE map - a homography of the output rectangle: RandomPerspective
+ * and the homography augmentations of a training loader, a tilted viewport, a document rectified from a photograph.  32768 and 65536 are not
+ * flags.  The flag combines with the fill (no border flag) or any one of the four borders and with the bilinear sampling, QOIMI_WARP_NEAREST
+ * or QOIMI_WARP_BICUBIC; it never combines with QOIMI_WARP_SUPER2, QOIMI_WARP_SUPER4, QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4.  With the flag set
+ * `reserved` is not 0: it holds the two perspective coefficients g = (int16)(reserved & 0xFFFF) and h = (int16)(reserved >> 16), both two's
+ * complement; without the flag reserved != 0 is rejected exactly as before.  All arithmetic is integer, every division and shift floors;
+ * ow = out_width, oh = out_height:
+ *   L = the smallest integer >= 0 with 2^L >= max(ow, oh);  F = 14 + L, so F is 14..34
+ *   U = 2X + 1, V = 2Y + 1 as above;  Uc = U - ow, Vc = V - oh: the doubled offsets from the output's centre, |Uc| < ow, |Vc| < oh
+ *   Nx = a * U + b * V + c,  Ny = d * U + e * V + f: the Px and Py of an item without the flag
+ *   W  = 2^F + g * Uc + h * Vc: the denominator is 1.0 at the centre of the output
+ *   Px = floor(Nx * 2^F / W),  Py = floor(Ny * 2^F / W)
+ * From Px and Py on nothing changes: k0, the fractions and the weights; the NEAREST column Px >> 17; the cubic weights; the clamp or fold of
+ * each tap on its own; the fill; both alpha modes and the one rounding; the byte and tensor stores.  The scale is sized by the item: W > 0
+ * everywhere requires |gamma| * ow < 1 for the real coefficient gamma, so the useful range of g is 1 / ow; a fixed scale would waste bits on
+ * small outputs and lose sub-pixel accuracy on large ones, and with F = 14 + L the 16 bits cover exactly that range at every size.
+ * Limits of an item with the flag, checked behind all the limits below, in this order, each with a message of its own: the flag together
+ * with a SUPER or VOTE flag; |c| or |f| of 2^53 or more; 2^F - |g| * (ow - 1) - |h| * (oh - 1) < 2^(F - 3) - W is linear, so this is its
+ * exact minimum over the pixel grid, and the limit keeps the denominator at or above 1/8 inside the output.  Then |Nx| < 2^52 + 2^52 + 2^53 =
+ * 2^54, 2^(F-3) <= W < 5 * 2^F < 2^37 and |Px| <= 8 * |Nx| < 2^57, the bound of an item without the flag.  qoimi_warp_size and
+ * qoimi_warp_tensor_size accept the flag and return 0 for the three new rejections.
+ * Consequences.  With g = h = 0, W = 2^F and Px = Nx: the item gives the bytes of the same item without the flag, in every sampling, border,
+ * mode and format.  The map applied is the QUANTISED homography, exactly - still a homography, so lines stay lines; qoi_amd/warp.py:
+ * homography and perspective quantise a 3 x 3 matrix or four corner points and REPORT the displacement that costs at the output's corners
+ * (it is not promised).  Against a float64 evaluation of that same quantised map a bilinear value differs by at most 1, and only at a
+ * rounding boundary: the position is floored by less than 2^-17 of a pixel.  A constant rectangle stays the constant under
+ * QOIMI_WARP_REPLICATE.  Items with and without the flag, of every sampling and border, SUPER and VOTE items included, mix freely in one
+ * call; a call with a projective item runs a kernel of its own that serves all its items, a call without one launches exactly what it
+ * launches today.  The flag applies unchanged to qoimi_decode_warped_tensors and qoimi_decode_warped_indexed.
+ * Not here (of the projective map): projective SUPER and VOTE items, a free denominator at the origin (the map is normalised at the centre
+ * of the output), coefficients wider than 16 bits, W <= 0 - a horizon inside the output.
  * Not here: other cubic kernels (a = -3/4), Lanczos in the warp, adaptive antialiasing of reducing maps, supersampling beyond 4 x 4,
- * supersampled bicubic or nearest, projective maps, a border per axis, mixing reflect with a fill.
+ * supersampled bicubic or nearest, projective maps with a supersampling or a vote, a border per axis, mixing reflect with a fill.
  * The rectangle is what is staged and what the border is taken at: rows_i of the plan is the maximum of y + height over the items of image i,
  * so the caller keeps the rectangle tight around what the map reaches - a rectangle of the whole image under a map that reaches one corner
  * decodes the whole image.
@@ -817,7 +849,7 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
  * QOIMI_WARP_REPLICATE, QOIMI_WARP_NEAREST, QOIMI_WARP_BICUBIC, QOIMI_WARP_REFLECT, QOIMI_WARP_REFLECT_101 and QOIMI_WARP_WRAP, then NEAREST and
  * BICUBIC together, then more than one of the four border flags (QOIMI_WARP_SUPER2 and QOIMI_WARP_SUPER4 are flags too; then both of them
  * together, then one of them with NEAREST or BICUBIC; QOIMI_WARP_VOTE2 and QOIMI_WARP_VOTE4 likewise; then both of them together, then one
- * of them with NEAREST, BICUBIC or a SUPER flag); reserved != 0.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
+ * of them with NEAREST, BICUBIC or a SUPER flag; QOIMI_WARP_PROJECTIVE is a flag too); reserved != 0 without QOIMI_WARP_PROJECTIVE, with it the three limits named there.  Then U, V < 2^21, |a * U| and |b * V| are at most 2^31 * 2^21 = 2^52, and |Px|, |Py| < 2^56 + 2 * 2^52 <
  * 2^57: both positions fit 64 bits with room to spare.  N_c <= 255 * 2^34 < 2^42, the alpha-weighted sums are below 2^50.
  *   stream_offsets, sizes, descs, channels, out_offsets, staging_bytes  as for qoimi_decode_resized; the plan is that of qoimi_decode_crops
  *                  over the items' rectangles (normative; qoi_amd/warp.py: plan)
@@ -831,17 +863,18 @@ void qoimi_bilinear_stats(qoimi_ctx *ctx, long long out[4]);
 enum { QOIMI_WARP_REPLICATE = 1, QOIMI_WARP_NEAREST = 4, QOIMI_WARP_BICUBIC = 16,      /* 2, 8 and 32 are not flags */
        QOIMI_WARP_REFLECT = 64, QOIMI_WARP_REFLECT_101 = 128, QOIMI_WARP_WRAP = 256,    /* at most one of these three and REPLICATE */
        QOIMI_WARP_SUPER2 = 1024, QOIMI_WARP_SUPER4 = 2048,                              /* at most one; bilinear only; 512 is not a flag */
-       QOIMI_WARP_VOTE2 = 8192, QOIMI_WARP_VOTE4 = 16384 };                             /* at most one; a sampling of its own; 4096 is not a flag */
+       QOIMI_WARP_VOTE2 = 8192, QOIMI_WARP_VOTE4 = 16384,                               /* at most one; a sampling of its own; 4096 is not a flag */
+       QOIMI_WARP_PROJECTIVE = 131072 };                                                /* reserved holds g and h; never with SUPER or VOTE; 32768 and 65536 are not flags */
 typedef struct {                 /* 72 bytes, offsets 0/4/8/12/16/20/24/28/32/36/40/44/48/52/56/64 */
     unsigned int image;          /* index into the call's images */
     unsigned int x, y;           /* top-left corner of the source rectangle */
     unsigned int width, height;  /* both >= 1; x + width <= image width, y + height <= image height */
     unsigned int out_width, out_height;  /* both >= 1 and below 2^20; their product below 400 000 000 */
-    unsigned int flags;          /* one border at most (REPLICATE, REFLECT, REFLECT_101, WRAP), QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC, or QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4, or QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4; no other bit */
+    unsigned int flags;          /* one border at most (REPLICATE, REFLECT, REFLECT_101, WRAP), QOIMI_WARP_NEAREST or QOIMI_WARP_BICUBIC, or QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4, or QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4; QOIMI_WARP_PROJECTIVE with none of the last four; no other bit */
     int a, b, d, e;              /* the linear part of the inverse map, 16 fractional bits */
     unsigned int fill;           /* r | g << 8 | b << 16 | a << 24: the value of a sample outside the rectangle without a border flag */
-    unsigned int reserved;       /* 0 */
-    long long c, f;              /* the offsets of the inverse map, doubled coordinates with 16 fractional bits; |c|, |f| < 2^56 */
+    unsigned int reserved;       /* 0; with QOIMI_WARP_PROJECTIVE g = (int16)(reserved & 0xFFFF) and h = (int16)(reserved >> 16) */
+    long long c, f;              /* the offsets of the inverse map, doubled coordinates with 16 fractional bits; |c|, |f| < 2^56, with QOIMI_WARP_PROJECTIVE < 2^53 */
 } qoimi_warp;
 int qoimi_decode_warped(qoimi_ctx *ctx, const void *d_streams, const size_t *stream_offsets /* host */, const int *sizes /* host */,
                         const qoi_desc *descs /* host */, int n_images, int channels /* 0, 3, 4 */,

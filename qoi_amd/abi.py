@@ -57,7 +57,8 @@ assert ctypes.sizeof(QoimiResize) == 32 and [getattr(QoimiResize, f).offset for 
 
 class QoimiWarp(ctypes.Structure):
     """``qoimi_warp``: 72 bytes - a rectangle of image ``image``, the size of the output, the inverse affine map from the output into the
-    rectangle (``warp.py`` states it), the border (``warp.REPLICATE`` or ``fill``)."""
+    rectangle (``warp.py`` states it), the border (``warp.REPLICATE`` or ``fill``); ``reserved`` is 0, or with ``warp.PROJECTIVE`` the two
+    perspective coefficients as 16-bit halves (``warp.proj_reserved``)."""
     _fields_ = [("image", ctypes.c_uint), ("x", ctypes.c_uint), ("y", ctypes.c_uint), ("width", ctypes.c_uint), ("height", ctypes.c_uint),
                 ("out_width", ctypes.c_uint), ("out_height", ctypes.c_uint), ("flags", ctypes.c_uint), ("a", ctypes.c_int), ("b", ctypes.c_int),
                 ("d", ctypes.c_int), ("e", ctypes.c_int), ("fill", ctypes.c_uint), ("reserved", ctypes.c_uint), ("c", ctypes.c_longlong),

@@ -664,7 +664,7 @@ class Context:
                       items, mode: int, d_out: int, out_offsets: Sequence[int], staging_bytes: int = 0, stream: int = 0) -> None:
         """Rectangles of a pack's images sampled through an affine map with bilinear weights (``qoimi_decode_warped``, synchronous, through
         bounded staging): output j is written tightly packed at d_out + out_offsets[j].  items: ``QoimiWarp`` structures or the tuples of
-        ``warp.fields`` (``warp.item`` makes one; the flag ``warp.NEAREST`` takes one sample instead of 2 x 2 taps - for label maps -, ``warp.BICUBIC`` = 16 takes 4 x 4 under Keys' cubic; ``warp.REFLECT`` = 64, ``warp.REFLECT_101`` = 128 and ``warp.WRAP`` = 256 fold every tap into the rectangle instead of ``warp.REPLICATE`` or the fill; ``warp.SUPER2`` = 1024 and ``warp.SUPER4`` = 2048 average 2 x 2 or 4 x 4 bilinear sub-samples per output pixel with one rounding, for maps that reduce by up to 4; ``warp.VOTE2`` = 8192 and ``warp.VOTE4`` = 16384 take the majority vote of 2 x 2 or 4 x 4 nearest sub-samples per output pixel - for label maps under such maps -, a sampling of their own); mode: ``warp.PLAIN`` or ``warp.ALPHA_WEIGHTED``; an image no item names is not decoded;
+        ``warp.fields`` (``warp.item`` makes one; the flag ``warp.NEAREST`` takes one sample instead of 2 x 2 taps - for label maps -, ``warp.BICUBIC`` = 16 takes 4 x 4 under Keys' cubic; ``warp.REFLECT`` = 64, ``warp.REFLECT_101`` = 128 and ``warp.WRAP`` = 256 fold every tap into the rectangle instead of ``warp.REPLICATE`` or the fill; ``warp.SUPER2`` = 1024 and ``warp.SUPER4`` = 2048 average 2 x 2 or 4 x 4 bilinear sub-samples per output pixel with one rounding, for maps that reduce by up to 4; ``warp.VOTE2`` = 8192 and ``warp.VOTE4`` = 16384 take the majority vote of 2 x 2 or 4 x 4 nearest sub-samples per output pixel - for label maps under such maps -, a sampling of their own; ``warp.PROJECTIVE`` = 131072 makes the map a perspective map whose two coefficients g and h travel in ``reserved`` - ``warp.item(..., proj=(g, h))``, ``warp.perspective`` -, with the bilinear, nearest or bicubic sampling and any border); mode: ``warp.PLAIN`` or ``warp.ALPHA_WEIGHTED``; an image no item names is not decoded;
         ``qoi_amd/warp.py: warp`` states the result."""
         self._gather("decode_warped", QoimiWarp, d_streams, stream_offsets, sizes, descs, channels, items, (mode,), d_out, out_offsets, staging_bytes, stream)
 

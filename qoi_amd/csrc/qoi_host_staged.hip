@@ -333,6 +333,8 @@ static_assert(QOIMI_WARP_SUPER2 == (int)kWarpSuper2 && QOIMI_WARP_SUPER4 == (int
               "the supersampling flags: 512 is not a flag, nor is 4096; the table carries 16 flag bits");
 static_assert(QOIMI_WARP_VOTE2 == (int)kWarpVote2 && QOIMI_WARP_VOTE4 == (int)kWarpVote4 && (kWarpVote4 << 16) == (1u << 30),
               "the vote flags: 4096 is not a flag, nor is a bit from 32768 on; the table carries 16 flag bits");
+static_assert(QOIMI_WARP_PROJECTIVE == (int)kWarpProjective && kWarpProjective == (1u << 17) && (kWarpEntryProjective & 0xFFFFFDFFu) == 0u,
+              "the projective flag: 32768 and 65536 are not flags; the table carries it in bit 9 of cfg, between the alpha mode and the 16 flag bits");
 
 extern "C" size_t qoimi_warp_size(const qoi_desc* desc, const qoimi_warp* item, int channels) {
     size_t bytes = 0;
@@ -365,14 +367,15 @@ extern "C" int qoimi_warp_orient(const qoi_desc* desc, unsigned x, unsigned y, u
 // gather_warped (qoi_staged.h) with bytes as the output: one launch of warp_gather over the sub-batch's items - of warp_bicubic_bytes
 // (qoi_warp_cubic.hip) where an item of the call carries QOIMI_WARP_BICUBIC, of warp_border_bytes (qoi_warp_border.hip) where one carries
 // QOIMI_WARP_REFLECT, QOIMI_WARP_REFLECT_101 or QOIMI_WARP_WRAP, of warp_super_bytes (qoi_warp_super.hip) where one carries QOIMI_WARP_SUPER2 or
-// QOIMI_WARP_SUPER4, of warp_vote_bytes (qoi_warp_vote.hip) where one carries QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4.
+// QOIMI_WARP_SUPER4, of warp_vote_bytes (qoi_warp_vote.hip) where one carries QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4, of warp_proj_bytes (qoi_warp_proj.hip)
+// where one carries QOIMI_WARP_PROJECTIVE.
 extern "C" int qoimi_decode_warped(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs,
                                    int n_images, int channels, const qoimi_warp* items, int n_items, int mode, void* d_out, const size_t* out_offsets,
                                    size_t staging_bytes, void* stream) {
     return gather_warped(c, d_streams, stream_offsets, sizes, descs, n_images, channels, items, n_items, mode, d_out, out_offsets, staging_bytes, stream,
-                         accept_any, warp_bytes, accept_outputs, &qoimi_ctx::warp_stats, {"warp_gather", "warp_bicubic_bytes", "warp_border_bytes", "warp_super_bytes", "warp_vote_bytes"},
+                         accept_any, warp_bytes, accept_outputs, &qoimi_ctx::warp_stats, {"warp_gather", "warp_bicubic_bytes", "warp_border_bytes", "warp_super_bytes", "warp_vote_bytes"}, "warp_proj_bytes",
         [&](WarpKernel kind, const WarpEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
-            (kind == kWarpKernelVote ? launch_warp_vote
+            (kind == kWarpKernelProj ? launch_warp_proj : kind == kWarpKernelVote ? launch_warp_vote
                                     : (kind == kWarpKernelSuper ? launch_warp_super : (kind == kWarpKernelBorder ? launch_warp_border : (kind == kWarpKernelCubic ? launch_warp_cubic : launch_warp))))(
                 (const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, grid, st);
         });

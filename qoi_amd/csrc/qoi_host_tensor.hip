@@ -172,9 +172,9 @@ extern "C" int qoimi_decode_warped_tensors(qoimi_ctx* c, const void* d_streams, 
         [&]() { return check_tensor_format(format); },
         [&](const qoimi_warp* r, unsigned och, size_t* bytes) { return tensor_bytes(warp_bytes, r, och, format, bytes); },
         [&](const CheckedItems&) { return check_tensor_alignment(d_out, out_offsets, (size_t)n_items, format_elem(format)); },
-        &qoimi_ctx::tensor_stats, {"tensor_warp", "warp_bicubic_tensor", "warp_border_tensor", "warp_super_tensor", "warp_vote_tensor"},
+        &qoimi_ctx::tensor_stats, {"tensor_warp", "warp_bicubic_tensor", "warp_border_tensor", "warp_super_tensor", "warp_vote_tensor"}, "warp_proj_tensor",
         [&](WarpKernel kind, const WarpEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) {
-            (kind == kWarpKernelVote ? launch_tensor_warp_vote
+            (kind == kWarpKernelProj ? launch_tensor_warp_proj : kind == kWarpKernelVote ? launch_tensor_warp_vote
                                      : (kind == kWarpKernelSuper ? launch_tensor_warp_super
                                      : (kind == kWarpKernelBorder ? launch_tensor_warp_border : (kind == kWarpKernelCubic ? launch_tensor_warp_cubic : launch_tensor_warp))))(
                 (const uint8_t*)c->ver_stage.base, tab, m, tiles, (uint8_t*)d_out, kernel_format(format), grid, st);

@@ -298,7 +298,7 @@ static_assert(sizeof(CmpImage) == 32 && sizeof(CmpDiff) == 32, "table layouts");
 void launch_compare(const uint8_t* a, const uint8_t* b, const CmpImage* tab, uint32_t m, uint32_t tiles, CmpDiff* diffs, uint32_t grid,
                     hipStream_t st, KernelTimer* tm);
 
-// ---- table-driven kernels over staged pixels (qoi_thumb.hip, qoi_crop.hip, qoi_resize.hip, qoi_warp.hip, qoi_warp_cubic.hip, qoi_warp_border.hip, qoi_warp_super.hip, qoi_warp_vote.hip, qoi_tensor.hip, qoi_cubic.hip, qoi_lanczos.hip, qoi_nearest.hip, qoi_mode.hip, qoi_stats.hip) ------
+// ---- table-driven kernels over staged pixels (qoi_thumb.hip, qoi_crop.hip, qoi_resize.hip, qoi_warp.hip, qoi_warp_cubic.hip, qoi_warp_border.hip, qoi_warp_super.hip, qoi_warp_vote.hip, qoi_warp_proj.hip, qoi_tensor.hip, qoi_cubic.hip, qoi_lanczos.hip, qoi_nearest.hip, qoi_mode.hip, qoi_stats.hip) ------
 // One entry per output (thumbnail, crop, resized item, region); the tile sizes, the largest factors and the arithmetic stand in
 // qoi_*_core.h, which the host tests compile without HIP.  launch_*: the kernel over the m table entries at tab (their tiles: [0, tiles));
 // grid: workgroups, at most `tiles`.  No timer marks: these kernels have no entry in the name table (the calls count their launches).
@@ -311,10 +311,11 @@ struct CropEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, ch, first_tile, c
 struct ResizeEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, rh, ow, oh, first_tile, cfg, reserved; };
 // StatsEntry::index: the region's entry in the result table (and its histogram); cfg: the region's flags
 struct StatsEntry { u64 src_off; uint32_t w, x, y, cw, ch, first_tile, index, cfg, reserved[2]; };
-// WarpEntry::cfg: och | (alpha weighted ? 1 : 0) << 8 | flags << 16 (kWarpReplicate, kWarpNearest, kWarpBicubic, kWarpReflect, kWarpReflect101, kWarpWrap, kWarpSuper2, kWarpSuper4, kWarpVote2, kWarpVote4); a, b, c, d, e, f: the item's map (qoi_warp_core.h), fill: its fill colour
-struct WarpEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, rh, ow, oh, first_tile, cfg, fill; int32_t a, b, d, e; long long c, f; };
+// WarpEntry::cfg: och | (alpha weighted ? 1 : 0) << 8 | flags << 16 (kWarpReplicate, kWarpNearest, kWarpBicubic, kWarpReflect, kWarpReflect101, kWarpWrap, kWarpSuper2, kWarpSuper4, kWarpVote2, kWarpVote4) | kWarpEntryProjective where the item carries kWarpProjective (1 << 17 does not fit the 16 flag bits; bits 10..15 are 0); a, b, c, d, e, f: the item's map (qoi_warp_core.h), fill: its fill colour; g, h: its perspective coefficients (qoi_warp_proj_core.h), 0 without the flag
+struct WarpEntry { u64 src_off, dst_off; uint32_t w, x, y, cw, rh, ow, oh, first_tile, cfg, fill; int32_t a, b, d, e; long long c, f; int32_t g, h; };
+constexpr uint32_t kWarpEntryProjective = 1u << 9;
 static_assert(sizeof(ThumbImage) == 48 && sizeof(CropEntry) == 48 && sizeof(ResizeEntry) == 56 && sizeof(StatsEntry) == 48, "table layouts");
-static_assert(sizeof(WarpEntry) == 88 && offsetof(WarpEntry, first_tile) == 44 && offsetof(WarpEntry, a) == 56 && offsetof(WarpEntry, c) == 72, "table layouts");
+static_assert(sizeof(WarpEntry) == 96 && offsetof(WarpEntry, first_tile) == 44 && offsetof(WarpEntry, a) == 56 && offsetof(WarpEntry, c) == 72 && offsetof(WarpEntry, g) == 88, "table layouts");
 struct StatsAcc;                                       // a region's result (qoi_stats_core.h)
 constexpr uint32_t kStatsBins = 4u * 256u;             // counters of a region's histogram
 
@@ -348,6 +349,9 @@ void launch_tensor_warp_super(const uint8_t* stage, const WarpEntry* tab, uint32
 // ... and for a call with a QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4 item: the majority vote of s x s nearest sub-samples for its tiles, the tiles above as they are for every other item (qoi_warp_vote.hip; qoi_warp_vote_core.h)
 void launch_warp_vote(const uint8_t* stage, const WarpEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, uint32_t grid, hipStream_t st);
 void launch_tensor_warp_vote(const uint8_t* stage, const WarpEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, const TensorFormat& fmt, uint32_t grid, hipStream_t st);
+// ... and for a call with a QOIMI_WARP_PROJECTIVE item: the position of an output pixel divided by the item's denominator for its tiles, the tiles above as they are for every other item (qoi_warp_proj.hip; qoi_warp_proj_core.h)
+void launch_warp_proj(const uint8_t* stage, const WarpEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, uint32_t grid, hipStream_t st);
+void launch_tensor_warp_proj(const uint8_t* stage, const WarpEntry* tab, uint32_t m, uint32_t tiles, uint8_t* out, const TensorFormat& fmt, uint32_t grid, hipStream_t st);
 // hist: NULL or the call's histograms
 void launch_stats(const uint8_t* stage, const StatsEntry* tab, uint32_t m, uint32_t tiles, StatsAcc* res, unsigned* hist, uint32_t grid, hipStream_t st);
 

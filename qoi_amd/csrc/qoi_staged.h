@@ -12,6 +12,7 @@
 #include "qoi_warp_cubic_core.h"
 #include "qoi_warp_super_core.h"
 #include "qoi_warp_vote_core.h"
+#include "qoi_warp_proj_core.h"
 
 // ------------------------------------------------------------------------------------
 // the few lines several entry points repeat
@@ -130,7 +131,9 @@ static bool resize_bytes(const qoimi_resize* r, unsigned och, size_t* bytes) {
 // The items of qoimi_decode_warped, in this order: the rectangle rules of resample_rect_wrong (a zero size, then a rectangle that leaves its
 // image), the output's sides, its pixels, the map's offsets (qoi_warp_core.h: what keeps both positions in 64 bits), the flags (a bit that is
 // none, then the two samplings together, then more than one of the four borders, then both SUPER flags, then a SUPER flag with a sampling
-// that is not the bilinear one, then both VOTE flags, then a VOTE flag with another sampling or a SUPER flag), reserved.
+// that is not the bilinear one, then both VOTE flags, then a VOTE flag with another sampling or a SUPER flag), reserved.  With
+// QOIMI_WARP_PROJECTIVE `reserved` holds the item's g and h and is not looked at as such; in its place stand the rules of
+// qoi_warp_proj_core.h: the flag with a SUPER or VOTE flag, then the tighter offsets, then the least denominator inside the output.
 static const char* warp_item_wrong(const qoi_desc* d, const qoimi_warp* r) {
     if (r->width == 0u || r->height == 0u || r->out_width == 0u || r->out_height == 0u) return "zero width or height";
     if ((uint64_t)r->x + r->width > d->width || (uint64_t)r->y + r->height > d->height) return "the rectangle leaves its image";
@@ -139,7 +142,7 @@ static const char* warp_item_wrong(const qoi_desc* d, const qoimi_warp* r) {
     if (r->c <= -kWarpMaxOffset || r->c >= kWarpMaxOffset || r->f <= -kWarpMaxOffset || r->f >= kWarpMaxOffset) return "|c| or |f| is 2^56 or more";
     const unsigned supers = r->flags & (QOIMI_WARP_SUPER2 | QOIMI_WARP_SUPER4);
     const unsigned known = QOIMI_WARP_REPLICATE | QOIMI_WARP_NEAREST | QOIMI_WARP_BICUBIC | QOIMI_WARP_REFLECT | QOIMI_WARP_REFLECT_101 | QOIMI_WARP_WRAP |
-                           QOIMI_WARP_SUPER2 | QOIMI_WARP_SUPER4 | QOIMI_WARP_VOTE2 | QOIMI_WARP_VOTE4;
+                           QOIMI_WARP_SUPER2 | QOIMI_WARP_SUPER4 | QOIMI_WARP_VOTE2 | QOIMI_WARP_VOTE4 | QOIMI_WARP_PROJECTIVE;
     const unsigned votes = r->flags & (QOIMI_WARP_VOTE2 | QOIMI_WARP_VOTE4);
     const unsigned borders = r->flags & (QOIMI_WARP_REPLICATE | QOIMI_WARP_REFLECT | QOIMI_WARP_REFLECT_101 | QOIMI_WARP_WRAP);
     if ((r->flags & ~known) != 0u) return "unknown flag bit";
@@ -152,6 +155,16 @@ static const char* warp_item_wrong(const qoi_desc* d, const qoimi_warp* r) {
     if ((votes & (votes - 1u)) != 0u) return "QOIMI_WARP_VOTE2 and QOIMI_WARP_VOTE4 together";
     if (votes != 0u && (r->flags & (QOIMI_WARP_NEAREST | QOIMI_WARP_BICUBIC | QOIMI_WARP_SUPER2 | QOIMI_WARP_SUPER4)) != 0u)
         return "the vote is a sampling of its own: QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4 with QOIMI_WARP_NEAREST, QOIMI_WARP_BICUBIC, QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4";
+    if ((r->flags & QOIMI_WARP_PROJECTIVE) != 0u) {
+        if (supers != 0u || votes != 0u)
+            return "the projective map is defined for the bilinear, nearest and bicubic samplings: QOIMI_WARP_PROJECTIVE with QOIMI_WARP_SUPER2, QOIMI_WARP_SUPER4, QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4";
+        if (r->c <= -kWarpProjMaxOffset || r->c >= kWarpProjMaxOffset || r->f <= -kWarpProjMaxOffset || r->f >= kWarpProjMaxOffset)
+            return "|c| or |f| is 2^53 or more with QOIMI_WARP_PROJECTIVE";
+        const uint32_t F = warp_proj_bits(r->out_width, r->out_height);
+        if (warp_proj_least(warp_proj_of(r->reserved), F, r->out_width, r->out_height) < ((int64_t)1 << (F - 3u)))
+            return "the denominator of QOIMI_WARP_PROJECTIVE falls below 1/8 inside the output: 2^F - |g| * (out_width - 1) - |h| * (out_height - 1) < 2^(F - 3)";
+        return nullptr;                                            // (reserved holds g and h)
+    }
     if (r->reserved != 0u) return "reserved is not 0";
     return nullptr;
 }
@@ -321,7 +334,9 @@ static int gather_resampled(const ResampleKind& kind, qoimi_ctx* c, const void* 
         }, launch, stream);
 }
 
-// ... and the warp call (the plan: qoi_amd/warp.py: plan).  launch(kind, entries, m, tiles, workgroups, stream): kind is kWarpKernelVote
+// ... and the warp call (the plan: qoi_amd/warp.py: plan).  launch(kind, entries, m, tiles, workgroups, stream): kind is kWarpKernelProj
+// where an item of the CALL carries QOIMI_WARP_PROJECTIVE - then every sub-batch runs the kernel of qoi_warp_proj.hip, which serves every
+// other item as well, VOTE items included; `proj_kernel` is its name in the message of a failed launch -, else kWarpKernelVote
 // where an item of the CALL carries QOIMI_WARP_VOTE2 or QOIMI_WARP_VOTE4 - then every sub-batch runs the kernel of qoi_warp_vote.hip, which
 // serves every other item as well -, else kWarpKernelSuper
 // where one carries QOIMI_WARP_SUPER2 or QOIMI_WARP_SUPER4 - the kernel of qoi_warp_super.hip, likewise -, else kWarpKernelBorder
@@ -329,11 +344,11 @@ static int gather_resampled(const ResampleKind& kind, qoimi_ctx* c, const void* 
 // qoi_warp_border.hip, likewise -, else kWarpKernelCubic where one carries QOIMI_WARP_BICUBIC - the kernel of
 // qoi_warp_cubic.hip, likewise -, else kWarpKernelPlain: a call without those flags launches what it always launched.  kernels[kind] is the
 // name in the message of a failed launch.
-enum WarpKernel { kWarpKernelPlain = 0, kWarpKernelCubic = 1, kWarpKernelBorder = 2, kWarpKernelSuper = 3, kWarpKernelVote = 4 };
+enum WarpKernel { kWarpKernelPlain = 0, kWarpKernelCubic = 1, kWarpKernelBorder = 2, kWarpKernelSuper = 3, kWarpKernelVote = 4, kWarpKernelProj = 5 };
 template <class Before, class Bytes, class After, class Launch>
 static int gather_warped(qoimi_ctx* c, const void* d_streams, const size_t* stream_offsets, const int* sizes, const qoi_desc* descs, int n_images, int channels,
                          const qoimi_warp* items, int n_items, int mode, void* d_out, const size_t* out_offsets, size_t staging_bytes, void* stream,
-                         Before before, Bytes bytes_of, After after, long long (qoimi_ctx::*stats)[4], const char* const (&kernels)[5], Launch launch) {
+                         Before before, Bytes bytes_of, After after, long long (qoimi_ctx::*stats)[4], const char* const (&kernels)[5], const char* proj_kernel, Launch launch) {
     // (everything is looked at before the context is: a rejected call launches nothing and leaves the caller's buffers as they were)
     if (!c || !d_streams || !stream_offsets || !sizes || !descs || !items || !d_out || !out_offsets || n_images <= 0 || n_items <= 0) return fail(QOIMI_E_ARG, "NULL/empty argument");
     if (const int rc = check_out_channels(channels)) return rc;
@@ -352,16 +367,21 @@ static int gather_warped(qoimi_ctx* c, const void* d_streams, const size_t* stre
     const uint32_t weighted = (mode == QOIMI_RESIZE_ALPHA_WEIGHTED && och == 4u) ? 1u : 0u;   // with 3 output channels the mode is PLAIN
     unsigned any = 0u;
     for (size_t j = 0; j < n; ++j) any |= items[j].flags;
-    const WarpKernel kind = (any & kWarpVotes) != 0u ? kWarpKernelVote
+    const WarpKernel kind = (any & kWarpProjective) != 0u ? kWarpKernelProj
+                          : (any & kWarpVotes) != 0u ? kWarpKernelVote
                           : ((any & kWarpSupers) != 0u ? kWarpKernelSuper
                           : ((any & kWarpBorders) != 0u ? kWarpKernelBorder : ((any & QOIMI_WARP_BICUBIC) != 0u ? kWarpKernelCubic : kWarpKernelPlain)));
-    return run_staged<WarpEntry>(c, c->*stats, (long long)plan.refs.size(), kernels[kind], d_streams, stream_offsets, sizes, descs, plan, ok.rows, order,
+    return run_staged<WarpEntry>(c, c->*stats, (long long)plan.refs.size(), kind == kWarpKernelProj ? proj_kernel : kernels[kind], d_streams, stream_offsets, sizes, descs, plan, ok.rows, order,
         [&](WarpEntry& t, size_t e) {
             const size_t j = order.by_ref[e];
             const qoimi_warp& r = items[j];
             t.src_off = (u64)plan.at[(size_t)plan.ref_of[r.image]]; t.dst_off = (u64)out_offsets[j];
             t.w = descs[r.image].width; t.x = r.x; t.y = r.y; t.cw = r.width; t.rh = r.height; t.ow = r.out_width; t.oh = r.out_height;
-            t.first_tile = order.first_tile[e]; t.cfg = och | (weighted << 8) | (r.flags << 16); t.fill = r.fill;
+            t.first_tile = order.first_tile[e]; t.cfg = och | (weighted << 8) | ((r.flags & 0xFFFFu) << 16); t.fill = r.fill;
             t.a = r.a; t.b = r.b; t.d = r.d; t.e = r.e; t.c = r.c; t.f = r.f;
+            const bool projective = (r.flags & kWarpProjective) != 0u;
+            const WarpProj pj = warp_proj_of(projective ? r.reserved : 0u);
+            if (projective) t.cfg |= kWarpEntryProjective;
+            t.g = pj.g; t.h = pj.h;
         }, [&](const WarpEntry* tab, uint32_t m, uint32_t tiles, uint32_t grid, hipStream_t st) { launch(kind, tab, m, tiles, grid, st); }, stream);
 }

@@ -95,12 +95,12 @@ QOIMI_RESIZE_HD void warp_border_cubic_axis(int64_t P, const WarpFold& fo, WarpC
     }
 }
 
-// Output pixel (X, Y) of an item with a border flag, by its sampling: one, 2 x 2 or 4 x 4 samples, every one of them inside the rectangle.
+// The output pixel at the position (Px, Py) of an item with a border flag, by its sampling: one, 2 x 2 or 4 x 4 samples, every one of them
+// inside the rectangle.
 template <bool WEIGHTED, class Mem>
-QOIMI_RESIZE_HD uint32_t warp_border_pixel(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
+QOIMI_RESIZE_HD uint32_t warp_border_pixel_at(const Mem& mem, const WarpGeom& g, int64_t Px, int64_t Py) {
     const uint32_t border = g.flags & kWarpBorders;
     const WarpFold fx = warp_fold_of(border, g.cw), fy = warp_fold_of(border, g.rh);
-    const int64_t Px = warp_position(g.a, g.b, g.c, X, Y), Py = warp_position(g.d, g.e, g.f, X, Y);
     if ((g.flags & kWarpNearest) != 0u) {
         const uint32_t k = warp_fold_index(warp_fold_position(Px >> 17, fx.P), fx), r = warp_fold_index(warp_fold_position(Py >> 17, fy.P), fy);
         return mem.load((uint64_t)(g.y + r) * g.w + g.x + k);
@@ -115,6 +115,12 @@ QOIMI_RESIZE_HD uint32_t warp_border_pixel(const Mem& mem, const WarpGeom& g, ui
     warp_border_axis(Px, fx, ax);
     warp_border_axis(Py, fy, ay);
     return warp_blend<WEIGHTED>(mem, g, ax, ay);
+}
+
+// Output pixel (X, Y) of an item with a border flag: warp_border_pixel_at its position under the affine map.
+template <bool WEIGHTED, class Mem>
+QOIMI_RESIZE_HD uint32_t warp_border_pixel(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
+    return warp_border_pixel_at<WEIGHTED>(mem, g, warp_position(g.a, g.b, g.c, X, Y), warp_position(g.d, g.e, g.f, X, Y));
 }
 
 // Work item t of tile `tile` of the item: warp_border_pixel for an item with a border flag, warp_cubic_work as it is for any other (the

@@ -116,7 +116,19 @@ QOIMI_RESIZE_HD uint32_t warp_blend(const Mem& mem, const WarpGeom& g, const War
     return resize_pixel(s, kWarpTotal, WEIGHTED);
 }
 
-// Output pixel (X, Y): the axes with the border by kWarpReplicate or the fill, and their blend.
+// The output pixel whose position in the rectangle is (Px, Py): the axes with the border by kWarpReplicate or the fill, and their blend.
+template <bool WEIGHTED, class Mem>
+QOIMI_RESIZE_HD uint32_t warp_pixel_at(const Mem& mem, const WarpGeom& g, int64_t Px, int64_t Py) {
+    const bool replicate = (g.flags & kWarpReplicate) != 0u;
+    WarpAxis ax, ay;
+    warp_axis(Px, g.cw, replicate, ax);
+    warp_axis(Py, g.rh, replicate, ay);
+    return warp_blend<WEIGHTED>(mem, g, ax, ay);
+}
+
+// Output pixel (X, Y): warp_pixel_at its position under the affine map.  (Written out, each position formed where its axis takes it, not as
+// a call of warp_pixel_at: handed both positions first, the compiler allots warp_gather and tensor_warp other registers than the ones
+// tests/test_warp_bicubic_api.py holds them to; the results are the same.)
 template <bool WEIGHTED, class Mem>
 QOIMI_RESIZE_HD uint32_t warp_pixel(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
     const bool replicate = (g.flags & kWarpReplicate) != 0u;
@@ -126,10 +138,10 @@ QOIMI_RESIZE_HD uint32_t warp_pixel(const Mem& mem, const WarpGeom& g, uint32_t 
     return warp_blend<WEIGHTED>(mem, g, ax, ay);
 }
 
-// Output pixel (X, Y) under kWarpNearest: one load, none where the pixel takes the fill.
+// The output pixel at the position (Px, Py) under kWarpNearest: one load, none where the pixel takes the fill.
 template <class Mem>
-QOIMI_RESIZE_HD uint32_t warp_nearest(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
-    int64_t k = warp_position(g.a, g.b, g.c, X, Y) >> 17, r = warp_position(g.d, g.e, g.f, X, Y) >> 17;   // (64-bit: the border test comes before the narrowing)
+QOIMI_RESIZE_HD uint32_t warp_nearest_at(const Mem& mem, const WarpGeom& g, int64_t Px, int64_t Py) {
+    int64_t k = Px >> 17, r = Py >> 17;                            // (64-bit: the border test comes before the narrowing)
     bool in = k >= 0 && k < (int64_t)g.cw && r >= 0 && r < (int64_t)g.rh;
     if ((g.flags & kWarpReplicate) != 0u) {
         k = k < 0 ? 0 : (k < (int64_t)g.cw ? k : (int64_t)g.cw - 1);
@@ -137,6 +149,12 @@ QOIMI_RESIZE_HD uint32_t warp_nearest(const Mem& mem, const WarpGeom& g, uint32_
         in = true;
     }
     return in ? mem.load((uint64_t)(g.y + (uint32_t)r) * g.w + g.x + (uint32_t)k) : g.fill;
+}
+
+// Output pixel (X, Y) under kWarpNearest: warp_nearest_at its position under the affine map.
+template <class Mem>
+QOIMI_RESIZE_HD uint32_t warp_nearest(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
+    return warp_nearest_at(mem, g, warp_position(g.a, g.b, g.c, X, Y), warp_position(g.d, g.e, g.f, X, Y));
 }
 
 // Pixel (X, Y) to its place in the output at q: one dword where the output holds 4 bytes per pixel and the address is aligned, else och

@@ -113,14 +113,20 @@ QOIMI_RESIZE_HD uint32_t warp_cubic_blend(const Mem& mem, const WarpGeom& g, con
     return cubic_pixel(s, WEIGHTED);
 }
 
-// Output pixel (X, Y): the axes with the border by kWarpReplicate or the fill, and their blend.
+// The output pixel whose position in the rectangle is (Px, Py): the axes with the border by kWarpReplicate or the fill, and their blend.
 template <bool WEIGHTED, class Mem>
-QOIMI_RESIZE_HD uint32_t warp_cubic_pixel(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
+QOIMI_RESIZE_HD uint32_t warp_cubic_pixel_at(const Mem& mem, const WarpGeom& g, int64_t Px, int64_t Py) {
     const bool replicate = (g.flags & kWarpReplicate) != 0u;
     WarpCubicAxis ax, ay;
-    warp_cubic_axis(warp_position(g.a, g.b, g.c, X, Y), g.cw, replicate, ax);
-    warp_cubic_axis(warp_position(g.d, g.e, g.f, X, Y), g.rh, replicate, ay);
+    warp_cubic_axis(Px, g.cw, replicate, ax);
+    warp_cubic_axis(Py, g.rh, replicate, ay);
     return warp_cubic_blend<WEIGHTED>(mem, g, ax, ay);
+}
+
+// Output pixel (X, Y): warp_cubic_pixel_at its position under the affine map.
+template <bool WEIGHTED, class Mem>
+QOIMI_RESIZE_HD uint32_t warp_cubic_pixel(const Mem& mem, const WarpGeom& g, uint32_t X, uint32_t Y) {
+    return warp_cubic_pixel_at<WEIGHTED>(mem, g, warp_position(g.a, g.b, g.c, X, Y), warp_position(g.d, g.e, g.f, X, Y));
 }
 
 // Work item t of tile `tile` of the item: its pixel computed - 4 x 4 samples for an item with kWarpBicubic, warp_nearest / warp_pixel as they

@@ -97,11 +97,28 @@ integer, every shift and division floors.
   byte; a constant rectangle stays the constant under any map with any of the four borders; there is no adaptivity, and beyond 4 : 1 the
   result still skips pixels.  ``vote_reference`` is the same statement as a naive loop.
 
+* With ``PROJECTIVE`` = 131072 (``1 << 17``; a flag; 32768 and 65536 are not flags) the map is a PERSPECTIVE map, a homography of the output
+  rectangle.  The flag goes with the fill or any one of the four borders and with the bilinear sampling, ``NEAREST`` or ``BICUBIC``, never
+  with ``SUPER2``, ``SUPER4``, ``VOTE2`` or ``VOTE4``.  With it ``reserved`` holds ``g = int16(reserved & 0xFFFF)`` and
+  ``h = int16(reserved >> 16)``, two's complement (``proj_of``; ``item(..., proj=(g, h))`` packs them).  With ``ow, oh`` the output's size:
+  ``L`` is the smallest integer >= 0 with ``2**L >= max(ow, oh)`` and ``F = 14 + L`` (14..34, ``proj_bits``); ``Uc = U - ow``,
+  ``Vc = V - oh`` (the doubled offsets from the output's centre); ``Nx = a*U + b*V + c``, ``Ny = d*U + e*V + f`` (the positions without the
+  flag); ``W = 2**F + g*Uc + h*Vc`` (the denominator, 1.0 at the centre); ``Px = floor(Nx * 2**F / W)``, ``Py = floor(Ny * 2**F / W)``
+  (``positions``).  From Px and Py on nothing changes.  The scale is the item's because ``W > 0`` needs ``|gamma| * ow < 1``: the useful range
+  of g is ``1 / ow``, and 16 bits at ``F = 14 + L`` cover it at every size.  Limits, behind all others, in this order: the flag with a
+  ``SUPER`` or ``VOTE`` flag; ``|c|`` or ``|f|`` from ``2**53``; ``2**F - |g|*(ow - 1) - |h|*(oh - 1) < 2**(F - 3)`` (the exact minimum of the
+  linear W over the pixel grid: the denominator stays at or above 1/8).  Then ``|Nx| < 2**54``, ``2**(F-3) <= W < 5 * 2**F < 2**37`` and
+  ``|Px| <= 8 * |Nx| < 2**57``.  With ``g = h = 0``, ``Px = Nx``: the bytes of the item without the flag.  The map applied is the quantised
+  homography, exactly; against a float64 evaluation of that same map a bilinear value differs by at most 1, at a rounding boundary only
+  (the position is floored by less than 2**-17 of a pixel); a constant stays the constant under ``REPLICATE``.  ``homography`` and
+  ``perspective`` quantise a 3 x 3 matrix or four corner points and report what that costs at the output's corners.
+
 Limits, in the order the C side checks them: a zero size; a rectangle that leaves its image; ``ow, oh < 2**20``; ``ow * oh < 400 000 000``;
 ``|c|, |f| < 2**56``; no flag bit but ``REPLICATE``, ``NEAREST``, ``BICUBIC``, ``REFLECT``, ``REFLECT_101``, ``WRAP``, ``SUPER2``, ``SUPER4``,
 ``VOTE2`` and ``VOTE4`` (2, 8, 32, 512 and 4096 are not flags), then not ``NEAREST`` and ``BICUBIC`` together, then not more than one of the
 four borders, then not both ``SUPER`` flags, then no ``SUPER`` flag with ``NEAREST`` or ``BICUBIC``, then not both ``VOTE`` flags, then no
-``VOTE`` flag with ``NEAREST``, ``BICUBIC`` or a ``SUPER`` flag; ``reserved == 0``.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
+``VOTE`` flag with ``NEAREST``, ``BICUBIC`` or a ``SUPER`` flag (``PROJECTIVE`` is a flag too); ``reserved == 0`` without ``PROJECTIVE``, with
+it the three limits above.  Then ``|a*U|, |b*V| <= 2**31 * 2**21 = 2**52`` and
 ``|Px|, |Py| < 2**57``; ``N_c <= 255 * 2**34 < 2**42``; the alpha-weighted sums are below ``2**50``: everything fits int64.
 
 With the identity the result is ``crops.crop``; with ``a = ONE // s`` and REPLICATE it is ``bilinear.bilinear`` enlarging by the power of two s;
@@ -131,6 +148,9 @@ SUPERS = SUPER2 | SUPER4        # at most one of them, with the bilinear samplin
 VOTE2 = 8192                    # the majority vote of 2 x 2 nearest sub-samples per output pixel: for label maps (4096 is not a flag)
 VOTE4 = 16384                   # 4 x 4
 VOTES = VOTE2 | VOTE4           # at most one of them, a sampling of its own: with no other sampling and no SUPER flag
+PROJECTIVE = 1 << 17            # a perspective map: reserved holds g and h; never with a SUPER or VOTE flag (32768 and 65536 are not flags)
+PROJ_BASE = 14                  # F = PROJ_BASE + L: the fractional bits of the denominator
+PROJ_MAX_OFFSET = 1 << 53       # |c|, |f| of an item with PROJECTIVE stay below it
 CUBIC_ONE = bicubic.ONE         # the weights of an axis add up to it
 CUBIC_L1_MAX = 5 << 13          # sum |q| of an axis stays at or below it
 PLAIN = resize.PLAIN
@@ -153,12 +173,68 @@ def fields(it) -> Tuple[int, ...]:
     return tuple(int(v) for v in it)
 
 
-def item(image: int, rect, out_size, matrix=IDENTITY, flags: int = 0, fill: int = 0) -> Tuple[int, ...]:
-    """An item's tuple from rect (x, y, width, height), out_size (out_width, out_height) and matrix (a, b, c, d, e, f)."""
+def item(image: int, rect, out_size, matrix=IDENTITY, flags: int = 0, fill: int = 0, proj=None) -> Tuple[int, ...]:
+    """An item's tuple from rect (x, y, width, height), out_size (out_width, out_height) and matrix (a, b, c, d, e, f); proj = (g, h), each
+    16-bit signed, makes it a ``PROJECTIVE`` item: the flag is set and ``reserved`` holds the two (``proj_reserved``)."""
     x, y, cw, rh = rect
     ow, oh = out_size
     a, b, c, d, e, f = matrix
-    return (image, x, y, cw, rh, ow, oh, flags, a, b, d, e, fill, 0, c, f)
+    if proj is None:
+        return (image, x, y, cw, rh, ow, oh, flags, a, b, d, e, fill, 0, c, f)
+    return (image, x, y, cw, rh, ow, oh, flags | PROJECTIVE, a, b, d, e, fill, proj_reserved(*proj), c, f)
+
+
+def proj_reserved(g: int, h: int) -> int:
+    """``reserved`` of a ``PROJECTIVE`` item: g in its lower and h in its upper 16 bits, two's complement."""
+    if not (-2 ** 15 <= g < 2 ** 15 and -2 ** 15 <= h < 2 ** 15):
+        raise ValueError("proj_reserved: g and h are 16-bit signed")
+    return (int(g) & 0xFFFF) | ((int(h) & 0xFFFF) << 16)
+
+
+def proj_of(reserved: int) -> Tuple[int, int]:
+    """(g, h) of a ``PROJECTIVE`` item's ``reserved``."""
+    g, h = reserved & 0xFFFF, (reserved >> 16) & 0xFFFF
+    return g - ((g & 0x8000) << 1), h - ((h & 0x8000) << 1)
+
+
+def proj_bits(ow: int, oh: int) -> int:
+    """F of an ow x oh output: 14 + L with L the smallest integer >= 0 with 2**L >= max(ow, oh)."""
+    return PROJ_BASE + (max(ow, oh) - 1).bit_length()
+
+
+def _scaled_quotient(N: np.ndarray, W: np.ndarray, F: int) -> np.ndarray:
+    """int64: floor(N * 2**F / W) for |N| < 2**54 and 0 < W < 2**37 without leaving int64 (the product has up to 88 bits): long division -
+    the head floor(N / W), then the F fractional bits in chunks of at most 17, so that the remainder r < W shifted up stays below 2**54."""
+    P = N // W                                                           # (numpy's // floors)
+    r = N - P * W
+    left = F
+    while left:
+        s = min(left, 17)
+        t = r << s
+        q = t // W
+        r = t - q * W
+        P = P * (1 << s) + q
+        left -= s
+    return P
+
+
+def positions(out_size, matrix=IDENTITY, flags: int = 0, reserved: int = 0):
+    """(Px, Py), int64[out_height, out_width] each: the position of every output pixel in the source rectangle in doubled coordinates with 16
+    fractional bits - ``a*U + b*V + c`` and ``d*U + e*V + f``, and with ``PROJECTIVE`` those divided by the item's denominator:
+    ``floor(N * 2**F / W)``, exactly.  Integers only."""
+    ow, oh = (int(v) for v in out_size)
+    a, b, c, d, e, f = (int(v) for v in matrix)
+    U = (2 * np.arange(ow, dtype=np.int64) + 1)[None, :]
+    V = (2 * np.arange(oh, dtype=np.int64) + 1)[:, None]
+    Nx, Ny = a * U + b * V + c, d * U + e * V + f
+    if not flags & PROJECTIVE:
+        return Nx, Ny
+    g, h = proj_of(reserved)
+    F = proj_bits(ow, oh)
+    W = (1 << F) + g * (U - ow) + h * (V - oh)
+    if W.min() <= 0:
+        raise ValueError("positions: the denominator is not positive inside the output")
+    return _scaled_quotient(Nx, W, F), _scaled_quotient(Ny, W, F)
 
 
 def as_crop(it) -> Tuple[int, int, int, int, int, int]:
@@ -183,7 +259,7 @@ def _wrong(w: int, h: int, rect, out_size, matrix, flags: int, reserved: int = 0
         return "|c| or |f| from 2**56"
     if any(not -2 ** 31 <= v < 2 ** 31 for v in (a, b, d, e)):
         return "a, b, d, e are 32-bit"
-    if flags & ~(BORDERS | NEAREST | BICUBIC | SUPERS | VOTES):
+    if flags & ~(BORDERS | NEAREST | BICUBIC | SUPERS | VOTES | PROJECTIVE):
         return "unknown flag bit"
     if flags & NEAREST and flags & BICUBIC:
         return "NEAREST and BICUBIC together"
@@ -197,6 +273,16 @@ def _wrong(w: int, h: int, rect, out_size, matrix, flags: int, reserved: int = 0
         return "VOTE2 and VOTE4 together"
     if flags & VOTES and flags & (NEAREST | BICUBIC | SUPERS):
         return "the vote is a sampling of its own: a VOTE flag with NEAREST, BICUBIC, SUPER2 or SUPER4"
+    if flags & PROJECTIVE:                                              # reserved holds g and h
+        if flags & (SUPERS | VOTES):
+            return "the projective map is defined for the bilinear, nearest and bicubic samplings: PROJECTIVE with a SUPER or VOTE flag"
+        if abs(c) >= PROJ_MAX_OFFSET or abs(f) >= PROJ_MAX_OFFSET:
+            return "|c| or |f| from 2**53 with PROJECTIVE"
+        g, h = proj_of(reserved)
+        F = proj_bits(ow, oh)
+        if (1 << F) - abs(g) * (ow - 1) - abs(h) * (oh - 1) < 1 << (F - 3):
+            return "the denominator of PROJECTIVE falls below 1/8 inside the output"
+        return ""
     if reserved:
         return "reserved is not 0"
     return ""
@@ -269,7 +355,7 @@ def _clamp(v: np.ndarray) -> np.ndarray:
     return np.minimum(np.maximum(v, 0), 255)
 
 
-def cubic_reference(D: np.ndarray, rect, out_size, matrix=IDENTITY, flags: int = 0, fill: int = 0) -> np.ndarray:
+def cubic_reference(D: np.ndarray, rect, out_size, matrix=IDENTITY, flags: int = 0, fill: int = 0, reserved: int = 0) -> np.ndarray:
     """float64[out_height, out_width, och]: Keys' kernel (a = -1/2) at the same positions with the same border rule (``fill``, ``REPLICATE``
     or a folding border), evaluated in
     float64, PLAIN, neither rounded nor clamped (positions below 2**53 are exact there)."""
@@ -291,8 +377,9 @@ def cubic_reference(D: np.ndarray, rect, out_size, matrix=IDENTITY, flags: int =
         i, inside = _border(k, n, flags)
         return i, w, inside
 
-    kx, wx, inx = axis(a * U + b * V + c, cw)
-    ky, wy, iny = axis(d * U + e * V + f, rh)
+    Px, Py = positions((ow, oh), matrix, flags, reserved)
+    kx, wx, inx = axis(Px, cw)
+    ky, wy, iny = axis(Py, rh)
     out = np.zeros((oh, ow, och), dtype=np.float64)
     for r in range(4):
         for k in range(4):
@@ -308,9 +395,9 @@ def cubic_bound() -> int:
 
 
 def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, int], matrix=IDENTITY, flags: int = 0, fill: int = 0,
-         mode: int = PLAIN, och: int = 0) -> np.ndarray:
+         mode: int = PLAIN, och: int = 0, reserved: int = 0) -> np.ndarray:
     """D uint8[h, w, 3 or 4], rect (x, y, width, height) inside it, out_size (out_width, out_height), matrix (a, b, c, d, e, f)
-    -> uint8[out_height, out_width, och]; och 0 is D's own channel count.  D with 3 channels is a decode whose alpha is 255; a 4-channel
+    -> uint8[out_height, out_width, och]; och 0 is D's own channel count; reserved: the item's, g and h under ``PROJECTIVE``.  D with 3 channels is a decode whose alpha is 255; a 4-channel
     stream decoded with och 3 under a ``VOTE`` flag is stated by its 4-channel decode as D and och = 3: its alpha votes, the output lacks it
     (``mode.mode`` likewise; every other sampling gives the bytes of the 3-channel decode either way)."""
     D = np.asarray(D)
@@ -318,7 +405,7 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
         raise ValueError("warp: D must be uint8[h, w, 3 or 4]")
     if mode not in (PLAIN, ALPHA_WEIGHTED):
         raise ValueError("warp: mode must be PLAIN or ALPHA_WEIGHTED")
-    wrong = _wrong(D.shape[1], D.shape[0], rect, out_size, matrix, flags)
+    wrong = _wrong(D.shape[1], D.shape[0], rect, out_size, matrix, flags, reserved)
     if wrong:
         raise ValueError("warp: " + wrong)
     if not 0 <= fill < 2 ** 32:
@@ -336,6 +423,8 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
     F = np.array([(fill >> (8 * k)) & 255 for k in range(4)], dtype=np.int64)
     U = (2 * np.arange(ow, dtype=np.int64) + 1)[None, :]
     V = (2 * np.arange(oh, dtype=np.int64) + 1)[:, None]
+    Pxc, Pyc = positions((ow, oh), matrix, flags, reserved)              # of the pixel's own centre: a*U + b*V + c, d*U + e*V + f without PROJECTIVE
+
     def select(Px, Py):
         """the one sample of NEAREST at the positions: R[Py >> 17][Px >> 17], brought inside by the border, or the fill"""
         k, ink = _border(Px >> 17, cw, flags)
@@ -343,7 +432,7 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
         return np.where((ink & inr)[..., None], R[r, k], F[None, None, :])
 
     if flags & NEAREST:
-        return np.ascontiguousarray(select(a * U + b * V + c, d * U + e * V + f)[..., :och].astype(np.uint8))
+        return np.ascontiguousarray(select(Pxc, Pyc)[..., :och].astype(np.uint8))
     if flags & VOTES:
         L = vote_log2(flags)
         s = 1 << L
@@ -353,15 +442,15 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
                 Us, Vs = s * U + (2 * i + 1 - s), s * V + (2 * j + 1 - s)
                 keys.append(_key(select(((a * Us + b * Vs) >> L) + c, ((d * Us + e * Vs) >> L) + f)))
         keys = np.stack(keys, axis=-1)                                   # int64[oh, ow, s * s]
-        centre = _key(select(a * U + b * V + c, d * U + e * V + f))     # decides a tie where it is a winner; it does not vote
+        centre = _key(select(Pxc, Pyc))                                  # decides a tie where it is a winner; it does not vote
         count = (keys[..., :, None] == keys[..., None, :]).sum(axis=-1)
         word = (count << 33) | ((keys == centre[..., None]).astype(np.int64) << 32) | (0xFFFFFFFF - keys)   # the largest: count, centre, lowest key
         win = np.take_along_axis(keys, np.argmax(word, axis=-1)[..., None], axis=-1)[..., 0]
         out = np.stack([(win >> sh) & 255 for sh in (24, 16, 8, 0)], axis=-1)
         return np.ascontiguousarray(out[..., :och].astype(np.uint8))
     if flags & BICUBIC:
-        kx, qx, inx = _cubic_axis(a * U + b * V + c, cw, flags)
-        ky, qy, iny = _cubic_axis(d * U + e * V + f, rh, flags)
+        kx, qx, inx = _cubic_axis(Pxc, cw, flags)
+        ky, qy, iny = _cubic_axis(Pyc, rh, flags)
         N = np.zeros((oh, ow, 4), dtype=np.int64)
         M = np.zeros((oh, ow, 3), dtype=np.int64)
         for r in range(4):
@@ -382,8 +471,9 @@ def warp(D: np.ndarray, rect: Tuple[int, int, int, int], out_size: Tuple[int, in
     for j in range(s):
         for i in range(s):
             Us, Vs = s * U + (2 * i + 1 - s), s * V + (2 * j + 1 - s)    # below 2**23; the sums below are under 2**55
-            kx, wx, inx = _axis(((a * Us + b * Vs) >> L) + c, cw, flags)
-            ky, wy, iny = _axis(((d * Us + e * Vs) >> L) + f, rh, flags)
+            Px, Py = (Pxc, Pyc) if L == 0 else (((a * Us + b * Vs) >> L) + c, ((d * Us + e * Vs) >> L) + f)   # (L == 0: Us = U, Vs = V)
+            kx, wx, inx = _axis(Px, cw, flags)
+            ky, wy, iny = _axis(Py, rh, flags)
             for r in range(2):
                 for k in range(2):
                     v = np.where((iny[..., r] & inx[..., k])[..., None], R[ky[..., r], kx[..., k]], F[None, None, :])
@@ -532,6 +622,75 @@ def rotation(rect_size: Tuple[int, int], out_size: Tuple[int, int], degrees: flo
     a, b, d, e = (int(round(v * ONE)) for v in (co, -si, si, co))
     # the output's centre (U, V) = (ow, oh) in doubled coordinates goes to the rectangle's centre (cw, rh) << 16
     return (a, b, cw * ONE - a * ow - b * oh, d, e, rh * ONE - d * ow - e * oh)
+
+
+def homography(rect_size: Tuple[int, int], out_size: Tuple[int, int], H):
+    """((a, b, c, d, e, f), (g, h), displacement) of the ``PROJECTIVE`` item that shows the rectangle through the 3 x 3 float matrix H, which
+    takes output pixel centres to source pixel centres of the rectangle: ``(k, r) = (H0 . (X, Y, 1), H1 . (X, Y, 1)) / (H2 . (X, Y, 1))``
+    with pixel (0, 0)'s centre at (0, 0) on both sides.  The denominator is normalised to 1 at the output's centre - it must not vanish
+    there - and everything is quantised: g and h to ``2**-F`` per doubled pixel, a, b, d, e to ``2**-16``, c and f so that the output's
+    centre keeps its place to ``2**-17`` of a pixel.  displacement is the largest distance in source pixels between the real and the
+    quantised map over the four corner pixels of the output: the accuracy is REPORTED, not promised, and whether the item is accepted is
+    ``_wrong``'s to say (a horizon inside or near the output is not)."""
+    H = np.asarray(H, dtype=np.float64)
+    if H.shape != (3, 3):
+        raise ValueError("homography: H is 3 x 3")
+    cw, rh = rect_size
+    if cw < 1 or rh < 1:
+        raise ValueError("homography: an empty rectangle")
+    ow, oh = (int(v) for v in out_size)
+    F = proj_bits(ow, oh)
+    Dc = H[2, 0] * (ow - 1) / 2 + H[2, 1] * (oh - 1) / 2 + H[2, 2]       # the denominator at the output's centre (U, V) = (ow, oh)
+    if not np.isfinite(H).all() or Dc == 0:
+        raise ValueError("homography: the denominator vanishes at the output's centre")
+    H = H / Dc
+    g, h = (int(round(float(v) * 2 ** F / 2)) for v in (H[2, 0], H[2, 1]))   # X - Xc = Uc / 2
+    # the doubled position (2k + 1) * ONE = ONE * (2 * numerator + denominator) / denominator: its numerator is linear in U = 2X + 1, V = 2Y + 1
+    rows = []
+    for n in (H[0], H[1]):
+        m = 2 * n + H[2]
+        rows.append((ONE * m[0] / 2, ONE * m[1] / 2, ONE * (m[2] - m[0] / 2 - m[1] / 2)))
+    (ar, br, cr), (dr, er, fr) = rows
+    a, b, d, e = (int(round(v)) for v in (ar, br, dr, er))
+    c = int(round(ar * ow + br * oh + cr)) - a * ow - b * oh             # the centre's numerator, where W is 2**F exactly
+    f = int(round(dr * ow + er * oh + fr)) - d * ow - e * oh
+    if not (-2 ** 15 <= g < 2 ** 15 and -2 ** 15 <= h < 2 ** 15) or any(not -2 ** 31 <= v < 2 ** 31 for v in (a, b, d, e)):
+        raise ValueError("homography: a coefficient leaves its 16 or 32 bits")
+    worst = 0.0
+    for X in (0, ow - 1):
+        for Y in (0, oh - 1):
+            den = H[2, 0] * X + H[2, 1] * Y + H[2, 2]
+            U, V = 2 * X + 1, 2 * Y + 1
+            W = 2 ** F + g * (U - ow) + h * (V - oh)
+            if den == 0 or W == 0:
+                worst = float("inf")
+                continue
+            real = np.array([H[0] @ (X, Y, 1.0), H[1] @ (X, Y, 1.0)]) / den
+            quant = (np.array([a * U + b * V + c, d * U + e * V + f], dtype=np.float64) * 2.0 ** F / W / ONE - 1) / 2
+            worst = max(worst, float(np.hypot(*(real - quant))))
+    return (a, b, c, d, e, f), (g, h), worst
+
+
+def perspective(rect_size: Tuple[int, int], out_size: Tuple[int, int], corners):
+    """``homography`` of the map under which the output's four corner pixels - top-left, top-right, bottom-right, bottom-left - show the four
+    source points ``corners`` ((x, y) in pixel-centre coordinates of the rectangle, in that order): torchvision's ``endpoints`` with the
+    output's corners as ``startpoints``."""
+    ow, oh = (int(v) for v in out_size)
+    if ow < 2 or oh < 2:
+        raise ValueError("perspective: the output's corners must be four different pixels")
+    src = np.asarray(corners, dtype=np.float64)
+    if src.shape != (4, 2):
+        raise ValueError("perspective: four (x, y) points")
+    dst = [(0, 0), (ow - 1, 0), (ow - 1, oh - 1), (0, oh - 1)]
+    A, rhs = [], []
+    for (X, Y), (k, r) in zip(dst, src):
+        A.append([X, Y, 1, 0, 0, 0, -k * X, -k * Y]); rhs.append(k)
+        A.append([0, 0, 0, X, Y, 1, -r * X, -r * Y]); rhs.append(r)
+    try:
+        p = np.linalg.solve(np.array(A, dtype=np.float64), np.array(rhs, dtype=np.float64))
+    except np.linalg.LinAlgError:
+        raise ValueError("perspective: the four points do not define a homography")
+    return homography(rect_size, out_size, np.append(p, 1.0).reshape(3, 3))
 
 
 # ---------------------------------------------------------------------------------- the kernel's tiles

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
-"""qoiwarp for the MI355X path: a set of .qoi files as PNGs, re-oriented or turned about their centre.
+"""qoiwarp for the MI355X path: a set of .qoi files as PNGs, re-oriented, turned about their centre or seen in perspective.
 
     python tools/qoiwarp_mi355x.py FILE_OR_DIR... -o DIR (--orient N | --rotate DEG [--scale S]) [--size WxH] [--border fill|replicate|reflect|reflect101|wrap]
+                                   (or --perspective x0,y0,x1,y1,x2,y2,x3,y3 in the place of --orient / --rotate)
                                    [--sample bilinear|nearest|bicubic|vote2|vote4] [--supersample 1|2|4]
                                    [--fill RRGGBBAA] [--mode plain|weighted] [--staging-mb M]
 
@@ -16,7 +17,11 @@ border cv2.warpAffine pipelines default to) and --border wrap repeats it (warp.W
 one source pixel per output pixel instead of the 2 x 2 bilinear taps (warp.NEAREST): for label maps, whose values must not be averaged; --sample bicubic takes 4 x 4 under Keys' cubic with a = -1/2 (warp.BICUBIC): sharper photographs under a turn; --sample vote2 or vote4 takes the majority vote of 2 x 2 or 4 x 4 nearest sub-samples per output pixel (warp.VOTE2, warp.VOTE4): label maps under a scale down to about 1/4, where nearest skips pixels.  There is no
 adaptive antialiasing: --supersample 2 or 4 (warp.SUPER2, warp.SUPER4; default 1; with --sample bilinear only) averages 2 x 2 or 4 x 4 bilinear
 sub-samples per output pixel with one rounding, which serves scales down to about 1/4; a scale well below that wants
-tools/qoiresize_mi355x.py first.  Outputs hold 4 channels if any file does, else 3, and are
+tools/qoiresize_mi355x.py first.  --perspective x0,y0,x1,y1,x2,y2,x3,y3 names the source points - in pixel-centre coordinates of each
+image - that the output's top-left, top-right, bottom-right and bottom-left corner pixels show (warp.perspective, warp.PROJECTIVE): the
+output, of --size or the image's own size, is that quadrilateral rectified.  It goes with every --border and with --sample bilinear, nearest
+or bicubic, not with --supersample 2 or 4 or a vote.  The homography is quantised on the host; the row of a file ends with the largest
+displacement that costs at the output's corners, in source pixels.  Outputs hold 4 channels if any file does, else 3, and are
 written as DIR/<name>.png through tools/png_io.py.  One row per file: w x h x channels, the map, the output size.  A file that is no QOI
 stream (size, magic, header rules of qoi.h:497-521) is reported and left out; exit status 1 if there was one, else 0.  Needs torch for device
 memory, as tools/qoicheck_mi355x.py does.
@@ -69,6 +74,17 @@ def rotation_matrix(w: int, h: int, ow: int, oh: int, degrees: float, scale: flo
     return a, b, c, d, e, f
 
 
+def parse_perspective(text: str):
+    """'x0,y0,x1,y1,x2,y2,x3,y3' -> [(x0, y0), ..., (x3, y3)] as floats; None if it is not eight finite numbers"""
+    try:
+        v = [float(t) for t in text.split(",")]
+    except ValueError:
+        return None
+    if len(v) != 8 or not all(math.isfinite(t) for t in v):
+        return None
+    return [(v[0], v[1]), (v[2], v[3]), (v[4], v[5]), (v[6], v[7])]
+
+
 def main(argv, out=print) -> int:
     ap = argparse.ArgumentParser(prog="qoiwarp_mi355x.py", description=".qoi files as re-oriented or turned PNGs through one qoimi_decode_warped call")
     ap.add_argument("paths", nargs="+", metavar="FILE_OR_DIR")
@@ -76,6 +92,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("--orient", type=int, default=None, metavar="N")
     ap.add_argument("--rotate", type=float, default=None, metavar="DEG")
     ap.add_argument("--scale", type=float, default=1.0, metavar="S")
+    ap.add_argument("--perspective", default=None, metavar="x0,y0,x1,y1,x2,y2,x3,y3")
     ap.add_argument("--size", default=None, metavar="WxH")
     ap.add_argument("--border", choices=tuple(BORDERS), default="fill")
     ap.add_argument("--sample", choices=tuple(SAMPLES) + tuple(VOTE_SAMPLES), default="bilinear")
@@ -87,7 +104,19 @@ def main(argv, out=print) -> int:
         a = ap.parse_args(argv)
     except SystemExit:
         return 2
-    if (a.orient is None) == (a.rotate is None):
+    corners = None
+    if a.perspective is not None:
+        if a.orient is not None or a.rotate is not None or a.scale != 1.0:
+            out("--perspective takes the place of --orient and --rotate and takes no --scale")
+            return 2
+        corners = parse_perspective(a.perspective)
+        if corners is None:
+            out("--perspective must be x0,y0,x1,y1,x2,y2,x3,y3: eight finite numbers")
+            return 2
+        if a.supersample != 1 or a.sample in VOTE_SAMPLES:
+            out("--perspective goes with --sample bilinear, nearest or bicubic and --supersample 1 only")
+            return 2
+    elif (a.orient is None) == (a.rotate is None):
         out("one of --orient N and --rotate DEG")
         return 2
     if a.orient is not None and (a.orient < 1 or a.orient > 8 or a.size is not None or a.scale != 1.0):
@@ -123,14 +152,27 @@ def main(argv, out=print) -> int:
     flags = BORDERS[a.border] | {**SAMPLES, **VOTE_SAMPLES}[a.sample] | SUPERSAMPLES[a.supersample]
     blobs = [open(f, "rb").read() for f in files]
     heads = [parse_header(b) for b in blobs]
-    good, items = [], []
+    good, items, moved = [], [], []
     for i, hd in enumerate(heads):
         if hd is None:
             out(f"{os.path.basename(files[i])}: not a QOI stream, left out")
             continue
         w, h = hd[0], hd[1]
         k = len(good)
-        if a.orient is not None:
+        if corners is not None:
+            ow, oh = size if size is not None else (w, h)
+            try:
+                m, proj, displaced = warp.perspective((w, h), (ow, oh), corners)
+            except ValueError as err:
+                out(f"{os.path.basename(files[i])}: {err}, left out")
+                continue
+            it = warp.item(k, (0, 0, w, h), (ow, oh), m, flags, fill, proj=proj)
+            wrong = warp._wrong(w, h, (0, 0, w, h), (ow, oh), m, it[7], it[13])
+            if wrong:
+                out(f"{os.path.basename(files[i])}: {wrong}, left out")
+                continue
+            moved.append(displaced)
+        elif a.orient is not None:
             it = warp.orient(w, h, (0, 0, w, h), a.orient)
             it = (k,) + it[1:7] + (flags,) + it[8:12] + (fill,) + it[13:]
         else:
@@ -176,7 +218,8 @@ def main(argv, out=print) -> int:
             fh.write(png_io.write_png(px))
         d = descs[k]
         m = items[k]
-        out(f"{os.path.basename(files[i])[-32:]:<32} {f'{d.width}x{d.height}x{d.channels}':>16} {f'{m[8]} {m[9]} / {m[10]} {m[11]}':>32} {f'{ow}x{oh}x{och}':>14}")
+        out(f"{os.path.basename(files[i])[-32:]:<32} {f'{d.width}x{d.height}x{d.channels}':>16} {f'{m[8]} {m[9]} / {m[10]} {m[11]}':>32} {f'{ow}x{oh}x{och}':>14}"
+            + (f"  g h {' '.join(str(v) for v in warp.proj_of(m[13]))}, corners displaced by at most {moved[k]:.6f} source pixels" if corners is not None else ""))
     out(f"total: {len(good)} images, {opos} bytes, {subs} sub-batch{'es' if subs != 1 else ''}")
     return 0 if len(good) == len(files) else 1
 
