@@ -1449,6 +1449,73 @@ struct PipeReaderT {
     }
 };
 
+// LineReader: PipeReader's ring and descriptor with a LINE-granular refill (batch calls at segments of 1 KiB and above).
+// Why: a lane of PipeReader asks for 32 bytes at a time and so comes back to a 128-byte line four times; one line per lane in
+// flight over an XCD's resident lanes is the whole of its L2, the line is gone by the next request and the kernel fetched 2.45 x
+// its streams (EXPERIMENTS.md "the transcoder's stream reads").  Here a lane asks for the whole line in ONE refill - eight
+// 16-byte requests that leave together - into a register set Q of eight u32x4, and moves it into the ring a 32-byte piece at a
+// time; the ring stays 128 bytes per lane (the LDS and the wavefronts per CU stay what they were).
+// The schedule is static, as PipeReader's is: a turn of the loop is kLinePeriods periods; period 0 asks (lanes whose Q is free, under
+// the execution mask: the other lanes keep their pieces), period kLineLand0 + k lands piece k of the lanes that hold it and have
+// 32 bytes of room.  A piece is read kLineLand0 periods behind its request at the earliest, so the wait in front of a landing is
+// for loads that old.  A walk consumes at most 10 bytes per period (two five-byte chunks: QOI_OP_RGBA takes two steps, the run-up
+// of a line lane takes two steps per period); over every such walk the unread bytes never fall below 29 (18 are needed: 10 +
+// the two dwords a peek reads) - tests/test_line_reader_schedule.py searches all of them with these constants.
+constexpr uint32_t kLinePeriods = 7, kLineLand0 = 3;
+struct LineReaderT : PipeReaderT<true> {
+    static constexpr uint32_t kRunupSteps = 2;
+    u32x4 q[8];                // the line on its way / waiting for room: piece k = q[2k], q[2k + 1]
+    uint32_t nxt;              // the next piece to land (0..3), 4: Q is free, 5: the lane never asks (no segment, or out of the descriptor's reach)
+    // as init_desc; the ring takes the 128 bytes from the 32-byte aligned start, Q the rest of the line those end in
+    __device__ __forceinline__ bool init_line(uint32_t ring_addr, const uint8_t* wave_base, unsigned long long wave_bytes, const uint8_t* stream, uint32_t pos0, bool lane_ok,
+                                              const uint8_t* lane_end) {
+        const bool ok = init_desc(ring_addr, wave_base, wave_bytes, stream, pos0, lane_ok, lane_end);
+        const bool reach = boff != idle;
+        const uint32_t k0 = ((uint32_t)reinterpret_cast<uintptr_t>(stream + pos0) >> 5) & 3u;       // the piece of its line that the byte at a + 128 lies in
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t off = (reach && k >= k0) ? boff + 128u + 32u * (k - k0) : idle;
+            q[2u * k] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+            q[2u * k + 1u] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 16u, 0, 0);
+        }
+        nxt = reach ? k0 : 5u;
+        return ok;
+    }
+    template <int T>
+    __device__ __forceinline__ void turn_rel(uint32_t rp) {
+        static_assert(T >= 0 && T < (int)kLinePeriods && kLineLand0 >= 1u && kLineLand0 + 3u < kLinePeriods, "one request period, four landing periods behind it");
+        if (T >= (int)kLineLand0 && T < (int)kLineLand0 + 4) {
+            constexpr uint32_t k = (uint32_t)(T - (int)kLineLand0) & 3u;
+            if (nxt == k && wr - (rp >> 2) <= RD - 8u) {                  // eight dwords neither unread nor in the dword under the cursor
+                lds_u32* w = (lds_u32*)(ring + (wr & (RD - 1u)) * 256u);  // (wr is a multiple of eight: no wrap inside a piece)
+                const u32x4 v0 = q[2u * k], v1 = q[2u * k + 1u];
+                w[0] = v0.x; w[64] = v0.y; w[128] = v0.z; w[192] = v0.w;
+                w[256] = v1.x; w[320] = v1.y; w[384] = v1.z; w[448] = v1.w;
+                if ((wr & (RD - 1u)) == 0u) ((lds_u32*)ring)[RD * 64u] = v0.x;        // mirror of slot 0
+                wr += 8u;
+                nxt = k + 1u;
+            }
+        }
+        if (T == 0) {
+            if (nxt == 4u) {                                              // the whole line the ring ends in front of
+                const uint32_t off = boff + wr * 4u;
+#pragma unroll
+                for (uint32_t i = 0; i < 8u; ++i) q[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 16u * i, 0, 0);
+                nxt = 0u;
+            }
+        }
+    }
+    template <int T>
+    __device__ __forceinline__ void turn(uint32_t pos) { turn_rel<T>(pos - aoff); }
+    // In front of a loop of turns: Q has arrived.  (The compiler counts a load as outstanding per REGISTER: a request of init_line that
+    // no landing has waited for yet would stand on whatever the loop keeps in those registers, and every write to one of them - the
+    // records' store data - would wait for all but the newest memory operations, the loop's own requests included.)
+    __device__ __forceinline__ void settle() {
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; ++i) asm volatile("" : "+v"(q[i]));
+    }
+};
+
 #ifndef QOIMI_TR_WAVES
 #define QOIMI_TR_WAVES 4
 #endif
@@ -1591,13 +1658,17 @@ __device__ __forceinline__ void transcode_scan_tail(const DecParams& p, ScanShar
 // instructions per record, so that dec_scan_entry needs no tail walk.  Measured: what the scan saves the transcoder pays (see there).
 // SPLIT (round 6, DecParams::tr_split): two lanes per segment, each walks half of it from a run-up of its own; the even lane writes
 // the segment's outputs (the odd lane's values come over by a lane shift).
-template <int MODE, bool TRACK = false, bool SPLIT = false, bool SCAN = false>
+// WHICH = 2 (batch calls at segments of 1 KiB and above, launch_decode_parse): MODE 0 with the stream bytes through LineReader.
+template <int WHICH, bool TRACK = false, bool SPLIT = false, bool SCAN = false>
 __global__ __launch_bounds__(kTrThreads) void dec_transcode(DecParams p) {
+    constexpr int MODE = WHICH == 2 ? 0 : WHICH;
+    constexpr bool LINE = WHICH == 2;
     __shared__ uint32_t s_ring[QOIMI_TR_WAVES][TransReader::kSlots * 64];
     __shared__ LdsLutT s_lut;
     __shared__ ScanShared s_scan;
     __shared__ uint32_t s_gb;
     static_assert(!SCAN || (SPLIT && MODE == 0), "the scan rides on the two-lane form of the first transcoder pass");
+    static_assert(!LINE || (MODE == 0 && !SPLIT && !TRACK), "the line reader serves the batch form of the first transcoder pass");
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = lane_id();
     if (MODE == 1 && !p.sync_all && *p.sync_fails == 0u) return;
     if (MODE == 1 && !p.sync_all) {                        // (a workgroup without a flagged segment returns before it builds its table: see dec_parse_fine)
@@ -1654,7 +1725,7 @@ __global__ __launch_bounds__(kTrThreads) void dec_transcode(DecParams p) {
     }
     const uint32_t end = min(base + hbytes, im.chunks_end);
     const uint32_t lut_base = lds_addr_of(&s_lut.e[0]);
-    PipeReaderT<MODE == 0> R;                 // MODE 0: requests through a descriptor; MODE 1 (rare): plain pointers, reaches anything
+    typename std::conditional<LINE, LineReaderT, PipeReaderT<MODE == 0>>::type R;     // MODE 0: requests through a descriptor; MODE 1 (rare): plain pointers, reaches anything
     uint32_t pos;
     bool failed = false;
     const uint8_t* dummy16 = reinterpret_cast<const uint8_t*>(p.sync_fail);     // any 16 readable bytes: what lanes without a request load
@@ -1685,8 +1756,13 @@ __global__ __launch_bounds__(kTrThreads) void dec_transcode(DecParams p) {
         // (base: the first stream aligned DOWN to 32 bytes - the lanes' 32-byte aligned requests then never start in front of it, whatever
         // the alignment of the caller's streams)
         const uintptr_t wave_base = first_stream & ~(uintptr_t)31;
-        const bool reach = R.init_desc(lds_addr_of(&s_ring[wave][lane]), reinterpret_cast<const uint8_t*>(wave_base), (unsigned long long)(last_end - wave_base),
-                                       my_stream, t0, have, reinterpret_cast<const uint8_t*>(my_end));
+        auto reader_init = [&](uint32_t from) {
+            if constexpr (LINE) return R.init_line(lds_addr_of(&s_ring[wave][lane]), reinterpret_cast<const uint8_t*>(wave_base), (unsigned long long)(last_end - wave_base),
+                                                   my_stream, from, have, reinterpret_cast<const uint8_t*>(my_end));
+            else return R.init_desc(lds_addr_of(&s_ring[wave][lane]), reinterpret_cast<const uint8_t*>(wave_base), (unsigned long long)(last_end - wave_base),
+                                    my_stream, from, have, reinterpret_cast<const uint8_t*>(my_end));
+        };
+        const bool reach = reader_init(t0);
         ParseState s; parse_init(s, t0);
         if (from_start) { s.p1 = s.p2 = s.p3 = s.p4 = t0; }
         uint32_t m = t0;
@@ -1694,7 +1770,7 @@ __global__ __launch_bounds__(kTrThreads) void dec_transcode(DecParams p) {
         bool going = have && reach && m < base;
         auto sync_steps = [&]() {
 #pragma unroll
-          for (uint32_t u = 0; u < TransReader::kPeriod; ++u) {
+          for (uint32_t u = 0; u < (LINE ? LineReaderT::kRunupSteps : TransReader::kPeriod); ++u) {      // (LINE: at most ten bytes per period, see LineReader)
             if (going) {
                 uint32_t w32, b5; R.peek(m, w32, b5);
                 const uint32_t b1 = w32 & 0xFFu;
@@ -1709,11 +1785,21 @@ __global__ __launch_bounds__(kTrThreads) void dec_transcode(DecParams p) {
             }
           }
         };
-        while (lanes_where(going)) {                              // three periods per turn of the register sets (PipeReader)
-            R.template turn<0>(m); sync_steps();
-            R.template turn<1>(m); sync_steps();
-            R.template turn<2>(m); sync_steps();
-        }
+        auto sync_walk = [&]() {
+            while (lanes_where(going)) {                          // three periods per turn of the register sets (PipeReader), seven of LineReader's
+                R.template turn<0>(m); sync_steps();
+                R.template turn<1>(m); sync_steps();
+                R.template turn<2>(m); sync_steps();
+                if constexpr (LINE) {
+                    static_assert(kLinePeriods == 7u, "the turns below");
+                    R.template turn<3>(m); sync_steps();
+                    R.template turn<4>(m); sync_steps();
+                    R.template turn<5>(m); sync_steps();
+                    R.template turn<6>(m); sync_steps();
+                }
+            }
+        };
+        sync_walk();
         bool reach2 = true;
         if (kSyncRetryBytes != 0u && lanes_where(have && reach && !merged) != 0ull) {
             // Chains that have not met within the run-up (a Kodak-like 4K photograph: 7 of 67 000 segments at 32 bytes) get ONE more, longer one
@@ -1723,19 +1809,14 @@ __global__ __launch_bounds__(kTrThreads) void dec_transcode(DecParams p) {
             const bool again = have && reach && !merged;
             const bool from_start2 = base <= (uint32_t)kHeaderBytes + kSyncRetryBytes;
             const uint32_t t1 = again ? (from_start2 ? (uint32_t)kHeaderBytes : base - kSyncRetryBytes) : m;
-            reach2 = R.init_desc(lds_addr_of(&s_ring[wave][lane]), reinterpret_cast<const uint8_t*>(wave_base), (unsigned long long)(last_end - wave_base),
-                                 my_stream, t1, have, reinterpret_cast<const uint8_t*>(my_end));
+            reach2 = reader_init(t1);
             if (again) {
                 parse_init(s, t1);
                 if (from_start2) { s.p1 = s.p2 = s.p3 = s.p4 = t1; }
                 m = t1; merged = from_start2;
             }
             going = again && reach2 && m < base;
-            while (lanes_where(going)) {
-                R.template turn<0>(m); sync_steps();
-                R.template turn<1>(m); sync_steps();
-                R.template turn<2>(m); sync_steps();
-            }
+            sync_walk();
         }
         failed = have && (!merged || !reach || !reach2);
         if (SPLIT) {                                          // either half: the whole segment takes the five-phase parse
@@ -1749,6 +1830,7 @@ __global__ __launch_bounds__(kTrThreads) void dec_transcode(DecParams p) {
         if (fails != 0 && lane == (uint32_t)__builtin_ctzll(fails)) atomicAdd(p.sync_fails, (uint32_t)__builtin_popcountll(fails));
     }
     bool active = have && !failed && pos < end;
+    if constexpr (LINE) R.settle();
     // The walk keeps its cursor relative to the ring's origin (rp) and forms the table offset of the byte under it with one
     // SDWA shift: 20 vector instructions per chunk in the common path (23 with an absolute cursor, round 2).
     uint32_t rp = pos - R.aoff;
@@ -1852,6 +1934,12 @@ __global__ __launch_bounds__(kTrThreads) void dec_transcode(DecParams p) {
         R.template turn_rel<0>(rp); granule_steps();
         R.template turn_rel<1>(rp); granule_steps();
         R.template turn_rel<2>(rp); granule_steps();
+        if constexpr (LINE) {
+            R.template turn_rel<3>(rp); granule_steps();
+            R.template turn_rel<4>(rp); granule_steps();
+            R.template turn_rel<5>(rp); granule_steps();
+            R.template turn_rel<6>(rp); granule_steps();
+        }
     }
     pos = rp + R.aoff;
     uint32_t gran_word = (roff - roff0) >> 10;                          // granules written
@@ -2970,7 +3058,9 @@ void launch_decode_parse(const DecParams& p, hipStream_t st, KernelTimer* tm) {
     if (p.total_segs) {
         if (!p.sync_all) {
             // parse + transcode in one walk (dec_transcode<0>); the five-phase parse only for the segments it flags
-            hipLaunchKernelGGL(dec_transcode<0>, dim3((p.total_segs + kTrThreads - 1u) / kTrThreads), dim3(kTrThreads), 0, st, p);
+            // (segments of 1 KiB and above - eight lines and more per lane: every stream line is fetched once, LineReader)
+            if (p.seg_bytes >= 1024u) hipLaunchKernelGGL(dec_transcode<2>, dim3((p.total_segs + kTrThreads - 1u) / kTrThreads), dim3(kTrThreads), 0, st, p);
+            else hipLaunchKernelGGL(dec_transcode<0>, dim3((p.total_segs + kTrThreads - 1u) / kTrThreads), dim3(kTrThreads), 0, st, p);
             tm->mark(kT_dec_slot_walk, st);
             hipLaunchKernelGGL(dec_parse_fine, dim3((p.total_segs * p.fine_per_seg + 255u) / 256u), dim3(256), 0, st, p);
         } else hipLaunchKernelGGL(dec_parse, dim3((p.total_segs + 255u) / 256u), dim3(256), 0, st, p);   // segment sizes without the piece parse: every segment
