@@ -30,7 +30,7 @@ END = bytes([0, 0, 0, 0, 0, 0, 0, 1])
 
 def soup(rng: np.random.Generator, nbytes: int) -> bytes:
     """chunk bytes of one character"""
-    style = int(rng.integers(0, 9))
+    style = int(rng.integers(0, 11))
     if style == 0:                                                    # anything
         return rng.integers(0, 256, size=nbytes, dtype=np.uint8).tobytes()
     if style == 1:                                                    # INDEX on arbitrary slots (most of them never written: zero pixels, or stale ones)
@@ -53,7 +53,18 @@ def soup(rng: np.random.Generator, nbytes: int) -> bytes:
         k = rng.random(nbytes) < 0.02
         b[k] = rng.integers(0, 64, size=int(k.sum()), dtype=np.uint8)
         return b.tobytes()
-    # RGBA with few alpha levels, then INDEX back to them: alpha travels through the colour table
+    if style == 9:                                                    # RGBA chunks whose alpha byte reads as an RGBA tag: the transcoder's five parse chains never meet
+        a = rng.integers(0, 256, size=(nbytes // 5 + 1, 5), dtype=np.uint8); a[:, 0] = a[:, 2] = a[:, 4] = 0xFF
+        return a.tobytes()[:nbytes]
+    if style == 10:                                                   # the same with a one-byte chunk every 25th (period 121) and a chunk behind it on which the chains
+        g = np.empty((nbytes // 121 + 1, 121), dtype=np.uint8)        # meet: the 64-byte run-up often holds no such place, the 192-byte one always does (tests/chain_model.py)
+        c = g[:, :120].reshape(-1, 24, 5)
+        c[:, :, 0] = c[:, :, 2] = c[:, :, 4] = 0xFF
+        c[:, :, 1] = rng.integers(0, 0x80, size=c.shape[:2]); c[:, :, 3] = rng.integers(0xC0, 0xFE, size=c.shape[:2])
+        c[:, 0, 1] = 0xFE; c[:, 0, 2] = rng.integers(0, 0x80, size=len(g)); c[:, 0, 3] = rng.integers(0x80, 0xC0, size=len(g)); c[:, 0, 4] = rng.integers(0x40, 0x80, size=len(g))
+        g[:, 120] = rng.integers(0x40, 0x80, size=len(g))
+        return g.tobytes()[:nbytes]
+    # (style 8) RGBA with few alpha levels, then INDEX back to them: alpha travels through the colour table
     out = bytearray()
     while len(out) < nbytes:
         if rng.random() < 0.3:
