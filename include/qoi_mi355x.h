@@ -309,6 +309,42 @@ int qoimi_encode_images_packed(qoimi_ctx *ctx, const void *d_pixels, const size_
  * a vote over blocks above 16 x 16, a vote per channel, a mode per tile, QOIMI_TILE_NEAREST / QOIMI_TILE_MODE in qoimi_decode_thumbnails
  * (qoimi_decode_tensors serves them), row-pitched sources, a channel count per tile. */
 enum { QOIMI_TILE_NEAREST = 4, QOIMI_TILE_MODE = 5 };   /* 2 and 3 are not modes */
+/* Tensors as the source (qoimi_tile.flags beside the two flips; accepted by qoimi_encode_tiles and qoimi_tile_size).  The two formats an
+ * image really has on a device are a uint8 C x H x W tensor and a model's float output; with these bits the gather kernel converts them on
+ * its way into the encoder's staging, and the caller runs no conversion passes and owns no interleaved u8 copy.
+ *   QOIMI_TILE_SRC            the image this tile names is a TENSOR in the format the bits below give (none: u8, HWC - what it is without)
+ *   QOIMI_TILE_SRC_CHW        planar: element (c, Y, X) at element index (c * h + Y) * w + X; without it HWC: (Y * w + X) * sch + c
+ *   QOIMI_TILE_SRC_F16 / _BF16 / _F32   the dtype field, bits 6-7: QOIMI_TENSOR_U8 / _F16 / _BF16 / _F32 << 6 (element sizes 1 / 2 / 2 / 4)
+ *   QOIMI_TILE_SRC_SYMMETRIC / _BYTES   the range field, bits 8-9, floats only.  0: UNIT, the element is in [0, 1]; SYMMETRIC: in [-1, 1];
+ *                             BYTES: the element already is 0..255; 768 is not a range
+ * descs[image] gives w, h and sch = 3 or 4 ELEMENTS per pixel (planes for CHW); pixel_offsets[image] stays a BYTE offset; the image takes
+ * w * h * sch * element size bytes.  The conversion (normative; qoi_amd/tiles.py: convert states it in Python; qoi_amd/csrc/qoi_ingest_core.h
+ * is the kernel's).  x is the element widened exactly to binary32 (binary16 and bfloat16 widen without rounding).
+ *   UNIT       t = x * 255.0f, rounded to binary32
+ *   SYMMETRIC  m = x * 127.5f, rounded; t = m + 127.5f, rounded: TWO roundings, never a fused multiply-add - the convention of qoimi_decode_tensors
+ *   BYTES      t = x
+ *   U8         the byte is the element
+ * The byte is 0 if t is NaN or t <= 0 (which covers -inf and -0.0), 255 if t >= 255 (which covers +inf), otherwise t rounded to the nearest
+ * integer, ties to even.  Every channel, alpha included, goes through the same conversion.  Whether subnormals are flushed cannot change a
+ * byte: |t| < 0.5 gives 0 either way.  Let B be the h x w x sch byte image this defines: the tile is what qoimi_encode_tiles gives for B
+ * without the bits - the rectangle, the flips, the conversion to och (4 to 3 drops alpha, 3 to 4 sets 255), the reference encoder's stream
+ * byte for byte, the pack, the tables, the capacity rules, the staging plan and the slots.  No size changes.  At factor 1 all four values
+ * of `mode` give the same bytes, as they do without the bits.  Of an image nothing is read but whole, naturally aligned elements (u8: the
+ * aligned 4-byte words that hold one of its bytes); nothing of the caller's is written.
+ * Limits, each QOIMI_E_ARG before anything is launched with the caller's buffers untouched, looked at per tile behind the checks above, in
+ * this order: a SRC_* bit without QOIMI_TILE_SRC; range 768; a non-zero range with dtype U8; factor != 1 on a SRC tile; then, over the
+ * call: some but not all tiles carry QOIMI_TILE_SRC (a call is a byte call or a tensor call; QOIMI_TILE_SRC alone marks a u8 HWC image
+ * inside a tensor call, so formats still mix per image); two tiles that name the same image with different source bits; d_pixels +
+ * pixel_offsets[image] not a multiple of the element size; the address-space and pack-overlap checks above, taken over the image's extent
+ * in BYTES; a sub-batch of the plan with 2^31 - 1 or more tiles of 256 work items of the kernel (an item is four consecutive pixels of a
+ * tile's output).  A tensor call runs a gather kernel of its own over the same table; qoimi_tile_stats counts its launches in [1].
+ * Properties (qoi_amd/tiles.py asserts them).  A call whose tiles all carry QOIMI_TILE_SRC alone gives the pack of the same call without
+ * the bit, byte for byte.  Round trip: for every byte v and each of F32, F16 and BF16, the element qoimi_decode_tensors writes for v
+ * converts back to v with scale 1/255, bias 0 and UNIT; scale 2/255, bias -1 and SYMMETRIC; scale 1, bias 0 and BYTES.
+ * Not here (of tensor sources): box, selection and vote over them (factor 1 only: convert once at factor 1, or decode the pack), integer
+ * dtypes other than u8, a scale and bias of the caller's, one-plane (HW) sources, row-pitched tensors. */
+enum { QOIMI_TILE_SRC = 16, QOIMI_TILE_SRC_CHW = 32, QOIMI_TILE_SRC_F16 = 64, QOIMI_TILE_SRC_BF16 = 128, QOIMI_TILE_SRC_F32 = 192,
+       QOIMI_TILE_SRC_SYMMETRIC = 256, QOIMI_TILE_SRC_BYTES = 512 };   /* bits 2, 3 and 10 up stay unknown flag bits */
 typedef struct {                 /* 32 bytes, offsets 0/4/8/12/16/20/24/28 */
     unsigned int image;          /* index into the call's images */
     unsigned int x, y;           /* top-left corner of the source rectangle */
@@ -1012,7 +1048,7 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * Not here: indexed forms, a majority (mode) filter per channel, with weights or over cells above 16 x 16 (QOIMI_FILTER_MODE votes on whole
  * pixels of cells up to that; the warp has QOIMI_WARP_VOTE2 / QOIMI_WARP_VOTE4), 16-bit or signed label sources (a label is a byte of the image), a remapping table from byte to class index, a single
  * 8-byte store per QOIMI_TENSOR_I64 element (it is two dword stores), a u8 entry point or a stats function of the bicubic, the Lanczos, the nearest or the mode filter's own, other cubic kernels (a = -3/4), other Lanczos windows, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
- * size of its rectangle, or divides it, is those), tensors as the source of an encode (qoimi_encode_tiles takes bytes). */
+ * size of its rectangle, or divides it, is those). */
 enum { QOIMI_TENSOR_U8 = 0, QOIMI_TENSOR_F16 = 1, QOIMI_TENSOR_BF16 = 2, QOIMI_TENSOR_F32 = 3 };   /* element sizes 1 / 2 / 2 / 4 */
 enum { QOIMI_TENSOR_I32 = 5, QOIMI_TENSOR_I64 = 6 };   /* element sizes 4 / 8; 4 is not a dtype */
 enum { QOIMI_TENSOR_HWC = 0, QOIMI_TENSOR_CHW = 1, QOIMI_TENSOR_HW = 3 };   /* 2 is not a layout */

@@ -498,7 +498,9 @@ class Context:
         tiles: ``QoimiTile`` structures or (image, x, y, width, height, factor[, flags]) tuples; mode: ``tiles.PLAIN`` /
         ``tiles.ALPHA_WEIGHTED`` (the box average) or, for label maps, ``tiles.NEAREST`` (the centre pixel of every block) / ``tiles.MODE`` (the
         majority vote of ``FILTER_MODE`` over every block; factor <= 16); channels 0: every tile keeps its image's channel count;
-        ``qoi_amd/tiles.py: tile`` states the pixels."""
+        ``qoi_amd/tiles.py: tile`` states the pixels.  With ``tiles.source_flags(dtype, layout, range)`` in every tile's flags the images are
+        tensors - u8 / f16 / bf16 / f32, HWC or CHW, factor 1 - converted on the way in (``tiles.convert``); pixel_offsets stay byte offsets
+        (``tiles.source_bytes`` an image; d_pixels is an address: no length of it is looked at here)."""
         n_images = len(descs)
         seqs = self._per_image("encode_tiles", "pixel offset per descriptor", n_images, pixel_offsets=pixel_offsets, descs=descs)
         shortest, longest, noun, malformed = _ITEMS[QoimiTile]

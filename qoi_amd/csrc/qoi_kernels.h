@@ -362,6 +362,8 @@ struct TileEntry;
 void launch_tile_gather(const uint8_t* pixels, const TileEntry* tab, uint32_t m, uint32_t tiles, uint8_t* stage, uint32_t grid, hipStream_t st);
 // tile_select: the same over a table of QOIMI_TILE_NEAREST / QOIMI_TILE_MODE entries (tile_select_cfg, tile_select_tiles)
 void launch_tile_select(const uint8_t* pixels, const TileEntry* tab, uint32_t m, uint32_t tiles, uint8_t* stage, uint32_t grid, hipStream_t st);
+// tensor_ingest: the same over a table of QOIMI_TILE_SRC entries - tensor sources (qoi_ingest.hip; ingest_cfg, ingest_tiles: qoi_ingest_core.h)
+void launch_tensor_ingest(const uint8_t* pixels, const TileEntry* tab, uint32_t m, uint32_t tiles, uint8_t* stage, uint32_t grid, hipStream_t st);
 
 // ---- row seek index (qoi_seek.hip; the arithmetic: qoi_seek_core.h) ------------------
 struct SeekPoint;                                       // = qoimi_seek_point (qoi_seek_core.h)

@@ -26,6 +26,19 @@ The modes change no size: ``size`` and ``plan`` take no mode.
 
 The work items of the kernel tile_select, which these two modes run in the place of tile_gather: ``select_split`` and ``select_tiles`` below.
 
+Tensors as the source (``SRC`` and the bits beside it in a tile's flags; ``source_flags`` builds them).  The image a tile names then is a
+tensor: uint8, float16, bfloat16 or float32, ``[h, w, sch]`` (HWC) or ``[sch, h, w]`` (``SRC_CHW``), tightly packed at a byte offset that is a
+multiple of the element size.  ``convert`` states the byte image B it stands for: x is the element widened exactly to float32; ``UNIT``
+``t = x * 255``; ``SYMMETRIC`` ``m = x * 127.5`` rounded, ``t = m + 127.5`` rounded - two roundings, the convention of ``tensors.convert``;
+``BYTES`` ``t = x``; the byte is 0 if t is NaN or t <= 0, 255 if t >= 255, else t rounded to the nearest integer, ties to even; a uint8
+element is the byte; alpha goes the same way.  Whether subnormals are flushed cannot change a byte: ``|t| < 0.5`` gives 0 either way.  The
+tile is the tile of B without the source bits - the rectangle, the flips, och - at factor 1 only, where all four modes agree; sizes, slots and
+the plan do not change.  A call is a byte call or a tensor call (``SRC`` alone marks a u8 HWC image inside a tensor call) and an image has one
+format.  Two properties, asserted by tests/test_ingest_model.py: a tile with ``SRC`` alone is the tile without it, and for every byte v and
+each of F32, F16 and BF16 the element ``tensors.convert`` writes for v converts back to v - scale 1/255 and bias 0 with ``UNIT``, scale 2/255
+and bias -1 with ``SYMMETRIC``, scale 1 and bias 0 with ``BYTES``.  The work items of the kernel tensor_ingest, which a tensor call runs in
+the place of tile_gather: ``ingest_items`` and ``ingest_tiles`` - four consecutive output pixels an item.
+
 The plan: tile j's slot is ``tw * th * och`` rounded up to 256 plus the encode bound of its descriptor rounded up to 256; sub-batches are cut
 by ``packplan.plan`` over those slots, in tile order.
 """
@@ -43,6 +56,17 @@ NEAREST = 4                     # QOIMI_TILE_NEAREST (2 and 3 are not modes)
 MODE = 5                        # QOIMI_TILE_MODE
 MAX_FACTOR = thumbs.MAX_FACTOR
 MODE_MAX_FACTOR = _mode.MAX_RATIO   # a block votes over at most 16 x 16 pixels
+SRC = 16                        # QOIMI_TILE_SRC: the image is a tensor in the format the bits below give (none: u8, HWC)
+SRC_CHW = 32                    # QOIMI_TILE_SRC_CHW
+SRC_F16, SRC_BF16, SRC_F32 = 64, 128, 192       # QOIMI_TILE_SRC_F16 / _BF16 / _F32: the dtype field, bits 6-7
+SRC_SYMMETRIC, SRC_BYTES = 256, 512             # QOIMI_TILE_SRC_SYMMETRIC / _BYTES: the range field, bits 8-9 (768 is not a range)
+SRC_MASK = SRC | SRC_CHW | SRC_F32 | 768
+U8, F16, BF16, F32 = 0, 1, 2, 3                 # QOIMI_TENSOR_U8 .. _F32
+HWC, CHW = 0, 1
+UNIT, SYMMETRIC, BYTES = 0, SRC_SYMMETRIC, SRC_BYTES
+ELEM = {U8: 1, F16: 2, BF16: 2, F32: 4}
+SOURCE_ARRAYS = {U8: np.uint8, F16: np.float16, BF16: np.uint16, F32: np.float32}     # (NumPy has no bfloat16: its bits)
+INGEST_PIXELS = 4               # output pixels of a work item of tensor_ingest
 THREADS = 256                   # work items of a tile of the gather kernels
 MAX_LEVELS = 7
 MAX_TILE_SIDE = 1 << 24
@@ -76,10 +100,106 @@ def size(w: int, h: int, sch: int, t, channels: int = 0) -> Tuple[int, int, int]
     _, x, y, cw, ch, f, flags, reserved = fields(t)
     if not _desc_ok(w, h, sch) or channels not in (0, 3, 4):
         return 0, 0, 0
-    if cw < 1 or ch < 1 or x < 0 or y < 0 or x + cw > w or y + ch > h or not 1 <= f <= MAX_FACTOR or (flags & ~(FLIP_X | FLIP_Y)) or reserved:
+    if cw < 1 or ch < 1 or x < 0 or y < 0 or x + cw > w or y + ch > h or not 1 <= f <= MAX_FACTOR or (flags & ~(FLIP_X | FLIP_Y | SRC_MASK)) or reserved:
+        return 0, 0, 0
+    if source_wrong(flags, f):
         return 0, 0, 0
     tw, th = thumbs.size(cw, ch, f)
     return tw * th * (channels or sch), tw, th
+
+
+# ---------------------------------------------------------------------------------- tensors as the source (QOIMI_TILE_SRC*)
+def source_flags(dtype: int = U8, layout: int = HWC, range: int = UNIT) -> int:
+    """The bits of ``qoimi_tile.flags`` for a tensor source: dtype ``U8`` / ``F16`` / ``BF16`` / ``F32``, layout ``HWC`` / ``CHW``, range ``UNIT``
+    / ``SYMMETRIC`` / ``BYTES`` (floats only; a u8 source takes ``UNIT``, which is no bit).  Or them to a tile's flips."""
+    if dtype not in (U8, F16, BF16, F32) or layout not in (HWC, CHW) or range not in (UNIT, SYMMETRIC, BYTES) or (dtype == U8 and range != UNIT):
+        raise ValueError("source_flags: no such format")
+    return SRC | (SRC_CHW if layout == CHW else 0) | (dtype << 6) | range
+
+
+def source_format(flags: int) -> Tuple[int, int, int]:
+    """(dtype, layout, range) of a tile's flags (the flips and ``SRC`` itself are not looked at)."""
+    return (flags >> 6) & 3, CHW if flags & SRC_CHW else HWC, flags & (3 << 8)
+
+
+def source_wrong(flags: int, factor: int = 1) -> str:
+    """"" if the flags are those of a byte tile or of a tensor tile the calls accept, else what is wrong - in the order the calls look."""
+    src = flags & SRC_MASK
+    if not src:
+        return ""
+    dtype, _, rng = source_format(src)
+    if not src & SRC:
+        return "a SRC_* bit without SRC"
+    if rng == 768:
+        return "768 is not a range"
+    if rng != UNIT and dtype == U8:
+        return "a range with a u8 source"
+    if factor != 1:
+        return "a tensor source takes factor 1 only"
+    return ""
+
+
+def source_bytes(w: int, h: int, sch: int, flags: int) -> int:
+    """Bytes the image takes behind its ``pixel_offsets`` entry: ``w * h * sch`` elements of its dtype (a byte tile: of one byte)."""
+    return w * h * sch * ELEM[source_format(flags)[0]]
+
+
+def widen(A: np.ndarray, dtype: int) -> np.ndarray:
+    """The elements as float32, exactly: float16 and the uint16 bits of a bfloat16 widen without rounding."""
+    A = np.asarray(A)
+    want = SOURCE_ARRAYS[dtype]
+    if A.dtype != want:
+        raise ValueError("widen: the array of this dtype is " + np.dtype(want).name)
+    if dtype == BF16:
+        return (A.astype(np.uint32) << 16).view(np.float32)
+    return A.astype(np.float32)
+
+
+def to_bytes(x: np.ndarray, range: int) -> np.ndarray:
+    """float32 elements -> uint8: ``t = x * 255`` (``UNIT``), ``t = x * 127.5`` and then ``+ 127.5``, each rounded to float32 (``SYMMETRIC``),
+    ``t = x`` (``BYTES``); 0 where t is NaN or t <= 0, 255 where t >= 255, else t rounded to the nearest integer, ties to even."""
+    x = np.asarray(x, np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        if range == UNIT:
+            t = x * np.float32(255.0)
+        elif range == SYMMETRIC:
+            m = x * np.float32(127.5)
+            t = m + np.float32(127.5)
+        elif range == BYTES:
+            t = x
+        else:
+            raise ValueError("to_bytes: no such range")
+        assert t.dtype == np.float32
+        out = np.zeros(t.shape, np.uint8)
+        mid = (t > 0) & (t < 255)                                      # (NaN is in neither)
+        out[mid] = np.rint(t[mid]).astype(np.uint8)
+        out[t >= 255] = 255
+    return out
+
+
+def convert(A: np.ndarray, flags: int) -> np.ndarray:
+    """The tensor A - [h, w, sch] (HWC) or [sch, h, w] (CHW) of uint8 / float16 / uint16 holding bfloat16 bits / float32 - in the format the
+    source bits of `flags` give -> B uint8[h, w, sch]: the byte image the tile is taken from."""
+    what = source_wrong(flags)
+    if what:
+        raise ValueError("convert: " + what)
+    dtype, layout, rng = source_format(flags)
+    A = np.asarray(A)
+    if A.ndim != 3 or A.shape[0 if layout == CHW else 2] not in (3, 4) or A.dtype != SOURCE_ARRAYS[dtype]:
+        raise ValueError("convert: A is [h, w, 3 or 4] (HWC) or [3 or 4, h, w] (CHW) of " + np.dtype(SOURCE_ARRAYS[dtype]).name)
+    if layout == CHW:
+        A = np.transpose(A, (1, 2, 0))
+    return np.ascontiguousarray(A if dtype == U8 else to_bytes(widen(A, dtype), rng))
+
+
+def ingest_items(cw: int, ch: int) -> int:
+    """Work items of a tile of a tensor call (the kernel tensor_ingest): one per ``INGEST_PIXELS`` = 4 consecutive pixels of its output."""
+    return -(-cw * ch // INGEST_PIXELS)
+
+
+def ingest_tiles(cw: int, ch: int) -> int:
+    """Tiles of 256 work items of a tile of a tensor call."""
+    return -(-ingest_items(cw, ch) // THREADS)
 
 
 def select(R: np.ndarray, f: int, mode: int) -> np.ndarray:
@@ -107,11 +227,18 @@ def select(R: np.ndarray, f: int, mode: int) -> np.ndarray:
 
 
 def tile(S: np.ndarray, t, channels: int = 0, mode: int = PLAIN) -> np.ndarray:
-    """S uint8[h, w, sch] (sch 3 or 4), t a tile of it -> uint8[th, tw, och]: the pixels stream j encodes."""
+    """S uint8[h, w, sch] (sch 3 or 4), t a tile of it -> uint8[th, tw, och]: the pixels stream j encodes.  A tile with ``SRC`` takes S as the
+    tensor its flags describe (``convert`` states the bytes B it stands for) and is the tile of B without the source bits."""
+    _, x, y, cw, ch, f, flags, reserved = fields(t)
+    if flags & SRC_MASK:
+        S = convert(S, flags)                                          # (raises where the bits are no format)
+        t = (0, x, y, cw, ch, f, flags & ~SRC_MASK, reserved)
+        flags &= ~SRC_MASK
+        if f != 1:
+            raise ValueError("tile: a tensor source takes factor 1 only")
     S = np.asarray(S)
     if S.ndim != 3 or S.shape[2] not in (3, 4) or S.dtype != np.uint8:
         raise ValueError("tile: S must be uint8[h, w, 3 or 4]")
-    _, x, y, cw, ch, f, flags, _ = fields(t)
     if size(S.shape[1], S.shape[0], S.shape[2], t, channels)[0] == 0:
         raise ValueError("tile: the tile or the channel count is one qoimi_encode_tiles rejects")
     R = S[y:y + ch, x:x + cw]
@@ -162,6 +289,11 @@ def plan(descs: Sequence, tiles: Sequence, channels: int, staging_bytes: int):
     (``packplan.plan`` over the slots; staging_bytes 0: 1 GiB), the bytes of the largest sub-batch - what ``qoimi_tile_stats`` reports as [2];
     ``len(subs)`` is [0] and [1] - and the number of images the tiles name: [3].  descs: ``QoiDesc`` or (w, h, channels) per image."""
     slots, named = [], set()
+    srcs = [fields(t)[6] & SRC_MASK for t in tiles]
+    if any(srcs) and not all(srcs):
+        raise ValueError("plan: a call is a byte call or a tensor call")
+    if len({(fields(t)[0], s) for t, s in zip(tiles, srcs)}) != len({fields(t)[0] for t in tiles}):
+        raise ValueError("plan: an image is named with two source formats")
     for t in tiles:
         image = fields(t)[0]
         d = descs[image]
