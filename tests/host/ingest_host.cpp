@@ -17,35 +17,47 @@ namespace {
 
 // The kernel's memory with every address checked.  A load of a float image is one or more whole elements: aligned to its own size and
 // inside the image.  A 4-byte load of a u8 image is aligned and holds at least one byte of the image; no other load of it is allowed.  A
-// store is aligned dwords inside the slot.
+// store is aligned dwords inside the slot.  Every access is counted by its kind in n[]; with touch == false the addresses are virtual: they
+// are checked and counted, loads give 0 and stores are dropped (ingest_host_paths).
+enum { kLoad2, kLoad4, kLoad8, kLoad16, kStore4, kStore12, kStore16, kKinds };
 struct HostMem {
     uint64_t img_lo, img_hi, out_lo, out_hi;
     uint32_t elem;
+    bool touch = true;
     mutable int bad = 0;
+    mutable uint64_t n[kKinds] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
     bool inside(uint64_t a, uint32_t n) const { return elem != 1u && n >= elem && (a % n) == 0u && a >= img_lo && a + n <= img_hi; }
     uint32_t load2(uint64_t a) const {
+        ++n[kLoad2];
         if (!inside(a, 2u)) { bad |= 1; return 0u; }
+        if (!touch) return 0u;
         uint16_t v; memcpy(&v, (const void*)(uintptr_t)a, 2); return v;
     }
     uint32_t load4(uint64_t a) const {
+        ++n[kLoad4];
         if (elem == 1u ? ((a & 3u) != 0u || a + 4u <= img_lo || a >= img_hi) : !inside(a, 4u)) { bad |= 1; return 0u; }
+        if (!touch) return 0u;
         uint32_t v; memcpy(&v, (const void*)(uintptr_t)a, 4); return v;
     }
     void load8(uint64_t a, uint32_t (&W)[2]) const {
-        if (!inside(a, 8u)) { bad |= 2; W[0] = W[1] = 0u; return; }
-        memcpy(W, (const void*)(uintptr_t)a, 8);
+        ++n[kLoad8];
+        W[0] = W[1] = 0u;
+        if (!inside(a, 8u)) { bad |= 2; return; }
+        if (touch) memcpy(W, (const void*)(uintptr_t)a, 8);
     }
     void load16(uint64_t a, uint32_t (&W)[4]) const {
-        if (!inside(a, 16u)) { bad |= 2; W[0] = W[1] = W[2] = W[3] = 0u; return; }
-        memcpy(W, (const void*)(uintptr_t)a, 16);
+        ++n[kLoad16];
+        W[0] = W[1] = W[2] = W[3] = 0u;
+        if (!inside(a, 16u)) { bad |= 2; return; }
+        if (touch) memcpy(W, (const void*)(uintptr_t)a, 16);
     }
     void store(uint64_t a, const uint32_t* W, uint32_t n, uint32_t align) const {
         if ((a % align) != 0u || a < out_lo || a + n > out_hi) { bad |= 4; return; }
-        memcpy((void*)(uintptr_t)a, W, n);
+        if (touch) memcpy((void*)(uintptr_t)a, W, n);
     }
-    void store4(uint64_t a, uint32_t v) const { store(a, &v, 4u, 4u); }
-    void store12(uint64_t a, const uint32_t (&W)[3]) const { store(a, W, 12u, 4u); }
-    void store16(uint64_t a, const uint32_t (&W)[4]) const { store(a, W, 16u, 16u); }
+    void store4(uint64_t a, uint32_t v) const { ++n[kStore4]; store(a, &v, 4u, 4u); }
+    void store12(uint64_t a, const uint32_t (&W)[3]) const { ++n[kStore12]; store(a, W, 12u, 4u); }
+    void store16(uint64_t a, const uint32_t (&W)[4]) const { ++n[kStore16]; store(a, W, 16u, 16u); }
 };
 
 template <uint32_t DT>
@@ -55,24 +67,17 @@ void item(const HostMem& mem, const qoimi::TileEntry& e, uint64_t base, uint64_t
     else { if (sch == 4u) qoimi::ingest_item<DT, false, 4u>(mem, e, base, q, k); else qoimi::ingest_item<DT, false, 3u>(mem, e, base, q, k); }
 }
 
-}  // namespace
-
-extern "C" {
-
-// One tile, item by item and tile by tile as tensor_ingest numbers them.  img: the tensor's first byte (a multiple of the element size; 16
-// readable bytes in front of it and behind it); src_flags: QOIMI_TILE_SRC*; out: 256-aligned, (cw * ch * och rounded up to 256) bytes.
-// Returns the tiles walked, or -(bits) where an address was wrong (1: an element load, 2: a wide load, 4: a store).
-long long ingest_host_run(const uint8_t* img, uint32_t w, uint32_t h, uint32_t sch, uint32_t src_flags, uint32_t x, uint32_t y, uint32_t cw, uint32_t ch,
-                          uint32_t flags, uint32_t och, uint8_t* out) {
+// The walk of one tile over the memory at `base` (the image) and q (the slot); touch: the addresses are real.
+long long walk(uint64_t base, uint64_t q, bool touch, uint32_t w, uint32_t h, uint32_t sch, uint32_t src_flags, uint32_t x, uint32_t y, uint32_t cw, uint32_t ch,
+               uint32_t flags, uint32_t och, uint64_t* counts) {
     qoimi::TileEntry e;
     memset(&e, 0, sizeof e);
     e.w = w; e.x = x; e.y = y; e.cw = cw; e.ch = ch; e.tw = cw; e.th = ch;
     e.f = h;                                                                  // (an ingest entry holds the image's height there)
     e.cfg = qoimi::ingest_cfg(src_flags, sch, och, flags);
     const uint32_t dtype = qoimi::ingest_dtype(src_flags), elem = qoimi::ingest_elem(dtype);
-    const uint64_t base = (uint64_t)(uintptr_t)img, q = (uint64_t)(uintptr_t)out;
     const size_t slot = ((size_t)cw * ch * och + 255u) & ~(size_t)255u;
-    HostMem mem = {base, base + (uint64_t)w * h * sch * elem, q, q + slot, elem};
+    HostMem mem = {base, base + (uint64_t)w * h * sch * elem, q, q + slot, elem, touch};
     const uint64_t items = qoimi::ingest_items(cw, ch), tiles = qoimi::ingest_tiles(cw, ch);
     for (uint64_t t = 0; t < tiles; ++t)
         for (uint32_t lane = 0; lane < qoimi::kTileThreads; ++lane) {
@@ -85,7 +90,30 @@ long long ingest_host_run(const uint8_t* img, uint32_t w, uint32_t h, uint32_t s
                 default:                 item<qoimi::kIngestF32>(mem, e, base, q, (uint32_t)k); break;
             }
         }
+    if (counts) memcpy(counts, mem.n, sizeof mem.n);
     return mem.bad ? -(long long)mem.bad : (long long)tiles;
+}
+
+}  // namespace
+
+extern "C" {
+
+// One tile, item by item and tile by tile as tensor_ingest numbers them.  img: the tensor's first byte (a multiple of the element size; 16
+// readable bytes in front of it and behind it); src_flags: QOIMI_TILE_SRC*; out: 256-aligned, (cw * ch * och rounded up to 256) bytes.
+// Returns the tiles walked, or -(bits) where an address was wrong (1: an element load, 2: a wide load, 4: a store).
+long long ingest_host_run(const uint8_t* img, uint32_t w, uint32_t h, uint32_t sch, uint32_t src_flags, uint32_t x, uint32_t y, uint32_t cw, uint32_t ch,
+                          uint32_t flags, uint32_t och, uint8_t* out) {
+    return walk((uint64_t)(uintptr_t)img, (uint64_t)(uintptr_t)out, true, w, h, sch, src_flags, x, y, cw, ch, flags, och, nullptr);
+}
+
+// The same walk over virtual addresses - no memory is touched, so the image may be of any legal size: the image at an address that is
+// base_mod modulo 256 (a multiple of the element size), the slot at a multiple of 256.  counts[7]: the loads of 2, 4, 8 and 16 bytes and the
+// stores of 4, 12 and 16 bytes the tile makes - which branches of ingest_item, ingest_pixel and ingest_load_run it reaches.  Returns as
+// ingest_host_run does; -8: base_mod is no address of an element.
+long long ingest_host_paths(uint32_t w, uint32_t h, uint32_t sch, uint32_t src_flags, uint32_t x, uint32_t y, uint32_t cw, uint32_t ch, uint32_t flags,
+                            uint32_t och, uint32_t base_mod, uint64_t* counts) {
+    if (base_mod >= 256u || base_mod % qoimi::ingest_elem(qoimi::ingest_dtype(src_flags)) != 0u) return -8;
+    return walk(((uint64_t)1 << 40) + base_mod, (uint64_t)1 << 44, false, w, h, sch, src_flags, x, y, cw, ch, flags, och, counts);
 }
 
 uint64_t ingest_host_tiles(uint32_t cw, uint32_t ch) { return qoimi::ingest_tiles(cw, ch); }

@@ -1,17 +1,19 @@
 """Tensors as the source of qoimi_encode_tiles on the GPU (-m gpu): u8 / f16 / bf16 / f32 tensors, interleaved or planar, converted by the
 kernel tensor_ingest on their way into the encoder.  A tile's pixels are those of qoi_amd/tiles.py: convert and tile, its stream is the
 reference encoder's stream of them, byte for byte, and the pack is laid out by the numpy model of tests/test_packed_api.py - the checks of
-tests/test_gpu_encode_tiles.py: run, which this file reuses as it is."""
+tests/test_gpu_encode_tiles.py: run, which this file reuses as it is.  The tensors stand at two placements: 1 or 3 elements behind a
+16-byte boundary (the element-by-element loads), and at multiples of 256, where torch hands a tensor over (the 8- and 16-byte loads of a
+four-element HWC pixel and of a CHW run).  The shapes, formats, placements and tiles are those of tests/ingest_cases.py, which
+tests/test_ingest_paths.py replays on the CPU."""
 import numpy as np
 import pytest
 
+import ingest_cases
+from ingest_cases import ALIGNED, FORMATS, ODD
 from qoi_amd import tensors, tiles
 from test_gpu_encode_tiles import FILL, Sources, api, ctx, dev, oracle, run  # noqa: F401  (api, ctx and oracle are fixtures)
 
 pytestmark = pytest.mark.gpu
-SHAPES = [(1, 1), (5, 3), (37, 23), (70, 9), (300, 17)]
-FORMATS = [(d, l, r) for d in (tiles.U8, tiles.F16, tiles.BF16, tiles.F32) for l in (tiles.HWC, tiles.CHW)
-           for r in ((tiles.UNIT,) if d == tiles.U8 else (tiles.UNIT, tiles.SYMMETRIC, tiles.BYTES))]
 SPECIALS = [np.nan, np.inf, -np.inf, -0.0, 1e30, -1e30, 65504.0]
 
 
@@ -27,16 +29,16 @@ def elements(rng, count, dtype, rng_bits):
 
 
 class Tensors:
-    """Tensors of different formats in one device buffer, each at an element-aligned byte offset that is no multiple of 16; the interface of
+    """Tensors of different formats in one device buffer, each at an element-aligned byte offset that is no multiple of 16 - or, how=ALIGNED,
+    each at a multiple of 256; how may name a placement per tensor (ingest_cases.offsets) -; the interface of
     test_gpu_encode_tiles.Sources as far as run looks at it (d, off, descs).  specs: (w, h, sch, (dtype, layout, range), elements or None)."""
 
-    def __init__(self, api, specs, seed=7):
+    def __init__(self, api, specs, seed=7, how=ODD):
         rng = np.random.default_rng(seed)
-        self.off, self.flags, self.arrays, self.descs, parts, cur = [], [], [], [], [], 0
+        self.off, self.flags, self.arrays, self.descs, parts = [], [], [], [], []
+        placed, cur = ingest_cases.offsets(specs, how)                      # ODD: 1 or 3 elements behind a 16-byte boundary
         for i, (w, h, sch, fmt, given) in enumerate(specs):
-            elem = tiles.ELEM[fmt[0]]
-            off = (cur + 15) // 16 * 16 + elem * (1 + 2 * (i & 1))          # 1 or 3 elements behind a 16-byte boundary
-            assert off % elem == 0 and off % 16 != 0
+            off = placed[i]
             a = np.ascontiguousarray(elements(rng, w * h * sch, fmt[0], fmt[2]) if given is None else given)
             assert a.size == w * h * sch and a.dtype == tiles.SOURCE_ARRAYS[fmt[0]]
             self.arrays.append(a.reshape((sch, h, w) if fmt[1] == tiles.CHW else (h, w, sch)))
@@ -44,12 +46,12 @@ class Tensors:
             self.flags.append(tiles.source_flags(*fmt))
             self.descs.append(api.QoiDesc(w, h, sch, i & 1))
             parts.append((off, a.view(np.uint8).reshape(-1)))
-            cur = off + a.nbytes
         self.host = rng.integers(0, 256, size=cur + 64, dtype=np.uint8)
         for off, b in parts:
             self.host[off:off + b.size] = b
         self.d = dev(self.host)
         assert self.d.data_ptr() % 256 == 0
+        self.specs = specs
         self.bytes = [tiles.convert(a, f) for a, f in zip(self.arrays, self.flags)]         # computed once, never changed
 
 
@@ -60,27 +62,37 @@ def model(oracle, src, ts, channels):
 
 def tiles_of(src, k0=0):
     """every image whole, and where it is wide enough a rectangle at x = 1 and one at the right edge; the four flips go round"""
-    ts = []
-    for i, d in enumerate(src.descs):
-        w, h, f = d.width, d.height, src.flags[i]
-        ts.append((i, 0, 0, w, h, 1, f | ((i + k0) & 3)))
-        if w > 4:
-            ts.append((i, 1, 0, w - 2, h, 1, f | ((i + k0 + 1) & 3)))
-            ts.append((i, w - 4, 1, 4, h - 1, 1, f | ((i + k0 + 2) & 3)))
-    return ts
+    return ingest_cases.tiles_of(src.specs, k0)
 
 
 @pytest.fixture(scope="module", params=[0, 1])
 def mixed(request, api):
     """every legal dtype x layout x range with sch 3 and 4: 40 tensors of the five shapes in one buffer"""
-    specs = [(*SHAPES[(i + 2 * request.param + (sch == 4)) % 5], sch, fmt, None) for i, fmt in enumerate(FORMATS) for sch in (3, 4)]
-    assert len(specs) == 40
-    return request.param, Tensors(api, specs, seed=7 + request.param)
+    src = Tensors(api, ingest_cases.mixed_specs(request.param), seed=7 + request.param)
+    assert all(o % 16 != 0 for o in src.off)
+    return request.param, src
+
+
+@pytest.fixture(scope="module", params=[0, 1])
+def mixed_aligned(request, api):
+    """the same 40 tensors, each at a multiple of 256"""
+    src = Tensors(api, ingest_cases.mixed_specs(request.param), seed=7 + request.param, how=ALIGNED)
+    assert all(o % 256 == 0 for o in src.off)
+    return request.param, src
 
 
 # ------------------------------------------------------------------ 1: byte identity
 @pytest.mark.parametrize("channels", [0, 3, 4])
 def test_byte_identity(ctx, oracle, mixed, channels):
+    byte_identity(ctx, oracle, mixed, channels)
+
+
+@pytest.mark.parametrize("channels", ingest_cases.MIXED_CHANNELS)
+def test_byte_identity_aligned(ctx, oracle, mixed_aligned, channels):
+    byte_identity(ctx, oracle, mixed_aligned, channels)
+
+
+def byte_identity(ctx, oracle, mixed, channels):
     k0, src = mixed
     ts = tiles_of(src, k0)
     assert {t[6] & 3 for t in ts} == {0, 1, 2, 3} and {src.flags[t[0]] for t in ts} == {tiles.source_flags(*f) for f in FORMATS}
@@ -116,9 +128,23 @@ def test_special_values(api, ctx, oracle):
 
 
 # ------------------------------------------------------------------ 3: round trip on the device (no model)
+ROUND_TRIPS = ((tensors.F16, tensors.CHW, 1.0 / 255.0, 0.0, tiles.UNIT), (tensors.F32, tensors.HWC, 2.0 / 255.0, -1.0, tiles.SYMMETRIC))
+
+
 @pytest.mark.parametrize("ch", [3, 4])
 def test_round_trip_on_the_device(api, ctx, ch):
+    round_trip(api, ctx, ch, False)
+
+
+@pytest.mark.parametrize("ch", [3, 4])
+def test_round_trip_on_the_device_aligned(api, ctx, ch):
+    """decode_tensors writes to 256-aligned out_offsets, which the second encode reads: the wide loads"""
+    round_trip(api, ctx, ch, True)
+
+
+def round_trip(api, ctx, ch, aligned):
     import torch
+    assert ingest_cases.ROUND_TRIP_SHAPES == [(37, 23), (70, 9), (300, 17)]
     u8 = Sources(api, [(37, 23, ch, 0), (70, 9, ch, 4096 + 3), (300, 17, ch, 8192 + 1)], seed=9)       # (a tensor call decodes to one channel count)
     n = 3
     whole = [(i, 0, 0, w, h, 1, i & 3) for i, (w, h, _, _) in enumerate(u8.shapes)]
@@ -131,10 +157,12 @@ def test_round_trip_on_the_device(api, ctx, ch):
 
     pack, off, sizes, descs = encode(u8.d.data_ptr(), u8.off, whole)
     want = pack[:int(off[-1])].cpu().numpy()
-    for dtype, layout, scale, bias, rng in ((tensors.F16, tensors.CHW, 1.0 / 255.0, 0.0, tiles.UNIT), (tensors.F32, tensors.HWC, 2.0 / 255.0, -1.0, tiles.SYMMETRIC)):
+    assert [(d, l, r) for d, l, _, _, r in ROUND_TRIPS] == ingest_cases.ROUND_TRIP_FORMATS
+    for dtype, layout, scale, bias, rng in ROUND_TRIPS:
         elem = tensors.ELEM[dtype]
         nbytes = [d.width * d.height * d.channels * elem for d in u8.descs]
-        out_off = [int(v) + 4 * (k + 1) for k, v in enumerate(np.cumsum([0] + [(b + 15) // 16 * 16 for b in nbytes[:-1]]))]     # element-aligned, not 16-aligned
+        out_off = ingest_cases.round_trip_offsets(nbytes, aligned)             # element-aligned and not 16-aligned, or multiples of 256
+        assert all(o % 256 == 0 for o in out_off) if aligned else all(o % elem == 0 and o % 16 != 0 for o in out_off)
         out = torch.zeros(out_off[-1] + nbytes[-1] + 64, dtype=torch.uint8, device="cuda")
         items = [(i, 0, 0, d.width, d.height, d.width, d.height, 0) for i, d in enumerate(u8.descs)]
         ctx.decode_tensors(pack.data_ptr(), [int(o) for o in off[:n]], sizes, descs, 0, items, tensors.FILTER_AREA, tensors.PLAIN,
@@ -143,6 +171,7 @@ def test_round_trip_on_the_device(api, ctx, ch):
         # (the pack holds the mirrored images, the tensors are those: encoded again as they are they give the pack)
         again, off2, sizes2, _ = encode(out.data_ptr(), out_off, [t[:6] + (src_flags,) for t in whole])
         assert np.array_equal(off2, off) and sizes2.tolist() == sizes.tolist()
+        assert out.data_ptr() % 256 == 0
         assert np.array_equal(again[:int(off[-1])].cpu().numpy(), want), (dtype, layout)
         assert ctx.tile_stats()[:2] == (1, 1)
 

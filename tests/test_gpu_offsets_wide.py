@@ -23,6 +23,10 @@ That the decoy of every item of the newer filters and samplings resamples to oth
     qoimi_decode_batch                              pixel stride
     qoimi_encode_tiles                              pixel_offsets (f = 1, 3, 64; PLAIN and ALPHA_WEIGHTED: tile_gather; NEAREST, and MODE with
                                                     f = 1, 3, 16: tile_select; each at channels 0, 4, 3; one launch per sub-batch)
+    qoimi_encode_tiles, tensor sources                  pixel_offsets (tensor_ingest: f16 CHW, bf16 HWC, f32 CHW and u8 CHW tensors of 3 and 4 elements
+                                                    a pixel in ONE call at channels 0 and 3; every offset a multiple of 4, so an f32
+                                                    element ends at byte B32 inside the f32 CHW tensor that lies across it; every
+                                                    dtype has a tensor across or beyond; decoys: tensors of other elements)
     qoimi_decode_thumbnails                         stream_offsets, thumb_offsets
     qoimi_decode_crops / _resized / _bilinear / _warped                 stream_offsets, out_offsets
     qoimi_decode_tensors, all six filters (tensor_area, tensor_tent, tensor_cubic, tensor_lanczos, tensor_nearest, tensor_mode)
@@ -50,11 +54,19 @@ wholly on the device:
        41 x 41 result 400 x 400 times (position-sensitive at a 400-pixel grain, the fourth plane lies past 2^32)
     2. warp, f32, HWC, flags 0: a 64 x 48 rectangle under the identity into the corner, the converted fill everywhere else
     3. tent filter, f32, CHW: a constant image stays four constant planes
+and single SOURCES of the same size, the image of a tensor call of qoimi_encode_tiles (tensor_ingest), once HWC and once CHW:
+    4. the allocation is filled with one byte on the device - as f32 an element that converts to a known byte -, and windows of whole
+       rows hold random elements (tests/ingest_cases.py: BIG_WINDOWS): low in the image (control), around byte 2^32 of the image (HWC:
+       pixel 2^28 stands at column 256 of row 16368; CHW: in the fourth plane, at column 1024 of row 16272), and the last rows; the
+       elements 2^32 bytes below the last two - what a 32-bit byte offset would read - hold decoys.  Tiles of 400 to 403 x 8 pixels of each
+       window in every flip, and one of the constant, against tiles.tile over the window alone (a tile depends on its rectangle's elements
+       only: tests/test_ingest_paths.py); the tile a wrapped offset would read is built from the decoys and asserted to differ.
 The model conditions these rest on - integer enlargement by the area filter replicates, the identity warp pads with the fill and does not
 depend on the output's size, the tent filter keeps a constant - are asserted without a GPU by the first three tests of this file."""
 import numpy as np
 import pytest
 
+import ingest_cases
 from gpu_util import GuardedRegion
 from mode_cases import IMAGES as LABEL_MAPS
 from mode_cases import label_map
@@ -460,6 +472,60 @@ def test_encode_tiles(ctx, oracle, pack, src, dst):
         assert_bytes(dst.take([int(o) for o in want_off[:-1]], lens, what), want, what)
         subs = tiles.plan(SHAPES, ts, channels, 0)[1]
         assert ctx.tile_stats()[:2] == (len(subs), len(subs)), what       # one launch (tile_gather, or tile_select) per sub-batch
+    src.check()
+
+
+def tensor_offsets():
+    """pixel_offsets of the tensor call: ingest_cases.WIDE_SPECS control, across byte B32 (the longest: f32 CHW) and beyond in turn; every
+    offset is a multiple of 4, the largest element"""
+    return layout([tiles.source_bytes(w, h, sch, tiles.source_flags(*fmt)) for w, h, sch, fmt in ingest_cases.WIDE_SPECS], elem=ingest_cases.WIDE_ELEM, lane=2)
+
+
+def wide_tensors(seed):
+    """the tensors of ingest_cases.WIDE_SPECS: random elements over both clamps of each range"""
+    from test_gpu_ingest import elements
+    rng = np.random.default_rng(seed)
+    return [np.ascontiguousarray(elements(rng, w * h * sch, fmt[0], fmt[2])).reshape((sch, h, w) if fmt[1] == tiles.CHW else (h, w, sch))
+            for w, h, sch, fmt in ingest_cases.WIDE_SPECS]
+
+
+@gpu
+def test_encode_tiles_tensor_sources(api, ctx, oracle, src, dst):
+    """tensor_ingest reads `pixels + e.src_off` itself: tensors of every dtype at control, straddling and beyond offsets in one call"""
+    import torch
+    specs, ts = ingest_cases.WIDE_SPECS, ingest_cases.wide_tiles()
+    po = tensor_offsets()
+    true, decoys = wide_tensors(32), wide_tensors(33)
+    sizes = [a.nbytes for a in true]
+    assert src.t.data_ptr() % 256 == 0                             # (tests/test_ingest_paths.py replays the offsets modulo 256)
+    assert all(o % tiles.ELEM[s[3][0]] == 0 for o, s in zip(po, specs))
+    assert {s[3][0] for o, n, s in zip(po, sizes, specs) if o + n > B32} == {tiles.U8, tiles.F16, tiles.BF16, tiles.F32}
+    across = [i for i, (o, n) in enumerate(zip(po, sizes)) if o < B32 < o + n]
+    assert len(across) == 1 and specs[across[0]][3][:2] == (tiles.F32, tiles.CHW) and (B32 - po[across[0]]) % 4 == 0      # an element ends at byte B32
+    assert {(s[3][0], s[3][1]) for s in specs} == {(tiles.F16, tiles.CHW), (tiles.BF16, tiles.HWC), (tiles.F32, tiles.CHW), (tiles.U8, tiles.CHW)}
+    assert all({s[2] for s in specs if s[3][0] == d} == {3, 4} for d in (tiles.U8, tiles.F16, tiles.BF16, tiles.F32))
+    src.place(po, true, decoys)
+    descs = [api.QoiDesc(w, h, sch, i & 1) for i, (w, h, sch, _) in enumerate(specs)]
+    B = [tiles.convert(a, tiles.source_flags(*s[3])) for a, s in zip(true, specs)]
+    for channels in ingest_cases.WIDE_CHANNELS:
+        px = [tiles.tile(B[t[0]], t[:6] + (t[6] & 3,), channels) for t in ts]
+        want = [oracle.encode(p.reshape(-1), p.shape[1], p.shape[0], p.shape[2], descs[t[0]].colorspace) for p, t in zip(px, ts)]
+        for t, p in zip(ts, px):                                   # whoever dropped a high half would convert the decoy: another tile
+            i = t[0]
+            if po[i] + sizes[i] > B32:
+                seen = np.frombuffer(src.misread(po[i], sizes[i]).tobytes(), dtype=true[i].dtype).reshape(true[i].shape)
+                assert not np.array_equal(tiles.tile(seen, t, channels), p), (t, channels)
+        lens = [len(s) for s in want]
+        want_off = pack_offsets(lens, 1)
+        off = torch.full((len(ts) + 1,), -1, dtype=torch.int64, device="cuda")
+        d_len = torch.full((len(ts),), -1, dtype=torch.int32, device="cuda")
+        got_off, got_len, got_descs = ctx.encode_tiles(src.t.data_ptr(), po, descs, channels, ts, tiles.PLAIN, 1, dst.t.data_ptr(), int(want_off[-1]),
+                                                       off.data_ptr(), d_len.data_ptr())
+        what = ("encode_tiles, tensor sources", channels)
+        assert np.array_equal(got_off, want_off) and got_len.tolist() == lens and d_len.cpu().numpy().tolist() == lens, what
+        assert [(d.width, d.height, d.channels) for d in got_descs] == [(p.shape[1], p.shape[0], p.shape[2]) for p in px], what
+        assert_bytes(dst.take([int(o) for o in want_off[:-1]], lens, what), want, what)
+        assert ctx.tile_stats()[:2] == (1, 1) and ctx.tile_stats()[3] == len(specs), what
     src.check()
 
 
@@ -950,5 +1016,94 @@ def test_warp_f32_hwc_longer_than_4gib(ctx, sources):
 def test_tent_f32_chw_longer_than_4gib(ctx, sources):
     t = filled(BIG_BYTES + 2 * PAGE, GUARD)
     big_tent(ctx, sources, t, PAGE)
+    del t
+    release()
+
+
+# ------------------------------------------------------------------ 6: a single source longer than 4 GiB
+BIG_FILL = 0x3E                 # as f32 0x3E3E3E3E = 0.18578...: UNIT gives 47.37...
+BIG_FILL_BYTE = 47
+assert ingest_cases.BIG_SIDE == SIDE
+
+
+def big_windows(order):
+    """(true, decoys): lists of (first element, float32 elements) - whole rows of the image, of every plane for CHW (the decoys: of the
+    first plane, where the aliases of the fourth lie)"""
+    rng = np.random.default_rng(64 + order)
+    win = ingest_cases.BIG_WINDOWS[order]
+
+    def rows(r0, r1, planes):
+        if order == tiles.HWC:
+            return [(r0 * SIDE * 4, rng.uniform(-0.25, 1.25, size=(r1 - r0) * SIDE * 4).astype(np.float32))]
+        return [((c * SIDE + r0) * SIDE, rng.uniform(-0.25, 1.25, size=(r1 - r0) * SIDE).astype(np.float32)) for c in planes]
+
+    true = [w for name in ("control", "straddle", "last") for w in rows(*win[name], range(4))]
+    return true, [w for r0, r1 in win["decoys"] for w in rows(r0, r1, (0,))]
+
+
+def big_gather(windows, idx, fill):
+    """the elements at the indices idx by the construction"""
+    out = np.full(idx.shape, fill, dtype=np.float32)
+    for start, a in windows:
+        m = (idx >= start) & (idx < start + a.size)
+        out[m] = a[idx[m] - start]
+    return out
+
+
+@gpu
+@pytest.mark.parametrize("order", [tiles.HWC, tiles.CHW], ids=["hwc", "chw"])
+def test_encode_tiles_f32_source_longer_than_4gib(api, ctx, oracle, order):
+    import torch
+    fill = np.frombuffer(bytes([BIG_FILL]) * 4, dtype=np.float32)[0]
+    assert int(tiles.to_bytes(fill, tiles.UNIT)) == BIG_FILL_BYTE and 0.18 < float(fill) < 0.19
+    true, decoys = big_windows(order)
+    t = filled(BIG_BYTES + 2 * PAGE, BIG_FILL)
+    assert t.data_ptr() % 256 == 0 and PAGE % 256 == 0
+    for start, a in true + decoys:
+        assert 0 <= start and (start + a.size) * 4 <= BIG_BYTES
+        t[PAGE + 4 * start:PAGE + 4 * (start + a.size)].copy_(torch.from_numpy(a.view(np.uint8)))
+    named = ingest_cases.big_tiles(order)
+    ts = [tile for _, tile in named]
+    desc = api.QoiDesc(SIDE, SIDE, 4, 0)
+    hwc = tiles.source_flags(tiles.F32, tiles.HWC, tiles.UNIT)
+    wrapped_tiles = 0
+    for channels in ingest_cases.BIG_CHANNELS:
+        px = []
+        for name, (_, x, y, cw, ch, _, flags) in named:
+            idx = ingest_cases.big_index(order, y + np.arange(ch, dtype=np.int64)[:, None, None], x + np.arange(cw, dtype=np.int64)[None, :, None],
+                                         np.arange(4, dtype=np.int64)[None, None, :])
+            window = (0, 0, 0, cw, ch, 1, hwc | (flags & 3))
+            p = tiles.tile(big_gather(true, idx, fill), window, channels)
+            if name == "fill":
+                assert np.all(p[:, :, :3] == BIG_FILL_BYTE)
+            else:
+                assert all(any(start <= int(i) < start + a.size for start, a in true) for i in (idx.min(), idx.max()))
+            if idx.max() * 4 >= B32:                               # what a byte offset cut to 32 bits reads: the decoys, another tile
+                low = np.where(idx * 4 >= B32, idx - (B32 >> 2), idx)
+                assert all(any(start <= int(i) < start + a.size for start, a in decoys) for i in (low[idx * 4 >= B32].min(), low[idx * 4 >= B32].max()))
+                if order == tiles.HWC or channels != 3:             # (of a CHW image the fourth plane alone lies there: och 3 drops it)
+                    assert not np.array_equal(tiles.tile(big_gather(true + decoys, low, fill), window, channels), p), (name, flags)
+                    wrapped_tiles += 1
+            else:
+                assert name in ("control", "fill")
+            px.append(p)
+        want = [oracle.encode(p.reshape(-1), p.shape[1], p.shape[0], p.shape[2], 0) for p in px]
+        lens = [len(s) for s in want]
+        want_off = pack_offsets(lens, 1)
+        pack = filled(int(want_off[-1]) + 2 * PAGE, GUARD)
+        off = torch.full((len(ts) + 1,), -1, dtype=torch.int64, device="cuda")
+        d_len = torch.full((len(ts),), -1, dtype=torch.int32, device="cuda")
+        got_off, got_len, _ = ctx.encode_tiles(t.data_ptr(), [PAGE], [desc], channels, ts, tiles.PLAIN, 1, pack.data_ptr() + PAGE, int(want_off[-1]),
+                                               off.data_ptr(), d_len.data_ptr())
+        what = ("a source longer than 4 GiB", order, channels)
+        assert np.array_equal(got_off, want_off) and got_len.tolist() == lens and d_len.cpu().numpy().tolist() == lens, what
+        host = pack.cpu().numpy()
+        assert_bytes([host[PAGE + int(o):PAGE + int(o) + n] for o, n in zip(want_off[:-1], lens)], want, what)
+        assert np.all(host[:PAGE] == GUARD) and np.all(host[PAGE + int(want_off[-1]):] == GUARD), what
+        assert ctx.tile_stats()[:2] == (1, 1), what
+    assert wrapped_tiles == 2 * 4 * (2 if order == tiles.HWC else 1) and ingest_cases.BIG_CHANNELS == (0, 3)
+    for start, a in true + decoys:                                     # the source is only read
+        assert np.array_equal(t[PAGE + 4 * start:PAGE + 4 * (start + a.size)].cpu().numpy(), a.view(np.uint8)), start
+    assert bool((t[:PAGE] == BIG_FILL).all()) and bool((t[PAGE + BIG_BYTES:] == BIG_FILL).all())
     del t
     release()

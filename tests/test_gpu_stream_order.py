@@ -279,6 +279,39 @@ def encode_tiles_in_sub_batches(W):
                  lambda st: W.ctx.encode_tiles(inp.ptr, W.po, W.descs, 0, TILES, tiles.PLAIN, 1, outs[0].ptr, int(off[-1]), outs[1].ptr, outs[2].ptr, staging, st), ok))
 
 
+TENSOR_SHAPES = [(160, 120, 4), (97, 61, 3), (130, 70, 4)]
+
+
+@case("encode_tiles")
+def encode_tiles_tensors(W):
+    """a tensor call: launch_tensor_ingest stands on another branch of the launch line than the byte call's kernels.  f16 CHW tensors in a
+    sub-batch each; the stale inputs are other elements, which convert to other bytes"""
+    flags = tiles.source_flags(tiles.F16, tiles.CHW, tiles.UNIT)
+    rng = np.random.default_rng(77)
+    true, stale = ([rng.uniform(-0.25, 1.25, size=(ch, h, w)).astype(np.float16) for w, h, ch in TENSOR_SHAPES] for _ in range(2))
+    ts = [(0, 0, 0, 160, 120, 1, flags), (1, 1, 2, 90, 51, 1, flags | 2), (2, 3, 5, 120, 64, 1, flags | 1), (1, 0, 0, 97, 61, 1, flags | 3)]
+    px = [tiles.tile(true[t[0]], t, 0) for t in ts]
+    assert all(not np.array_equal(tiles.tile(stale[t[0]], t, 0), p) for t, p in zip(ts, px))
+    want = [W.oracle.encode(p.reshape(-1), p.shape[1], p.shape[0], p.shape[2]) for p in px]
+    lens = [len(s) for s in want]
+    po, total = W.lay([u8(a) for a in true], front=0, gap=2)
+    assert all(o % 2 == 0 for o in po)
+    inp = Inp(W.blob([u8(a) for a in true], po, total), W.blob([u8(a) for a in stale], po, total))
+    off, outs = packed_outputs(lens, want, 1)
+    descs = [W.api.QoiDesc(w, h, ch, 0) for w, h, ch in TENSOR_SHAPES]
+    staging = max(tiles.plan(TENSOR_SHAPES, ts, 0, 0)[0])
+    subs = tiles.plan(TENSOR_SHAPES, ts, 0, staging)[1]
+    assert len(subs) >= 2
+
+    def ok(result):
+        tables_ok(off, lens)(result[:2])
+        assert [(d.width, d.height, d.channels) for d in result[2]] == [(p.shape[1], p.shape[0], p.shape[2]) for p in px]
+        assert W.ctx.tile_stats()[:2] == (len(subs), len(subs))
+
+    W.H.run(Case("encode_tiles, tensors", True, [inp], outs,
+                 lambda st: W.ctx.encode_tiles(inp.ptr, po, descs, 0, ts, tiles.PLAIN, 1, outs[0].ptr, int(off[-1]), outs[1].ptr, outs[2].ptr, staging, st), ok))
+
+
 # ------------------------------------------------------------------ decode
 def decode_case(W, name, streams, shapes, och, batch):
     """qoimi_decode_batch (streams a stride apart) or qoimi_decode_images (a pack at odd offsets, images back to back)"""
