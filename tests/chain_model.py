@@ -15,8 +15,8 @@ import math
 import struct
 
 import numpy as np
+from model_cases import line_stream as _stream, line_walk as _walk
 
-from test_transcode_line_fetch import _stream, _walk
 
 HEADER = 14
 TRAILER = 8

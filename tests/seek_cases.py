@@ -3,7 +3,7 @@ their oracle decodes (computed once, never changed) and a pack of them on the de
 import numpy as np
 
 from qoi_amd import seekindex as si
-from test_seekindex_model import END, header
+from model_cases import END, header
 
 STREAM_FILL = 0xEE
 

@@ -6,13 +6,9 @@ import numpy as np
 import pytest
 
 import chain_model as cm
+from gpu_pack import oracle  # noqa: F401  (fixtures)
 
 SEGS = [1024, 2048, 4096]
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 def _not_flat(case):

@@ -7,26 +7,10 @@ import numpy as np
 import pytest
 
 from seek_cases import DevicePack, cases
-from test_gpu_encode_packed import filled
+from gpu_pack import E_ARG, GUARD, filled
+from gpu_pack import api, ctx  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
 
 
 @pytest.fixture(scope="module")

@@ -5,7 +5,7 @@ channels, 1 x 1, 130 x 34, a 70 x 66 checkerboard of 0 / 255 whose alpha alterna
 64-tap item) - for it the model is first shown to clamp at 0, to clamp at 255 and to meet A <= 0, the paths a wrong sign or a missing clamp
 would break - and a column 4 x 4160, whose reduction by 16 to one column fills the row table of a tile: 256 rows of 64 entries.  The images
 of 16384 x 1 and 1 x 16384 for the far end of the size limits are a pack of their own (tests/table_tiles.py).  The outputs of a call lie at
-element-aligned but otherwise odd addresses with guard bytes between them (test_gpu_tensors.py: layout_of, run); every guard byte is checked
+element-aligned but otherwise odd addresses with guard bytes between them (gpu_calls.py: tensor_layout, run_tensors); every guard byte is checked
 after every call.  The items use 1, 2, 4, 8 and 16 lanes per pixel, 4 to 64 taps, tiles that hold whole rows and tiles that wrap one
 (assert_paths, which tests/test_table_walk.py runs without a GPU)."""
 import ctypes
@@ -17,14 +17,12 @@ import table_tiles as tt
 from qoi_amd import bicubic, tensors
 from qoi_amd.bicubic import ALPHA_WEIGHTED, PLAIN
 from qoi_amd.tensors import BF16, CHW, F16, F32, FILTER_BICUBIC, HWC, U8
-from test_gpu_encode_packed import filled
-from test_gpu_tensors import IMAGENET, WILD, layout_of, run
-from test_gpu_thumbnails import Pack, batch_of
+from gpu_calls import WILD, run_tensors as run
+from gpu_pack import E_ARG, GUARD, IMAGENET, Pack, batch_of, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
+from model_cases import BICUBIC_ITEMS as ITEMS, BICUBIC_TABLES as TABLES, CHECK, CHECK_UP, ONE, RGB, SOFT, STRIP, assert_bicubic_paths as assert_paths
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
-SOFT, RGB, ONE, STRIP, CHECK, TALL = 0, 1, 2, 3, 4, 5
 SHAPES = [(67, 45, 4), (67, 45, 3), (1, 1, 4), (130, 34, 4), (70, 66, 4), (4, 4160, 4)]
 
 
@@ -46,26 +44,6 @@ def pixels():
 
 
 @pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-@pytest.fixture(scope="module")
 def pack(api, ctx, oracle):
     return Pack(ctx, oracle, batch_of(api, oracle, SHAPES, pixels()))
 
@@ -74,24 +52,6 @@ def pack(api, ctx, oracle):
 def limits(api, ctx, oracle):
     return Pack(ctx, oracle, batch_of(api, oracle, tt.LIMIT_SHAPES, tt.limit_pixels()))
 
-
-# identity; 5 x 3 -> 17 x 11 (the borders truncate the kernel); 64 x 64 -> 4 x 4 (64 taps, 16 lanes); 37 x 29 -> 5 x 7; 1 x 1 -> 9 x 9;
-# rectangles at the image's edges; the whole strip at 58 taps; the checkerboard enlarged to five tiles; the flips take turns
-IDENTITY = (SOFT, 3, 2, 40, 30, 40, 30, 2)
-CHECK_UP = (CHECK, 5, 4, 9, 7, 40, 30, 0)
-CHECK_DOWN = (CHECK, 2, 1, 64, 64, 4, 4, 0)
-CAP = (STRIP, 0, 0, 128, 3, 8, 1, 0)                 # exactly 16 : 1 - 64 taps, sixteen lanes of four columns
-NEAR_CAP = (STRIP, 3, 1, 127, 33, 8, 3, 1)           # 64 taps in x, 44 in y
-BORDERS = (SOFT, 30, 20, 3, 3, 19, 11, 0)            # 3 x 3 enlarged: the kernel is cut at all four borders of every output pixel
-CORNER = (SOFT, 64, 42, 3, 3, 5, 7, 3)               # ... at the image's corner
-WRAP = (SOFT, 5, 4, 5, 3, 300, 2, 1)                 # 600 pixels of one lane: three tiles, each narrower than a row
-WRAP_TWO = (STRIP, 0, 30, 130, 3, 129, 2, 0)         # 5 taps, two lanes: tiles of 128 pixels under rows of 129
-ROWS = (TALL, 1, 0, 1, 4160, 1, 260, 2)              # tiles of 256 rows of 64 entries: the row table full
-WIDE_ROW = (TALL, 0, 17, 4, 256, 256, 16, 0)         # a tile is one row of 256 pixels (the column table full) whose row has 64 entries
-ADDED = [CAP, NEAR_CAP, BORDERS, CORNER, WRAP, WRAP_TWO]
-ITEMS = [IDENTITY, (SOFT, 10, 7, 5, 3, 17, 11, 1), CHECK_DOWN, (SOFT, 20, 10, 37, 29, 5, 7, 3), (ONE, 0, 0, 1, 1, 9, 9, 0),
-         (SOFT, 55, 36, 12, 9, 7, 5, 0), (SOFT, 0, 0, 67, 45, 20, 13, 1), (STRIP, 0, 0, 130, 3, 9, 5, 2), CHECK_UP, (RGB, 60, 0, 7, 45, 3, 50, 3)] + ADDED
-TABLES = [ROWS, WIDE_ROW]
 
 _MODELS = {}
 
@@ -111,30 +71,6 @@ def assert_items(p, got, items, och, mode, f, what):
     for j, it in enumerate(items):
         w = tensors.convert(model(p, it, och, mode), f).view(np.uint8).reshape(-1)
         assert got[j].size == w.size and np.array_equal(got[j], w), (what, j, it, int(np.argmax(got[j] != w)) // tensors.ELEM[f[0]])
-
-
-def assert_paths():
-    """what the items make of the kernel, from the model alone (no GPU)"""
-    assert {bicubic.split(it[3], it[5])[0] for it in ITEMS} == {0, 1, 2, 3, 4}
-    assert bicubic.taps(64, 4) == 64 and bicubic.split(64, 4) == (4, 4)
-    assert bicubic.tiles(9, 40, 30) == 5
-    assert [bicubic.split(it[3], it[5])[0] for it in (BORDERS, CORNER, WRAP, WRAP_TWO, CAP, NEAR_CAP, ROWS, WIDE_ROW)] == [0, 0, 0, 1, 4, 4, 0, 0]
-    assert bicubic.taps(128, 8) == 64 and bicubic.split(128, 8) == (4, 4) and bicubic.split(127, 8) == (4, 4) and bicubic.taps(33, 3) == 44
-    assert int(np.count_nonzero(bicubic.kernel(128, 8)[3])) >= 62
-    # the 3 x 3 rectangles have fewer samples than the kernel has taps: it is cut for every output pixel, in both axes
-    assert bicubic.taps(3, 19) == bicubic.taps(3, 11) == bicubic.taps(3, 5) == bicubic.taps(3, 7) == 4 > 3 and bicubic.first(0, 3, 19) == 0
-    # the two forms of the column table; three tiles of one item; both tables full
-    assert bicubic.tiles(5, 300, 2) == 3 and len(bicubic.tile(1, 5, 300, 2)[0]) == 256 and bicubic.tile(1, 5, 300, 2)[0][44] == 0
-    assert bicubic.tile(1, 5, 300, 2) == (list(range(256, 300)) + list(range(212)), [0, 1])
-    assert bicubic.split(130, 129) == (1, 3) and len(bicubic.tile(0, 130, 129, 2)[0]) == 128 < 129
-    assert bicubic.tile(1, 130, 129, 2) == (list(range(128, 129)) + list(range(127)), [0, 1])
-    assert all(bicubic.tile(0, it[3], it[5], it[6])[0] == list(range(it[5])) for it in (BORDERS, CORNER, CAP, NEAR_CAP))
-    assert bicubic.tiles(1, 1, 260) == 2 and len(bicubic.tile(0, 1, 1, 260)[1]) == 256 and bicubic.taps(4160, 260) == 64 and 256 * 64 == 16384
-    assert bicubic.tile(3, 4, 256, 16) == (list(range(256)), [3]) and bicubic.taps(256, 16) == 64 and 256 * (bicubic.split(4, 256)[1] << 0) == 1024
-    # the kernel forms qy * qx in 32 bits: the added items reach 2^30 and stay below 2^31
-    largest = {it: int(np.abs(bicubic.weights(it[4], it[6])).max()) * int(np.abs(bicubic.weights(it[3], it[5])).max()) for it in ADDED + TABLES}
-    assert all(largest[it] >= 1 << 30 for it in (BORDERS, CORNER)) and max(largest.values()) < 1 << 31
-    assert int(bicubic.weights(3, 19)[0, 0]) > 1 << 15 and int(bicubic.weights(3, 11)[10, 2]) > 1 << 15      # (the corner pixels: one pixel, both)
 
 
 def test_the_items_use_every_lane_count_and_the_model_every_path(pack):

@@ -11,33 +11,12 @@ import pytest
 from qoi_amd import bilinear, crops
 from qoi_amd.bilinear import ALPHA_WEIGHTED, PLAIN
 from qoi_amd.packplan import slot
-from test_gpu_encode_packed import KINDS, Batch, filled
-from test_gpu_thumbnails import MIXED_SHAPES, Pack
+from gpu_calls import sizes_of
+from gpu_pack import E_ARG, GUARD, KINDS, MIXED_SHAPES, Batch, Pack, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 BIG = 7                               # 130 x 70 x 4, sprite_alpha
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -64,10 +43,6 @@ def standard(i, w, h, first_flag=0):
     out.append((w // 3, h // 3, min(5, w - w // 3), min(3, h - h // 3), 13, 7))
     out.append((0, 0, w, min(h, 3), max(1, w // 3), 8))
     return [(i, x, y, cw, rh, ow, oh, (first_flag + k) & 3) for k, (x, y, cw, rh, ow, oh) in enumerate(out)]
-
-
-def sizes_of(items, och):
-    return [it[5] * it[6] * och for it in items]
 
 
 def run(ctx, p, channels, items, mode=PLAIN, staging=0, offsets=None, total=None, front=64, call=None):

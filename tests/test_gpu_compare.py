@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 
 from qoi_amd.imagediff import DIFF_PIXELS, NONE, diff
+from gpu_pack import dev
+from gpu_pack import api, ctx  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(1, 1), (1, 97), (131, 1), (37, 23), (257, 9), (64, 48), (333, 7), (300, 300)]
@@ -14,26 +16,6 @@ PAIRINGS = [(4, 4), (3, 3), (4, 3), (3, 4)]
 SHIFTS = [0, 1, 2, 3, 5]
 GAP = 7                                         # guard bytes between two images (odd: every image begins at another residue)
 FRONT = 256
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-def dev(arr):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(arr)).cuda()
 
 
 class Side:

@@ -11,33 +11,12 @@ import pytest
 
 from qoi_amd import crops
 from qoi_amd.packplan import slot
-from test_gpu_encode_packed import KINDS, Batch, dev, filled
-from test_gpu_thumbnails import MIXED_SHAPES, Pack
+from gpu_calls import standard_crops as standard
+from gpu_pack import E_ARG, GUARD, KINDS, MIXED_SHAPES, Batch, Pack, dev, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 BIG = 7                               # 130 x 70 x 4, sprite_alpha
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -51,15 +30,6 @@ def mixed(api, ctx, oracle):
 @pytest.fixture(scope="module")
 def equal(api, ctx, oracle):
     return Pack(ctx, oracle, Batch(api, oracle, [(64, 48, 4)] * 7, [KINDS[i % 5] for i in range(7)]))
-
-
-def standard(i, w, h, first_flag=0):
-    """the whole image, the 1 x 1 crop at each corner, one column, one row, an interior rectangle with odd origin and odd size; the flag
-    values take turns"""
-    out = [(0, 0, w, h), (0, 0, 1, 1), (w - 1, 0, 1, 1), (0, h - 1, 1, 1), (w - 1, h - 1, 1, 1), (w // 2, 0, 1, h), (0, h // 2, w, 1)]
-    if w >= 3 and h >= 4:
-        out.append((1, 3, w - 1 if (w - 1) % 2 else w - 2, h - 3 if (h - 3) % 2 else h - 4))
-    return [(i, x, y, cw, ch, (first_flag + k) & 3) for k, (x, y, cw, ch) in enumerate(out)]
 
 
 def sizes_of(cs, och):

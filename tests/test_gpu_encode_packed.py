@@ -1,72 +1,19 @@
 """qoimi_encode_packed / qoimi_encode_images_packed on the GPU (-m gpu): pixels in, pack out through bounded staging.  The result is
 defined as encode_batch + pack_streams over all streams, so everything is compared with the oracle's streams laid out by the numpy model of
-tests/test_packed_api.py (offsets) - the pack's bytes, both device tables, both host tables, 0xA5 in every gap and around the pack - and
+tests/model_cases.py (pack_offsets) - the pack's bytes, both device tables, both host tables, 0xA5 in every gap and around the pack - and
 the sub-batch boundaries are forced through staging_bytes by the plan of qoi_amd/packplan.py (the launch count of the append scan says
 that the call really ran that many sub-batches)."""
 import ctypes
 
 import numpy as np
 import pytest
+from gpu_pack import E_ARG, GUARD, KINDS, Batch, dev, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
+from model_cases import pack_offsets as offsets
 
-from test_packed_api import offsets
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 FRONT = 256                                  # guard bytes in front of the pack; the pack begins at a 256-aligned address + shift
-KINDS = ["noise", "constant", "photo", "uiflat", "sprite_alpha"]
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-def dev(arr):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(arr)).cuda()
-
-
-def filled(n, value=GUARD):
-    import torch
-    return torch.full((int(n),), value, dtype=torch.uint8, device="cuda")
-
-
-def image(kind, w, h, ch, frame=0):
-    from qoi_amd import synth
-    if kind == "noise":
-        return np.random.default_rng(w * 7919 + h * 31 + ch + frame).integers(0, 256, size=w * h * ch, dtype=np.uint8)
-    return (synth.frame_rgba if ch == 4 else synth.frame_rgb)(kind, w, h, frame).reshape(-1)
-
-
-class Batch:
-    """Images on the device, tightly packed one behind the other, and the oracle's streams (computed once, never changed)."""
-
-    def __init__(self, api, oracle, shapes, kinds):
-        self.shapes = shapes
-        self.px = [image(k, w, h, ch, frame=i) for i, ((w, h, ch), k) in enumerate(zip(shapes, kinds))]
-        self.want = [oracle.encode(p, w, h, ch) for p, (w, h, ch) in zip(self.px, shapes)]
-        self.lens = [len(s) for s in self.want]
-        self.descs = [api.QoiDesc(w, h, ch, 0) for (w, h, ch) in shapes]
-        self.bounds = [api.encode_bound(w, h, ch) for (w, h, ch) in shapes]
-        self.pix_off = [int(x) for x in np.cumsum([0] + [p.size for p in self.px[:-1]])]
-        self.d_px = dev(np.concatenate(self.px))
-        self.n = len(shapes)
 
 
 @pytest.fixture(scope="module")

@@ -1,67 +1,19 @@
 """qoimi_encode_tiles on the GPU (-m gpu): tiles and pyramid levels of device images as a pack.  The pixels of a tile are those of
 qoi_amd/tiles.py: tile, its stream is the reference encoder's stream of them, byte for byte, and the pack is laid out by the numpy model of
-tests/test_packed_api.py (offsets) - every stream, both device tables, both host tables, the descriptors, the fill byte everywhere else."""
+tests/model_cases.py (pack_offsets) - every stream, both device tables, both host tables, the descriptors, the fill byte everywhere else."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from gpu_util import GuardedRegion
 from qoi_amd import tiles
-from test_packed_api import offsets
+from gpu_calls import TILE_FILL as FILL, Sources, run_tiles as run, tile_model as model
+from gpu_pack import dev
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
+from model_cases import pack_offsets as offsets
 
 pytestmark = pytest.mark.gpu
-FILL = 0xA5
-FRONT = 256
 FACTORS = (1, 2, 3, 4, 5, 8, 13, 16, 33, 64)
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-def dev(arr):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(arr)).cuda()
-
-
-class Sources:
-    """Images in one device buffer with gaps, at the byte offsets given; the buffer's host copy never changes."""
-
-    def __init__(self, api, shapes, seed=5):
-        rng = np.random.default_rng(seed)
-        self.shapes = shapes
-        end = max(off + w * h * ch for (w, h, ch, off) in shapes)
-        self.host = rng.integers(0, 256, size=end + 64, dtype=np.uint8)
-        self.img = []
-        for (w, h, ch, off) in shapes:
-            v = self.host[off:off + w * h * ch].reshape(h, w, ch)
-            if ch == 4:
-                v[:, :, 3] = rng.choice(np.array([0, 2, 200, 255], dtype=np.uint8), size=(h, w))
-                v[: h // 2, : w // 2, 3] = 0
-            if w * h > 64:
-                v[h // 3: h // 3 + 4, :, :] = v[h // 3, 0]                 # some runs and repeats: streams of every chunk kind
-            self.img.append(v)
-        self.off = [s[3] for s in shapes]
-        self.descs = [api.QoiDesc(w, h, ch, i & 1) for i, (w, h, ch, _) in enumerate(shapes)]
-        self.d = dev(self.host)
-        assert self.d.data_ptr() % 256 == 0
 
 
 @pytest.fixture(scope="module")
@@ -83,45 +35,6 @@ def mixed_tiles():
         ts.append((4, 4 * (k % 3), k, 128 - 4 * (k % 3), 64 - k, f, k & 3))
     ts += [(4, 0, 0, 128, 64, 1, 0), (4, 0, 0, 128, 64, 1, 1), (4, 8, 1, 64, 32, 1, 3), (4, 1, 0, 127, 64, 1, 0), (3, 69, 44, 1, 1, 1, 0), (2, 36, 0, 1, 29, 2, 0)]
     return ts
-
-
-def model(oracle, src, ts, channels, mode):
-    px = [tiles.tile(src.img[t[0]], t, channels, mode) for t in ts]
-    streams = [oracle.encode(p.reshape(-1), p.shape[1], p.shape[0], p.shape[2], src.descs[t[0]].colorspace) for p, t in zip(px, ts)]
-    return px, streams
-
-
-def run(ctx, src, ts, channels, mode, align, streams, staging=0, capacity=None, null_dest=False, shift=0):
-    """One call; checks tables, descriptors, bytes and guards.  Returns (offsets, sizes, descs)."""
-    import torch
-    n = len(ts)
-    lens = [len(s) for s in streams]
-    want_off = offsets(lens, align)
-    cap = int(want_off[-1]) if capacity is None else capacity
-    starts = [FRONT + shift + int(o) for o in want_off[:n]]
-    region = GuardedRegion(FRONT + shift + max(cap, 0) + 512, starts, FILL)
-    buf = torch.full((region.size,), FILL, dtype=torch.uint8, device="cuda")
-    d_off = torch.full((n + 1,), -1, dtype=torch.int64, device="cuda")
-    d_len = torch.full((n,), -1, dtype=torch.int32, device="cuda")
-    dest = 0 if null_dest else buf[FRONT + shift:].data_ptr()
-    got_off, got_len, got_descs = ctx.encode_tiles(src.d.data_ptr(), src.off, src.descs, channels, ts, mode, align, dest, cap, d_off.data_ptr(), d_len.data_ptr(), staging)
-    what = (channels, mode, align, staging, cap)
-    assert got_len.tolist() == lens, what
-    assert np.array_equal(got_off, want_off), what
-    assert np.array_equal(d_off.cpu().numpy().astype(np.uint64), want_off) and d_len.cpu().numpy().tolist() == lens, what
-    for t, d in zip(ts, got_descs):
-        sd = src.descs[t[0]]
-        nbytes, tw, th = tiles.size(sd.width, sd.height, sd.channels, t, channels)
-        assert (d.width, d.height, d.channels, d.colorspace) == (tw, th, channels or sd.channels, sd.colorspace), (what, t)
-    host = buf.cpu().numpy()
-    present = [ln if int(o) + ln <= cap else 0 for o, ln in zip(want_off[:n], lens)]         # a stream that does not fit wholly is absent
-    for k, s in enumerate(streams):
-        if present[k]:
-            assert host[starts[k]:starts[k] + lens[k]].tobytes() == s, (what, "stream", k, ts[k])
-    region.starts = [min(s, region.size) for s in starts]
-    region.assert_untouched(host, present, what)
-    ctx.encode_status(0)                                      # QOIMI_OK, and nothing is encoded again
-    return got_off, got_len, got_descs
 
 
 # ------------------------------------------------------------------ 1: byte identity

@@ -9,31 +9,10 @@ import pytest
 from qoi_amd import crops
 from qoi_amd import seekindex as si
 from seek_cases import DevicePack, cases
-from test_gpu_encode_packed import Batch, filled
-from test_gpu_thumbnails import Pack
+from gpu_pack import GUARD, Batch, Pack, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-GUARD = 0xA5
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")

@@ -9,55 +9,13 @@ import numpy as np
 import pytest
 
 import ingest_cases
-from ingest_cases import ALIGNED, FORMATS, ODD
+from ingest_cases import ALIGNED, FORMATS
 from qoi_amd import tensors, tiles
-from test_gpu_encode_tiles import FILL, Sources, api, ctx, dev, oracle, run  # noqa: F401  (api, ctx and oracle are fixtures)
+from gpu_calls import TILE_FILL as FILL, Sources, Tensors, ingest_model as model, run_tiles as run
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 SPECIALS = [np.nan, np.inf, -np.inf, -0.0, 1e30, -1e30, 65504.0]
-
-
-def elements(rng, count, dtype, rng_bits):
-    """random elements over [-0.25, 1.25] scaled to the range (both clamps occur), as the dtype's array (BF16: its bits)"""
-    if dtype == tiles.U8:
-        return rng.integers(0, 256, size=count, dtype=np.uint8)
-    x = rng.uniform(-0.25, 1.25, size=count).astype(np.float32)
-    x = {tiles.UNIT: x, tiles.SYMMETRIC: x * 2 - 1, tiles.BYTES: x * 255}[rng_bits]
-    if dtype == tiles.F32:
-        return x
-    return x.astype(np.float16) if dtype == tiles.F16 else tensors.bf16_bits(x)
-
-
-class Tensors:
-    """Tensors of different formats in one device buffer, each at an element-aligned byte offset that is no multiple of 16 - or, how=ALIGNED,
-    each at a multiple of 256; how may name a placement per tensor (ingest_cases.offsets) -; the interface of
-    test_gpu_encode_tiles.Sources as far as run looks at it (d, off, descs).  specs: (w, h, sch, (dtype, layout, range), elements or None)."""
-
-    def __init__(self, api, specs, seed=7, how=ODD):
-        rng = np.random.default_rng(seed)
-        self.off, self.flags, self.arrays, self.descs, parts = [], [], [], [], []
-        placed, cur = ingest_cases.offsets(specs, how)                      # ODD: 1 or 3 elements behind a 16-byte boundary
-        for i, (w, h, sch, fmt, given) in enumerate(specs):
-            off = placed[i]
-            a = np.ascontiguousarray(elements(rng, w * h * sch, fmt[0], fmt[2]) if given is None else given)
-            assert a.size == w * h * sch and a.dtype == tiles.SOURCE_ARRAYS[fmt[0]]
-            self.arrays.append(a.reshape((sch, h, w) if fmt[1] == tiles.CHW else (h, w, sch)))
-            self.off.append(off)
-            self.flags.append(tiles.source_flags(*fmt))
-            self.descs.append(api.QoiDesc(w, h, sch, i & 1))
-            parts.append((off, a.view(np.uint8).reshape(-1)))
-        self.host = rng.integers(0, 256, size=cur + 64, dtype=np.uint8)
-        for off, b in parts:
-            self.host[off:off + b.size] = b
-        self.d = dev(self.host)
-        assert self.d.data_ptr() % 256 == 0
-        self.specs = specs
-        self.bytes = [tiles.convert(a, f) for a, f in zip(self.arrays, self.flags)]         # computed once, never changed
-
-
-def model(oracle, src, ts, channels):
-    px = [tiles.tile(src.bytes[t[0]], t[:6] + (t[6] & 3,), channels) for t in ts]
-    return px, [oracle.encode(p.reshape(-1), p.shape[1], p.shape[0], p.shape[2], src.descs[t[0]].colorspace) for p, t in zip(px, ts)]
 
 
 def tiles_of(src, k0=0):
@@ -194,7 +152,7 @@ def test_src_alone_is_the_unflagged_call(api, ctx, oracle, channels):
 
 # ------------------------------------------------------------------ 5: memory contract and sub-batches
 def test_memory_contract_and_sub_batches(ctx, oracle, mixed):
-    from test_packed_api import offsets
+    from model_cases import pack_offsets as offsets
     k0, src = mixed
     ts = tiles_of(src, k0)
     shapes = [(d.width, d.height, d.channels) for d in src.descs]

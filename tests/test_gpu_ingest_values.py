@@ -14,35 +14,10 @@ import pytest
 
 import ingest_cases
 from qoi_amd import tiles
-from test_gpu_encode_tiles import api, ctx, oracle, run  # noqa: F401  (fixtures)
-from test_gpu_ingest import Tensors, model
+from gpu_calls import Tensors, conditions, ingest_model as model, run_tiles as run
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-def conditions(dtype, specs, ts, bytes_of):
-    """what makes the exact comparison a test of the conversion (no GPU): the expected bytes hold 0 and 255, ties that round down to an
-    even byte and ties that round up to one, and - binary32, SYMMETRIC - every tile would be another one had the kernel fused the multiply
-    and the add.  bytes_of[i]: the model's byte image of tensor i."""
-    P = ingest_cases.patterns(dtype)
-    parities = set()
-    for rng in ingest_cases.RANGES:
-        B = tiles.to_bytes(tiles.widen(P, dtype), rng)
-        assert B.min() == 0 and B.max() == 255, (dtype, rng)
-        t = ingest_cases.ties(P, dtype, rng)
-        parities |= set((np.floor(t).astype(np.int64) % 2).tolist())
-        assert t.size >= 1 and np.array_equal(tiles.to_bytes(t, tiles.BYTES), (np.floor(t).astype(np.int64) + 1) // 2 * 2), (dtype, rng)     # to even
-    assert parities == {0, 1}, dtype
-    fused = 0
-    for t in ts:
-        w, h, sch, fmt, A = specs[t[0]]
-        assert np.array_equal(bytes_of[t[0]], tiles.to_bytes(tiles.widen(P, dtype), fmt[2]))          # (HWC and CHW hold the same pixels)
-        if dtype == tiles.F32 and fmt[2] == tiles.SYMMETRIC:
-            for och in ingest_cases.VALUE_CHANNELS:
-                plain = t[:6] + (t[6] & 3,)
-                assert not np.array_equal(tiles.tile(ingest_cases.fused_bytes(P), plain, och), tiles.tile(bytes_of[t[0]], plain, och)), (t, och)
-                fused += 1
-    assert fused == (2 * 2 * 5 * 2 if dtype == tiles.F32 else 0)
 
 
 @pytest.fixture(scope="module", params=ingest_cases.FLOATS, ids=["f16", "bf16", "f32"])

@@ -8,35 +8,12 @@ import pytest
 
 import cases
 from qoi_amd import streaminfo as si
+from gpu_calls import assert_info
+from gpu_pack import E_ARG, dev
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
 BLOCK = 16384          # bytes of a stream's body one wavefront takes (qoi_inspect.hip: kInsBlock)
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-def dev(arr):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(arr)).cuda()
 
 
 def image(kind, w, h, ch, frame=0):
@@ -50,13 +27,6 @@ def pack_host(streams):
         offs.append(len(blob))
         blob += s
     return bytes(blob), offs
-
-
-def assert_info(got, want, tag):
-    for k in ("pixels", "run_pixels", "repeat_index", "walk_end", "flags"):
-        assert int(got[k]) == want[k], (tag, k, int(got[k]), want[k], [int(x) for x in got["ops"]], want["ops"])
-    assert [int(x) for x in got["ops"]] == want["ops"], (tag, [int(x) for x in got["ops"]], want["ops"])
-    assert not got["reserved"].any(), tag
 
 
 def check_call(ctx, streams, sizes=None, order=None, models=None, stream=0):

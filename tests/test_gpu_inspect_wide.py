@@ -11,7 +11,9 @@ import cases
 import inspect_maps as im
 from inspect_maps import BLOCK
 from qoi_amd import streaminfo as si
-from test_gpu_inspect import assert_info, dev
+from gpu_calls import assert_info
+from gpu_pack import dev
+from gpu_pack import api, ctx  # noqa: F401  (fixtures)
 
 gpu = pytest.mark.gpu          # (not the module: test_closed_form_is_the_model needs no GPU)
 HEAD = cases.header(640, 360)
@@ -19,21 +21,6 @@ HEAD = cases.header(640, 360)
 FILLERS = [bytes([0xC0]), bytes([0xFE]), bytes([0xFF]), bytes([0x80]), bytes([0xFE, 0x00])]
 WAVE_STAGES = ("without before", "without excl", "without own", "excl reversed", "own reversed")
 TILE_STAGES = ("without carry", "before reversed")
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
 
 
 class Call:
@@ -248,7 +235,6 @@ def test_closed_form_is_the_model():
         for mixed in (False, True):
             want = si.inspect_stream(HEAD + host_body(body, mixed) + cases.END)
             assert closed_form(body, mixed) == want, (body, mixed)
-
 
 
 def device_stream(buf, at, size, mixed):

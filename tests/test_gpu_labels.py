@@ -13,15 +13,13 @@ import pytest
 from qoi_amd import nearest, tensors, warp
 from qoi_amd.tensors import (ALPHA_WEIGHTED, BF16, CHW, F16, F32, FILTER_AREA, FILTER_BICUBIC, FILTER_BILINEAR, FILTER_LANCZOS, FILTER_NEAREST, HW, HWC, I32, I64,
                              PLAIN, U8)
-from test_gpu_encode_packed import Batch, filled
-from test_gpu_thumbnails import Pack
+from gpu_calls import fmt_of, run_label_tensors as run
+from gpu_pack import E_ARG, GUARD, Batch, Pack, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 DOT, LINE, ODD, WIDE = 0, 1, 2, 3
 SHAPES = [(1, 1, 3), (130, 1, 3), (37, 29, 3), (70, 45, 4)]
-IMAGENET = tensors.normalise((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
 DTYPES = (U8, F16, BF16, F32, I32, I64)
 LAYOUTS = (HWC, CHW, HW)
 
@@ -32,32 +30,8 @@ ITEMS = [(ODD, 0, 0, 37, 29, 50, 41, 0), (WIDE, 0, 0, 70, 45, 3, 2, 3), (DOT, 0,
 
 
 @pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-@pytest.fixture(scope="module")
 def pack(api, ctx, oracle):
     return Pack(ctx, oracle, Batch(api, oracle, SHAPES, ["noise"] * 4))
-
-
-def fmt_of(dtype, layout):
-    return tensors.fmt(dtype, layout) if dtype in (U8, I32, I64) else (dtype, layout, *IMAGENET)
 
 
 _MODELS = {}
@@ -76,36 +50,6 @@ def model(p, filt, it, och, mode=PLAIN):
         P.setflags(write=False)
         _MODELS[key] = P
     return _MODELS[key]
-
-
-def layout_of(items, och, f, front=None):
-    """(offsets, byte sizes, total): the first output at an odd element-aligned address, 1 to 3 guard bytes - in whole elements - between"""
-    elem = tensors.elem(f[0])
-    nbytes = [it[5] * it[6] * (1 if f[1] == HW else och) * elem for it in items]
-    pos = 64 + elem if front is None else front
-    offsets = []
-    for j, n in enumerate(nbytes):
-        offsets.append(pos)
-        pos += n + -(-(1 + j % 3) // elem) * elem
-    return offsets, nbytes, pos + 64
-
-
-def run(ctx, p, filt, channels, items, mode, f, staging=0):
-    """One call; returns the outputs as bytes.  The buffer's base is a multiple of 256 (torch's allocator), so the offsets are the alignment."""
-    och = channels or p.shapes[items[0][0]][2]
-    offsets, nbytes, total = layout_of(items, och, f)
-    buf = filled(total, GUARD)
-    assert buf.data_ptr() % 256 == 0
-    if filt == "warp":
-        ctx.decode_warped_tensors(p.packed.data_ptr(), p.so, p.sizes, p.descs, channels, items, mode, f, buf.data_ptr(), offsets, staging)
-    else:
-        ctx.decode_tensors(p.packed.data_ptr(), p.so, p.sizes, p.descs, channels, items, filt, mode, f, buf.data_ptr(), offsets, staging)
-    got = buf.cpu().numpy()
-    mask = np.ones(total, dtype=bool)
-    for o, n in zip(offsets, nbytes):
-        mask[o:o + n] = False
-    assert np.all(got[mask] == GUARD), ("a byte outside the outputs was written", int(np.argmax(mask & (got != GUARD))))
-    return [got[o:o + n] for o, n in zip(offsets, nbytes)]
 
 
 def assert_items(p, got, filt, items, och, mode, f, what):

@@ -5,7 +5,7 @@ channels, 1 x 1, 130 x 34, a 70 x 66 checkerboard of 0 / 255 whose alpha alterna
 clamp at 0, to clamp at 255 and to meet A <= 0, the paths a wrong sign or a missing clamp would break - and a column 4 x 4160, whose reduction
 by 16 to one column fills the row table of a tile: 256 rows of 96 entries.  The images of 16384 x 1 and 1 x 16384 for the far end of the size
 limits are a pack of their own (tests/table_tiles.py).  The outputs of a call lie at element-aligned but otherwise odd
-addresses with guard bytes between them (test_gpu_tensors.py: layout_of, run); every guard byte is checked after every call.  The items use
+addresses with guard bytes between them (gpu_calls.py: tensor_layout, run_tensors); every guard byte is checked after every call.  The items use
 1, 2, 4, 8 and 16 lanes per pixel, 6 to 96 taps, tiles that hold whole rows and tiles that wrap one."""
 import ctypes
 
@@ -16,13 +16,11 @@ import table_tiles as tt
 from qoi_amd import lanczos, tensors
 from qoi_amd.lanczos import ALPHA_WEIGHTED, PLAIN
 from qoi_amd.tensors import BF16, CHW, F16, F32, FILTER_LANCZOS, HWC, U8
-from test_gpu_encode_packed import filled
-from test_gpu_tensors import IMAGENET, WILD, layout_of, run
-from test_gpu_thumbnails import Pack, batch_of
+from gpu_calls import WILD, run_tensors as run
+from gpu_pack import E_ARG, GUARD, IMAGENET, Pack, batch_of, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 SOFT, RGB, ONE, STRIP, CHECK, TALL = 0, 1, 2, 3, 4, 5
 SHAPES = [(67, 45, 4), (67, 45, 3), (1, 1, 4), (130, 34, 4), (70, 66, 4), (4, 4160, 4)]
 
@@ -42,26 +40,6 @@ def pixels():
     check[:, :, 3] = ((xx // 2 + yy // 2) % 2) * 255
     tall = rng.integers(0, 256, size=(4160, 4, 4), dtype=np.uint8)
     return [soft, rgb, one, strip, check, tall]
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")

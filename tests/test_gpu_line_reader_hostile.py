@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import chain_model as cm
-from test_transcode_line_fetch import api, lctx, oracle  # noqa: F401  (fixtures)
+from gpu_pack import api, lctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 

@@ -14,24 +14,12 @@ import pytest
 
 import cases
 from gpu_util import GUARD, OUT_FILL, STREAM_FILL, EdgeBatch, GuardedRegion
+from gpu_pack import api, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(517, 313), (1025, 3), (7, 3)]          # 159 slabs (three groups of 64 sets, partial last slab and last set) / 4 slabs / a few pixels
 ROTATION = ("full", "constant", "uiflat", "photo", "full")      # a full slot in front of another header, a flat image behind a full slot
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 class Vault:

@@ -12,12 +12,11 @@ import mode_cases as MC
 import table_tiles as TT
 from qoi_amd import mode, tensors
 from qoi_amd.tensors import ALPHA_WEIGHTED, BF16, CHW, F16, F32, FILTER_AREA, FILTER_MODE, FILTER_NEAREST, HW, HWC, I32, I64, PLAIN, U8
-from test_gpu_encode_packed import filled
-from test_gpu_labels import GUARD, fmt_of, run
-from test_gpu_thumbnails import Pack, batch_of
+from gpu_calls import fmt_of, run_label_tensors as run
+from gpu_pack import E_ARG, GUARD, Pack, batch_of, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
 DTYPES = (U8, F16, BF16, F32, I32, I64)
 LAYOUTS = (HWC, CHW, HW)
 SMALL, WIDE, DISTINCT, BLOCKS, CONST, SIXTEEN, LONG, TALL = range(8)
@@ -41,26 +40,6 @@ def pixels():
     const[:] = (9, 200, 31, 77)
     return MC.images() + [distinct, blocks, const, MC.label_map(64, 48, 4, 5, 13), MC.PALETTE[rng.integers(0, 3, size=(3, 16384))][:, :, :3],
                           MC.PALETTE[rng.integers(0, 3, size=(16384, 3))][:, :, :3]]
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")

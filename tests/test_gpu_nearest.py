@@ -2,7 +2,7 @@
 every output is compared bit for bit, over its whole length, with the definition - the oracle decodes the stream at the call's output
 channel count, qoi_amd/warp.py selects from that, qoi_amd/tensors.py: convert makes the tensor (each u8 model is computed once and shared).
 The pack is small: 130 x 70 photographs with 4 and with 3 channels, a 64 x 64 label map (four values in sharp regions), a 4096 x 1 strip
-and a 1 x 1 image.  Outputs stand behind, between and in front of guard bytes (test_gpu_warp.py: run; test_gpu_tensors.py: run); every
+and a 1 x 1 image.  Outputs stand behind, between and in front of guard bytes (gpu_calls.py: run_warp, run_tensors); every
 guard byte is checked after every call."""
 import ctypes
 
@@ -12,14 +12,11 @@ import pytest
 from qoi_amd import tensors, warp
 from qoi_amd.tensors import CHW, F16
 from qoi_amd.warp import ALPHA_WEIGHTED, NEAREST, ONE, PLAIN, REPLICATE
-from test_gpu_encode_packed import filled
-from test_gpu_tensors import IMAGENET, WARP, run
-from test_gpu_thumbnails import Pack, batch_of
-from test_gpu_warp import run as run_warp
+from gpu_calls import WARP, run_tensors as run, run_warp
+from gpu_pack import E_ARG, GUARD, IMAGENET, Pack, batch_of, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 FILL = 0x40C08020
 PHOTO4, PHOTO3, LABELS, STRIP, DOT = 0, 1, 2, 3, 4
 SHAPES = [(130, 70, 4), (130, 70, 3), (64, 64, 4), (4096, 1, 4), (1, 1, 4)]
@@ -38,26 +35,6 @@ def pixels():
     strip = rng.integers(0, 256, size=(1, 4096, 4), dtype=np.uint8)
     dot = np.array([[[200, 100, 50, 180]]], dtype=np.uint8)
     return [photo4, photo3, labels, strip, dot]
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")

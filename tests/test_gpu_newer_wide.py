@@ -6,7 +6,7 @@ between small ones, encoded by the oracle and decoded by it for the expectation 
 index is at least 2**24: a block of noise (the flat pieces of the image would forgive a misplaced sample) and a label map of five classes
 (ordinary image content has no majority for FILTER_MODE).  Every expectation is the existing definition - the oracle's decode at the call's
 output channel count, the model of qoi_amd/, tensors.convert -, every comparison is exact and covers the whole output, and every byte around
-the outputs is a guard (0xA5) checked after every call (tests/test_gpu_labels.py: run; tests/test_gpu_warp.py: run).
+the outputs is a guard (0xA5) checked after every call (tests/gpu_calls.py: run_label_tensors, run_warp).
 Part 3 holds the kernels of the folding borders and of supersampling to the same two regimes: warp_border_bytes and warp_border_tensor walk
 border_walk_table - more tiles than workgroups, a map that spans six and a half periods of the rectangle, so that tiles take either branch of
 warp_fold_position and some both (test_warp_border_walks_many_tiles_per_workgroup, test_warp_border_and_super_tensor_kernels_walk_many_tiles)
@@ -16,60 +16,17 @@ import numpy as np
 import pytest
 
 import resize_window as rw
-from mode_cases import label_map
 from qoi_amd import mode, nearest, tensors, warp
 from qoi_amd.tensors import CHW, F16, F32, FILTER_BICUBIC, FILTER_LANCZOS, FILTER_MODE, FILTER_NEAREST, HW, HWC, I32, I64, U8
 from qoi_amd.warp import ALPHA_WEIGHTED, BICUBIC, NEAREST, ONE, PLAIN, REFLECT, REFLECT_101, REPLICATE, SUPER2, SUPER4, WRAP
-from test_gpu_encode_packed import KINDS, image
-from test_gpu_labels import IMAGENET
-from test_gpu_labels import run as run_tensors
-from test_gpu_resize_wide import OraclePack
-from test_gpu_warp import run as run_warp
+from gpu_calls import run_label_tensors as run_tensors, run_warp
+from gpu_pack import IMAGENET, KINDS, OraclePack, image
+from gpu_pack import api, ctx, cus, oracle  # noqa: F401  (fixtures)
+from wide_cases import DOT, FILL, FIRST_ROW, HH, HUGE, HW_, LABELS_AT, NOISE_AT, NOISE_RECT, ODD, SPRITE, huge_with_plantings, past_2_24, super_walk_table, super_windows, walk_shape, window_of
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(1, 1, 4), (37, 23, 3), rw.HUGE + (4,), (130, 70, 4)]
-DOT, ODD, HUGE, SPRITE = range(4)
-HW_, HH = rw.HUGE
-FIRST_ROW = -(-(1 << 24) // HW_)       # 3641: from this row on every pixel of `huge` has an index of at least 2**24
-NOISE_AT = (96, 3650, 420, 186)        # (x, y, width, height) of the planted noise ...
-LABELS_AT = (1000, 3644, 1200, 192)    # ... and of the planted label map
-FILL = 0x40C08020
 assert FIRST_ROW * HW_ >= 1 << 24 > (FIRST_ROW - 1) * HW_ and all(y >= FIRST_ROW and y + h <= HH and x + w <= HW_ for x, y, w, h in (NOISE_AT, LABELS_AT))
-
-
-def huge_with_plantings():
-    D = rw.huge_image()
-    x, y, w, h = NOISE_AT
-    D[y:y + h, x:x + w] = np.random.default_rng(24).integers(0, 256, size=(h, w, 4), dtype=np.uint8)
-    x, y, w, h = LABELS_AT
-    D[y:y + h, x:x + w] = label_map(w, h, 4, 5, 24)
-    return D
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-@pytest.fixture(scope="module")
-def cus():
-    import torch
-    return torch.cuda.get_device_properties(0).multi_processor_count
 
 
 @pytest.fixture(scope="module")
@@ -78,17 +35,6 @@ def pack(api, oracle):
     p = OraclePack(api, oracle, SHAPES, pixels)
     assert np.array_equal(p.decoded(HUGE, 4).reshape(-1), p.px[HUGE])      # the oracle gives back what it was given
     return p
-
-
-def first_index(it):
-    """the staged pixel index of the first - the lowest - pixel of an item's rectangle"""
-    return it[2] * HW_ + it[1]
-
-
-def past_2_24(items):
-    """the items over `huge`: at least two, and not one pixel of their rectangles has an index below 2**24"""
-    big = [it for it in items if it[0] == HUGE]
-    return len(big) >= 2 and all(first_index(it) >= 1 << 24 for it in big)
 
 
 def u8_of(p, filt, it, och, alpha_mode):
@@ -238,7 +184,6 @@ def test_warp_bicubic_walks_many_tiles_per_workgroup(ctx, pack, cus):
 
 # ------------------------------------------------------------------ 3: the border kernels and the super tensor kernel in both regimes
 _WARPED = {}
-NOISE_RECT = (100, 3652, 400, 180)
 F16_CHW = (F16, CHW, *IMAGENET)
 
 
@@ -250,38 +195,6 @@ def warped_once(p, it, och, alpha_mode):
         P.setflags(write=False)
         _WARPED[key] = P
     return _WARPED[key]
-
-
-def walk_shape(cus):
-    """(ow, oh, across, down) of an output of more than 3 * 8 * cus tiles of 16 x 16 whose last tile column and row are partial"""
-    across = 80
-    down = (3 * 8 * cus) // across + 1
-    return 16 * across - 3, 16 * down - 5, across, down
-
-
-def window_of(it, X0, Y0, ow, oh):
-    """the item whose output is the ow x oh window at (X0, Y0) of `it`'s: U = U' + 2 * X0 and V = V' + 2 * Y0 move every sub-sample's sum by
-    2 * s * (a * X0 + b * Y0), a multiple of s, so the shift passes it on exactly: c' = c + 2 * (a * X0 + b * Y0), f' likewise"""
-    i, x, y, cw, rh, _, _, flags, a, b, d, e, fill, _, c, f = it
-    return warp.item(i, (x, y, cw, rh), (ow, oh), (a, b, c + 2 * (a * X0 + b * Y0), d, e, f + 2 * (d * X0 + e * Y0)), flags, fill)
-
-
-def super_walk_table(cus):
-    """(items, big's index) of tests/test_gpu_warp_super.py: test_many_tiles_per_workgroup_beyond_2_24 - [small, big, small x 5, small]: big shears
-    the planted noise under SUPER2 | REFLECT into more than 3 * 8 * cus tiles, the five behind it are one-tile items of `huge` of both flags and
-    the older samplings"""
-    ow, oh, _, _ = walk_shape(cus)
-    rect = NOISE_RECT
-    a, b, d, e = round(ONE * 1.1 * rect[2] / ow), round(ONE * 0.12 * rect[2] / oh), round(-ONE * 0.1 * rect[3] / ow), round(ONE * 1.1 * rect[3] / oh)
-    big = warp.item(HUGE, rect, (ow, oh), (a, b, rect[2] * ONE - a * ow - b * oh, d, e, rect[3] * ONE - d * ow - e * oh), SUPER2 | REFLECT, FILL)     # a shear about the centre
-    kinds = (SUPER4 | REPLICATE, NEAREST, SUPER2, BICUBIC | WRAP, SUPER4 | REFLECT_101)
-    inner = [warp.item(HUGE, (HW_ - 19 - j, HH - 17 - j, 19, 17), (11 + j, 5), warp.rotation((19, 17), (11 + j, 5), 25.0 * j, 0.4), s, FILL) for j, s in enumerate(kinds)]
-    return [warp.item(DOT, (0, 0, 1, 1), (5, 4), (ONE // 3, 0, 0, 0, ONE // 3, 0), SUPER4, FILL), big] + inner + [warp.item(SPRITE, (100, 40, 30, 30), (7, 7), (4 * ONE, 0, 0, 0, 4 * ONE, 0), SUPER4)]
-
-
-def super_windows(ow, oh):
-    """the four 45 x 27 windows of the big entry of super_walk_table that are compared with the model: the corners of the walk"""
-    return ((0, 0), (ow - 45, 3), (5, oh - 27), (ow - 45, oh - 27))
 
 
 BIG_BORDERS = {"bilinear, reflect": REFLECT, "bicubic, wrap": BICUBIC | WRAP}

@@ -77,23 +77,18 @@ from qoi_amd.imagediff import DIFF_DTYPE, DIFF_PIXELS, NONE, diff
 from qoi_amd.tensors import (BF16, CHW, F16, F32, FILTER_AREA, FILTER_BICUBIC, FILTER_BILINEAR, FILTER_LANCZOS, FILTER_MODE, FILTER_NEAREST, HW, HWC, I32, I64,
                              U8)
 from seek_cases import cases as seek_cases
-from test_gpu_encode_packed import filled, image
-from test_gpu_thumbnails import Pack, batch_of
-from test_packed_api import offsets as pack_offsets
+from gpu_calls import assert_outputs as assert_bytes
+from gpu_pack import IMAGENET, Pack, batch_of, filled, image
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
+from model_cases import pack_offsets
+from wide_cases import ARENA, B32, layout, tensor_offsets
 
 gpu = pytest.mark.gpu
-B32 = 1 << 32
-MIB = 1 << 20
-ARENA = B32 + 96 * MIB
 GUARD, SRC_FILL = 0xA5, 0x5C
 GUARD64 = int.from_bytes(bytes([GUARD]) * 8, "little", signed=True)
-LANE = 4 * MIB                  # the room of one layout's control items, and of its items beyond B32
-CONTROL = 16 * MIB              # control items: [16 MiB + lane * 4 MiB, + 4 MiB), lanes 0..7; [0, 16 MiB) is the alias of a straddling item's tail
-BEYOND = B32 + 48 * MIB         # items beyond: [B32 + 48 MiB + lane * 4 MiB, + 4 MiB); their aliases lie from 48 MiB on, behind the control items
 PAGE = 4096
 SIDE = 16400                    # the smallest practical side at which side * side * 4 channels of f32 pass 2^32
 BIG_BYTES = SIDE * SIDE * 4 * 4
-IMAGENET = tensors.normalise((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
 F32_CHW, F32_HWC = (F32, CHW, *IMAGENET), (F32, HWC, *IMAGENET)
 FILL = 0xFF804020               # opaque, four distinct bytes
 CONSTANT = (200, 17, 90, 255)   # the constant image of part 2: four distinct values, opaque
@@ -135,37 +130,6 @@ def test_the_tent_filter_keeps_a_constant():
 
 
 # ------------------------------------------------------------------ the arenas
-def layout(sizes, elem=1, lane=0, straddle=True, spans=None):
-    """Byte offsets for items of `sizes` bytes in an arena: the item with the longest span (the bytes really read or written, default: its
-    size) straddles B32 - unless straddle is False -, the others are control and beyond in turn, at odd element-aligned addresses with 1 to 3
-    guard bytes (in whole elements) between neighbours.  Asserts what makes a dropped high half a wrong answer and never a fault."""
-    sizes = [int(s) for s in sizes]
-    spans = sizes if spans is None else [int(s) for s in spans]
-    n = len(sizes)
-    assert 0 <= lane < 8 and sum(sizes) + 4 * elem * n + 256 <= LANE and all(0 < sp <= sz and sz % elem == 0 for sp, sz in zip(spans, sizes))
-    s = max(range(n), key=lambda j: spans[j]) if straddle else -1
-    offsets = [0] * n
-    pos = {False: CONTROL + lane * LANE + 64 + elem, True: BEYOND + lane * LANE + 64 + elem}
-    far = False
-    for j in range(n):
-        if j == s:
-            k = (spans[j] // elem // 2 | 1) * elem
-            assert 0 < k < spans[j] and k // elem % 2 == 1
-            offsets[j] = B32 - k
-        else:
-            offsets[j] = pos[far]
-            pos[far] += sizes[j] + -(-(1 + j % 3) // elem) * elem
-            far = not far
-    ranges = sorted(zip(offsets, sizes))
-    assert all(o % elem == 0 and 0 <= o and o + sz <= ARENA for o, sz in ranges)
-    assert all(a + sz <= b for (a, sz), (b, _) in zip(ranges, ranges[1:]))
-    kinds = {"control" if o + sz <= B32 else "straddling" if o < B32 else "beyond" for o, sz in ranges}
-    assert kinds == ({"control", "straddling", "beyond"} if straddle else {"control", "beyond"}), kinds
-    for o, sz in ranges:                                           # the alias of whatever lies beyond B32: inside the arena, on no item
-        if o + sz > B32:
-            lo, hi = max(o, B32) - B32, o + sz - B32
-            assert 0 <= lo < hi <= ARENA and all(hi <= a or a + n2 <= lo for a, n2 in ranges), (o, sz)
-    return offsets
 
 
 def flat(a):
@@ -260,12 +224,6 @@ class Dest:
         return got
 
 
-def assert_bytes(got, want, what):
-    for j, (g, w) in enumerate(zip(got, want)):
-        w = flat(w)
-        assert g.size == w.size and np.array_equal(g, w), (what, "output", j, "first difference at byte", int(np.argmax(g != w)), "of", w.size)
-
-
 def into_dst(dst, want, call, what, elem=1, lane=0, spans=None, sizes=None):
     """call(base of dst, offsets) writes want[j] to a control, a straddling or a beyond placement; every other byte of dst stays the guard"""
     want = [flat(w) for w in want]
@@ -276,24 +234,6 @@ def into_dst(dst, want, call, what, elem=1, lane=0, spans=None, sizes=None):
 
 
 # ------------------------------------------------------------------ fixtures
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -475,15 +415,9 @@ def test_encode_tiles(ctx, oracle, pack, src, dst):
     src.check()
 
 
-def tensor_offsets():
-    """pixel_offsets of the tensor call: ingest_cases.WIDE_SPECS control, across byte B32 (the longest: f32 CHW) and beyond in turn; every
-    offset is a multiple of 4, the largest element"""
-    return layout([tiles.source_bytes(w, h, sch, tiles.source_flags(*fmt)) for w, h, sch, fmt in ingest_cases.WIDE_SPECS], elem=ingest_cases.WIDE_ELEM, lane=2)
-
-
 def wide_tensors(seed):
     """the tensors of ingest_cases.WIDE_SPECS: random elements over both clamps of each range"""
-    from test_gpu_ingest import elements
+    from gpu_calls import elements
     rng = np.random.default_rng(seed)
     return [np.ascontiguousarray(elements(rng, w * h * sch, fmt[0], fmt[2])).reshape((sch, h, w) if fmt[1] == tiles.CHW else (h, w, sch))
             for w, h, sch, fmt in ingest_cases.WIDE_SPECS]

@@ -7,35 +7,16 @@ import numpy as np
 import pytest
 
 from qoi_amd import streaminfo as si
-from test_gpu_inspect import assert_info
-from test_gpu_packed import GUARD, Item, dev, filled
-from test_packed_api import offsets
+from gpu_calls import assert_info
+from gpu_pack import GUARD, Item, dev, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
+from model_cases import pack_offsets as offsets
 
 pytestmark = pytest.mark.gpu
 B32 = 1 << 32
 INT_MAX, INT_MIN = (1 << 31) - 1, -(1 << 31)
 STRIDE_MAX = 0x7FFFFFFF + 256          # the largest stride qoimi_pack_streams takes
 N = 2 * 8192 + 5                       # two tiles of pack_offsets and five lengths of a third
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 def clamp(lens, stride):

@@ -8,55 +8,11 @@ import numpy as np
 import pytest
 
 import cases
-from test_packed_api import offsets
+from gpu_pack import E_ARG, GUARD, Item, dev, filled, packed_image as image
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
+from model_cases import pack_offsets as offsets
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-def dev(arr):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(arr)).cuda()
-
-
-def filled(n, value=GUARD):
-    import torch
-    return torch.full((int(n),), value, dtype=torch.uint8, device="cuda")
-
-
-def image(kind, w, h, ch, frame=0):
-    from qoi_amd import synth
-    if kind == "rand":
-        return np.random.default_rng(w * 7919 + h * 31 + ch + frame).integers(0, 256, size=w * h * ch, dtype=np.uint8)
-    return (synth.frame_rgba if ch == 4 else synth.frame_rgb)(kind, w, h, frame).reshape(-1)
-
-
-class Item:
-    def __init__(self, api, oracle, kind, w, h, ch, frame=0, stream=None):
-        self.w, self.h, self.ch = w, h, ch
-        self.stream = stream if stream is not None else oracle.encode(image(kind, w, h, ch, frame), w, h, ch)
-        self.desc = api.QoiDesc(w, h, ch, 0)
 
 
 def mixed_items(api, oracle):

@@ -7,34 +7,13 @@ import numpy as np
 import pytest
 
 from qoi_amd import pixelstats as ps
-from test_gpu_crops import standard
-from test_gpu_encode_packed import KINDS, Batch, dev, filled
-from test_gpu_thumbnails import MIXED_SHAPES, Pack
+from gpu_calls import standard_crops as standard
+from gpu_pack import GUARD, KINDS, MIXED_SHAPES, Batch, Pack, dev, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-GUARD = 0xA5
 BIG = 7                               # 130 x 70 x 4, sprite_alpha
 T = ps.TILE_PX
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -46,7 +25,7 @@ def mixed(api, ctx, oracle):
 
 
 class OraclePack(Pack):
-    """Given pixels as the oracle's streams, one behind the other in one device buffer; decoded(): tests/test_gpu_thumbnails.py: Pack."""
+    """Given pixels as the oracle's streams, one behind the other in one device buffer; decoded(): tests/gpu_pack.py: Pack."""
 
     def __init__(self, api, oracle, shapes, pixels):
         self.oracle, self.n, self.shapes = oracle, len(shapes), shapes

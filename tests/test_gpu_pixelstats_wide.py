@@ -9,10 +9,9 @@ import numpy as np
 import pytest
 
 from qoi_amd import pixelstats as ps
-from test_gpu_encode_packed import dev, filled
+from gpu_pack import GUARD, dev, filled
 
 pytestmark = pytest.mark.gpu
-GUARD = 0xA5
 T = ps.TILE_PX
 EDGE = 66052
 

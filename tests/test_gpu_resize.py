@@ -11,33 +11,12 @@ import pytest
 from qoi_amd import crops, resize, thumbs
 from qoi_amd.packplan import slot
 from qoi_amd.resize import ALPHA_WEIGHTED, PLAIN
-from test_gpu_encode_packed import KINDS, Batch, dev, filled
-from test_gpu_thumbnails import MIXED_SHAPES, Pack
+from gpu_calls import run_resized as run, sizes_of, standard
+from gpu_pack import E_ARG, GUARD, KINDS, MIXED_SHAPES, Batch, Pack, dev, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 BIG = 7                               # 130 x 70 x 4, sprite_alpha
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -51,42 +30,6 @@ def mixed(api, ctx, oracle):
 @pytest.fixture(scope="module")
 def equal(api, ctx, oracle):
     return Pack(ctx, oracle, Batch(api, oracle, [(64, 48, 4)] * 7, [KINDS[i % 5] for i in range(7)]))
-
-
-def standard(i, w, h, first_flag=0):
-    """identity; the whole image to 1 x 1 where the cap allows, else to ceil(w/64) x ceil(h/64); a non-integer downscale (130 x 70 -> 37 x 23,
-    smaller images in that proportion); an interior rectangle with odd origin and odd size to an odd size; an upscale of a 1 x 1 and of a
-    (up to) 5 x 3 rectangle; down in x with up in y; the flag values take turns"""
-    out = [(0, 0, w, h, w, h), (0, 0, w, h, -(-w // 64), -(-h // 64)), (0, 0, w, h, max(1, w * 37 // 130), max(1, h * 23 // 70))]
-    if w >= 3 and h >= 4:
-        out.append((1, 3, w - 1 if (w - 1) % 2 else w - 2, h - 3 if (h - 3) % 2 else h - 4, 7, 5))
-    out.append((w - 1, h - 1, 1, 1, 4, 3))
-    out.append((w // 3, h // 3, min(5, w - w // 3), min(3, h - h // 3), 13, 7))
-    out.append((0, 0, w, min(h, 3), max(1, w // 3), 8))
-    return [(i, x, y, cw, rh, ow, oh, (first_flag + k) & 3) for k, (x, y, cw, rh, ow, oh) in enumerate(out)]
-
-
-def sizes_of(items, och):
-    return [it[5] * it[6] * och for it in items]
-
-
-def run(ctx, p, channels, items, mode=PLAIN, staging=0, offsets=None, total=None, sizes=None, packed=None, front=64, descs=None):
-    """One call; outputs back to back behind `front` guard bytes unless offsets are given.  Returns the outputs."""
-    och = channels or p.shapes[items[0][0]][2]
-    nbytes = sizes_of(items, och)
-    if offsets is None:
-        offsets = [front + int(x) for x in np.cumsum([0] + nbytes[:-1])]
-    if total is None:
-        total = max(o + n for o, n in zip(offsets, nbytes)) + 64
-    buf = filled(total, GUARD)
-    ctx.decode_resized((p.packed if packed is None else packed).data_ptr(), p.so, p.sizes if sizes is None else sizes, p.descs if descs is None else descs,
-                       channels, items, mode, buf.data_ptr(), offsets, staging)
-    got = buf.cpu().numpy()
-    mask = np.ones(total, dtype=bool)
-    for o, n in zip(offsets, nbytes):
-        mask[o:o + n] = False
-    assert np.all(got[mask] == GUARD), ("a byte outside the outputs was written", int(np.argmax(mask & (got != GUARD))))
-    return [got[o:o + n] for o, n in zip(offsets, nbytes)]
 
 
 def want(p, it, och, mode, **how):

@@ -10,80 +10,21 @@ import numpy as np
 import pytest
 
 import resize_window as rw
-import test_gpu_thumbnails as tgt
 from qoi_amd import crops, resize, thumbs
 from qoi_amd.imagediff import DIFF_DTYPE, DIFF_PIXELS, NONE, pixel_word
 from qoi_amd.packplan import slot
 from qoi_amd.resize import ALPHA_WEIGHTED, PLAIN
-from test_gpu_encode_packed import KINDS, dev, filled, image
-from test_gpu_resize import run, standard
-from test_gpu_thumbnails import MIXED_SHAPES, Pack
+from gpu_calls import run_resized as run, run_thumbnails, standard
+from gpu_pack import GUARD, KINDS, MIXED_SHAPES, OraclePack, dev, filled, image
+from gpu_pack import api, ctx, cus, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-GUARD = 0xA5
 B32 = rw.B32
 SHAPES = [(1, 1, 4), (37, 23, 3), rw.HUGE + (4,), (1, 97, 4), (131, 1, 3), (257, 9, 4), (64, 48, 3), (333, 7, 4), rw.WIDE + (4,), (130, 70, 4), (127, 127, 4)]
 HUGE, WIDE, T127, SPRITE = 2, 8, 10, 9
 LARGE = (HUGE, WIDE)                   # resampled rectangles of these are expected from windows; the others from the model itself
 HW, HH = rw.HUGE
 CMP_TILE_PX = 4096                     # qoi_compare.hip: kCmpTilePx
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-@pytest.fixture(scope="module")
-def cus():
-    import torch
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-class OraclePack(Pack):
-    """Given pixels as the oracle's streams, 3 bytes apart in one device buffer; decoded(): tests/test_gpu_thumbnails.py: Pack.  px[i]: the
-    source pixels, window(): the sums of an item over the oracle's 4-channel decode, computed once per rectangle."""
-
-    def __init__(self, api, oracle, shapes, pixels):
-        self.oracle, self.n, self.shapes = oracle, len(shapes), shapes
-        self.px = [np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in pixels]
-        streams = [oracle.encode(p, w, h, ch) for p, (w, h, ch) in zip(self.px, shapes)]
-        self.descs = [api.QoiDesc(w, h, ch, 0) for (w, h, ch) in shapes]
-        self.sizes = [len(s) for s in streams]
-        self.so = [int(x) for x in np.cumsum([5] + [n + 3 for n in self.sizes[:-1]])]
-        self.host = np.zeros(self.so[-1] + self.sizes[-1] + 64, dtype=np.uint8)
-        for o, s in zip(self.so, streams):
-            self.host[o:o + len(s)] = np.frombuffer(s, dtype=np.uint8)
-        self.packed = dev(self.host)
-        self._decoded, self._windows, self._boxes = {}, {}, {}
-
-    def box(self, i, och, f, mode):
-        """rw.box_thumbnail of image i, computed once"""
-        key = (i, och, f, mode if och == 4 else PLAIN)
-        if key not in self._boxes:
-            self._boxes[key] = rw.box_thumbnail(self.decoded(i, och), f, mode).reshape(-1)
-        return self._boxes[key]
-
-    def window(self, it):
-        key = tuple(it[:7])
-        if key not in self._windows:
-            self._windows[key] = rw.Window(self.decoded(it[0], 4), it[1:5], it[5:7])
-        return self._windows[key]
 
 
 @pytest.fixture(scope="module")
@@ -242,7 +183,7 @@ def test_resize_walks_many_tiles_per_workgroup(ctx, pack, cus):
         assert np.array_equal(got[2], cropped[64:-64]) and np.all(cropped[:64] == GUARD) and np.all(cropped[-64:] == GUARD)
         # the half is the thumbnail at 2, and what decode_thumbnails gives on the device
         assert np.array_equal(got[8], p.box(HUGE, channels, 2, mode))
-        reduced, _, _ = tgt.run(ctx, p, channels, [2] * p.n, mode)
+        reduced, _, _ = run_thumbnails(ctx, p, channels, [2] * p.n, mode)
         assert np.array_equal(got[8], reduced[HUGE])
         for j in (0, 1, 3, 4, 5, 6, 7, 9):
             assert np.array_equal(got[j], want(p, items[j], channels, mode)), (channels, j)
@@ -302,7 +243,7 @@ def test_thumbnails_walk_many_tiles_per_workgroup(ctx, pack, cus, mode):
             assert sum(tiles) > 3 * 8 * cus and tiles[HUGE] == (HW // f) * (HH // f) // 256
         else:
             assert tiles[HUGE] == 270
-        got, _, _ = tgt.run(ctx, p, channels, [f] * p.n, mode)
+        got, _, _ = run_thumbnails(ctx, p, channels, [f] * p.n, mode)
         assert ctx.thumbnail_stats()[:2] == (1, 1)
         for i in range(p.n):
             w = p.box(i, channels, f, mode) if i == HUGE else thumbs.thumbnail(p.decoded(i, channels), f, mode).reshape(-1)
@@ -310,7 +251,7 @@ def test_thumbnails_walk_many_tiles_per_workgroup(ctx, pack, cus, mode):
         if f == 2:
             staging = slot(HW * HH * 4)
             assert [c for _, c in plan([w * h * 4 for (w, h, _) in p.shapes], staging)] == [2, 1, 8]
-            again, _, _ = tgt.run(ctx, p, channels, [f] * p.n, mode, staging=staging)
+            again, _, _ = run_thumbnails(ctx, p, channels, [f] * p.n, mode, staging=staging)
             assert ctx.thumbnail_stats()[:2] == (3, 3) and all(np.array_equal(a, b) for a, b in zip(again, got))
 
 

@@ -10,24 +10,10 @@ import pytest
 from qoi_amd import packplan
 from qoi_amd import seekindex as si
 from seek_cases import DevicePack, cases
+from gpu_pack import E_ARG
+from gpu_pack import api, ctx  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
 
 
 @pytest.fixture(scope="module")

@@ -10,32 +10,11 @@ import pytest
 
 from qoi_amd import seekindex as si
 from seek_cases import Case, DevicePack, cases
-from test_gpu_encode_packed import filled
+from gpu_pack import E_ARG, GUARD, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 PIXEL_FILL = 0xC3
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 def my_cases(oracle):

@@ -29,7 +29,9 @@ from qoi_amd import streaminfo, synth
 from qoi_amd.imagediff import DIFF_DTYPE, DIFF_PIXELS, diff
 from qoi_amd.packplan import plan as pack_plan
 from stream_order import Case, Harness, Inp, Out, back_to_back, rotated, stale_stream, stream_taking_calls, u8
-from test_packed_api import offsets as pack_offsets
+from gpu_pack import IMAGENET
+from gpu_pack import api, oracle  # noqa: F401  (fixtures)
+from model_cases import pack_offsets
 
 gpu = pytest.mark.gpu
 SHAPES = [(160, 120, 4), (97, 61, 3), (130, 70, 4), (64, 48, 3)]
@@ -103,19 +105,6 @@ class World:
 
     def pixels_inp(self):
         return Inp(self.blob(self.px, self.po, self.px_bytes), None)
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -500,7 +489,6 @@ CROPS = [(0, 5, 17, 101, 50, 1), (1, 0, 9, 37, 20, 2), (2, 8, 13, 33, 30, 3), (3
 ITEMS = [(0, 8, 17, 120, 90, 43, 23, 1), (1, 0, 9, 90, 40, 50, 40, 2), (2, 3, 13, 100, 50, 40, 30, 3), (3, 0, 0, 64, 48, 9, 5, 0)]
 FACTORS = [3, 2, 5, 4]
 MAPS = [(0, (20, 17, 100, 50), (33, 18), 30.0, 0.3), (1, (3, 9, 30, 20), (17, 16), 30.0, 0.5), (2, (0, 13, 64, 35), (41, 29), -20.0, 0.4)]
-IMAGENET = tensors.normalise((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
 assert all(it[2] >= INTERVALS[it[0]] for it in CROPS[:3] + ITEMS[:3]) and all(m[1][1] >= INTERVALS[m[0]] for m in MAPS)   # (indexed: below a seek row)
 
 

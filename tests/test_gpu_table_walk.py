@@ -5,37 +5,18 @@ items, lane counts and table strides (tests/table_tiles.py: items; tests/test_ta
 tiles a workgroup runs back to back always differ, that a workgroup begins inside an item and that workgroups step from item to item).  Every
 output is compared bit for bit, over its whole length, with the definition - the oracle decodes the stream at the call's output channel count,
 qoi_amd/bicubic.py or lanczos.py resamples that, qoi_amd/tensors.py: convert makes the tensor; each of the few distinct items is computed
-once - and every guard byte between and around the outputs is checked (test_gpu_tensors.py: layout_of, run)."""
+once - and every guard byte between and around the outputs is checked (gpu_calls.py: tensor_layout, run_tensors)."""
 import numpy as np
 import pytest
 
 import table_tiles as tt
 from qoi_amd import tensors
 from qoi_amd.tensors import ALPHA_WEIGHTED, CHW, F16, FILTER_BICUBIC, FILTER_LANCZOS, HWC, PLAIN, U8
-from test_gpu_tensors import IMAGENET, run
-from test_gpu_thumbnails import Pack, batch_of
+from gpu_calls import run_tensors as run
+from gpu_pack import IMAGENET, Pack, batch_of
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")

@@ -15,41 +15,15 @@ import pytest
 from qoi_amd import bilinear, resize, tensors, warp
 from qoi_amd.tensors import BF16, CHW, F16, F32, FILTER_AREA, FILTER_BILINEAR, HWC, U8
 from qoi_amd.warp import ALPHA_WEIGHTED, PLAIN, REPLICATE
-from test_gpu_encode_packed import Batch, filled
-from test_gpu_thumbnails import Pack
+from gpu_calls import WARP, WILD, run_tensors as run, tensor_layout as layout_of
+from gpu_pack import E_ARG, GUARD, IMAGENET, Batch, Pack, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 FILL = 0x40C08020
-WARP = 2                               # the third kind of call, beside FILTER_AREA and FILTER_BILINEAR
 KIND_NAMES = {FILTER_AREA: "area", FILTER_BILINEAR: "bilinear", WARP: "warp"}
 BIG, PHOTO, NOISE, TINY = 0, 1, 2, 3
 SHAPES = [(200, 140, 4), (130, 70, 3), (64, 48, 4), (7, 5, 4)]
-
-IMAGENET = tensors.normalise((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
-# 255 * 300 - 300 is infinity in binary16; v * 2.4e-8 lies in its subnormals; v * 1e-40 in those of binary32 and bfloat16; -0 at v = 0
-WILD = (np.array([300.0, -1e-6, 2.4e-8, 1e-40], np.float32), np.array([-300.0, -0.0, -1e-41, 0.0], np.float32))
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -91,35 +65,6 @@ def model(p, kind, it, och, mode):
         P.setflags(write=False)
         _MODELS[key] = P
     return _MODELS[key]
-
-
-def layout_of(items, och, elem, front=None):
-    """(offsets, byte sizes, total): the first output at an odd element-aligned address, 1 to 3 guard bytes - in whole elements - between"""
-    nbytes = [it[5] * it[6] * och * elem for it in items]
-    pos = {1: 65, 2: 66, 4: 68}[elem] if front is None else front
-    offsets = []
-    for j, n in enumerate(nbytes):
-        offsets.append(pos)
-        pos += n + -(-(1 + j % 3) // elem) * elem
-    return offsets, nbytes, pos + 64
-
-
-def run(ctx, p, kind, channels, items, mode, f, staging=0, front=None):
-    """One call; returns the outputs as bytes.  The buffer's base is a multiple of 256 (torch's allocator), so the offsets are the alignment."""
-    och = channels or p.shapes[items[0][0]][2]
-    offsets, nbytes, total = layout_of(items, och, tensors.ELEM[f[0]], front)
-    buf = filled(total, GUARD)
-    assert buf.data_ptr() % 256 == 0
-    if kind == WARP:
-        ctx.decode_warped_tensors(p.packed.data_ptr(), p.so, p.sizes, p.descs, channels, items, mode, f, buf.data_ptr(), offsets, staging)
-    else:
-        ctx.decode_tensors(p.packed.data_ptr(), p.so, p.sizes, p.descs, channels, items, kind, mode, f, buf.data_ptr(), offsets, staging)
-    got = buf.cpu().numpy()
-    mask = np.ones(total, dtype=bool)
-    for o, n in zip(offsets, nbytes):
-        mask[o:o + n] = False
-    assert np.all(got[mask] == GUARD), ("a byte outside the outputs was written", int(np.argmax(mask & (got != GUARD))))
-    return [got[o:o + n] for o, n in zip(offsets, nbytes)]
 
 
 def assert_items(p, got, kind, items, och, mode, f, what):

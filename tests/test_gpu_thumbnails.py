@@ -10,74 +10,12 @@ import pytest
 
 from qoi_amd import thumbs
 from qoi_amd.thumbs import ALPHA_WEIGHTED, PLAIN
-from test_gpu_encode_packed import KINDS, Batch, dev, filled
+from gpu_calls import run_thumbnails as run, thumb_bytes
+from gpu_pack import E_ARG, GUARD, KINDS, MIXED_SHAPES, Batch, Pack, batch_of, dev, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
-MIXED_SHAPES = [(1, 1, 4), (1, 97, 4), (131, 1, 3), (37, 23, 3), (257, 9, 4), (64, 48, 3), (333, 7, 4), (130, 70, 4)]
 FACTORS = [2, 3, 4, 5, 7, 8, 16, 64]
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-class Pack:
-    """A batch encoded by the library into a pack (align 1), the pack's bytes on the host, and the oracle's decode of every stream as given
-    (computed once per output channel count and size, never changed)."""
-
-    def __init__(self, ctx, oracle, b):
-        import torch
-        cap = sum(b.bounds) + 256 * b.n
-        self.b, self.oracle, self.n, self.shapes, self.descs = b, oracle, b.n, b.shapes, b.descs
-        self.packed = filled(cap, 0)
-        off = torch.zeros(b.n + 1, dtype=torch.int64, device="cuda")
-        lens = torch.zeros(b.n, dtype=torch.int32, device="cuda")
-        so, sizes = ctx.encode_images_packed(b.d_px.data_ptr(), b.pix_off, b.descs, 1, self.packed.data_ptr(), cap, off.data_ptr(), lens.data_ptr())
-        self.so, self.sizes = [int(x) for x in so[:b.n]], [int(x) for x in sizes]
-        self.host = self.packed.cpu().numpy().copy()
-        self._decoded = {}
-
-    def decoded(self, i, och, host=None, size=None):
-        """the oracle's (lenient) decode of stream i as uint8[h, w, och]"""
-        w, h, _ = self.shapes[i]
-        if host is None and size is None:
-            if (i, och) not in self._decoded:
-                px, _ = self.oracle.decode(self.host[self.so[i]:self.so[i] + self.sizes[i]].tobytes(), och)
-                self._decoded[(i, och)] = px.reshape(h, w, och)
-            return self._decoded[(i, och)]
-        host = self.host if host is None else host
-        px, _ = self.oracle.decode(host[self.so[i]:self.so[i] + (self.sizes[i] if size is None else size)].tobytes(), och)
-        assert px is not None
-        return px.reshape(h, w, och)
-
-
-def batch_of(api, oracle, shapes, pixels):
-    """a Batch (tests/test_gpu_encode_packed.py) of given pixels instead of a content class"""
-    b = Batch.__new__(Batch)
-    b.shapes, b.px, b.n = shapes, [np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in pixels], len(shapes)
-    b.descs = [api.QoiDesc(w, h, ch, 0) for (w, h, ch) in shapes]
-    b.bounds = [api.encode_bound(w, h, ch) for (w, h, ch) in shapes]
-    b.pix_off = [int(x) for x in np.cumsum([0] + [p.size for p in b.px[:-1]])]
-    b.d_px = dev(np.concatenate(b.px))
-    return b
 
 
 @pytest.fixture(scope="module")
@@ -97,30 +35,6 @@ def all_rgb(api, ctx, oracle):
 @pytest.fixture(scope="module")
 def equal(api, ctx, oracle):
     return Pack(ctx, oracle, Batch(api, oracle, [(64, 48, 4)] * 13, [KINDS[i % 5] for i in range(13)]))
-
-
-def thumb_bytes(shapes, factors, och):
-    return [int(np.prod(thumbs.size(w, h, f))) * och for (w, h, _), f in zip(shapes, factors)]
-
-
-def run(ctx, p, channels, factors, mode, staging=0, offsets=None, total=None, sizes=None, packed=None):
-    """One call; thumbnails back to back behind 64 guard bytes unless offsets are given.  Returns (thumbnails, the whole buffer, offsets)."""
-    och = channels or p.shapes[0][2]
-    if isinstance(factors, int):
-        factors = [factors] * p.n
-    nbytes = thumb_bytes(p.shapes, factors, och)
-    if offsets is None:
-        offsets = [64 + int(x) for x in np.cumsum([0] + nbytes[:-1])]
-        total = offsets[-1] + nbytes[-1] + 64
-    buf = filled(total, GUARD)
-    ctx.decode_thumbnails((p.packed if packed is None else packed).data_ptr(), p.so, p.sizes if sizes is None else sizes, p.descs, channels, factors, mode,
-                          buf.data_ptr(), offsets, staging)
-    got = buf.cpu().numpy()
-    mask = np.ones(total, dtype=bool)
-    for o, n in zip(offsets, nbytes):
-        mask[o:o + n] = False
-    assert np.all(got[mask] == GUARD), ("a byte outside the thumbnails was written", int(np.argmax(mask & (got != GUARD))))
-    return [got[o:o + n] for o, n in zip(offsets, nbytes)], got, offsets
 
 
 def want(p, i, och, f, mode, **how):

@@ -5,42 +5,25 @@ images (tests/labelimg.py), whose blocks hold unique winners, ties the centre wi
 import numpy as np
 import pytest
 
-import test_gpu_encode_tiles as T
 from labelimg import label_image, loop
 from qoi_amd import tensors, tiles
+from gpu_calls import TILE_FILL, Sources, run_tiles, tile_model
+from gpu_pack import dev
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
+from model_cases import pack_offsets
 
 pytestmark = pytest.mark.gpu
-FILL = T.FILL
+FILL = TILE_FILL
 FACTORS = {tiles.NEAREST: (1, 2, 3, 4, 5, 8, 13, 16, 33, 64), tiles.MODE: (1, 2, 3, 4, 5, 8, 13, 16)}
 MODES = (tiles.NEAREST, tiles.MODE)
 
 
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
 def label_sources(api, shapes, seed=11, cell=5, noise=True):
-    """T.Sources whose images are label images; the buffer between them keeps its random bytes"""
-    s = T.Sources(api, shapes, seed)
+    """Sources whose images are label images; the buffer between them keeps its random bytes"""
+    s = Sources(api, shapes, seed)
     for i, (w, h, ch, _) in enumerate(shapes):
         s.img[i][:] = label_image(w, h, ch, seed + i, cell, noise)
-    s.d = T.dev(s.host)
+    s.d = dev(s.host)
     assert s.d.data_ptr() % 256 == 0
     return s
 
@@ -75,7 +58,7 @@ def shapes_of(src):
 def test_byte_identity(ctx, oracle, small, channels, mode):
     ts = mixed_tiles(mode)
     before = small.host.copy()
-    px, streams = T.model(oracle, small, ts, channels, mode)
+    px, streams = tile_model(oracle, small, ts, channels, mode)
     if mode == tiles.MODE and channels == 0:
         # the images hold every way a vote is decided, counted by the definition as a loop (and the model agrees with the loop)
         census = {}
@@ -83,8 +66,8 @@ def test_byte_identity(ctx, oracle, small, channels, mode):
             assert np.array_equal(p, loop(small.img[t[0]], t, channels, mode, census)), t
         assert census["unique"] > 100 and census["centre"] > 20 and census["lowest"] > 5, census
     retries = ctx.encode_retries()
-    T.run(ctx, small, ts, channels, mode, 1, streams, shift=3)
-    T.run(ctx, small, ts, channels, mode, 64, streams)
+    run_tiles(ctx, small, ts, channels, mode, 1, streams, shift=3)
+    run_tiles(ctx, small, ts, channels, mode, 64, streams)
     subs = tiles.plan(shapes_of(small), ts, channels, 0)[1]
     assert ctx.tile_stats()[:2] == (len(subs), len(subs)) and ctx.tile_stats()[3] == 5 and ctx.encode_retries() == retries
     assert np.array_equal(small.d.cpu().numpy(), before)       # the source is only read
@@ -94,24 +77,24 @@ def test_byte_identity(ctx, oracle, small, channels, mode):
 @pytest.mark.parametrize("mode", MODES)
 def test_sub_batches_and_a_capacity_cut(ctx, oracle, small, mode):
     ts = mixed_tiles(mode)
-    px, streams = T.model(oracle, small, ts, 0, mode)
+    px, streams = tile_model(oracle, small, ts, 0, mode)
     slots = tiles.plan(shapes_of(small), ts, 0, 0)[0]
     mid = sum(slots[:7]) + slots[7] // 2
     results = []
     for staging in (1, mid, 0):
         _, subs, largest, referenced = tiles.plan(shapes_of(small), ts, 0, staging)
-        results.append(T.run(ctx, small, ts, 0, mode, 16, streams, staging=staging)[:2])
+        results.append(run_tiles(ctx, small, ts, 0, mode, 16, streams, staging=staging)[:2])
         assert ctx.tile_stats() == (len(subs), len(subs), largest, referenced) and referenced == 5, (staging, ctx.tile_stats())     # [1]: launches of tile_select
     assert len(tiles.plan(shapes_of(small), ts, 0, 1)[1]) == len(ts) and 1 < len(tiles.plan(shapes_of(small), ts, 0, mid)[1]) < len(ts)
     for r in results[1:]:
         assert np.array_equal(r[0], results[0][0]) and np.array_equal(r[1], results[0][1])
     lens = [len(s) for s in streams]
-    want_off = T.offsets(lens, 4)
+    want_off = pack_offsets(lens, 4)
     k = len(ts) // 2
     cap = int(want_off[k]) + lens[k] // 2                       # cuts the list in the middle: whole streams are missing, nothing is partial
-    got_off, _, _ = T.run(ctx, small, ts, 0, mode, 4, streams, capacity=cap, shift=5, staging=sum(slots[:9]))
+    got_off, _, _ = run_tiles(ctx, small, ts, 0, mode, 4, streams, capacity=cap, shift=5, staging=sum(slots[:9]))
     assert int(got_off[-1]) > cap
-    T.run(ctx, small, ts, 0, mode, 4, streams, capacity=0, null_dest=True)
+    run_tiles(ctx, small, ts, 0, mode, 4, streams, capacity=0, null_dest=True)
 
 
 # ------------------------------------------------------------------ 3: the walk
@@ -122,7 +105,7 @@ def test_a_workgroup_walks_tiles_of_entries_with_different_lane_splits(api, ctx,
     S = src.img[0]
     S[:, 336:352] = label_image(16, 1024, 4, 5, cell=2)          # noise in a narrow band only: most blocks are constant, the model stays quick
     S[500:508, :] = label_image(1024, 8, 4, 6, cell=3)
-    src.d = T.dev(src.host)
+    src.d = dev(src.host)
     workgroups = 8 * torch.cuda.get_device_properties(0).multi_processor_count
     calls = {tiles.MODE: [(0, 0, 0, 1024, 1024, f, k & 3) for k, f in enumerate((2, 3, 4, 16))],
              tiles.NEAREST: [(0, 0, 0, 1024, 1024, 1, 0), (0, 0, 0, 1024, 1024, 64, 3), (0, 0, 0, 1024, 1024, 1, 1), (0, 0, 0, 1024, 1024, 2, 2), (0, 0, 0, 1024, 1024, 1, 2)]}
@@ -130,8 +113,8 @@ def test_a_workgroup_walks_tiles_of_entries_with_different_lane_splits(api, ctx,
         count = sum(tiles.select_tiles(t[3], t[4], t[5], 4, mode) for t in ts)
         assert count > workgroups + 2, (mode, count, workgroups)
         assert len({tiles.select_split(t[5], mode)[0] for t in ts}) == (3 if mode == tiles.MODE else 1)
-        px, streams = T.model(oracle, src, ts, 0, mode)
-        T.run(ctx, src, ts, 0, mode, 1, streams)
+        px, streams = tile_model(oracle, src, ts, 0, mode)
+        run_tiles(ctx, src, ts, 0, mode, 1, streams)
         assert ctx.tile_stats()[:2] == (1, 1)
     census = {}
     band = (0, 0, 495, 1023, 15, 3, 0)                          # blocks of the MODE call's f = 3 entry, counted by the definition as a loop
@@ -175,12 +158,12 @@ def test_round_trip_with_the_serving_side(api, ctx, mode, filt):
 def test_the_box_filter_after_a_label_call_gives_its_bytes(ctx, oracle, small):
     ts = mixed_tiles(tiles.MODE)
     for first in MODES:
-        _, streams = T.model(oracle, small, ts, 0, first)
-        T.run(ctx, small, ts, 0, first, 1, streams)
+        _, streams = tile_model(oracle, small, ts, 0, first)
+        run_tiles(ctx, small, ts, 0, first, 1, streams)
         for mode in (tiles.PLAIN, tiles.ALPHA_WEIGHTED):
-            _, want = T.model(oracle, small, ts, 0, mode)
+            _, want = tile_model(oracle, small, ts, 0, mode)
             assert want != streams
-            T.run(ctx, small, ts, 0, mode, 1, want)
+            run_tiles(ctx, small, ts, 0, mode, 1, want)
             subs = tiles.plan(shapes_of(small), ts, 0, 0)[1]
             assert ctx.tile_stats()[:2] == (len(subs), len(subs))
 

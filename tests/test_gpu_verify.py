@@ -8,31 +8,11 @@ import numpy as np
 import pytest
 
 from qoi_amd.imagediff import DIFF_DTYPE, DIFF_HEADER, DIFF_PIXELS, NONE, diff
-from test_gpu_encode_packed import KINDS, Batch, dev, filled
+from gpu_pack import E_ARG, KINDS, Batch, dev, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
 MIXED_SHAPES = [(1, 1, 4), (1, 97, 4), (131, 1, 3), (37, 23, 3), (257, 9, 4), (64, 48, 3), (333, 7, 4), (130, 70, 4), (130, 70, 3)]
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")

@@ -12,34 +12,13 @@ import pytest
 from qoi_amd import warp
 from qoi_amd.packplan import slot
 from qoi_amd.warp import ALPHA_WEIGHTED, ONE, PLAIN, REPLICATE
-from test_gpu_encode_packed import KINDS, Batch, filled
-from test_gpu_thumbnails import MIXED_SHAPES, Pack
+from gpu_calls import assert_warp_items as assert_items, run_warp as run, sizes_of, want_warp as want
+from gpu_pack import E_ARG, GUARD, KINDS, MIXED_SHAPES, Batch, Pack, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 BIG = 7                               # 130 x 70 x 4, sprite_alpha
 FILL = 0x40C08020
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -53,42 +32,6 @@ def mixed(api, ctx, oracle):
 @pytest.fixture(scope="module")
 def equal(api, ctx, oracle):
     return Pack(ctx, oracle, Batch(api, oracle, [(64, 48, 4)] * 7, [KINDS[i % 5] for i in range(7)]))
-
-
-def sizes_of(items, och):
-    return [it[5] * it[6] * och for it in items]
-
-
-def run(ctx, p, channels, items, mode=PLAIN, staging=0, offsets=None, total=None, front=64, call=None):
-    """One call; outputs back to back behind `front` guard bytes unless offsets are given.  Returns the outputs."""
-    och = channels or p.shapes[items[0][0]][2]
-    nbytes = sizes_of(items, och)
-    if offsets is None:
-        offsets = [front + int(x) for x in np.cumsum([0] + nbytes[:-1])]
-    if total is None:
-        total = max(o + n for o, n in zip(offsets, nbytes)) + 64
-    buf = filled(total, GUARD)
-    if call is None:
-        ctx.decode_warped(p.packed.data_ptr(), p.so, p.sizes, p.descs, channels, items, mode, buf.data_ptr(), offsets, staging)
-    else:
-        call(buf.data_ptr(), offsets)
-    got = buf.cpu().numpy()
-    mask = np.ones(total, dtype=bool)
-    for o, n in zip(offsets, nbytes):
-        mask[o:o + n] = False
-    assert np.all(got[mask] == GUARD), ("a byte outside the outputs was written", int(np.argmax(mask & (got != GUARD))))
-    return [got[o:o + n] for o, n in zip(offsets, nbytes)]
-
-
-def want(p, it, och, mode):
-    i, x, y, cw, rh, ow, oh, flags, a, b, d, e, fill, _, c, f = it
-    return warp.warp(p.decoded(i, och), (x, y, cw, rh), (ow, oh), (a, b, c, d, e, f), flags, fill, mode).reshape(-1)
-
-
-def assert_items(p, got, items, och, mode, what):
-    for j, it in enumerate(items):
-        w = want(p, it, och, mode)
-        assert got[j].size == w.size and np.array_equal(got[j], w), (what, j, it, int(np.argmax(got[j] != w)))
 
 
 def general(i, rect, k=0):

@@ -3,7 +3,7 @@ output is compared bit for bit, over its whole length, with the definition - the
 count, qoi_amd/warp.py samples that, qoi_amd/tensors.py: convert makes the tensor (each u8 model is computed once and shared).  The pack is
 small: 24 x 20 photographs with 4 and with 3 channels, a 12 x 12 image whose alpha is 0 except for isolated texels, a 12 x 12 checkerboard of
 0 and 255, a 16 x 64 strip, a 1 x 1 image and a 130 x 70 photograph.  Outputs stand behind, between and in front of guard bytes
-(test_gpu_warp.py: run; test_gpu_labels.py: run); every guard byte is checked after every call."""
+(gpu_calls.py: run_warp, run_label_tensors); every guard byte is checked after every call."""
 import numpy as np
 import pytest
 
@@ -11,15 +11,11 @@ from qoi_amd import tensors, warp
 from qoi_amd.packplan import slot
 from qoi_amd.tensors import CHW, F16, F32, HW, HWC, I32, U8
 from qoi_amd.warp import ALPHA_WEIGHTED, BICUBIC, NEAREST, ONE, PLAIN, REPLICATE
-from test_gpu_labels import IMAGENET, run as run_tensors
-from test_gpu_encode_packed import Batch
-from test_gpu_thumbnails import Pack, batch_of
-from test_gpu_warp import assert_items
-from test_gpu_warp import run as run_warp
-from test_gpu_warp import want as want_warp
+from gpu_calls import assert_outputs, assert_warp_items as assert_items, run_label_tensors as run_tensors, run_warp, want_warp
+from gpu_pack import IMAGENET, Batch, Pack, batch_of
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-GUARD = 0xA5
 FILL = 0x40C08020
 PHOTO4, PHOTO3, SPARSE, BOARD, STRIP, DOT, BIG = range(7)
 SHAPES = [(24, 20, 4), (24, 20, 3), (12, 12, 4), (12, 12, 4), (16, 64, 4), (1, 1, 4), (130, 70, 4)]
@@ -44,26 +40,6 @@ def pixels():
 
 
 @pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-@pytest.fixture(scope="module")
 def pack(api, ctx, oracle):
     return Pack(ctx, oracle, batch_of(api, oracle, SHAPES, pixels()))
 
@@ -83,9 +59,7 @@ def model(p, it, och, mode=PLAIN):
 
 
 def assert_bytes(p, got, items, och, mode, what):
-    for j, it in enumerate(items):
-        w = model(p, it, och, mode).reshape(-1)
-        assert got[j].size == w.size and np.array_equal(got[j], w), (what, och, mode, j, it, int(np.argmax(got[j] != w)))
+    assert_outputs(got, [model(p, it, och, mode) for it in items], (what, och, mode))
 
 
 def cubic_items(flag=BICUBIC):

@@ -3,7 +3,7 @@ and qoimi_decode_warped_indexed: every output is compared bit for bit, over its 
 stream at the call's output channel count, qoi_amd/warp.py samples that, qoi_amd/tensors.py: convert makes the tensor (each u8 model is
 computed once and shared).  The pack is small: one 40 x 24 image with 4 channels and one with 3; the rectangles are 1 x 1, 1 x 7, 7 x 1,
 5 x 3 and 17 x 9, the outputs up to 48 x 40, so that whole and partial 16 x 16 tiles occur.  Outputs stand behind, between and in front of
-guard bytes (test_gpu_warp.py: run; test_gpu_labels.py: run); every guard byte is checked after every call.  Before the three flags existed
+guard bytes (gpu_calls.py: run_warp, run_label_tensors); every guard byte is checked after every call.  Before the three flags existed
 every call here with one of them was rejected with "unknown flag bit"."""
 import numpy as np
 import pytest
@@ -11,9 +11,9 @@ import pytest
 from qoi_amd import tensors, warp
 from qoi_amd.tensors import CHW, F16, HW, I64
 from qoi_amd.warp import ALPHA_WEIGHTED, BICUBIC, NEAREST, ONE, PLAIN, REFLECT, REFLECT_101, REPLICATE, WRAP
-from test_gpu_labels import IMAGENET, run as run_tensors
-from test_gpu_thumbnails import Pack, batch_of
-from test_gpu_warp import run as run_warp
+from gpu_calls import assert_outputs, run_label_tensors as run_tensors, run_warp
+from gpu_pack import IMAGENET, Pack, batch_of
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 FILL = 0x40C08020
@@ -29,26 +29,6 @@ def pixels():
     rgba = rng.integers(0, 256, size=(24, 40, 4), dtype=np.uint8)
     rgba[:, :, 3][rng.integers(0, 3, size=(24, 40)) == 0] = 0                # a third of the pixels transparent: the modes differ
     return [rgba, rng.integers(0, 256, size=(24, 40, 3), dtype=np.uint8)]
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -71,9 +51,7 @@ def model(p, it, och, mode=PLAIN):
 
 
 def assert_bytes(p, got, items, och, mode, what):
-    for j, it in enumerate(items):
-        w = model(p, it, och, mode).reshape(-1)
-        assert got[j].size == w.size and np.array_equal(got[j], w), (what, och, mode, j, it, int(np.argmax(got[j] != w)))
+    assert_outputs(got, [model(p, it, och, mode) for it in items], (what, och, mode))
 
 
 def border_items(border, samplings=SAMPLINGS):

@@ -17,6 +17,7 @@ import warp_fold_cases as W
 from qoi_amd import tensors, warp
 from qoi_amd.tensors import HW, I64
 from qoi_amd.warp import BICUBIC, NEAREST, PLAIN, SUPER2
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 gpu = pytest.mark.gpu
 _MODELS = {}
@@ -68,29 +69,11 @@ def test_the_sweep_is_the_fold_and_holds_every_class():
 
 
 # ------------------------------------------------------------------ on the device
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
 def pack(api, oracle):
-    from test_gpu_resize_wide import OraclePack
+    from gpu_pack import OraclePack
     p = OraclePack(api, oracle, W.SHAPES, W.pixels())
     assert all(np.array_equal(p.decoded(i, 4), D) and np.array_equal(p.decoded(i, 3), D[..., :3]) for i, D in enumerate(W.pixels()))
     return p
@@ -116,7 +99,7 @@ def assert_items(p, got, items, och, what):
 @gpu
 @pytest.mark.parametrize("channels", [4, 3])
 def test_the_nearest_sweep_in_one_call(ctx, pack, channels):
-    from test_gpu_warp import run as run_warp
+    from gpu_calls import run_warp
     items = [it for it, _, _ in W.sweep()]
     got = run_warp(ctx, pack, channels, items, PLAIN, offsets=guarded_offsets(items, channels))
     assert ctx.warp_stats()[:2] == (1, 1)
@@ -128,7 +111,7 @@ def test_the_nearest_sweep_in_one_call(ctx, pack, channels):
 def test_the_samplings_that_fold_more_than_one_tap(ctx, pack, sampling):
     """the positions of the sweep, q thinned to +-2, +-1000, +-(2**39 // P): two taps and warp_fold_next across P; four taps, the first at
     k - 1; warp_border_axis from warp_super_pixel"""
-    from test_gpu_warp import run as run_warp
+    from gpu_calls import run_warp
     items = [it for it, _, _ in W.sweep(sampling, True)]
     assert all(it[7] & (NEAREST | BICUBIC | SUPER2) == sampling for it in items)
     for channels in (4, 3):
@@ -140,7 +123,7 @@ def test_the_samplings_that_fold_more_than_one_tap(ctx, pack, sampling):
 @gpu
 def test_the_nearest_sweep_as_a_label_tensor(ctx, pack):
     """warp_border_tensor: the whole sweep as int64 HW in one call"""
-    from test_gpu_labels import run as run_tensors
+    from gpu_calls import run_label_tensors as run_tensors
     items = [it for it, _, _ in W.sweep()]
     f = tensors.fmt(I64, HW)
     got = run_tensors(ctx, pack, "warp", 4, items, PLAIN, f)

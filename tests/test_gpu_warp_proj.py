@@ -3,7 +3,7 @@ output is compared bit for bit, over its whole length, with the definition - the
 positions and samples, qoi_amd/tensors.py: convert makes the tensor (each u8 model is computed once and shared).  The pack is small: noise
 with alpha of 33 x 21 x 4, 64 x 48 x 3 and 5 x 1 x 4 and a strip of 33000 x 3 x 3, on which a position passes 2**32; the outputs run from
 1 x 1 over 17 x 9 to 33 x 40 (nine tiles, ragged edges) and 70000 x 3 (F = 31).  Outputs stand behind, between and in front of guard bytes
-(test_gpu_warp.py: run; test_gpu_labels.py: run); every guard byte is checked after every call.  With g = h = 0 the flagged call is compared
+(gpu_calls.py: run_warp, run_label_tensors); every guard byte is checked after every call.  With g = h = 0 the flagged call is compared
 with the unflagged call on the device; in a mixed call the older items keep the bytes of a call without a projective item.  Before the
 flag existed every call here with it was rejected with "unknown flag bit"."""
 import ctypes
@@ -15,14 +15,11 @@ from qoi_amd import tensors, warp
 from qoi_amd.tensors import CHW, F16, HW, I64
 from qoi_amd.warp import (ALPHA_WEIGHTED, BICUBIC, NEAREST, ONE, PLAIN, PROJECTIVE, REFLECT, REFLECT_101, REPLICATE, SUPER2, SUPER4, VOTE2, VOTE4,
                           WRAP)
-from test_gpu_encode_packed import filled
-from test_gpu_labels import IMAGENET, run as run_tensors
-from test_gpu_thumbnails import Pack, batch_of
-from test_gpu_warp import run as run_warp
+from gpu_calls import assert_outputs, run_label_tensors as run_tensors, run_warp
+from gpu_pack import E_ARG, GUARD, IMAGENET, Pack, batch_of, filled
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 FILL = 0x80FF4007
 RGBA, RGB, STRIP, LONG = 0, 1, 2, 3
 SHAPES = [(33, 21, 4), (64, 48, 3), (5, 1, 4), (33000, 3, 3)]
@@ -41,26 +38,6 @@ def pixels():
             D = np.repeat(D[:, ::8], 8, axis=1)[:, :w]
         out.append(np.ascontiguousarray(D))
     return out
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -84,9 +61,7 @@ def model(p, it, och, mode=PLAIN):
 
 
 def assert_bytes(p, got, items, och, mode, what):
-    for j, it in enumerate(items):
-        w = model(p, it, och, mode).reshape(-1)
-        assert got[j].size == w.size and np.array_equal(got[j], w), (what, och, mode, j, it, int(np.argmax(got[j] != w)))
+    assert_outputs(got, [model(p, it, och, mode) for it in items], (what, och, mode))
 
 
 def tilt(out_size, share_x, share_y):

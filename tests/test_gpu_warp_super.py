@@ -2,9 +2,9 @@
 qoimi_decode_warped_indexed: every output is compared bit for bit, over its whole length, with the definition - the oracle decodes the stream
 at the call's output channel count, qoi_amd/warp.py samples that, qoi_amd/tensors.py: convert makes the tensor (each u8 model is computed
 once and shared).  The pack is small: 33 x 21 x 4, 64 x 48 x 3 and 5 x 1 x 4; the outputs run from 1 x 1 to 17 x 9 (edge tiles) and one of
-40 x 24 (six tiles).  Outputs stand behind, between and in front of guard bytes (test_gpu_warp.py: run; test_gpu_labels.py: run); every guard
+40 x 24 (six tiles).  Outputs stand behind, between and in front of guard bytes (gpu_calls.py: run_warp, run_label_tensors); every guard
 byte is checked after every call.  The box identity is also compared with qoimi_decode_thumbnails and qoimi_decode_resized on the device.  The
-last test takes the pack of tests/test_gpu_newer_wide.py - a 17.7 Mpx image between small ones - for a call with more tiles than the launch
+last test takes the pack of tests/wide_cases.py: huge_with_plantings - a 17.7 Mpx image between small ones - for a call with more tiles than the launch
 has workgroups over staged pixel indices from 2**24 on.  Before the two flags existed every call here with one of them was rejected with
 "unknown flag bit"."""
 import ctypes
@@ -16,16 +16,12 @@ import resize_window as rw
 from qoi_amd import tensors, thumbs, warp
 from qoi_amd.tensors import CHW, F16, F32, HWC
 from qoi_amd.warp import ALPHA_WEIGHTED, BICUBIC, NEAREST, ONE, PLAIN, REFLECT, REFLECT_101, REPLICATE, SUPER2, SUPER4, WRAP
-from test_gpu_encode_packed import KINDS, filled, image
-from test_gpu_labels import IMAGENET, run as run_tensors
-from test_gpu_newer_wide import huge_with_plantings, past_2_24, super_walk_table, super_windows, walk_shape, window_of
-from test_gpu_resize_wide import OraclePack
-from test_gpu_thumbnails import Pack, batch_of
-from test_gpu_warp import run as run_warp
+from gpu_calls import assert_outputs, run_label_tensors as run_tensors, run_warp
+from gpu_pack import E_ARG, GUARD, IMAGENET, KINDS, OraclePack, Pack, batch_of, filled, image
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
+from wide_cases import huge_with_plantings, past_2_24, super_walk_table, super_windows, walk_shape, window_of
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 FILL = 0x40C08020
 RGBA, RGB, STRIP = 0, 1, 2
 SHAPES = [(33, 21, 4), (64, 48, 3), (5, 1, 4)]
@@ -42,26 +38,6 @@ def pixels():
             D[:, :, 3][rng.integers(0, 3, size=(h, w)) == 0] = 0                # a third of the pixels transparent: the modes differ
         out.append(D)
     return out
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -84,9 +60,7 @@ def model(p, it, och, mode=PLAIN):
 
 
 def assert_bytes(p, got, items, och, mode, what):
-    for j, it in enumerate(items):
-        w = model(p, it, och, mode).reshape(-1)
-        assert got[j].size == w.size and np.array_equal(got[j], w), (what, och, mode, j, it, int(np.argmax(got[j] != w)))
+    assert_outputs(got, [model(p, it, och, mode) for it in items], (what, och, mode))
 
 
 def super_items(flag, borders=BORDERS):

@@ -3,9 +3,9 @@ qoimi_decode_warped_indexed: every output is compared bit for bit, over its whol
 at 4 channels (the vote is over the 4-channel decode; a 3-channel stream has alpha 255), qoi_amd/warp.py votes and drops alpha for 3 output
 channels, qoi_amd/tensors.py: convert makes the tensor (each u8 model is computed once and shared).  The pack is small: label images
 (tests/labelimg.py) of 33 x 21 x 4, 64 x 48 x 3 and 5 x 1 x 4; the outputs run from 1 x 1 over 17 x 9 to 40 x 35 (nine tiles, ragged edges).
-Outputs stand behind, between and in front of guard bytes (test_gpu_warp.py: run; test_gpu_labels.py: run); every guard byte is checked
+Outputs stand behind, between and in front of guard bytes (gpu_calls.py: run_warp, run_label_tensors); every guard byte is checked
 after every call.  The whole-factor reduction is also compared with qoimi_decode_tensors under QOIMI_FILTER_MODE on the device, the
-orientations with QOIMI_WARP_NEAREST.  The last test takes the pack of tests/test_gpu_newer_wide.py - a 17.7 Mpx image between small ones -
+orientations with QOIMI_WARP_NEAREST.  The last test takes the pack of tests/wide_cases.py: huge_with_plantings - a 17.7 Mpx image between small ones -
 for a call with more tiles than the launch has workgroups over staged pixel indices from 2**24 on.  Before the two flags existed every call
 here with one of them was rejected with "unknown flag bit"."""
 import ctypes
@@ -18,16 +18,12 @@ import resize_window as rw
 from qoi_amd import tensors, warp
 from qoi_amd.tensors import CHW, F32, FILTER_MODE, HW, HWC, I64, U8
 from qoi_amd.warp import ALPHA_WEIGHTED, BICUBIC, NEAREST, ONE, PLAIN, REFLECT, REFLECT_101, REPLICATE, SUPER2, SUPER4, VOTE2, VOTE4, WRAP
-from test_gpu_encode_packed import KINDS, filled, image
-from test_gpu_labels import IMAGENET, run as run_tensors
-from test_gpu_newer_wide import LABELS_AT, huge_with_plantings, past_2_24, walk_shape, window_of
-from test_gpu_resize_wide import OraclePack
-from test_gpu_thumbnails import Pack, batch_of
-from test_gpu_warp import run as run_warp
+from gpu_calls import assert_outputs, run_label_tensors as run_tensors, run_warp
+from gpu_pack import E_ARG, GUARD, IMAGENET, KINDS, OraclePack, Pack, batch_of, filled, image
+from gpu_pack import api, ctx, oracle  # noqa: F401  (fixtures)
+from wide_cases import LABELS_AT, huge_with_plantings, past_2_24, walk_shape, window_of
 
 pytestmark = pytest.mark.gpu
-E_ARG = -1
-GUARD = 0xA5
 FILL = 0xFF000007                                                     # r 7, g 0, b 0, a 255: a class of the palette, so the fill joins votes
 RGBA, RGB, STRIP = 0, 1, 2
 SHAPES = [(33, 21, 4), (64, 48, 3), (5, 1, 4)]
@@ -45,26 +41,6 @@ def pixels():
             D[3::6, :] = labelimg.PALETTE[5][:ch]
         out.append(D)
     return out
-
-
-@pytest.fixture(scope="module")
-def api():
-    import torch  # noqa: F401  (first, so the library binds to torch's HIP runtime)
-    from qoi_amd import api as _api
-    assert torch.cuda.is_available()
-    return _api
-
-
-@pytest.fixture(scope="module")
-def ctx(api):
-    c = api.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
 
 
 @pytest.fixture(scope="module")
@@ -88,9 +64,7 @@ def model(p, it, och, mode=PLAIN):
 
 
 def assert_bytes(p, got, items, och, mode, what):
-    for j, it in enumerate(items):
-        w = model(p, it, och, mode).reshape(-1)
-        assert got[j].size == w.size and np.array_equal(got[j], w), (what, och, mode, j, it, int(np.argmax(got[j] != w)))
+    assert_outputs(got, [model(p, it, och, mode) for it in items], (what, och, mode))
 
 
 def vote_items(flag, borders=BORDERS):

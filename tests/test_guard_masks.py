@@ -9,11 +9,7 @@ import pytest
 import cases
 from gpu_util import GUARD, OUT_FILL, STREAM_FILL, EdgeBatch, GuardedRegion
 from qoi_amd import api, synth
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
+from gpu_pack import oracle  # noqa: F401  (fixtures)
 
 
 @pytest.mark.parametrize("ch", [4, 3])

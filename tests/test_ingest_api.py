@@ -9,7 +9,8 @@ import re
 import pytest
 
 from qoi_amd import api, tensors, tiles
-from test_tiles_api import E_ARG, args, tl, untouched  # noqa: F401  (args is a fixture)
+from model_cases import E_ARG, tl, untouched
+from model_cases import args  # noqa: F401  (fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F16 = tiles.source_flags(tiles.F16)

@@ -41,7 +41,7 @@ def crossing(case):
 
 
 def wide_cases():
-    from test_gpu_offsets_wide import ARENA, B32, tensor_offsets
+    from wide_cases import ARENA, B32, tensor_offsets
     offs = tensor_offsets()
     assert all(0 <= o < ARENA for o in offs) and any(o >= B32 for o in offs)
     return ic.cases_of(ic.WIDE_SPECS, offs, ic.wide_tiles(), ic.WIDE_CHANNELS)
@@ -141,7 +141,7 @@ def test_the_witnesses_tell_two_roundings_from_a_fused_multiply_add():
 
 @pytest.mark.parametrize("dtype", ic.FLOATS, ids=["f16", "bf16", "f32"])
 def test_the_expectations_of_the_values_module_can_fail(dtype):
-    from test_gpu_ingest_values import conditions
+    from gpu_calls import conditions
     specs, hows = ic.value_specs(dtype)
     offs, _ = ic.offsets(specs, hows)
     assert [o % 256 == 0 for o in offs] == [h == ic.ALIGNED for h in hows] and {h for h in hows} == {ic.ALIGNED, ic.ONE}

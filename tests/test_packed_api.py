@@ -5,25 +5,12 @@ import os
 import re
 import subprocess
 
-import numpy as np
 import pytest
+from model_cases import pack_offsets as offsets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("qoimi_pack_streams", "qoimi_decode_images", "qoimi_read_descs")
 QOIMI_E_ARG = -1
-
-
-def offsets(lens, align):
-    """d_packed_off of qoimi_pack_streams: uint64[n + 1] - the exclusive scan of the lengths, every start rounded up to `align`
-    (a power of two); the last entry is the END of the last stream, not rounded."""
-    lens = np.asarray(lens, dtype=np.uint64)
-    off = np.zeros(lens.size + 1, dtype=np.uint64)
-    a = np.uint64(align)
-    for i in range(lens.size):
-        if i:
-            off[i] = (off[i - 1] + lens[i - 1] + a - np.uint64(1)) // a * a
-    off[-1] = off[-2] + lens[-1]
-    return off
 
 
 def test_offsets_model():

@@ -7,6 +7,7 @@ import pytest
 from qoi_amd import crops, resize, thumbs
 from qoi_amd.packplan import slot
 from qoi_amd.resize import ALPHA_WEIGHTED, FLIP_X, FLIP_Y, PLAIN
+from model_cases import gradient_image as image
 
 
 def brute(D, rect, out_size, flags, mode):
@@ -38,16 +39,6 @@ def brute(D, rect, out_size, flags, mode):
     if flags & FLIP_X:
         out = [row[::-1] for row in out]
     return np.array(out, dtype=np.uint8)
-
-
-def image(w, h, och, seed):
-    """random pixels, a quarter of them with alpha 0 and - at 4 channels - one all-transparent block in the lower left"""
-    rng = np.random.default_rng(seed)
-    D = rng.integers(0, 256, size=(h, w, och), dtype=np.uint8)
-    if och == 4:
-        D[:, :, 3][rng.integers(0, 4, size=(h, w)) == 0] = 0
-        D[h // 2:, :w // 2, 3] = 0
-    return D
 
 
 SIZES = [((11, 9), (3, 2)), ((11, 9), (5, 4)), ((11, 9), (13, 11)), ((11, 9), (1, 1)), ((11, 9), (4, 9)),

@@ -7,9 +7,9 @@ import pytest
 import resize_window as rw
 from qoi_amd import resize, thumbs
 from qoi_amd.resize import ALPHA_WEIGHTED, PLAIN
-from test_gpu_resize import standard
-from test_gpu_thumbnails import MIXED_SHAPES
-from test_resize_model import image
+from gpu_calls import standard
+from gpu_pack import MIXED_SHAPES
+from model_cases import gradient_image as image
 
 
 def same(D, rect, out, flags, mode):

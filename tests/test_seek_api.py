@@ -10,7 +10,7 @@ import pytest
 
 from qoi_amd import api
 from qoi_amd import seekindex as si
-from test_seekindex_model import END, header, index_image, runs_image
+from model_cases import END, header, index_image, runs_image
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG = -1

@@ -12,7 +12,7 @@ import pytest
 import hostbuild
 from hostbuild import GUARD, cuint, i64, u32, u32p, u64
 from qoi_amd import seekindex as si
-from test_seekindex_model import END, alpha_image, header, index_image, runs_image
+from model_cases import END, alpha_image, header, index_image, runs_image
 
 SRC = "seek_host.cpp"
 

@@ -7,13 +7,9 @@ import numpy as np
 import pytest
 
 from qoi_amd import seekindex as si
+from model_cases import END, alpha_image, header, index_image, runs_image
 
 WIDTHS = [1, 2, 61, 62, 63, 64, 65, 127, 128, 129]
-END = bytes([0, 0, 0, 0, 0, 0, 0, 1])
-
-
-def header(w, h, ch, cs=0):
-    return b"qoif" + w.to_bytes(4, "big") + h.to_bytes(4, "big") + bytes([ch, cs])
 
 
 def intervals(w):
@@ -23,32 +19,6 @@ def intervals(w):
 
 def height(w):
     return 5 * (-(-128 // w)) + 3
-
-
-def runs_image(w, h, ch, seed):
-    """runs of 1 to 200 pixels that cross row ends, some longer than 62 (several RUN chunks in a row)"""
-    rng = np.random.default_rng(seed)
-    px = np.zeros((w * h, ch), dtype=np.uint8)
-    at = 0
-    while at < w * h:
-        n = int(rng.integers(1, 200))
-        px[at:at + n] = rng.integers(0, 256, size=ch, dtype=np.uint8)
-        at += n
-    return px
-
-
-def index_image(w, h, ch, seed):
-    """five colours in random order: INDEX chunks, short runs, slots last written many rows back"""
-    rng = np.random.default_rng(seed)
-    palette = rng.integers(0, 256, size=(5, ch), dtype=np.uint8)
-    px = palette[rng.integers(0, 5, size=w * h)]
-    px[: w * h // 3] = palette[rng.integers(0, 2, size=w * h // 3)]          # colours 2..4 not seen for the first third
-    return px
-
-
-def alpha_image(w, h, ch, seed):
-    """noise with changing alpha (RGBA chunks where ch == 4)"""
-    return np.random.default_rng(seed).integers(0, 256, size=(w * h, ch), dtype=np.uint8)
 
 
 def streams_of(oracle, w):

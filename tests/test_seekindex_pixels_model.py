@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from qoi_amd import seekindex as si
-from test_seekindex_model import alpha_image, index_image, runs_image
+from model_cases import alpha_image, index_image, runs_image
 
 
 def flat_image(w, h, ch, seed):

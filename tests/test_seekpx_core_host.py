@@ -12,7 +12,7 @@ import pytest
 import hostbuild
 from hostbuild import cuint, i64, u32, u64
 from qoi_amd import seekindex as si
-from test_seekindex_model import END, header
+from model_cases import END, header
 
 SRC = "seekpx_host.cpp"
 INTERVALS = [1, 3, 255, 256, 1023, 1024, 1025, 2064]

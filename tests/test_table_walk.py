@@ -94,5 +94,5 @@ def test_the_limit_items():
 
 
 def test_the_bicubic_items_take_the_paths_they_are_named_for():
-    import test_gpu_bicubic as gb
-    gb.assert_paths()
+    from model_cases import assert_bicubic_paths
+    assert_bicubic_paths()

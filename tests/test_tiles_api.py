@@ -10,10 +10,11 @@ import subprocess
 import pytest
 
 from qoi_amd import api, tiles
+from model_cases import E_ARG, tl, untouched
+from model_cases import args  # noqa: F401  (fixtures)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("qoimi_encode_tiles", "qoimi_tile_size", "qoimi_tile_pyramid", "qoimi_tile_stats")
-E_ARG = -1
 
 
 def test_symbols_in_every_layer():
@@ -118,36 +119,6 @@ def test_tile_pyramid():
     # reached by an accepted descriptor (fewer than 400 000 000 pixels a level, 7 levels at most), so the count always fits an int
     assert lib.qoimi_tile_pyramid(ctypes.byref(api.QoiDesc(19999, 20000, 3, 0)), 1, 1, 7, None, 0) == sum(
         -(-19999 // (1 << l)) * -(-20000 // (1 << l)) for l in range(7))
-
-
-@pytest.fixture()
-def args():
-    class A:
-        pass
-    a = A()
-    a.lib = api.load_library()
-    a.fake_ctx = (ctypes.c_ubyte * (1 << 20))()                  # never looked at: every rejection comes first
-    a.ctx = ctypes.addressof(a.fake_ctx)
-    a.buf = (ctypes.c_ubyte * 8192)()                            # stands in for d_pixels, the device tables and the pack
-    ctypes.memset(a.buf, 0x5A, 8192)
-    a.p = ctypes.addressof(a.buf)
-    a.pack, a.off, a.len = a.p + 4096, a.p + 6144, a.p + 7168
-    a.po = (ctypes.c_size_t * 3)(1, 1024, 2051)
-    a.descs = (api.QoiDesc * 3)(api.QoiDesc(4, 4, 4, 0), api.QoiDesc(0, 0, 9, 9), api.QoiDesc(5, 3, 3, 1))   # image 1 is named by no tile: garbage
-    a.tiles = tl((0, 1, 1, 2, 2, 1, 0, 0), (2, 0, 0, 5, 3, 2, 3, 0))
-    a.h_off = (ctypes.c_ulonglong * 3)(7, 7, 7)
-    a.h_len = (ctypes.c_int * 2)(7, 7)
-    a.h_desc = (api.QoiDesc * 2)(api.QoiDesc(7, 7, 7, 7), api.QoiDesc(7, 7, 7, 7))
-    return a
-
-
-def tl(*rows):
-    return (api.QoimiTile * len(rows))(*[api.QoimiTile(*r) for r in rows])
-
-
-def untouched(a):
-    return (bytes(a.buf) == b"\x5A" * 8192 and bytes(a.fake_ctx[:4096]) == b"\0" * 4096 and list(a.h_off) == [7] * 3 and list(a.h_len) == [7] * 2
-            and all((d.width, d.height, d.channels, d.colorspace) == (7, 7, 7, 7) for d in a.h_desc))
 
 
 REJECTED_DESCS = {"width 0": (0, 3, 4, 0), "height 0": (3, 0, 4, 0), "channels 2": (3, 3, 2, 0), "channels 5": (3, 3, 5, 0),

@@ -3,19 +3,12 @@ goes through qoimi_decode_batch on the batch path (QOIMI_DEC_FUSED=0) at 1 KiB, 
 reference decoder's pixels.  What the cases aim at: the last line of a stream partial / exactly full / one byte into the next; a
 lane's first line entered at every offset; chunks that straddle every line end at every phase; lanes out of the wavefront
 descriptor's reach (they take the plain reader); wavefronts with idle lanes and lanes that end mid-line."""
-import os
-import struct
-
 import numpy as np
 import pytest
+from gpu_pack import lctx, oracle  # noqa: F401  (fixtures)
+from model_cases import line_stream as _stream, line_walk as _walk
 
 pytestmark = pytest.mark.gpu
-
-SEGS = ["1024", "2048", "4096"]
-
-
-def _stream(w, h, body):
-    return b"qoif" + struct.pack(">II", w, h) + bytes([4, 0]) + bytes(body) + bytes([0, 0, 0, 0, 0, 0, 0, 1])
 
 
 def _diff_body(n, seed):
@@ -26,38 +19,14 @@ def _diff_body(n, seed):
     return b.tobytes()
 
 
-def _walk(w, h, seed, alpha=False):
-    rng = np.random.default_rng(seed)
-    px = np.cumsum(rng.integers(-3, 4, size=(w * h, 4)), axis=0).astype(np.uint8)
-    if not alpha:
-        px[:, 3] = 255
-    return px
-
-
+# this module's own api: the body of gpu_pack.api without the lint mark on its torch import - nothing else differs.  lctx (gpu_pack) asks
+# for `api` by name and so gets this one here.
 @pytest.fixture(scope="module")
 def api():
     import torch
     from qoi_amd import api as _api
     assert torch.cuda.is_available()
     return _api
-
-
-@pytest.fixture(scope="module")
-def oracle(ref, port):
-    return ref or port
-
-
-@pytest.fixture(scope="module", params=SEGS)
-def lctx(api, request):
-    os.environ["QOIMI_SEG_BYTES"] = request.param
-    os.environ["QOIMI_DEC_FUSED"] = "0"
-    try:
-        c = api.Context(0)
-    finally:
-        del os.environ["QOIMI_SEG_BYTES"]
-        del os.environ["QOIMI_DEC_FUSED"]
-    yield c
-    c.close()
 
 
 _WANT = {}
