@@ -341,10 +341,50 @@ enum { QOIMI_TILE_NEAREST = 4, QOIMI_TILE_MODE = 5 };   /* 2 and 3 are not modes
  * Properties (qoi_amd/tiles.py asserts them).  A call whose tiles all carry QOIMI_TILE_SRC alone gives the pack of the same call without
  * the bit, byte for byte.  Round trip: for every byte v and each of F32, F16 and BF16, the element qoimi_decode_tensors writes for v
  * converts back to v with scale 1/255, bias 0 and UNIT; scale 2/255, bias -1 and SYMMETRIC; scale 1, bias 0 and BYTES.
- * Not here (of tensor sources): box, selection and vote over them (factor 1 only: convert once at factor 1, or decode the pack), integer
- * dtypes other than u8, a scale and bias of the caller's, one-plane (HW) sources, row-pitched tensors. */
+ * Not here (of tensor sources): box, selection and vote over them (factor 1 only: convert once at factor 1, or decode the pack), a scale
+ * and bias of the caller's, row-pitched tensors; integer dtypes other than u8 and one-plane (HW) sources are label sources: the
+ * QOIMI_TILE_LABELS bits below. */
 enum { QOIMI_TILE_SRC = 16, QOIMI_TILE_SRC_CHW = 32, QOIMI_TILE_SRC_F16 = 64, QOIMI_TILE_SRC_BF16 = 128, QOIMI_TILE_SRC_F32 = 192,
-       QOIMI_TILE_SRC_SYMMETRIC = 256, QOIMI_TILE_SRC_BYTES = 512 };   /* bits 2, 3 and 10 up stay unknown flag bits */
+       QOIMI_TILE_SRC_SYMMETRIC = 256, QOIMI_TILE_SRC_BYTES = 512 };   /* bits 2, 3 and 10 stay unknown flag bits; 11-13: QOIMI_TILE_LABELS */
+/* Label tensors as the source (qoimi_tile.flags beside the two flips; accepted by qoimi_encode_tiles and qoimi_tile_size): the ingest side
+ * of QOIMI_TENSOR_I32 / _I64 in QOIMI_TENSOR_HW.  The label maps a device really holds are the int64 H x W argmax of a segmentation model,
+ * an int32 instance map and a uint8 mask plane; with these bits they become a label pack - and a label pyramid - in one call, and the
+ * caller clamps, narrows and interleaves nothing.
+ *   QOIMI_TILE_LABELS                 the image this tile names is ONE PLANE of w x h elements: element (Y, X) at element index Y * w + X
+ *   QOIMI_TILE_LABELS_I32 / _I64      the dtype field, bits 12-13: 0 u8, 1 little-endian two's-complement int32, 2 int64 (element size
+ *                                     E = 1 / 4 / 8); 12288 is not a dtype
+ * The plane is tightly packed at d_pixels + pixel_offsets[image], a BYTE offset that makes a multiple of E, and takes w * h * E bytes.
+ * descs[image] gives w, h and colorspace; its channels (3 or 4, by the descriptor rules) only says what och is when the call's `channels`
+ * is 0.  The conversion (normative; qoi_amd/tiles.py: labels_to_bytes states it in Python; qoi_amd/csrc/qoi_label_core.h is the kernel's).
+ * The byte b of the element v is 0 for v < 0, 255 for v > 255, else v: saturation of the full 32- / 64-bit value - the high dword of an
+ * int64 takes part: 2^32 is 255, not 0.  Saturation is SILENT: nothing counts or reports it, and an ignore index of -100 becomes class 0;
+ * a caller who must know counts before the call.  Pixel (Y, X) of the byte image B (h x w x 4) is (b, b, b, 255).  The tile is what
+ * qoimi_encode_tiles gives for B as a 4-channel byte image without the bits, in the call's `mode`: the rectangle, the reduction, the
+ * flips, the conversion to och (4 to 3 drops the 255), the reference encoder's stream byte for byte, the pack, both tables,
+ * tile_descs_out, the capacity rules, the staging plan and the slots.  No size changes: qoimi_tile_size needs no new argument.
+ * Factor.  Unlike a QOIMI_TILE_SRC tile a label tile may reduce - with the label modes: QOIMI_TILE_NEAREST at factor 1..64,
+ * QOIMI_TILE_MODE at factor 1..16 (the check above).  A label source is never averaged: QOIMI_THUMB_PLAIN / _ALPHA_WEIGHTED with
+ * factor != 1 on a label tile is QOIMI_E_ARG.  At factor 1 all four modes give the same bytes, as everywhere.  All pixels of B are grey with
+ * alpha 255, so the whole-pixel vote is the vote on b: among several winners the centre pixel wins if it is one, else the lowest b - the
+ * rule of qoi_amd/mode.py: vote, unchanged.  Of a plane nothing is read but whole, naturally aligned elements (u8: the aligned 4-byte
+ * words that hold one of its bytes); nothing of the caller's is written.
+ * Properties (tests/test_label_ingest_model.py asserts them on qoi_amd/tiles.py).  (a) For a tensor with all values in 0..255, any dtype,
+ * whole-image tiles at factor 1: qoimi_decode_tensors of the pack with QOIMI_FILTER_NEAREST, QOIMI_TENSOR_I64 and QOIMI_TENSOR_HW at the
+ * image's size returns the tensor widened to int64.  (b) A u8 label call equals the byte call over B.  (c) With f dividing w and h, a
+ * QOIMI_TILE_MODE label tile is what qoimi_decode_tensors gives with QOIMI_FILTER_MODE for the factor-1 pack at w/f x h/f - the statement
+ * the byte tiles make above.
+ * Limits, each QOIMI_E_ARG before anything is launched with the caller's buffers untouched, looked at per tile behind every check above
+ * (those of QOIMI_TILE_SRC included), in this order: a LABELS_* dtype bit without QOIMI_TILE_LABELS; dtype 12288; QOIMI_TILE_LABELS
+ * together with any QOIMI_TILE_SRC* bit; one of the two averaging modes with factor != 1 (qoimi_tile_size has no mode and does not look at
+ * this one); then, over the call: some but not all tiles carry QOIMI_TILE_LABELS (a call is a byte call, a tensor call or a label call);
+ * two tiles that name the same image with different label bits; d_pixels + pixel_offsets[image] not a multiple of E; the address-space
+ * and pack-overlap checks above, taken over w * h * E bytes; a sub-batch of the plan with 2^31 - 1 or more tiles of 256 work items of the
+ * kernel (an item is four consecutive pixels of a tile's output at factor 1, else 1 to 64 per output pixel as in the label modes).  A
+ * label call runs a gather kernel of its own over the same table; qoimi_tile_stats counts its launches in [1].
+ * Not here (of label sources): a count of saturated elements, a remap table, i16 / u16, ids above 255 spread over r, g and b, float class
+ * maps, a plane of a CHW tensor chosen by index (offset it yourself), row-pitched planes, label and tensor tiles in one call. */
+enum { QOIMI_TILE_LABELS = 2048, QOIMI_TILE_LABELS_I32 = 4096, QOIMI_TILE_LABELS_I64 = 8192 };
+/* dtype field, bits 12-13: 0 u8, 1 i32, 2 i64; 12288 is not a dtype.  Bit 10 and bits 14 up stay unknown flag bits. */
 typedef struct {                 /* 32 bytes, offsets 0/4/8/12/16/20/24/28 */
     unsigned int image;          /* index into the call's images */
     unsigned int x, y;           /* top-left corner of the source rectangle */

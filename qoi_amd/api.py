@@ -500,7 +500,9 @@ class Context:
         majority vote of ``FILTER_MODE`` over every block; factor <= 16); channels 0: every tile keeps its image's channel count;
         ``qoi_amd/tiles.py: tile`` states the pixels.  With ``tiles.source_flags(dtype, layout, range)`` in every tile's flags the images are
         tensors - u8 / f16 / bf16 / f32, HWC or CHW, factor 1 - converted on the way in (``tiles.convert``); pixel_offsets stay byte offsets
-        (``tiles.source_bytes`` an image; d_pixels is an address: no length of it is looked at here)."""
+        (``tiles.source_bytes`` an image; d_pixels is an address: no length of it is looked at here).  With ``tiles.label_flags(dtype)`` in
+        every tile's flags the images are one-plane u8 / int32 / int64 label maps (``tiles.labels_to_bytes``; ``tiles.label_bytes`` an
+        image), saturated to 0..255 silently; they reduce with ``tiles.NEAREST`` and ``tiles.MODE`` and are never averaged."""
         n_images = len(descs)
         seqs = self._per_image("encode_tiles", "pixel offset per descriptor", n_images, pixel_offsets=pixel_offsets, descs=descs)
         shortest, longest, noun, malformed = _ITEMS[QoimiTile]

@@ -2,6 +2,7 @@
 // qoimi_encode_tiles / qoimi_tile_size / qoimi_tile_pyramid, qoimi_read_descs, qoimi_inspect_streams.
 #include "qoi_ctx.h"
 #include "qoi_ingest_core.h"
+#include "qoi_label_core.h"
 #include "qoi_tile_core.h"
 
 // ------------------------------------------------------------------------------------
@@ -152,13 +153,16 @@ static_assert(QOIMI_TILE_SRC == (int)kTileSrc && QOIMI_TILE_SRC_CHW == (int)kTil
               QOIMI_TILE_SRC_SYMMETRIC == (int)(kIngestSymmetric << kTileSrcRangeShift) && QOIMI_TILE_SRC_BYTES == (int)(kIngestBytes << kTileSrcRangeShift) &&
               (int)kIngestU8 == QOIMI_TENSOR_U8 && (int)kIngestF16 == QOIMI_TENSOR_F16 && (int)kIngestBF16 == QOIMI_TENSOR_BF16 && (int)kIngestF32 == QOIMI_TENSOR_F32,
               "the source format's bits: the dtype field holds QOIMI_TENSOR_U8 .. _F32");
+static_assert(QOIMI_TILE_LABELS == (int)kTileLabels && QOIMI_TILE_LABELS_I32 == (int)(kLabelI32 << kTileLabelsDtypeShift) &&
+              QOIMI_TILE_LABELS_I64 == (int)(kLabelI64 << kTileLabelsDtypeShift) && kTileLabelsMask == 0x3800u && (kTileLabelsMask & kTileSrcMask) == 0u,
+              "the label source's bits: 11, and the dtype field in 12-13; bit 10 stays an unknown flag bit");
 
 // nullptr if the tile is fine for an accepted descriptor, else what is wrong with it
 static const char* tile_wrong(const qoi_desc* d, const qoimi_tile* t) {
     if (t->width == 0u || t->height == 0u) return "zero width or height";
     if ((uint64_t)t->x + t->width > d->width || (uint64_t)t->y + t->height > d->height) return "the rectangle leaves its image";
     if (t->factor < 1u || t->factor > kThumbMaxFactor) return "factor outside 1..64";
-    if ((t->flags & ~((unsigned)(QOIMI_CROP_FLIP_X | QOIMI_CROP_FLIP_Y) | kTileSrcMask)) != 0u) return "unknown flag bit";
+    if ((t->flags & ~((unsigned)(QOIMI_CROP_FLIP_X | QOIMI_CROP_FLIP_Y) | kTileSrcMask | kTileLabelsMask)) != 0u) return "unknown flag bit";
     if (t->reserved != 0u) return "reserved is not 0";
     return nullptr;
 }
@@ -174,8 +178,19 @@ static const char* tile_src_wrong(const qoimi_tile* t) {
     return nullptr;
 }
 
+// ... and of its label source (QOIMI_TILE_LABELS*), looked at behind those; averaging: the call's mode is one of the two box averages
+static const char* tile_label_wrong(const qoimi_tile* t, bool averaging) {
+    const uint32_t lab = t->flags & kTileLabelsMask;
+    if (lab == 0u) return nullptr;
+    if ((lab & kTileLabels) == 0u) return "a QOIMI_TILE_LABELS_* bit without QOIMI_TILE_LABELS";
+    if (label_dtype(lab) == 3u) return "12288 is not a dtype of a label source";
+    if ((t->flags & kTileSrcMask) != 0u) return "QOIMI_TILE_LABELS together with a QOIMI_TILE_SRC bit (a source is a tensor or a label plane)";
+    if (averaging && t->factor != 1u) return "a label source is never averaged: factor != 1 takes QOIMI_TILE_NEAREST or QOIMI_TILE_MODE";
+    return nullptr;
+}
+
 extern "C" size_t qoimi_tile_size(const qoi_desc* desc, const qoimi_tile* tile, int channels, unsigned* tw, unsigned* th) {
-    if (!desc_ok(desc) || !tile || (channels != 0 && channels != 3 && channels != 4) || tile_wrong(desc, tile) || tile_src_wrong(tile)) return 0;
+    if (!desc_ok(desc) || !tile || (channels != 0 && channels != 3 && channels != 4) || tile_wrong(desc, tile) || tile_src_wrong(tile) || tile_label_wrong(tile, false)) return 0;
     const uint32_t x = thumb_extent(tile->width, tile->factor), y = thumb_extent(tile->height, tile->factor);
     if (tw) *tw = x;
     if (th) *th = y;
@@ -213,6 +228,7 @@ extern "C" int qoimi_tile_pyramid(const qoi_desc* desc, unsigned tile_w, unsigne
 // (qoi_amd/tiles.py: plan).  Every sub-batch: one launch of tile_gather - of tile_select in QOIMI_TILE_NEAREST / QOIMI_TILE_MODE, which
 // change the reduction and the count of work items, no size - over its tiles, then the loop of encode_packed as it is.  A tensor call
 // (every tile carries QOIMI_TILE_SRC) runs tensor_ingest in their place: a third kind of entry, factor 1 only, the same table and plan.
+// A label call (every tile carries QOIMI_TILE_LABELS) runs label_ingest: one-plane integer sources, copied or reduced by the two label modes.
 extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size_t* pixel_offsets, const qoi_desc* descs, int n_images, int channels,
                                   const qoimi_tile* tiles, int n_tiles, int mode, unsigned align, void* d_packed, size_t packed_capacity,
                                   unsigned long long* d_packed_off, int* d_stream_len, size_t staging_bytes, unsigned long long* packed_off_out,
@@ -228,7 +244,7 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
     uint32_t kind = mode == QOIMI_TILE_NEAREST ? kTileKindNearest : mode == QOIMI_TILE_MODE ? kTileKindMode : kTileKindBox;
     const size_t n = (size_t)n_tiles;
     std::vector<uint8_t> named((size_t)n_images, 0);
-    size_t n_src = 0;
+    size_t n_src = 0, n_lab = 0;
     for (size_t j = 0; j < n; ++j) {
         const qoimi_tile& t = tiles[j];
         if (t.image >= (unsigned)n_images) return fail(QOIMI_E_ARG, "tile " + std::to_string(j) + ": no image " + std::to_string(t.image));
@@ -240,10 +256,13 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
         if (kind == kTileKindMode && t.factor > kTileModeMaxFactor)
             return fail(QOIMI_E_ARG, "tile " + std::to_string(j) + ": factor above 16 with QOIMI_TILE_MODE (a block votes over at most 16 x 16 pixels; QOIMI_TILE_NEAREST has no such limit)");
         if (const char* what = tile_src_wrong(&t)) return fail(QOIMI_E_ARG, "tile " + std::to_string(j) + ": " + what);
+        if (const char* what = tile_label_wrong(&t, mode == QOIMI_THUMB_PLAIN || mode == QOIMI_THUMB_ALPHA_WEIGHTED)) return fail(QOIMI_E_ARG, "tile " + std::to_string(j) + ": " + what);
         if ((t.flags & kTileSrc) != 0u) ++n_src;
+        if ((t.flags & kTileLabels) != 0u) ++n_lab;
     }
     // a call is a byte call or a tensor call; in a tensor call an image has ONE format (its element size: 1 in a byte call)
     if (n_src != 0u && n_src != n) return fail(QOIMI_E_ARG, "some tiles carry QOIMI_TILE_SRC and some do not: a call is a byte call or a tensor call");
+    if (n_lab != 0u && n_lab != n) return fail(QOIMI_E_ARG, "some tiles carry QOIMI_TILE_LABELS and some do not: a call is a byte call, a tensor call or a label call");
     std::vector<uint32_t> src_of((size_t)n_images, 0u);
     if (n_src != 0u) {
         kind = kTileKindIngest;                                // (at factor 1 all four modes are the rectangle itself)
@@ -257,12 +276,28 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
             if (named[i] && ((uintptr_t)d_pixels + pixel_offsets[i]) % ingest_elem(ingest_dtype(src_of[i])) != 0u)
                 return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": its address is not a multiple of the element size");
     }
+    // in a label call an image is ONE plane of elements of one dtype
+    const bool labels = n_lab != 0u, vote = mode == QOIMI_TILE_MODE;
+    std::vector<uint32_t> lab_of((size_t)n_images, 0u);
+    if (labels) {
+        kind = kTileKindLabel;
+        for (size_t j = 0; j < n; ++j) {
+            const uint32_t lab = tiles[j].flags & kTileLabelsMask;
+            if (lab_of[tiles[j].image] != 0u && lab_of[tiles[j].image] != lab)
+                return fail(QOIMI_E_ARG, "tile " + std::to_string(j) + ": image " + std::to_string(tiles[j].image) + " is named with two different label dtypes");
+            lab_of[tiles[j].image] = lab;
+        }
+        for (size_t i = 0; i < named.size(); ++i)
+            if (named[i] && ((uintptr_t)d_pixels + pixel_offsets[i]) % label_elem(label_dtype(lab_of[i])) != 0u)
+                return fail(QOIMI_E_ARG, "image " + std::to_string(i) + ": its address is not a multiple of the element size");
+    }
     long long referenced = 0;
     for (size_t i = 0; i < named.size(); ++i) {
         if (!named[i]) continue;
         ++referenced;
         const uintptr_t room = ~(uintptr_t)0 - (uintptr_t)d_pixels;
-        const size_t last = (size_t)descs[i].width * descs[i].height * descs[i].channels * ingest_elem(ingest_dtype(src_of[i])) - 1u;     // the image's last byte from its first
+        const size_t last = labels ? (size_t)descs[i].width * descs[i].height * label_elem(label_dtype(lab_of[i])) - 1u                   // (one plane, whatever channels says)
+                                   : (size_t)descs[i].width * descs[i].height * descs[i].channels * ingest_elem(ingest_dtype(src_of[i])) - 1u;     // the image's last byte from its first
         if (pixel_offsets[i] > room || last > room - pixel_offsets[i]) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + " ends behind the address space");
         const uintptr_t s0 = (uintptr_t)d_pixels + pixel_offsets[i], p0 = (uintptr_t)d_packed;
         if (packed_capacity != 0 && s0 <= p0 + (packed_capacity - 1u) && p0 <= s0 + last) return fail(QOIMI_E_ARG, "image " + std::to_string(i) + " and the pack overlap");
@@ -285,7 +320,8 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
         for (int j = plan.firsts[k]; j < plan.firsts[k + 1]; ++j) {
             if (sum >= 0x7FFFFFFFull) break;
             first_tile[(size_t)j] = (uint32_t)sum;
-            sum += kind == kTileKindIngest ? ingest_tiles(tiles[j].width, tiles[j].height)
+            sum += kind == kTileKindLabel ? label_tiles(tiles[j].width, tiles[j].height, tiles[j].factor, vote, td[(size_t)j].channels)
+                 : kind == kTileKindIngest ? ingest_tiles(tiles[j].width, tiles[j].height)
                  : kind == kTileKindBox ? tile_tiles(tiles[j].width, tiles[j].height, tiles[j].factor, td[(size_t)j].channels)
                                         : tile_select_tiles(kind, tiles[j].width, tiles[j].height, tiles[j].factor, td[(size_t)j].channels);
         }
@@ -306,6 +342,7 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
                 e.src_off = (u64)pixel_offsets[t.image]; e.dst_off = (u64)plan.at[j];
                 e.w = d.width; e.x = t.x; e.y = t.y; e.cw = t.width; e.ch = t.height; e.tw = td[j].width; e.th = td[j].height; e.f = t.factor;
                 e.first_tile = first_tile[j];
+                if (kind == kTileKindLabel) { e.cfg = label_cfg(t.flags, t.factor, vote, td[j].channels); continue; }
                 if (kind == kTileKindIngest) { e.f = d.height; e.cfg = ingest_cfg(t.flags, d.channels, td[j].channels, t.flags); continue; }   // (the factor is 1: f holds the image's height)
                 e.cfg = kind == kTileKindBox ? tile_cfg(t.factor, d.channels, td[j].channels, mode == QOIMI_THUMB_ALPHA_WEIGHTED && d.channels == 4u, t.flags)   // with 3 source channels the mode is PLAIN
                                              : tile_select_cfg(kind, t.factor, d.channels, td[j].channels, t.flags);
@@ -315,9 +352,9 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
         },
         [&](size_t k, int first, int m, uint8_t* staging, hipStream_t st) {
             stats[0] += 1;
-            (kind == kTileKindIngest ? launch_tensor_ingest : kind == kTileKindBox ? launch_tile_gather : launch_tile_select)((const uint8_t*)d_pixels, d_tab + first, (uint32_t)m, sub_tiles[k], staging, grid_bound(c, sub_tiles[k]), st);
+            (kind == kTileKindLabel ? launch_label_ingest : kind == kTileKindIngest ? launch_tensor_ingest : kind == kTileKindBox ? launch_tile_gather : launch_tile_select)((const uint8_t*)d_pixels, d_tab + first, (uint32_t)m, sub_tiles[k], staging, grid_bound(c, sub_tiles[k]), st);
             const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(QOIMI_E_INTERNAL, std::string(kind == kTileKindIngest ? "tensor_ingest: " : kind == kTileKindBox ? "tile_gather: " : "tile_select: ") + hipGetErrorString(e));
+            if (e != hipSuccess) return fail(QOIMI_E_INTERNAL, std::string(kind == kTileKindLabel ? "label_ingest: " : kind == kTileKindIngest ? "tensor_ingest: " : kind == kTileKindBox ? "tile_gather: " : "tile_select: ") + hipGetErrorString(e));
             stats[1] += 1;
             return (int)QOIMI_OK;
         });

@@ -364,6 +364,8 @@ void launch_tile_gather(const uint8_t* pixels, const TileEntry* tab, uint32_t m,
 void launch_tile_select(const uint8_t* pixels, const TileEntry* tab, uint32_t m, uint32_t tiles, uint8_t* stage, uint32_t grid, hipStream_t st);
 // tensor_ingest: the same over a table of QOIMI_TILE_SRC entries - tensor sources (qoi_ingest.hip; ingest_cfg, ingest_tiles: qoi_ingest_core.h)
 void launch_tensor_ingest(const uint8_t* pixels, const TileEntry* tab, uint32_t m, uint32_t tiles, uint8_t* stage, uint32_t grid, hipStream_t st);
+// label_ingest: the same over a table of QOIMI_TILE_LABELS entries - one-plane integer sources (qoi_label.hip; label_cfg, label_tiles: qoi_label_core.h)
+void launch_label_ingest(const uint8_t* pixels, const TileEntry* tab, uint32_t m, uint32_t tiles, uint8_t* stage, uint32_t grid, hipStream_t st);
 
 // ---- row seek index (qoi_seek.hip; the arithmetic: qoi_seek_core.h) ------------------
 struct SeekPoint;                                       // = qoimi_seek_point (qoi_seek_core.h)

@@ -39,6 +39,19 @@ each of F32, F16 and BF16 the element ``tensors.convert`` writes for v converts 
 and bias -1 with ``SYMMETRIC``, scale 1 and bias 0 with ``BYTES``.  The work items of the kernel tensor_ingest, which a tensor call runs in
 the place of tile_gather: ``ingest_items`` and ``ingest_tiles`` - four consecutive output pixels an item.
 
+Label tensors as the source (``LABELS`` and the dtype bits beside it; ``label_flags`` builds them).  The image a tile names then is ONE
+PLANE ``[h, w]`` of uint8, int32 or int64 class indices, tightly packed at a byte offset that is a multiple of the element size.
+``labels_to_bytes`` states the byte image B it stands for: the byte b of an element v is 0 for v < 0, 255 for v > 255, else v - saturation
+of the whole 32- / 64-bit value (2^32 is 255), and silent: an ignore index of -100 becomes 0 - and pixel (Y, X) of B ``uint8[h, w, 4]`` is
+``(b, b, b, 255)``.  The tile is the tile of B as a 4-channel byte image without the label bits, in the call's mode: unlike a tensor tile it
+may reduce, with ``NEAREST`` (factor 1..64) and ``MODE`` (factor 1..16); a label source is never averaged, so ``PLAIN`` and
+``ALPHA_WEIGHTED`` take factor 1 only (``label_wrong``).  All pixels of B are grey with alpha 255, so the whole-pixel vote is the vote on b.
+A call is a byte call, a tensor call or a label call, and an image has one dtype.  The descriptor's channel count only says what och is
+where the call's channels is 0; ``tile`` has no descriptor, so there 0 is B's own 4.  Three properties, asserted by
+tests/test_label_ingest_model.py: values in 0..255 come back from ``nearest`` of the factor-1 tile's first channel; a uint8 label tile is
+the byte tile over B; with f dividing w and h a ``MODE`` label tile is ``mode.mode`` of B at ``w/f x h/f``.  The work items of the kernel
+label_ingest, which a label call runs in the place of tile_gather: ``label_tiles`` - ``ingest_tiles`` at factor 1, ``select_tiles`` above.
+
 The plan: tile j's slot is ``tw * th * och`` rounded up to 256 plus the encode bound of its descriptor rounded up to 256; sub-batches are cut
 by ``packplan.plan`` over those slots, in tile order.
 """
@@ -66,6 +79,12 @@ HWC, CHW = 0, 1
 UNIT, SYMMETRIC, BYTES = 0, SRC_SYMMETRIC, SRC_BYTES
 ELEM = {U8: 1, F16: 2, BF16: 2, F32: 4}
 SOURCE_ARRAYS = {U8: np.uint8, F16: np.float16, BF16: np.uint16, F32: np.float32}     # (NumPy has no bfloat16: its bits)
+LABELS = 2048                   # QOIMI_TILE_LABELS: the image is one plane of class indices of the dtype the bits below give (none: u8)
+LABELS_I32, LABELS_I64 = 4096, 8192             # QOIMI_TILE_LABELS_I32 / _I64: the dtype field, bits 12-13 (12288 is not a dtype)
+LABELS_MASK = LABELS | 12288                    # (bit 10 and bits 14 up stay unknown; SRC_MASK is what it was)
+L_U8, L_I32, L_I64 = 0, 1, 2                    # the dtype field's values
+LABEL_ELEM = {L_U8: 1, L_I32: 4, L_I64: 8}
+LABEL_ARRAYS = {L_U8: np.uint8, L_I32: np.int32, L_I64: np.int64}
 INGEST_PIXELS = 4               # output pixels of a work item of tensor_ingest
 THREADS = 256                   # work items of a tile of the gather kernels
 MAX_LEVELS = 7
@@ -100,9 +119,9 @@ def size(w: int, h: int, sch: int, t, channels: int = 0) -> Tuple[int, int, int]
     _, x, y, cw, ch, f, flags, reserved = fields(t)
     if not _desc_ok(w, h, sch) or channels not in (0, 3, 4):
         return 0, 0, 0
-    if cw < 1 or ch < 1 or x < 0 or y < 0 or x + cw > w or y + ch > h or not 1 <= f <= MAX_FACTOR or (flags & ~(FLIP_X | FLIP_Y | SRC_MASK)) or reserved:
+    if cw < 1 or ch < 1 or x < 0 or y < 0 or x + cw > w or y + ch > h or not 1 <= f <= MAX_FACTOR or (flags & ~(FLIP_X | FLIP_Y | SRC_MASK | LABELS_MASK)) or reserved:
         return 0, 0, 0
-    if source_wrong(flags, f):
+    if source_wrong(flags, f) or label_wrong(flags, f):
         return 0, 0, 0
     tw, th = thumbs.size(cw, ch, f)
     return tw * th * (channels or sch), tw, th
@@ -202,6 +221,63 @@ def ingest_tiles(cw: int, ch: int) -> int:
     return -(-ingest_items(cw, ch) // THREADS)
 
 
+# ---------------------------------------------------------------------------------- label tensors as the source (QOIMI_TILE_LABELS*)
+def label_flags(dtype: int = L_U8) -> int:
+    """The bits of ``qoimi_tile.flags`` for a label source of dtype ``L_U8`` / ``L_I32`` / ``L_I64``.  Or them to a tile's flips."""
+    if dtype not in (L_U8, L_I32, L_I64):
+        raise ValueError("label_flags: no such dtype")
+    return LABELS | (dtype << 12)
+
+
+def label_dtype(flags: int) -> int:
+    """The dtype field of a tile's flags (``LABELS`` itself is not looked at)."""
+    return (flags >> 12) & 3
+
+
+def label_wrong(flags: int, factor: int = 1, mode=None) -> str:
+    """"" if the flags carry no label bit or are those of a label tile the calls accept, else what is wrong - in the order the calls look,
+    behind ``source_wrong``.  mode None: ``qoimi_tile_size``, which has no mode and does not apply the averaging rule."""
+    lab = flags & LABELS_MASK
+    if not lab:
+        return ""
+    if not lab & LABELS:
+        return "a LABELS_* bit without LABELS"
+    if label_dtype(lab) == 3:
+        return "12288 is not a dtype"
+    if flags & SRC_MASK:
+        return "LABELS together with a SRC bit"
+    if mode in (PLAIN, ALPHA_WEIGHTED) and factor != 1:
+        return "a label source is never averaged"
+    return ""
+
+
+def label_bytes(w: int, h: int, flags: int) -> int:
+    """Bytes the plane takes behind its ``pixel_offsets`` entry: ``w * h`` elements of its dtype."""
+    return w * h * LABEL_ELEM[label_dtype(flags)]
+
+
+def labels_to_bytes(A: np.ndarray, flags: int) -> np.ndarray:
+    """The plane A ``[h, w]`` of uint8 / int32 / int64 in the dtype the label bits of `flags` give -> B ``uint8[h, w, 4]``: the byte image
+    the tile is taken from.  b = 0 for v < 0, 255 for v > 255, else v - exact for the whole int64 range -; the pixel is (b, b, b, 255)."""
+    what = label_wrong(flags)
+    if what or not flags & LABELS:
+        raise ValueError("labels_to_bytes: " + (what or "no LABELS bit"))
+    A = np.asarray(A)
+    want = LABEL_ARRAYS[label_dtype(flags)]
+    if A.ndim != 2 or A.dtype != want:
+        raise ValueError("labels_to_bytes: A is [h, w] of " + np.dtype(want).name)
+    b = np.clip(A, 0, 255).astype(np.uint8)                            # (a clip in A's own dtype: no value is narrowed before it)
+    B = np.full(A.shape + (4,), 255, dtype=np.uint8)
+    B[:, :, :3] = b[:, :, None]
+    return B
+
+
+def label_tiles(cw: int, ch: int, f: int, och: int, mode: int) -> int:
+    """Tiles of 256 work items of a tile of a label call (the kernel label_ingest): at factor 1 tensor_ingest's - four consecutive output
+    pixels an item -, else tile_select's in ``NEAREST`` or ``MODE``."""
+    return ingest_tiles(cw, ch) if f == 1 else select_tiles(cw, ch, f, och, mode)
+
+
 def select(R: np.ndarray, f: int, mode: int) -> np.ndarray:
     """R uint8[ch, cw, sch] -> uint8[th, tw, sch]: of every f-block (the box filter's partition) the centre pixel (``NEAREST``) or the winner of
     ``mode.vote`` (``MODE``, f <= 16), taken at 4 bytes per pixel - alpha 255 behind a 3-channel R - and given back with R's channels."""
@@ -228,8 +304,16 @@ def select(R: np.ndarray, f: int, mode: int) -> np.ndarray:
 
 def tile(S: np.ndarray, t, channels: int = 0, mode: int = PLAIN) -> np.ndarray:
     """S uint8[h, w, sch] (sch 3 or 4), t a tile of it -> uint8[th, tw, och]: the pixels stream j encodes.  A tile with ``SRC`` takes S as the
-    tensor its flags describe (``convert`` states the bytes B it stands for) and is the tile of B without the source bits."""
+    tensor its flags describe (``convert`` states the bytes B it stands for) and is the tile of B without the source bits.  A tile with
+    ``LABELS`` takes S as the plane [h, w] its flags describe (``labels_to_bytes``) and is the tile of that B in `mode`; channels 0 is B's 4."""
     _, x, y, cw, ch, f, flags, reserved = fields(t)
+    if flags & LABELS_MASK and not source_wrong(flags, f):
+        what = label_wrong(flags, f, mode)
+        if what:
+            raise ValueError("tile: " + what)
+        S = labels_to_bytes(S, flags)
+        flags &= ~LABELS_MASK
+        t = (0, x, y, cw, ch, f, flags, reserved)
     if flags & SRC_MASK:
         S = convert(S, flags)                                          # (raises where the bits are no format)
         t = (0, x, y, cw, ch, f, flags & ~SRC_MASK, reserved)
@@ -294,6 +378,11 @@ def plan(descs: Sequence, tiles: Sequence, channels: int, staging_bytes: int):
         raise ValueError("plan: a call is a byte call or a tensor call")
     if len({(fields(t)[0], s) for t, s in zip(tiles, srcs)}) != len({fields(t)[0] for t in tiles}):
         raise ValueError("plan: an image is named with two source formats")
+    labs = [fields(t)[6] & LABELS_MASK for t in tiles]
+    if any(labs) and not all(labs):
+        raise ValueError("plan: a call is a byte call, a tensor call or a label call")
+    if len({(fields(t)[0], s) for t, s in zip(tiles, labs)}) != len({fields(t)[0] for t in tiles}):
+        raise ValueError("plan: an image is named with two label dtypes")
     for t in tiles:
         image = fields(t)[0]
         d = descs[image]
