@@ -381,10 +381,32 @@ enum { QOIMI_TILE_SRC = 16, QOIMI_TILE_SRC_CHW = 32, QOIMI_TILE_SRC_F16 = 64, QO
  * and pack-overlap checks above, taken over w * h * E bytes; a sub-batch of the plan with 2^31 - 1 or more tiles of 256 work items of the
  * kernel (an item is four consecutive pixels of a tile's output at factor 1, else 1 to 64 per output pixel as in the label modes).  A
  * label call runs a gather kernel of its own over the same table; qoimi_tile_stats counts its launches in [1].
- * Not here (of label sources): a count of saturated elements, a remap table, i16 / u16, ids above 255 spread over r, g and b, float class
+ * 24-bit ids.  An instance map, a panoptic map (class * 1000 + instance) or a superpixel map has ids far above 255, which the byte rule
+ * would all make 255.
+ *   QOIMI_TILE_LABELS_ID24            bit 15, only together with QOIMI_TILE_LABELS: the elements of the plane are ids, not class indices
+ * The plane, its dtype field, its alignment and its extent are those of a label tile.  The conversion (normative; qoi_amd/tiles.py:
+ * label_ids_to_bytes states it in Python).  The id of the element v is 0 for v < 0, 2^24 - 1 for v > 2^24 - 1, else v: saturation of the
+ * full 32- / 64-bit value - the high dword of an int64 takes part: 2^32 + 5 is 2^24 - 1, not 5 - and silent, as the byte rule is.  Pixel
+ * (Y, X) of B is (id & 255, (id >> 8) & 255, id >> 16, 255) - as a dword id | 0xFF000000 -: the COCO panoptic convention
+ * id = R + 256 * G + 256^2 * B, so a panoptic PNG converted to QOI already is such a pack.  A u8 plane with the bit gives (v, 0, 0, 255):
+ * it is allowed so that a mask can join an id pack.  Everything behind B is what a label tile does without the bit: the rectangle, the
+ * flips, och (4 to 3 drops the 255), factor 1, QOIMI_TILE_NEAREST at factor 1..64 and QOIMI_TILE_MODE at 1..16, never the averaging
+ * modes, the reference encoder's stream byte for byte, the pack, the tables, the plan and the slots.  The pixels are no longer grey, so
+ * the vote is the whole-pixel vote as it stands: among several winners without the centre pixel the lowest
+ * r << 24 | g << 16 | b << 8 | a wins - the order of the id's bytes from the LOW byte up, not the lowest id: of the ids 256 and 1 it is
+ * 256, which is (0, 1, 0, 255).  The rule of qoi_amd/mode.py: vote is not changed.
+ * Properties (tests/test_label_id_model.py asserts them on qoi_amd/tiles.py and qoi_amd/tensors.py).  (a) For a plane with all values in
+ * 0..2^24 - 1, any dtype, whole-image tiles at factor 1: qoimi_decode_tensors of the pack with QOIMI_FILTER_NEAREST, QOIMI_TENSOR_I64 and
+ * QOIMI_TENSOR_HW_ID24 at the image's size returns the plane widened to int64.  (b) A call without the bit gives the bytes it gave.  (c)
+ * With f dividing w and h, an ID24 QOIMI_TILE_MODE tile decodes to what QOIMI_FILTER_MODE gives from the factor-1 pack at w/f x h/f.
+ * Its checks, where the label checks stand: bit 15 without QOIMI_TILE_LABELS is "a LABELS_* bit without QOIMI_TILE_LABELS"; "two tiles
+ * that name the same image with different label bits" compares bit 15 too - an image is bytes or ids -; images with and without the bit
+ * mix in one label call.  The gather kernel is the label call's, with the id variant as three more values of an entry's dtype field.
+ * Not here (of label sources): a count of saturated elements, a remap table, i16 / u16, ids above 2^24 - 1 (alpha is 255), float class
  * maps, a plane of a CHW tensor chosen by index (offset it yourself), row-pitched planes, label and tensor tiles in one call. */
 enum { QOIMI_TILE_LABELS = 2048, QOIMI_TILE_LABELS_I32 = 4096, QOIMI_TILE_LABELS_I64 = 8192 };
-/* dtype field, bits 12-13: 0 u8, 1 i32, 2 i64; 12288 is not a dtype.  Bit 10 and bits 14 up stay unknown flag bits. */
+enum { QOIMI_TILE_LABELS_ID24 = 32768 };   /* bit 15: 24-bit ids over r, g and b; bit 14 stays an unknown flag bit */
+/* dtype field, bits 12-13: 0 u8, 1 i32, 2 i64; 12288 is not a dtype.  Bit 10, bit 14 and bits 16 up stay unknown flag bits; bit 15: QOIMI_TILE_LABELS_ID24. */
 typedef struct {                 /* 32 bytes, offsets 0/4/8/12/16/20/24/28 */
     unsigned int image;          /* index into the call's images */
     unsigned int x, y;           /* top-left corner of the source rectangle */
@@ -999,6 +1021,13 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  * what is stored.  Every layout goes with every dtype, every filter and the warp: QOIMI_TENSOR_I64 with QOIMI_TENSOR_HW is the N x H x W of
  * class indices a loss function takes.  QOIMI_TENSOR_U8 with QOIMI_TENSOR_HWC therefore is the underlying call byte for byte, and every
  * other format a pure function of its bytes: the exact-integer definitions of the three filters stand as they are.
+ * QOIMI_TENSOR_HW_ID24 is one plane, as QOIMI_TENSOR_HW is: the element at index Y * ow + X is r | g << 8 | b << 16 of the pixel the u8
+ * call would store at (Y, X) - the 24-bit id of the COCO panoptic convention id = R + 256 * G + 256^2 * B, what QOIMI_TILE_LABELS_ID24
+ * packs and what a panoptic PNG converted to QOI holds.  Alpha is ignored (channels 3 and 4 give the same ids); `channels` still only says
+ * how the image is decoded; sizes, overlap and alignment count one element per pixel.  It goes with QOIMI_TENSOR_I32 and QOIMI_TENSOR_I64
+ * only, whose scale is 1 and bias +0.  It goes with every filter and the warp, the element being a pure function of the underlying
+ * call's bytes, but it MEANS something only under the selections, which invent no pixel: QOIMI_FILTER_NEAREST / _MODE and
+ * QOIMI_WARP_NEAREST / _VOTE2 / _VOTE4; an averaged id is no id.
  * Only whole, naturally aligned elements are stored (u8 HWC: as the underlying call stores): no word is read and written back, two outputs
  * may share one.
  * QOIMI_FILTER_BICUBIC (normative; qoi_amd/bicubic.py: bicubic states it in Python) is the antialiased bicubic filter - Keys' cubic with
@@ -1080,24 +1109,25 @@ int qoimi_warp_orient(const qoi_desc *desc, unsigned x, unsigned y, unsigned wid
  *   everything else      as for the underlying call
  * SYNCHRONOUS: returns when every output is written.  QOIMI_E_ARG, looked for in this order: an unknown filter; a NULL or empty argument
  * (format apart); channels; mode; the format - NULL, an unknown dtype, an unknown layout, reserved != 0, a scale or bias that is not finite,
- * QOIMI_TENSOR_U8, QOIMI_TENSOR_I32 or QOIMI_TENSOR_I64 with a scale other than 1 or a bias other than +0; then everything the underlying call rejects, with its messages, item by
+ * QOIMI_TENSOR_U8, QOIMI_TENSOR_I32 or QOIMI_TENSOR_I64 with a scale other than 1 or a bias other than +0, QOIMI_TENSOR_HW_ID24 with a dtype other than QOIMI_TENSOR_I32 / _I64 (the last of the format checks; its message names ID24); then everything the underlying call rejects, with its messages, item by
  * item - an output whose size in BYTES does not fit a size_t or that ends behind the address space among them -, output ranges that overlap,
  * in bytes; an output address that is not a multiple of the element size; a sub-batch of the plan with 2^31 - 1 tiles or more.  All are
  * reported before anything is launched, the caller's buffers are untouched; qoimi_last_error names the cause.  The sub-batches count as decode
  * calls of the context.  One call at a time per context, as everywhere.
  * Not here: indexed forms, a majority (mode) filter per channel, with weights or over cells above 16 x 16 (QOIMI_FILTER_MODE votes on whole
- * pixels of cells up to that; the warp has QOIMI_WARP_VOTE2 / QOIMI_WARP_VOTE4), 16-bit or signed label sources (a label is a byte of the image), a remapping table from byte to class index, a single
+ * pixels of cells up to that; the warp has QOIMI_WARP_VOTE2 / QOIMI_WARP_VOTE4), 16-bit or signed label sources (a label is a byte of the image, or with QOIMI_TENSOR_HW_ID24 three), ids above 2^24 - 1, a remapping table from byte to class index, a single
  * 8-byte store per QOIMI_TENSOR_I64 element (it is two dword stores), a u8 entry point or a stats function of the bicubic, the Lanczos, the nearest or the mode filter's own, other cubic kernels (a = -3/4), other Lanczos windows, a format per item, tensor forms of qoimi_decode_thumbnails and qoimi_decode_crops (an item whose output has the
  * size of its rectangle, or divides it, is those). */
 enum { QOIMI_TENSOR_U8 = 0, QOIMI_TENSOR_F16 = 1, QOIMI_TENSOR_BF16 = 2, QOIMI_TENSOR_F32 = 3 };   /* element sizes 1 / 2 / 2 / 4 */
 enum { QOIMI_TENSOR_I32 = 5, QOIMI_TENSOR_I64 = 6 };   /* element sizes 4 / 8; 4 is not a dtype */
 enum { QOIMI_TENSOR_HWC = 0, QOIMI_TENSOR_CHW = 1, QOIMI_TENSOR_HW = 3 };   /* 2 is not a layout */
+enum { QOIMI_TENSOR_HW_ID24 = 5 };   /* one plane of r | g << 8 | b << 16, QOIMI_TENSOR_I32 / _I64 only; 4 is not a layout */
 enum { QOIMI_FILTER_AREA = 0, QOIMI_FILTER_BILINEAR = 1, QOIMI_FILTER_BICUBIC = 3, QOIMI_FILTER_LANCZOS = 6 };   /* 2 is not a filter, nor are 4, 5 and 7 */
 enum { QOIMI_FILTER_NEAREST = 9 };   /* 8 is not a filter */
 enum { QOIMI_FILTER_MODE = 11 };   /* 10 is not a filter */
 typedef struct {                 /* 48 bytes, offsets 0/4/8/24/40 */
     unsigned int dtype;          /* QOIMI_TENSOR_* */
-    unsigned int layout;         /* QOIMI_TENSOR_HWC / _CHW / _HW */
+    unsigned int layout;         /* QOIMI_TENSOR_HWC / _CHW / _HW / _HW_ID24 */
     float scale[4];              /* per channel r, g, b, a */
     float bias[4];
     unsigned int reserved[2];    /* 0 */
@@ -1111,7 +1141,7 @@ int qoimi_decode_warped_tensors(qoimi_ctx *ctx, const void *d_streams, const siz
                                 const qoimi_warp *items /* host */, int n_items, int mode, const qoimi_tensor_format *format /* host */,
                                 void *d_out, const size_t *out_offsets /* host, n_items */, size_t staging_bytes, void *stream);
 
-/* out_width * out_height * channels * element size (QOIMI_TENSOR_HW: out_width * out_height * element size) - the bytes of the item's output -
+/* out_width * out_height * channels * element size (QOIMI_TENSOR_HW, QOIMI_TENSOR_HW_ID24: out_width * out_height * element size) - the bytes of the item's output -
  * or 0 if filter is unknown, the format is one the calls reject, qoimi_resize_size / qoimi_bilinear_size (by filter) or qoimi_warp_size would
  * return 0, the item is beyond the limits of QOIMI_FILTER_BICUBIC, QOIMI_FILTER_LANCZOS, QOIMI_FILTER_NEAREST or QOIMI_FILTER_MODE with that filter, or the
  * product does not fit a size_t.  Pure

@@ -502,7 +502,9 @@ class Context:
         tensors - u8 / f16 / bf16 / f32, HWC or CHW, factor 1 - converted on the way in (``tiles.convert``); pixel_offsets stay byte offsets
         (``tiles.source_bytes`` an image; d_pixels is an address: no length of it is looked at here).  With ``tiles.label_flags(dtype)`` in
         every tile's flags the images are one-plane u8 / int32 / int64 label maps (``tiles.labels_to_bytes``; ``tiles.label_bytes`` an
-        image), saturated to 0..255 silently; they reduce with ``tiles.NEAREST`` and ``tiles.MODE`` and are never averaged."""
+        image), saturated to 0..255 silently; they reduce with ``tiles.NEAREST`` and ``tiles.MODE`` and are never averaged.  With
+        ``tiles.label_flags(dtype, ids=True)`` (``tiles.LABELS_ID24``) the elements are 24-bit ids, saturated to 0..2^24 - 1 and spread over
+        r, g and b (``tiles.label_ids_to_bytes``); ``tensors.HW_ID24`` puts them together again."""
         n_images = len(descs)
         seqs = self._per_image("encode_tiles", "pixel offset per descriptor", n_images, pixel_offsets=pixel_offsets, descs=descs)
         shortest, longest, noun, malformed = _ITEMS[QoimiTile]
@@ -690,7 +692,7 @@ class Context:
         likewise) with the outputs written
         as tensors (``qoimi_decode_tensors``, synchronous, through bounded staging): f is a ``QoimiTensorFormat`` or the tuple of
         ``tensors.fmt`` - u8, f16, bf16 or f32 elements, HWC or CHW, each channel scaled and shifted, or i32 / i64 class indices, and HW: the
-        first channel as one plane; every d_out + out_offsets[j] is a
+        first channel as one plane, or HW_ID24 (i32 / i64 only): ``r | g << 8 | b << 16`` as one plane of 24-bit ids; every d_out + out_offsets[j] is a
         multiple of the element size; ``qoi_amd/tensors.py: tensors`` states the result."""
         self._gather("decode_tensors", QoimiResize, d_streams, stream_offsets, sizes, descs, channels, items, (filter, mode), d_out, out_offsets, staging_bytes,
                      stream, f=f)

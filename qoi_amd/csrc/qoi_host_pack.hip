@@ -156,13 +156,15 @@ static_assert(QOIMI_TILE_SRC == (int)kTileSrc && QOIMI_TILE_SRC_CHW == (int)kTil
 static_assert(QOIMI_TILE_LABELS == (int)kTileLabels && QOIMI_TILE_LABELS_I32 == (int)(kLabelI32 << kTileLabelsDtypeShift) &&
               QOIMI_TILE_LABELS_I64 == (int)(kLabelI64 << kTileLabelsDtypeShift) && kTileLabelsMask == 0x3800u && (kTileLabelsMask & kTileSrcMask) == 0u,
               "the label source's bits: 11, and the dtype field in 12-13; bit 10 stays an unknown flag bit");
+static_assert(QOIMI_TILE_LABELS_ID24 == (int)kTileLabelsId24 && kTileLabelsId24 == 1u << 15 && (kTileLabelsId24 & (kTileLabelsMask | kTileSrcMask)) == 0u && (kLabelId24 & 3u) == 0u,
+              "24-bit ids: bit 15, beside the dtype field; bit 14 stays an unknown flag bit");
 
 // nullptr if the tile is fine for an accepted descriptor, else what is wrong with it
 static const char* tile_wrong(const qoi_desc* d, const qoimi_tile* t) {
     if (t->width == 0u || t->height == 0u) return "zero width or height";
     if ((uint64_t)t->x + t->width > d->width || (uint64_t)t->y + t->height > d->height) return "the rectangle leaves its image";
     if (t->factor < 1u || t->factor > kThumbMaxFactor) return "factor outside 1..64";
-    if ((t->flags & ~((unsigned)(QOIMI_CROP_FLIP_X | QOIMI_CROP_FLIP_Y) | kTileSrcMask | kTileLabelsMask)) != 0u) return "unknown flag bit";
+    if ((t->flags & ~((unsigned)(QOIMI_CROP_FLIP_X | QOIMI_CROP_FLIP_Y) | kTileSrcMask | kTileLabelsMask | kTileLabelsId24)) != 0u) return "unknown flag bit";
     if (t->reserved != 0u) return "reserved is not 0";
     return nullptr;
 }
@@ -180,7 +182,7 @@ static const char* tile_src_wrong(const qoimi_tile* t) {
 
 // ... and of its label source (QOIMI_TILE_LABELS*), looked at behind those; averaging: the call's mode is one of the two box averages
 static const char* tile_label_wrong(const qoimi_tile* t, bool averaging) {
-    const uint32_t lab = t->flags & kTileLabelsMask;
+    const uint32_t lab = t->flags & (kTileLabelsMask | kTileLabelsId24);
     if (lab == 0u) return nullptr;
     if ((lab & kTileLabels) == 0u) return "a QOIMI_TILE_LABELS_* bit without QOIMI_TILE_LABELS";
     if (label_dtype(lab) == 3u) return "12288 is not a dtype of a label source";
@@ -282,7 +284,7 @@ extern "C" int qoimi_encode_tiles(qoimi_ctx* c, const void* d_pixels, const size
     if (labels) {
         kind = kTileKindLabel;
         for (size_t j = 0; j < n; ++j) {
-            const uint32_t lab = tiles[j].flags & kTileLabelsMask;
+            const uint32_t lab = tiles[j].flags & (kTileLabelsMask | kTileLabelsId24);      // (bit 15 too: an image is bytes or ids)
             if (lab_of[tiles[j].image] != 0u && lab_of[tiles[j].image] != lab)
                 return fail(QOIMI_E_ARG, "tile " + std::to_string(j) + ": image " + std::to_string(tiles[j].image) + " is named with two different label dtypes");
             lab_of[tiles[j].image] = lab;

@@ -20,9 +20,10 @@ static_assert(QOIMI_TENSOR_U8 == (int)kTensorU8 && QOIMI_TENSOR_F16 == (int)kTen
               QOIMI_TENSOR_I32 == (int)kTensorI32 && QOIMI_TENSOR_I64 == (int)kTensorI64 &&
               QOIMI_TENSOR_HWC == (int)kTensorHWC && QOIMI_TENSOR_CHW == (int)kTensorCHW && QOIMI_TENSOR_HW == (int)kTensorHW, "the kernels take dtype and layout as numbers");
 static_assert(QOIMI_TENSOR_I32 == 5 && QOIMI_TENSOR_I64 == 6 && QOIMI_TENSOR_HW == 3, "4 is not a dtype, 2 is not a layout");
+static_assert(QOIMI_TENSOR_HW_ID24 == (int)kTensorHWId24 && QOIMI_TENSOR_HW_ID24 == 5, "the id layout; 4 is not a layout");
 
 static bool tensor_dtype_known(unsigned dtype) { return dtype <= (unsigned)QOIMI_TENSOR_F32 || dtype == (unsigned)QOIMI_TENSOR_I32 || dtype == (unsigned)QOIMI_TENSOR_I64; }
-static bool tensor_layout_known(unsigned layout) { return layout <= (unsigned)QOIMI_TENSOR_CHW || layout == (unsigned)QOIMI_TENSOR_HW; }
+static bool tensor_layout_known(unsigned layout) { return layout <= (unsigned)QOIMI_TENSOR_CHW || layout == (unsigned)QOIMI_TENSOR_HW || layout == (unsigned)QOIMI_TENSOR_HW_ID24; }
 
 // nullptr if the format is fine, else what is wrong with it - in the order the header gives
 static const char* tensor_format_wrong(const qoimi_tensor_format* f) {
@@ -40,6 +41,8 @@ static const char* tensor_format_wrong(const qoimi_tensor_format* f) {
                      : f->dtype == (unsigned)QOIMI_TENSOR_I32 ? "QOIMI_TENSOR_I32 takes scale 1 and bias +0 only" : "QOIMI_TENSOR_I64 takes scale 1 and bias +0 only";
         }
     }
+    if (f->layout == (unsigned)QOIMI_TENSOR_HW_ID24 && f->dtype != (unsigned)QOIMI_TENSOR_I32 && f->dtype != (unsigned)QOIMI_TENSOR_I64)
+        return "QOIMI_TENSOR_HW_ID24 takes QOIMI_TENSOR_I32 or QOIMI_TENSOR_I64 only (an id does not fit a byte, and is not scaled)";
     return nullptr;
 }
 
@@ -57,8 +60,10 @@ static TensorFormat kernel_format(const qoimi_tensor_format* f) {
 
 // Bytes of an element of the format; 1 for a format the check rejects (used behind the format's check only)
 static size_t format_elem(const qoimi_tensor_format* f) { return (f && tensor_dtype_known(f->dtype)) ? tensor_elem(f->dtype) : 1u; }
-// Elements of a pixel of an output with och channels: one under QOIMI_TENSOR_HW
-static unsigned format_channels(const qoimi_tensor_format* f, unsigned och) { return (f && f->layout == (unsigned)QOIMI_TENSOR_HW) ? 1u : och; }
+// Elements of a pixel of an output with och channels: one under QOIMI_TENSOR_HW and QOIMI_TENSOR_HW_ID24
+static unsigned format_channels(const qoimi_tensor_format* f, unsigned och) {
+    return (f && (f->layout == (unsigned)QOIMI_TENSOR_HW || f->layout == (unsigned)QOIMI_TENSOR_HW_ID24)) ? 1u : och;
+}
 
 // pixel_bytes (resize_bytes, warp_bytes: the u8 output) at the format's elements per pixel times the element size, false if that does not
 // fit a size_t

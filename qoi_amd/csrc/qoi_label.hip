@@ -15,7 +15,9 @@
 //                 entry's: the workgroup branches once per tile of the walk, never per lane, and every cross-lane operation is reached
 //                 by all 256 lanes - lanes behind the tile's last pixel take part holding nothing.  Loads are plain.  No LDS, no
 //                 barrier, no atomics; nothing of the caller's is written, and of a plane nothing is read but its whole, naturally aligned
-//                 elements (u8: the aligned dwords that hold one of its bytes).
+//                 elements (u8: the aligned dwords that hold one of its bytes).  QOIMI_TILE_LABELS_ID24 is three more values of the
+//                 entry's dtype field, so three more cases of that one branch: the same loads, items and stores, a saturation at
+//                 2^24 - 1 in the place of 255 and an or in the place of the multiply.
 #include "qoi_dev.h"
 #include "qoi_label_core.h"
 
@@ -54,28 +56,28 @@ __device__ __forceinline__ u64 label_xor_max(u64 v, uint32_t step) {
 }
 
 // One tile of kTileThreads items of an entry with f == 1.
-template <uint32_t DT>
+template <uint32_t DT, uint32_t ID>
 __device__ __forceinline__ void label_copy(const LabelMem& mem, const TileEntry& e, u64 base, u64 q, uint32_t tile) {
     const u64 k = (u64)tile * kTileThreads + threadIdx.x;
-    if (k < ingest_items(e.cw, e.ch)) label_item<DT>(mem, e, base, q, (uint32_t)k);
+    if (k < ingest_items(e.cw, e.ch)) label_item<DT, ID>(mem, e, base, q, (uint32_t)k);
 }
 
 // One tile of kTileThreads items of a NEAREST entry with f >= 2: a lane per output pixel.
-template <uint32_t DT>
+template <uint32_t DT, uint32_t ID>
 __device__ __forceinline__ void label_nearest(const LabelMem& mem, const TileEntry& e, u64 base, u64 q, uint32_t tile) {
     const u64 o = (u64)tile * kTileThreads + threadIdx.x;
-    if (o < (u64)e.tw * e.th) label_nearest_item<DT>(mem, e, base, q, (uint32_t)o);
+    if (o < (u64)e.tw * e.th) label_nearest_item<DT, ID>(mem, e, base, q, (uint32_t)o);
 }
 
 // One tile of kTileThreads items of a MODE entry with f >= 2: tile_select's meeting loop and butterfly over the block.
-template <uint32_t DT>
+template <uint32_t DT, uint32_t ID>
 __device__ __forceinline__ void label_vote(const LabelMem& mem, const TileEntry& e, u64 base, u64 q, uint32_t tile) {
     const uint32_t lg = e.cfg & 255u, L = 1u << lg;
     const u64 item = (u64)tile * kTileThreads + threadIdx.x, o = item >> lg;
     const uint32_t l = (uint32_t)item & (L - 1u);
     const bool valid = o < (u64)e.tw * e.th;                          // (a pixel's lanes are valid or not together)
     ModeHeld h;
-    if (valid) label_vote_hold<DT>(mem, e, base, (uint32_t)o, l, lg, h);
+    if (valid) label_vote_hold<DT, ID>(mem, e, base, (uint32_t)o, l, lg, h);
     else mode_none(h);
     uint32_t count[kModeHold] = {0u, 0u, 0u, 0u};
     mode_meet(h, h.v, h.n, count);
@@ -91,11 +93,11 @@ __device__ __forceinline__ void label_vote(const LabelMem& mem, const TileEntry&
     if (valid && l == 0u) tile_put(mem, e, q, (uint32_t)o, mode_pick(best));
 }
 
-template <uint32_t DT>
+template <uint32_t DT, uint32_t ID>
 __device__ __forceinline__ void label_tile(const LabelMem& mem, const TileEntry& e, u64 base, u64 q, uint32_t tile) {
-    if (e.f == 1u) label_copy<DT>(mem, e, base, q, tile);
-    else if ((e.cfg & (1u << 24)) == 0u) label_nearest<DT>(mem, e, base, q, tile);
-    else label_vote<DT>(mem, e, base, q, tile);
+    if (e.f == 1u) label_copy<DT, ID>(mem, e, base, q, tile);
+    else if ((e.cfg & (1u << 24)) == 0u) label_nearest<DT, ID>(mem, e, base, q, tile);
+    else label_vote<DT, ID>(mem, e, base, q, tile);
 }
 
 __global__ __launch_bounds__(kTileThreads) void label_ingest(const uint8_t* __restrict__ pixels, const TileEntry* __restrict__ tab, uint32_t m, uint32_t tiles,
@@ -105,9 +107,13 @@ __global__ __launch_bounds__(kTileThreads) void label_ingest(const uint8_t* __re
         const u64 base = (u64)reinterpret_cast<uintptr_t>(pixels) + e.src_off;
         const u64 q = (u64)reinterpret_cast<uintptr_t>(stage) + e.dst_off;
         switch ((e.cfg >> 16) & 15u) {                                  // (the entry's: the whole workgroup takes the same way)
-            case kLabelU8:  label_tile<kLabelU8>(mem, e, base, q, tile); break;
-            case kLabelI32: label_tile<kLabelI32>(mem, e, base, q, tile); break;
-            default:        label_tile<kLabelI64>(mem, e, base, q, tile); break;
+            case kLabelU8:               label_tile<kLabelU8, 0u>(mem, e, base, q, tile); break;
+            case kLabelI32:              label_tile<kLabelI32, 0u>(mem, e, base, q, tile); break;
+            case kLabelI64:              label_tile<kLabelI64, 0u>(mem, e, base, q, tile); break;
+            case kLabelId24 | kLabelU8:  label_tile<kLabelU8, 1u>(mem, e, base, q, tile); break;
+            case kLabelId24 | kLabelI32: label_tile<kLabelI32, 1u>(mem, e, base, q, tile); break;
+            case kLabelId24 | kLabelI64: label_tile<kLabelI64, 1u>(mem, e, base, q, tile); break;
+            default: break;                                             // (label_cfg writes no other value)
         }
     });
 }

@@ -15,6 +15,8 @@
 // to be read first.  Where u8 HWC holds 4 bytes per pixel and the address is aligned the pixel is one dword, as resize_store writes it.
 // With HW only channel 0 (r) of a pixel is stored, at element index yo * ow + xo: one plane of ow * oh elements; och still says how the image
 // was decoded.  An 8-byte element is two aligned dword stores, the value at a and 0 at a + 4 (Mem has no 8-byte store).
+// With HW_ID24 (I32 and I64 only, the host sees to it) the one element of a pixel, at element index yo * ow + xo, is r | g << 8 | b << 16 = px & 0xFFFFFF,
+// the 24-bit id of the COCO panoptic convention; alpha is ignored: the dword at a, and 0 at a + 4 for I64.
 //
 // Plain sequential code over a memory functor `Mem` (store1 / store2 / store4(address, value)), compiled for the device by hipcc
 // (qoi_tensor.hip: the conversions are the hardware's) and - by tests/host/tensor_host.cpp only - for the host, where the narrowing is integer
@@ -28,6 +30,7 @@ namespace qoimi {
 
 constexpr uint32_t kTensorU8 = 0, kTensorF16 = 1, kTensorBF16 = 2, kTensorF32 = 3, kTensorI32 = 5, kTensorI64 = 6;   // (4 is not a dtype)
 constexpr uint32_t kTensorHWC = 0, kTensorCHW = 1, kTensorHW = 3;                                                    // (2 is not a layout)
+constexpr uint32_t kTensorHWId24 = 5;                                                                                // (nor is 4)
 
 // What the kernels take by value: ten dwords (qoimi_tensor_format without its reserved words)
 struct TensorFormat { uint32_t dtype, layout; float scale[4], bias[4]; };
@@ -103,6 +106,12 @@ QOIMI_RESIZE_HD void tensor_store(const Mem& mem, const TensorFormat& fmt, uint6
         return;
     }
     const uint32_t elem = tensor_elem(fmt.dtype);
+    if (fmt.layout == kTensorHWId24) {                             // (I32 or I64: one aligned dword, or two)
+        const uint64_t a = q + at * elem;
+        mem.store4(a, px & 0xFFFFFFu);
+        if (elem == 8u) mem.store4(a + 4u, 0u);
+        return;
+    }
     const uint64_t plane = (uint64_t)ow * oh;
     const uint32_t n = fmt.layout == kTensorHW ? 1u : och;         // elements of a pixel
     QOIMI_RESIZE_UNROLL

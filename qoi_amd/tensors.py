@@ -19,6 +19,11 @@ scale[0] and bias[0] (the others are ignored but must still be finite); och stil
 layout goes with every dtype.  U8 with HWC is P itself; everything else is a pure function
 of P, so the exact-integer definitions of the filters stand as they are.
 
+``HW_ID24`` is one plane [oh, ow] as ``HW`` is, but its element is ``r | g << 8 | b << 16`` of the pixel: the 24-bit id of the COCO panoptic
+convention, what ``tiles.LABELS_ID24`` packs.  Alpha is ignored; och still says how the image is decoded.  It goes with I32 and I64 only
+(the last of ``wrong``'s checks) and with every filter and the warp, but means something only under the selections - ``FILTER_NEAREST`` /
+``FILTER_MODE``, the warp's NEAREST / VOTE2 / VOTE4 -, which invent no pixel.
+
 NumPy has no bfloat16: ``convert`` returns BF16 as uint16 holding the bits (``numpy_dtype`` says what an output's array is).
 
 Normalisation (p / 255 - mean) / std is scale = 1 / (255 * std), bias = -mean / std: ``normalise`` computes both in float64 and rounds once.
@@ -35,6 +40,7 @@ U8, F16, BF16, F32 = 0, 1, 2, 3
 I32, I64 = 5, 6                 # (4 is not a dtype)
 HWC, CHW = 0, 1
 HW = 3                          # (2 is not a layout)
+HW_ID24 = 5                     # (nor is 4)
 FILTER_AREA, FILTER_BILINEAR = 0, 1
 FILTER_BICUBIC = 3              # (2 is not a filter)
 FILTER_LANCZOS = 6              # (nor are 4, 5 and 7)
@@ -46,6 +52,7 @@ ELEM = {U8: 1, F16: 2, BF16: 2, F32: 4}
 INT_ELEM = {I32: 4, I64: 8}     # the integer class-index dtypes, beside ELEM
 DTYPE_NAMES = {"u8": U8, "f16": F16, "bf16": BF16, "f32": F32, "i32": I32, "i64": I64}
 LAYOUT_NAMES = {"hwc": HWC, "chw": CHW, "hw": HW}
+ID_LAYOUT_NAMES = {"id24": HW_ID24}     # the id layouts, beside LAYOUT_NAMES
 _INT_NAMES = {U8: "QOIMI_TENSOR_U8", I32: "QOIMI_TENSOR_I32", I64: "QOIMI_TENSOR_I64"}
 PLAIN = resize.PLAIN
 ALPHA_WEIGHTED = resize.ALPHA_WEIGHTED
@@ -82,13 +89,15 @@ def wrong(f) -> str:
     dtype, layout, scale, bias = f
     if dtype not in ELEM and dtype not in INT_ELEM:
         return "unknown dtype"
-    if layout not in (HWC, CHW, HW):
+    if layout not in (HWC, CHW, HW, HW_ID24):
         return "unknown layout"
     scale, bias = np.asarray(scale, np.float32), np.asarray(bias, np.float32)
     if scale.shape != (4,) or bias.shape != (4,) or not (np.isfinite(scale).all() and np.isfinite(bias).all()):
         return "scale or bias is not finite"
     if dtype in _INT_NAMES and not ((scale == 1.0).all() and (bias.view(np.uint32) == 0).all()):
         return _INT_NAMES[dtype] + " takes scale 1 and bias +0 only"
+    if layout == HW_ID24 and dtype not in INT_ELEM:
+        return "QOIMI_TENSOR_HW_ID24 takes QOIMI_TENSOR_I32 or QOIMI_TENSOR_I64 only"
     return ""
 
 
@@ -105,7 +114,7 @@ def bf16_bits(s: np.ndarray) -> np.ndarray:
 
 def convert(P: np.ndarray, f) -> np.ndarray:
     """P uint8[oh, ow, och] (och 3 or 4), f a format -> [oh, ow, och] (HWC), [och, oh, ow] (CHW) or [oh, ow] (HW: channel 0) of
-    ``numpy_dtype(dtype)``, contiguous."""
+    ``numpy_dtype(dtype)``, contiguous; [oh, ow] of ``r | g << 8 | b << 16`` under ``HW_ID24``."""
     P = np.asarray(P)
     if P.ndim != 3 or P.shape[2] not in (3, 4) or P.dtype != np.uint8:
         raise ValueError("convert: P is uint8[oh, ow, 3 or 4]")
@@ -114,6 +123,9 @@ def convert(P: np.ndarray, f) -> np.ndarray:
         raise ValueError("convert: " + what)
     dtype, layout, scale, bias = f
     och = P.shape[2]
+    if layout == HW_ID24:
+        ids = P[:, :, 0].astype(np.uint32) | (P[:, :, 1].astype(np.uint32) << 8) | (P[:, :, 2].astype(np.uint32) << 16)
+        return np.ascontiguousarray(ids.astype(numpy_dtype(dtype)))
     if dtype == U8:
         out = P
     elif dtype in INT_ELEM:
@@ -134,7 +146,7 @@ def size(u8_bytes: int, dtype: int) -> int:
 
 
 def size_hw(u8_bytes: int, och: int, dtype: int) -> int:
-    """... under ``HW``: one element per pixel, u8_bytes / och of them."""
+    """... under ``HW`` and ``HW_ID24``: one element per pixel, u8_bytes / och of them."""
     return u8_bytes // och * elem(dtype)
 
 

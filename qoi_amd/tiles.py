@@ -52,6 +52,17 @@ tests/test_label_ingest_model.py: values in 0..255 come back from ``nearest`` of
 the byte tile over B; with f dividing w and h a ``MODE`` label tile is ``mode.mode`` of B at ``w/f x h/f``.  The work items of the kernel
 label_ingest, which a label call runs in the place of tile_gather: ``label_tiles`` - ``ingest_tiles`` at factor 1, ``select_tiles`` above.
 
+24-bit ids (``LABELS_ID24``, bit 15, only beside ``LABELS``; ``label_flags(dtype, ids=True)``).  The plane, its dtype, its alignment and its
+extent are a label tile's, but its elements are ids - an instance map, a panoptic map, superpixels - and ``label_ids_to_bytes`` states B:
+the id of an element v is 0 for v < 0, 2^24 - 1 for v > 2^24 - 1, else v (``ID_MAX`` is the bound) - of the whole 32- / 64-bit value (2^32 + 5 is
+2^24 - 1, not 5), silently - and pixel (Y, X) of B is ``(id & 255, (id >> 8) & 255, id >> 16, 255)``: the COCO panoptic convention
+``id = R + 256 * G + 256^2 * B``.  A uint8 plane gives ``(v, 0, 0, 255)``.  Everything behind B is a label tile's.  The pixels are no longer
+grey, so the vote is the whole-pixel vote as it stands: among winners without the centre pixel the lowest ``r << 24 | g << 16 | b << 8 | a``
+- the order of the id's bytes from the low byte up, not the lowest id (of 256 and 1 it is 256).  An image is bytes or ids (``plan``); images
+with and without the bit mix in one label call.  Three properties, asserted by tests/test_label_id_model.py: ids in 0..2^24 - 1 come back
+from ``tensors.convert`` with ``tensors.HW_ID24`` of the factor-1 tile; a call without the bit gives the bytes it gave; with f dividing w and
+h an ID24 ``MODE`` tile decodes to what ``mode.mode`` gives from the factor-1 tile at ``w/f x h/f``.
+
 The plan: tile j's slot is ``tw * th * och`` rounded up to 256 plus the encode bound of its descriptor rounded up to 256; sub-batches are cut
 by ``packplan.plan`` over those slots, in tile order.
 """
@@ -81,7 +92,9 @@ ELEM = {U8: 1, F16: 2, BF16: 2, F32: 4}
 SOURCE_ARRAYS = {U8: np.uint8, F16: np.float16, BF16: np.uint16, F32: np.float32}     # (NumPy has no bfloat16: its bits)
 LABELS = 2048                   # QOIMI_TILE_LABELS: the image is one plane of class indices of the dtype the bits below give (none: u8)
 LABELS_I32, LABELS_I64 = 4096, 8192             # QOIMI_TILE_LABELS_I32 / _I64: the dtype field, bits 12-13 (12288 is not a dtype)
-LABELS_MASK = LABELS | 12288                    # (bit 10 and bits 14 up stay unknown; SRC_MASK is what it was)
+LABELS_MASK = LABELS | 12288                    # (bit 10, bit 14 and bits 16 up stay unknown; SRC_MASK is what it was)
+LABELS_ID24 = 32768             # QOIMI_TILE_LABELS_ID24, bit 15: the elements are ids, spread over r, g and b (bit 14 stays unknown)
+ID_MAX = (1 << 24) - 1          # the largest id
 L_U8, L_I32, L_I64 = 0, 1, 2                    # the dtype field's values
 LABEL_ELEM = {L_U8: 1, L_I32: 4, L_I64: 8}
 LABEL_ARRAYS = {L_U8: np.uint8, L_I32: np.int32, L_I64: np.int64}
@@ -119,7 +132,7 @@ def size(w: int, h: int, sch: int, t, channels: int = 0) -> Tuple[int, int, int]
     _, x, y, cw, ch, f, flags, reserved = fields(t)
     if not _desc_ok(w, h, sch) or channels not in (0, 3, 4):
         return 0, 0, 0
-    if cw < 1 or ch < 1 or x < 0 or y < 0 or x + cw > w or y + ch > h or not 1 <= f <= MAX_FACTOR or (flags & ~(FLIP_X | FLIP_Y | SRC_MASK | LABELS_MASK)) or reserved:
+    if cw < 1 or ch < 1 or x < 0 or y < 0 or x + cw > w or y + ch > h or not 1 <= f <= MAX_FACTOR or (flags & ~(FLIP_X | FLIP_Y | SRC_MASK | LABELS_MASK | LABELS_ID24)) or reserved:
         return 0, 0, 0
     if source_wrong(flags, f) or label_wrong(flags, f):
         return 0, 0, 0
@@ -222,11 +235,12 @@ def ingest_tiles(cw: int, ch: int) -> int:
 
 
 # ---------------------------------------------------------------------------------- label tensors as the source (QOIMI_TILE_LABELS*)
-def label_flags(dtype: int = L_U8) -> int:
-    """The bits of ``qoimi_tile.flags`` for a label source of dtype ``L_U8`` / ``L_I32`` / ``L_I64``.  Or them to a tile's flips."""
+def label_flags(dtype: int = L_U8, ids: bool = False) -> int:
+    """The bits of ``qoimi_tile.flags`` for a label source of dtype ``L_U8`` / ``L_I32`` / ``L_I64``, with ids its elements are 24-bit ids
+    (``LABELS_ID24``).  Or them to a tile's flips."""
     if dtype not in (L_U8, L_I32, L_I64):
         raise ValueError("label_flags: no such dtype")
-    return LABELS | (dtype << 12)
+    return LABELS | (dtype << 12) | (LABELS_ID24 if ids else 0)
 
 
 def label_dtype(flags: int) -> int:
@@ -237,7 +251,7 @@ def label_dtype(flags: int) -> int:
 def label_wrong(flags: int, factor: int = 1, mode=None) -> str:
     """"" if the flags carry no label bit or are those of a label tile the calls accept, else what is wrong - in the order the calls look,
     behind ``source_wrong``.  mode None: ``qoimi_tile_size``, which has no mode and does not apply the averaging rule."""
-    lab = flags & LABELS_MASK
+    lab = flags & (LABELS_MASK | LABELS_ID24)
     if not lab:
         return ""
     if not lab & LABELS:
@@ -266,9 +280,30 @@ def labels_to_bytes(A: np.ndarray, flags: int) -> np.ndarray:
     want = LABEL_ARRAYS[label_dtype(flags)]
     if A.ndim != 2 or A.dtype != want:
         raise ValueError("labels_to_bytes: A is [h, w] of " + np.dtype(want).name)
+    if flags & LABELS_ID24:
+        return label_ids_to_bytes(A, flags)
     b = np.clip(A, 0, 255).astype(np.uint8)                            # (a clip in A's own dtype: no value is narrowed before it)
     B = np.full(A.shape + (4,), 255, dtype=np.uint8)
     B[:, :, :3] = b[:, :, None]
+    return B
+
+
+def label_ids_to_bytes(A: np.ndarray, flags: int) -> np.ndarray:
+    """The plane A ``[h, w]`` of uint8 / int32 / int64 in the dtype the label bits of `flags` give, which carry ``LABELS_ID24`` -> B
+    ``uint8[h, w, 4]``.  id = 0 for v < 0, 2^24 - 1 for v > 2^24 - 1, else v - exact for the whole int64 range -; the pixel is
+    (id & 255, (id >> 8) & 255, id >> 16, 255)."""
+    what = label_wrong(flags)
+    if what or not flags & LABELS or not flags & LABELS_ID24:
+        raise ValueError("label_ids_to_bytes: " + (what or "no LABELS or no LABELS_ID24 bit"))
+    A = np.asarray(A)
+    want = LABEL_ARRAYS[label_dtype(flags)]
+    if A.ndim != 2 or A.dtype != want:
+        raise ValueError("label_ids_to_bytes: A is [h, w] of " + np.dtype(want).name)
+    ids = (A if A.dtype == np.uint8 else np.clip(A, 0, ID_MAX)).astype(np.uint32)   # (a clip in A's own dtype: no value is narrowed before it)
+    B = np.full(A.shape + (4,), 255, dtype=np.uint8)
+    B[:, :, 0] = ids & 255
+    B[:, :, 1] = (ids >> 8) & 255
+    B[:, :, 2] = ids >> 16
     return B
 
 
@@ -307,12 +342,12 @@ def tile(S: np.ndarray, t, channels: int = 0, mode: int = PLAIN) -> np.ndarray:
     tensor its flags describe (``convert`` states the bytes B it stands for) and is the tile of B without the source bits.  A tile with
     ``LABELS`` takes S as the plane [h, w] its flags describe (``labels_to_bytes``) and is the tile of that B in `mode`; channels 0 is B's 4."""
     _, x, y, cw, ch, f, flags, reserved = fields(t)
-    if flags & LABELS_MASK and not source_wrong(flags, f):
+    if flags & (LABELS_MASK | LABELS_ID24) and not source_wrong(flags, f):
         what = label_wrong(flags, f, mode)
         if what:
             raise ValueError("tile: " + what)
         S = labels_to_bytes(S, flags)
-        flags &= ~LABELS_MASK
+        flags &= ~(LABELS_MASK | LABELS_ID24)
         t = (0, x, y, cw, ch, f, flags, reserved)
     if flags & SRC_MASK:
         S = convert(S, flags)                                          # (raises where the bits are no format)
@@ -378,7 +413,7 @@ def plan(descs: Sequence, tiles: Sequence, channels: int, staging_bytes: int):
         raise ValueError("plan: a call is a byte call or a tensor call")
     if len({(fields(t)[0], s) for t, s in zip(tiles, srcs)}) != len({fields(t)[0] for t in tiles}):
         raise ValueError("plan: an image is named with two source formats")
-    labs = [fields(t)[6] & LABELS_MASK for t in tiles]
+    labs = [fields(t)[6] & (LABELS_MASK | LABELS_ID24) for t in tiles]
     if any(labs) and not all(labs):
         raise ValueError("plan: a call is a byte call, a tensor call or a label call")
     if len({(fields(t)[0], s) for t, s in zip(tiles, labs)}) != len({fields(t)[0] for t in tiles}):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """qoifromlabels for the MI355X path: an .npy batch of label maps to .qoi files - the sibling of tools/qoifromtensor_mi355x.py.
 
-    python tools/qoifromlabels_mi355x.py FILE.npy -o DIR [--levels L --tile T --mode nearest|vote] [--channels 3|4] [--staging-mb M]
+    python tools/qoifromlabels_mi355x.py FILE.npy -o DIR [--levels L --tile T --mode nearest|vote] [--channels 3|4] [--staging-mb M] [--ids]
 
 FILE.npy holds H x W or N x H x W of uint8, int32 or int64 class indices.  Uploads the array as it is and makes ONE qoimi_encode_tiles call
 whose tiles carry QOIMI_TILE_LABELS and the dtype's bits: the saturation to bytes (qoi_amd/tiles.py: labels_to_bytes - below 0 gives 0, above
@@ -10,7 +10,9 @@ Without --levels it writes DIR/NNNN.qoi, one file a map; with --levels L (1..7) 
 of T x T pixels (default 256), reduced by --mode: nearest (the centre element of every block, any level) or vote (the majority of every
 block; levels up to 5, a block is at most 16 x 16).  A label map is never averaged.  The library saturates silently, so the tool counts the
 elements outside 0..255 with torch before the call and prints the count.  `plan_call` is a pure function.  Exit status 0, 1 if the array
-is none of those, 2 for a bad command line.  Needs torch for device memory, as tools/qoithumb_mi355x.py does.
+is none of those, 2 for a bad command line.  With --ids the elements are 24-bit ids - instance, panoptic or superpixel maps - and the tiles
+carry QOIMI_TILE_LABELS_ID24 too: an id is saturated to 0..2^24 - 1 (qoi_amd/tiles.py: label_ids_to_bytes) and spread over r, g and b, low
+byte first, as a COCO panoptic PNG holds it (id = R + 256 * G + 256^2 * B); the count of saturated elements is then taken at 2^24 - 1.  Needs torch for device memory, as tools/qoithumb_mi355x.py does.
 """
 from __future__ import annotations
 
@@ -30,7 +32,7 @@ MODES = {"nearest": tiles.NEAREST, "vote": tiles.MODE}
 DTYPES = {np.dtype(np.uint8): tiles.L_U8, np.dtype(np.int32): tiles.L_I32, np.dtype(np.int64): tiles.L_I64}
 
 
-def plan_call(shape: Tuple[int, ...], dtype, levels: int = 0, tile: int = 256, mode: str = "nearest"):
+def plan_call(shape: Tuple[int, ...], dtype, levels: int = 0, tile: int = 256, mode: str = "nearest", ids: bool = False):
     """(n, w, h, flags, plane_bytes, tiles of one map) of the call for an array of this shape and dtype - the tiles as (x, y, width, height,
     factor) with their (level, row, col) - or a string saying what is wrong with it."""
     dt = DTYPES.get(np.dtype(dtype))
@@ -48,7 +50,7 @@ def plan_call(shape: Tuple[int, ...], dtype, levels: int = 0, tile: int = 256, m
         return "levels must be 1..7, with --mode vote 1..5 (a block votes over at most 16 x 16 elements)"
     if not 1 <= tile <= tiles.MAX_TILE_SIDE:
         return "the tile side must be 1..2^24"
-    flags = tiles.label_flags(dt)
+    flags = tiles.label_flags(dt, ids)
     if not levels:
         grid = [((0, 0, 0), (0, 0, w, h, 1))]
     else:
@@ -65,6 +67,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("--mode", choices=sorted(MODES), default="nearest", help="how a pyramid's levels are reduced: the centre element or the majority vote")
     ap.add_argument("--channels", type=int, default=3, choices=[3, 4], help="channels of the files: grey, or grey with alpha 255")
     ap.add_argument("--staging-mb", type=int, default=0, metavar="M", help="device memory for converted pixels and streams (0: 1 GiB)")
+    ap.add_argument("--ids", action="store_true", help="the elements are 24-bit ids, spread over r, g and b (QOIMI_TILE_LABELS_ID24)")
     try:
         a = ap.parse_args(argv)
     except SystemExit:
@@ -74,7 +77,7 @@ def main(argv, out=print) -> int:
     except (OSError, ValueError) as e:
         out(f"{os.path.basename(a.path)}: {e}")
         return 1
-    call = plan_call(arr.shape, arr.dtype, a.levels, a.tile, a.mode)
+    call = plan_call(arr.shape, arr.dtype, a.levels, a.tile, a.mode, a.ids)
     if isinstance(call, str):
         out(f"{os.path.basename(a.path)}: {call}")
         return 1
@@ -83,7 +86,8 @@ def main(argv, out=print) -> int:
     from qoi_amd import api
 
     src = torch.from_numpy(np.ascontiguousarray(arr).reshape(n, h, w)).cuda()
-    outside = int(((src < 0) | (src > 255)).sum().item()) if arr.dtype != np.uint8 else 0      # the library does not count them
+    top = tiles.ID_MAX if a.ids else 255
+    outside = int(((src < 0) | (src > top)).sum().item()) if arr.dtype != np.uint8 else 0      # the library does not count them
     descs = [api.QoiDesc(w, h, a.channels, 0)] * n
     ts: List[tuple] = [(i,) + t + (flags,) for i in range(n) for _, t in grid]
     cap = sum(tiles.encode_bound(-(-t[2] // t[4]), -(-t[3] // t[4]), a.channels) for _, t in grid) * n
@@ -107,7 +111,7 @@ def main(argv, out=print) -> int:
             k += 1
     what = f"{a.levels} levels by {a.mode}, " if a.levels else ""
     out(f"{os.path.basename(a.path)}: {n} x {w}x{h} {arr.dtype.name} -> {what}{len(ts)} files of {a.channels} channels, {int(off[-1])} bytes, "
-        f"{subs} sub-batch{'es' if subs != 1 else ''}; {outside} elements outside 0..255 saturated")
+        f"{subs} sub-batch{'es' if subs != 1 else ''}; {outside} elements outside 0..{top} saturated")
     return 0
 
 

@@ -2,7 +2,7 @@
 """qoitensor for the MI355X path: a set of .qoi files as ONE .npy tensor, N x C x H x W or N x H x W x C, normalised.
 
     python tools/qoitensor_mi355x.py FILE_OR_DIR... --size WxH -o OUT.npy [--filter area|bilinear|bicubic|lanczos|nearest|mode] [--dtype u8|f16|bf16|f32|i32|i64]
-                                     [--layout chw|hwc|hw]
+                                     [--layout chw|hwc|hw|id24]
                                      [--mean M[,M,M[,M]]] [--std S[,S,S[,S]]] [--fit whole|crop] [--channels 3|4] [--staging-mb M]
 
 Loads the .qoi files (directories are walked), uploads them as ONE pack and makes ONE qoimi_decode_tensors call: every stream is decoded on the
@@ -12,7 +12,8 @@ scale = 1 / (255 * std) and bias = -mean / std are computed in float64 and round
 float32(p) * scale + bias with two roundings and narrows once (qoi_amd/tensors.py states it).  Without --mean / --std the elements are
 p / 255; --dtype u8, i32 and i64 take neither and store p.  --filter nearest --dtype i64 --layout hw makes N x H x W class indices of label maps:
 one pixel of the source per element, nothing averaged, the first channel alone; --filter mode instead takes the most frequent pixel of each
-element's cell (qoi_amd/mode.py: a majority vote, for REDUCING label maps).  One value of --mean / --std serves every channel; a fourth (alpha) defaults to mean 0, std 1.
+element's cell (qoi_amd/mode.py: a majority vote, for REDUCING label maps).  --layout id24 (with --dtype i32 or i64 only) makes N x H x W of
+24-bit ids, r | g << 8 | b << 16 of each pixel - instance and panoptic maps, what tools/qoifromlabels_mi355x.py --ids writes; it means something only with --filter nearest or mode.  One value of --mean / --std serves every channel; a fourth (alpha) defaults to mean 0, std 1.
 --channels defaults to 3.  bf16 is stored as the uint16 of its bits (NumPy has no bfloat16).  A file that is no QOI stream or whose
 rectangle the filter cannot reduce to the target (64 times in an axis, 32 for bilinear, 16 for bicubic and lanczos, no limit but a side of 16384 for nearest, 16 and a side of 16384 for mode) is reported and left out; exit status 1 if there was
 one, else 0.  Needs torch for device memory, as tools/qoicheck_mi355x.py does.
@@ -67,7 +68,7 @@ def main(argv, out=print) -> int:
     ap.add_argument("-o", "--out", required=True, metavar="OUT.npy")
     ap.add_argument("--filter", choices=("area", "bilinear", "bicubic", "lanczos", "nearest", "mode"), default="bilinear")
     ap.add_argument("--dtype", choices=("u8", "f16", "bf16", "f32", "i32", "i64"), default="f32")
-    ap.add_argument("--layout", choices=("chw", "hwc", "hw"), default="chw")
+    ap.add_argument("--layout", choices=("chw", "hwc", "hw", "id24"), default="chw")
     ap.add_argument("--mean", default=None, metavar="M[,M,M[,M]]")
     ap.add_argument("--std", default=None, metavar="S[,S,S[,S]]")
     ap.add_argument("--fit", choices=("whole", "crop"), default="whole")
@@ -85,6 +86,9 @@ def main(argv, out=print) -> int:
         out("--staging-mb must not be negative")
         return 2
     och = a.channels
+    if a.layout == "id24" and a.dtype not in ("i32", "i64"):
+        out("--layout id24 goes with --dtype i32 or i64 only")
+        return 2
     if a.dtype in ("u8", "i32", "i64"):
         if a.mean is not None or a.std is not None:
             out(f"--dtype {a.dtype} stores the pixel values: it takes no --mean / --std")
@@ -122,8 +126,8 @@ def main(argv, out=print) -> int:
         good.append(i)
     if not good:
         return 1
-    f = (tensors.DTYPE_NAMES[a.dtype], tensors.LAYOUT_NAMES[a.layout], sb[0], sb[1])
-    one = ow * oh * (1 if a.layout == "hw" else och) * tensors.elem(f[0])
+    f = (tensors.DTYPE_NAMES[a.dtype], {**tensors.LAYOUT_NAMES, **tensors.ID_LAYOUT_NAMES}[a.layout], sb[0], sb[1])
+    one = ow * oh * (1 if a.layout in ("hw", "id24") else och) * tensors.elem(f[0])
     offsets, sizes, descs, items = [], [], [], []
     pos = 0
     for k, i in enumerate(good):
@@ -140,7 +144,7 @@ def main(argv, out=print) -> int:
         subs = ctx.tensor_stats()[0]
     finally:
         ctx.close()
-    shape = {"chw": (len(good), och, oh, ow), "hwc": (len(good), oh, ow, och), "hw": (len(good), oh, ow)}[a.layout]
+    shape = {"chw": (len(good), och, oh, ow), "hwc": (len(good), oh, ow, och), "hw": (len(good), oh, ow), "id24": (len(good), oh, ow)}[a.layout]
     res = d_out.cpu().numpy().view(tensors.numpy_dtype(f[0])).reshape(shape)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     np.save(a.out, res)
